@@ -23,6 +23,12 @@ weak scaling); value = frames solved by all ranks / max-over-ranks wall time.
   for N = 1 "train_step" is the same step without the process group.
   --dtype    MFMA operand type of the headline line (f16 = the shipping default, parity-gated at 1e-3; bf16 = BASELINE's
              word for "16-bit operands", ~4e-3).  The other type is timed after the headline region ("other_dtype").
+  --dump-outputs DIR
+             after the timed steps, write the mel spectrograms the LAST timed step returned as float32 DIR/<name>.npy:
+             "mel" (config 2) or "mel_bucket<i>" (--ragged, longest bucket first), prefixed "rank<r>_" when N > 1.
+             Inputs and weights are seeded, so the same arguments give the same inputs on every run and two builds can
+             be compared file for file.  At most 64 MB in all: when the outputs are larger, every array is replaced by
+             the same fraction of its elements, at seeded flat positions (ascending), 1-D.
 
 Extra objects on the JSON line:
   roofline     -- the dominant kernel class (largest total time, measured live with HIP events on the
@@ -183,6 +189,25 @@ ENGINE_ENV = ("STABLETTS_HIP_LIB", "ST_BIG_MIN_BLOCKS", "ST_PHASED", "ST_FUSED_F
 ENGINE_NEUTRAL_ENV = ("ST_SPLIT", "ST_HIP_GRAPH", "ST_BUILD_OUT", "ST_BUILD_DEFS")
 DDP_WATCHDOG_S = 240           # bench.py --gpus N: seconds the config-5 DDP-over-RCCL leg may take before the line is printed without it
 RAGGED_UTTERANCES = 256        # BASELINE config 4: "batch=256 utterances sharded"; the same set at every N (strong scaling)
+DUMP_MAX_BYTES = 64 * 10**6    # --dump-outputs: all ranks' .npy files together, headers included
+
+
+def dump_outputs(outdir, named, world):
+    """--dump-outputs: writes each (name, tensor) as float32 outdir/<name>.npy.  If this rank's share of DUMP_MAX_BYTES is
+    exceeded, each array keeps the same fraction of its elements at seeded flat positions (ascending, 1-D)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    arrays = [(name, t.detach().float().cpu().numpy()) for name, t in named]
+    budget = DUMP_MAX_BYTES // world - 128 * len(arrays)        # 128 = a .npy file's header
+    total = sum(a.nbytes for _, a in arrays)
+    keep = min(1.0, budget / total)
+    for i, (name, a) in enumerate(arrays):
+        if keep < 1.0:
+            flat = a.reshape(-1)
+            pos = np.random.default_rng(i).choice(flat.size, int(flat.size * keep), replace=False)
+            a = flat[np.sort(pos)]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return {"dir": outdir, "arrays": [n for n, _ in arrays], "fraction_of_elements": keep}
 
 
 def ragged_batches(world, rank, dev, n_utt=RAGGED_UTTERANCES):
@@ -390,7 +415,11 @@ def main():
     ap.add_argument("--dev-env", action="store_true",
                     help="developer runs only: accept engine-changing ST_* / STABLETTS_HIP_LIB variables (the line is then marked "
                          "'dev_env' and is NOT a headline measurement)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the mel spectrograms of the last timed step to DIR/<name>.npy (float32, <= 64 MB in all; see above)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     N_STEPS = args.n_timesteps
     # The headline line describes the library AS SHIPPED: refuse to run with any variable that changes which kernels run or what
     # they return.  (ST_SPLIT / ST_HIP_GRAPH only change how the same kernels are enqueued -- results are bitwise identical,
@@ -473,9 +502,7 @@ def main():
         return dec(gg["mu"], gg["mask"], N_STEPS, 1.0, gg["c"], "euler", kw, z=gg["z"])
 
     def step_all():
-        for b in batches:
-            out = solve(b["g"])
-        return out
+        return [solve(b["g"]) for b in batches]
 
     def step():
         return solve(g)
@@ -532,10 +559,17 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        out = step_all()
+        outs = step_all()
     sync()
     elapsed = allreduce_max(time.perf_counter() - t0)
+    out = outs[-1]
     assert torch.isfinite(out).all()
+    if args.dump_outputs:
+        names = [f"mel_bucket{i}" for i in range(len(outs))] if args.ragged else ["mel"]
+        prefix = f"rank{rank}_" if world > 1 else ""
+        dumped = dump_outputs(args.dump_outputs, [(prefix + n, o) for n, o in zip(names, outs)], world)
+        print(f"[bench] rank {rank}: wrote {dumped}", file=sys.stderr, flush=True)
+    del outs
     os.environ["ST_SPLIT"] = "1"
     step()
     eng.profile_enable(True, [dom], stride=PROFILE_STRIDE)

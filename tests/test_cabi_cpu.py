@@ -227,6 +227,39 @@ def test_bench_refuses_engine_changing_environment():
         assert r.returncode != 0 and "needs a HIP device" in (r.stderr + r.stdout)
 
 
+def test_bench_dump_outputs_bounds_and_seeded_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: arrays within the byte bound are written whole as float32; beyond it every array keeps the same
+    fraction of its elements at seeded ascending flat positions, identical from run to run, and the files stay within the bound.
+    A CLI value of --steps below 1 is refused before any work."""
+    import importlib.util
+    import subprocess
+    import sys
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = torch.arange(2 * 3 * 50, dtype=torch.float32).reshape(2, 3, 50)
+    b = torch.arange(4 * 3 * 70, dtype=torch.float64).reshape(4, 3, 70)
+    info = bench.dump_outputs(str(tmp_path / "whole"), [("a", a), ("b", b)], 1)
+    assert info["fraction_of_elements"] == 1.0
+    for name, t in (("a", a), ("b", b)):
+        got = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, t.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2 * (128 + 2000))
+    runs = []
+    for d in ("s1", "s2"):
+        info = bench.dump_outputs(str(tmp_path / d), [("a", a), ("b", b)], 2)      # two ranks: half the bound each
+        assert 0 < info["fraction_of_elements"] < 1
+        assert sum(os.path.getsize(tmp_path / d / f"{n}.npy") for n in ("a", "b")) <= bench.DUMP_MAX_BYTES // 2
+        runs.append([np.load(tmp_path / d / f"{n}.npy") for n in ("a", "b")])
+    for (sa, sb), (ra, rb) in zip(runs, runs[1:]):
+        assert np.array_equal(sa, ra) and np.array_equal(sb, rb)
+    for s, t in zip(runs[0], (a, b)):
+        assert s.ndim == 1 and s.dtype == np.float32 and np.all(np.diff(s) > 0) and s.max() < t.numel()       # arange: values = positions
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr
+
+
 def test_micro_benchmarks_still_compile_against_the_kernel_headers():
     """pruning a kernel header silently broke tools/micro/ffn_bench.hip (it included the deleted ffn_fused16.h), i.e. the
     evidence tools DESIGN.md cites.  A front-end-only pass (hipcc -fsyntax-only, host + gfx950 device, ~8 s) over the micro-benchmarks

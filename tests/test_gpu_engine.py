@@ -426,6 +426,25 @@ def test_bench_ragged_headline_is_one_workload_in_equal_cost_buckets():
     assert j["value"] > 0 and j["sharding"]["valid_frames"] < 96 * 1000
 
 
+def test_bench_dump_outputs_is_what_the_timed_path_returns(sd, cfg_params, tmp_path):
+    """`bench.py --dump-outputs DIR` writes the mel the last timed step returned (config 2: 32 x 128 x 1000 float32, under the
+    64 MB bound, so not sampled); the same seeded inputs solved here by the library give the same array bit for bit."""
+    import numpy as np
+    from stabletts_amd.flow_matching import CFMDecoder
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-extras",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert sorted(os.listdir(tmp_path)) == ["mel.npy"]
+    mel = np.load(tmp_path / "mel.npy")
+    assert mel.dtype == np.float32 and mel.shape == (32, 128, 1000)
+    d = CFMDecoder(128, 128, 256, 128, 1024, 4, 6, 3, 0.1, 256)
+    d.estimator.load_state_dict(sd)
+    d = d.to("cuda:0")
+    out = _solve(d, make_inputs(32, 1000, seed=0), 10, "euler", _kw(cfg_params, 3.0))
+    assert np.array_equal(mel, out.numpy())
+
+
 @pytest.mark.parametrize("dtype", ["f16", "bf16"])
 def test_ragged_tile_skipping_and_qkv_two_block_tiles_are_bitwise_neutral(sd, cfg_params, monkeypatch, dtype):
     """Round-3 launch-level changes must not change a single bit of the result:
