@@ -590,6 +590,25 @@ __global__ __launch_bounds__(512, 1) void attention_small_kernel(const AttnArgs 
     if (qt * 32 + q < T)
         *(uint2*)((unsigned char*)a.out + (((size_t)n * T + qt * 32 + q) * (H * 64) + h * 64 + d0) * 2) =
             pack4<P>(acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv);
+    // run-time statistic (st_attention_stats), as in attention_kernel: the largest merged log2-sum-exp of any VALID query row
+    // of this block (16 threads hold each row's M and L), one atomic per block
+    if (a.lse_max) {
+        __shared__ float wave_lse[NW];
+        float v = -3.0e38f;
+        if (qt * 32 + q < T && qt * 32 + q < kvend && L > 0.f) v = M + log2f(L);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+        if (lane == 0) wave_lse[wave] = v;
+        __syncthreads();
+        if (tid == 0) {
+            float b = wave_lse[0];
+#pragma unroll
+            for (int w = 1; w < NW; ++w) b = fmaxf(b, wave_lse[w]);
+            int bits = __float_as_int(b);
+            bits = bits >= 0 ? bits : bits ^ 0x7fffffff;      // order-preserving map of floats onto signed ints
+            atomicMax((int*)a.lse_max + ((blockIdx.x % kLseCells) << 4), bits);
+        }
+    }
 }
 
 template <class P>

@@ -768,7 +768,8 @@ __global__ __launch_bounds__(256) void wgrad_reduce_multi_kernel(const float* pa
     const float us = o.unscale ? o.unscale[1] : 1.0f;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nci = min(64, o.ci_cnt - ci0);           // valid input channels of this tile
-    for (int col = wave; col < 64; col += 4) {
+    const int nco = min(64, o.co_start + o.co_cnt - co0);    // valid output channels (final_proj: co_cnt = M, not a multiple of 64)
+    for (int col = wave; col < nco; col += 4) {
         float* dst = o.dW + ((size_t)(co0 + col - o.co_start) * o.cin_total + o.ci_off + ci0) * TAPS;
         for (int e = lane; e < nci * TAPS; e += 64) dst[e] = tile[col * ROW + e] * us;
     }

@@ -51,6 +51,12 @@ def test_reference_assertions_are_mirrored(lib):
     assert rc == -4
 
 
+def test_noise_channels_outside_1_to_1024_are_rejected(lib):
+    for m in (0, -1, 1025):
+        rc, _, msg = _create(lib, noise_channels=m)
+        assert rc == -1 and "noise_channels" in msg, (m, rc, msg)
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="CPU-box behaviour")
 def test_no_gpu_fails_loudly(lib):
     rc, _, msg = _create(lib)

@@ -613,6 +613,49 @@ def test_attention_statistic_matches_the_oracle(ada, qk):
     assert eng.attention_stats(stream) == float("-inf")                 # the query resets the statistic
 
 
+def _statistic_engine(sd2, monkeypatch, small_grid):
+    from stabletts_amd.flow_matching import CFMDecoder
+    if small_grid:
+        monkeypatch.delenv("ST_SMALL_GRID", raising=False)
+    else:
+        monkeypatch.setenv("ST_SMALL_GRID", "0")          # read at st_create: this engine never takes the key-split kernel
+    dec = CFMDecoder(128, 128, 256, 128, 1024, 4, 6, 3, 0.1, 256)
+    dec.estimator.load_state_dict(sd2)
+    dec = dec.cuda()
+    dec.estimator.engine()                                # (created on first use: here, while the variable is set)
+    monkeypatch.delenv("ST_SMALL_GRID", raising=False)
+    return dec
+
+
+@pytest.mark.parametrize("B,T,lengths,seed", [(1, 520, [520], 18), (2, 300, [300, 211], 19)])
+@pytest.mark.parametrize("ada,qk", [(0.02, 1.0), (0.15, 1.0), (0.15, 3.0)])
+def test_attention_statistic_on_the_small_grid_kernel(monkeypatch, ada, qk, B, T, lengths, seed):
+    """The statistic of test_attention_statistic_matches_the_oracle where the estimator's attention takes the key-split kernel
+    (attention_small_kernel: one launch of n_items * H * ceil(T / 256) <= attn_small_blocks = 32 blocks on a single-part engine):
+    B = 1 x T = 520 is 1 * 4 * 3 = 12 blocks, B = 2 x T = 300 ragged 2 * 4 * 2 = 16 -- single-utterance serving, where an engine
+    that never published it kept attention_precision='auto' pending forever.  Against the fp32 oracle, and against the big kernel
+    at the same shape (an engine created with ST_SMALL_GRID=0) with the same tolerance."""
+    sd2 = _trained_like(ada, qk) if (ada, qk) != (0.02, 1.0) else oracle.make_state_dict(1234)
+    inp = make_inputs(B, T, seed=seed, lengths=lengths)
+    t = torch.tensor(0.5)
+    stream = torch.cuda.current_stream().cuda_stream
+    got = {}
+    for small in (True, False):
+        dec = _statistic_engine(sd2, monkeypatch, small)
+        eng = dec.estimator.engine()
+        assert eng.attention_stats(stream) == float("-inf")
+        dec.estimator(t.cuda(), inp["z"].cuda(), inp["mask"].cuda(), inp["mu"].cuda(), inp["c"].cuda())
+        got[small] = eng.attention_stats(stream)
+        assert eng.attention_stats(stream) == float("-inf")
+        del dec
+    want = _oracle_max_lse(sd2, t, inp)
+    print(f"ada_std {ada}, q/k x{qk}, B={B} x T={T}: max log-sum-exp small-grid kernel {got[True]:.3f}, big kernel {got[False]:.3f}, "
+          f"oracle {want:.3f}")
+    assert abs(got[True] - want) <= 0.02 * abs(want) + 0.05
+    assert abs(got[False] - want) <= 0.02 * abs(want) + 0.05
+    assert abs(got[True] - got[False]) <= 0.02 * abs(got[False]) + 0.05
+
+
 @pytest.mark.parametrize("ada,qk", [(0.15, 1.0), (0.15, 3.0)])
 def test_split_precision_attention_operands_at_benchmark_size(cfg_params, ada, qk):
     """attention_precision='split' (q and k as hi + lo operand pairs, scores from three products; st_set_option) measured where 16-bit
@@ -676,6 +719,46 @@ def test_attention_precision_auto_switches_in_the_arg_max_regime(cfg_params):
         assert torch.equal(outs["auto"], outs["split" if expect_split else "16bit"])
         assert torch.equal(outs["auto2"], outs["auto"])
         assert not torch.equal(outs["split"], outs["16bit"])
+
+
+def test_attention_precision_auto_resolves_on_the_small_grid_kernel(cfg_params, monkeypatch):
+    """attention_precision='auto' at single-utterance serving size: B = 1 x T = 600 with CFG (both branches: 2 * 4 * ceil(600 / 256) = 24
+    blocks <= 32, the key-split attention kernel).  The same contract as the B = 4 test above -- warn once and switch in the arg-max
+    regime, bit-identical to 'split'; stay on and equal '16bit' with the seeded weights -- and the decision is taken after the first
+    solve in both cases (no statistic: it stayed pending, one sync + copy + reset per solve).  Control: the statistic of a 16-bit solve
+    on this kernel against the same solve on an engine that never takes it (ST_SMALL_GRID=0)."""
+    import warnings
+    from stabletts_amd.flow_matching import CFMDecoder
+    inp = make_inputs(1, 600, seed=29)
+    kw = _cfg(cfg_params, 3.0, True)
+    stream = torch.cuda.current_stream().cuda_stream
+    for sd2, expect_split in ((_trained_like(0.15, 3.0), True), (oracle.make_state_dict(1234), False)):
+        outs = {}
+        for mode in ("auto", "split", "16bit"):
+            dec = CFMDecoder(128, 128, 256, 128, 1024, 4, 6, 3, 0.1, 256, attention_precision=mode)
+            dec.estimator.load_state_dict(sd2)
+            dec = dec.cuda()
+            with warnings.catch_warnings(record=True) as w:
+                warnings.simplefilter("always")
+                outs[mode] = _solve(dec, inp, 3, "euler", kw, inp["z"])
+                if mode == "auto":
+                    assert dec._auto_pending is False
+                outs[mode + "2"] = _solve(dec, inp, 3, "euler", kw, inp["z"])
+            if mode == "auto":
+                assert (len([x for x in w if "arg-max" in str(x.message)]) == 1) == expect_split
+                assert dec.estimator.engine().get_option("attention_precision") == int(expect_split)
+            del dec
+        assert torch.equal(outs["auto"], outs["split" if expect_split else "16bit"])
+        assert torch.equal(outs["auto2"], outs["auto"])
+        assert not torch.equal(outs["split"], outs["16bit"])
+        lse = {}
+        for small in (True, False):
+            dec = _statistic_engine(sd2, monkeypatch, small)
+            _solve(dec, inp, 3, "euler", kw, inp["z"])
+            lse[small] = dec.estimator.engine().attention_stats(stream)
+            del dec
+        print(f"B=1 x T=600, CFG, expect split {expect_split}: max log-sum-exp of the solve, small-grid kernel {lse[True]:.3f}, big kernel {lse[False]:.3f}")
+        assert lse[True] > float("-inf") and abs(lse[True] - lse[False]) <= 0.02 * abs(lse[False]) + 0.05
 
 
 def test_ffn_intermediate_in_the_upper_half_of_f16_range(sd, monkeypatch):
