@@ -1,7 +1,5 @@
-// Host side of libstabletts_hip.so: parameter store, weight packing, workspace arena, the
-// estimator launch sequence and the fixed-grid ODE loop behind the C ABI of
-// include/stabletts_hip.h.  Reference path: models/flow_matching.py:25-67 (CFMDecoder.forward,
-// cfg_wrapper), models/estimator.py:103-138 (Decoder.forward), torchdiffeq fixed-grid solvers.
+// Host side of libstabletts_hip.so: parameter store, weight packing, workspace arena and the estimator launch sequence behind
+// the C ABI of include/stabletts_hip.h (the ODE solve around it: engine_solve.cpp).  Reference path: models/estimator.py:103-138.
 #include "engine_internal.h"
 #include "train_launch.h"
 
@@ -9,22 +7,15 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <iterator>
 #include <map>
 #include <string>
-#include <deque>
 #include <vector>
 
 using namespace st;
 using namespace sthost;
 
 namespace sthost {
-constexpr int kPartPhaseUs = 100;      // start offset between the launch sequences of a multi-part solve (engine.cpp: body)
-
 std::string g_create_error;
-
-// Default of the two-part solve (see st_cfm_solve): -1 = automatic (large fixed-grid batches), 1 = never.
-constexpr int kDefaultSplit = -1;
 
 const char* kProfNames[PC_COUNT] = {
     "prep", "prenet_conv", "in_proj", "film_ln1", "qkv_rope", "attention", "out_proj", "ln2",
@@ -195,26 +186,7 @@ void capture(st_engine* e, const std::string& name, const void* dev, int64_t n, 
     hipMemcpyAsync(c.dev, dev, bytes, hipMemcpyDeviceToDevice, s);
 }
 
-// ---- workspace plan --------------------------------------------------------------------------
-struct Plan {
-    int B, T, Tp, N, Pn, n_t;
-    bool cfg;
-    // 16-bit MFMA operands.  *lo tensors hold x - float(hi): the split-precision operand pairs of the three GEMMs
-    // whose rounding error reaches the output un-gated (in_proj x-part and cond-part, final_proj)
-    void *mu16, *pre1, *pre2, *cond16, *cond16lo, *x16, *x16lo, *h16, *h2_16, *q16, *k16, *q16lo, *k16lo, *vt16, *ao16, *u16, *cur16, *cur16lo;
-    void* skip16[8];
-    // fp32
-    float *cpart, *X, *v32, *xstate, *kbuf[7], *ynew, *ode_partial, *ode_out, *tvals, *emb, *th, *tau, *film, *cvec, *ada, *ada_tmp;
-    int *n_full, *kv_end;
-    int* t_lim;         // [B + 1] frames of every utterance that are computed (mask_prep: last valid + 1 + halo), [B] = the longest
-    float* kbias;
-    float* maskbuf;     // engine-owned copy of the caller's (B,1,T) mask: the solve body touches arena memory only
-    struct Slot { void** dst; size_t off; };
-    std::vector<Slot> slots;
-};
-
-// Lays the tensors of one solve (or solve part) out in the arena starting at byte `off`; returns the end offset.
-// Pointers become valid after ensure_ws() + bind_plan().
+// ---- workspace plan (engine_internal.h: Plan) ------------------------------------------------
 size_t layout_plan(st_engine* e, int B, int T, bool cfg, int n_t, size_t off, Plan* p) {
     const int C = e->C, F = e->F, Mp = e->Mp, L = e->L;
     p->B = B; p->T = T; p->cfg = cfg; p->n_t = n_t;
@@ -288,7 +260,7 @@ int arena_fresh(st_engine* e, uint64_t sig, size_t used_bytes, hipStream_t s) {
     return ST_OK;
 }
 
-static uint64_t layout_sig(int entry, int B, int T, int cfg, int n_t, int parts) {
+uint64_t layout_sig(int entry, int B, int T, int cfg, int n_t, int parts) {
     uint64_t h = 1469598103934665603ull;
     for (uint64_t v : {(uint64_t)entry, (uint64_t)B, (uint64_t)T, (uint64_t)cfg, (uint64_t)n_t, (uint64_t)parts}) { h ^= v + 0x9E3779B97F4A7C15ull; h *= 1099511628211ull; }
     return h | 1ull;
@@ -622,307 +594,12 @@ int run_text_blocks(st_engine* e, const Plan& p, const float* mask, hipStream_t 
     return ST_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// torchdiffeq's explicit ADAPTIVE Runge-Kutta solvers: `dopri5` -- the reference's default
-// (models/flow_matching.py:54 with solver=None; rtol = atol = 1e-5 hard-coded there) -- and the other embedded
-// pairs the reference's web UI offers (webui.py:110: bosh3, fehlberg2, adaptive_heun).  Restated from the
-// published algorithm (rk_common.py / dopri5.py / bosh3.py / fehlberg2.py / adaptive_heun.py / misc.py of
-// torchdiffeq 0.2.x): RMS error norm over the whole state tensor, controller safety 0.9 / ifactor 10 / dfactor
-// 0.2 with exponent 1/order, initial step from _select_initial_step(order - 1), steps NOT clipped to t = 1 and the
-// result taken from the 4th-order dense output (_interp_fit with f0 = k[0], f1 = k[-1]); like torchdiffeq the
-// derivative carried into the next step is k[-1] whether or not the tableau is FSAL.
-// The state, stage derivatives and norms live on the device; time and the controller run on the host
-// (float64), with one 8-byte read-back per step (torchdiffeq synchronises the same way).
-struct RkTableau {
-    const char* name; int n; int order;       // n stages after k0 (k has n + 1 entries)
-    double alpha[6]; double beta[6][6]; double csol[7]; double cerr[7]; double cmid[7];
-};
-static const RkTableau kDopri5 = {
-    "dopri5", 6, 5,
-    {1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0, 1.0},
-    {{1.0 / 5},
-     {3.0 / 40, 9.0 / 40},
-     {44.0 / 45, -56.0 / 15, 32.0 / 9},
-     {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729},
-     {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656},
-     {35.0 / 384, 0.0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84}},
-    {35.0 / 384, 0.0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84, 0.0},
-    {35.0 / 384 - 1951.0 / 21600, 0.0, 500.0 / 1113 - 22642.0 / 50085, 125.0 / 192 - 451.0 / 720,
-     -2187.0 / 6784 + 12231.0 / 42400, 11.0 / 84 - 649.0 / 6300, -1.0 / 60},
-    {6025192743.0 / 30085553152.0 / 2, 0.0, 51252292925.0 / 65400821598.0 / 2, -2691868925.0 / 45128329728.0 / 2,
-     187940372067.0 / 1594534317056.0 / 2, -1776094331.0 / 19743644256.0 / 2, 11237099.0 / 235043384.0 / 2}};
-static const RkTableau kBosh3 = {
-    "bosh3", 3, 3,
-    {1.0 / 2, 3.0 / 4, 1.0},
-    {{1.0 / 2}, {0.0, 3.0 / 4}, {2.0 / 9, 1.0 / 3, 4.0 / 9}},
-    {2.0 / 9, 1.0 / 3, 4.0 / 9, 0.0},
-    {2.0 / 9 - 7.0 / 24, 1.0 / 3 - 1.0 / 4, 4.0 / 9 - 1.0 / 3, -1.0 / 8},
-    {0.0, 0.5, 0.0, 0.0}};
-static const RkTableau kFehlberg2 = {
-    "fehlberg2", 2, 2,
-    {1.0 / 2, 1.0},
-    {{1.0 / 2}, {1.0 / 256, 255.0 / 256}},
-    {1.0 / 512, 255.0 / 256, 1.0 / 512},
-    {-1.0 / 512, 0.0, 1.0 / 512},
-    {0.0, 0.5, 0.0}};
-static const RkTableau kAdaptiveHeun = {
-    "adaptive_heun", 1, 2,
-    {1.0}, {{1.0}}, {0.5, 0.5}, {0.5, -0.5}, {0.5, 0.0}};
-
-int solve_adaptive(st_engine* e, const Plan& p, const float* mask, int use_cfg, float cfg_strength,
-                   const RkTableau& tb, hipStream_t s) {
-    const int S = tb.n;
-    bool fsal = tb.csol[S] == 0.0;
-    for (int j = 0; j < S; ++j) fsal = fsal && tb.csol[j] == tb.beta[S - 1][j];
-    const double rtol = 1e-5, atol = 1e-5, t_end = 1.0;
-    const int B = p.B;
-    const int64_t per_item = (int64_t)p.T * e->Mp;
-    const int64_t nstate = (int64_t)B * per_item;
-    const double count = (double)B * e->M * p.T;            // padded channels carry zeros and do not count
-    int rc;
-    // f(t, state in x16) -> kout
-    auto eval = [&](double t, float* kout) -> int {
-        HIPCHK(e, launch_set_scalar(p.tvals, (float)t, s));
-        int r = run_time_tables(e, p, s); if (r) return r;
-        r = run_estimator(e, p, mask, 0, s); if (r) return r;
-        ProfScope ps(e, s, PC_ODE, 0);
-        HIPCHK(e, launch_cfg_combine(e->dt, p.v32, B, per_item, use_cfg, cfg_strength, kout, nullptr, nullptr, nullptr, 0.f, s));
-        e->last_nfe += 1;
-        return ST_OK;
-    };
-    float host2[2];
-    auto norms = [&](OdeNormArgs a) -> int {
-        a.rtol = (float)rtol; a.atol = (float)atol; a.n = nstate; a.partial = p.ode_partial; a.out = p.ode_out;
-        HIPCHK(e, launch_ode_norm(a, s));
-        HIPCHK(e, hipMemcpyAsync(host2, p.ode_out, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(e, hipStreamSynchronize(s));
-        return ST_OK;
-    };
-    float* y = p.xstate; float* y1 = p.ynew;
-    float* k[7];
-    for (int j = 0; j < 7; ++j) k[j] = p.kbuf[j];
-    // f0 = f(0, y0)   (x16 already holds y0)
-    if ((rc = eval(0.0, k[0]))) return rc;
-    // _select_initial_step(order - 1)
-    OdeNormArgs na; memset(&na, 0, sizeof(na));
-    na.mode = 0; na.y = y; na.b = k[0];
-    if ((rc = norms(na))) return rc;
-    const double d0 = sqrt(host2[0] / count), d1 = sqrt(host2[1] / count);
-    const double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-    {
-        const float* ks[1] = {k[0]}; const float cf[1] = {(float)h0};
-        HIPCHK(e, launch_lincomb(e->dt, y, ks, cf, 1, nstate, nullptr, p.x16, p.x16lo, s));
-    }
-    if ((rc = eval(0.0 + h0, k[1]))) return rc;
-    memset(&na, 0, sizeof(na));
-    na.mode = 1; na.y = y; na.a = k[0]; na.b = k[1];
-    if ((rc = norms(na))) return rc;
-    const double d2 = sqrt(host2[0] / count) / h0;
-    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? std::max(1e-6, h0 * 1e-3)
-                                                   : pow(0.01 / std::max(d1, d2), 1.0 / (double)tb.order);
-    double dt = std::min(100.0 * h0, h1), t = 0.0;
-    for (int64_t step = 0; step < 1000000; ++step) {
-        const double t1 = t + dt;
-        for (int i = 0; i < S; ++i) {       // stage i+1: y_i = y + dt * sum_j beta[i][j] k_j ; k_{i+1} = f(t_i, y_i)
-            const float* ks[7]; float cf[7]; int nk = 0;
-            for (int j = 0; j <= i; ++j) if (tb.beta[i][j] != 0.0) { ks[nk] = k[j]; cf[nk] = (float)(tb.beta[i][j] * dt); ++nk; }
-            {
-                ProfScope ps(e, s, PC_ODE, 0);
-                // with an FSAL tableau (c_sol[:-1] == beta[-1], c_sol[-1] == 0) the last stage input IS y1
-                HIPCHK(e, launch_lincomb(e->dt, y, ks, cf, nk, nstate, (fsal && i == S - 1) ? y1 : nullptr, p.x16, p.x16lo, s));
-            }
-            const double ti = (tb.alpha[i] == 1.0) ? t1 : t + tb.alpha[i] * dt;
-            if ((rc = eval(ti, k[i + 1]))) return rc;
-        }
-        if (!fsal) {                        // y1 = y + dt * sum_j c_sol[j] k_j
-            const float* ks[7]; float cf[7]; int nk = 0;
-            for (int j = 0; j <= S; ++j) if (tb.csol[j] != 0.0) { ks[nk] = k[j]; cf[nk] = (float)(tb.csol[j] * dt); ++nk; }
-            ProfScope ps(e, s, PC_ODE, 0);
-            HIPCHK(e, launch_lincomb(e->dt, y, ks, cf, nk, nstate, y1, p.x16, p.x16lo, s));
-        }
-        // error estimate from the stage derivatives
-        memset(&na, 0, sizeof(na));
-        na.mode = 2; na.y = y; na.a = y1; na.nk = 0;
-        for (int j = 0; j <= S; ++j) if (tb.cerr[j] != 0.0) { na.k[na.nk] = k[j]; na.coef[na.nk] = (float)(tb.cerr[j] * dt); ++na.nk; }
-        if ((rc = norms(na))) return rc;
-        const double ratio = sqrt(host2[0] / count);
-        if (!(ratio == ratio)) return e->fail(ST_ERR_INVALID, std::string(tb.name) + ": non-finite error estimate");
-        const bool accept = ratio <= 1.0;
-        double dt_next;
-        if (ratio == 0.0) dt_next = dt * 10.0;
-        else {
-            const double dfactor = ratio < 1.0 ? 1.0 : 0.2;
-            dt_next = dt * std::min(10.0, std::max(0.9 / pow(ratio, 1.0 / (double)tb.order), dfactor));
-        }
-        e->last_steps += 1;
-        if (accept) {
-            if (t1 >= t_end) {      // dense output at t_end inside [t, t1] -> p.ynew; slot 6 of the kernel is f1 = k[S]
-                const float* ks[7]; float cm[7];
-                for (int j = 0; j < 7; ++j) { ks[j] = k[0]; cm[j] = 0.f; }
-                for (int j = 0; j < S; ++j) { ks[j] = k[j]; cm[j] = (float)(tb.cmid[j] * dt); }
-                ks[6] = k[S]; cm[6] = (float)(tb.cmid[S] * dt);
-                ProfScope ps(e, s, PC_ODE, 0);
-                // elementwise, so writing p.ynew in place is safe whichever of y / y1 it currently aliases
-                HIPCHK(e, launch_dopri5_interp(y, y1, ks, cm, (float)dt, (float)((t_end - t) / (t1 - t)), nstate, p.ynew, s));
-                return ST_OK;
-            }
-            std::swap(y, y1);                        // y <- y1
-            std::swap(k[0], k[S]);                   // f0 <- k[-1]
-            t = t1;
-        } else {
-            e->last_rejects += 1;
-        }
-        dt = dt_next;
-        if (!(dt > 0.0) || dt < 1e-12) return e->fail(ST_ERR_INVALID, std::string(tb.name) + ": step size underflow");
-    }
-    return e->fail(ST_ERR_INVALID, std::string(tb.name) + ": too many steps");
-}
-
-std::vector<float> linspace01(int n);
-
-// Exact Adams-Bashforth / Adams-Moulton weights for `order` samples on a uniform grid, newest first (bashforth: samples at
-// t0, t0 - dt, ...; moulton: t1, t0, t0 - dt, ...), from the integrals of the Lagrange basis over one step.  Long double is
-// ample for order <= 12 (the integer tables torchdiffeq stores are these numbers over a common divisor).
-static void adams_weights(int order, bool implicit, double* w) {
-    std::vector<long double> nodes((size_t)order);
-    for (int i = 0; i < order; ++i) nodes[(size_t)i] = implicit ? (i == 0 ? 1.0L : -(long double)(i - 1)) : -(long double)i;
-    for (int j = 0; j < order; ++j) {
-        std::vector<long double> poly(1, 1.0L);     // prod_{i != j} (u - x_i), lowest degree first
-        long double den = 1.0L;
-        for (int i = 0; i < order; ++i) {
-            if (i == j) continue;
-            poly.insert(poly.begin(), 0.0L);
-            for (size_t k = 0; k + 1 < poly.size(); ++k) poly[k] -= nodes[(size_t)i] * poly[k + 1];
-            den *= nodes[(size_t)j] - nodes[(size_t)i];
-        }
-        long double integ = 0.0L;
-        for (size_t k = 0; k < poly.size(); ++k) integ += poly[k] / (long double)(k + 1);
-        w[j] = (double)(integ / den);
-    }
-}
-
-// torchdiffeq's 'implicit_adams' (fixed_adams.py: AdamsBashforthMoulton, max_order 12, max_iters 4) on the fixed grid of
-// models/flow_matching.py:46, rtol = atol = 1e-5 as at :54 -- the eighth solver the reference's web UI offers (webui.py:110).
-// Restated from the published source (oracle: odeint_implicit_adams, which says PARITY UNPINNED: torchdiffeq is absent offline).
-// Per step: f0 = f(t0, y0) joins the history (newest first, <= 11 entries); fewer than 3 entries -> 3/8-rule Runge-Kutta step
-// reusing f0; otherwise Adams-Bashforth predictor over the history, then functional iteration of the Adams-Moulton corrector
-// dy <- dt m0 f(t1, y0 + dy) + delta until max |dy_old - dy| / (atol + rtol max(|dy_old|, |dy|)) < 1 (one device reduction and
-// an 8-byte read-back per iteration), at most 4 times; no convergence -> the oldest history entry is dropped.
-int solve_implicit_adams(st_engine* e, const Plan& p, const float* mask, int use_cfg, float cfg_strength, int n_steps,
-                         hipStream_t s) {
-    constexpr int kMaxHist = 11, kMaxIters = 4, kExtra = 11;
-    const double rtol = 1e-5, atol = 1e-5;
-    const int B = p.B;
-    const int64_t per_item = (int64_t)p.T * e->Mp;
-    const int64_t nstate = (int64_t)B * per_item;
-    const size_t sbytes = (size_t)nstate * 4;
-    int rc;
-    // 19 state-sized fp32 buffers: 11 history + zero + dy x 2 + delta + f / Runge-Kutta stages x 3 + 1 spare; the plan has 8
-    if (e->adams_bytes < sbytes * kExtra) {
-        if (e->adams_buf) { HIPCHK(e, hipStreamSynchronize(s)); hipFree(e->adams_buf); e->adams_buf = nullptr; e->adams_bytes = 0; }
-        HIPCHK(e, hipMalloc(&e->adams_buf, sbytes * kExtra));
-        e->adams_bytes = sbytes * kExtra;
-    }
-    std::vector<float*> pool;
-    for (int j = 0; j < 7; ++j) pool.push_back(p.kbuf[j]);
-    pool.push_back(p.ynew);
-    for (int j = 0; j < kExtra; ++j) pool.push_back((float*)((char*)e->adams_buf + (size_t)j * sbytes));
-    float* zero = pool.back(); pool.pop_back();
-    float* dyA = pool.back(); pool.pop_back();
-    float* dyB = pool.back(); pool.pop_back();
-    float* delta = pool.back(); pool.pop_back();
-    float* tmp[3]; for (int j = 0; j < 3; ++j) { tmp[j] = pool.back(); pool.pop_back(); }
-    HIPCHK(e, hipMemsetAsync(zero, 0, sbytes, s));
-    std::deque<float*> hist;        // newest first; `pool` holds the free buffers (>= 12 left)
-    auto eval = [&](float t, float* kout) -> int {
-        HIPCHK(e, launch_set_scalar(p.tvals, t, s));
-        int r = run_time_tables(e, p, s); if (r) return r;
-        r = run_estimator(e, p, mask, 0, s); if (r) return r;
-        ProfScope ps(e, s, PC_ODE, 0);
-        HIPCHK(e, launch_cfg_combine(e->dt, p.v32, B, per_item, use_cfg, cfg_strength, kout, nullptr, nullptr, nullptr, 0.f, s));
-        e->last_nfe += 1;
-        return ST_OK;
-    };
-    // out = base + sum_j cf[j] * ks[j] for any number of terms (lincomb takes 7 at a time); optionally also the operand pair
-    auto combine = [&](const float* base, const std::vector<const float*>& ks, const std::vector<float>& cf, float* out32, bool operands) -> int {
-        size_t done = 0;
-        const float* cur = base;
-        do {
-            const int nk = (int)std::min<size_t>(7, ks.size() - done);
-            const bool last = done + (size_t)nk == ks.size();
-            ProfScope ps(e, s, PC_ODE, 0);
-            HIPCHK(e, launch_lincomb(e->dt, cur, ks.data() + done, cf.data() + done, nk, nstate, out32,
-                                     last && operands ? p.x16 : nullptr, last && operands ? p.x16lo : nullptr, s));
-            cur = out32; done += (size_t)nk;
-        } while (done < ks.size());
-        return ST_OK;
-    };
-    float* y = p.xstate;
-    const std::vector<float> grid = linspace01(n_steps);
-    float host2[2];
-    for (int i = 0; i < n_steps; ++i) {
-        const float t0 = grid[(size_t)i], t1 = grid[(size_t)i + 1], dt = t1 - t0;
-        // f0 = f(t0, y)  (x16 holds y); joins the history
-        if ((int)hist.size() == kMaxHist) { pool.push_back(hist.back()); hist.pop_back(); }
-        float* f0 = pool.back(); pool.pop_back();
-        if ((rc = eval(t0, f0))) return rc;
-        hist.push_front(f0);
-        const int order = (int)hist.size();
-        if (order < 3) {        // rk4_alt_step_func with k1 = f0
-            if ((rc = combine(y, {f0}, {dt / 3.0f}, nullptr, true))) return rc;
-            if ((rc = eval(t0 + dt / 3.0f, tmp[0]))) return rc;
-            if ((rc = combine(y, {tmp[0], f0}, {dt, -dt / 3.0f}, nullptr, true))) return rc;
-            if ((rc = eval(t0 + dt * 2.0f / 3.0f, tmp[1]))) return rc;
-            if ((rc = combine(y, {f0, tmp[0], tmp[1]}, {dt, -dt, dt}, nullptr, true))) return rc;
-            if ((rc = eval(t1, tmp[2]))) return rc;
-            if ((rc = combine(y, {f0, tmp[0], tmp[1], tmp[2]}, {dt * 0.125f, dt * 0.375f, dt * 0.375f, dt * 0.125f}, y, true))) return rc;
-            continue;
-        }
-        double wb[12], wm[13];
-        adams_weights(order, false, wb);
-        adams_weights(order + 1, true, wm);
-        std::vector<const float*> hs(hist.begin(), hist.end());
-        std::vector<float> cb((size_t)order), cm((size_t)order);
-        for (int j = 0; j < order; ++j) { cb[(size_t)j] = (float)((double)dt * wb[j]); cm[(size_t)j] = (float)((double)dt * wm[j + 1]); }
-        float* dy = dyA; float* dyn = dyB;
-        if ((rc = combine(zero, hs, cb, dy, false))) return rc;             // predictor
-        if ((rc = combine(zero, hs, cm, delta, false))) return rc;
-        bool converged = false;
-        for (int it = 0; it < kMaxIters && !converged; ++it) {
-            if ((rc = combine(y, {dy}, {1.0f}, nullptr, true))) return rc;      // operands of f(t1, y + dy)
-            if ((rc = eval(t1, tmp[0]))) return rc;
-            if ((rc = combine(delta, {tmp[0]}, {(float)((double)dt * wm[0])}, dyn, false))) return rc;
-            OdeNormArgs na; memset(&na, 0, sizeof(na));
-            na.mode = 3; na.y = dy; na.a = dy; na.b = dyn; na.rtol = (float)rtol; na.atol = (float)atol; na.n = nstate;
-            na.partial = p.ode_partial; na.out = p.ode_out;
-            HIPCHK(e, launch_ode_norm(na, s));
-            HIPCHK(e, hipMemcpyAsync(host2, p.ode_out, 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(e, hipStreamSynchronize(s));
-            converged = host2[0] == 0.0f;
-            std::swap(dy, dyn);
-        }
-        if (!converged) { pool.push_back(hist.back()); hist.pop_back(); e->last_rejects += 1; }     // (torchdiffeq warns and drops the oldest sample)
-        if ((rc = combine(y, {dy}, {1.0f}, y, true))) return rc;            // y1 = y0 + dy, and its operands for the next f0
-    }
-    return ST_OK;
-}
-
 int check_ready(st_engine* e, int B, int T) {
     if (!e) return ST_ERR_INVALID;
     if (!e->finalized) return e->fail(ST_ERR_STATE, "st_finalize() has not been called after loading parameters");
     if (B < 1 || T < 1) return e->fail(ST_ERR_INVALID, "B and T must be >= 1");
     if ((int64_t)2 * B * T * e->F >= (int64_t)1 << 31) return e->fail(ST_ERR_INVALID, "B*T too large for 32-bit row indexing");
     return ST_OK;
-}
-
-// torch.linspace(0, 1, n + 1) in fp32 (CPU kernel: symmetric fill from both ends)
-std::vector<float> linspace01(int n) {
-    const int steps = n + 1;
-    std::vector<float> t(steps);
-    const float step = (1.0f - 0.0f) / (float)(steps - 1);
-    const int half = steps / 2;
-    for (int i = 0; i < steps; ++i) t[i] = i < half ? 0.0f + step * (float)i : 1.0f - step * (float)(steps - i - 1);
-    return t;
 }
 
 }  // namespace sthost
@@ -1018,11 +695,7 @@ void st_destroy(st_engine* e) {
     train_destroy(e);
     vocos_destroy(e);
     if (e->gstream) hipStreamDestroy(e->gstream);
-    for (int k = 1; k < kMaxParts; ++k) {
-        if (e->sx[k]) hipStreamDestroy(e->sx[k]);
-        if (e->ev_joinx[k]) hipEventDestroy(e->ev_joinx[k]);
-    }
-    if (e->ev_fork) hipEventDestroy(e->ev_fork);
+    e->part_streams.destroy();
     for (auto& kv : e->params) if (kv.second.dev && !kv.second.borrowed) hipFree(kv.second.dev);
     for (void* p : e->owned) hipFree(p);
     for (auto& kv : e->caps) if (kv.second.dev) hipFree(kv.second.dev);
@@ -1311,230 +984,6 @@ int st_estimator_forward(st_engine* e, const float* t, int t_len, const float* x
     {
         ProfScope ps(e, s, PC_PREP, 0);
         HIPCHK(e, launch_from_time_major(p.v32, B, e->M, T, e->Mp, out, s, e->status_dev));
-    }
-    return ST_OK;
-}
-
-int st_cfm_solve(st_engine* e, const float* mu, const float* mask, const float* z, const float* c,
-                 int n_steps, int solver, int use_cfg, float cfg_strength,
-                 const float* fake_speaker, const float* fake_content,
-                 float* out, int B, int T, void* stream) {
-    int rc = check_ready(e, B, T); if (rc) return rc;
-    if (e->kind != 0) return e->fail(ST_ERR_STATE, "this handle is not a CFM decoder (st_create)");
-    if (!mu || !mask || !z || !c || !out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
-    if (n_steps < 1 || n_steps > 4096) return e->fail(ST_ERR_INVALID, "n_steps out of range");
-    if (solver < ST_SOLVER_EULER || solver > ST_SOLVER_IMPLICIT_ADAMS)
-        return e->fail(ST_ERR_UNSUPPORTED, "solver not implemented natively (euler, midpoint, rk4, dopri5, bosh3, "
-                                           "fehlberg2, adaptive_heun, implicit_adams are)");
-    if (use_cfg && (!fake_speaker || !fake_content)) return e->fail(ST_ERR_INVALID, "CFG needs fake_speaker and fake_content");
-    HIPCHK(e, hipSetDevice(e->device));
-    hipStream_t s = (hipStream_t)stream;
-    const bool adams = solver == ST_SOLVER_IMPLICIT_ADAMS;
-    const bool adaptive = solver >= ST_SOLVER_DOPRI5;      // host-side controller: one part, eager, time tables per evaluation (incl. implicit Adams)
-    const RkTableau& tableau = solver == ST_SOLVER_BOSH3 ? kBosh3 : solver == ST_SOLVER_FEHLBERG2 ? kFehlberg2
-                             : solver == ST_SOLVER_ADAPTIVE_HEUN ? kAdaptiveHeun : kDopri5;
-    const int stages = solver == ST_SOLVER_EULER ? 1 : (solver == ST_SOLVER_MIDPOINT ? 2 : 4);
-    const int n_t = adaptive ? 1 : n_steps * stages;
-
-    // Utterances are independent ODE solves.  A large fixed-grid batch is solved as TWO (from B = 32 at T = 1000: FOUR) parts
-    // (contiguous utterance ranges) on as many streams: every kernel of this path alternates an MFMA-bound K loop with an
-    // HBM-bound epilogue, and with one launch at a time all CUs sit in the same phase (1 block per CU, lock step).
-    // Two half-size launch sequences, started one evaluation apart, put different kernels / phases on the chip at
-    // the same time, so the matrix pipes of one part's blocks run under the other part's epilogues.  Results are
-    // bitwise independent of the split (an utterance never shares a tile with another).  Adaptive solvers keep ONE
-    // part: their step controller takes the error norm over the whole batch.  ST_SPLIT=0|1|2 overrides (read per call).
-    int nparts = 1;
-    {
-        const char* sv = getenv("ST_SPLIT");
-        const int want = sv ? atoi(sv) : kDefaultSplit;
-        const int64_t frames = (int64_t)(use_cfg ? 2 : 1) * B * T;
-        if (!adaptive && !e->capture && B >= 2 && (want >= 2 || (want != 0 && want != 1 && frames >= 24000 && B >= 8))) nparts = 2;
-        // four parts from 48 000 CFG-doubled frames on (B >= 32 at T = 1000): 25.5 -> 24.8 ms at the headline size, interleaved A/B
-        // (profiles/r03_ab_solve_parts.txt); six or eight parts are much slower (31 / 29.5 ms: 40-block launches from 6-8 queues)
-        // ... with the generic q/k/v tile.  With the weight-stationary q/k/v kernel (qkv_ws.hip, default) TWO parts are faster: its
-        // persistent blocks want >= 5 tiles each, i.e. half-batch launches (paired A/B, round 4: 2 parts + qkv_ws 24.60 ms against
-        // 4 parts + generic tile 24.91, ragged 21.61 against 22.09; profiles/r04b_ab_parts_qkv_ws.txt)
-        if (!adaptive && !e->capture && want != 0 && want != 1 && want != 2 && frames >= 48000 && B >= 32 && !(e->qkv_ws && e->sink)) nparts = 4;
-        if (want > 2 && B >= want) nparts = std::min(want, kMaxParts);
-        if (want == 1 || want == 0) nparts = 1;
-    }
-    struct Part { Plan p; int b0, nb; hipStream_t s; const float* mask; };
-    std::vector<Part> parts((size_t)nparts);
-    {
-        size_t off = 0;
-        for (int k = 0; k < nparts; ++k) {
-            parts[k].b0 = (int)((int64_t)B * k / nparts);
-            parts[k].nb = (int)((int64_t)B * (k + 1) / nparts) - parts[k].b0;
-            off = layout_plan(e, parts[k].nb, T, use_cfg != 0, n_t, off, &parts[k].p);
-        }
-        if ((rc = ensure_ws(e, off))) return rc;
-        e->arena_poisoned();
-        if ((rc = arena_fresh(e, layout_sig(2, B, T, use_cfg != 0, n_t, nparts), off, s))) return rc;
-        for (auto& pt : parts) bind_plan(e, &pt.p);
-    }
-    if ((rc = ensure_rope(e, T, s))) return rc;
-    if (nparts > 1 && !e->ev_fork) HIPCHK(e, hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-    for (int k = 1; k < nparts; ++k)
-        if (!e->sx[k]) {
-            HIPCHK(e, hipStreamCreateWithFlags(&e->sx[k], hipStreamNonBlocking));
-            HIPCHK(e, hipEventCreateWithFlags(&e->ev_joinx[k], hipEventDisableTiming));
-        }
-
-    // evaluation times, fp32 arithmetic as torchdiffeq does on the fp32 t_span (flow_matching.py:46)
-    const std::vector<float> grid = linspace01(n_steps);
-    std::vector<float> tv((size_t)n_t), dts((size_t)n_steps);
-    for (int i = 0; i < n_steps && !adaptive; ++i) {
-        const float t0 = grid[i], t1 = grid[i + 1], dt = t1 - t0;
-        dts[i] = dt;
-        if (stages == 1) tv[i] = t0;
-        else if (stages == 2) { tv[2 * i] = t0; tv[2 * i + 1] = t0 + 0.5f * dt; }
-        else { tv[4 * i] = t0; tv[4 * i + 1] = t0 + dt / 3.0f; tv[4 * i + 2] = t0 + dt * 2.0f / 3.0f; tv[4 * i + 3] = t1; }
-    }
-    const int64_t per_item = (int64_t)T * e->Mp;
-    const int64_t bct = (int64_t)e->M * T;        // elements per utterance of a (B, n_feats, T) boundary tensor
-    for (auto& pt : parts) {      // boundary conversions (caller's layouts -> engine operands), on the caller's stream
-        const Plan& p = pt.p;
-        ProfScope ps(e, s, PC_PREP, 0);
-        HIPCHK(e, launch_set_values(p.tvals, tv.data(), (int)tv.size(), s));   // by kernel argument: no copy, no sync
-        HIPCHK(e, launch_mask_prep(mask + (int64_t)pt.b0 * T, pt.nb, T, p.Tp, p.n_full, p.kv_end, p.kbias, p.t_lim, s));
-        HIPCHK(e, hipMemsetAsync(p.v32, 0, (size_t)p.N * T * e->Mp * 4, s));      // frames of skipped tiles: v = 0 (estimator.py:138)
-        HIPCHK(e, launch_cvec_prep(mask + (int64_t)pt.b0 * T, nullptr, pt.nb, T, p.maskbuf, s));      // plain copy of the (B,1,T) mask
-        pt.mask = p.maskbuf;
-        HIPCHK(e, launch_to_time_major(e->dt, mu + pt.b0 * bct, pt.nb, e->M, T, e->Mp, nullptr, p.mu16, nullptr, s));
-        HIPCHK(e, launch_to_time_major(e->dt, z + pt.b0 * bct, pt.nb, e->M, T, e->Mp, p.xstate, p.x16, p.x16lo, s));
-        HIPCHK(e, launch_cvec_prep(c + (int64_t)pt.b0 * e->G, use_cfg ? fake_speaker : nullptr, pt.nb, e->G, p.cvec, s));
-        if (use_cfg) {
-            // uncond branch inputs (flow_matching.py:59-60): fake_content over ALL frames, fake_speaker per item
-            HIPCHK(e, launch_fill_rows16(e->dt, fake_content, e->M, e->Mp, T,
-                                         (char*)p.mu16 + (size_t)pt.nb * per_item * 2, s));
-        }
-    }
-    e->last_nfe = adaptive ? 0 : (int64_t)n_t; e->last_steps = adaptive && !adams ? 0 : n_steps; e->last_rejects = 0;
-
-    // One solver step of one part (fixed grid): estimator evaluation(s) + state update.
-    auto step_fixed = [&](const Part& pt, int i, hipStream_t ps_) -> int {
-        const Plan& p = pt.p;
-        const int Bp = pt.nb;
-        const int64_t nstate = (int64_t)Bp * per_item;
-        const float dt = dts[i];
-        int rc;
-        if (solver == ST_SOLVER_EULER) {
-            if ((rc = run_estimator(e, p, pt.mask, i, ps_))) return rc;
-            ProfScope ps(e, ps_, PC_ODE, 0);
-            HIPCHK(e, launch_cfg_combine(e->dt, p.v32, Bp, per_item, use_cfg, cfg_strength, nullptr, p.xstate, p.x16, p.x16lo, dt, ps_));
-        } else if (solver == ST_SOLVER_MIDPOINT) {
-            if ((rc = run_estimator(e, p, pt.mask, 2 * i, ps_))) return rc;
-            {
-                ProfScope ps(e, ps_, PC_ODE, 0);
-                HIPCHK(e, launch_cfg_combine(e->dt, p.v32, Bp, per_item, use_cfg, cfg_strength, p.kbuf[0], nullptr, nullptr, nullptr, 0.f, ps_));
-                const float* ks[1] = {p.kbuf[0]}; const float cf[1] = {0.5f * dt};
-                HIPCHK(e, launch_lincomb(e->dt, p.xstate, ks, cf, 1, nstate, nullptr, p.x16, p.x16lo, ps_));
-            }
-            if ((rc = run_estimator(e, p, pt.mask, 2 * i + 1, ps_))) return rc;
-            ProfScope ps(e, ps_, PC_ODE, 0);
-            HIPCHK(e, launch_cfg_combine(e->dt, p.v32, Bp, per_item, use_cfg, cfg_strength, nullptr, p.xstate, p.x16, p.x16lo, dt, ps_));
-        } else {   // rk4 = torchdiffeq's 3/8 rule
-            for (int st = 0; st < 4; ++st) {
-                if ((rc = run_estimator(e, p, pt.mask, 4 * i + st, ps_))) return rc;
-                ProfScope ps(e, ps_, PC_ODE, 0);
-                HIPCHK(e, launch_cfg_combine(e->dt, p.v32, Bp, per_item, use_cfg, cfg_strength, p.kbuf[st], nullptr, nullptr, nullptr, 0.f, ps_));
-                if (st == 0) {
-                    const float* ks[1] = {p.kbuf[0]}; const float cf[1] = {dt / 3.0f};
-                    HIPCHK(e, launch_lincomb(e->dt, p.xstate, ks, cf, 1, nstate, nullptr, p.x16, p.x16lo, ps_));
-                } else if (st == 1) {
-                    const float* ks[2] = {p.kbuf[1], p.kbuf[0]}; const float cf[2] = {dt, -dt / 3.0f};
-                    HIPCHK(e, launch_lincomb(e->dt, p.xstate, ks, cf, 2, nstate, nullptr, p.x16, p.x16lo, ps_));
-                } else if (st == 2) {
-                    const float* ks[3] = {p.kbuf[0], p.kbuf[1], p.kbuf[2]}; const float cf[3] = {dt, -dt, dt};
-                    HIPCHK(e, launch_lincomb(e->dt, p.xstate, ks, cf, 3, nstate, nullptr, p.x16, p.x16lo, ps_));
-                } else {
-                    const float* ks[4] = {p.kbuf[0], p.kbuf[1], p.kbuf[2], p.kbuf[3]};
-                    const float cf[4] = {dt * 0.125f, dt * 0.375f, dt * 0.375f, dt * 0.125f};
-                    HIPCHK(e, launch_lincomb(e->dt, p.xstate, ks, cf, 4, nstate, p.xstate, p.x16, p.x16lo, ps_));
-                }
-            }
-        }
-        return ST_OK;
-    };
-
-    // Everything between the boundary conversions above and below touches engine memory only, so for the fixed-grid
-    // solvers it is a static launch sequence: `body` enqueues it, either directly or once into a HIP graph.  With two
-    // parts the second one runs on the engine's second stream (forked from / joined back into `cs` with events) and
-    // the host interleaves the parts step by step, so part 1 trails part 0 by about one evaluation's enqueue time.
-    auto body = [&](hipStream_t cs) -> int {
-        int rc;
-        e->conc = nparts;
-        if (nparts > 1) {
-            HIPCHK(e, hipEventRecord(e->ev_fork, cs));
-            for (int k = 1; k < nparts; ++k) HIPCHK(e, hipStreamWaitEvent(e->sx[k], e->ev_fork, 0));
-        }
-        for (int k = 0; k < nparts; ++k) parts[k].s = k == 0 ? cs : e->sx[k];
-        for (auto& pt : parts) {
-            if ((rc = run_prenet(e, pt.p, pt.s))) return rc;
-            if ((rc = run_adaln(e, pt.p, pt.s))) return rc;
-            if (!adaptive && (rc = run_time_tables(e, pt.p, pt.s))) return rc;
-        }
-        if (adams) {
-            if ((rc = solve_implicit_adams(e, parts[0].p, parts[0].mask, use_cfg, cfg_strength, n_steps, cs))) return rc;
-        } else if (adaptive) {
-            if ((rc = solve_adaptive(e, parts[0].p, parts[0].mask, use_cfg, cfg_strength, tableau, cs))) return rc;
-        } else {
-            // The parts run the same kernel sequence; started together they tend to sit in the same kernel at the same time (FFN beside
-            // FFN: two power-limited kernels sharing the CUs).  Part k starts 100 k us late -- about half a layer of a half batch: any
-            // offset from 30 to 250 us measured +0.4 ... +0.6 % per solve, paired (profiles/r05_ab_part_phase.txt).
-            // (Measured for TWO parts at the headline size only: other part counts -- ST_SPLIT=3, 4 -- start together.)
-            if (nparts == 2) HIPCHK(e, launch_delay(kPartPhaseUs, parts[1].s));
-            for (int i = 0; i < n_steps; ++i)
-                for (auto& pt : parts)
-                    if ((rc = step_fixed(pt, i, pt.s))) return rc;
-        }
-        for (int k = 1; k < nparts; ++k) {
-            HIPCHK(e, hipEventRecord(e->ev_joinx[k], e->sx[k]));
-            HIPCHK(e, hipStreamWaitEvent(cs, e->ev_joinx[k], 0));
-        }
-        return ST_OK;
-    };
-
-    // ST_HIP_GRAPH=1 (read per call): the fixed-grid solve body (~45 launches per evaluation) is captured into a HIP
-    // graph the second time a solve signature is seen (the first run is eager: it also performs the one-time
-    // per-kernel attribute set-up, which must not happen inside a capture) and replayed afterwards.  Adaptive
-    // solvers have a host-side controller and always run eagerly; so do profiled / debug-captured solves.
-    const char* genv = getenv("ST_HIP_GRAPH");
-    const bool want_graph = genv && atoi(genv) == 1 && !adaptive && !e->prof && !e->capture;
-    bool done = false;
-    int brc = ST_OK;
-    if (want_graph) {
-        st_engine::SolveGraph* g = nullptr;
-        for (auto& q : e->graphs)
-            if (q.B == B && q.T == T && q.n_steps == n_steps && q.solver == solver && q.use_cfg == (use_cfg != 0) &&
-                q.cfg_strength == cfg_strength && q.ws == e->ws && q.parts == nparts) g = &q;
-        if (!g) {
-            if (e->graphs.size() >= 16) e->drop_graphs();
-            e->graphs.push_back({B, T, n_steps, solver, use_cfg != 0, cfg_strength, e->ws, nparts, 0, nullptr});
-            g = &e->graphs.back();
-        }
-        if (g->seen >= 1 && !g->exec) {
-            // captured on an engine-owned stream (the caller's may be the legacy default stream, which cannot
-            // capture); nothing executes during capture, the instantiated graph is launched on the caller's stream
-            if (!e->gstream) HIPCHK(e, hipStreamCreateWithFlags(&e->gstream, hipStreamNonBlocking));
-            hipGraph_t graph = nullptr;
-            HIPCHK(e, hipStreamBeginCapture(e->gstream, hipStreamCaptureModeRelaxed));
-            brc = body(e->gstream);
-            const hipError_t ec = hipStreamEndCapture(e->gstream, &graph);
-            e->conc = 1;
-            if (brc) { if (graph) hipGraphDestroy(graph); return brc; }
-            if (ec != hipSuccess || !graph) return e->fail(ST_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ec));
-            const hipError_t ei = hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0);
-            hipGraphDestroy(graph);
-            if (ei != hipSuccess) { g->exec = nullptr; return e->fail(ST_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ei)); }
-        }
-        g->seen += 1;
-        if (g->exec) { HIPCHK(e, hipGraphLaunch(g->exec, s)); done = true; }
-    }
-    if (!done) { brc = body(s); e->conc = 1; if (brc) { e->ws_sig = 0; return brc; } }      // (a half-enqueued body: re-zero the arena next time)
-    for (auto& pt : parts) {
-        ProfScope ps(e, s, PC_PREP, 0);
-        HIPCHK(e, launch_from_time_major(adaptive && !adams ? pt.p.ynew : pt.p.xstate, pt.nb, e->M, T, e->Mp, out + pt.b0 * bct, s, e->status_dev));
     }
     return ST_OK;
 }

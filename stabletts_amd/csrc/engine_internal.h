@@ -1,8 +1,9 @@
-// Host-side internals shared by engine.cpp (inference: parameter store, packing, solve loop) and engine_train.cpp
-// (training: forward that keeps activations + backward).  Not part of the C ABI.
+// Host-side internals shared by engine.cpp (inference: parameter store, packing, estimator launch sequence), engine_solve.cpp
+// (the ODE solvers behind st_cfm_solve) and engine_train.cpp (training: forward that keeps activations + backward).  Not part of the C ABI.
 #pragma once
 #include "../../include/stabletts_hip.h"
 #include "launch.h"
+#include "stream_fork.h"
 
 #include <map>
 #include <string>
@@ -41,7 +42,7 @@ struct VocosState;     // engine_vocos.cpp
 
 }  // namespace sthost
 
-constexpr int kMaxParts = 4;
+constexpr int kMaxParts = 1 + sthost::StreamFork::kMaxChildren;      // solve parts: part 0 on the caller's stream, the others on part_streams
 constexpr int kSplitKMax = 16;
 constexpr size_t kSplitKBytes = 32u << 20;
 
@@ -131,8 +132,7 @@ struct st_engine {
     float* kpart = nullptr;             // split-K partial planes [ks][items][T][256] fp32
     size_t kpart_bytes = 0;
     int conc = 1;                       // solve parts in flight on separate streams (their launches share the chip)
-    hipStream_t sx[kMaxParts] = {};     // streams of solve parts 1.. (part 0 runs on the caller's stream)
-    hipEvent_t ev_fork = nullptr, ev_joinx[kMaxParts] = {};
+    sthost::StreamFork part_streams;    // streams of solve parts 1.. (part 0 runs on the caller's stream)
 
     // HIP-graph replay of the fixed-grid solve body (ST_HIP_GRAPH=1): one instantiated graph per solve signature
     struct SolveGraph {
@@ -197,6 +197,33 @@ struct ProfScope {
     ProfScope(st_engine* e_, hipStream_t s_, int cls, double flops);
     ~ProfScope();
 };
+
+// ---- engine.cpp: the workspace plan of one estimator pass (or solve part) and the launch sequences that use it
+struct Plan {
+    int B, T, Tp, N, Pn, n_t;
+    bool cfg;
+    // 16-bit MFMA operands.  *lo tensors hold x - float(hi): the split-precision operand pairs of the three GEMMs
+    // whose rounding error reaches the output un-gated (in_proj x-part and cond-part, final_proj)
+    void *mu16, *pre1, *pre2, *cond16, *cond16lo, *x16, *x16lo, *h16, *h2_16, *q16, *k16, *q16lo, *k16lo, *vt16, *ao16, *u16, *cur16, *cur16lo;
+    void* skip16[8];
+    // fp32
+    float *cpart, *X, *v32, *xstate, *kbuf[7], *ynew, *ode_partial, *ode_out, *tvals, *emb, *th, *tau, *film, *cvec, *ada, *ada_tmp;
+    int *n_full, *kv_end;
+    int* t_lim;         // [B + 1] frames of every utterance that are computed (mask_prep: last valid + 1 + halo), [B] = the longest
+    float* kbias;
+    float* maskbuf;     // engine-owned copy of the caller's (B,1,T) mask: the solve body touches arena memory only
+    struct Slot { void** dst; size_t off; };
+    std::vector<Slot> slots;
+};
+// Lays the tensors of one solve (or solve part) out in the arena starting at byte `off`; returns the end offset.
+// Pointers become valid after ensure_ws() + bind_plan().
+size_t layout_plan(st_engine* e, int B, int T, bool cfg, int n_t, size_t off, Plan* p);
+void bind_plan(st_engine* e, Plan* p);
+uint64_t layout_sig(int entry, int B, int T, int cfg, int n_t, int parts);
+int run_prenet(st_engine* e, const Plan& p, hipStream_t s);
+int run_adaln(st_engine* e, const Plan& p, hipStream_t s);
+int run_time_tables(st_engine* e, const Plan& p, hipStream_t s);
+int run_estimator(st_engine* e, const Plan& p, const float* mask, int ev, hipStream_t s);
 
 // engine_train.cpp
 int train_prepare(st_engine* e, hipStream_t s);       // packs the transposed (dgrad) weights if the parameters changed

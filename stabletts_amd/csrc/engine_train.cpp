@@ -89,10 +89,8 @@ struct TrainState {
     //            for them, and their small reduce launches run beside the main chain's big kernels.
     //   side2 -- the gradient-INDEPENDENT operand copies of a block's attention backward (centred q / k / v copies, T layouts),
     //            forked at the start of the block and joined in front of its attention kernels.
-    hipStream_t side = nullptr, side2 = nullptr;
-    hipEvent_t ev_fork[16] = {}, ev_site[DY_COUNT] = {}, ev_join = nullptr, ev_blk = nullptr, ev_prep = nullptr;
-    bool site_pending[DY_COUNT] = {};
-    int fork_idx = 0;
+    StreamFork side, side2;             // side: a ring of 16 fork events and one site per dY operand; side2: one fork event
+    static_assert(DY_COUNT <= StreamFork::kMaxSites, "one site per dY operand");
     // The conv_q / conv_k weight gradients are ill-conditioned in v at random init (near-uniform softmax: dS ~ dO.(v_j - o_i), the
     // key-independent bulk of v cancels in that difference, its 16-bit error does not): with v and its input h1 as single 16-bit operands they
     // are 25 % off the fp32 oracle end to end at B = 4 x T = 1000 (cosine 0.991; tools/train_qk_split_estimate.py: rounding v 18 %, rounding
@@ -164,18 +162,9 @@ int train_prepare(st_engine* e, hipStream_t s) {
             // 18.51 ms per step, the main chain being the critical path) -- but inside bench.py, next to the inference engines' part streams,
             // the same setting took the step from 18.6 to 24.9 ms (streams alias onto the process's few hardware queues): not the default.
             int least = 0, greatest = 0;
-            if (t0->side_prio && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess) {
-                HIPCHK(e, hipStreamCreateWithPriority(&t0->side, hipStreamNonBlocking, least));
-                HIPCHK(e, hipStreamCreateWithPriority(&t0->side2, hipStreamNonBlocking, least));
-            } else {
-                HIPCHK(e, hipStreamCreateWithFlags(&t0->side, hipStreamNonBlocking));
-                HIPCHK(e, hipStreamCreateWithFlags(&t0->side2, hipStreamNonBlocking));
-            }
-            for (auto& ev : t0->ev_fork) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            for (auto& ev : t0->ev_site) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            HIPCHK(e, hipEventCreateWithFlags(&t0->ev_join, hipEventDisableTiming));
-            HIPCHK(e, hipEventCreateWithFlags(&t0->ev_blk, hipEventDisableTiming));
-            HIPCHK(e, hipEventCreateWithFlags(&t0->ev_prep, hipEventDisableTiming));
+            const bool prio = t0->side_prio && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess;
+            HIPCHK(e, t0->side.ensure(1, 16, TrainState::DY_COUNT, prio ? &least : nullptr));
+            HIPCHK(e, t0->side2.ensure(1, 1, 0, prio ? &least : nullptr));
         }
     }
     TrainState* ts = e->train;
@@ -258,11 +247,8 @@ int64_t train_bytes(const st_engine* e) {      // transposed weights + gradient 
 void train_destroy(st_engine* e) {
     if (!e->train) return;
     for (void* p : e->train->owned) hipFree(p);
-    if (e->train->side) { hipStreamSynchronize(e->train->side); hipStreamDestroy(e->train->side); }
-    if (e->train->side2) { hipStreamSynchronize(e->train->side2); hipStreamDestroy(e->train->side2); }
-    for (auto ev : e->train->ev_fork) if (ev) hipEventDestroy(ev);
-    for (auto ev : e->train->ev_site) if (ev) hipEventDestroy(ev);
-    for (auto ev : {e->train->ev_join, e->train->ev_blk, e->train->ev_prep}) if (ev) hipEventDestroy(ev);
+    e->train->side.destroy();
+    e->train->side2.destroy();
     if (e->train->ws) hipFree(e->train->ws);
     delete e->train;
     e->train = nullptr;
@@ -632,31 +618,14 @@ int wgrad(st_engine* e, TrainState* ts, const void* x0, int c0, const void* x1, 
 float* G(TrainState* ts, const std::string& name) { return ts->gbase + ts->goff.at(name); }
 
 // The weight gradient of one site on the side stream: it starts when everything enqueued on `s` so far (the producer of its dY
-// operand) has run, and records the site's event when it is done with that operand.
+// operand) has run, and records the site's event when it is done with that operand (the kernel that OVERWRITES the operand
+// waits for it: side.wait_site).  Without side streams it runs on `s`.
 int wgrad_side(st_engine* e, TrainState* ts, int site, const void* x0, int c0, const void* x1, int c1, int cout16, int taps,
                const WgradOut* outs, int n_outs, hipStream_t s) {
-    const void* dy = ts->dy[site];
-    if (!ts->use_side) return wgrad(e, ts, x0, c0, x1, c1, dy, cout16, taps, outs, n_outs, s);
-    hipEvent_t f = ts->ev_fork[ts->fork_idx]; ts->fork_idx = (ts->fork_idx + 1) % 16;
-    HIPCHK(e, hipEventRecord(f, s));
-    HIPCHK(e, hipStreamWaitEvent(ts->side, f, 0));
-    int rc = wgrad(e, ts, x0, c0, x1, c1, dy, cout16, taps, outs, n_outs, ts->side);
+    HIPCHK(e, ts->side.fork(s));
+    int rc = wgrad(e, ts, x0, c0, x1, c1, ts->dy[site], cout16, taps, outs, n_outs, ts->side.on(s));
     if (rc) return rc;
-    HIPCHK(e, hipEventRecord(ts->ev_site[site], ts->side));
-    ts->site_pending[site] = true;
-    return ST_OK;
-}
-// ... and in front of the kernel that OVERWRITES a site's dY operand: wait until the previous block's weight gradient has read it
-int site_free(st_engine* e, TrainState* ts, int site, hipStream_t s) {
-    if (ts->use_side && ts->site_pending[site]) { HIPCHK(e, hipStreamWaitEvent(s, ts->ev_site[site], 0)); ts->site_pending[site] = false; }
-    return ST_OK;
-}
-// end of a backward part: the parameter gradients must be complete when the call returns its stream to the caller
-int side_join(st_engine* e, TrainState* ts, hipStream_t s) {
-    if (!ts->use_side) return ST_OK;
-    HIPCHK(e, hipEventRecord(ts->ev_join, ts->side));
-    HIPCHK(e, hipStreamWaitEvent(s, ts->ev_join, 0));
-    for (auto& p : ts->site_pending) p = false;
+    HIPCHK(e, ts->side.record_site(site));
     return ST_OK;
 }
 
@@ -736,11 +705,11 @@ int bwd_block(st_engine* e, TrainState* ts, int i, hipStream_t s) {
     const float* m = ts->maskbuf;
     int rc;
     const bool cap = e->capture;
+    ForkGuard guard{ts->side2, s};
     if (ts->use_side) {      // (everything enqueued on s so far includes the previous block's attention kernels, the last readers of the copies)
-        HIPCHK(e, hipEventRecord(ts->ev_blk, s));
-        HIPCHK(e, hipStreamWaitEvent(ts->side2, ts->ev_blk, 0));
-        if ((rc = attn_prep(e, ts, i, ts->side2))) return rc;
-        HIPCHK(e, hipEventRecord(ts->ev_prep, ts->side2));
+        HIPCHK(e, ts->side2.fork(s));
+        if ((rc = attn_prep(e, ts, i, ts->side2.on(s)))) return rc;
+        HIPCHK(e, ts->side2.record_join());
     }
     {
         LayerAct& A = ts->L[i];
@@ -762,12 +731,12 @@ int bwd_block(st_engine* e, TrainState* ts, int i, hipStream_t s) {
             return ts->red_site[k];
         };
         // ---- x3 = x2 + g_mlp * f
-        if ((rc = site_free(e, ts, TrainState::DY_FFN2, s))) return rc;
+        HIPCHK(e, ts->side.wait_site(TrainState::DY_FFN2, s));
         HIPCHK(e, launch_gate_bwd(e->dt, ts->dX, A.f32b, ada_i + 5 * C, 6 * C, m, B, T, N, ts->dy[TrainState::DY_FFN2], site(0, 1, dada_i, 6 * C, 5 * C, 0), s));
         {   // conv_2
             WgradOut o = {G(ts, b + "mlp.conv_2.weight"), F, 0, F, 0, C, G(ts, b + "mlp.conv_2.bias")};
             if ((rc = wgrad_side(e, ts, TrainState::DY_FFN2, A.u16, F, nullptr, 0, C, K, &o, 1, s))) return rc;
-            if ((rc = site_free(e, ts, TrainState::DY_FFN1, s))) return rc;
+            HIPCHK(e, ts->side.wait_site(TrainState::DY_FFN1, s));
             ConvGemmArgs a = cargs(e, ts->ffn2T[i], N, T, B); a.a0 = ts->dy[TrainState::DY_FFN2]; a.c0 = C;
             const DropCfg dc = make_drop(ts->p_drop, ts->seed, 2 * i);
             if (ts->fuse_silu && K == 3 && gemm_is_phased(e, 3, a) && !a.bias) {      // d pre-activation straight from the dgrad's epilogue
@@ -790,7 +759,7 @@ int bwd_block(st_engine* e, TrainState* ts, int i, hipStream_t s) {
         if ((rc = recentre(e, ts, d, true, s))) return rc;
         if (cap) capture(e, "g.scale_a" + std::to_string(i), ts->gsc, 2, false, s);      // the scale of this block's attention-part tensors
         // ---- x2 = x1 + g_msa * o
-        if ((rc = site_free(e, ts, TrainState::DY_OPROJ, s))) return rc;
+        HIPCHK(e, ts->side.wait_site(TrainState::DY_OPROJ, s));
         HIPCHK(e, launch_gate_bwd(e->dt, ts->dX, A.o32, ada_i + 2 * C, 6 * C, m, B, T, N, ts->dy[TrainState::DY_OPROJ], site(2, 1, dada_i, 6 * C, 2 * C, 0), s));
         {   // out projection
             WgradOut o = {G(ts, b + "attn.conv_o.weight"), C, 0, C, 0, C, G(ts, b + "attn.conv_o.bias")};
@@ -799,7 +768,7 @@ int bwd_block(st_engine* e, TrainState* ts, int i, hipStream_t s) {
             HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
         }
         {   // attention
-            if (ts->use_side) HIPCHK(e, hipStreamWaitEvent(s, ts->ev_prep, 0));      // the operand copies forked at the start of the block
+            if (ts->use_side) HIPCHK(e, ts->side2.join(s));      // the operand copies forked at the start of the block
             else if ((rc = attn_prep(e, ts, i, s))) return rc;
             HIPCHK(e, launch_attn_to_T(e->dt, ts->dy[TrainState::DY_DATTN], (int64_t)T * C, 64, C, N, H, T, Tp, nullptr, ts->dOT, s));
             AttnBwdArgs a; memset(&a, 0, sizeof(a));
@@ -818,7 +787,7 @@ int bwd_block(st_engine* e, TrainState* ts, int i, hipStream_t s) {
             // range ends at 6e-5); the fused dgrad GEMM takes the copy with one common factor
             float* qs = ts->qs + 16 * i;
             HIPCHK(e, launch_qkv_grad_scales(ts->dq, ts->dk, ts->dv, R * C, ts->gsc, qbits, qs, s, true));
-            if ((rc = site_free(e, ts, TrainState::DY_QKVW, s))) return rc;
+            HIPCHK(e, ts->side.wait_site(TrainState::DY_QKVW, s));
             HIPCHK(e, launch_qkv_grad_pack(e->dt, ts->dq, ts->dk, ts->dv, e->rope_cos, e->rope_sin, N, H, T, qs, ts->dy[TrainState::DY_QKVD], ts->dy[TrainState::DY_QKVW], s));
         }
         if (cap) { capture(e, "g.dq_" + std::to_string(i), ts->dq, R * C, false, s); capture(e, "g.dk_" + std::to_string(i), ts->dk, R * C, false, s);
@@ -839,7 +808,7 @@ int bwd_block(st_engine* e, TrainState* ts, int i, hipStream_t s) {
         if ((rc = recentre(e, ts, d, true, s))) return rc;
         if (cap) capture(e, "g.scale_b" + std::to_string(i), ts->gsc, 2, false, s);      // ... and of what follows (g.xin_i)
         // ---- x1 = (gamma * xpre + beta) * mask
-        if (i >= L / 2 && (rc = site_free(e, ts, TrainState::DY_LSC, s))) return rc;
+        if (i >= L / 2) HIPCHK(e, ts->side.wait_site(TrainState::DY_LSC, s));
         HIPCHK(e, launch_film_bwd(e->dt, xpre_of(ts, i, L), ts->film + (size_t)i * N * 2 * C, 2 * C, N, m, B, T, N, ts->dX,
                                   i >= L / 2 ? ts->dy[TrainState::DY_LSC] : nullptr, site(4, 2, ts->dfilm + (size_t)i * N * 2 * C, 2 * C, 0, C), s));
         HIPCHK(e, launch_reduce_sites(sites, N, chunks, s));
@@ -987,6 +956,7 @@ int bwd_check(st_engine* e, int64_t serial, int B_, int T_, const char* who) {
 
 int bwd_part(st_engine* e, TrainState* ts, int part, const float* grad_out, float* grad_x, float* grad_mu, float* grad_c, hipStream_t s) {
     ProfScope prof(e, s, PC_TRAIN_BWD, 0);
+    ForkGuard guard{ts->side, s};      // (an early error return joins the side stream too)
     const int L = e->L;
     int rc;
     if (part == 0) {
@@ -999,7 +969,8 @@ int bwd_part(st_engine* e, TrainState* ts, int part, const float* grad_out, floa
     } else {
         if ((rc = bwd_tail(e, ts, grad_x, grad_mu, grad_c, s))) return rc;
     }
-    return side_join(e, ts, s);
+    HIPCHK(e, ts->side.join(s));      // the parameter gradients are complete when the call returns its stream to the caller
+    return ST_OK;
 }
 
 }  // namespace
