@@ -102,6 +102,7 @@ struct TrainState {
     bool v_lo = true, h_lo = true;
     bool use_side = true, side_prio = false;     // ST_TRAIN_SIDE=2: side streams at the device's lowest stream priority (0: no side streams)
     size_t partial_cap = 0, xt_cap = 0, dyt_cap = 0;
+    size_t wg_max_frames = 0, wg_max_cout = 0, wg_max_prod = 0;   // layout_train's largest taps*Cin, Cout and product: wgrad() refuses more
 };
 
 namespace {
@@ -303,13 +304,31 @@ int layout_train(st_engine* e, TrainState* ts, int B, int T) {
     want((void**)&ts->alphabuf, N * H * TT * 4);
     want((void**)&ts->vmean, N * H * 64 * 4); want((void**)&ts->qmean, N * H * 64 * 4); want((void**)&ts->kmean, N * H * 64 * 4);
     want((void**)&ts->dq, R * C * 4); want((void**)&ts->dk, R * C * 4); want((void**)&ts->dv, R * C * 4);
-    // weight-gradient operands: the largest are (taps*Cin, Cout) = (3F, F) [cond_proj.2]; rows padded per split
+    // weight-gradient operands, sized by the largest (taps*Cin, Cout) that wgrad() is called with: the wgrad_side() calls of bwd_head,
+    // bwd_block and bwd_tail, listed below -- keep the table in step with them (wgrad() fails on any call larger than the table, at
+    // every R).  Rows padded per split.  Which of them takes the TN path depends on the widths, so all count.  At C = 256 and
+    // F = 1024 the largest are 3F frames, F columns and 3F x F [cond_proj.1]; at F = 128 ffn1's 3C frames, at Mp > F final_proj's
+    // Mp columns are larger
+    size_t max_frames = 0, max_cout = 0, max_prod = 0;
+    {
+        const size_t K = e->K;
+        const size_t shapes[][2] = {{(size_t)C, (size_t)Mp},              // final_proj
+                                    {K * F, (size_t)C}, {K * C, (size_t)F},  // ffn conv_2, conv_1
+                                    {(size_t)C, (size_t)C}, {(size_t)C, (size_t)3 * C},  // out-proj, q / k / v
+                                    {K * 2 * C, (size_t)C},                  // long-skip convs
+                                    {(size_t)Mp, (size_t)C}, {(size_t)C, (size_t)C},   // in_proj (x, cond)
+                                    {K * F, (size_t)C}, {K * F, (size_t)F}, {K * Mp, (size_t)F}};   // cond_proj.2, .1, .0
+        for (const auto& sh : shapes) {
+            max_frames = std::max(max_frames, sh[0]); max_cout = std::max(max_cout, sh[1]); max_prod = std::max(max_prod, sh[0] * sh[1]);
+        }
+    }
+    ts->wg_max_frames = max_frames; ts->wg_max_cout = max_cout; ts->wg_max_prod = max_prod;
     const size_t Rpad = align_up(R, 64) + 64 * 64;           // every split rounds its rows up to a multiple of 64
-    ts->xt_cap = (size_t)3 * F * Rpad * 2; ts->dyt_cap = (size_t)F * Rpad * 2;
+    ts->xt_cap = max_frames * Rpad * 2; ts->dyt_cap = max_cout * Rpad * 2;
     want(&ts->xt, ts->xt_cap); want(&ts->dyt, ts->dyt_cap);
-    ts->partial_cap = (size_t)64 * 3 * F * F * 4 / 4;        // S * taps*Cin * Cout fp32 with S chosen to fit (see wgrad())
+    ts->partial_cap = (size_t)16 * max_prod * 4;               // S * taps*Cin * Cout fp32 with S chosen to fit (see wgrad())
     want((void**)&ts->partial, ts->partial_cap);
-    want((void**)&ts->part_b, (Rpad / 64) * (size_t)std::max(F, 3 * C) * 4);
+    want((void**)&ts->part_b, (Rpad / 64) * max_cout * 4);
     want((void**)&ts->red, N * (size_t)red_chunks(T) * 2 * 256 * 4);
     for (int k = 0; k < 5; ++k) want((void**)&ts->red_site[k], N * (size_t)red_chunks(T) * 2 * 256 * 4);
     ts->gsc_slots = 4 * L + 8;
@@ -565,6 +584,8 @@ int wgrad(st_engine* e, TrainState* ts, const void* x0, int c0, const void* x1, 
     const int frames = taps * cin;
     const int target_blocks = 512;        // transposed-copy path (cout = 128: final_proj): two rounds of its smaller blocks
     const int target_tn = 256;            // TN path: one block per CU
+    if ((size_t)frames > ts->wg_max_frames || (size_t)cout16 > ts->wg_max_cout || (size_t)frames * cout16 > ts->wg_max_prod)
+        return e->fail(ST_ERR_INVALID, "weight-gradient call larger than layout_train's operand table");
     if (cout16 % 256 == 0 && !(c0 & 63) && !(c1 & 63) && (!c1 || c0 % 256 == 0)) {
         // no transposed copies: the TN GEMM reads dY and X as they are (wgrad_tn.hip).  K (= items x 32-frame chunks) is split
         // into S ranges such that tiles x S fills ONE round of blocks (the kernel holds 128 KB of LDS: one block per CU) --

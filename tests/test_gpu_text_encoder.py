@@ -76,6 +76,29 @@ def test_vs_oracle_other_inputs_and_determinism(encoders, enc_sd):
         assert torch.equal(x2, x) and torch.equal(mu2, mu_x)      # bitwise repeatable
 
 
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+@pytest.mark.parametrize("n_layers,filter_channels", [(1, 384), (4, 1024)])
+def test_other_depths_and_filter_widths_vs_oracle(dt, n_layers, filter_channels):
+    """The handle accepts any n_layers in 1..16 and filter_channels % 128 == 0: one block at F = 384, whose FFN GEMMs run 128-wide
+    column tiles (not a multiple of 256), and four blocks at the default width, against the fp32 oracle at the same gates."""
+    from stabletts_amd.text_encoder import TextEncoder
+    cfg = oracle.TextEncoderConfig(n_layers=n_layers, filter_channels=filter_channels)
+    sd = oracle.make_text_encoder_state_dict(2468 + 10 * n_layers, cfg)
+    enc = TextEncoder(401, 128, 256, filter_channels, 4, n_layers, 3, 0.1, 256, operand_dtype=dt)
+    enc.load_state_dict(sd)
+    enc = enc.cuda()
+    tok, c, lens = text_inputs(3, 150, [150, 101, 7], 90 + n_layers)
+    with torch.inference_mode():
+        rx, rmu, rmask = oracle.text_encoder_forward(sd, tok, c, lens)
+    x, mu_x, mask = enc(tok.cuda(), c.cuda(), lens.cuda())
+    assert torch.equal(mask.cpu(), rmask)
+    ex, em = _rel(x.cpu().numpy(), rx.numpy()), _rel(mu_x.cpu().numpy(), rmu.numpy())
+    print(f"text encoder {dt} L={n_layers} F={filter_channels}: x {ex:.2e} (gate {TOL_X[dt]:.0e}), mu_x {em:.2e} (gate {TOL_MU[dt]:.0e})")
+    assert ex <= TOL_X[dt] and em <= TOL_MU[dt]
+    assert float(mu_x[~mask.bool().expand_as(mu_x)].abs().max()) == 0.0
+    assert float(x[~mask.bool().expand_as(x)].abs().max()) == 0.0
+
+
 def test_handle_kinds_are_not_interchangeable(encoders):
     from stabletts_amd._lib import NativeError
     eng = encoders["bf16"].engine()

@@ -164,6 +164,50 @@ def test_oracle_gradients_match_reference_fixture(sd, golden):
         assert np.abs(got - want).max() <= 2e-4 * np.abs(want).max()
 
 
+@pytest.mark.parametrize("name", ["f384_g260_l2", "f128_g4_l4"])
+def test_oracle_matches_reference_at_other_decoder_configs(name):
+    """oracle.decoder_forward, cfm_forward and compute_loss (with its autograd) vs the REAL reference at filter_channels,
+    gin_channels and n_layers other than the default (tests/golden/config_outputs.npz, oracle/make_golden_configs.py): one
+    evaluation, a 3-step Euler CFG solve, the loss, every parameter's gradient norm, a few gradients in full, d mu and d c.
+    The tolerances are those of the default-config tests above."""
+    import os
+    from oracle.make_golden_configs import B, CASES, T, case_inputs, config, state_dict
+    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "config_outputs.npz"))
+    sd = state_dict(name)
+    inp = case_inputs(name)
+    with torch.inference_mode():
+        _close(oracle.decoder_forward(sd, torch.tensor(0.4), inp["z"], inp["mask"], inp["mu"], inp["c"]), g[name + ".nfe"])
+        fs, fc = oracle.make_cfg_params(CASES[name][3] + 1000, config(name))
+        out = oracle.cfm_forward(sd, inp["mu"], inp["mask"], 3, torch.from_numpy(g[name + ".solve_z"]), inp["c"], "euler",
+                                 dict(fake_speaker=fs, fake_content=fc, cfg_strength=3.0))
+        _close(out, g[name + ".solve"], 5e-5)
+    p = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    x1 = make_inputs(B, T, seed=CASES[name][3] + 100)["z"]
+    linp = case_inputs(name, 200)
+    mu = linp["mu"].clone().requires_grad_(True)
+    c = linp["c"].clone().requires_grad_(True)
+    loss, _ = oracle.compute_loss(p, x1, linp["mask"], mu, c, torch.from_numpy(g[name + ".loss_t_rand"]),
+                                  torch.from_numpy(g[name + ".loss_z"]))
+    loss.backward()
+    want_loss = float(g[name + ".loss_value"][0])
+    assert abs(float(loss.detach()) - want_loss) <= 1e-5 * want_loss
+    names = [str(n) for n in g[name + ".names"]]
+    assert set(names) == set(sd.keys()) and len(names) == len(sd)
+    norms = g[name + ".grad_norms"]
+    scale = float(norms.max())
+    for pname, want in zip(names, norms):
+        got = float(p[pname].grad.double().norm())
+        assert abs(got - want) <= 2e-4 * want + 1e-7 * scale, pname
+    full = [k for k in g.files if k.startswith(name + ".grad.")]
+    assert len(full) >= 5
+    for key in full:
+        got, want = p[key[len(name) + 6:]].grad.numpy(), g[key]
+        assert np.abs(got - want).max() <= 2e-4 * np.abs(want).max() + 1e-9, key
+    for got, want in ((mu.grad.numpy(), g[name + ".grad_mu"]), (c.grad.numpy(), g[name + ".grad_c"])):
+        assert got.shape == want.shape
+        assert np.abs(got - want).max() <= 2e-4 * np.abs(want).max()
+
+
 def _order_conditions(b, c, A, order, theta=1.0):
     """Residuals of the Runge-Kutta order conditions up to ``order`` (<= 4) for weights b (at abscissa theta),
     nodes c and stage matrix A: a method y(t + theta h) = y + h sum b_i k_i of that order satisfies all of them."""
