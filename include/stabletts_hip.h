@@ -196,6 +196,55 @@ int st_create_vocoder(const st_vocos_config* cfg, int device, st_engine** out);
  * reference there is no mask: every utterance is vocoded at the padded length T. */
 int st_vocos_forward(st_engine* e, const float* mel, float* audio, int B, int T, void* stream);
 
+/* ---- MelStyleEncoder and DurationPredictor: stages 1 and 3 of StableTTS.synthesise (models/model.py:79-81) ------- */
+/* Both run in fp32 (fp32-input MFMA for every convolution and linear): the durations they feed are ceil()ed
+ * (model.py:83-84), so a 16-bit logw error would add or drop whole frames.  Inference only (eval mode: no dropout). */
+
+/* Replaces MelStyleEncoder.__init__ (models/reference_encoder.py:25-62) as StableTTS builds it (model.py:38). */
+typedef struct st_style_encoder_config {
+    int32_t n_mel_channels;    /* in_dim */
+    int32_t style_hidden;      /* hidden_dim; native kernels: style_head * 64 */
+    int32_t style_vector_dim;  /* out_dim = gin_channels */
+    int32_t style_kernel_size; /* Conv1dGLU kernel; native kernels: 1, 3 or 5 */
+    int32_t style_head;        /* heads of slf_attn; native kernels: head_dim style_hidden / style_head == 64 */
+} st_style_encoder_config;
+
+/* The handle takes MelStyleEncoder.state_dict() under the reference names ("spectral.0.weight", "spectral.3.bias",
+ * "temporal.<i>.conv1.weight", "slf_attn.in_proj_weight", "slf_attn.out_proj.bias", "fc.weight", ...) through
+ * st_load_param / st_finalize and is destroyed with st_destroy.  Entry points of the other kinds reject it and vice versa. */
+int st_create_style_encoder(const st_style_encoder_config* cfg, int device, st_engine** out);
+
+/* Replaces MelStyleEncoder.forward(x, x_mask) (reference_encoder.py:74-93) in eval mode.
+ *   mel   : (B, n_mel_channels, T) fp32 reference mel spectrogram
+ *   mask  : (B, 1, T) fp32 frame mask, or NULL (synthesise passes None, model.py:79).  Frames with mask == 0 are left out
+ *           of the attention keys (key_padding_mask) and of the temporal mean; like the reference, the convolutions see
+ *           them unmasked.  An item without any valid frame yields NaN in c_out, as the reference's 0 / 0 does.
+ *   c_out : (B, style_vector_dim) fp32 style vectors                                  -- all device pointers
+ * Enqueued on `stream`; the host is not synchronised. */
+int st_style_encoder_forward(st_engine* e, const float* mel, const float* mask, float* c_out, int B, int T, void* stream);
+
+/* Replaces DurationPredictor.__init__ (models/duration_predictor.py:6-22) as StableTTS builds it (model.py:39). */
+typedef struct st_duration_predictor_config {
+    int32_t in_channels;       /* hidden_channels of the text encoder */
+    int32_t filter_channels;   /* native kernels: a multiple of 128 */
+    int32_t kernel_size;       /* native kernels: 1, 3 or 5 */
+    int32_t gin_channels;      /* width of g */
+} st_duration_predictor_config;
+
+/* The handle takes DurationPredictor.state_dict() under the reference names ("conv1.weight", "norm1.weight", "conv2.bias",
+ * "norm2.bias", "proj.weight", "cond.weight", "cond.bias", ...) through st_load_param / st_finalize and is destroyed with
+ * st_destroy.  Entry points of the other kinds reject it and vice versa. */
+int st_create_duration_predictor(const st_duration_predictor_config* cfg, int device, st_engine** out);
+
+/* Replaces DurationPredictor.forward(x, x_mask, g) (duration_predictor.py:24-37) in eval mode.
+ *   x        : (B, in_channels, Tx) fp32 text-encoder states (st_text_encoder_forward's x_out)
+ *   x_mask   : (B, 1, Tx) fp32 token mask (st_text_encoder_forward's mask_out); multiplied in where the reference does
+ *   g        : (B, gin_channels) fp32 speaker vectors (st_style_encoder_forward's c_out)
+ *   logw_out : (B, 1, Tx) fp32 log-durations, exactly 0 where x_mask is 0              -- all device pointers
+ * Enqueued on `stream`; the host is not synchronised. */
+int st_duration_predictor_forward(st_engine* e, const float* x, const float* x_mask, const float* g, float* logw_out,
+                                  int B, int Tx, void* stream);
+
 /* ---- training: autograd counterpart of Decoder.forward ------------------------------------------- */
 
 /* Replaces Decoder.forward(t, x, mask, mu, c) UNDER AUTOGRAD as CFMDecoder.compute_loss calls it (models/flow_matching.py:99,

@@ -7,16 +7,19 @@ Public surface mirrors the reference's ``models/flow_matching.py``:
 ``install()`` registers that module as ``models.flow_matching`` so the reference's
 ``models/model.py:7`` (``from models.flow_matching import CFMDecoder``) picks it up unmodified;
 ``install(text_encoder=True)`` also registers ``stabletts_amd.text_encoder`` as ``models.text_encoder``
-(``models/model.py:6``), the caller side of the path on the same block kernels.
+(``models/model.py:6``), the caller side of the path on the same block kernels;
+``install(reference_encoder=True, duration_predictor=True)`` registers the fp32 ``MelStyleEncoder`` /
+``DurationPredictor`` as ``models.reference_encoder`` / ``models.duration_predictor`` (``models/model.py:8-9``).
 """
 import sys
 
-__all__ = ["install", "CFMDecoder", "TextEncoder"]
+__all__ = ["install", "CFMDecoder", "TextEncoder", "MelStyleEncoder", "DurationPredictor"]
 
 
-def install(text_encoder=False, vocoder=False):
-    """Make ``models.flow_matching`` (and optionally ``models.text_encoder`` / ``vocoders.vocos.models.model``)
-    resolve to the native drop-ins (call before importing models.model / api.get_vocoder)."""
+def install(text_encoder=False, vocoder=False, reference_encoder=False, duration_predictor=False):
+    """Make ``models.flow_matching`` (and optionally ``models.text_encoder`` / ``vocoders.vocos.models.model`` /
+    ``models.reference_encoder`` / ``models.duration_predictor``) resolve to the native drop-ins (call before importing
+    models.model / api.get_vocoder)."""
     from . import flow_matching
     sys.modules["models.flow_matching"] = flow_matching
     if text_encoder:
@@ -25,6 +28,12 @@ def install(text_encoder=False, vocoder=False):
     if vocoder:
         from . import vocos
         sys.modules["vocoders.vocos.models.model"] = vocos      # api.py:26-28: from vocoders.vocos.models.model import Vocos
+    if reference_encoder:
+        from . import reference_encoder as re_
+        sys.modules["models.reference_encoder"] = re_            # models/model.py:8
+    if duration_predictor:
+        from . import duration_predictor as dp
+        sys.modules["models.duration_predictor"] = dp            # models/model.py:9
     return flow_matching
 
 
@@ -38,4 +47,10 @@ def __getattr__(name):
     if name == "TextEncoder":
         from .text_encoder import TextEncoder
         return TextEncoder
+    if name == "MelStyleEncoder":
+        from .reference_encoder import MelStyleEncoder
+        return MelStyleEncoder
+    if name == "DurationPredictor":
+        from .duration_predictor import DurationPredictor
+        return DurationPredictor
     raise AttributeError(name)

@@ -32,6 +32,7 @@ EXPORTS = [
     "st_durations", "st_generate_path", "st_align", "st_create_vocoder", "st_vocos_forward",
     "st_cfm_loss_prep", "st_cfm_loss", "st_cfm_loss_backward", "st_cfm_loss_scratch_floats",
     "st_set_option", "st_get_option", "st_attention_stats",
+    "st_create_style_encoder", "st_style_encoder_forward", "st_create_duration_predictor", "st_duration_predictor_forward",
 ]
 
 
@@ -44,6 +45,15 @@ class StConfig(ctypes.Structure):
 class StVocosConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in (
         "input_channels", "dim", "intermediate_dim", "num_layers", "n_fft", "hop_length", "operand_dtype")]
+
+
+class StStyleEncoderConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "n_mel_channels", "style_hidden", "style_vector_dim", "style_kernel_size", "style_head")]
+
+
+class StDurationPredictorConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("in_channels", "filter_channels", "kernel_size", "gin_channels")]
 
 
 class NativeError(RuntimeError):
@@ -167,6 +177,14 @@ def load():
     lib.st_get_option.restype = c_int
     lib.st_attention_stats.argtypes = [c_void_p, c_void_p, ctypes.POINTER(c_float)]
     lib.st_attention_stats.restype = c_int
+    lib.st_create_style_encoder.argtypes = [ctypes.POINTER(StStyleEncoderConfig), c_int, ctypes.POINTER(c_void_p)]
+    lib.st_create_style_encoder.restype = c_int
+    lib.st_style_encoder_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]
+    lib.st_style_encoder_forward.restype = c_int
+    lib.st_create_duration_predictor.argtypes = [ctypes.POINTER(StDurationPredictorConfig), c_int, ctypes.POINTER(c_void_p)]
+    lib.st_create_duration_predictor.restype = c_int
+    lib.st_duration_predictor_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]
+    lib.st_duration_predictor_forward.restype = c_int
     if lib.st_abi_version() != 4:
         raise ImportError("libstabletts_hip.so ABI version mismatch; rebuild it")
     _lib = lib
@@ -177,11 +195,15 @@ class Engine:
     """Thin owner of one ``st_engine`` handle."""
 
     def __init__(self, noise_channels, hidden_channels, filter_channels, n_heads, n_layers, kernel_size,
-                 gin_channels, operand_dtype="f16", device=0, text_encoder_vocab=None, vocoder=None):
+                 gin_channels, operand_dtype="f16", device=0, text_encoder_vocab=None, vocoder=None,
+                 style_encoder=None, duration_predictor=None):
         """text_encoder_vocab: None -> CFM decoder estimator (st_create); n_vocab -> TextEncoder handle
         (st_create_text_encoder; noise_channels is then the encoder's out_channels).
         vocoder: dict(input_channels, dim, intermediate_dim, num_layers, n_fft, hop_length) -> Vocos handle
-        (st_create_vocoder; the decoder arguments are ignored)."""
+        (st_create_vocoder; the decoder arguments are ignored).
+        style_encoder: dict(n_mel_channels, style_hidden, style_vector_dim, style_kernel_size, style_head) -> MelStyleEncoder
+        handle (st_create_style_encoder); duration_predictor: dict(in_channels, filter_channels, kernel_size, gin_channels)
+        -> DurationPredictor handle (st_create_duration_predictor).  Both fp32: the decoder arguments are ignored."""
         self.lib = load()
         if operand_dtype not in OPERAND_DTYPES:
             raise ValueError(f"operand_dtype must be one of {sorted(OPERAND_DTYPES)}")
@@ -189,7 +211,13 @@ class Engine:
         cfg = StConfig(noise_channels, hidden_channels, filter_channels, n_heads, n_layers, kernel_size,
                        gin_channels, OPERAND_DTYPES[operand_dtype])
         h = ctypes.c_void_p()
-        if vocoder is not None:
+        if style_encoder is not None:
+            sc = StStyleEncoderConfig(*(int(style_encoder[n]) for n, _ in StStyleEncoderConfig._fields_))
+            rc = self.lib.st_create_style_encoder(ctypes.byref(sc), int(device), ctypes.byref(h))
+        elif duration_predictor is not None:
+            dc = StDurationPredictorConfig(*(int(duration_predictor[n]) for n, _ in StDurationPredictorConfig._fields_))
+            rc = self.lib.st_create_duration_predictor(ctypes.byref(dc), int(device), ctypes.byref(h))
+        elif vocoder is not None:
             vc = StVocosConfig(vocoder["input_channels"], vocoder["dim"], vocoder["intermediate_dim"], vocoder["num_layers"],
                                vocoder["n_fft"], vocoder["hop_length"], OPERAND_DTYPES[operand_dtype])
             rc = self.lib.st_create_vocoder(ctypes.byref(vc), int(device), ctypes.byref(h))
@@ -276,6 +304,16 @@ class Engine:
     def vocos_forward(self, mel, audio, stream):
         B, _, T = mel.shape
         self._check(self.lib.st_vocos_forward(self.handle, mel.data_ptr(), audio.data_ptr(), B, T, ctypes.c_void_p(stream)))
+
+    def style_encoder_forward(self, mel, mask, c_out, stream):
+        B, _, T = mel.shape
+        self._check(self.lib.st_style_encoder_forward(self.handle, mel.data_ptr(), mask.data_ptr() if mask is not None else None,
+                                                      c_out.data_ptr(), B, T, ctypes.c_void_p(stream)))
+
+    def duration_predictor_forward(self, x, x_mask, g, logw_out, stream):
+        B, _, T = x.shape
+        self._check(self.lib.st_duration_predictor_forward(self.handle, x.data_ptr(), x_mask.data_ptr(), g.data_ptr(),
+                                                           logw_out.data_ptr(), B, T, ctypes.c_void_p(stream)))
 
     # ---- training: forward that keeps activations + backward (include/stabletts_hip.h, "training")
     def train_forward(self, t, x, mu, mask, c, out, p_dropout, seed, stream):

@@ -39,6 +39,8 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct TrainState;     // engine_train.cpp
 struct VocosState;     // engine_vocos.cpp
+struct StyleState;     // engine_style.cpp
+struct DurState;       // engine_duration.cpp
 
 }  // namespace sthost
 
@@ -51,7 +53,8 @@ struct st_engine {
     int device = 0;
     int dt = st::DT_BF16;
     int M = 0, Mp = 0, C = 0, F = 0, H = 0, L = 0, K = 0, G = 0;
-    int kind = 0;                       // 0: CFM decoder estimator, 1: TextEncoder (same DiT block kernels), 2: Vocos vocoder
+    int kind = 0;                       // 0: CFM decoder estimator, 1: TextEncoder (same DiT block kernels), 2: Vocos vocoder,
+                                        // 3: MelStyleEncoder, 4: DurationPredictor (fp32 kernels reading the loaded parameters in place)
     int n_vocab = 0;
     // parameter-name prefix of DiT block i: estimator.py:13,79 "blocks.i.block." / text_encoder.py:25 "encoder.i."
     std::string blk(int i) const {
@@ -148,6 +151,8 @@ struct st_engine {
     // training (engine_train.cpp): transposed dgrad weights, saved activations, gradient buffers
     sthost::TrainState* train = nullptr;
     sthost::VocosState* voc = nullptr;  // kind == 2 (engine_vocos.cpp)
+    sthost::StyleState* sty = nullptr;  // kind == 3 (engine_style.cpp)
+    sthost::DurState* dur = nullptr;    // kind == 4 (engine_duration.cpp)
 
     int fail(int code, const std::string& msg) { err = msg; return code; }
 };
@@ -190,6 +195,8 @@ int pk_weight_t(st_engine* e, st_engine::PackList& L, const float* src, int cout
                 int cin_p, int ld, int col_off, hipStream_t s);
 int pk_copy(st_engine* e, st_engine::PackList& L, float* dst, const float* src, int n, hipStream_t s);            // (re)packs every 16-bit weight; allocates on the first call only
 void vocos_destroy(st_engine* e);
+void style_destroy(st_engine* e);
+void duration_destroy(st_engine* e);
 
 // HIP-event bracket around the launches of one kernel class (st_profile_*)
 struct ProfScope {

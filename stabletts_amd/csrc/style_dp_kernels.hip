@@ -1,0 +1,229 @@
+// MelStyleEncoder and DurationPredictor kernels (models/reference_encoder.py:22-93, models/duration_predictor.py:5-37).
+// fp32 throughout: the durations downstream are ceil()ed (models/model.py:83-84), so a logw error of 1e-3 already flips about
+// one frame per 200-token utterance; the convolutions and linears therefore run on the fp32-input MFMA
+// (v_mfma_f32_32x32x2_f32: bit-for-bit a k-ordered fp32 FMA chain) instead of the 16-bit operands of the DiT blocks.
+// Tensors stay in the reference's channel-major layout (B, C, T); both modules run once per utterance and are small.
+#include "style_dp_launch.h"
+
+#include <math.h>
+
+namespace st {
+
+typedef __attribute__((ext_vector_type(16))) float sd_f32x16;
+
+constexpr int kSdTileCo = 64, kSdTileT = 64, kSdChunk = 16;     // output tile 64 channels x 64 frames, 16 input channels per K step
+
+// One block = 4 waves = a 64 x 64 output tile; wave w owns the 32 x 32 sub-tile (channels 32 (w & 1), frames 32 (w >> 1)).
+// K = (input channel, tap) pairs in the weight's own order, 16 channels x TAPS per LDS chunk; MFMA 32x32x2 f32 operands:
+// lane l holds A[i = l & 31][k = l >> 5] (weight row) and B[k = l >> 5][j = l & 31] (input frame); D: row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31.
+template <int TAPS>
+__global__ __launch_bounds__(256) void sd_conv_kernel(SdConvArgs a) {
+    constexpr int KC = kSdChunk * TAPS, WS = KC + 1, PAD = TAPS / 2, XS = kSdTileT + TAPS - 1;
+    __shared__ float Ws[kSdTileCo * WS];
+    __shared__ float Xs[kSdChunk * XS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 31, h = lane >> 5, wco = wave & 1, wt = wave >> 1;
+    const int t0 = blockIdx.x * kSdTileT, co0 = blockIdx.y * kSdTileCo, b = blockIdx.z;
+    const int Cin = a.Cin, Cout = a.Cout, T = a.T;
+    const float* inb = a.in + (size_t)b * Cin * T;
+    sd_f32x16 acc;
+    for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
+    for (int ci0 = 0; ci0 < Cin; ci0 += kSdChunk) {
+        for (int i = tid; i < kSdTileCo * KC; i += 256) {
+            const int row = i / KC, kk = i - row * KC;
+            const int co = co0 + row, ci = ci0 + kk / TAPS;
+            Ws[row * WS + kk] = (co < Cout && ci < Cin) ? a.w[((size_t)co * Cin + ci0) * TAPS + kk] : 0.0f;
+        }
+        for (int i = tid; i < kSdChunk * XS; i += 256) {
+            const int row = i / XS, j = i - row * XS;
+            const int ci = ci0 + row, t = t0 + j - PAD;
+            float v = 0.0f;
+            if (ci < Cin && t >= 0 && t < T) {
+                v = inb[(size_t)ci * T + t];
+                if (a.addv) v += a.addv[(size_t)b * Cin + ci];
+                if (a.imask) v *= a.imask[(size_t)b * T + t];
+            }
+            Xs[row * XS + j] = v;
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int kk = 0; kk < KC; kk += 2) {
+            const int k = kk + h, cil = k / TAPS, tap = k - cil * TAPS;
+            const float av = Ws[(wco * 32 + r) * WS + k];
+            const float bv = Xs[cil * XS + wt * 32 + r + tap];
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    const int t = t0 + wt * 32 + r;
+    if (t >= T) return;
+    const float om = a.omask ? a.omask[(size_t)b * T + t] : 1.0f;
+    for (int i = 0; i < 16; ++i) {
+        const int co = co0 + wco * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+        if (co >= Cout) continue;
+        float v = acc[i] + a.bias[co];
+        if (a.epi == SD_EPI_MISH) {          // x * tanh(softplus(x)), softplus at torch's threshold 20
+            const float sp = v > 20.0f ? v : log1pf(expf(v));
+            v = v * tanhf(sp);
+        } else if (a.epi == SD_EPI_RELU) {
+            v = fmaxf(v, 0.0f);
+        }
+        a.out[((size_t)b * Cout + co) * T + t] = v * om;
+    }
+}
+
+hipError_t launch_sd_conv(const SdConvArgs& a, hipStream_t s) {
+    if (a.B < 1 || a.T < 1 || a.Cin < 1 || a.Cout < 1 || !a.in || !a.w || !a.bias || !a.out) return hipErrorInvalidValue;
+    const dim3 grid((a.T + kSdTileT - 1) / kSdTileT, (a.Cout + kSdTileCo - 1) / kSdTileCo, a.B), blk(256);
+    switch (a.taps) {
+        case 1: hipLaunchKernelGGL(sd_conv_kernel<1>, grid, blk, 0, s, a); break;
+        case 3: hipLaunchKernelGGL(sd_conv_kernel<3>, grid, blk, 0, s, a); break;
+        case 5: hipLaunchKernelGGL(sd_conv_kernel<5>, grid, blk, 0, s, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void sd_glu_residual_kernel(float* __restrict__ h, const float* __restrict__ u, int C, int T, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t per = (int64_t)C * T;
+        const int64_t b = i / per, rem = i - b * per;          // rem = c * T + t
+        const float* ub = u + b * 2 * per;
+        const float val = ub[rem], gate = ub[per + rem];
+        h[i] = h[i] + val * (1.0f / (1.0f + expf(-gate)));
+    }
+}
+
+hipError_t launch_sd_glu_residual(float* h, const float* u, int B, int C, int T, hipStream_t s) {
+    const int64_t n = (int64_t)B * C * T;
+    const int64_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(sd_glu_residual_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, h, u, C, T, n);
+    return hipGetLastError();
+}
+
+// One block = 64 frames of one item; 4 threads per frame split the channels, partial sums meet in LDS.  Two passes
+// (mean, then the mean squared deviation: nn.LayerNorm's biased variance), then the affine write.
+__global__ __launch_bounds__(256) void sd_layernorm_channels_kernel(float* __restrict__ x, const float* __restrict__ w,
+                                                                    const float* __restrict__ bb, float eps, int C, int T) {
+    __shared__ float red[4][64];
+    const int tl = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const int t = blockIdx.x * 64 + tl, b = blockIdx.y;
+    const bool ok = t < T;
+    float* xb = x + (size_t)b * C * T;
+    float sum = 0.0f;
+    if (ok) for (int c = g; c < C; c += 4) sum += xb[(size_t)c * T + t];
+    red[g][tl] = sum;
+    __syncthreads();
+    const float mean = (red[0][tl] + red[1][tl] + red[2][tl] + red[3][tl]) / (float)C;
+    __syncthreads();
+    float sq = 0.0f;
+    if (ok) for (int c = g; c < C; c += 4) { const float d = xb[(size_t)c * T + t] - mean; sq += d * d; }
+    red[g][tl] = sq;
+    __syncthreads();
+    const float var = (red[0][tl] + red[1][tl] + red[2][tl] + red[3][tl]) / (float)C;
+    const float rstd = 1.0f / sqrtf(var + eps);
+    if (ok) for (int c = g; c < C; c += 4) {
+        const size_t i = (size_t)c * T + t;
+        xb[i] = (xb[i] - mean) * rstd * w[c] + bb[c];
+    }
+}
+
+hipError_t launch_sd_layernorm_channels(float* x, const float* w, const float* b, float eps, int B, int C, int T, hipStream_t s) {
+    hipLaunchKernelGGL(sd_layernorm_channels_kernel, dim3((T + 63) / 64, B), dim3(256), 0, s, x, w, b, eps, C, T);
+    return hipGetLastError();
+}
+
+// One wave = 64 queries of one (item, head), one query per lane: q and the output accumulator (64 + 64 fp32) live in
+// registers, keys and values stream through LDS 64 frames at a time (every lane reads the same element: broadcast).
+// Softmax is the online form, rescaled once per key tile; exact expf.  Masked keys get a score of -inf and weight 0.
+__global__ __launch_bounds__(64) void sd_attention_kernel(const float* __restrict__ qkv, const float* __restrict__ kmask,
+                                                          float* __restrict__ out, int H, int T) {
+    __shared__ float Ks[64 * 64];
+    __shared__ float Vs[64 * 64];
+    __shared__ float valid[64];
+    const int lane = threadIdx.x, hd = blockIdx.y, b = blockIdx.z;
+    const int tq = blockIdx.x * 64 + lane, D = H * 64;
+    const float* qb = qkv + ((size_t)b * 3 * D + hd * 64) * T;
+    const float* kb = qb + (size_t)D * T;
+    const float* vb = qb + (size_t)2 * D * T;
+    float q[64], acc[64];
+#pragma unroll
+    for (int d = 0; d < 64; ++d) { q[d] = tq < T ? qb[(size_t)d * T + tq] * 0.125f : 0.0f; acc[d] = 0.0f; }
+    float m = -INFINITY, l = 0.0f;
+    for (int k0 = 0; k0 < T; k0 += 64) {
+        const int tk = k0 + lane;
+        const bool kv = tk < T && (!kmask || kmask[(size_t)b * T + tk] != 0.0f);
+        for (int d = 0; d < 64; ++d) {
+            Ks[d * 64 + lane] = tk < T ? kb[(size_t)d * T + tk] : 0.0f;
+            Vs[d * 64 + lane] = tk < T ? vb[(size_t)d * T + tk] : 0.0f;
+        }
+        valid[lane] = kv ? 1.0f : 0.0f;
+        __syncthreads();
+        float sc[64];
+        float mt = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < 64; ++j) {
+            float s = 0.0f;
+#pragma unroll
+            for (int d = 0; d < 64; ++d) s = fmaf(q[d], Ks[d * 64 + j], s);
+            sc[j] = valid[j] != 0.0f ? s : -INFINITY;
+            mt = fmaxf(mt, sc[j]);
+        }
+        const float mn = fmaxf(m, mt);
+        if (mn != -INFINITY) {
+            const float corr = expf(m - mn);          // m == -inf: 0 (acc and l are 0 then)
+            l *= corr;
+#pragma unroll
+            for (int d = 0; d < 64; ++d) acc[d] *= corr;
+#pragma unroll
+            for (int j = 0; j < 64; ++j) {
+                const float p = expf(sc[j] - mn);     // masked: exp(-inf) = 0
+                l += p;
+#pragma unroll
+                for (int d = 0; d < 64; ++d) acc[d] = fmaf(p, Vs[d * 64 + j], acc[d]);
+            }
+            m = mn;
+        }
+        __syncthreads();
+    }
+    if (tq >= T) return;
+    const float inv = l > 0.0f ? 1.0f / l : 0.0f;
+    float* ob = out + ((size_t)b * D + hd * 64) * T + tq;
+#pragma unroll
+    for (int d = 0; d < 64; ++d) ob[(size_t)d * T] = acc[d] * inv;
+}
+
+hipError_t launch_sd_attention(const float* qkv, const float* kmask, float* out, int B, int H, int T, hipStream_t s) {
+    hipLaunchKernelGGL(sd_attention_kernel, dim3((T + 63) / 64, H, B), dim3(64), 0, s, qkv, kmask, out, H, T);
+    return hipGetLastError();
+}
+
+// One block = one (item, channel) row: the 256 lanes stride over the frames (coalesced loads), partial sums and valid-frame
+// counts meet in a fixed LDS tree (deterministic).
+__global__ __launch_bounds__(256) void sd_mean_pool_kernel(const float* __restrict__ x, const float* __restrict__ mask,
+                                                           float* __restrict__ c, int O, int T) {
+    __shared__ float ssum[256], scnt[256];
+    const int o = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const float* xo = x + ((size_t)b * O + o) * T;
+    const float* mb = mask ? mask + (size_t)b * T : nullptr;
+    float sum = 0.0f, n = 0.0f;
+    for (int t = tid; t < T; t += 256) {
+        if (mb && mb[t] == 0.0f) continue;
+        sum += xo[t];
+        n += 1.0f;
+    }
+    ssum[tid] = sum; scnt[tid] = n;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) { ssum[tid] += ssum[tid + w]; scnt[tid] += scnt[tid + w]; }
+        __syncthreads();
+    }
+    if (tid == 0) c[(size_t)b * O + o] = scnt[0] > 0.0f ? ssum[0] / scnt[0] : __builtin_nanf("");
+}
+
+hipError_t launch_sd_mean_pool(const float* x, const float* mask, float* c, int B, int O, int T, hipStream_t s) {
+    hipLaunchKernelGGL(sd_mean_pool_kernel, dim3(O, B), dim3(256), 0, s, x, mask, c, O, T);
+    return hipGetLastError();
+}
+
+}  // namespace st
