@@ -160,6 +160,27 @@ int st_generate_path(const float* duration, const float* mask, int B, int Tx, in
 int st_align(const float* cum, const float* x_mask, const int64_t* y_lengths, const float* mu_x, int B, int M, int Tx, int Ty,
              float* attn, float* mu_y, float* y_mask, void* stream);
 
+/* ---- monotonic alignment search of training (models/model.py:148-158), stateless like the alignment helpers above ------ */
+
+/* Replaces monotonic_align.maximum_path (monotonic_align/core.py:14-46) without the host round trip: bit-exact for every
+ * item with t_x >= 1 and t_y >= 1 (t_x > t_y included).
+ *   neg_cent  : (B, Ty, Tx) fp32, rows = mel frames; read only.
+ *   t_y, t_x  : (B) int32, the reference's mask.sum(1)[:, 0] and mask.sum(2)[:, 0] truncated (clamped to [0, Ty] / [0, Tx]).
+ *   path      : (B, Ty, Tx) fp32 0/1, every cell written; an item with t_x == 0 or t_y == 0 gets an all-zero path (the
+ *               reference writes the last column through a negative index there; models/model.py never makes that case).
+ *   durations : (B, Tx) int32 frames per token (= path.sum(1)), or NULL.
+ *   workspace : st_maximum_path_workspace_bytes(B, Ty, Tx) bytes of device memory, NULL when that is 0.
+ * Tx <= 4096 (one wave holds a row in registers); a wider Tx returns ST_ERR_UNSUPPORTED before any launch.  Any Ty. */
+int st_maximum_path(const float* neg_cent, const int32_t* t_y, const int32_t* t_x, int B, int Ty, int Tx, float* path,
+                    int32_t* durations, void* workspace, void* stream);
+/* 0 when each utterance's decision bits (Ty x ceil(Tx / 64) x 8 bytes) fit the kernel's LDS budget (64 KiB). */
+int64_t st_maximum_path_workspace_bytes(int B, int Ty, int Tx);
+
+/* models/model.py:150-155 with s_p_sq_r = 1, all four terms:
+ * neg_cent[b][t][s] = D (-1/2 log 2 pi) - 1/2 sum_d y[b][d][t]^2 + sum_d y[b][d][t] mu_x[b][d][s] - 1/2 sum_d mu_x[b][d][s]^2
+ *   mu_x (B, D, Tx), y (B, D, Ty) fp32 -> neg_cent (B, Ty, Tx) fp32 (the cross term on the fp32-input MFMA). */
+int st_mas_neg_cent(const float* mu_x, const float* y, int B, int D, int Tx, int Ty, float* neg_cent, void* stream);
+
 /* ---- CFMDecoder.compute_loss's own arithmetic (models/flow_matching.py:86-100), stateless like the alignment helpers ------
  * st_cfm_loss_prep: t = 1 - cos(t_rand pi / 2) (:88), y = (1 - (1 - sigma) t) z + t x1 (:93), u = x1 - (1 - sigma) z (:96).
  *   x1, z, y, u: (B, M, T); t_rand, t: (B).

@@ -9,17 +9,19 @@ Public surface mirrors the reference's ``models/flow_matching.py``:
 ``install(text_encoder=True)`` also registers ``stabletts_amd.text_encoder`` as ``models.text_encoder``
 (``models/model.py:6``), the caller side of the path on the same block kernels;
 ``install(reference_encoder=True, duration_predictor=True)`` registers the fp32 ``MelStyleEncoder`` /
-``DurationPredictor`` as ``models.reference_encoder`` / ``models.duration_predictor`` (``models/model.py:8-9``).
+``DurationPredictor`` as ``models.reference_encoder`` / ``models.duration_predictor`` (``models/model.py:8-9``);
+``install(monotonic_align=True)`` registers ``stabletts_amd.monotonic_align`` as ``monotonic_align`` (``models/model.py:5``),
+so the reference's training ``forward`` imports and runs its alignment search on the device, without numba.
 """
 import sys
 
-__all__ = ["install", "CFMDecoder", "TextEncoder", "MelStyleEncoder", "DurationPredictor"]
+__all__ = ["install", "CFMDecoder", "TextEncoder", "MelStyleEncoder", "DurationPredictor", "maximum_path"]
 
 
-def install(text_encoder=False, vocoder=False, reference_encoder=False, duration_predictor=False):
+def install(text_encoder=False, vocoder=False, reference_encoder=False, duration_predictor=False, monotonic_align=False):
     """Make ``models.flow_matching`` (and optionally ``models.text_encoder`` / ``vocoders.vocos.models.model`` /
-    ``models.reference_encoder`` / ``models.duration_predictor``) resolve to the native drop-ins (call before importing
-    models.model / api.get_vocoder)."""
+    ``models.reference_encoder`` / ``models.duration_predictor`` / ``monotonic_align``) resolve to the native drop-ins
+    (call before importing models.model / api.get_vocoder)."""
     from . import flow_matching
     sys.modules["models.flow_matching"] = flow_matching
     if text_encoder:
@@ -34,6 +36,9 @@ def install(text_encoder=False, vocoder=False, reference_encoder=False, duration
     if duration_predictor:
         from . import duration_predictor as dp
         sys.modules["models.duration_predictor"] = dp            # models/model.py:9
+    if monotonic_align:
+        from . import monotonic_align as ma
+        sys.modules["monotonic_align"] = ma                      # models/model.py:5
     return flow_matching
 
 
@@ -53,4 +58,7 @@ def __getattr__(name):
     if name == "DurationPredictor":
         from .duration_predictor import DurationPredictor
         return DurationPredictor
+    if name == "maximum_path":
+        from .monotonic_align import maximum_path
+        return maximum_path
     raise AttributeError(name)

@@ -33,6 +33,7 @@ EXPORTS = [
     "st_cfm_loss_prep", "st_cfm_loss", "st_cfm_loss_backward", "st_cfm_loss_scratch_floats",
     "st_set_option", "st_get_option", "st_attention_stats",
     "st_create_style_encoder", "st_style_encoder_forward", "st_create_duration_predictor", "st_duration_predictor_forward",
+    "st_maximum_path", "st_maximum_path_workspace_bytes", "st_mas_neg_cent",
 ]
 
 
@@ -185,6 +186,12 @@ def load():
     lib.st_create_duration_predictor.restype = c_int
     lib.st_duration_predictor_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]
     lib.st_duration_predictor_forward.restype = c_int
+    lib.st_maximum_path.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.st_maximum_path.restype = c_int
+    lib.st_maximum_path_workspace_bytes.argtypes = [c_int, c_int, c_int]
+    lib.st_maximum_path_workspace_bytes.restype = ctypes.c_int64
+    lib.st_mas_neg_cent.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
+    lib.st_mas_neg_cent.restype = c_int
     if lib.st_abi_version() != 4:
         raise ImportError("libstabletts_hip.so ABI version mismatch; rebuild it")
     _lib = lib

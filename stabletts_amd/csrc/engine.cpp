@@ -2,6 +2,7 @@
 // the C ABI of include/stabletts_hip.h (the ODE solve around it: engine_solve.cpp).  Reference path: models/estimator.py:103-138.
 #include "engine_internal.h"
 #include "train_launch.h"
+#include "mas_launch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1048,6 +1049,29 @@ int st_align(const float* cum, const float* x_mask, const int64_t* y_lengths, co
     if (B < 1 || M < 1 || Tx < 1 || Ty < 1 || B > 65535) return align_fail(ST_ERR_INVALID, "shape out of range");
     if (launch_align(cum, x_mask, (const long long*)y_lengths, mu_x, B, M, Tx, Ty, attn, mu_y, y_mask, (hipStream_t)stream) != hipSuccess)
         return align_fail(ST_ERR_HIP, "align kernel launch failed");
+    return ST_OK;
+}
+
+// ---- monotonic alignment search: stateless helpers (errors through st_last_error(NULL))
+int64_t st_maximum_path_workspace_bytes(int B, int Ty, int Tx) { return (int64_t)mas_workspace_bytes(B, Ty, Tx); }
+
+int st_maximum_path(const float* neg_cent, const int32_t* t_y, const int32_t* t_x, int B, int Ty, int Tx, float* path,
+                    int32_t* durations, void* workspace, void* stream) {
+    if (!neg_cent || !t_y || !t_x || !path) return align_fail(ST_ERR_INVALID, "null tensor pointer");
+    if (B < 1 || Ty < 1 || Tx < 1 || B > 65535) return align_fail(ST_ERR_INVALID, "shape out of range");
+    if (Tx > kMasMaxTx) return align_fail(ST_ERR_UNSUPPORTED, "maximum_path supports Tx <= 4096 (one row per wave in registers)");
+    if (mas_workspace_bytes(B, Ty, Tx) && !workspace)
+        return align_fail(ST_ERR_INVALID, "this shape needs st_maximum_path_workspace_bytes() of workspace");
+    if (launch_mas_path(neg_cent, t_y, t_x, B, Ty, Tx, path, durations, workspace, (hipStream_t)stream) != hipSuccess)
+        return align_fail(ST_ERR_HIP, "maximum_path kernel launch failed");
+    return ST_OK;
+}
+
+int st_mas_neg_cent(const float* mu_x, const float* y, int B, int D, int Tx, int Ty, float* neg_cent, void* stream) {
+    if (!mu_x || !y || !neg_cent) return align_fail(ST_ERR_INVALID, "null tensor pointer");
+    if (B < 1 || D < 1 || Tx < 1 || Ty < 1 || B > 65535 || (Ty + 63) / 64 > 65535) return align_fail(ST_ERR_INVALID, "shape out of range");
+    if (launch_mas_neg_cent(mu_x, y, B, D, Tx, Ty, neg_cent, (hipStream_t)stream) != hipSuccess)
+        return align_fail(ST_ERR_HIP, "neg_cent kernel launch failed");
     return ST_OK;
 }
 
