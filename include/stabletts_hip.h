@@ -214,7 +214,9 @@ int st_create_vocoder(const st_vocos_config* cfg, int device, st_engine** out);
 
 /* Replaces Vocos.forward(x) (model.py:17-20) = ISTFTHead(VocosBackbone(x)) (backbone.py:50-56, head.py:93-117 with
  * padding="same"):  mel (B, input_channels, T) fp32 -> audio (B, T * hop_length) fp32, device pointers.  Like the
- * reference there is no mask: every utterance is vocoded at the padded length T. */
+ * reference there is no mask: every utterance is vocoded at the padded length T.  Large batches run in chunks of whole
+ * utterances (32-bit row offsets inside the GEMMs, the device's grid-y limit); only a T that exceeds the row bound on its
+ * own is rejected (ST_ERR_INVALID), as is a batch that needs more than one chunk while debug capture is on. */
 int st_vocos_forward(st_engine* e, const float* mel, float* audio, int B, int T, void* stream);
 
 /* ---- MelStyleEncoder and DurationPredictor: stages 1 and 3 of StableTTS.synthesise (models/model.py:79-81) ------- */

@@ -20,6 +20,14 @@ class VocosConfig:
     hop_length = 512
 
 
+def vocos_config(**fields):
+    """VocosConfig with some fields replaced, e.g. ``vocos_config(input_channels=64, num_layers=3)``."""
+    unknown = set(fields) - set(vars(VocosConfig))
+    if unknown:
+        raise ValueError(f"not VocosConfig fields: {sorted(unknown)}")
+    return type("VocosConfig", (VocosConfig,), dict(fields))
+
+
 def make_vocos_state_dict(seed, cfg=VocosConfig, dtype=np.float32):
     """Seeded, non-degenerate stand-in for a trained checkpoint, keyed like ``Vocos.state_dict()`` (model.py:11-15):
     every LayerNorm has non-trivial affine parameters, layer scales vary per channel, biases are non-zero."""

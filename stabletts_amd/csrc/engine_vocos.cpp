@@ -6,6 +6,7 @@
 #include "engine_internal.h"
 #include "vocos_launch.h"
 
+#include <algorithm>
 #include <cstring>
 #include <string>
 
@@ -134,19 +135,14 @@ int st_create_vocoder(const st_vocos_config* cfg, int device, st_engine** out) {
     return ST_OK;
 }
 
-int st_vocos_forward(st_engine* e, const float* mel, float* audio, int B, int T, void* stream) {
-    if (!e) return ST_ERR_INVALID;
-    if (e->kind != 2) return e->fail(ST_ERR_STATE, "this handle is not a vocoder (st_create_vocoder)");
-    if (!e->finalized) return e->fail(ST_ERR_STATE, "st_finalize() has not been called after loading parameters");
-    if (!mel || !audio) return e->fail(ST_ERR_INVALID, "null tensor pointer");
-    if (B < 1 || T < 1) return e->fail(ST_ERR_INVALID, "B and T must be >= 1");
+// One chunk of whole utterances: every GEMM runs over its R = B * T flattened rows.  The K loop of the conv GEMM forms an
+// activation row's byte offset as a 32-bit value (t * cin * 2, conv_gemm2_impl.h), so st_vocos_forward sizes chunks to
+// keep R * max(7 * M, C, F) * 2 below 2^31.
+static int vocos_forward_chunk(st_engine* e, const float* mel, float* audio, int B, int T, hipStream_t s) {
     VocosState* v = e->voc;
     const st_vocos_config& c = v->cfg;
     const int C = c.dim, F = c.intermediate_dim, M = c.input_channels, L = c.num_layers;
     const int64_t R = (int64_t)B * T;
-    if (R * 2 * kVocHeadPlane >= ((int64_t)1 << 31)) return e->fail(ST_ERR_INVALID, "B*T too large for 32-bit row indexing");
-    HIPCHK(e, hipSetDevice(e->device));
-    hipStream_t s = (hipStream_t)stream;
 
     // workspace: im2col rows, fp32 residual stream, 16-bit operands, head output, windowed frames
     size_t off = 0;
@@ -203,6 +199,31 @@ int st_vocos_forward(st_engine* e, const float* mel, float* audio, int B, int T,
         ProfScope ps(e, s, PC_ODE, 0);
         HIPCHK(e, launch_voc_spec_ifft(head, P(e, "head.istft.window"), R, frames, s));
         HIPCHK(e, launch_voc_overlap_add(frames, P(e, "head.istft.window"), B, T, audio, s));
+    }
+    return ST_OK;
+}
+
+int st_vocos_forward(st_engine* e, const float* mel, float* audio, int B, int T, void* stream) {
+    if (!e) return ST_ERR_INVALID;
+    if (e->kind != 2) return e->fail(ST_ERR_STATE, "this handle is not a vocoder (st_create_vocoder)");
+    if (!e->finalized) return e->fail(ST_ERR_STATE, "st_finalize() has not been called after loading parameters");
+    if (!mel || !audio) return e->fail(ST_ERR_INVALID, "null tensor pointer");
+    if (B < 1 || T < 1) return e->fail(ST_ERR_INVALID, "B and T must be >= 1");
+    const st_vocos_config& c = e->voc->cfg;
+    // rows per chunk: 32-bit GEMM operand offsets (widest operand row: the im2col rows, C or F) and head output indices
+    const int64_t widest = std::max({7 * (int64_t)c.input_channels, (int64_t)c.dim, (int64_t)c.intermediate_dim, (int64_t)kVocHeadPlane});
+    const int64_t max_rows = (((int64_t)1 << 31) - 1) / (widest * 2);
+    if (T > max_rows) return e->fail(ST_ERR_INVALID, "T too large: one utterance exceeds the vocoder's 32-bit row indexing");
+    HIPCHK(e, hipSetDevice(e->device));
+    int grid_y = 0;       // the im2col and overlap-add kernels put the utterance on grid.y
+    HIPCHK(e, hipDeviceGetAttribute(&grid_y, hipDeviceAttributeMaxGridDimY, e->device));
+    const int chunk = (int)std::min<int64_t>({(int64_t)B, max_rows / T, (int64_t)grid_y});
+    if (chunk < B && e->capture) return e->fail(ST_ERR_INVALID, "debug capture holds whole-batch tensors: this batch runs in chunks");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t mel_item = (size_t)c.input_channels * T, audio_item = (size_t)T * c.hop_length;
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        const int rc = vocos_forward_chunk(e, mel + b0 * mel_item, audio + b0 * audio_item, std::min(chunk, B - b0), T, s);
+        if (rc) return rc;
     }
     return ST_OK;
 }

@@ -393,17 +393,22 @@ def test_alignment_oracle_matches_reference_fixture():
 
 def test_vocos_oracle_matches_reference_fixture():
     """oracle.vocos_oracle (numpy restatement of vocoders/vocos/models/{backbone,module,head}.py) vs outputs of the REAL
-    Vocos module in fp32 (tests/golden/vocos_outputs.npz, oracle/make_golden_vocos.py): backbone output and waveform."""
+    Vocos module in fp32 (tests/golden/vocos_outputs.npz, oracle/make_golden_vocos.py): backbone output and waveform,
+    at the default config (lengths 1 .. 129) and at the non-default configs of CONFIG_CASES."""
     import os
     import numpy as np
     from oracle import vocos_oracle as vo
-    from oracle.make_golden_vocos import CASES, SD_SEED
+    from oracle.make_golden_vocos import CASES, CONFIG_CASES, CONFIGS, SD_SEED
     g = np.load(os.path.join(os.path.dirname(__file__), "golden", "vocos_outputs.npz"))
-    sd = vo.make_vocos_state_dict(SD_SEED)
-    for name, (B, T, seed) in CASES.items():
-        mel = vo.make_mel(B, T, seed)
-        hid = vo.backbone_forward(sd, mel)
-        audio = vo.head_forward(sd, hid)
+    cases = {name: ({}, B, T, seed) for name, (B, T, seed) in CASES.items()}
+    cases.update({name: (CONFIGS[c], B, T, seed) for name, (c, B, T, seed) in CONFIG_CASES.items()})
+    assert {k.rsplit(".", 1)[0] for k in g.files} - {"state_dict"} == set(cases)
+    for name, (fields, B, T, seed) in cases.items():
+        cfg = vo.vocos_config(**fields)
+        sd = vo.make_vocos_state_dict(SD_SEED, cfg)
+        mel = vo.make_mel(B, T, seed, cfg.input_channels)
+        hid = vo.backbone_forward(sd, mel, cfg)
+        audio = vo.head_forward(sd, hid, cfg)
         assert audio.shape == (B, T * 512)
         assert np.abs(hid - g[name + ".hidden"]).max() <= 2e-6 * np.abs(g[name + ".hidden"]).max(), name
         assert np.abs(audio - g[name + ".audio"]).max() <= 5e-6 * np.abs(g[name + ".audio"]).max(), name
