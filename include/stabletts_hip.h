@@ -307,6 +307,22 @@ int st_train_param_part(const st_engine* e, const char* name);        /* 0, 1, 2
 int64_t st_train_grad_offset(const st_engine* e, const char* name);   /* element offset in the flat gradient layout; < 0: unknown */
 int64_t st_train_grad_numel(const st_engine* e);                      /* floats of the flat layout (alignment gaps included) */
 
+/* ---- text-encoder training: autograd counterpart of TextEncoder.forward (models/text_encoder.py:34-44) on a handle of
+ * st_create_text_encoder.  The forward is st_text_encoder_forward that keeps the activations (same outputs, same dropout
+ * scheme as st_train_forward: FFN site 2i, attention site 2i + 1 of block i); st_train_serial applies to it.
+ * The backward takes d loss / d x (B, hidden, T) and / or d loss / d mu_x (B, out, T) -- either may be NULL, not both --
+ * and writes EVERY parameter gradient (emb.weight, every block, proj) into grad_flat: st_train_grad_numel() floats in the
+ * layout of st_train_grad_offset (NULL = the engine's own buffers, fetch with st_param_grad), and d loss / d c (B, gin) into
+ * grad_c unless NULL.  Rows of emb.weight that no valid position reads get exact zeros; the result is bitwise repeatable.
+ * A backward whose serial is not that of the forward the engine holds fails with ST_ERR_STATE.  st_train_param_part reports
+ * part 0 for every text-encoder parameter (one part). */
+int st_text_encoder_train_forward(st_engine* e, const int64_t* tokens, const int64_t* lengths, const float* c,
+                                  float* x_out, float* mu_out, float* mask_out, int B, int T,
+                                  float p_dropout, uint64_t seed, void* stream);
+int st_text_encoder_train_backward(st_engine* e, int64_t serial, int B, int T, const float* grad_x /* nullable */,
+                                   const float* grad_mu /* nullable */, float* grad_flat, float* grad_c /* nullable */,
+                                   void* stream);
+
 /* Copies the gradient of one parameter (reference state_dict name, `numel` fp32 values) to the device pointer dst. */
 int st_param_grad(st_engine* e, const char* name, float* dst, int64_t numel, void* stream);
 

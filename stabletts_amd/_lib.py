@@ -28,7 +28,7 @@ EXPORTS = [
     "st_create_text_encoder", "st_text_encoder_forward", "st_param_info",
     "st_profile_enable", "st_profile_select", "st_profile_stride", "st_profile_num_classes", "st_profile_class_name", "st_profile_read",
     "st_device_bytes", "st_train_forward", "st_train_backward", "st_train_backward_part", "st_train_param_part", "st_train_grad_offset",
-    "st_train_grad_numel", "st_param_grad", "st_param_grads_flat",
+    "st_train_grad_numel", "st_param_grad", "st_param_grads_flat", "st_text_encoder_train_forward", "st_text_encoder_train_backward",
     "st_durations", "st_generate_path", "st_align", "st_create_vocoder", "st_vocos_forward",
     "st_cfm_loss_prep", "st_cfm_loss", "st_cfm_loss_backward", "st_cfm_loss_scratch_floats",
     "st_set_option", "st_get_option", "st_attention_stats",
@@ -144,6 +144,10 @@ def load():
     lib.st_train_backward.restype = c_int
     lib.st_train_backward_part.argtypes = [c_void_p, ctypes.c_int64, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_int64] + [c_void_p] * 3 + [c_void_p]
     lib.st_train_backward_part.restype = c_int
+    lib.st_text_encoder_train_forward.argtypes = [c_void_p] + [c_void_p] * 6 + [c_int, c_int, c_float, ctypes.c_uint64, c_void_p]
+    lib.st_text_encoder_train_forward.restype = c_int
+    lib.st_text_encoder_train_backward.argtypes = [c_void_p, ctypes.c_int64, c_int, c_int] + [c_void_p] * 4 + [c_void_p]
+    lib.st_text_encoder_train_backward.restype = c_int
     lib.st_train_param_part.argtypes = [c_void_p, ctypes.c_char_p]
     lib.st_train_param_part.restype = c_int
     lib.st_train_grad_offset.argtypes = [c_void_p, ctypes.c_char_p]
@@ -328,6 +332,21 @@ class Engine:
         self._check(self.lib.st_train_forward(self.handle, t.data_ptr(), x.data_ptr(), mu.data_ptr(), mask.data_ptr(),
                                               c.data_ptr(), out.data_ptr(), B, T, float(p_dropout), int(seed),
                                               ctypes.c_void_p(stream)))
+
+    def text_encoder_train_forward(self, tokens, lengths, c, x_out, mu_out, mask_out, p_dropout, seed, stream):
+        """st_text_encoder_forward that keeps the activations for text_encoder_train_backward (text-encoder handles)."""
+        B, T = tokens.shape
+        self._check(self.lib.st_text_encoder_train_forward(self.handle, tokens.data_ptr(), lengths.data_ptr(), c.data_ptr(),
+                                                           x_out.data_ptr(), mu_out.data_ptr(), mask_out.data_ptr(), B, T,
+                                                           float(p_dropout), int(seed), ctypes.c_void_p(stream)))
+
+    def text_encoder_train_backward(self, serial, B, T, grad_x, grad_mu, grad_flat, grad_c, stream):
+        """Every parameter gradient into grad_flat (grad_layout(); None: the engine's own buffers), d c into grad_c."""
+        ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+        if grad_flat is not None and grad_flat.numel() != self.grad_layout()[None]:
+            raise ValueError("grad_flat must hold grad_layout()[None] floats")
+        self._check(self.lib.st_text_encoder_train_backward(self.handle, int(serial), B, T, ptr(grad_x), ptr(grad_mu), ptr(grad_flat),
+                                                            ptr(grad_c), ctypes.c_void_p(stream)))
 
     def train_serial(self):
         """Serial of the grad-enabled forward whose activations the engine holds (0: none)."""

@@ -1,7 +1,8 @@
 // Training side of libstabletts_hip.so: a forward evaluation of the estimator that keeps the activations and the
 // matching backward pass, both as launch sequences of hand-written gfx950 kernels.  Autograd counterpart of
 // models/estimator.py:103-138 (Decoder.forward) + models/diffusion_transformer.py:98-121 as exercised by
-// CFMDecoder.compute_loss (models/flow_matching.py:69-100) under DDP in train.py:78-81.
+// CFMDecoder.compute_loss (models/flow_matching.py:69-100) under DDP in train.py:78-81, and of TextEncoder.forward
+// (models/text_encoder.py:34-44, kind 1): the same blocks without FiLM or long skips, proj, and the embedding (emb_bwd.hip).
 //
 // Structure of the backward pass:
 //   * data gradients of every convolution run through the FORWARD implicit-GEMM kernel with transposed, tap-flipped
@@ -103,6 +104,9 @@ struct TrainState {
     bool use_side = true, side_prio = false;     // ST_TRAIN_SIDE=2: side streams at the device's lowest stream priority (0: no side streams)
     size_t partial_cap = 0, xt_cap = 0, dyt_cap = 0;
     size_t wg_max_frames = 0, wg_max_cout = 0, wg_max_prod = 0;   // layout_train's largest taps*Cin, Cout and product: wgrad() refuses more
+    // text encoder (kind 1): the forward's clamped token id per row (-1: padded), the embedding backward's scratch, and {1, 1}: the
+    // scale pair a caller's d x is written at (launch_add_rescaled's sc_b)
+    int* ids = nullptr; void* emb_ws = nullptr; float* unit_sc = nullptr;
 };
 
 namespace {
@@ -150,7 +154,7 @@ void train_invalidate(st_engine* e) {
 
 // (re)packs the transposed weights after a parameter update; lazy: inference-only users never pay for it
 int train_prepare(st_engine* e, hipStream_t s) {
-    if (e->kind != 0) return ST_OK;
+    if (e->kind != 0 && e->kind != 1) return ST_OK;
     if (!e->train) {
         e->train = new TrainState();
         if (const char* v = getenv("ST_FUSE_SILU")) e->train->fuse_silu = atoi(v) != 0;
@@ -179,14 +183,19 @@ int train_prepare(st_engine* e, hipStream_t s) {
         return ST_OK;
     }
     pk_begin(e->pk_T);
-    if ((rc = pack_T(e, ts, ts->finT, "final_proj.weight", M, C, 1, 0, C, C, Mp, s))) return rc;
-    if ((rc = pack_T(e, ts, ts->inxT, "in_proj.weight", C, C + M, 1, 0, M, Mp, C, s))) return rc;
-    if ((rc = pack_T(e, ts, ts->incT, "in_proj.weight", C, C + M, 1, M, C, C, C, s))) return rc;
-    if ((rc = pack_T(e, ts, ts->preT[0], "cond_proj.0.weight", F, M, K, 0, M, Mp, F, s))) return rc;
-    if ((rc = pack_T(e, ts, ts->preT[1], "cond_proj.2.weight", F, F, K, 0, F, F, F, s))) return rc;
-    if ((rc = pack_T(e, ts, ts->preT[2], "cond_proj.4.weight", C, F, K, 0, F, F, C, s))) return rc;
+    if (e->kind == 1) {      // text encoder: proj is the only convolution outside the blocks
+        if ((rc = pack_T(e, ts, ts->finT, "proj.weight", M, C, 1, 0, C, C, Mp, s))) return rc;
+    } else {
+        if ((rc = pack_T(e, ts, ts->finT, "final_proj.weight", M, C, 1, 0, C, C, Mp, s))) return rc;
+        if ((rc = pack_T(e, ts, ts->inxT, "in_proj.weight", C, C + M, 1, 0, M, Mp, C, s))) return rc;
+        if ((rc = pack_T(e, ts, ts->incT, "in_proj.weight", C, C + M, 1, M, C, C, C, s))) return rc;
+        if ((rc = pack_T(e, ts, ts->preT[0], "cond_proj.0.weight", F, M, K, 0, M, Mp, F, s))) return rc;
+        if ((rc = pack_T(e, ts, ts->preT[1], "cond_proj.2.weight", F, F, K, 0, F, F, F, s))) return rc;
+        if ((rc = pack_T(e, ts, ts->preT[2], "cond_proj.4.weight", C, F, K, 0, F, F, C, s))) return rc;
+    }
+    const int n_lsc = e->kind == 0 ? L / 2 : 0;
     ts->ffn1T.resize(L); ts->ffn2T.resize(L); ts->oprojT.resize(L); ts->qkvT.resize(L);
-    ts->lscTa.resize(L / 2); ts->lscTb.resize(L / 2);
+    ts->lscTa.resize(n_lsc); ts->lscTb.resize(n_lsc);
     for (int i = 0; i < L; ++i) {
         const std::string b = e->blk(i);
         if ((rc = pack_T(e, ts, ts->ffn1T[i], b + "mlp.conv_1.weight", F, C, K, 0, C, C, F, s))) return rc;
@@ -215,7 +224,7 @@ int train_prepare(st_engine* e, hipStream_t s) {
             ++r;
         }
     }
-    for (int j = 0; j < L / 2; ++j) {
+    for (int j = 0; j < n_lsc; ++j) {
         const std::string n = "lsc_layers." + std::to_string(j) + ".weight";
         if ((rc = pack_T(e, ts, ts->lscTa[j], n, C, 2 * C, K, 0, C, C, C, s))) return rc;
         if ((rc = pack_T(e, ts, ts->lscTb[j], n, C, 2 * C, K, C, C, C, C, s))) return rc;
@@ -265,21 +274,30 @@ int layout_train(st_engine* e, TrainState* ts, int B, int T) {
     struct Slot { void** dst; size_t off; };
     std::vector<Slot> slots;
     auto want = [&](void** dst, size_t bytes) { slots.push_back({dst, off}); off = align_up(off + bytes, 256); };
+    // dec: tensors of the decoder's own layers (in_proj, cond prenet, time MLP, FiLM, long skips); the text encoder (kind 1) has none
+    const bool dec = e->kind == 0;
+    auto want_dec = [&](void** dst, size_t bytes) { if (dec) want(dst, bytes); else *dst = nullptr; };
     ts->L.assign(L, LayerAct());
-    want(&ts->mu16, R * Mp * 2); want(&ts->x16, R * Mp * 2); want(&ts->x16lo, R * Mp * 2);
-    want(&ts->a1, R * F * 2); want(&ts->p1, R * F * 2); want(&ts->a2, R * F * 2); want(&ts->p2, R * F * 2);
-    want(&ts->cond16, R * C * 2); want(&ts->cond16lo, R * C * 2); want(&ts->h0_16, R * C * 2); want(&ts->x3lo, R * C * 2);
+    want_dec(&ts->mu16, R * Mp * 2); want_dec(&ts->x16, R * Mp * 2); want_dec(&ts->x16lo, R * Mp * 2);
+    want_dec(&ts->a1, R * F * 2); want_dec(&ts->p1, R * F * 2); want_dec(&ts->a2, R * F * 2); want_dec(&ts->p2, R * F * 2);
+    want_dec(&ts->cond16, R * C * 2); want_dec(&ts->cond16lo, R * C * 2); want_dec(&ts->h0_16, R * C * 2); want(&ts->x3lo, R * C * 2);
     want((void**)&ts->maskbuf, R * 4); want((void**)&ts->kbias, N * Tp * 4);
     want((void**)&ts->n_full, N * 4); want((void**)&ts->kv_end, N * 4);
-    want((void**)&ts->cvec, N * G * 4); want((void**)&ts->tvals, N * 4);
+    want((void**)&ts->cvec, N * G * 4); want_dec((void**)&ts->tvals, N * 4);
     want((void**)&ts->ada_pre, (size_t)L * N * C * 4); want((void**)&ts->dada_pre, N * C * 4);
-    want((void**)&ts->emb, N * C * 4); want((void**)&ts->th_pre, N * F * 4); want((void**)&ts->tau, N * C * 4);
-    want((void**)&ts->film, (size_t)L * N * 2 * C * 4); want((void**)&ts->ada, (size_t)L * N * 6 * C * 4);
-    want((void**)&ts->cpart, R * C * 4); want((void**)&ts->h0, R * C * 4); want((void**)&ts->v32, R * Mp * 4);
+    want_dec((void**)&ts->emb, N * C * 4); want_dec((void**)&ts->th_pre, N * F * 4); want_dec((void**)&ts->tau, N * C * 4);
+    want_dec((void**)&ts->film, (size_t)L * N * 2 * C * 4); want((void**)&ts->ada, (size_t)L * N * 6 * C * 4);
+    want_dec((void**)&ts->cpart, R * C * 4); want((void**)&ts->h0, R * C * 4); want((void**)&ts->v32, R * Mp * 4);
+    if (!dec) {
+        want((void**)&ts->ids, R * 4);
+        want(&ts->emb_ws, emb_bwd_scratch_bytes((int64_t)R, e->n_vocab, C));
+        want((void**)&ts->unit_sc, 16);
+    }
     for (int i = 0; i < L; ++i) {
         LayerAct& a = ts->L[i];
-        if (i >= L / 2) want((void**)&a.lscout, R * C * 4); else a.lscout = nullptr;
-        want((void**)&a.x1, R * C * 4); want((void**)&a.o32, R * C * 4); want((void**)&a.x2, R * C * 4);
+        if (dec && i >= L / 2) want((void**)&a.lscout, R * C * 4); else a.lscout = nullptr;
+        if (dec) want((void**)&a.x1, R * C * 4); else a.x1 = nullptr;      // text encoder: x1 = xpre (already masked), bound below
+        want((void**)&a.o32, R * C * 4); want((void**)&a.x2, R * C * 4);
         want((void**)&a.f32b, R * C * 4); want((void**)&a.x3, R * C * 4);
         want(&a.h1, R * C * 2); want(&a.q, R * C * 2); want(&a.k, R * C * 2); want(&a.vt, N * C * Tp * 2);
         if (ts->v_lo) want(&a.vt_lo, N * C * Tp * 2); else a.vt_lo = nullptr;
@@ -290,7 +308,7 @@ int layout_train(st_engine* e, TrainState* ts, int B, int T) {
     }
     // backward scratch
     want((void**)&ts->dX, R * C * 4);
-    for (int j = 0; j < L / 2; ++j) want((void**)&ts->dskip[j], R * C * 4);
+    for (int j = 0; j < L / 2; ++j) want_dec((void**)&ts->dskip[j], R * C * 4);
     want((void**)&ts->tmpC, R * C * 4); want((void**)&ts->tmpF, R * F * 4); want((void**)&ts->gin, R * Mp * 4);
     {
         const size_t w[TrainState::DY_COUNT] = {(size_t)C, (size_t)F, (size_t)C, (size_t)C, (size_t)3 * C, (size_t)3 * C, (size_t)C, (size_t)std::max(C, Mp),
@@ -340,8 +358,8 @@ int layout_train(st_engine* e, TrainState* ts, int B, int T) {
     }
     ts->drop_row_stride = (size_t)N * H * TT + 64; ts->drop_col_stride = (size_t)(Tp / 2 + 64);
     want((void**)&ts->drop_rowh_all, (size_t)L * ts->drop_row_stride * 4); want((void**)&ts->drop_colh_all, (size_t)L * ts->drop_col_stride * 4);
-    want((void**)&ts->dada, (size_t)L * N * 6 * C * 4); want((void**)&ts->dfilm, (size_t)L * N * 2 * C * 4);
-    want((void**)&ts->dtau, N * C * 4); want((void**)&ts->dth, N * F * 4); want((void**)&ts->demb, N * C * 4);
+    want((void**)&ts->dada, (size_t)L * N * 6 * C * 4); want_dec((void**)&ts->dfilm, (size_t)L * N * 2 * C * 4);
+    want_dec((void**)&ts->dtau, N * C * 4); want_dec((void**)&ts->dth, N * F * 4); want_dec((void**)&ts->demb, N * C * 4);
     want((void**)&ts->dcvec, N * G * 4);
     want((void**)&ts->gsc, 16); want((void**)&ts->gbits, 16); want((void**)&ts->skip_sc, 64);
     if (off > ts->ws_cap) {
@@ -350,6 +368,7 @@ int layout_train(st_engine* e, TrainState* ts, int B, int T) {
         ts->ws_cap = off;
     }
     for (auto& sl : slots) *sl.dst = ts->ws + sl.off;
+    if (!dec) for (int i = 0; i < L; ++i) ts->L[i].x1 = i == 0 ? ts->h0 : ts->L[i - 1].x3;
     ts->cells_ring = ts->zero_region;
     ts->qbits_all = ts->zero_region + (size_t)(4 * L + 8) * kMaxCellWords;
     ts->dsmax_all = ts->qbits_all + (size_t)4 * L;
@@ -358,7 +377,118 @@ int layout_train(st_engine* e, TrainState* ts, int B, int T) {
 }
 
 inline const float* xpre_of(const TrainState* ts, int i, int L) {
-    return i == 0 ? ts->h0 : (i >= L / 2 ? ts->L[i].lscout : ts->L[i - 1].x3);
+    return i == 0 ? ts->h0 : (ts->L[i].lscout ? ts->L[i].lscout : ts->L[i - 1].x3);
+}
+
+void capture_train(st_engine* e, TrainState* ts, hipStream_t s) {
+    const int C = e->C, F = e->F, L = e->L, H = e->H, N = ts->B, T = ts->T, Tp = ts->Tp;
+    const int64_t R = (int64_t)N * T;
+    if (e->capture) {
+        for (int i = 0; i < L; ++i) {
+            const std::string bn = "t" + std::to_string(i) + ".";
+            capture(e, bn + "x1", ts->L[i].x1, R * C, false, s); capture(e, bn + "x2", ts->L[i].x2, R * C, false, s);
+            capture(e, bn + "x3", ts->L[i].x3, R * C, false, s); capture(e, bn + "h1", ts->L[i].h1, R * C, true, s);
+            capture(e, bn + "q", ts->L[i].q, R * C, true, s); capture(e, bn + "k", ts->L[i].k, R * C, true, s);
+            capture(e, bn + "vt", ts->L[i].vt, (int64_t)N * C * Tp, true, s); if (ts->L[i].vt_lo) capture(e, bn + "vtlo", ts->L[i].vt_lo, (int64_t)N * C * Tp, true, s);
+             capture(e, bn + "attn", ts->L[i].attn16, R * C, true, s);
+            capture(e, bn + "lse", ts->L[i].lse, (int64_t)N * H * T, false, s);
+            capture(e, bn + "u", ts->L[i].u16, R * F, true, s);
+        }
+    }
+}
+
+// The L DiT blocks of a training forward (diffusion_transformer.py:98-117), activations kept: the decoder's with FiLM on the
+// block input and the long-skip merges (estimator.py:126-132), the text encoder's without either (text_encoder.py:40-41).
+int fwd_blocks(st_engine* e, TrainState* ts, const float* m, float p_dropout, unsigned long long seed, hipStream_t s) {
+    const int C = e->C, F = e->F, L = e->L, H = e->H, N = ts->B, B = ts->B, T = ts->T, Tp = ts->Tp;
+    const int64_t R = (int64_t)N * T;
+    for (int i = 0; i < L; ++i) {
+        LayerAct& A = ts->L[i];
+        const float* ada_i = ts->ada + (size_t)i * N * 6 * C;
+        if (e->kind == 0 && i >= L / 2) {   // long-skip merge (estimator.py:131-132)
+            const int j = i - L / 2;
+            const int src = L - 1 - i;      // 2, 1, 0 -> x3[1], x3[0], h0
+            ConvGemmArgs a = cargs(e, e->lsc[j], N, T, B);
+            a.a0 = ts->L[i - 1].x3_16; a.c0 = C; a.a1 = src == 0 ? ts->h0_16 : ts->L[src - 1].x3_16; a.c1 = C; a.out32 = A.lscout;
+            HIPCHK(e, gemm(e, 3, EPI_F32, a, s));
+        }
+        {   // FiLM * mask -> x1 (decoder) ; LN1 + modulate -> h1
+            TrainLnArgs a; memset(&a, 0, sizeof(a));
+            a.xin = xpre_of(ts, i, L); a.h16 = A.h1; a.h16lo = A.h1lo;
+            if (e->kind == 0) { a.xout = A.x1; a.film = ts->film + (size_t)i * N * 2 * C; a.film_stride = 2 * C; a.film_mod = N; }
+            // (text encoder: x1 = xpre * mask = xpre -- the embedding kernel and every block leave padded frames at zero -- and A.x1 IS xpre)
+            a.ada = ada_i; a.ada_stride = 6 * C; a.shift_off = 0; a.scale_off = C;
+            a.mask = m; a.mask_mod = B; a.mask_out = 0; a.T = T; a.rows = (int)R;
+            HIPCHK(e, launch_train_ln(e->dt, a, s));
+        }
+        {
+            ConvGemmArgs a = cargs(e, ts->h_lo ? ts->qkv2[i] : e->qkv[i], N, T, B);
+            a.a0 = A.h1; a.c0 = C; a.q = A.q; a.k = A.k; a.vt = A.vt; a.vt_lo = A.vt_lo; a.rope_cos = e->rope_cos; a.rope_sin = e->rope_sin;
+            if (ts->h_lo) { a.a1 = A.h1lo; a.c1 = C; a.flags |= GF_K2_V_ONLY; }      // K = [h_hi | h_lo] against [W 0] (q, k rows: bit-identical) / [W_v W_v] (v rows)
+            a.Tp = Tp; a.n_heads = H; a.qscale = 1.4426950408889634f / sqrtf((float)(C / H));
+            if ((int)e->qkv_frag.size() == e->L) a.w_frag = e->qkv_frag[i];      // weight-stationary kernel on big batches (bit-identical; re-packed with the other forward weights)
+            HIPCHK(e, gemm(e, 1, EPI_QKV, a, s));
+        }
+        {
+            AttnArgs a; memset(&a, 0, sizeof(a));
+            a.q = A.q; a.k = A.k; a.vt = A.vt; a.vt_lo = A.vt_lo; a.out = A.attn16; a.kbias = ts->kbias; a.mask_mod = B; a.zeros = e->zeros;
+            a.kv_end = ts->kv_end; a.n_full = ts->n_full; a.T = T; a.Tp = Tp; a.H = H; a.n_items = N;
+            a.lse = A.lse; a.drop = make_drop(p_dropout, seed, 2 * i + 1);
+            if (a.drop.thresh16) { a.drop.rowh = ts->drop_rowh_all + (size_t)i * ts->drop_row_stride; a.drop.colh = ts->drop_colh_all + (size_t)i * ts->drop_col_stride; }
+            HIPCHK(e, launch_attention(e->dt, a, s));
+        }
+        if (ts->fuse_ln) {   // o = (Wo attn + b) * mask ; x2 = x1 + g_msa * o ; LN2 + modulate, masked -> h2: one GEMM with the
+            // inference epilogue (EPI_RESGATE + fused LayerNorm) that also stores the branch output o the gate's gradient needs
+            ConvGemmArgs a = cargs(e, e->oproj[i], N, T, B);
+            a.a0 = A.attn16; a.c0 = C; a.mask = m; a.gate = ada_i + 2 * C; a.gate_stride = 6 * C;
+            a.res32 = A.x1; a.out32 = A.x2; a.branch32 = A.o32;
+            a.ln_h16 = A.h2; a.ln_film = nullptr; a.ln_film_mod = 1;
+            a.ln_ada = ada_i; a.ln_ada_stride = 6 * C; a.ln_shift_off = 3 * C; a.ln_scale_off = 4 * C; a.ln_mask_out = 1;
+            HIPCHK(e, gemm(e, 1, EPI_RESGATE, a, s));
+        } else {
+            {   // o = (Wo attn + b) * mask
+                ConvGemmArgs a = cargs(e, e->oproj[i], N, T, B);
+                a.a0 = A.attn16; a.c0 = C; a.mask = m; a.flags = GF_MASK; a.out32 = A.o32;
+                HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
+            }
+            {   // x2 = x1 + g_msa * o ; LN2 + modulate, masked -> h2
+                TrainLnArgs a; memset(&a, 0, sizeof(a));
+                a.xin = A.x1; a.xout = A.x2; a.h16 = A.h2;
+                a.gate = ada_i + 2 * C; a.gate_stride = 6 * C; a.branch = A.o32;
+                a.ada = ada_i; a.ada_stride = 6 * C; a.shift_off = 3 * C; a.scale_off = 4 * C;
+                a.mask = m; a.mask_mod = B; a.mask_out = 1; a.T = T; a.rows = (int)R;
+                HIPCHK(e, launch_train_ln(e->dt, a, s));
+            }
+        }
+        {   // FFN (diffusion_transformer.py:25-30)
+            ConvGemmArgs a = cargs(e, e->ffn1[i], N, T, B); a.a0 = A.h2; a.c0 = C; a.out16 = A.a16;
+            const DropCfg dc = make_drop(p_dropout, seed, 2 * i);
+            if (ts->fuse_silu && gemm_is_phased(e, 3, a)) {      // SiLU + dropout + mask in the GEMM's epilogue (bit-identical)
+                a.act16 = A.u16; a.mask = m; a.drop_seed = dc.seed; a.drop_thresh16 = dc.thresh16; a.drop_scale = dc.scale;
+                HIPCHK(e, gemm(e, 3, EPI_SILU, a, s));
+            } else {
+                HIPCHK(e, gemm(e, 3, EPI_F32, a, s));
+                HIPCHK(e, launch_silu_drop(e->dt, A.a16, A.u16, m, B, T, F, R, dc, s));
+            }
+            a = cargs(e, e->ffn2[i], N, T, B); a.a0 = A.u16; a.c0 = F; a.mask = m;
+            if (ts->fuse_ln) {      // f = (W2 u + b) * mask ; x3 = x2 + g_mlp * f (+ its 16-bit copies) in the GEMM's epilogue
+                a.gate = ada_i + 5 * C; a.gate_stride = 6 * C; a.res32 = A.x2; a.out32 = A.x3; a.branch32 = A.f32b;
+                a.out16 = A.x3_16; a.out16_lo = i + 1 == L ? ts->x3lo : nullptr;
+                HIPCHK(e, gemm(e, 3, EPI_RESGATE, a, s));
+            } else {
+                a.flags = GF_MASK; a.out32 = A.f32b;
+                HIPCHK(e, gemm(e, 3, EPI_F32, a, s));
+            }
+        }
+        if (!ts->fuse_ln) {   // x3 = x2 + g_mlp * f  (+ 16-bit copies: long-skip / final_proj operands)
+            TrainLnArgs a; memset(&a, 0, sizeof(a));
+            a.xin = A.x2; a.xout = A.x3; a.x16 = A.x3_16; a.x16lo = i + 1 == L ? ts->x3lo : nullptr;
+            a.gate = ada_i + 5 * C; a.gate_stride = 6 * C; a.branch = A.f32b;
+            a.T = T; a.rows = (int)R;
+            HIPCHK(e, launch_train_ln(e->dt, a, s));
+        }
+    }
+    return ST_OK;
 }
 
 }  // namespace
@@ -453,109 +583,14 @@ int st_train_forward(st_engine* e, const float* t, const float* x, const float* 
         a.add32 = ts->cpart; a.add_clamp = N; a.out32 = ts->h0; a.out16 = ts->h0_16;
         HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
     }
-    for (int i = 0; i < L; ++i) {
-        LayerAct& A = ts->L[i];
-        const float* ada_i = ts->ada + (size_t)i * N * 6 * C;
-        if (i >= L / 2) {   // long-skip merge (estimator.py:131-132)
-            const int j = i - L / 2;
-            const int src = L - 1 - i;      // 2, 1, 0 -> x3[1], x3[0], h0
-            ConvGemmArgs a = cargs(e, e->lsc[j], N, T, B);
-            a.a0 = ts->L[i - 1].x3_16; a.c0 = C; a.a1 = src == 0 ? ts->h0_16 : ts->L[src - 1].x3_16; a.c1 = C; a.out32 = A.lscout;
-            HIPCHK(e, gemm(e, 3, EPI_F32, a, s));
-        }
-        {   // FiLM * mask -> x1 ; LN1 + modulate -> h1
-            TrainLnArgs a; memset(&a, 0, sizeof(a));
-            a.xin = xpre_of(ts, i, L); a.xout = A.x1; a.h16 = A.h1; a.h16lo = A.h1lo;
-            a.film = ts->film + (size_t)i * N * 2 * C; a.film_stride = 2 * C; a.film_mod = N;
-            a.ada = ada_i; a.ada_stride = 6 * C; a.shift_off = 0; a.scale_off = C;
-            a.mask = m; a.mask_mod = B; a.mask_out = 0; a.T = T; a.rows = (int)R;
-            HIPCHK(e, launch_train_ln(e->dt, a, s));
-        }
-        {
-            ConvGemmArgs a = cargs(e, ts->h_lo ? ts->qkv2[i] : e->qkv[i], N, T, B);
-            a.a0 = A.h1; a.c0 = C; a.q = A.q; a.k = A.k; a.vt = A.vt; a.vt_lo = A.vt_lo; a.rope_cos = e->rope_cos; a.rope_sin = e->rope_sin;
-            if (ts->h_lo) { a.a1 = A.h1lo; a.c1 = C; a.flags |= GF_K2_V_ONLY; }      // K = [h_hi | h_lo] against [W 0] (q, k rows: bit-identical) / [W_v W_v] (v rows)
-            a.Tp = Tp; a.n_heads = H; a.qscale = 1.4426950408889634f / sqrtf((float)(C / H));
-            if ((int)e->qkv_frag.size() == e->L) a.w_frag = e->qkv_frag[i];      // weight-stationary kernel on big batches (bit-identical; re-packed with the other forward weights)
-            HIPCHK(e, gemm(e, 1, EPI_QKV, a, s));
-        }
-        {
-            AttnArgs a; memset(&a, 0, sizeof(a));
-            a.q = A.q; a.k = A.k; a.vt = A.vt; a.vt_lo = A.vt_lo; a.out = A.attn16; a.kbias = ts->kbias; a.mask_mod = B; a.zeros = e->zeros;
-            a.kv_end = ts->kv_end; a.n_full = ts->n_full; a.T = T; a.Tp = Tp; a.H = H; a.n_items = N;
-            a.lse = A.lse; a.drop = make_drop(p_dropout, seed, 2 * i + 1);
-            if (a.drop.thresh16) { a.drop.rowh = ts->drop_rowh_all + (size_t)i * ts->drop_row_stride; a.drop.colh = ts->drop_colh_all + (size_t)i * ts->drop_col_stride; }
-            HIPCHK(e, launch_attention(e->dt, a, s));
-        }
-        if (ts->fuse_ln) {   // o = (Wo attn + b) * mask ; x2 = x1 + g_msa * o ; LN2 + modulate, masked -> h2: one GEMM with the
-            // inference epilogue (EPI_RESGATE + fused LayerNorm) that also stores the branch output o the gate's gradient needs
-            ConvGemmArgs a = cargs(e, e->oproj[i], N, T, B);
-            a.a0 = A.attn16; a.c0 = C; a.mask = m; a.gate = ada_i + 2 * C; a.gate_stride = 6 * C;
-            a.res32 = A.x1; a.out32 = A.x2; a.branch32 = A.o32;
-            a.ln_h16 = A.h2; a.ln_film = nullptr; a.ln_film_mod = 1;
-            a.ln_ada = ada_i; a.ln_ada_stride = 6 * C; a.ln_shift_off = 3 * C; a.ln_scale_off = 4 * C; a.ln_mask_out = 1;
-            HIPCHK(e, gemm(e, 1, EPI_RESGATE, a, s));
-        } else {
-            {   // o = (Wo attn + b) * mask
-                ConvGemmArgs a = cargs(e, e->oproj[i], N, T, B);
-                a.a0 = A.attn16; a.c0 = C; a.mask = m; a.flags = GF_MASK; a.out32 = A.o32;
-                HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
-            }
-            {   // x2 = x1 + g_msa * o ; LN2 + modulate, masked -> h2
-                TrainLnArgs a; memset(&a, 0, sizeof(a));
-                a.xin = A.x1; a.xout = A.x2; a.h16 = A.h2;
-                a.gate = ada_i + 2 * C; a.gate_stride = 6 * C; a.branch = A.o32;
-                a.ada = ada_i; a.ada_stride = 6 * C; a.shift_off = 3 * C; a.scale_off = 4 * C;
-                a.mask = m; a.mask_mod = B; a.mask_out = 1; a.T = T; a.rows = (int)R;
-                HIPCHK(e, launch_train_ln(e->dt, a, s));
-            }
-        }
-        {   // FFN (diffusion_transformer.py:25-30)
-            ConvGemmArgs a = cargs(e, e->ffn1[i], N, T, B); a.a0 = A.h2; a.c0 = C; a.out16 = A.a16;
-            const DropCfg dc = make_drop(p_dropout, seed, 2 * i);
-            if (ts->fuse_silu && gemm_is_phased(e, 3, a)) {      // SiLU + dropout + mask in the GEMM's epilogue (bit-identical)
-                a.act16 = A.u16; a.mask = m; a.drop_seed = dc.seed; a.drop_thresh16 = dc.thresh16; a.drop_scale = dc.scale;
-                HIPCHK(e, gemm(e, 3, EPI_SILU, a, s));
-            } else {
-                HIPCHK(e, gemm(e, 3, EPI_F32, a, s));
-                HIPCHK(e, launch_silu_drop(e->dt, A.a16, A.u16, m, B, T, F, R, dc, s));
-            }
-            a = cargs(e, e->ffn2[i], N, T, B); a.a0 = A.u16; a.c0 = F; a.mask = m;
-            if (ts->fuse_ln) {      // f = (W2 u + b) * mask ; x3 = x2 + g_mlp * f (+ its 16-bit copies) in the GEMM's epilogue
-                a.gate = ada_i + 5 * C; a.gate_stride = 6 * C; a.res32 = A.x2; a.out32 = A.x3; a.branch32 = A.f32b;
-                a.out16 = A.x3_16; a.out16_lo = i + 1 == L ? ts->x3lo : nullptr;
-                HIPCHK(e, gemm(e, 3, EPI_RESGATE, a, s));
-            } else {
-                a.flags = GF_MASK; a.out32 = A.f32b;
-                HIPCHK(e, gemm(e, 3, EPI_F32, a, s));
-            }
-        }
-        if (!ts->fuse_ln) {   // x3 = x2 + g_mlp * f  (+ 16-bit copies: long-skip / final_proj operands)
-            TrainLnArgs a; memset(&a, 0, sizeof(a));
-            a.xin = A.x2; a.xout = A.x3; a.x16 = A.x3_16; a.x16lo = i + 1 == L ? ts->x3lo : nullptr;
-            a.gate = ada_i + 5 * C; a.gate_stride = 6 * C; a.branch = A.f32b;
-            a.T = T; a.rows = (int)R;
-            HIPCHK(e, launch_train_ln(e->dt, a, s));
-        }
-    }
+    if ((rc = fwd_blocks(e, ts, m, p_dropout, seed, s))) return rc;
     {
         ConvGemmArgs a = cargs(e, e->fin, N, T, B);
         a.a0 = ts->L[L - 1].x3_16; a.c0 = C; a.a1 = ts->x3lo; a.c1 = C; a.c2 = C; a.mask = m; a.flags = GF_MASK; a.out32 = ts->v32;
         HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
     }
     HIPCHK(e, launch_from_time_major(ts->v32, B, e->M, T, Mp, out, s));
-    if (e->capture) {
-        for (int i = 0; i < L; ++i) {
-            const std::string bn = "t" + std::to_string(i) + ".";
-            capture(e, bn + "x1", ts->L[i].x1, R * C, false, s); capture(e, bn + "x2", ts->L[i].x2, R * C, false, s);
-            capture(e, bn + "x3", ts->L[i].x3, R * C, false, s); capture(e, bn + "h1", ts->L[i].h1, R * C, true, s);
-            capture(e, bn + "q", ts->L[i].q, R * C, true, s); capture(e, bn + "k", ts->L[i].k, R * C, true, s);
-            capture(e, bn + "vt", ts->L[i].vt, (int64_t)N * C * Tp, true, s); if (ts->L[i].vt_lo) capture(e, bn + "vtlo", ts->L[i].vt_lo, (int64_t)N * C * Tp, true, s);
-             capture(e, bn + "attn", ts->L[i].attn16, R * C, true, s);
-            capture(e, bn + "lse", ts->L[i].lse, (int64_t)N * H * T, false, s);
-            capture(e, bn + "u", ts->L[i].u16, R * F, true, s);
-        }
-    }
+    capture_train(e, ts, s);
     ts->have_fwd = true;
     ts->serial += 1;
     ts->gbase = ts->grad_flat; ts->next_part = 0;      // a pruned / abandoned multi-part backward of the previous forward leaves no state behind
@@ -565,6 +600,68 @@ int st_train_forward(st_engine* e, const float* t, const float* x, const float* 
 int64_t st_train_serial(const st_engine* e) {
     if (!e || !e->train || !e->train->have_fwd) return 0;
     return e->train->serial;
+}
+
+// TextEncoder.forward (models/text_encoder.py:34-44) keeping the activations for st_text_encoder_train_backward: the embedding,
+// the L blocks of fwd_blocks without FiLM or long skips, proj on the split-precision operand pair (as the inference path).
+int st_text_encoder_train_forward(st_engine* e, const int64_t* tokens, const int64_t* lengths, const float* c, float* x_out,
+                                  float* mu_out, float* mask_out, int B, int T, float p_dropout, uint64_t seed, void* stream) {
+    int rc = check_ready(e, B, T); if (rc) return rc;
+    if (e->kind != 1) return e->fail(ST_ERR_STATE, "this handle is not a text encoder (st_create_text_encoder)");
+    if (!tokens || !lengths || !c || !x_out || !mu_out || !mask_out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
+    if (!(p_dropout >= 0.f && p_dropout < 1.f)) return e->fail(ST_ERR_INVALID, "p_dropout must be in [0, 1)");
+    HIPCHK(e, hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = train_prepare(e, s))) return rc;
+    TrainState* ts = e->train;
+    ts->have_fwd = false;
+    if ((rc = layout_train(e, ts, B, T))) return rc;
+    if ((rc = ensure_rope(e, T, s))) return rc;
+    ProfScope prof(e, s, PC_TRAIN_FWD, 0);
+    const int C = e->C, Mp = e->Mp, L = e->L, H = e->H, N = B, Tp = ts->Tp;
+    ts->p_drop = p_dropout; ts->seed = seed;
+    // x = emb[token] * sqrt(C) * mask (time-major fp32: block 0's input), the (B,1,T) mask, the ids the embedding backward sums by
+    HIPCHK(e, launch_embed_tokens((const long long*)tokens, (const long long*)lengths, P(e, "emb.weight"), e->n_vocab, C,
+                                  sqrtf((float)C), B, T, ts->h0, ts->maskbuf, s));
+    HIPCHK(e, launch_emb_ids((const long long*)tokens, (const long long*)lengths, e->n_vocab, B, T, ts->ids, s));
+    HIPCHK(e, launch_mask_prep(ts->maskbuf, B, T, Tp, ts->n_full, ts->kv_end, ts->kbias, nullptr, s));
+    HIPCHK(e, launch_cvec_prep(c, nullptr, B, e->G, ts->cvec, s));
+    const float* m = ts->maskbuf;
+    // adaLN modulation of every block (diffusion_transformer.py:92-96): one launch per 8 blocks
+    for (int i0 = 0; i0 < L; i0 += 8) {
+        LinearJobs ja; memset(&ja, 0, sizeof(ja));
+        for (int i = i0; i < std::min(L, i0 + 8); ++i) {
+            const std::string pa = e->blk(i) + "adaLN_modulation.2.";
+            const float* ain = ts->cvec;
+            if (e->G != C) {
+                const std::string p0 = e->blk(i) + "adaLN_modulation.0.";
+                float* pre = ts->ada_pre + (size_t)i * N * C;
+                HIPCHK(e, launch_linear(ts->cvec, N, e->G, P(e, p0 + "weight"), P(e, p0 + "bias"), C, pre, 0, 0, s));
+                ain = pre;
+            }
+            ja.in[ja.n] = ain; ja.W[ja.n] = P(e, pa + "weight"); ja.bias[ja.n] = P(e, pa + "bias"); ja.out[ja.n] = ts->ada + (size_t)i * N * 6 * C; ja.n += 1;
+        }
+        HIPCHK(e, launch_linear_multi(ja, N, C, 6 * C, 1, 0, s));
+    }
+    if (make_drop(p_dropout, seed, 1).thresh16) {      // the decoder's salt scheme: attention site 2i + 1, FFN site 2i
+        DropSeeds sd; memset(&sd, 0, sizeof(sd));
+        for (int i = 0; i < L; ++i) sd.seed[i] = make_drop(p_dropout, seed, 2 * i + 1).seed;
+        HIPCHK(e, launch_drop_tables_multi(sd, L, N * H * T + 64, Tp / 2, ts->drop_rowh_all, ts->drop_colh_all, ts->drop_row_stride, ts->drop_col_stride, s));
+    }
+    if ((rc = fwd_blocks(e, ts, m, p_dropout, seed, s))) return rc;
+    {   // mu_x = proj(x) * x_mask (text_encoder.py:42)
+        ConvGemmArgs a = cargs(e, e->fin, N, T, B);
+        a.a0 = ts->L[L - 1].x3_16; a.c0 = C; a.a1 = ts->x3lo; a.c1 = C; a.c2 = C; a.mask = m; a.flags = GF_MASK; a.out32 = ts->v32;
+        HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
+    }
+    HIPCHK(e, launch_from_time_major(ts->L[L - 1].x3, B, C, T, C, x_out, s));
+    HIPCHK(e, launch_from_time_major(ts->v32, B, e->M, T, Mp, mu_out, s));
+    HIPCHK(e, hipMemcpyAsync(mask_out, ts->maskbuf, (size_t)B * T * 4, hipMemcpyDeviceToDevice, s));
+    capture_train(e, ts, s);
+    ts->have_fwd = true;
+    ts->serial += 1;
+    ts->gbase = ts->grad_flat; ts->next_part = 0;
+    return ST_OK;
 }
 
 }  // extern "C"
@@ -685,27 +782,36 @@ int recentre(st_engine* e, TrainState* ts, const BwdDims& d, bool have_max, hipS
 }
 inline unsigned* next_cells(TrainState* ts) { return ts->cells_ring + (size_t)ts->cell_idx * kMaxCellWords; }
 
-int bwd_head(st_engine* e, TrainState* ts, const float* grad_out, hipStream_t s) {
+// out = (W x + b) * mask, the last layer of both trained modules (the decoder's final_proj, the text encoder's proj): the pass-wide
+// gradient scale from d out, d out as the masked 16-bit operand, its weight gradient on the side stream and dX = W^T d out.
+int bwd_out_proj(st_engine* e, TrainState* ts, const float* grad_out, const char* name, hipStream_t s) {
     const BwdDims d = bwd_dims(e, ts);
     const int C = d.C, M = d.M, Mp = d.Mp, L = d.L, N = d.N, B = d.B, T = d.T;
     const int64_t R = d.R;
     const float* m = ts->maskbuf;
+    const std::string n(name);
+    int rc;
+    HIPCHK(e, launch_grad_scale(grad_out, (int64_t)B * M * T, ts->gbits, ts->gsc, s));
+    HIPCHK(e, launch_to_time_major(e->dt, grad_out, B, M, T, Mp, ts->gin, nullptr, nullptr, s));
+    HIPCHK(e, launch_cast16(e->dt, ts->gin, m, B, T, Mp, R, ts->gsc, ts->dy[TrainState::DY_HEAD], s));
+    WgradOut o = {G(ts, n + ".weight"), C, 0, C, 0, M, G(ts, n + ".bias")};
+    if ((rc = wgrad_side(e, ts, TrainState::DY_HEAD, ts->L[L - 1].x3_16, C, nullptr, 0, Mp, 1, &o, 1, s))) return rc;
+    ConvGemmArgs a = cargs(e, ts->finT, N, T, B); a.a0 = ts->dy[TrainState::DY_HEAD]; a.c0 = Mp; a.mask = m; a.flags = GF_MASK; a.out32 = ts->dX;
+    HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
+    return ST_OK;
+}
+
+int bwd_head(st_engine* e, TrainState* ts, const float* grad_out, hipStream_t s) {
+    const BwdDims d = bwd_dims(e, ts);
+    const int C = d.C, L = d.L;
+    const int64_t R = d.R;
     int rc;
     const bool cap = e->capture;
     // ONE memset per backward: the maximum cells of the re-centring points, the attention kernels' max / bound cells of every block.
     // (d ada / d film rows, the per-item linears' gradients and d c / d tau are WRITTEN by their first producer: no zero fills.)
     HIPCHK(e, hipMemsetAsync(ts->zero_region, 0, ts->zero_bytes, s));
     ts->cell_idx = 0; ts->gsc = ts->gsc_ring;
-    // d v (time-major, masked: out = (W x + b) * mask), as the 16-bit operand of the first GEMMs
-    HIPCHK(e, launch_grad_scale(grad_out, (int64_t)B * M * T, ts->gbits, ts->gsc, s));
-    HIPCHK(e, launch_to_time_major(e->dt, grad_out, B, M, T, Mp, ts->gin, nullptr, nullptr, s));
-    HIPCHK(e, launch_cast16(e->dt, ts->gin, m, B, T, Mp, R, ts->gsc, ts->dy[TrainState::DY_HEAD], s));
-    {   // final_proj
-        WgradOut o = {G(ts, "final_proj.weight"), C, 0, C, 0, M, G(ts, "final_proj.bias")};
-        if ((rc = wgrad_side(e, ts, TrainState::DY_HEAD, ts->L[L - 1].x3_16, C, nullptr, 0, Mp, 1, &o, 1, s))) return rc;
-        ConvGemmArgs a = cargs(e, ts->finT, N, T, B); a.a0 = ts->dy[TrainState::DY_HEAD]; a.c0 = Mp; a.mask = m; a.flags = GF_MASK; a.out32 = ts->dX;
-        HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
-    }
+    if ((rc = bwd_out_proj(e, ts, grad_out, "final_proj", s))) return rc;
     if (cap) { capture(e, "g.scale", ts->gsc, 2, false, s); capture(e, "g.x3_" + std::to_string(L - 1), ts->dX, R * C, false, s); }
     return ST_OK;
 }
@@ -742,8 +848,10 @@ int bwd_block(st_engine* e, TrainState* ts, int i, hipStream_t s) {
         // re-centred on the running gradient here and after each LayerNorm backward (recentre), so that every 16-bit operand
         // derived from it sits in f16's range.  Every fp32 result is un-scaled by the pair current at the time it is written; a
         // long-skip gradient remembers the scale it was written at (skip_sc) and is converted when it is added.
-        // (block i + 1 wrote dX last through add_rescaled -- which published the maximum -- when it lies in the first half, else through a GEMM)
-        if (i < L - 1 && (rc = recentre(e, ts, d, i + 1 < L / 2, s))) return rc;
+        // (block i + 1 wrote dX last through add_rescaled -- which published the maximum -- when it lies in the first half, else through a GEMM;
+        // in the text encoder through mask_bwd, which publishes it too)
+        const bool dec = e->kind == 0;
+        if (i < L - 1 && (rc = recentre(e, ts, d, !dec || i + 1 < L / 2, s))) return rc;
         if (cap) capture(e, "g.scale_" + std::to_string(i), ts->gsc, 2, false, s);      // the scale block i's captured tensors carry
         RedSites sites; memset(&sites, 0, sizeof(sites));      // the block's per-(item, channel) sums: ONE reduce launch at its end
         auto site = [&](int k, int K, float* out, int out_stride, int off0, int off1) {
@@ -828,12 +936,16 @@ int bwd_block(st_engine* e, TrainState* ts, int i, hipStream_t s) {
         if (cap) capture(e, "g.x1_" + std::to_string(i), ts->dX, R * C, false, s);
         if ((rc = recentre(e, ts, d, true, s))) return rc;
         if (cap) capture(e, "g.scale_b" + std::to_string(i), ts->gsc, 2, false, s);      // ... and of what follows (g.xin_i)
-        // ---- x1 = (gamma * xpre + beta) * mask
-        if (i >= L / 2) HIPCHK(e, ts->side.wait_site(TrainState::DY_LSC, s));
-        HIPCHK(e, launch_film_bwd(e->dt, xpre_of(ts, i, L), ts->film + (size_t)i * N * 2 * C, 2 * C, N, m, B, T, N, ts->dX,
-                                  i >= L / 2 ? ts->dy[TrainState::DY_LSC] : nullptr, site(4, 2, ts->dfilm + (size_t)i * N * 2 * C, 2 * C, 0, C), s));
+        // ---- x1 = (gamma * xpre + beta) * mask  (text encoder: x1 = xpre * mask)
+        if (!dec) {
+            HIPCHK(e, launch_mask_bwd(m, B, T, N, ts->dX, i > 0 ? next_cells(ts) : nullptr, s));
+        } else {
+            if (i >= L / 2) HIPCHK(e, ts->side.wait_site(TrainState::DY_LSC, s));
+            HIPCHK(e, launch_film_bwd(e->dt, xpre_of(ts, i, L), ts->film + (size_t)i * N * 2 * C, 2 * C, N, m, B, T, N, ts->dX,
+                                      i >= L / 2 ? ts->dy[TrainState::DY_LSC] : nullptr, site(4, 2, ts->dfilm + (size_t)i * N * 2 * C, 2 * C, 0, C), s));
+        }
         HIPCHK(e, launch_reduce_sites(sites, N, chunks, s));
-        if (i >= L / 2) {   // long-skip conv: xpre_i = W [x3_{i-1} ; skip] + b
+        if (dec && i >= L / 2) {   // long-skip conv: xpre_i = W [x3_{i-1} ; skip] + b
             const int j = i - L / 2, src = L - 1 - i;
             const std::string n = "lsc_layers." + std::to_string(j);
             const void* skip16 = src == 0 ? ts->h0_16 : ts->L[src - 1].x3_16;
@@ -846,7 +958,7 @@ int bwd_block(st_engine* e, TrainState* ts, int i, hipStream_t s) {
             HIPCHK(e, gemm(e, K, EPI_F32, a, s));
         }
         // x3_{i-1} (or the in_proj output) is also a long-skip source of a later block: add that gradient
-        if (i < L / 2) HIPCHK(e, launch_add_rescaled(ts->dX, ts->dskip[i], R * C, ts->gsc, ts->skip_gsc[i], i > 0 ? next_cells(ts) : nullptr, s));
+        if (dec && i < L / 2) HIPCHK(e, launch_add_rescaled(ts->dX, ts->dskip[i], R * C, ts->gsc, ts->skip_gsc[i], i > 0 ? next_cells(ts) : nullptr, s));
         if (cap) capture(e, "g.xin_" + std::to_string(i), ts->dX, R * C, false, s);
     }
     {   // this block's per-item linears: adaLN modulation (-> d c), FiLM (-> d tau); its d ada / d film rows are complete now.
@@ -869,6 +981,7 @@ int bwd_block(st_engine* e, TrainState* ts, int i, hipStream_t s) {
             HIPCHK(e, launch_linear_bwd_w(ts->cvec, ts->dada_pre, N, e->G, C, 0, g0w, g0b, 0, s));
             HIPCHK(e, launch_linear_bwd_in(ts->cvec, ts->dada_pre, P(e, p0 + "weight"), N, e->G, C, 0, ts->dcvec, acc, s));
         }
+        if (e->kind != 0) return ST_OK;      // (the text encoder's blocks have no FiLM)
         const std::string pf = "blocks." + std::to_string(i) + ".time_fusion.film.";
         gw = G(ts, pf + "weight"); gb = G(ts, pf + "bias");
         const float* dfo = ts->dfilm + (size_t)i * N * 2 * C;
@@ -890,6 +1003,7 @@ int bwd_linears(st_engine* e, TrainState* ts, int lo, int hi, int acc, hipStream
             const std::string pa = e->blk(i) + "adaLN_modulation.2.";
             ja.in[ja.n] = ts->cvec; ja.dout[ja.n] = ts->dada + (size_t)i * N * 6 * C; ja.W[ja.n] = P(e, pa + "weight");
             ja.dW[ja.n] = G(ts, pa + "weight"); ja.db[ja.n] = G(ts, pa + "bias"); ja.n += 1;
+            if (e->kind != 0) continue;      // (the text encoder's blocks have no FiLM)
             const std::string pf = "blocks." + std::to_string(i) + ".time_fusion.film.";
             jf.in[jf.n] = ts->tau; jf.dout[jf.n] = ts->dfilm + (size_t)i * N * 2 * C; jf.W[jf.n] = P(e, pf + "weight");
             jf.dW[jf.n] = G(ts, pf + "weight"); jf.db[jf.n] = G(ts, pf + "bias"); jf.n += 1;
@@ -897,6 +1011,7 @@ int bwd_linears(st_engine* e, TrainState* ts, int lo, int hi, int acc, hipStream
         const int a = (acc || i0 > lo) ? 1 : 0;
         HIPCHK(e, launch_linear_bwd_w_multi(ja, N, C, 6 * C, 1, s));
         HIPCHK(e, launch_linear_bwd_in_multi(ja, ts->cvec, N, C, 6 * C, 1, ts->dcvec, a, s));
+        if (!jf.n) continue;
         HIPCHK(e, launch_linear_bwd_w_multi(jf, N, C, 2 * C, 0, s));
         HIPCHK(e, launch_linear_bwd_in_multi(jf, ts->tau, N, C, 2 * C, 0, ts->dtau, a, s));
     }
@@ -965,13 +1080,55 @@ int bwd_tail(st_engine* e, TrainState* ts, float* grad_x, float* grad_mu, float*
     return ST_OK;
 }
 
-int bwd_check(st_engine* e, int64_t serial, int B_, int T_, const char* who) {
-    if (e->kind != 0 || !e->train || !e->train->have_fwd)
-        return e->fail(ST_ERR_STATE, std::string(who) + " needs a preceding st_train_forward (none held: never run, or invalidated by a parameter update)");
+int bwd_check(st_engine* e, int kind, int64_t serial, int B_, int T_, const char* who) {
+    if (e->kind != kind || !e->train || !e->train->have_fwd)
+        return e->fail(ST_ERR_STATE, std::string(who) + (kind == 0 ? " needs a preceding st_train_forward" : " needs a preceding st_text_encoder_train_forward") +
+                       " (none held: never run, or invalidated by a parameter update)");
     if (serial != e->train->serial || B_ != e->train->B || T_ != e->train->T)
         return e->fail(ST_ERR_STATE, std::string(who) + ": the engine holds the activations of forward #" + std::to_string(e->train->serial) +
                        " (B=" + std::to_string(e->train->B) + ", T=" + std::to_string(e->train->T) + "), not of #" + std::to_string(serial) +
                        " (B=" + std::to_string(B_) + ", T=" + std::to_string(T_) + "): one backward per forward, before the next grad-enabled forward");
+    return ST_OK;
+}
+
+// ---- text encoder (kind 1): d mu_x through proj and / or d x straight into the last block's output, the L blocks, d emb.weight
+int bwd_head_text(st_engine* e, TrainState* ts, const float* grad_x, const float* grad_mu, hipStream_t s) {
+    const BwdDims d = bwd_dims(e, ts);
+    const int C = d.C, M = d.M, B = d.B, T = d.T;
+    const int64_t R = d.R;
+    int rc;
+    HIPCHK(e, hipMemsetAsync(ts->zero_region, 0, ts->zero_bytes, s));
+    ts->cell_idx = 0; ts->gsc = ts->gsc_ring;
+    if (grad_mu) {      // mu_x = (W x + b) * mask
+        if ((rc = bwd_out_proj(e, ts, grad_mu, "proj", s))) return rc;
+    } else {            // only d x: proj gets no gradient
+        HIPCHK(e, launch_grad_scale(grad_x, (int64_t)B * C * T, ts->gbits, ts->gsc, s));
+        HIPCHK(e, hipMemsetAsync(ts->dX, 0, (size_t)R * C * 4, s));
+        HIPCHK(e, hipMemsetAsync(G(ts, "proj.weight"), 0, (size_t)M * C * 4, s));
+        HIPCHK(e, hipMemsetAsync(G(ts, "proj.bias"), 0, (size_t)M * 4, s));
+    }
+    if (grad_x) {       // x is the last block's output: d x adds to its gradient at the current scale, which is then re-centred on the sum
+        HIPCHK(e, launch_to_time_major(e->dt, grad_x, B, C, T, C, ts->tmpC, nullptr, nullptr, s));
+        HIPCHK(e, hipMemsetD32Async((hipDeviceptr_t)ts->unit_sc, 0x3f800000u, 4, s));      // {1, 1}: grad_x is in unscaled units
+        HIPCHK(e, launch_add_rescaled(ts->dX, ts->tmpC, R * C, ts->gsc, ts->unit_sc, next_cells(ts), s));
+        if ((rc = recentre(e, ts, d, true, s))) return rc;
+    }
+    return ST_OK;
+}
+
+int bwd_text(st_engine* e, TrainState* ts, const float* grad_x, const float* grad_mu, float* grad_c, hipStream_t s) {
+    ProfScope prof(e, s, PC_TRAIN_BWD, 0);
+    ForkGuard guard{ts->side, s};
+    const int L = e->L, C = e->C;
+    int rc;
+    if ((rc = bwd_head_text(e, ts, grad_x, grad_mu, s))) return rc;
+    for (int i = L - 1; i >= 0; --i) if ((rc = bwd_block(e, ts, i, s))) return rc;
+    if ((rc = bwd_linears(e, ts, 0, L, 0, s))) return rc;
+    // x = emb[token] * sqrt(C): dX is d (block 0's input), masked by its entry, in units of the current scale pair
+    HIPCHK(e, launch_emb_bwd(ts->dX, C, ts->ids, (int64_t)ts->B * ts->T, e->n_vocab, sqrtf((float)C), ts->gsc, ts->emb_ws,
+                             G(ts, "emb.weight"), s));
+    if (grad_c) HIPCHK(e, hipMemcpyAsync(grad_c, ts->dcvec, (size_t)ts->B * e->G * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(e, ts->side.join(s));
     return ST_OK;
 }
 
@@ -1002,7 +1159,7 @@ extern "C" {
 int st_train_backward(st_engine* e, int64_t serial, int B_, int T_, const float* grad_out, float* grad_x, float* grad_mu,
                       float* grad_c, void* stream) {
     if (!e) return ST_ERR_INVALID;
-    int rc = bwd_check(e, serial, B_, T_, "st_train_backward"); if (rc) return rc;
+    int rc = bwd_check(e, 0, serial, B_, T_, "st_train_backward"); if (rc) return rc;
     if (!grad_out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     HIPCHK(e, hipSetDevice(e->device));
     TrainState* ts = e->train;
@@ -1016,7 +1173,7 @@ int st_train_backward(st_engine* e, int64_t serial, int B_, int T_, const float*
 int st_train_backward_part(st_engine* e, int64_t serial, int B_, int T_, int part, const float* grad_out, float* grad_flat,
                            int64_t grad_numel, float* grad_x, float* grad_mu, float* grad_c, void* stream) {
     if (!e) return ST_ERR_INVALID;
-    int rc = bwd_check(e, serial, B_, T_, "st_train_backward_part"); if (rc) return rc;
+    int rc = bwd_check(e, 0, serial, B_, T_, "st_train_backward_part"); if (rc) return rc;
     TrainState* ts = e->train;
     if (part < 0 || part > 2) return e->fail(ST_ERR_INVALID, "st_train_backward_part: part must be 0, 1 or 2");
     if (part == 0) {
@@ -1036,10 +1193,25 @@ int st_train_backward_part(st_engine* e, int64_t serial, int B_, int T_, int par
     return ST_OK;
 }
 
+int st_text_encoder_train_backward(st_engine* e, int64_t serial, int B_, int T_, const float* grad_x, const float* grad_mu,
+                                   float* grad_flat, float* grad_c, void* stream) {
+    if (!e) return ST_ERR_INVALID;
+    int rc = bwd_check(e, 1, serial, B_, T_, "st_text_encoder_train_backward"); if (rc) return rc;
+    if (!grad_x && !grad_mu) return e->fail(ST_ERR_INVALID, "st_text_encoder_train_backward: grad_x and grad_mu are both null");
+    HIPCHK(e, hipSetDevice(e->device));
+    TrainState* ts = e->train;
+    ts->gbase = grad_flat ? grad_flat : ts->grad_flat; ts->own_grads_valid = false;
+    rc = bwd_text(e, ts, grad_x, grad_mu, grad_c, (hipStream_t)stream);
+    ts->own_grads_valid = !rc && ts->gbase == ts->grad_flat;
+    ts->gbase = ts->grad_flat;
+    return rc;
+}
+
 int st_train_param_part(const st_engine* e, const char* name) {
-    if (!e || !name || e->kind != 0) return ST_ERR_INVALID;
+    if (!e || !name || (e->kind != 0 && e->kind != 1)) return ST_ERR_INVALID;
     const std::string n(name);
     if (!e->params.count(n)) return ST_ERR_INVALID;
+    if (e->kind == 1) return 0;      // the text encoder's backward is one part
     if (n.rfind("blocks.", 0) == 0) return atoi(n.c_str() + 7) >= e->L / 2 ? 0 : 1;
     if (n.rfind("final_proj.", 0) == 0 || n.rfind("lsc_layers.", 0) == 0) return 0;
     return 2;

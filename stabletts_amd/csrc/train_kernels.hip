@@ -373,6 +373,28 @@ hipError_t launch_film_bwd(int dtype, const float* xpre, const float* film, int 
     return hipGetLastError();
 }
 
+// x = xpre * mask (the text encoder's block entry, diffusion_transformer.py:106: no FiLM, so no d gamma / d beta sums):
+// dX = dX * mask in place, and max |dX| into the cell group `amax` (the next re-centring point's input; may be null)
+__global__ __launch_bounds__(256) void mask_bwd_kernel(const float* mask, int mask_mod, int T, float* dX, unsigned* amax) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int chunk = blockIdx.x, n = blockIdx.y;
+    float mx = 0.f;
+    for (int t = chunk * kRedRows + wave; t < T && t < (chunk + 1) * kRedRows; t += 4) {
+        const size_t o = ((size_t)n * T + t) * 256 + lane * 4;
+        const float m = mask[(size_t)(n % mask_mod) * T + t];
+        float4 d = *(const float4*)(dX + o);
+        d.x *= m; d.y *= m; d.z *= m; d.w *= m;
+        *(float4*)(dX + o) = d;
+        mx = absmax_take(absmax_take(absmax_take(absmax_take(mx, d.x), d.y), d.z), d.w);
+    }
+    if (amax) publish_block_max(mx, amax);      // (no early return above: every thread reaches the barrier inside)
+}
+
+hipError_t launch_mask_bwd(const float* mask, int mask_mod, int T, int n_items, float* dX, unsigned* amax, hipStream_t s) {
+    hipLaunchKernelGGL(mask_bwd_kernel, dim3(red_chunks(T), n_items), dim3(256), 0, s, mask, mask_mod, T, dX, amax);
+    return hipGetLastError();
+}
+
 template <class P>
 __global__ __launch_bounds__(256) void cast16_kernel(const float* x, const float* mask, int mask_mod, int T, int C, int64_t rows,
                                                      const float* scale, typename P::elem* y16) {

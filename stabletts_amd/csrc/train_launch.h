@@ -78,6 +78,16 @@ hipError_t launch_ln_bwd(const float* x, const float* dH, const float* ada, int 
 hipError_t launch_film_bwd(int dtype, const float* xpre, const float* film, int film_stride, int film_mod,
                            const float* mask, int mask_mod, int T, int n_items, float* dX, void* dX16, float* part,
                            hipStream_t s);
+// x = xpre * mask (text encoder block entry, no FiLM):  dX = dX * mask (in place); amax != null: max |dX| into that cell group
+hipError_t launch_mask_bwd(const float* mask, int mask_mod, int T, int n_items, float* dX, unsigned* amax, hipStream_t s);
+// Embedding weight gradient of the text encoder (emb_bwd.hip).  ids[r] = the forward's clamped token id of row r = b*T + t,
+// -1 for padded rows (t >= len_b).  dE[v][c] = scale * unscale[1] * sum over rows r with ids[r] == v of dX[r][c], summed in a
+// fixed order (stable counting sort by id, 32-row pieces, pieces added in order): bitwise repeatable, no float atomics; rows no
+// token touches get exact zeros.  Scratch from emb_bwd_scratch_bytes(R, n_vocab, C).
+hipError_t launch_emb_ids(const long long* tokens, const long long* lengths, int n_vocab, int B, int T, int* ids, hipStream_t s);
+size_t emb_bwd_scratch_bytes(int64_t R, int n_vocab, int C);
+hipError_t launch_emb_bwd(const float* dX, int C, const int* ids, int64_t R, int n_vocab, float scale, const float* unscale,
+                          void* scratch, float* dE, hipStream_t s);
 // dA16 = dU * mask * dropout * SiLU'(a16)   over [rows][F]
 hipError_t launch_silu_bwd(int dtype, const float* dU, const void* a16, const float* mask, int mask_mod, int T, int F,
                            int64_t rows, DropCfg drop, void* dA16, hipStream_t s);

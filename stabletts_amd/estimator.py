@@ -29,6 +29,32 @@ def _param_key(module):
     return tuple(ptrs), tuple(vers)
 
 
+def sync_engine_params(module, dev):
+    """Brings ``module._engine``'s view of the parameters up to date (shared by the decoder's and the text encoder's engine()).
+    A change of storage (first use, ``.to()``, dtype change) binds the fp32 tensors in place (st_bind_param, or fp32 staging
+    copies for a non-fp32 module) and packs the 16-bit copies (st_finalize); an in-place update (optimizer step) only re-packs,
+    as kernels on the current stream (st_repack).  Uses / sets ``_engine_key``, ``_engine_vers``, ``_staging``."""
+    key, vers = module._param_key()
+    if key != module._engine_key:
+        with torch.no_grad():
+            named = list(module.named_parameters())
+            if all(p.dtype == torch.float32 and p.is_contiguous() for _, p in named):
+                module._staging = None
+                bound = [(n, p.detach()) for n, p in named]
+            else:       # e.g. a .half() module: the engine reads fp32 staging copies
+                module._staging = [p.detach().to(dtype=torch.float32).contiguous() for _, p in named]
+                bound = [(n, s) for (n, _), s in zip(named, module._staging)]
+            module._engine.bind_parameters(bound)        # st_finalize synchronises the device: pending writes have landed
+        module._engine_key, module._engine_vers = key, vers
+    elif vers != module._engine_vers:
+        with torch.no_grad(), torch.cuda.device(dev):
+            if module._staging is not None:
+                for s, p in zip(module._staging, module.parameters()):
+                    s.copy_(p)
+            module._engine.repack(torch.cuda.current_stream(dev).cuda_stream)
+        module._engine_vers = vers
+
+
 class _ParamsOnly(nn.Module):
     def forward(self, *a, **k):  # pragma: no cover
         raise RuntimeError("parameter container: the computation runs in the native HIP engine")
@@ -202,25 +228,7 @@ class Decoder(nn.Module):
             self._engine_key = None
             if getattr(self, "_attn_split", False):
                 self._engine.set_option("attention_precision", 1)
-        key, vers = self._param_key()
-        if key != self._engine_key:
-            with torch.no_grad():
-                named = list(self.named_parameters())
-                if all(p.dtype == torch.float32 and p.is_contiguous() for _, p in named):
-                    self._staging = None
-                    bound = [(n, p.detach()) for n, p in named]
-                else:       # e.g. a .half() module: the engine reads fp32 staging copies
-                    self._staging = [p.detach().to(dtype=torch.float32).contiguous() for _, p in named]
-                    bound = [(n, s) for (n, _), s in zip(named, self._staging)]
-                self._engine.bind_parameters(bound)        # st_finalize synchronises the device: pending writes have landed
-            self._engine_key, self._engine_vers = key, vers
-        elif vers != self._engine_vers:
-            with torch.no_grad(), torch.cuda.device(dev):
-                if self._staging is not None:
-                    for s, p in zip(self._staging, self.parameters()):
-                        s.copy_(p)
-                self._engine.repack(torch.cuda.current_stream(dev).cuda_stream)
-            self._engine_vers = vers
+        sync_engine_params(self, dev)
         return self._engine
 
     AUTO_SPLIT_LSE = 50.0      # natural units; seeded / initialised weights give ~10, the arg-max regime of DESIGN.md section 2 80-200

@@ -5,13 +5,18 @@ of the hot path, on the same DiT block kernels).
 signature (:34) and the checkpoint key layout (``emb.weight``, ``encoder.<i>.attn.conv_q.weight``, ...,
 ``proj.bias``), but embedding, the ``n_layers`` DiTConVBlocks (adaLN-Zero, RoPE attention, conv-FFN) and the
 output projection run as hand-written gfx950 kernels behind ``st_text_encoder_forward``
-(include/stabletts_hip.h).  Inference only (no autograd graph); there is no PyTorch fallback.
+(include/stabletts_hip.h); there is no PyTorch fallback.
+
+Under autograd (a parameter or ``c`` requires grad) the forward is ``st_text_encoder_train_forward``, which keeps the
+activations in the engine, and ``loss.backward()`` runs ``st_text_encoder_train_backward``: every parameter gradient
+(``emb.weight`` included) is a view of one flat buffer the kernels wrote, and ``c`` receives d loss / d c.  Train-mode
+dropout is counter-based with a seed drawn from torch's CPU generator, as in the decoder's training path.
 """
 import torch
 import torch.nn as nn
 
 from . import _lib
-from .estimator import DiTConVBlock, _param_key
+from .estimator import DiTConVBlock, _param_key, sync_engine_params
 
 
 class TextEncoder(nn.Module):
@@ -32,6 +37,8 @@ class TextEncoder(nn.Module):
         self.initialize_weights()
         self._engine = None
         self._engine_key = None
+        self._engine_vers = None
+        self._staging = None
 
     def initialize_weights(self):
         """adaLN-Zero (models/text_encoder.py:29-32)."""
@@ -42,15 +49,15 @@ class TextEncoder(nn.Module):
     def __getstate__(self):
         st = self.__dict__.copy()      # the ctypes engine handle is per-process, never copied/pickled
         st["_engine"] = None
-        st["_engine_key"] = None
+        st["_engine_key"] = st["_engine_vers"] = st["_staging"] = None
         return st
 
     def _param_key(self):
         return _param_key(self)
 
     def sync_weights(self):
-        """Force a weight re-upload at the next call (after writes through ``p.data`` that bypass the version counter)."""
-        self._engine_key = None
+        """Force a weight re-pack at the next call (after writes through ``p.data`` that bypass the version counter)."""
+        self._engine_vers = None
 
     def _apply(self, fn, *a, **k):
         self._engine_key = None
@@ -61,7 +68,9 @@ class TextEncoder(nn.Module):
         return super()._load_from_state_dict(*a, **k)
 
     def engine(self):
-        """The native handle bound to the device of the parameters, with weights in sync."""
+        """The native handle bound to the device of the parameters, with weights in sync.  As the decoder's
+        (estimator.py): the engine reads the fp32 parameters in place (st_bind_param) and, after an in-place update such
+        as an optimizer step, re-packs its 16-bit copies on the current stream (st_repack): no re-upload, no allocation."""
         p0 = next(self.parameters())
         if p0.device.type != "cuda":
             raise RuntimeError("stabletts_amd: the text encoder runs only on a HIP device (move the module with "
@@ -74,12 +83,7 @@ class TextEncoder(nn.Module):
                                        self.n_layers, self.kernel_size, self.gin_channels, self.operand_dtype, dev,
                                        text_encoder_vocab=self.n_vocab)
             self._engine_key = None
-        key = self._param_key()
-        if key != self._engine_key:
-            with torch.no_grad():
-                torch.cuda.synchronize(dev)
-                self._engine.load_state_dict(self.state_dict())
-            self._engine_key = key
+        sync_engine_params(self, dev)
         return self._engine
 
     def forward(self, x: torch.Tensor, c: torch.Tensor, x_lengths: torch.Tensor):
@@ -88,13 +92,12 @@ class TextEncoder(nn.Module):
         if self.emb.weight.device.type != "cuda":
             self.engine()      # raises: no CPU fallback
         if torch.is_grad_enabled() and (c.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("the native TextEncoder is inference-only (no backward kernels): call it under "
-                                      "torch.no_grad(), or train with the reference module and load its checkpoint")
+            names, params = zip(*self.named_parameters())
+            return _TextEncoderFn.apply(self, names, x, c, x_lengths, *params)
         with torch.no_grad():
             return self._forward(x, c, x_lengths)
 
-    def _forward(self, x, c, x_lengths):
-        eng = self.engine()
+    def _inputs(self, x, c, x_lengths):
         dev = self.emb.weight.device
         for name, t in (("x", x), ("c", c), ("x_lengths", x_lengths)):
             if t.device != dev:
@@ -105,9 +108,70 @@ class TextEncoder(nn.Module):
         tok = x.detach().to(device=dev, dtype=torch.long).contiguous()
         lens = x_lengths.detach().to(device=dev, dtype=torch.long).contiguous()
         cc = c.detach().to(device=dev, dtype=torch.float32).contiguous()
+        return dev, tok, lens, cc
+
+    def _forward(self, x, c, x_lengths):
+        eng = self.engine()
+        dev, tok, lens, cc = self._inputs(x, c, x_lengths)
+        B, T = tok.shape
         h = torch.empty(B, self.hidden_channels, T, device=dev, dtype=torch.float32)
         mu_x = torch.empty(B, self.out_channels, T, device=dev, dtype=torch.float32)
         mask = torch.empty(B, 1, T, device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
             eng.text_encoder_forward(tok, lens, cc, h, mu_x, mask, torch.cuda.current_stream(dev).cuda_stream)
         return h, mu_x, mask
+
+
+class _TextEncoderFn(torch.autograd.Function):
+    """TextEncoder.forward under autograd: st_text_encoder_train_forward keeps the activations in the engine, the backward is
+    st_text_encoder_train_backward.  Inputs (module, names, ids, c, lengths, *parameters); outputs (x, mu_x, x_mask)."""
+
+    @staticmethod
+    def forward(ctx, mod, names, x, c, x_lengths, *params):
+        eng = mod.engine()
+        dev, tok, lens, cc = mod._inputs(x, c, x_lengths)
+        B, T = tok.shape
+        f32 = dict(device=dev, dtype=torch.float32)
+        h = torch.empty(B, mod.hidden_channels, T, **f32)
+        mu_x = torch.empty(B, mod.out_channels, T, **f32)
+        mask = torch.empty(B, 1, T, **f32)
+        p_drop = float(mod.p_dropout) if mod.training else 0.0
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p_drop > 0.0 else 0
+        with torch.cuda.device(dev):
+            eng.text_encoder_train_forward(tok, lens, cc, h, mu_x, mask, p_drop, seed, torch.cuda.current_stream(dev).cuda_stream)
+        ctx.mod, ctx.eng, ctx.serial, ctx.vers = mod, eng, eng.train_serial(), mod._param_key()[1]
+        ctx.names, ctx.params, ctx.shape, ctx.dev, ctx.c_shape = names, params, (B, T), dev, tuple(cc.shape)
+        ctx.mark_non_differentiable(mask)
+        ctx.set_materialize_grads(False)
+        return h, mu_x, mask
+
+    @staticmethod
+    def backward(ctx, grad_x, grad_mu, _grad_mask):
+        mod, eng = ctx.mod, ctx.eng
+        if (eng is not mod._engine or eng.handle is None or eng.train_serial() != ctx.serial
+                or mod._param_key()[1] != ctx.vers):
+            raise RuntimeError(
+                "stabletts_amd: this backward's activations are gone -- the text encoder's engine keeps the activations of ONE "
+                "grad-enabled forward, and another grad-enabled forward, an optimizer step / parameter update or a device move "
+                "happened since.  Call backward() before the next grad-enabled forward or parameter update.")
+        need = ctx.needs_input_grad          # (mod, names, x, c, x_lengths, *params)
+        if grad_x is None and grad_mu is None:
+            return (None,) * len(need)
+        dev = ctx.dev
+        B, T = ctx.shape
+        prep = lambda g: g.detach().to(device=dev, dtype=torch.float32).contiguous() if g is not None else None      # noqa: E731
+        gx, gmu = prep(grad_x), prep(grad_mu)
+        lay = eng.grad_layout()
+        with torch.cuda.device(dev):
+            # (zeros, not empty: the 64-byte alignment gaps between the slices are never written)
+            flat = torch.zeros(lay[None], device=dev, dtype=torch.float32)
+            gc = torch.empty(ctx.c_shape, device=dev, dtype=torch.float32) if need[3] else None
+            eng.text_encoder_train_backward(ctx.serial, B, T, gx, gmu, flat, gc, torch.cuda.current_stream(dev).cuda_stream)
+        pg = []
+        for name, p, nd in zip(ctx.names, ctx.params, need[5:]):
+            if not nd:
+                pg.append(None)
+                continue
+            off, n, _ = lay[name]
+            pg.append(flat[off:off + n].view(p.shape))
+        return (None, None, None, gc, None, *pg)
