@@ -268,6 +268,26 @@ int st_create_duration_predictor(const st_duration_predictor_config* cfg, int de
 int st_duration_predictor_forward(st_engine* e, const float* x, const float* x_mask, const float* g, float* logw_out,
                                   int B, int Tx, void* stream);
 
+/* ---- style-encoder / duration-predictor training: autograd counterparts of the two forwards above, fp32 like them.
+ * The *_train_forward calls compute what the inference forwards compute (bit for bit when p_dropout == 0) and keep the
+ * activations of this ONE call in the engine (buffers that grow on demand, then are reused; the inputs are copied in).
+ * Train-mode dropout is counter-based with the hash and seed words of st_train_forward and the salts
+ *     style encoder: 64 spectral.2, 65 spectral.5, 66 temporal.0, 67 temporal.1 (the GLU product, before the residual add),
+ *                    68 the attention probabilities;      duration predictor: 72 after norm1, 73 after norm2;
+ * the backward re-evaluates the masks.  st_train_serial reports the forward held (0: none; a re-bind / st_finalize drops it).
+ * The backward takes d loss / d c (B, style_vector_dim) resp. d loss / d logw (B, 1, Tx) and writes EVERY parameter gradient
+ * into grad_flat: st_train_grad_numel() floats in the layout of st_train_grad_offset (parameter-name order, 64-byte aligned
+ * slices; the gaps are not written).  Neither module has an input gradient (the reference detaches x and g, duration_predictor.py
+ * :25-26; the mel is data).  (serial, B, T) must be those of the held forward (ST_ERR_STATE otherwise).  No atomics: the
+ * gradients are bitwise repeatable. */
+int st_style_encoder_train_forward(st_engine* e, const float* mel, const float* mask, float* c_out, int B, int T,
+                                   float p_dropout, uint64_t seed, void* stream);
+int st_style_encoder_train_backward(st_engine* e, int64_t serial, int B, int T, const float* grad_c, float* grad_flat, void* stream);
+int st_duration_predictor_train_forward(st_engine* e, const float* x, const float* x_mask, const float* g, float* logw_out,
+                                        int B, int Tx, float p_dropout, uint64_t seed, void* stream);
+int st_duration_predictor_train_backward(st_engine* e, int64_t serial, int B, int Tx, const float* grad_logw, float* grad_flat,
+                                         void* stream);
+
 /* ---- training: autograd counterpart of Decoder.forward ------------------------------------------- */
 
 /* Replaces Decoder.forward(t, x, mask, mu, c) UNDER AUTOGRAD as CFMDecoder.compute_loss calls it (models/flow_matching.py:99,
@@ -278,7 +298,8 @@ int st_duration_predictor_forward(st_engine* e, const float* x, const float* x_m
 int st_train_forward(st_engine* e, const float* t, const float* x, const float* mu, const float* mask, const float* c,
                      float* out, int B, int T, float p_dropout, uint64_t seed, void* stream);
 
-/* Serial number of the st_train_forward whose activations the engine holds now (monotonically increasing from 1;
+/* Serial number of the st_train_forward (or of the text-encoder / style-encoder / duration-predictor training forward, on
+ * those handles) whose activations the engine holds now (monotonically increasing from 1;
  * 0 = none: never run, or invalidated by a parameter update).  The engine keeps the activations of ONE forward. */
 int64_t st_train_serial(const st_engine* e);
 

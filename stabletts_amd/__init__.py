@@ -9,7 +9,8 @@ Public surface mirrors the reference's ``models/flow_matching.py``:
 ``install(text_encoder=True)`` also registers ``stabletts_amd.text_encoder`` as ``models.text_encoder``
 (``models/model.py:6``), the caller side of the path on the same block kernels;
 ``install(reference_encoder=True, duration_predictor=True)`` registers the fp32 ``MelStyleEncoder`` /
-``DurationPredictor`` as ``models.reference_encoder`` / ``models.duration_predictor`` (``models/model.py:8-9``);
+``DurationPredictor`` as ``models.reference_encoder`` / ``models.duration_predictor`` (``models/model.py:8-9``), inference-only;
+with ``"train"`` instead of ``True`` they register subclasses that also train natively (``native_training = True``);
 ``install(monotonic_align=True)`` registers ``stabletts_amd.monotonic_align`` as ``monotonic_align`` (``models/model.py:5``),
 so the reference's training ``forward`` imports and runs its alignment search on the device, without numba.
 """
@@ -30,12 +31,18 @@ def install(text_encoder=False, vocoder=False, reference_encoder=False, duration
     if vocoder:
         from . import vocos
         sys.modules["vocoders.vocos.models.model"] = vocos      # api.py:26-28: from vocoders.vocos.models.model import Vocos
-    if reference_encoder:
-        from . import reference_encoder as re_
+    if reference_encoder == "train":                             # MelStyleEncoder with native_training = True
+        from . import reference_encoder_train as re_
         sys.modules["models.reference_encoder"] = re_            # models/model.py:8
-    if duration_predictor:
-        from . import duration_predictor as dp
+    elif reference_encoder:
+        from . import reference_encoder as re_
+        sys.modules["models.reference_encoder"] = re_
+    if duration_predictor == "train":                            # DurationPredictor with native_training = True
+        from . import duration_predictor_train as dp
         sys.modules["models.duration_predictor"] = dp            # models/model.py:9
+    elif duration_predictor:
+        from . import duration_predictor as dp
+        sys.modules["models.duration_predictor"] = dp
     if monotonic_align:
         from . import monotonic_align as ma
         sys.modules["monotonic_align"] = ma                      # models/model.py:5

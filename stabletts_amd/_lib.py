@@ -33,6 +33,8 @@ EXPORTS = [
     "st_cfm_loss_prep", "st_cfm_loss", "st_cfm_loss_backward", "st_cfm_loss_scratch_floats",
     "st_set_option", "st_get_option", "st_attention_stats",
     "st_create_style_encoder", "st_style_encoder_forward", "st_create_duration_predictor", "st_duration_predictor_forward",
+    "st_style_encoder_train_forward", "st_style_encoder_train_backward", "st_duration_predictor_train_forward",
+    "st_duration_predictor_train_backward",
     "st_maximum_path", "st_maximum_path_workspace_bytes", "st_mas_neg_cent",
 ]
 
@@ -190,6 +192,14 @@ def load():
     lib.st_create_duration_predictor.restype = c_int
     lib.st_duration_predictor_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]
     lib.st_duration_predictor_forward.restype = c_int
+    lib.st_style_encoder_train_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, ctypes.c_uint64, c_void_p]
+    lib.st_style_encoder_train_forward.restype = c_int
+    lib.st_style_encoder_train_backward.argtypes = [c_void_p, ctypes.c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    lib.st_style_encoder_train_backward.restype = c_int
+    lib.st_duration_predictor_train_forward.argtypes = [c_void_p] + [c_void_p] * 4 + [c_int, c_int, c_float, ctypes.c_uint64, c_void_p]
+    lib.st_duration_predictor_train_forward.restype = c_int
+    lib.st_duration_predictor_train_backward.argtypes = [c_void_p, ctypes.c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    lib.st_duration_predictor_train_backward.restype = c_int
     lib.st_maximum_path.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.st_maximum_path.restype = c_int
     lib.st_maximum_path_workspace_bytes.argtypes = [c_int, c_int, c_int]
@@ -325,6 +335,33 @@ class Engine:
         B, _, T = x.shape
         self._check(self.lib.st_duration_predictor_forward(self.handle, x.data_ptr(), x_mask.data_ptr(), g.data_ptr(),
                                                            logw_out.data_ptr(), B, T, ctypes.c_void_p(stream)))
+
+    def style_encoder_train_forward(self, mel, mask, c_out, p_dropout, seed, stream):
+        """st_style_encoder_forward that keeps the activations for style_encoder_train_backward (style-encoder handles)."""
+        B, _, T = mel.shape
+        self._check(self.lib.st_style_encoder_train_forward(self.handle, mel.data_ptr(), mask.data_ptr() if mask is not None else None,
+                                                            c_out.data_ptr(), B, T, float(p_dropout), int(seed), ctypes.c_void_p(stream)))
+
+    def style_encoder_train_backward(self, serial, B, T, grad_c, grad_flat, stream):
+        """Every parameter gradient into grad_flat (grad_layout()[None] floats) from d loss / d c."""
+        if grad_flat.numel() != self.grad_layout()[None]:
+            raise ValueError("grad_flat must hold grad_layout()[None] floats")
+        self._check(self.lib.st_style_encoder_train_backward(self.handle, int(serial), B, T, grad_c.data_ptr(), grad_flat.data_ptr(),
+                                                             ctypes.c_void_p(stream)))
+
+    def duration_predictor_train_forward(self, x, x_mask, g, logw_out, p_dropout, seed, stream):
+        """st_duration_predictor_forward that keeps the activations for duration_predictor_train_backward."""
+        B, _, T = x.shape
+        self._check(self.lib.st_duration_predictor_train_forward(self.handle, x.data_ptr(), x_mask.data_ptr(), g.data_ptr(),
+                                                                 logw_out.data_ptr(), B, T, float(p_dropout), int(seed),
+                                                                 ctypes.c_void_p(stream)))
+
+    def duration_predictor_train_backward(self, serial, B, T, grad_logw, grad_flat, stream):
+        """Every parameter gradient into grad_flat (grad_layout()[None] floats) from d loss / d logw."""
+        if grad_flat.numel() != self.grad_layout()[None]:
+            raise ValueError("grad_flat must hold grad_layout()[None] floats")
+        self._check(self.lib.st_duration_predictor_train_backward(self.handle, int(serial), B, T, grad_logw.data_ptr(),
+                                                                  grad_flat.data_ptr(), ctypes.c_void_p(stream)))
 
     # ---- training: forward that keeps activations + backward (include/stabletts_hip.h, "training")
     def train_forward(self, t, x, mu, mask, c, out, p_dropout, seed, stream):

@@ -697,6 +697,7 @@ void st_destroy(st_engine* e) {
     vocos_destroy(e);
     style_destroy(e);
     duration_destroy(e);
+    sd_train_destroy(e);
     if (e->gstream) hipStreamDestroy(e->gstream);
     e->part_streams.destroy();
     for (auto& kv : e->params) if (kv.second.dev && !kv.second.borrowed) hipFree(kv.second.dev);
@@ -798,7 +799,11 @@ int st_finalize(st_engine* e) {
     for (auto& kv : e->params)
         if (!kv.second.loaded) return e->fail(ST_ERR_STATE, "parameter not loaded: " + kv.first);
     HIPCHK(e, hipDeviceSynchronize());
-    if (e->kind >= 3) { e->finalized = true; return ST_OK; }      // fp32 kernels read the loaded tensors in place: nothing to pack
+    if (e->kind >= 3) {      // fp32 kernels read the loaded tensors in place: nothing to pack
+        if (e->sdt) e->sdt->have = false;      // a re-bind / re-load: the held training activations are of other weights
+        e->finalized = true;
+        return ST_OK;
+    }
     if (e->kind == 2) {
         e->drop_graphs();
         for (void* p : e->owned) hipFree(p);
@@ -1241,6 +1246,7 @@ int st_profile_read(st_engine* e, int cls, int64_t* launches, double* total_ms, 
 int64_t st_device_bytes(const st_engine* e) {
     if (!e) return ST_ERR_INVALID;
     int64_t n = e->weight_bytes + (int64_t)e->ws_cap + train_bytes(e);
+    if (e->sdt) n += (int64_t)(e->sdt->act_cap + e->sdt->scr_cap);
     for (auto& kv : e->params) if (kv.second.dev && !kv.second.borrowed) n += kv.second.numel() * 4;
     return n;
 }

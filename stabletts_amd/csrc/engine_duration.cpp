@@ -4,6 +4,7 @@
 #include "engine_internal.h"
 #include "style_dp_launch.h"
 
+#include <algorithm>
 #include <string>
 
 using namespace st;
@@ -94,6 +95,147 @@ int st_duration_predictor_forward(st_engine* e, const float* x, const float* x_m
         a.out = logw_out; a.Cout = 1; a.B = B; a.T = Tx; a.taps = 1;
         HIPCHK(e, launch_sd_conv(a, s));
     }
+    return ST_OK;
+}
+
+}  // extern "C"
+
+// ---- training (kind 4): the forward above with its activations kept and dropout after norm1 / norm2 (salts 72, 73), and the
+// backward.  x and g get no gradient (the reference detaches them, :25-26); cond's gradient comes from conv1's data gradient.
+namespace {
+
+struct DurActs {        // float offsets into SdTrain::act; R = B * Tx
+    size_t x, mask, g, gb, r1, m1, s1, d1, r2, m2, s2, d2, end;
+};
+
+DurActs dur_acts(const st_duration_predictor_config& c, int B, int T) {
+    const size_t R = (size_t)B * T, F = c.filter_channels;
+    DurActs a{};
+    size_t off = 0;
+    auto want = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
+    a.x = want(R * c.in_channels); a.mask = want(R); a.g = want((size_t)B * c.gin_channels); a.gb = want((size_t)B * c.in_channels);
+    a.r1 = want(R * F); a.m1 = want(R); a.s1 = want(R); a.d1 = want(R * F);
+    a.r2 = want(R * F); a.m2 = want(R); a.s2 = want(R); a.d2 = want(R * F);
+    a.end = off;
+    return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int st_duration_predictor_train_forward(st_engine* e, const float* x, const float* x_mask, const float* g, float* logw_out,
+                                        int B, int Tx, float p_dropout, uint64_t seed, void* stream) {
+    if (!e) return ST_ERR_INVALID;
+    if (e->kind != 4) return e->fail(ST_ERR_STATE, "this handle is not a duration predictor (st_create_duration_predictor)");
+    if (!e->finalized) return e->fail(ST_ERR_STATE, "st_finalize() has not been called after loading parameters");
+    if (!x || !x_mask || !g || !logw_out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
+    if (B < 1 || Tx < 1) return e->fail(ST_ERR_INVALID, "B and Tx must be >= 1");
+    if (!(p_dropout >= 0.0f && p_dropout < 1.0f)) return e->fail(ST_ERR_INVALID, "p_dropout must be in [0, 1)");
+    const st_duration_predictor_config& c = e->dur->cfg;
+    const int Ci = c.in_channels, F = c.filter_channels, K = c.kernel_size, Gc = c.gin_channels;
+    const int64_t R = (int64_t)B * Tx;
+    if (R * F >= ((int64_t)1 << 31) || R * Ci >= ((int64_t)1 << 31)) return e->fail(ST_ERR_INVALID, "B*Tx too large");
+    HIPCHK(e, hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (!e->sdt) e->sdt = new SdTrain();
+    SdTrain* st = e->sdt;
+    st->have = false;
+    const DurActs A = dur_acts(c, B, Tx);
+    int rc = sd_train_grow(e, &st->act, &st->act_cap, A.end * 4); if (rc) return rc;
+    float* act = (float*)st->act;
+    auto at = [&](size_t o) { return act + o; };
+    HIPCHK(e, hipMemcpyAsync(at(A.x), x, (size_t)R * Ci * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(at(A.mask), x_mask, (size_t)R * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(at(A.g), g, (size_t)B * Gc * 4, hipMemcpyDeviceToDevice, s));
+    const float* mask = at(A.mask);
+    const SdDrop d1 = sd_make_drop(p_dropout, seed, 72), d2 = sd_make_drop(p_dropout, seed, 73);
+    {   // cond(g): per-item bias of in_channels
+        SdConvArgs a; a.in = at(A.g); a.Cin = Gc; a.w = P(e, "cond.weight"); a.bias = P(e, "cond.bias"); a.out = at(A.gb); a.Cout = Ci;
+        a.B = B; a.T = 1; a.taps = 1;
+        HIPCHK(e, launch_sd_conv(a, s));
+    }
+    {   // relu(conv1((x + cond(g)) * x_mask)) -> norm1 -> dropout
+        SdConvArgs a; a.in = at(A.x); a.addv = at(A.gb); a.imask = mask; a.Cin = Ci; a.w = P(e, "conv1.weight"); a.bias = P(e, "conv1.bias");
+        a.out = at(A.r1); a.Cout = F; a.B = B; a.T = Tx; a.taps = K; a.epi = SD_EPI_RELU;
+        HIPCHK(e, launch_sd_conv(a, s));
+        HIPCHK(e, launch_sd_layernorm_train(at(A.r1), at(A.d1), at(A.m1), at(A.s1), P(e, "norm1.weight"), P(e, "norm1.bias"), 1e-5f, d1, B, F, Tx, s));
+    }
+    {   // relu(conv2(x * x_mask)) -> norm2 -> dropout
+        SdConvArgs a; a.in = at(A.d1); a.imask = mask; a.Cin = F; a.w = P(e, "conv2.weight"); a.bias = P(e, "conv2.bias");
+        a.out = at(A.r2); a.Cout = F; a.B = B; a.T = Tx; a.taps = K; a.epi = SD_EPI_RELU;
+        HIPCHK(e, launch_sd_conv(a, s));
+        HIPCHK(e, launch_sd_layernorm_train(at(A.r2), at(A.d2), at(A.m2), at(A.s2), P(e, "norm2.weight"), P(e, "norm2.bias"), 1e-5f, d2, B, F, Tx, s));
+    }
+    {   // proj(x * x_mask) * x_mask
+        SdConvArgs a; a.in = at(A.d2); a.imask = mask; a.omask = mask; a.Cin = F; a.w = P(e, "proj.weight"); a.bias = P(e, "proj.bias");
+        a.out = logw_out; a.Cout = 1; a.B = B; a.T = Tx; a.taps = 1;
+        HIPCHK(e, launch_sd_conv(a, s));
+    }
+    st->serial += 1; st->have = true; st->B = B; st->T = Tx; st->p = p_dropout; st->seed = seed; st->masked = true;
+    return ST_OK;
+}
+
+int st_duration_predictor_train_backward(st_engine* e, int64_t serial, int B, int Tx, const float* grad_logw, float* grad_flat,
+                                         void* stream) {
+    if (!e) return ST_ERR_INVALID;
+    if (e->kind != 4) return e->fail(ST_ERR_STATE, "this handle is not a duration predictor (st_create_duration_predictor)");
+    if (!grad_logw || !grad_flat) return e->fail(ST_ERR_INVALID, "null tensor pointer");
+    SdTrain* st = e->sdt;
+    if (!st || !st->have) return e->fail(ST_ERR_STATE, "st_duration_predictor_train_backward needs a preceding st_duration_predictor_train_forward");
+    if (serial != st->serial || B != st->B || Tx != st->T)
+        return e->fail(ST_ERR_STATE, "st_duration_predictor_train_backward: the engine holds the activations of forward #" + std::to_string(st->serial) +
+                       " (B=" + std::to_string(st->B) + ", Tx=" + std::to_string(st->T) + "), not of #" + std::to_string(serial) +
+                       " (B=" + std::to_string(B) + ", Tx=" + std::to_string(Tx) + ")");
+    const st_duration_predictor_config& c = e->dur->cfg;
+    const int Ci = c.in_channels, F = c.filter_channels, K = c.kernel_size, Gc = c.gin_channels;
+    const int64_t R = (int64_t)B * Tx;
+    HIPCHK(e, hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    const DurActs A = dur_acts(c, B, Tx);
+    float* act = (float*)st->act;
+    auto at = [&](size_t o) { return act + o; };
+    const float* mask = at(A.mask);
+    const SdDrop d1 = sd_make_drop(st->p, st->seed, 72), d2 = sd_make_drop(st->p, st->seed, 73);
+
+    size_t ws = 0;
+    ws = std::max(ws, sd_wgrad_scratch_floats(B, F, 1, Tx, 1));
+    ws = std::max(ws, sd_wgrad_scratch_floats(B, F, F, Tx, K));
+    ws = std::max(ws, sd_wgrad_scratch_floats(B, Ci, F, Tx, K));
+    ws = std::max(ws, sd_wgrad_scratch_floats(B, Gc, Ci, 1, 1));
+    size_t off = 0;
+    auto want = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
+    const size_t o_dy = want(R), o_a = want(R * F), o_b = want(R * F), o_dx = want(R * Ci), o_dc = want((size_t)B * Ci), o_ws = want(ws);
+    int rc = sd_train_grow(e, &st->scr, &st->scr_cap, off * 4); if (rc) return rc;
+    float* scr = (float*)st->scr;
+    float* dY = scr + o_dy; float* Pa = scr + o_a; float* Pb = scr + o_b; float* dX = scr + o_dx; float* dC = scr + o_dc; float* wsp = scr + o_ws;
+
+    std::map<std::string, int64_t> goff;
+    train_grad_layout(e, &goff);
+    auto G = [&](const std::string& n) { return grad_flat + goff.at(n); };
+    auto wb = [&](const std::string& w, const std::string& b, const float* dy, int cout, const float* x, const float* addv, int cin, int taps, int T) {
+        SdWgradArgs a; a.dy = dy; a.in = x; a.addv = addv; a.dw = G(w); a.scratch = wsp;
+        a.imask = x == at(A.g) ? nullptr : mask;      // (cond: one frame per item, no mask)
+        a.B = B; a.Cin = cin; a.Cout = cout; a.T = T; a.taps = taps;
+        hipError_t r = launch_sd_wgrad(a, s);
+        if (r != hipSuccess) return r;
+        return launch_sd_sum_frames(dy, G(b), B, cout, T, 0, s);
+    };
+    auto dgrad = [&](const std::string& w, const float* dy, int cout, int cin, int taps, float* out) {     // masked: the input mask
+        SdConvArgs a; a.in = dy; a.Cin = cout; a.w = P(e, w); a.out = out; a.Cout = cin; a.B = B; a.T = Tx; a.taps = taps; a.omask = mask;
+        return launch_sd_conv_dgrad(a, s);
+    };
+    HIPCHK(e, launch_sd_mul_mask(grad_logw, mask, dY, B, 1, Tx, s));                      // logw = proj(.) * x_mask
+    HIPCHK(e, wb("proj.weight", "proj.bias", dY, 1, at(A.d2), nullptr, F, 1, Tx));
+    HIPCHK(e, dgrad("proj.weight", dY, 1, F, 1, Pa));                                      // d (dropped norm2 output)
+    HIPCHK(e, launch_sd_layernorm_bwd(Pa, at(A.r2), at(A.m2), at(A.s2), P(e, "norm2.weight"), Pb, G("norm2.weight"), G("norm2.bias"), d2, 1, B, F, Tx, s));
+    HIPCHK(e, wb("conv2.weight", "conv2.bias", Pb, F, at(A.d1), nullptr, F, K, Tx));
+    HIPCHK(e, dgrad("conv2.weight", Pb, F, F, K, Pa));
+    HIPCHK(e, launch_sd_layernorm_bwd(Pa, at(A.r1), at(A.m1), at(A.s1), P(e, "norm1.weight"), Pb, G("norm1.weight"), G("norm1.bias"), d1, 1, B, F, Tx, s));
+    HIPCHK(e, wb("conv1.weight", "conv1.bias", Pb, F, at(A.x), at(A.gb), Ci, K, Tx));
+    HIPCHK(e, dgrad("conv1.weight", Pb, F, Ci, K, dX));                                    // d (x + cond(g)), masked
+    HIPCHK(e, launch_sd_sum_frames(dX, dC, B, Ci, Tx, 1, s));                              // d cond(g)[b] = sum over frames
+    HIPCHK(e, wb("cond.weight", "cond.bias", dC, Ci, at(A.g), nullptr, Gc, 1, 1));
     return ST_OK;
 }
 

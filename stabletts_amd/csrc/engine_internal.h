@@ -42,6 +42,20 @@ struct VocosState;     // engine_vocos.cpp
 struct StyleState;     // engine_style.cpp
 struct DurState;       // engine_duration.cpp
 
+// Training state of a style-encoder / duration-predictor handle (kinds 3 / 4): the activations of ONE grad-enabled forward
+// (serial, B, T; inputs copied in) and the backward's scratch, in two device buffers that grow on demand and are then reused.
+struct SdTrain {
+    char* act = nullptr; size_t act_cap = 0;
+    char* scr = nullptr; size_t scr_cap = 0;
+    int64_t serial = 0;            // counts the training forwards of this handle
+    bool have = false;             // the activations of forward #serial are held
+    int B = 0, T = 0;
+    float p = 0.0f; unsigned long long seed = 0;
+    bool masked = false;           // style encoder: the forward had a mask
+};
+int sd_train_grow(st_engine* e, char** buf, size_t* cap, size_t bytes);     // engine_style.cpp
+void sd_train_destroy(st_engine* e);
+
 }  // namespace sthost
 
 constexpr int kMaxParts = 1 + sthost::StreamFork::kMaxChildren;      // solve parts: part 0 on the caller's stream, the others on part_streams
@@ -152,6 +166,7 @@ struct st_engine {
     sthost::TrainState* train = nullptr;
     sthost::VocosState* voc = nullptr;  // kind == 2 (engine_vocos.cpp)
     sthost::StyleState* sty = nullptr;  // kind == 3 (engine_style.cpp)
+    sthost::SdTrain* sdt = nullptr;     // kinds 3 / 4 after their first training forward
     sthost::DurState* dur = nullptr;    // kind == 4 (engine_duration.cpp)
 
     int fail(int code, const std::string& msg) { err = msg; return code; }

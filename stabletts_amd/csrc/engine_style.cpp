@@ -4,6 +4,7 @@
 #include "engine_internal.h"
 #include "style_dp_launch.h"
 
+#include <algorithm>
 #include <string>
 
 using namespace st;
@@ -30,6 +31,21 @@ static void style_build_params(st_engine* e, const st_style_encoder_config& c) {
 }
 
 void style_destroy(st_engine* e) { delete e->sty; e->sty = nullptr; }
+
+int sd_train_grow(st_engine* e, char** buf, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return ST_OK;
+    if (*buf) { HIPCHK(e, hipDeviceSynchronize()); HIPCHK(e, hipFree(*buf)); *buf = nullptr; *cap = 0; }
+    HIPCHK(e, hipMalloc((void**)buf, bytes));
+    *cap = bytes;
+    return ST_OK;
+}
+
+void sd_train_destroy(st_engine* e) {
+    if (!e->sdt) return;
+    if (e->sdt->act) hipFree(e->sdt->act);
+    if (e->sdt->scr) hipFree(e->sdt->scr);
+    delete e->sdt; e->sdt = nullptr;
+}
 
 }  // namespace sthost
 
@@ -98,6 +114,163 @@ int st_style_encoder_forward(st_engine* e, const float* mel, const float* mask, 
     // fc (:90) and the temporal average pool (:92)
     HIPCHK(e, conv(h2, Hd, "fc.weight", "fc.bias", O, 1, SD_EPI_NONE, f));
     HIPCHK(e, launch_sd_mean_pool(f, mask, c_out, B, O, T, s));
+    return ST_OK;
+}
+
+}  // extern "C"
+
+// ---- training (kind 3): the forward above with its activations kept, dropout at the five sites of the reference in train
+// mode, and the backward.  Salts 64 .. 68 (include/stabletts_hip.h).
+namespace {
+
+struct StyleActs {      // float offsets into SdTrain::act; R = B * T
+    size_t mel, mask, pre1, h1, pre2, g0, u0, g1, u1, g2, qkv, att, stats, ao, f, end;
+};
+
+StyleActs style_acts(const st_style_encoder_config& c, int B, int T) {
+    const size_t R = (size_t)B * T, Hd = c.style_hidden;
+    StyleActs a{};
+    size_t off = 0;
+    auto want = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
+    a.mel = want(R * c.n_mel_channels); a.mask = want(R);
+    a.pre1 = want(R * Hd); a.h1 = want(R * Hd); a.pre2 = want(R * Hd); a.g0 = want(R * Hd);
+    a.u0 = want(R * 2 * Hd); a.g1 = want(R * Hd); a.u1 = want(R * 2 * Hd); a.g2 = want(R * Hd);
+    a.qkv = want(R * 3 * Hd); a.att = want(R * Hd); a.stats = want(2 * R * c.style_head); a.ao = want(R * Hd);
+    a.f = want(R * c.style_vector_dim);
+    a.end = off;
+    return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int st_style_encoder_train_forward(st_engine* e, const float* mel, const float* mask, float* c_out, int B, int T,
+                                   float p_dropout, uint64_t seed, void* stream) {
+    if (!e) return ST_ERR_INVALID;
+    if (e->kind != 3) return e->fail(ST_ERR_STATE, "this handle is not a style encoder (st_create_style_encoder)");
+    if (!e->finalized) return e->fail(ST_ERR_STATE, "st_finalize() has not been called after loading parameters");
+    if (!mel || !c_out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
+    if (B < 1 || T < 1) return e->fail(ST_ERR_INVALID, "B and T must be >= 1");
+    if (!(p_dropout >= 0.0f && p_dropout < 1.0f)) return e->fail(ST_ERR_INVALID, "p_dropout must be in [0, 1)");
+    const st_style_encoder_config& c = e->sty->cfg;
+    const int I = c.n_mel_channels, Hd = c.style_hidden, O = c.style_vector_dim, K = c.style_kernel_size, NH = c.style_head;
+    const int64_t R = (int64_t)B * T;
+    if (R * 3 * Hd >= ((int64_t)1 << 31) || R * O >= ((int64_t)1 << 31) || R * I >= ((int64_t)1 << 31)) return e->fail(ST_ERR_INVALID, "B*T too large");
+    HIPCHK(e, hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (!e->sdt) e->sdt = new SdTrain();
+    SdTrain* st = e->sdt;
+    st->have = false;
+    const StyleActs A = style_acts(c, B, T);
+    int rc = sd_train_grow(e, &st->act, &st->act_cap, A.end * 4); if (rc) return rc;
+    float* act = (float*)st->act;
+    auto at = [&](size_t o) { return act + o; };
+    HIPCHK(e, hipMemcpyAsync(at(A.mel), mel, (size_t)R * I * 4, hipMemcpyDeviceToDevice, s));
+    if (mask) HIPCHK(e, hipMemcpyAsync(at(A.mask), mask, (size_t)R * 4, hipMemcpyDeviceToDevice, s));
+    const float* kmask = mask ? at(A.mask) : nullptr;
+    SdDrop dr[5];
+    for (int i = 0; i < 5; ++i) dr[i] = sd_make_drop(p_dropout, seed, 64 + i);
+
+    auto conv = [&](const float* in, int cin, const std::string& w, const std::string& b, int cout, int taps, float* out) {
+        SdConvArgs a; a.in = in; a.Cin = cin; a.w = P(e, w); a.bias = P(e, b); a.out = out; a.Cout = cout;
+        a.B = B; a.T = T; a.taps = taps;
+        return launch_sd_conv(a, s);
+    };
+    // spectral: the inference launches' fused Mish epilogue (bitwise the inference activations), the pre-activations kept
+    auto conv_mish = [&](const float* in, int cin, const std::string& w, const std::string& b, float* pre, float* out) {
+        SdConvArgs a; a.in = in; a.Cin = cin; a.w = P(e, w); a.bias = P(e, b); a.out = out; a.pre = pre; a.Cout = Hd;
+        a.B = B; a.T = T; a.taps = 1; a.epi = SD_EPI_MISH;
+        return launch_sd_conv_pre(a, s);
+    };
+    HIPCHK(e, conv_mish(at(A.mel), I, "spectral.0.weight", "spectral.0.bias", at(A.pre1), at(A.h1)));
+    HIPCHK(e, launch_sd_drop(at(A.h1), dr[0], R * Hd, s));
+    HIPCHK(e, conv_mish(at(A.h1), Hd, "spectral.3.weight", "spectral.3.bias", at(A.pre2), at(A.g0)));
+    HIPCHK(e, launch_sd_drop(at(A.g0), dr[1], R * Hd, s));
+    HIPCHK(e, conv(at(A.g0), Hd, "temporal.0.conv1.weight", "temporal.0.conv1.bias", 2 * Hd, K, at(A.u0)));
+    HIPCHK(e, launch_sd_glu_train(at(A.g0), at(A.u0), at(A.g1), dr[2], B, Hd, T, s));
+    HIPCHK(e, conv(at(A.g1), Hd, "temporal.1.conv1.weight", "temporal.1.conv1.bias", 2 * Hd, K, at(A.u1)));
+    HIPCHK(e, launch_sd_glu_train(at(A.g1), at(A.u1), at(A.g2), dr[3], B, Hd, T, s));
+    HIPCHK(e, conv(at(A.g2), Hd, "slf_attn.in_proj_weight", "slf_attn.in_proj_bias", 3 * Hd, 1, at(A.qkv)));
+    HIPCHK(e, launch_sd_attention_train(at(A.qkv), kmask, at(A.att), at(A.stats), dr[4], B, NH, T, s));
+    HIPCHK(e, conv(at(A.att), Hd, "slf_attn.out_proj.weight", "slf_attn.out_proj.bias", Hd, 1, at(A.ao)));
+    HIPCHK(e, conv(at(A.ao), Hd, "fc.weight", "fc.bias", O, 1, at(A.f)));
+    HIPCHK(e, launch_sd_mean_pool(at(A.f), kmask, c_out, B, O, T, s));
+    st->serial += 1; st->have = true; st->B = B; st->T = T; st->p = p_dropout; st->seed = seed; st->masked = mask != nullptr;
+    return ST_OK;
+}
+
+int st_style_encoder_train_backward(st_engine* e, int64_t serial, int B, int T, const float* grad_c, float* grad_flat, void* stream) {
+    if (!e) return ST_ERR_INVALID;
+    if (e->kind != 3) return e->fail(ST_ERR_STATE, "this handle is not a style encoder (st_create_style_encoder)");
+    if (!grad_c || !grad_flat) return e->fail(ST_ERR_INVALID, "null tensor pointer");
+    SdTrain* st = e->sdt;
+    if (!st || !st->have) return e->fail(ST_ERR_STATE, "st_style_encoder_train_backward needs a preceding st_style_encoder_train_forward");
+    if (serial != st->serial || B != st->B || T != st->T)
+        return e->fail(ST_ERR_STATE, "st_style_encoder_train_backward: the engine holds the activations of forward #" + std::to_string(st->serial) +
+                       " (B=" + std::to_string(st->B) + ", T=" + std::to_string(st->T) + "), not of #" + std::to_string(serial) +
+                       " (B=" + std::to_string(B) + ", T=" + std::to_string(T) + ")");
+    const st_style_encoder_config& c = e->sty->cfg;
+    const int I = c.n_mel_channels, Hd = c.style_hidden, O = c.style_vector_dim, K = c.style_kernel_size, NH = c.style_head;
+    const int64_t R = (int64_t)B * T;
+    HIPCHK(e, hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    const StyleActs A = style_acts(c, B, T);
+    float* act = (float*)st->act;
+    auto at = [&](size_t o) { return act + o; };
+    const float* kmask = st->masked ? at(A.mask) : nullptr;
+    SdDrop dr[5];
+    for (int i = 0; i < 5; ++i) dr[i] = sd_make_drop(st->p, st->seed, 64 + i);
+
+    // scratch: dF (O), two hidden-width planes, d att, d qkv / d u (3 Hd), the attention row sums, the split-K planes
+    size_t ws = 0;
+    ws = std::max(ws, sd_wgrad_scratch_floats(B, Hd, O, T, 1));
+    ws = std::max(ws, sd_wgrad_scratch_floats(B, Hd, 3 * Hd, T, 1));
+    ws = std::max(ws, sd_wgrad_scratch_floats(B, Hd, 2 * Hd, T, K));
+    ws = std::max(ws, sd_wgrad_scratch_floats(B, Hd, Hd, T, 1));
+    ws = std::max(ws, sd_wgrad_scratch_floats(B, I, Hd, T, 1));
+    size_t off = 0;
+    auto want = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
+    const size_t o_dF = want(R * O), o_x = want(R * Hd), o_y = want(R * Hd), o_z = want(R * Hd), o_d3 = want(R * 3 * Hd),
+                 o_ds = want(R * NH), o_ws = want(ws);
+    int rc = sd_train_grow(e, &st->scr, &st->scr_cap, off * 4); if (rc) return rc;
+    float* scr = (float*)st->scr;
+    float* dF = scr + o_dF; float* X = scr + o_x; float* Y = scr + o_y; float* Z = scr + o_z; float* D3 = scr + o_d3;
+    float* dsum = scr + o_ds; float* wsp = scr + o_ws;
+
+    std::map<std::string, int64_t> goff;
+    train_grad_layout(e, &goff);
+    auto G = [&](const std::string& n) { return grad_flat + goff.at(n); };
+    // weight + bias gradient of the conv `name` (weight name + "weight" / "bias") from dY (cout) and its input x (cin)
+    auto wb = [&](const std::string& w, const std::string& b, const float* dy, int cout, const float* x, int cin, int taps) {
+        SdWgradArgs a; a.dy = dy; a.in = x; a.dw = G(w); a.scratch = wsp; a.B = B; a.Cin = cin; a.Cout = cout; a.T = T; a.taps = taps;
+        hipError_t r = launch_sd_wgrad(a, s);
+        if (r != hipSuccess) return r;
+        return launch_sd_sum_frames(dy, G(b), B, cout, T, 0, s);
+    };
+    auto dgrad = [&](const std::string& w, const float* dy, int cout, int cin, int taps, const float* res, float* out) {
+        SdConvArgs a; a.in = dy; a.Cin = cout; a.w = P(e, w); a.out = out; a.Cout = cin; a.B = B; a.T = T; a.taps = taps; a.res = res;
+        return launch_sd_conv_dgrad(a, s);
+    };
+    HIPCHK(e, launch_sd_mean_pool_bwd(grad_c, kmask, dF, B, O, T, s));
+    HIPCHK(e, wb("fc.weight", "fc.bias", dF, O, at(A.ao), Hd, 1));
+    HIPCHK(e, dgrad("fc.weight", dF, O, Hd, 1, nullptr, X));                                   // d ao
+    HIPCHK(e, wb("slf_attn.out_proj.weight", "slf_attn.out_proj.bias", X, Hd, at(A.att), Hd, 1));
+    HIPCHK(e, dgrad("slf_attn.out_proj.weight", X, Hd, Hd, 1, nullptr, Y));                    // d att
+    HIPCHK(e, launch_sd_attention_bwd(at(A.qkv), kmask, at(A.att), Y, at(A.stats), dsum, D3, dr[4], B, NH, T, s));
+    HIPCHK(e, wb("slf_attn.in_proj_weight", "slf_attn.in_proj_bias", D3, 3 * Hd, at(A.g2), Hd, 1));
+    HIPCHK(e, dgrad("slf_attn.in_proj_weight", D3, 3 * Hd, Hd, 1, nullptr, X));               // d g2
+    HIPCHK(e, launch_sd_glu_bwd(X, at(A.u1), D3, dr[3], B, Hd, T, s));                         // d u1
+    HIPCHK(e, wb("temporal.1.conv1.weight", "temporal.1.conv1.bias", D3, 2 * Hd, at(A.g1), Hd, K));
+    HIPCHK(e, dgrad("temporal.1.conv1.weight", D3, 2 * Hd, Hd, K, X, Y));                      // d g1 (+ the residual)
+    HIPCHK(e, launch_sd_glu_bwd(Y, at(A.u0), D3, dr[2], B, Hd, T, s));                         // d u0
+    HIPCHK(e, wb("temporal.0.conv1.weight", "temporal.0.conv1.bias", D3, 2 * Hd, at(A.g0), Hd, K));
+    HIPCHK(e, dgrad("temporal.0.conv1.weight", D3, 2 * Hd, Hd, K, Y, X));                      // d g0
+    HIPCHK(e, launch_sd_mish_bwd(X, at(A.pre2), Z, dr[1], R * Hd, s));                         // d pre2
+    HIPCHK(e, wb("spectral.3.weight", "spectral.3.bias", Z, Hd, at(A.h1), Hd, 1));
+    HIPCHK(e, dgrad("spectral.3.weight", Z, Hd, Hd, 1, nullptr, Y));                           // d h1
+    HIPCHK(e, launch_sd_mish_bwd(Y, at(A.pre1), Z, dr[0], R * Hd, s));                         // d pre1
+    HIPCHK(e, wb("spectral.0.weight", "spectral.0.bias", Z, Hd, at(A.mel), I, 1));
     return ST_OK;
 }
 

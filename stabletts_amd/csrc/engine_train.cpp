@@ -598,6 +598,7 @@ int st_train_forward(st_engine* e, const float* t, const float* x, const float* 
 }
 
 int64_t st_train_serial(const st_engine* e) {
+    if (e && (e->kind == 3 || e->kind == 4)) return e->sdt && e->sdt->have ? e->sdt->serial : 0;
     if (!e || !e->train || !e->train->have_fwd) return 0;
     return e->train->serial;
 }

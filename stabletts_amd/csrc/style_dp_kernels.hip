@@ -3,7 +3,7 @@
 // one frame per 200-token utterance; the convolutions and linears therefore run on the fp32-input MFMA
 // (v_mfma_f32_32x32x2_f32: bit-for-bit a k-ordered fp32 FMA chain) instead of the 16-bit operands of the DiT blocks.
 // Tensors stay in the reference's channel-major layout (B, C, T); both modules run once per utterance and are small.
-#include "style_dp_launch.h"
+#include "style_dp_drop.h"
 
 #include <math.h>
 
@@ -16,7 +16,11 @@ constexpr int kSdTileCo = 64, kSdTileT = 64, kSdChunk = 16;     // output tile 6
 // One block = 4 waves = a 64 x 64 output tile; wave w owns the 32 x 32 sub-tile (channels 32 (w & 1), frames 32 (w >> 1)).
 // K = (input channel, tap) pairs in the weight's own order, 16 channels x TAPS per LDS chunk; MFMA 32x32x2 f32 operands:
 // lane l holds A[i = l & 31][k = l >> 5] (weight row) and B[k = l >> 5][j = l & 31] (input frame); D: row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31.
-template <int TAPS>
+// MODE (training, style_dp_bwd.hip) -- SD_MODE_FWD: the inference kernel.  SD_MODE_DGRAD: the data gradient of a conv whose
+// nn.Conv1d weight is W (Cin_fwd = a.Cout, Cout_fwd = a.Cin, TAPS): A is staged straight from W, transposed and tap-flipped,
+// W'[ci][co][j] = W[co][ci][TAPS - 1 - j]; no bias, no epilogue activation, a.res (if set) is added after the output mask.
+// SD_MODE_FWD_PRE: the inference kernel that also writes the pre-activation (acc + bias) to a.pre for the backward.
+template <int TAPS, int MODE>
 __global__ __launch_bounds__(256) void sd_conv_kernel(SdConvArgs a) {
     constexpr int KC = kSdChunk * TAPS, WS = KC + 1, PAD = TAPS / 2, XS = kSdTileT + TAPS - 1;
     __shared__ float Ws[kSdTileCo * WS];
@@ -32,7 +36,12 @@ __global__ __launch_bounds__(256) void sd_conv_kernel(SdConvArgs a) {
         for (int i = tid; i < kSdTileCo * KC; i += 256) {
             const int row = i / KC, kk = i - row * KC;
             const int co = co0 + row, ci = ci0 + kk / TAPS;
-            Ws[row * WS + kk] = (co < Cout && ci < Cin) ? a.w[((size_t)co * Cin + ci0) * TAPS + kk] : 0.0f;
+            if constexpr (MODE == SD_MODE_DGRAD) {
+                const int j = kk - (kk / TAPS) * TAPS;
+                Ws[row * WS + kk] = (co < Cout && ci < Cin) ? a.w[((size_t)ci * Cout + co) * TAPS + (TAPS - 1 - j)] : 0.0f;
+            } else {
+                Ws[row * WS + kk] = (co < Cout && ci < Cin) ? a.w[((size_t)co * Cin + ci0) * TAPS + kk] : 0.0f;
+            }
         }
         for (int i = tid; i < kSdChunk * XS; i += 256) {
             const int row = i / XS, j = i - row * XS;
@@ -61,7 +70,13 @@ __global__ __launch_bounds__(256) void sd_conv_kernel(SdConvArgs a) {
     for (int i = 0; i < 16; ++i) {
         const int co = co0 + wco * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
         if (co >= Cout) continue;
+        if constexpr (MODE == SD_MODE_DGRAD) {
+            const size_t o = ((size_t)b * Cout + co) * T + t;
+            a.out[o] = a.res ? acc[i] * om + a.res[o] : acc[i] * om;
+            continue;
+        }
         float v = acc[i] + a.bias[co];
+        if constexpr (MODE == SD_MODE_FWD_PRE) a.pre[((size_t)b * Cout + co) * T + t] = v;
         if (a.epi == SD_EPI_MISH) {          // x * tanh(softplus(x)), softplus at torch's threshold 20
             const float sp = v > 20.0f ? v : log1pf(expf(v));
             v = v * tanhf(sp);
@@ -76,9 +91,33 @@ hipError_t launch_sd_conv(const SdConvArgs& a, hipStream_t s) {
     if (a.B < 1 || a.T < 1 || a.Cin < 1 || a.Cout < 1 || !a.in || !a.w || !a.bias || !a.out) return hipErrorInvalidValue;
     const dim3 grid((a.T + kSdTileT - 1) / kSdTileT, (a.Cout + kSdTileCo - 1) / kSdTileCo, a.B), blk(256);
     switch (a.taps) {
-        case 1: hipLaunchKernelGGL(sd_conv_kernel<1>, grid, blk, 0, s, a); break;
-        case 3: hipLaunchKernelGGL(sd_conv_kernel<3>, grid, blk, 0, s, a); break;
-        case 5: hipLaunchKernelGGL(sd_conv_kernel<5>, grid, blk, 0, s, a); break;
+        case 1: hipLaunchKernelGGL((sd_conv_kernel<1, SD_MODE_FWD>), grid, blk, 0, s, a); break;
+        case 3: hipLaunchKernelGGL((sd_conv_kernel<3, SD_MODE_FWD>), grid, blk, 0, s, a); break;
+        case 5: hipLaunchKernelGGL((sd_conv_kernel<5, SD_MODE_FWD>), grid, blk, 0, s, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_sd_conv_pre(const SdConvArgs& a, hipStream_t s) {
+    if (a.B < 1 || a.T < 1 || a.Cin < 1 || a.Cout < 1 || !a.in || !a.w || !a.bias || !a.out || !a.pre) return hipErrorInvalidValue;
+    const dim3 grid((a.T + kSdTileT - 1) / kSdTileT, (a.Cout + kSdTileCo - 1) / kSdTileCo, a.B), blk(256);
+    switch (a.taps) {
+        case 1: hipLaunchKernelGGL((sd_conv_kernel<1, SD_MODE_FWD_PRE>), grid, blk, 0, s, a); break;
+        case 3: hipLaunchKernelGGL((sd_conv_kernel<3, SD_MODE_FWD_PRE>), grid, blk, 0, s, a); break;
+        case 5: hipLaunchKernelGGL((sd_conv_kernel<5, SD_MODE_FWD_PRE>), grid, blk, 0, s, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_sd_conv_dgrad(const SdConvArgs& a, hipStream_t s) {
+    if (a.B < 1 || a.T < 1 || a.Cin < 1 || a.Cout < 1 || !a.in || !a.w || !a.out || a.addv || a.imask) return hipErrorInvalidValue;
+    const dim3 grid((a.T + kSdTileT - 1) / kSdTileT, (a.Cout + kSdTileCo - 1) / kSdTileCo, a.B), blk(256);
+    switch (a.taps) {
+        case 1: hipLaunchKernelGGL((sd_conv_kernel<1, SD_MODE_DGRAD>), grid, blk, 0, s, a); break;
+        case 3: hipLaunchKernelGGL((sd_conv_kernel<3, SD_MODE_DGRAD>), grid, blk, 0, s, a); break;
+        case 5: hipLaunchKernelGGL((sd_conv_kernel<5, SD_MODE_DGRAD>), grid, blk, 0, s, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -136,11 +175,16 @@ hipError_t launch_sd_layernorm_channels(float* x, const float* w, const float* b
 // One wave = 64 queries of one (item, head), one query per lane: q and the output accumulator (64 + 64 fp32) live in
 // registers, keys and values stream through LDS 64 frames at a time (every lane reads the same element: broadcast).
 // Softmax is the online form, rescaled once per key tile; exact expf.  Masked keys get a score of -inf and weight 0.
+// TRAIN (style_dp_bwd.hip): the probabilities (not the normaliser) take the dropout factors of site d, and every query's final
+// running max and 1 / sum go to stats[0 / 1][(b * H + head) * T + query] for the backward.  TRAIN = false is the inference kernel.
+template <bool TRAIN>
 __global__ __launch_bounds__(64) void sd_attention_kernel(const float* __restrict__ qkv, const float* __restrict__ kmask,
-                                                          float* __restrict__ out, int H, int T) {
+                                                          float* __restrict__ out, int H, int T, SdDrop drop, float* __restrict__ stats) {
     __shared__ float Ks[64 * 64];
     __shared__ float Vs[64 * 64];
     __shared__ float valid[64];
+    __shared__ float Zs[TRAIN ? 64 * 64 : 1];
+    __shared__ float Ss[TRAIN ? 64 * 64 : 1];
     const int lane = threadIdx.x, hd = blockIdx.y, b = blockIdx.z;
     const int tq = blockIdx.x * 64 + lane, D = H * 64;
     const float* qb = qkv + ((size_t)b * 3 * D + hd * 64) * T;
@@ -159,6 +203,7 @@ __global__ __launch_bounds__(64) void sd_attention_kernel(const float* __restric
         }
         valid[lane] = kv ? 1.0f : 0.0f;
         __syncthreads();
+        if constexpr (!TRAIN) {
         float sc[64];
         float mt = -INFINITY;
 #pragma unroll
@@ -184,17 +229,61 @@ __global__ __launch_bounds__(64) void sd_attention_kernel(const float* __restric
             }
             m = mn;
         }
+        } else {
+        // TRAIN: the same arithmetic in the same order, the scores and this query's keep factors (sd_drop_attn's mask) in its
+        // own LDS columns instead of registers (the extra factor pushed the register-resident form past 256 VGPRs)
+        float mt = -INFINITY;
+        const unsigned rh = drop_rowh(drop.seed, (unsigned)((b * H + hd) * T + tq));
+#pragma unroll 1
+        for (int j = 0; j < 64; ++j) {
+            float s = 0.0f;
+#pragma unroll
+            for (int d = 0; d < 64; ++d) s = fmaf(q[d], Ks[d * 64 + j], s);
+            s = valid[j] != 0.0f ? s : -INFINITY;
+            Ss[j * 64 + lane] = s;
+            mt = fmaxf(mt, s);
+            const unsigned hh = drop_pair(rh, drop_colh(drop.seed, (unsigned)(k0 + j) >> 1));
+            Zs[j * 64 + lane] = !drop.thresh16 || ((j & 1) ? (hh >> 16) : (hh & 0xFFFFu)) >= drop.thresh16 ? drop.scale : 0.0f;
+        }
+        const float mn = fmaxf(m, mt);
+        if (mn != -INFINITY) {
+            const float corr = expf(m - mn);
+            l *= corr;
+#pragma unroll
+            for (int d = 0; d < 64; ++d) acc[d] *= corr;
+#pragma unroll 2
+            for (int j = 0; j < 64; ++j) {
+                float p = expf(Ss[j * 64 + lane] - mn);
+                l += p;
+                p *= Zs[j * 64 + lane];
+#pragma unroll
+                for (int d = 0; d < 64; ++d) acc[d] = fmaf(p, Vs[d * 64 + j], acc[d]);
+            }
+            m = mn;
+        }
+        }
         __syncthreads();
     }
     if (tq >= T) return;
     const float inv = l > 0.0f ? 1.0f / l : 0.0f;
+    if constexpr (TRAIN) {
+        const size_t r = (size_t)(b * H + hd) * T + tq;
+        stats[r] = m;
+        stats[(size_t)gridDim.z * H * T + r] = inv;
+    }
     float* ob = out + ((size_t)b * D + hd * 64) * T + tq;
 #pragma unroll
     for (int d = 0; d < 64; ++d) ob[(size_t)d * T] = acc[d] * inv;
 }
 
 hipError_t launch_sd_attention(const float* qkv, const float* kmask, float* out, int B, int H, int T, hipStream_t s) {
-    hipLaunchKernelGGL(sd_attention_kernel, dim3((T + 63) / 64, H, B), dim3(64), 0, s, qkv, kmask, out, H, T);
+    hipLaunchKernelGGL(sd_attention_kernel<false>, dim3((T + 63) / 64, H, B), dim3(64), 0, s, qkv, kmask, out, H, T, SdDrop{}, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_sd_attention_train(const float* qkv, const float* kmask, float* out, float* stats, const SdDrop& d, int B, int H, int T,
+                                     hipStream_t s) {
+    hipLaunchKernelGGL(sd_attention_kernel<true>, dim3((T + 63) / 64, H, B), dim3(64), 0, s, qkv, kmask, out, H, T, d, stats);
     return hipGetLastError();
 }
 

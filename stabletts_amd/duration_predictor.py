@@ -4,12 +4,14 @@
 Same constructor (duration_predictor.py:6) and checkpoint keys (``conv1``, ``norm1``, ``conv2``, ``norm2``, ``proj``,
 ``cond``), ``forward(x, x_mask, g)`` as :24.  The forward pass runs in fp32 on gfx950 kernels behind
 ``st_duration_predictor_forward`` (include/stabletts_hip.h): logw feeds ``ceil(exp(logw))``, where a 16-bit error would add
-or drop whole frames.  Eval-mode semantics (no dropout); inference only; there is no PyTorch fallback.
+or drop whole frames.  Eval-mode semantics (no dropout); there is no PyTorch fallback.  Grad-enabled calls raise unless ``native_training`` is
+set (``install(duration_predictor="train")`` registers ``duration_predictor_train``, whose DurationPredictor sets it): then
+they run the native training forward / backward with the reference's train-mode dropout.
 """
 import torch
 import torch.nn as nn
 
-from ._fp32_module import NativeFp32Module
+from ._fp32_module import NativeFp32Module, _DurationPredictorFn
 
 
 class DurationPredictor(NativeFp32Module):
@@ -47,6 +49,12 @@ class DurationPredictor(NativeFp32Module):
         B, _, T = x.shape
         if x_mask.numel() != B * T or g.shape != (B, self.gin_channels):
             raise ValueError("x_mask must be (B, 1, Tx) and g (B, gin_channels)")
+        if self._training_call((x_mask,)):
+            xx = x.detach().to(torch.float32).contiguous()
+            mm = x_mask.detach().to(torch.float32).reshape(B, 1, T).contiguous()
+            gg = g.detach().to(torch.float32).contiguous()
+            names, params = zip(*self.named_parameters())
+            return _DurationPredictorFn.apply(self, names, xx, mm, gg, *params)
         with torch.no_grad():
             eng = self.engine()
             xx = x.detach().to(torch.float32).contiguous()

@@ -4,13 +4,15 @@
 Same constructor (reference_encoder.py:25-33) and checkpoint keys (``spectral.0.weight``, ``temporal.<i>.conv1.weight``,
 ``slf_attn.in_proj_weight``, ``slf_attn.out_proj.weight``, ``fc.weight``, ...), ``forward(x, x_mask=None)`` as :74.  The
 forward pass runs in fp32 on gfx950 kernels behind ``st_style_encoder_forward`` (include/stabletts_hip.h); eval-mode
-semantics (no dropout).  Inference only; there is no PyTorch fallback.  An item whose ``x_mask`` has no valid frame gives
+semantics (no dropout).  There is no PyTorch fallback.  Grad-enabled calls raise unless ``native_training`` is set
+(``install(reference_encoder="train")`` registers ``reference_encoder_train``, whose MelStyleEncoder sets it): then they run
+the native training forward / backward, with the reference's train-mode dropout.  An item whose ``x_mask`` has no valid frame gives
 NaN, like the reference's 0 / 0.
 """
 import torch
 import torch.nn as nn
 
-from ._fp32_module import NativeFp32Module
+from ._fp32_module import NativeFp32Module, _StyleEncoderFn
 from .estimator import _ParamsOnly
 
 
@@ -58,6 +60,11 @@ class MelStyleEncoder(NativeFp32Module):
         B, _, T = x.shape
         if x_mask is not None and x_mask.numel() != B * T:
             raise ValueError("x_mask must be (B, 1, T)")
+        if self._training_call((x, x_mask)):
+            mel = x.detach().to(torch.float32).contiguous()
+            mask = x_mask.detach().to(torch.float32).reshape(B, 1, T).contiguous() if x_mask is not None else None
+            names, params = zip(*self.named_parameters())
+            return _StyleEncoderFn.apply(self, names, mel, mask, *params)
         with torch.no_grad():
             eng = self.engine()
             mel = x.detach().to(torch.float32).contiguous()
