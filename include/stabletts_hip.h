@@ -288,6 +288,47 @@ int st_duration_predictor_train_forward(st_engine* e, const float* x, const floa
 int st_duration_predictor_train_backward(st_engine* e, int64_t serial, int B, int Tx, const float* grad_logw, float* grad_flat,
                                          void* stream);
 
+/* ---- feature front end: waveform -> (log-mel) spectrogram (utils/audio.py:6-52) ----------------------------------- */
+/* fp32 throughout: reflect padding by index arithmetic, the window, a real FFT of length n_fft (one complex FFT of n_fft / 2
+ * plus a split pass), sqrt(re^2 + im^2 + 1e-6), the banded mel projection and log(clamp(x, 1e-5)).  No atomics: the output is
+ * bitwise repeatable and an utterance's values do not depend on the rest of the batch.  Inference only. */
+
+enum { ST_PAD_REFLECT = 0, ST_PAD_CONSTANT = 1, ST_PAD_REPLICATE = 2, ST_PAD_CIRCULAR = 3 };   /* F.pad modes */
+enum { ST_MEL_LOG = 0, ST_MEL_LINEAR = 1 };   /* output of st_mel_forward_ragged: log-mel, or the linear magnitude */
+
+/* Replaces LogMelSpectrogram.__init__ / LinearSpectrogram.__init__ (utils/audio.py:7-17,30-45).  sample_rate, f_min,
+ * f_max and mel_scale only shape the filter bank, which the caller loads. */
+typedef struct st_mel_config {
+    int32_t n_fft;        /* native kernels: a power of two in [32, 2048] */
+    int32_t win_length;   /* native kernels: == n_fft */
+    int32_t hop_length;   /* 1 .. n_fft */
+    int32_t pad;          /* reflect padding on both sides, >= 0 */
+    int32_t n_mels;       /* >= 1; 0 makes a linear-spectrogram extractor, which has no filter bank */
+    int32_t center;       /* native kernels: 0 (config.py: center=False) */
+    int32_t pad_mode;     /* native kernels: ST_PAD_REFLECT */
+} st_mel_config;
+
+/* The handle takes "spectrogram.window" (win_length) and, when n_mels > 0, "mel_scale.fb" (n_fft / 2 + 1, n_mels) through
+ * st_load_param / st_finalize; st_finalize derives each filter's nonzero bin range from the loaded fb.  Unsupported
+ * configurations return ST_ERR_UNSUPPORTED and invalid ones ST_ERR_INVALID before any device is touched.  Entry points of the
+ * other kinds reject this handle and vice versa.  Destroyed with st_destroy. */
+int st_create_mel_extractor(const st_mel_config* cfg, int device, st_engine** out);
+
+/* Frames of an utterance of L samples: 1 + (L + 2 pad - n_fft) / hop.  ST_ERR_INVALID when L <= pad (reflect padding needs
+ * pad < L) or L + 2 pad < n_fft (no frame), where the reference's F.pad / torch.stft raise. */
+int64_t st_mel_frames(const st_engine* e, int64_t L);
+
+/* Replaces LogMelSpectrogram.forward (utils/audio.py:50-52) on a padded batch:  wave (B, L) -> out (B, n_mels, frames), fp32
+ * device pointers.  Enqueued on `stream`; the host is not synchronised. */
+int st_mel_forward(st_engine* e, const float* wave, int B, int64_t L, float* out, void* stream);
+
+/* The ragged form, in one launch.  Utterance b is wave[sample_offsets[b] .. sample_offsets[b + 1]) and its result is the
+ * (rows, frames_b) block at out + rows * frame_offsets[b], where rows = n_mels (ST_MEL_LOG) or n_fft / 2 + 1 (ST_MEL_LINEAR:
+ * the magnitude of LinearSpectrogram.forward, :19-26) and frames_b = frame_offsets[b + 1] - frame_offsets[b] must equal
+ * st_mel_frames(e, L_b).  Both offset arrays have B + 1 entries in HOST memory; wave and out are device pointers. */
+int st_mel_forward_ragged(st_engine* e, const float* wave, const int64_t* sample_offsets, const int64_t* frame_offsets, int B,
+                          int output, float* out, void* stream);
+
 /* ---- training: autograd counterpart of Decoder.forward ------------------------------------------- */
 
 /* Replaces Decoder.forward(t, x, mask, mu, c) UNDER AUTOGRAD as CFMDecoder.compute_loss calls it (models/flow_matching.py:99,

@@ -12,16 +12,19 @@ Public surface mirrors the reference's ``models/flow_matching.py``:
 ``DurationPredictor`` as ``models.reference_encoder`` / ``models.duration_predictor`` (``models/model.py:8-9``), inference-only;
 with ``"train"`` instead of ``True`` they register subclasses that also train natively (``native_training = True``);
 ``install(monotonic_align=True)`` registers ``stabletts_amd.monotonic_align`` as ``monotonic_align`` (``models/model.py:5``),
-so the reference's training ``forward`` imports and runs its alignment search on the device, without numba.
+so the reference's training ``forward`` imports and runs its alignment search on the device, without numba;
+``install(audio=True)`` registers ``stabletts_amd.audio`` as ``utils.audio`` (``api.py:6,17``, ``preprocess.py:11``): the
+native ``LogMelSpectrogram`` feature front end, which needs no torchaudio.
 """
 import sys
 
-__all__ = ["install", "CFMDecoder", "TextEncoder", "MelStyleEncoder", "DurationPredictor", "maximum_path"]
+__all__ = ["install", "CFMDecoder", "TextEncoder", "MelStyleEncoder", "DurationPredictor", "maximum_path", "LogMelSpectrogram"]
 
 
-def install(text_encoder=False, vocoder=False, reference_encoder=False, duration_predictor=False, monotonic_align=False):
+def install(text_encoder=False, vocoder=False, reference_encoder=False, duration_predictor=False, monotonic_align=False,
+            audio=False):
     """Make ``models.flow_matching`` (and optionally ``models.text_encoder`` / ``vocoders.vocos.models.model`` /
-    ``models.reference_encoder`` / ``models.duration_predictor`` / ``monotonic_align``) resolve to the native drop-ins
+    ``models.reference_encoder`` / ``models.duration_predictor`` / ``monotonic_align`` / ``utils.audio``) resolve to the native drop-ins
     (call before importing models.model / api.get_vocoder)."""
     from . import flow_matching
     sys.modules["models.flow_matching"] = flow_matching
@@ -46,6 +49,9 @@ def install(text_encoder=False, vocoder=False, reference_encoder=False, duration
     if monotonic_align:
         from . import monotonic_align as ma
         sys.modules["monotonic_align"] = ma                      # models/model.py:5
+    if audio:
+        from . import audio as au
+        sys.modules["utils.audio"] = au                          # api.py:6, preprocess.py:11, vocoders/vocos/models/loss.py:6
     return flow_matching
 
 
@@ -65,6 +71,9 @@ def __getattr__(name):
     if name == "DurationPredictor":
         from .duration_predictor import DurationPredictor
         return DurationPredictor
+    if name == "LogMelSpectrogram":
+        from .audio import LogMelSpectrogram
+        return LogMelSpectrogram
     if name == "maximum_path":
         from .monotonic_align import maximum_path
         return maximum_path

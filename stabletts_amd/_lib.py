@@ -36,7 +36,10 @@ EXPORTS = [
     "st_style_encoder_train_forward", "st_style_encoder_train_backward", "st_duration_predictor_train_forward",
     "st_duration_predictor_train_backward",
     "st_maximum_path", "st_maximum_path_workspace_bytes", "st_mas_neg_cent",
+    "st_create_mel_extractor", "st_mel_frames", "st_mel_forward", "st_mel_forward_ragged",
 ]
+ST_PAD_MODES = {"reflect": 0, "constant": 1, "replicate": 2, "circular": 3}
+ST_MEL_LOG, ST_MEL_LINEAR = 0, 1
 
 
 class StConfig(ctypes.Structure):
@@ -57,6 +60,10 @@ class StStyleEncoderConfig(ctypes.Structure):
 
 class StDurationPredictorConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("in_channels", "filter_channels", "kernel_size", "gin_channels")]
+
+
+class StMelConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("n_fft", "win_length", "hop_length", "pad", "n_mels", "center", "pad_mode")]
 
 
 class NativeError(RuntimeError):
@@ -206,6 +213,15 @@ def load():
     lib.st_maximum_path_workspace_bytes.restype = ctypes.c_int64
     lib.st_mas_neg_cent.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.st_mas_neg_cent.restype = c_int
+    lib.st_create_mel_extractor.argtypes = [ctypes.POINTER(StMelConfig), c_int, ctypes.POINTER(c_void_p)]
+    lib.st_create_mel_extractor.restype = c_int
+    lib.st_mel_frames.argtypes = [c_void_p, ctypes.c_int64]
+    lib.st_mel_frames.restype = ctypes.c_int64
+    lib.st_mel_forward.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_int64, c_void_p, c_void_p]
+    lib.st_mel_forward.restype = c_int
+    lib.st_mel_forward_ragged.argtypes = [c_void_p, c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_int,
+                                          c_int, c_void_p, c_void_p]
+    lib.st_mel_forward_ragged.restype = c_int
     if lib.st_abi_version() != 4:
         raise ImportError("libstabletts_hip.so ABI version mismatch; rebuild it")
     _lib = lib
@@ -217,14 +233,16 @@ class Engine:
 
     def __init__(self, noise_channels, hidden_channels, filter_channels, n_heads, n_layers, kernel_size,
                  gin_channels, operand_dtype="f16", device=0, text_encoder_vocab=None, vocoder=None,
-                 style_encoder=None, duration_predictor=None):
+                 style_encoder=None, duration_predictor=None, mel=None):
         """text_encoder_vocab: None -> CFM decoder estimator (st_create); n_vocab -> TextEncoder handle
         (st_create_text_encoder; noise_channels is then the encoder's out_channels).
         vocoder: dict(input_channels, dim, intermediate_dim, num_layers, n_fft, hop_length) -> Vocos handle
         (st_create_vocoder; the decoder arguments are ignored).
         style_encoder: dict(n_mel_channels, style_hidden, style_vector_dim, style_kernel_size, style_head) -> MelStyleEncoder
         handle (st_create_style_encoder); duration_predictor: dict(in_channels, filter_channels, kernel_size, gin_channels)
-        -> DurationPredictor handle (st_create_duration_predictor).  Both fp32: the decoder arguments are ignored."""
+        -> DurationPredictor handle (st_create_duration_predictor).  Both fp32: the decoder arguments are ignored.
+        mel: dict(n_fft, win_length, hop_length, pad, n_mels, center, pad_mode) -> mel-extractor handle (st_create_mel_extractor;
+        pad_mode an ST_PAD_* value, n_mels 0 for a linear spectrogram)."""
         self.lib = load()
         if operand_dtype not in OPERAND_DTYPES:
             raise ValueError(f"operand_dtype must be one of {sorted(OPERAND_DTYPES)}")
@@ -232,7 +250,10 @@ class Engine:
         cfg = StConfig(noise_channels, hidden_channels, filter_channels, n_heads, n_layers, kernel_size,
                        gin_channels, OPERAND_DTYPES[operand_dtype])
         h = ctypes.c_void_p()
-        if style_encoder is not None:
+        if mel is not None:
+            mc = StMelConfig(*(int(mel[n]) for n, _ in StMelConfig._fields_))
+            rc = self.lib.st_create_mel_extractor(ctypes.byref(mc), int(device), ctypes.byref(h))
+        elif style_encoder is not None:
             sc = StStyleEncoderConfig(*(int(style_encoder[n]) for n, _ in StStyleEncoderConfig._fields_))
             rc = self.lib.st_create_style_encoder(ctypes.byref(sc), int(device), ctypes.byref(h))
         elif duration_predictor is not None:
@@ -325,6 +346,26 @@ class Engine:
     def vocos_forward(self, mel, audio, stream):
         B, _, T = mel.shape
         self._check(self.lib.st_vocos_forward(self.handle, mel.data_ptr(), audio.data_ptr(), B, T, ctypes.c_void_p(stream)))
+
+    def mel_frames(self, L):
+        """Frames of an utterance of L samples (mel-extractor handles); raises NativeError where the reference raises."""
+        n = int(self.lib.st_mel_frames(self.handle, int(L)))
+        if n < 0:
+            raise NativeError(n, f"no frames for an utterance of {L} samples (needs L > pad and L + 2 pad >= n_fft)")
+        return n
+
+    def mel_forward(self, wave, out, stream):
+        """wave (B, L) -> out (B, n_mels, frames), log-mel."""
+        B, L = wave.shape
+        self._check(self.lib.st_mel_forward(self.handle, wave.data_ptr(), B, L, out.data_ptr(), ctypes.c_void_p(stream)))
+
+    def mel_forward_ragged(self, wave, sample_offsets, frame_offsets, output, out, stream):
+        """Concatenated waveforms and host offsets (B + 1 each) -> concatenated (rows, frames_b) blocks in out."""
+        B = len(sample_offsets) - 1
+        so = (ctypes.c_int64 * (B + 1))(*sample_offsets)
+        fo = (ctypes.c_int64 * (B + 1))(*frame_offsets)
+        self._check(self.lib.st_mel_forward_ragged(self.handle, wave.data_ptr(), so, fo, B, int(output), out.data_ptr(),
+                                                   ctypes.c_void_p(stream)))
 
     def style_encoder_forward(self, mel, mask, c_out, stream):
         B, _, T = mel.shape

@@ -697,6 +697,7 @@ void st_destroy(st_engine* e) {
     vocos_destroy(e);
     style_destroy(e);
     duration_destroy(e);
+    mel_destroy(e);
     sd_train_destroy(e);
     if (e->gstream) hipStreamDestroy(e->gstream);
     e->part_streams.destroy();
@@ -779,6 +780,7 @@ int st_bind_param(st_engine* e, const char* name, const float* data, const int64
 int st_repack(st_engine* e, void* stream) {
     if (!e) return ST_ERR_INVALID;
     if (e->kind == 2) return e->fail(ST_ERR_UNSUPPORTED, "st_repack: vocoder handles re-pack through st_finalize");
+    if (e->kind == 5) return e->fail(ST_ERR_UNSUPPORTED, "st_repack: mel-extractor handles re-read their filter bank through st_finalize");
     if (e->kind >= 3) return e->fail(ST_ERR_UNSUPPORTED, "st_repack: style-encoder / duration-predictor handles read their parameters in place");
     if (!e->packed_once) return e->fail(ST_ERR_STATE, "st_repack needs one earlier st_finalize (it allocates the packed buffers)");
     // A re-bind / re-load since the last st_finalize may have moved fp32 tensors: st_repack is for in-place updates only.
@@ -799,6 +801,7 @@ int st_finalize(st_engine* e) {
     for (auto& kv : e->params)
         if (!kv.second.loaded) return e->fail(ST_ERR_STATE, "parameter not loaded: " + kv.first);
     HIPCHK(e, hipDeviceSynchronize());
+    if (e->kind == 5) return mel_finalize(e);      // the filter bank's band table
     if (e->kind >= 3) {      // fp32 kernels read the loaded tensors in place: nothing to pack
         if (e->sdt) e->sdt->have = false;      // a re-bind / re-load: the held training activations are of other weights
         e->finalized = true;

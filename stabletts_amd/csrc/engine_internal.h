@@ -41,6 +41,7 @@ struct TrainState;     // engine_train.cpp
 struct VocosState;     // engine_vocos.cpp
 struct StyleState;     // engine_style.cpp
 struct DurState;       // engine_duration.cpp
+struct MelState;       // engine_audio.cpp
 
 // Training state of a style-encoder / duration-predictor handle (kinds 3 / 4): the activations of ONE grad-enabled forward
 // (serial, B, T; inputs copied in) and the backward's scratch, in two device buffers that grow on demand and are then reused.
@@ -68,7 +69,8 @@ struct st_engine {
     int dt = st::DT_BF16;
     int M = 0, Mp = 0, C = 0, F = 0, H = 0, L = 0, K = 0, G = 0;
     int kind = 0;                       // 0: CFM decoder estimator, 1: TextEncoder (same DiT block kernels), 2: Vocos vocoder,
-                                        // 3: MelStyleEncoder, 4: DurationPredictor (fp32 kernels reading the loaded parameters in place)
+                                        // 3: MelStyleEncoder, 4: DurationPredictor (fp32 kernels reading the loaded parameters in place),
+                                        // 5: mel extractor (the feature front end, utils/audio.py)
     int n_vocab = 0;
     // parameter-name prefix of DiT block i: estimator.py:13,79 "blocks.i.block." / text_encoder.py:25 "encoder.i."
     std::string blk(int i) const {
@@ -168,6 +170,7 @@ struct st_engine {
     sthost::StyleState* sty = nullptr;  // kind == 3 (engine_style.cpp)
     sthost::SdTrain* sdt = nullptr;     // kinds 3 / 4 after their first training forward
     sthost::DurState* dur = nullptr;    // kind == 4 (engine_duration.cpp)
+    sthost::MelState* mel = nullptr;    // kind == 5 (engine_audio.cpp)
 
     int fail(int code, const std::string& msg) { err = msg; return code; }
 };
@@ -212,6 +215,8 @@ int pk_copy(st_engine* e, st_engine::PackList& L, float* dst, const float* src, 
 void vocos_destroy(st_engine* e);
 void style_destroy(st_engine* e);
 void duration_destroy(st_engine* e);
+int mel_finalize(st_engine* e);
+void mel_destroy(st_engine* e);
 
 // HIP-event bracket around the launches of one kernel class (st_profile_*)
 struct ProfScope {
