@@ -291,7 +291,8 @@ int st_duration_predictor_train_backward(st_engine* e, int64_t serial, int B, in
 /* ---- feature front end: waveform -> (log-mel) spectrogram (utils/audio.py:6-52) ----------------------------------- */
 /* fp32 throughout: reflect padding by index arithmetic, the window, a real FFT of length n_fft (one complex FFT of n_fft / 2
  * plus a split pass), sqrt(re^2 + im^2 + 1e-6), the banded mel projection and log(clamp(x, 1e-5)).  No atomics: the output is
- * bitwise repeatable and an utterance's values do not depend on the rest of the batch.  Inference only. */
+ * bitwise repeatable and an utterance's values do not depend on the rest of the batch.  The backward of a padded batch
+ * (st_mel_backward) recomputes the forward and writes the waveform's gradient. */
 
 enum { ST_PAD_REFLECT = 0, ST_PAD_CONSTANT = 1, ST_PAD_REPLICATE = 2, ST_PAD_CIRCULAR = 3 };   /* F.pad modes */
 enum { ST_MEL_LOG = 0, ST_MEL_LINEAR = 1 };   /* output of st_mel_forward_ragged: log-mel, or the linear magnitude */
@@ -328,6 +329,17 @@ int st_mel_forward(st_engine* e, const float* wave, int B, int64_t L, float* out
  * st_mel_frames(e, L_b).  Both offset arrays have B + 1 entries in HOST memory; wave and out are device pointers. */
 int st_mel_forward_ragged(st_engine* e, const float* wave, const int64_t* sample_offsets, const int64_t* frame_offsets, int B,
                           int output, float* out, void* stream);
+
+/* Backward of st_mel_forward (output ST_MEL_LOG) or of the linear spectrogram (ST_MEL_LINEAR) on a padded batch, for the Vocos
+ * multi-scale mel loss (vocoders/vocos/models/loss.py):  wave (B, L) and grad_out, the gradient of the output ((B, n_mels, frames)
+ * or (B, n_fft / 2 + 1, frames)) -> grad_wave (B, L), overwritten; fp32 device pointers.  The spectrum and the mel sums are
+ * recomputed exactly as the forward computes them, so torch.clamp's mask (mel >= 1e-5) is the forward's.  workspace is a
+ * caller-owned device buffer of st_mel_backward_workspace_bytes(e, B, L) bytes; no state is kept between calls.  No atomics: the
+ * result is bitwise repeatable.  Validates every argument before touching the device (the checks of st_mel_forward); a log-mel
+ * backward needs n_mels <= 2 n_fft (ST_ERR_UNSUPPORTED otherwise).  The window and the filter bank get no gradient. */
+int64_t st_mel_backward_workspace_bytes(const st_engine* e, int B, int64_t L);
+int st_mel_backward(st_engine* e, const float* wave, const float* grad_out, int B, int64_t L, int output, float* grad_wave,
+                    void* workspace, void* stream);
 
 /* ---- training: autograd counterpart of Decoder.forward ------------------------------------------- */
 

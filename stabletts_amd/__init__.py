@@ -14,7 +14,9 @@ with ``"train"`` instead of ``True`` they register subclasses that also train na
 ``install(monotonic_align=True)`` registers ``stabletts_amd.monotonic_align`` as ``monotonic_align`` (``models/model.py:5``),
 so the reference's training ``forward`` imports and runs its alignment search on the device, without numba;
 ``install(audio=True)`` registers ``stabletts_amd.audio`` as ``utils.audio`` (``api.py:6,17``, ``preprocess.py:11``): the
-native ``LogMelSpectrogram`` feature front end, which needs no torchaudio.
+native ``LogMelSpectrogram`` feature front end, which needs no torchaudio; ``install(audio="train")`` registers
+``stabletts_amd.audio_train`` instead, whose spectrograms are also differentiable in the waveform (``native_training = True``),
+for the Vocos multi-scale mel loss (``vocoders/vocos/models/loss.py:6``).
 """
 import sys
 
@@ -49,7 +51,10 @@ def install(text_encoder=False, vocoder=False, reference_encoder=False, duration
     if monotonic_align:
         from . import monotonic_align as ma
         sys.modules["monotonic_align"] = ma                      # models/model.py:5
-    if audio:
+    if audio == "train":                                         # spectrograms with native_training = True
+        from . import audio_train as au
+        sys.modules["utils.audio"] = au                          # vocoders/vocos/models/loss.py:6 (the multi-scale mel loss)
+    elif audio:
         from . import audio as au
         sys.modules["utils.audio"] = au                          # api.py:6, preprocess.py:11, vocoders/vocos/models/loss.py:6
     return flow_matching

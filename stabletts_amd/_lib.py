@@ -37,6 +37,7 @@ EXPORTS = [
     "st_duration_predictor_train_backward",
     "st_maximum_path", "st_maximum_path_workspace_bytes", "st_mas_neg_cent",
     "st_create_mel_extractor", "st_mel_frames", "st_mel_forward", "st_mel_forward_ragged",
+    "st_mel_backward_workspace_bytes", "st_mel_backward",
 ]
 ST_PAD_MODES = {"reflect": 0, "constant": 1, "replicate": 2, "circular": 3}
 ST_MEL_LOG, ST_MEL_LINEAR = 0, 1
@@ -222,6 +223,10 @@ def load():
     lib.st_mel_forward_ragged.argtypes = [c_void_p, c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_int,
                                           c_int, c_void_p, c_void_p]
     lib.st_mel_forward_ragged.restype = c_int
+    lib.st_mel_backward_workspace_bytes.argtypes = [c_void_p, c_int, ctypes.c_int64]
+    lib.st_mel_backward_workspace_bytes.restype = ctypes.c_int64
+    lib.st_mel_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_int64, c_int, c_void_p, c_void_p, c_void_p]
+    lib.st_mel_backward.restype = c_int
     if lib.st_abi_version() != 4:
         raise ImportError("libstabletts_hip.so ABI version mismatch; rebuild it")
     _lib = lib
@@ -366,6 +371,19 @@ class Engine:
         fo = (ctypes.c_int64 * (B + 1))(*frame_offsets)
         self._check(self.lib.st_mel_forward_ragged(self.handle, wave.data_ptr(), so, fo, B, int(output), out.data_ptr(),
                                                    ctypes.c_void_p(stream)))
+
+    def mel_backward_workspace_bytes(self, B, L):
+        """Bytes of the caller-owned workspace st_mel_backward needs for a (B, L) batch."""
+        n = int(self.lib.st_mel_backward_workspace_bytes(self.handle, int(B), int(L)))
+        if n < 0:
+            raise NativeError(n, f"no mel backward for B = {B} x L = {L}")
+        return n
+
+    def mel_backward(self, wave, grad_out, output, grad_wave, workspace, stream):
+        """wave (B, L) and the gradient of the (log-mel or linear) output -> grad_wave (B, L), overwritten."""
+        B, L = wave.shape
+        self._check(self.lib.st_mel_backward(self.handle, wave.data_ptr(), grad_out.data_ptr(), B, L, int(output),
+                                             grad_wave.data_ptr(), workspace.data_ptr(), ctypes.c_void_p(stream)))
 
     def style_encoder_forward(self, mel, mask, c_out, stream):
         B, _, T = mel.shape

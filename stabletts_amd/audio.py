@@ -7,7 +7,14 @@ the reference module's and ``LogMelSpectrogram(**asdict(MelConfig()))`` works un
 (``melscale_fbanks``, a restatement of torchaudio's formula), so nothing needs torchaudio; a loaded ``fb`` or ``window``
 wins over the built ones.  The forward pass (reflect padding, window, real FFT, magnitude, banded mel projection, log) runs
 in fp32 in libstabletts_hip.so behind ``st_mel_forward`` / ``st_mel_forward_ragged``; there is no PyTorch fallback, and it
-runs on a HIP device only.  Inference only: a grad-enabled call on a waveform that requires grad raises.
+runs on a HIP device only.
+
+Gradients: these classes are inference-only (``native_training = False``): a grad-enabled call on a waveform that requires grad
+raises.  The subclasses of ``stabletts_amd.audio_train`` (``install(audio="train")``, for the Vocos multi-scale mel loss) set
+``native_training = True``: such a call runs the same forward kernel, and ``backward`` runs ``st_mel_backward`` (the spectrum
+and mel sums recomputed, dmel, the transposed band projection, an inverse real FFT per frame and a deterministic overlap-add
+gather), giving the waveform's gradient in its own shape and dtype.  There is no double backward, the window and the filter bank
+get no gradient, and ``forward_ragged`` stays inference-only.
 
 Native limits: ``center=False``, ``pad_mode="reflect"``, ``win_length == n_fft``, ``n_fft`` a power of two in [32, 2048].
 File decoding and resampling still need torchaudio (``load_and_resample_audio`` imports it when called).
@@ -158,10 +165,11 @@ class _Extractor:
         return self.engine
 
 
-def _waveform(x, dev):
+def _waveform(x, dev, grad_ok=False):
     """(B, L) or (B, 1, L) -> (B, L) fp32 contiguous, with the module's device and gradient rules."""
-    if torch.is_grad_enabled() and x.requires_grad:
-        raise NotImplementedError("the native spectrogram is inference-only (no backward kernels): call it under torch.no_grad()")
+    if not grad_ok and torch.is_grad_enabled() and x.requires_grad:
+        raise NotImplementedError("the native spectrogram is inference-only here (native_training = False, or a ragged batch): "
+                                  "call it under torch.no_grad(), or use stabletts_amd.audio_train (install(audio=\"train\"))")
     if dev.type != "cuda":
         raise RuntimeError("stabletts_amd: the spectrogram runs only on a HIP device (move the module with .to('cuda')); "
                            "there is no CPU fallback")
@@ -194,8 +202,38 @@ def _ragged(eng, waves, dev, rows, output, frames_of):
     return [out[rows * f_off[b]:rows * f_off[b + 1]].view(rows, f_off[b + 1] - f_off[b]) for b in range(len(ws))]
 
 
+def _wants_grad(module, x):
+    return module.native_training and torch.is_grad_enabled() and x.requires_grad
+
+
+class _SpectrogramFn(torch.autograd.Function):
+    """The native forward under autograd; backward = st_mel_backward.  `run(wave)` is the module's forward on the (B, L) fp32
+    waveform and `eng` the handle it ran on."""
+
+    @staticmethod
+    def forward(ctx, x, wave, eng, output, run):
+        ctx.save_for_backward(wave)
+        ctx.eng, ctx.output, ctx.shape, ctx.dtype = eng, output, x.shape, x.dtype
+        return run(wave)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        (wave,) = ctx.saved_tensors
+        B, L = wave.shape
+        dev = wave.device
+        g = grad.to(torch.float32).contiguous()
+        gx = torch.empty(B, L, device=dev, dtype=torch.float32)
+        ws = torch.empty(ctx.eng.mel_backward_workspace_bytes(B, L), device=dev, dtype=torch.uint8)
+        with torch.cuda.device(dev):
+            ctx.eng.mel_backward(wave, g, ctx.output, gx, ws, torch.cuda.current_stream(dev).cuda_stream)
+        return gx.view(ctx.shape).to(ctx.dtype), None, None, None, None
+
+
 class LinearSpectrogram(nn.Module):
     """utils/audio.py:6-26: waveform (B, L) or (B, 1, L) -> magnitude (B, n_fft // 2 + 1, frames)."""
+
+    native_training = False     # True (audio_train): differentiable in the waveform through st_mel_backward
 
     def __init__(self, n_fft, win_length, hop_length, pad, center, pad_mode):
         super().__init__()
@@ -221,8 +259,14 @@ class LinearSpectrogram(nn.Module):
         return self._native.get({"spectrogram.window": self.window})
 
     def forward(self, waveform):
-        wave = _waveform(waveform, self.window.device)
+        grad = _wants_grad(self, waveform)
+        wave = _waveform(waveform, self.window.device, grad)
         eng = self._engine()
+        if grad:
+            return _SpectrogramFn.apply(waveform, wave, eng, _lib.ST_MEL_LINEAR, lambda w: self._run(eng, w))
+        return self._run(eng, wave)
+
+    def _run(self, eng, wave):
         B, L = wave.shape
         bins, T = self.n_fft // 2 + 1, self.frames(L)
         out = torch.empty(B * bins * T, device=wave.device, dtype=torch.float32)
@@ -240,6 +284,8 @@ class LinearSpectrogram(nn.Module):
 
 class LogMelSpectrogram(nn.Module):
     """utils/audio.py:29-52: waveform (B, L) or (B, 1, L) -> log-mel (B, n_mels, frames)."""
+
+    native_training = False     # True (audio_train): differentiable in the waveform through st_mel_backward
 
     def __init__(self, sample_rate, n_fft, win_length, hop_length, f_min, f_max, pad, n_mels, center, pad_mode, mel_scale):
         super().__init__()
@@ -278,10 +324,16 @@ class LogMelSpectrogram(nn.Module):
         return self._native.get({"spectrogram.window": self.spectrogram.window, "mel_scale.fb": self.mel_scale.fb})
 
     def forward(self, x):
-        wave = _waveform(x, self.spectrogram.window.device)
+        grad = _wants_grad(self, x)
+        wave = _waveform(x, self.spectrogram.window.device, grad)
         if self.mel_scale.fb.device != wave.device:
             raise ValueError("spectrogram.window and mel_scale.fb are on different devices")
         eng = self._engine()
+        if grad:
+            return _SpectrogramFn.apply(x, wave, eng, _lib.ST_MEL_LOG, lambda w: self._run(eng, w))
+        return self._run(eng, wave)
+
+    def _run(self, eng, wave):
         B, L = wave.shape
         dev = wave.device
         out = torch.empty(B, self.n_mels, self.frames(L), device=dev, dtype=torch.float32)

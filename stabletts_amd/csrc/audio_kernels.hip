@@ -10,6 +10,9 @@
 // every pass has one butterfly per thread.  The magnitudes of the tile's FR frames stay in LDS; the mel projection then
 // sums each filter's nonzero bins only (band table of st_finalize), in ascending bin order, and writes each mel row's
 // run of frames contiguously in the channel-major output.
+//
+// Backward (audio_launch.h, steps 1-5): mel_bwd_kernel<N> reuses the framing, FFT and split device functions, so the spectrum and
+// the mel sums it differentiates are bitwise the forward's; mel_gather_kernel sums each sample's frame terms without atomics.
 #include "audio_launch.h"
 
 namespace st {
@@ -31,10 +34,91 @@ __device__ __forceinline__ float2 twn(const float2* tw, int m, int H) {
     return m < H ? w : make_float2(-w.x, -w.y);
 }
 
+// ---- the pieces both directions share: twiddles, framing, the H-point FFT, the split pass ----
+
+template <int N>
+__device__ __forceinline__ void mel_twiddles(float2* tw, int tid) {
+    for (int m = tid; m < N / 2; m += 256) {
+        float sn, cs;
+        sincospif((float)(2 * m) / (float)N, &sn, &cs);
+        tw[m] = make_float2(cs, -sn);
+    }
+}
+
+// frames t0 .. t0 + S - 1 (zeros past `frames`) windowed into z, viewed as [S][N] floats = z[n] = x[2n] + i x[2n+1] per frame
+template <int N>
+__device__ __forceinline__ void mel_frame_load(float* z, const float* __restrict__ x, const float* __restrict__ win, int t0,
+                                               int frames, int hop, int pad, long long L, int tid) {
+    constexpr int S = MelGeo<N>::S;
+    for (int e = tid; e < S * N; e += 256) {
+        const int f = e / N, m = e & (N - 1);
+        const int t = t0 + f;
+        float v = 0.0f;
+        if (t < frames) {
+            long long q = (long long)t * hop + m - pad;
+            if (q < 0) q = -q;
+            if (q >= L) q = 2 * (L - 1) - q;
+            v = x[q] * win[m];
+        }
+        z[e] = v;
+    }
+}
+
+// S forward H-point FFTs (e^{-2 pi i ...}) from b0, ping-ponging with b1; returns the buffer that holds the result
+template <int N>
+__device__ __forceinline__ float2* mel_fft(float2* b0, float2* b1, const float2* tw, int tid) {
+    using G = MelGeo<N>;
+    constexpr int H = G::H, S = G::S, Q = G::Q;
+    float2* in = b0;
+    float2* out = b1;
+#pragma unroll
+    for (int Ns = 1; Ns * 4 <= H; Ns *= 4) {        // radix-4 Stockham passes, one butterfly per thread
+        const int f = tid / Q, j = tid - f * Q;
+        const int k = j & (Ns - 1);
+        const int ts = k * (H / (4 * Ns));          // twiddle e^{-2 pi i r k / (4 Ns)} = W_N^{2 r ts}
+        const float2* src = in + f * H;
+        const float2 u0 = src[j];
+        const float2 u1 = cmulf(src[j + Q], twn(tw, 2 * ts, H));
+        const float2 u2 = cmulf(src[j + 2 * Q], twn(tw, 4 * ts, H));
+        const float2 u3 = cmulf(src[j + 3 * Q], twn(tw, 6 * ts, H));
+        const float2 s02 = make_float2(u0.x + u2.x, u0.y + u2.y), d02 = make_float2(u0.x - u2.x, u0.y - u2.y);
+        const float2 s13 = make_float2(u1.x + u3.x, u1.y + u3.y), d13 = make_float2(u1.x - u3.x, u1.y - u3.y);
+        float2* dst = out + f * H + ((j - k) << 2) + k;
+        dst[0] = make_float2(s02.x + s13.x, s02.y + s13.y);
+        dst[Ns] = make_float2(d02.x + d13.y, d02.y - d13.x);          // u0 - i u1 - u2 + i u3
+        dst[2 * Ns] = make_float2(s02.x - s13.x, s02.y - s13.y);
+        dst[3 * Ns] = make_float2(d02.x - d13.y, d02.y + d13.x);      // u0 + i u1 - u2 - i u3
+        __syncthreads();
+        float2* tmp = in; in = out; out = tmp;
+    }
+    if constexpr ((H & 0x55555555) == 0) {           // log2 H odd: one radix-2 pass, Ns = H / 2
+        for (int e = tid; e < S * (H / 2); e += 256) {
+            const int f = e / (H / 2), j = e - f * (H / 2);
+            const float2 v0 = in[f * H + j], v1 = cmulf(in[f * H + j + H / 2], twn(tw, 2 * j, H));
+            out[f * H + j] = make_float2(v0.x + v1.x, v0.y + v1.y);
+            out[f * H + j + H / 2] = make_float2(v0.x - v1.x, v0.y - v1.y);
+        }
+        __syncthreads();
+        float2* tmp = in; in = out; out = tmp;
+    }
+    return in;
+}
+
+// bin k (0..H) of frame f's N-point real spectrum X from the H-point transform Z of its even / odd samples
+template <int N>
+__device__ __forceinline__ float2 mel_split_bin(const float2* Z, const float2* tw, int f, int k) {
+    constexpr int H = N / 2;
+    const float2 A = Z[f * H + (k & (H - 1))], Bz = Z[f * H + ((H - k) & (H - 1))];
+    const float2 E = make_float2(0.5f * (A.x + Bz.x), 0.5f * (A.y - Bz.y));
+    const float2 O = make_float2(0.5f * (A.x - Bz.x), 0.5f * (A.y + Bz.y));
+    const float2 P = cmulf(twn(tw, k, H), O);
+    return make_float2(E.x + P.y, E.y - P.x);
+}
+
 template <int N>
 __global__ __launch_bounds__(256) void mel_kernel(MelArgs a) {
     using G = MelGeo<N>;
-    constexpr int H = G::H, S = G::S, FR = G::FR, Q = G::Q;
+    constexpr int H = G::H, S = G::S, FR = G::FR;
     __shared__ float2 buf[2][S * H];                // 16 KiB for every N
     __shared__ float2 tw[H];                        // e^{-2 pi i m / N}, m < H
     __shared__ float mag[FR * (H + 1)];             // the tile's magnitudes, [frame][bin]
@@ -61,72 +145,20 @@ __global__ __launch_bounds__(256) void mel_kernel(MelArgs a) {
     const float* __restrict__ x = a.wave + s_off;
     const float* __restrict__ win = a.window;
 
-    for (int m = tid; m < H; m += 256) {
-        float sn, cs;
-        sincospif((float)(2 * m) / (float)N, &sn, &cs);
-        tw[m] = make_float2(cs, -sn);
-    }
+    mel_twiddles<N>(tw, tid);
 
 #pragma unroll 1
     for (int r = 0; r < FR / S; ++r) {
         // framing + window: buf[0] viewed as [S][N] floats is z = x[2n] + i x[2n+1] of each frame
-        float* z = reinterpret_cast<float*>(buf[0]);
-        for (int e = tid; e < S * N; e += 256) {
-            const int f = e / N, m = e & (N - 1);
-            const int t = t0 + r * S + f;
-            float v = 0.0f;
-            if (t < frames) {
-                long long q = (long long)t * a.hop + m - a.pad;
-                if (q < 0) q = -q;
-                if (q >= L) q = 2 * (L - 1) - q;
-                v = x[q] * win[m];
-            }
-            z[e] = v;
-        }
+        mel_frame_load<N>(reinterpret_cast<float*>(buf[0]), x, win, t0 + r * S, frames, a.hop, a.pad, L, tid);
         __syncthreads();
-
-        float2* in = buf[0];
-        float2* out = buf[1];
-#pragma unroll
-        for (int Ns = 1; Ns * 4 <= H; Ns *= 4) {        // radix-4 Stockham passes, one butterfly per thread
-            const int f = tid / Q, j = tid - f * Q;
-            const int k = j & (Ns - 1);
-            const int ts = k * (H / (4 * Ns));          // twiddle e^{-2 pi i r k / (4 Ns)} = W_N^{2 r ts}
-            const float2* src = in + f * H;
-            const float2 u0 = src[j];
-            const float2 u1 = cmulf(src[j + Q], twn(tw, 2 * ts, H));
-            const float2 u2 = cmulf(src[j + 2 * Q], twn(tw, 4 * ts, H));
-            const float2 u3 = cmulf(src[j + 3 * Q], twn(tw, 6 * ts, H));
-            const float2 s02 = make_float2(u0.x + u2.x, u0.y + u2.y), d02 = make_float2(u0.x - u2.x, u0.y - u2.y);
-            const float2 s13 = make_float2(u1.x + u3.x, u1.y + u3.y), d13 = make_float2(u1.x - u3.x, u1.y - u3.y);
-            float2* dst = out + f * H + ((j - k) << 2) + k;
-            dst[0] = make_float2(s02.x + s13.x, s02.y + s13.y);
-            dst[Ns] = make_float2(d02.x + d13.y, d02.y - d13.x);          // u0 - i u1 - u2 + i u3
-            dst[2 * Ns] = make_float2(s02.x - s13.x, s02.y - s13.y);
-            dst[3 * Ns] = make_float2(d02.x - d13.y, d02.y + d13.x);      // u0 + i u1 - u2 - i u3
-            __syncthreads();
-            float2* tmp = in; in = out; out = tmp;
-        }
-        if constexpr ((H & 0x55555555) == 0) {           // log2 H odd: one radix-2 pass, Ns = H / 2
-            for (int e = tid; e < S * (H / 2); e += 256) {
-                const int f = e / (H / 2), j = e - f * (H / 2);
-                const float2 v0 = in[f * H + j], v1 = cmulf(in[f * H + j + H / 2], twn(tw, 2 * j, H));
-                out[f * H + j] = make_float2(v0.x + v1.x, v0.y + v1.y);
-                out[f * H + j + H / 2] = make_float2(v0.x - v1.x, v0.y - v1.y);
-            }
-            __syncthreads();
-            float2* tmp = in; in = out; out = tmp;
-        }
+        const float2* in = mel_fft<N>(buf[0], buf[1], tw, tid);
 
         // split pass to the N-point real spectrum and its magnitude (utils/audio.py:24-25)
         for (int e = tid; e < S * (H + 1); e += 256) {
             const int f = e / (H + 1), k = e - f * (H + 1);
-            const float2 A = in[f * H + (k & (H - 1))], Bz = in[f * H + ((H - k) & (H - 1))];
-            const float2 E = make_float2(0.5f * (A.x + Bz.x), 0.5f * (A.y - Bz.y));
-            const float2 O = make_float2(0.5f * (A.x - Bz.x), 0.5f * (A.y + Bz.y));
-            const float2 P = cmulf(twn(tw, k, H), O);
-            const float re = E.x + P.y, im = E.y - P.x;
-            mag[(r * S + f) * (H + 1) + k] = sqrtf(re * re + im * im + 1e-6f);
+            const float2 X = mel_split_bin<N>(in, tw, f, k);
+            mag[(r * S + f) * (H + 1) + k] = sqrtf(X.x * X.x + X.y * X.y + 1e-6f);
         }
         __syncthreads();
     }
@@ -152,9 +184,145 @@ __global__ __launch_bounds__(256) void mel_kernel(MelArgs a) {
     }
 }
 
+// Backward, steps 1-4 of the header comment in audio_launch.h: per frame, the spectrum X and (log-mel) mel_m recomputed exactly as
+// mel_kernel computes them, then dmel = g / mel (0 under the clamp), dmag = fb dmel (bin-major band table), G = dmag X / mag,
+// C = the half-spectrum of the inverse real FFT, and w * (N irfft(C)) written to the frame's row of the workspace.  The inverse
+// is the mirror of the split pass: Z'_k = (C_k + conj C_{H-k}) + i e^{+2 pi i k / N} (C_k - conj C_{H-k}), k < H, and
+// IFFT_H(Z') = conj FFT_H(conj Z') holds N df[2n] + i N df[2n+1].  Same tiling and grid as the forward, S frames per round.
+template <int N>
+__global__ __launch_bounds__(256) void mel_bwd_kernel(MelBwdArgs a) {
+    using G = MelGeo<N>;
+    constexpr int H = G::H, S = G::S, FR = G::FR;
+    __shared__ float2 buf[2][S * H];                // FFT ping-pong; between the passes [S][rows] floats of dmel (rows <= 2 N)
+    __shared__ float2 tw[H];
+    __shared__ float2 spec[S * (H + 1)];            // X of the round's frames, then C
+    __shared__ float mag[S * (H + 1)];
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x / a.tiles_per;
+    const int t0 = (blockIdx.x - b * a.tiles_per) * FR;
+    const int frames = a.frames, rows = a.rows;
+    const float* __restrict__ x = a.wave + (long long)b * a.L;
+    const float* __restrict__ win = a.window;
+    const float* __restrict__ g = a.grad + (long long)b * rows * frames;       // (rows, frames) of this utterance
+    float* __restrict__ ws = a.ws + (long long)b * frames * N;                 // (frames, N)
+
+    mel_twiddles<N>(tw, tid);
+
+#pragma unroll 1
+    for (int r = 0; r < FR / S; ++r) {
+        const int tr = t0 + r * S;
+        if (tr >= frames) break;                                              // block-uniform
+        mel_frame_load<N>(reinterpret_cast<float*>(buf[0]), x, win, tr, frames, a.hop, a.pad, a.L, tid);
+        __syncthreads();
+        const float2* Z = mel_fft<N>(buf[0], buf[1], tw, tid);
+        for (int e = tid; e < S * (H + 1); e += 256) {
+            const int f = e / (H + 1), k = e - f * (H + 1);
+            const float2 X = mel_split_bin<N>(Z, tw, f, k);
+            spec[e] = X;
+            mag[e] = sqrtf(X.x * X.x + X.y * X.y + 1e-6f);
+        }
+        __syncthreads();
+
+        // 1. dmel_m = g_m / mel_m where mel_m >= 1e-5 (torch.clamp's mask), else 0; mel_m summed as mel_kernel sums it
+        float* dmel = reinterpret_cast<float*>(&buf[0][0]);
+        if (a.log_mel) {
+            for (int e = tid; e < S * rows; e += 256) {
+                const int f = e / rows, m = e - f * rows;
+                const int t = tr + f;
+                float d = 0.0f;
+                if (t < frames) {
+                    const int lo = a.band[3 * m], hi = a.band[3 * m + 1];
+                    const float* __restrict__ w = a.wband + a.band[3 * m + 2] - lo;
+                    const float* __restrict__ mg = mag + f * (H + 1);
+                    float acc = 0.0f;
+                    for (int k = lo; k < hi; ++k) acc += w[k] * mg[k];
+                    d = acc >= 1e-5f ? g[(long long)m * frames + t] / acc : 0.0f;
+                }
+                dmel[e] = d;
+            }
+            __syncthreads();
+        }
+
+        // 2-3. dmag_k = sum_m fb[k, m] dmel_m (ascending m), G_k = dmag_k X_k / mag_k, and C_k (halved off the two real bins)
+        for (int e = tid; e < S * (H + 1); e += 256) {
+            const int f = e / (H + 1), k = e - f * (H + 1);
+            const int t = tr + f;
+            float dmag = 0.0f;
+            if (t < frames) {
+                if (a.log_mel) {
+                    const int lo = a.bandT[3 * k], hi = a.bandT[3 * k + 1];
+                    const float* __restrict__ w = a.wbandT + a.bandT[3 * k + 2] - lo;
+                    const float* __restrict__ dm = dmel + f * rows;
+                    for (int m = lo; m < hi; ++m) dmag += w[m] * dm[m];
+                } else {
+                    dmag = g[(long long)k * frames + t];
+                }
+            }
+            const float sc = dmag / mag[e];
+            const float2 X = spec[e];
+            spec[e] = (k == 0 || k == H) ? make_float2(sc * X.x, 0.0f) : make_float2(0.5f * (sc * X.x), 0.5f * (sc * X.y));
+        }
+        __syncthreads();
+
+        // 4. pre-pass: conj Z'_k into buf[0], the forward FFT, and the conjugate of its result = N df
+        for (int e = tid; e < S * H; e += 256) {
+            const int f = e / H, k = e - f * H;
+            const float2 A = spec[f * (H + 1) + k], Bc0 = spec[f * (H + 1) + H - k];
+            const float2 Ev = make_float2(A.x + Bc0.x, A.y - Bc0.y);             // C_k + conj C_{H-k}
+            const float2 D = make_float2(A.x - Bc0.x, A.y + Bc0.y);              // C_k - conj C_{H-k}
+            const float2 w = twn(tw, k, H);
+            const float2 P = cmulf(make_float2(w.x, -w.y), D);                   // e^{+2 pi i k / N} D
+            buf[0][e] = make_float2(Ev.x - P.y, -(Ev.y + P.x));                  // conj(Ev + i P)
+        }
+        __syncthreads();
+        const float2* zz = mel_fft<N>(buf[0], buf[1], tw, tid);
+        for (int e = tid; e < S * N; e += 256) {
+            const int f = e / N, n = e & (N - 1);
+            const int t = tr + f;
+            if (t < frames) {
+                const float2 v = zz[f * H + (n >> 1)];
+                ws[(long long)t * N + n] = win[n] * ((n & 1) ? -v.y : v.x);
+            }
+        }
+        __syncthreads();                                                       // buf is the next round's frame buffer
+    }
+}
+
+// 5. dx[s] = sum over the padded positions q that read s (direct q = s + pad; left reflection q = pad - s for 1 <= s <= pad; right
+// reflection q = 2 (L - 1) - s + pad for s <= L - 2) and the frames t whose window covers q, of ws[t][q - t hop]: in that order of
+// positions and ascending t, one thread per sample, no atomics.
+__global__ __launch_bounds__(256) void mel_gather_kernel(MelBwdArgs a) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)a.B * a.L) return;
+    const long long b = i / a.L, s = i - b * a.L, L = a.L;
+    const int N = a.n_fft, hop = a.hop, frames = a.frames;
+    const float* __restrict__ ws = a.ws + b * frames * N;
+    float acc = 0.0f;
+    auto add = [&](long long q) {
+        const long long tlo = q < N ? 0 : (q - N + hop) / hop;                // first t with q < t hop + N
+        long long thi = q / hop;
+        if (thi > frames - 1) thi = frames - 1;
+        for (long long t = tlo; t <= thi; ++t) acc += ws[t * N + (q - t * hop)];
+    };
+    add(s + a.pad);
+    if (s >= 1 && s <= a.pad) add(a.pad - s);
+    if (s <= L - 2) add(2 * (L - 1) - s + a.pad);
+    a.out[i] = acc;
+}
+
 template <int N>
 hipError_t launch_n(const MelArgs& a, hipStream_t s) {
     hipLaunchKernelGGL((mel_kernel<N>), dim3((unsigned)a.total_tiles), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+template <int N>
+hipError_t launch_bwd_n(const MelBwdArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL((mel_bwd_kernel<N>), dim3((unsigned)a.total_tiles), dim3(256), 0, s, a);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return err;
+    const long long n = (long long)a.B * a.L;
+    hipLaunchKernelGGL(mel_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
@@ -175,6 +343,20 @@ hipError_t launch_mel(const MelArgs& a, hipStream_t s) {
         case 512: return launch_n<512>(a, s);
         case 1024: return launch_n<1024>(a, s);
         case 2048: return launch_n<2048>(a, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_mel_backward(const MelBwdArgs& a, hipStream_t s) {
+    if (a.total_tiles <= 0) return hipSuccess;
+    switch (a.n_fft) {
+        case 32: return launch_bwd_n<32>(a, s);
+        case 64: return launch_bwd_n<64>(a, s);
+        case 128: return launch_bwd_n<128>(a, s);
+        case 256: return launch_bwd_n<256>(a, s);
+        case 512: return launch_bwd_n<512>(a, s);
+        case 1024: return launch_bwd_n<1024>(a, s);
+        case 2048: return launch_bwd_n<2048>(a, s);
         default: return hipErrorInvalidValue;
     }
 }

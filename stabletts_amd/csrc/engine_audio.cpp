@@ -1,7 +1,9 @@
-// Feature front end behind the C ABI (st_create_mel_extractor / st_mel_forward / st_mel_forward_ragged): handle kind 5.
+// Feature front end behind the C ABI (st_create_mel_extractor / st_mel_forward / st_mel_forward_ragged / st_mel_backward):
+// handle kind 5.
 // Reference: utils/audio.py:6-52 (LinearSpectrogram, LogMelSpectrogram), config.py:4-19.  The window and the filter bank
 // are the module's buffers ("spectrogram.window", "mel_scale.fb"), loaded like parameters; st_finalize derives each
-// filter's nonzero bin range from the loaded fb and packs those weights.  The kernels are in audio_kernels.hip.
+// filter's nonzero bin range from the loaded fb and packs those weights, and the same table bin-major for the backward.  The
+// kernels are in audio_kernels.hip.
 #include "engine_internal.h"
 #include "audio_launch.h"
 
@@ -17,6 +19,8 @@ struct MelState {
     st_mel_config cfg{};
     int* band = nullptr;          // [n_mels][3]: lo, hi, offset into wband
     float* wband = nullptr;
+    int* bandT = nullptr;         // [n_fft / 2 + 1][3]: mlo, mhi, offset into wbandT (the backward's dmag = fb dmel)
+    float* wbandT = nullptr;
     // ragged launches: utterance tables in pinned host memory, copied to device slots; a slot is refilled only after the
     // event of its previous launch, so a call never waits for the one before it
     static constexpr int kSlots = 4;
@@ -37,11 +41,15 @@ void mel_destroy(st_engine* e) {
     }
     if (m->band) hipFree(m->band);
     if (m->wband) hipFree(m->wband);
+    if (m->bandT) hipFree(m->bandT);
+    if (m->wbandT) hipFree(m->wbandT);
     delete m; e->mel = nullptr;
 }
 
 // st_finalize of a mel handle: every filter's nonzero range [lo, hi) of bins, and its weights packed in bin order.  A filter
-// without a nonzero weight gets an empty range (its sum is 0, log(1e-5) after the clamp), as in the dense product.
+// without a nonzero weight gets an empty range (its sum is 0, log(1e-5) after the clamp), as in the dense product.  The
+// transposed table gives every bin its range of mels with nonzero weights and those weights in mel order; a bin that no filter
+// reaches gets an empty range (dmag = 0), and an all-zero filter appears in no bin's range.
 int mel_finalize(st_engine* e) {
     MelState* m = e->mel;
     const st_mel_config& c = m->cfg;
@@ -60,12 +68,29 @@ int mel_finalize(st_engine* e) {
             for (int k = lo; k < hi; ++k) w.push_back(fb[(size_t)k * M + j]);     // (zeros inside the range kept: same terms)
         }
         if (w.empty()) w.push_back(0.0f);
+        std::vector<int> bandT((size_t)3 * bins);
+        std::vector<float> wT;
+        for (int k = 0; k < bins; ++k) {
+            int lo = M, hi = 0;
+            for (int j = 0; j < M; ++j)
+                if (fb[(size_t)k * M + j] != 0.0f) { if (j < lo) lo = j; hi = j + 1; }
+            if (hi == 0) lo = 0;
+            bandT[3 * k] = lo; bandT[3 * k + 1] = hi; bandT[3 * k + 2] = (int)wT.size();
+            for (int j = lo; j < hi; ++j) wT.push_back(fb[(size_t)k * M + j]);
+        }
+        if (wT.empty()) wT.push_back(0.0f);
         if (m->band) { hipFree(m->band); m->band = nullptr; }
         if (m->wband) { hipFree(m->wband); m->wband = nullptr; }
+        if (m->bandT) { hipFree(m->bandT); m->bandT = nullptr; }
+        if (m->wbandT) { hipFree(m->wbandT); m->wbandT = nullptr; }
         HIPCHK(e, hipMalloc((void**)&m->band, band.size() * 4));
         HIPCHK(e, hipMalloc((void**)&m->wband, w.size() * 4));
+        HIPCHK(e, hipMalloc((void**)&m->bandT, bandT.size() * 4));
+        HIPCHK(e, hipMalloc((void**)&m->wbandT, wT.size() * 4));
         HIPCHK(e, hipMemcpy(m->band, band.data(), band.size() * 4, hipMemcpyHostToDevice));
         HIPCHK(e, hipMemcpy(m->wband, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(e, hipMemcpy(m->bandT, bandT.data(), bandT.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(e, hipMemcpy(m->wbandT, wT.data(), wT.size() * 4, hipMemcpyHostToDevice));
     }
     e->finalized = true;
     return ST_OK;
@@ -205,6 +230,44 @@ int st_mel_forward_ragged(st_engine* e, const float* wave, const int64_t* sample
     HIPCHK(e, launch_mel(a, s));
     HIPCHK(e, hipEventRecord(m->ev[slot], s));
     m->used[slot] = true;
+    return ST_OK;
+}
+
+int64_t st_mel_backward_workspace_bytes(const st_engine* e, int B, int64_t L) {
+    if (!e || e->kind != 5 || B < 1) return ST_ERR_INVALID;
+    const st_mel_config& c = e->mel->cfg;
+    const int64_t T = frames_of(c, L);
+    if (T < 0) return ST_ERR_INVALID;
+    return (int64_t)B * T * c.n_fft * (int64_t)sizeof(float);
+}
+
+int st_mel_backward(st_engine* e, const float* wave, const float* grad_out, int B, int64_t L, int output, float* grad_wave,
+                    void* workspace, void* stream) {
+    if (!e) return ST_ERR_INVALID;
+    int rc = mel_check(e, wave, grad_wave); if (rc) return rc;
+    if (!grad_out || !workspace) return e->fail(ST_ERR_INVALID, "null tensor pointer");
+    if (output != ST_MEL_LOG && output != ST_MEL_LINEAR) return e->fail(ST_ERR_INVALID, "output must be ST_MEL_LOG or ST_MEL_LINEAR");
+    MelState* m = e->mel;
+    const st_mel_config& c = m->cfg;
+    if (output == ST_MEL_LOG && c.n_mels < 1) return e->fail(ST_ERR_STATE, "a linear-spectrogram extractor (n_mels = 0) has no mel output");
+    if (output == ST_MEL_LOG && c.n_mels > 2 * c.n_fft)
+        return e->fail(ST_ERR_UNSUPPORTED, "the native backward is built for n_mels <= 2 n_fft");
+    if (B < 1) return e->fail(ST_ERR_INVALID, "B must be >= 1");
+    const int64_t T = frames_of(c, L);
+    if (T < 0) return e->fail(ST_ERR_INVALID, "L must exceed pad (reflect padding) and L + 2 pad must be >= n_fft");
+    const int FR = mel_tile_frames(c.n_fft);
+    const int64_t per = (T + FR - 1) / FR;
+    if (L >= ((int64_t)1 << 31) || (int64_t)B * per >= ((int64_t)1 << 31) || (int64_t)B * L >= ((int64_t)1 << 39))
+        return e->fail(ST_ERR_INVALID, "batch too large");
+    HIPCHK(e, hipSetDevice(e->device));
+    MelBwdArgs a{};
+    a.wave = wave; a.window = P(e, "spectrogram.window"); a.grad = grad_out;
+    a.wband = m->wband; a.band = m->band; a.wbandT = m->wbandT; a.bandT = m->bandT;
+    a.ws = (float*)workspace; a.out = grad_wave;
+    a.n_fft = c.n_fft; a.hop = c.hop_length; a.pad = c.pad;
+    a.rows = output == ST_MEL_LOG ? c.n_mels : c.n_fft / 2 + 1; a.log_mel = output == ST_MEL_LOG ? 1 : 0;
+    a.B = B; a.L = L; a.frames = (int)T; a.tiles_per = (int)per; a.total_tiles = (int)(B * per);
+    HIPCHK(e, launch_mel_backward(a, (hipStream_t)stream));
     return ST_OK;
 }
 
