@@ -21,24 +21,6 @@ SOLVERS = {"euler": ST_SOLVER_EULER, "midpoint": ST_SOLVER_MIDPOINT, "rk4": ST_S
            "fehlberg2": ST_SOLVER_FEHLBERG2, "adaptive_heun": ST_SOLVER_ADAPTIVE_HEUN,
            "implicit_adams": ST_SOLVER_IMPLICIT_ADAMS}      # = every method the reference's webui.py:110 offers
 
-# every symbol include/stabletts_hip.h declares
-EXPORTS = [
-    "st_abi_version", "st_create", "st_destroy", "st_last_error", "st_load_param", "st_num_params",
-    "st_finalize", "st_bind_param", "st_repack", "st_train_serial", "st_estimator_forward", "st_cfm_solve", "st_output_status", "st_last_solve_stats", "st_debug_capture", "st_debug_fetch",
-    "st_create_text_encoder", "st_text_encoder_forward", "st_param_info",
-    "st_profile_enable", "st_profile_select", "st_profile_stride", "st_profile_num_classes", "st_profile_class_name", "st_profile_read",
-    "st_device_bytes", "st_train_forward", "st_train_backward", "st_train_backward_part", "st_train_param_part", "st_train_grad_offset",
-    "st_train_grad_numel", "st_param_grad", "st_param_grads_flat", "st_text_encoder_train_forward", "st_text_encoder_train_backward",
-    "st_durations", "st_generate_path", "st_align", "st_create_vocoder", "st_vocos_forward",
-    "st_cfm_loss_prep", "st_cfm_loss", "st_cfm_loss_backward", "st_cfm_loss_scratch_floats",
-    "st_set_option", "st_get_option", "st_attention_stats",
-    "st_create_style_encoder", "st_style_encoder_forward", "st_create_duration_predictor", "st_duration_predictor_forward",
-    "st_style_encoder_train_forward", "st_style_encoder_train_backward", "st_duration_predictor_train_forward",
-    "st_duration_predictor_train_backward",
-    "st_maximum_path", "st_maximum_path_workspace_bytes", "st_mas_neg_cent",
-    "st_create_mel_extractor", "st_mel_frames", "st_mel_forward", "st_mel_forward_ragged",
-    "st_mel_backward_workspace_bytes", "st_mel_backward",
-]
 ST_PAD_MODES = {"reflect": 0, "constant": 1, "replicate": 2, "circular": 3}
 ST_MEL_LOG, ST_MEL_LINEAR = 0, 1
 
@@ -67,10 +49,90 @@ class StMelConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("n_fft", "win_length", "hop_length", "pad", "n_mels", "center", "pad_mode")]
 
 
+# Engine(...) keyword whose value is a configuration dict -> (its struct, the creator it goes to); in the order Engine looks
+CREATORS = {"mel": (StMelConfig, "st_create_mel_extractor"), "style_encoder": (StStyleEncoderConfig, "st_create_style_encoder"),
+            "duration_predictor": (StDurationPredictorConfig, "st_create_duration_predictor"),
+            "vocoder": (StVocosConfig, "st_create_vocoder")}
+
+
 class NativeError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libstabletts_hip error {code}: {msg}")
         self.code = code
+
+
+vp, i32, i64, u64, f32, f64, c_char_p, P = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float,
+                                              ctypes.c_double, ctypes.c_char_p, ctypes.POINTER)
+# Every symbol include/stabletts_hip.h declares: name -> (restype, argtypes).  load() sets the prototypes from it, so a symbol
+# cannot be exported without one.
+PROTOTYPES = {
+    "st_abi_version": (i32, []),
+    "st_create": (i32, [P(StConfig), i32, P(vp)]),
+    "st_destroy": (None, [vp]),
+    "st_last_error": (c_char_p, [vp]),
+    "st_load_param": (i32, [vp, c_char_p, vp, P(i64), i32]),
+    "st_num_params": (i32, [vp]),
+    "st_finalize": (i32, [vp]),
+    "st_bind_param": (i32, [vp, c_char_p, vp, P(i64), i32]),
+    "st_repack": (i32, [vp, vp]),
+    "st_train_serial": (i64, [vp]),
+    "st_estimator_forward": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "st_cfm_solve": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, i32, i32, vp]),
+    "st_output_status": (i32, [vp, vp, P(i32)]),
+    "st_last_solve_stats": (i32, [vp] + [P(i64)] * 3),
+    "st_debug_capture": (i32, [vp, i32]),
+    "st_debug_fetch": (i64, [vp, c_char_p, vp, i64]),
+    "st_profile_enable": (i32, [vp, i32]),
+    "st_profile_select": (i32, [vp, u64]),
+    "st_param_info": (i32, [vp, i32, P(c_char_p), P(i64)]),
+    "st_create_text_encoder": (i32, [P(StConfig), i32, i32, P(vp)]),
+    "st_text_encoder_forward": (i32, [vp] + [vp] * 6 + [i32, i32, vp]),
+    "st_profile_stride": (i32, [vp, i32]),
+    "st_profile_num_classes": (i32, []),
+    "st_profile_class_name": (c_char_p, [i32]),
+    "st_profile_read": (i32, [vp, i32, P(i64), P(f64), P(f64)]),
+    "st_device_bytes": (i64, [vp]),
+    "st_train_forward": (i32, [vp] + [vp] * 6 + [i32, i32, f32, u64, vp]),
+    "st_train_backward": (i32, [vp, i64, i32, i32] + [vp] * 4 + [vp]),
+    "st_train_backward_part": (i32, [vp, i64, i32, i32, i32, vp, vp, i64] + [vp] * 3 + [vp]),
+    "st_text_encoder_train_forward": (i32, [vp] + [vp] * 6 + [i32, i32, f32, u64, vp]),
+    "st_text_encoder_train_backward": (i32, [vp, i64, i32, i32] + [vp] * 4 + [vp]),
+    "st_train_param_part": (i32, [vp, c_char_p]),
+    "st_train_grad_offset": (i64, [vp, c_char_p]),
+    "st_train_grad_numel": (i64, [vp]),
+    "st_param_grad": (i32, [vp, c_char_p, vp, i64, vp]),
+    "st_param_grads_flat": (i32, [vp, vp, i64, vp]),
+    "st_durations": (i32, [vp, vp, f32, i32, i32, vp, vp, vp, vp]),
+    "st_generate_path": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
+    "st_align": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "st_cfm_loss_prep": (i32, [vp, vp, vp, f32, i32, i32, i32, vp, vp, vp, vp]),
+    "st_cfm_loss": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "st_cfm_loss_backward": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+    "st_cfm_loss_scratch_floats": (i32, []),
+    "st_create_vocoder": (i32, [P(StVocosConfig), i32, P(vp)]),
+    "st_vocos_forward": (i32, [vp, vp, vp, i32, i32, vp]),
+    "st_set_option": (i32, [vp, c_char_p, i32]),
+    "st_get_option": (i32, [vp, c_char_p, P(i32)]),
+    "st_attention_stats": (i32, [vp, vp, P(f32)]),
+    "st_create_style_encoder": (i32, [P(StStyleEncoderConfig), i32, P(vp)]),
+    "st_style_encoder_forward": (i32, [vp, vp, vp, vp, i32, i32, vp]),
+    "st_create_duration_predictor": (i32, [P(StDurationPredictorConfig), i32, P(vp)]),
+    "st_duration_predictor_forward": (i32, [vp, vp, vp, vp, vp, i32, i32, vp]),
+    "st_style_encoder_train_forward": (i32, [vp, vp, vp, vp, i32, i32, f32, u64, vp]),
+    "st_style_encoder_train_backward": (i32, [vp, i64, i32, i32, vp, vp, vp]),
+    "st_duration_predictor_train_forward": (i32, [vp] + [vp] * 4 + [i32, i32, f32, u64, vp]),
+    "st_duration_predictor_train_backward": (i32, [vp, i64, i32, i32, vp, vp, vp]),
+    "st_maximum_path": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "st_maximum_path_workspace_bytes": (i64, [i32, i32, i32]),
+    "st_mas_neg_cent": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
+    "st_create_mel_extractor": (i32, [P(StMelConfig), i32, P(vp)]),
+    "st_mel_frames": (i64, [vp, i64]),
+    "st_mel_forward": (i32, [vp, vp, i32, i64, vp, vp]),
+    "st_mel_forward_ragged": (i32, [vp, vp, P(i64), P(i64), i32, i32, vp, vp]),
+    "st_mel_backward_workspace_bytes": (i64, [vp, i32, i64]),
+    "st_mel_backward": (i32, [vp, vp, vp, i32, i64, i32, vp, vp, vp]),
+}
+EXPORTS = list(PROTOTYPES)
 
 
 _lib = None
@@ -94,139 +156,10 @@ def load():
         raise ImportError(f"{LIB_PATH} not found: build it with `python -m stabletts_amd.build` "
                           "(the native HIP path has no fallback)")
     lib = ctypes.CDLL(LIB_PATH)
-    c_void_p, c_int, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    lib.st_abi_version.restype = c_int
-    lib.st_create.argtypes = [ctypes.POINTER(StConfig), c_int, ctypes.POINTER(c_void_p)]
-    lib.st_create.restype = c_int
-    lib.st_destroy.argtypes = [c_void_p]
-    lib.st_destroy.restype = None
-    lib.st_last_error.argtypes = [c_void_p]
-    lib.st_last_error.restype = ctypes.c_char_p
-    lib.st_load_param.argtypes = [c_void_p, ctypes.c_char_p, c_void_p, ctypes.POINTER(ctypes.c_int64), c_int]
-    lib.st_load_param.restype = c_int
-    lib.st_num_params.argtypes = [c_void_p]
-    lib.st_num_params.restype = c_int
-    lib.st_finalize.argtypes = [c_void_p]
-    lib.st_finalize.restype = c_int
-    lib.st_bind_param.argtypes = [c_void_p, ctypes.c_char_p, c_void_p, ctypes.POINTER(ctypes.c_int64), c_int]
-    lib.st_bind_param.restype = c_int
-    lib.st_repack.argtypes = [c_void_p, c_void_p]
-    lib.st_repack.restype = c_int
-    lib.st_train_serial.argtypes = [c_void_p]
-    lib.st_train_serial.restype = ctypes.c_int64
-    lib.st_estimator_forward.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_int, c_int, c_void_p]
-    lib.st_estimator_forward.restype = c_int
-    lib.st_cfm_solve.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
-                                 c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]
-    lib.st_cfm_solve.restype = c_int
-    lib.st_output_status.argtypes = [c_void_p, c_void_p, ctypes.POINTER(c_int)]
-    lib.st_output_status.restype = c_int
-    lib.st_last_solve_stats.argtypes = [c_void_p] + [ctypes.POINTER(ctypes.c_int64)] * 3
-    lib.st_last_solve_stats.restype = c_int
-    lib.st_debug_capture.argtypes = [c_void_p, c_int]
-    lib.st_debug_capture.restype = c_int
-    lib.st_debug_fetch.argtypes = [c_void_p, ctypes.c_char_p, c_void_p, ctypes.c_int64]
-    lib.st_debug_fetch.restype = ctypes.c_int64
-    lib.st_profile_enable.argtypes = [c_void_p, c_int]
-    lib.st_profile_enable.restype = c_int
-    lib.st_profile_select.argtypes = [c_void_p, ctypes.c_uint64]
-    lib.st_profile_select.restype = c_int
-    lib.st_param_info.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_int64)]
-    lib.st_param_info.restype = c_int
-    lib.st_create_text_encoder.argtypes = [ctypes.POINTER(StConfig), c_int, c_int, ctypes.POINTER(c_void_p)]
-    lib.st_create_text_encoder.restype = c_int
-    lib.st_text_encoder_forward.argtypes = [c_void_p] + [c_void_p] * 6 + [c_int, c_int, c_void_p]
-    lib.st_text_encoder_forward.restype = c_int
-    lib.st_profile_stride.argtypes = [c_void_p, c_int]
-    lib.st_profile_stride.restype = c_int
-    lib.st_profile_num_classes.restype = c_int
-    lib.st_profile_class_name.argtypes = [c_int]
-    lib.st_profile_class_name.restype = ctypes.c_char_p
-    lib.st_profile_read.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_int64),
-                                    ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
-    lib.st_profile_read.restype = c_int
-    lib.st_device_bytes.argtypes = [c_void_p]
-    lib.st_device_bytes.restype = ctypes.c_int64
-    lib.st_train_forward.argtypes = [c_void_p] + [c_void_p] * 6 + [c_int, c_int, c_float, ctypes.c_uint64, c_void_p]
-    lib.st_train_forward.restype = c_int
-    lib.st_train_backward.argtypes = [c_void_p, ctypes.c_int64, c_int, c_int] + [c_void_p] * 4 + [c_void_p]
-    lib.st_train_backward.restype = c_int
-    lib.st_train_backward_part.argtypes = [c_void_p, ctypes.c_int64, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_int64] + [c_void_p] * 3 + [c_void_p]
-    lib.st_train_backward_part.restype = c_int
-    lib.st_text_encoder_train_forward.argtypes = [c_void_p] + [c_void_p] * 6 + [c_int, c_int, c_float, ctypes.c_uint64, c_void_p]
-    lib.st_text_encoder_train_forward.restype = c_int
-    lib.st_text_encoder_train_backward.argtypes = [c_void_p, ctypes.c_int64, c_int, c_int] + [c_void_p] * 4 + [c_void_p]
-    lib.st_text_encoder_train_backward.restype = c_int
-    lib.st_train_param_part.argtypes = [c_void_p, ctypes.c_char_p]
-    lib.st_train_param_part.restype = c_int
-    lib.st_train_grad_offset.argtypes = [c_void_p, ctypes.c_char_p]
-    lib.st_train_grad_offset.restype = ctypes.c_int64
-    lib.st_train_grad_numel.argtypes = [c_void_p]
-    lib.st_train_grad_numel.restype = ctypes.c_int64
-    lib.st_param_grad.argtypes = [c_void_p, ctypes.c_char_p, c_void_p, ctypes.c_int64, c_void_p]
-    lib.st_param_grad.restype = c_int
-    lib.st_param_grads_flat.argtypes = [c_void_p, c_void_p, ctypes.c_int64, c_void_p]
-    lib.st_param_grads_flat.restype = c_int
-    lib.st_durations.argtypes = [c_void_p, c_void_p, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.st_durations.restype = c_int
-    lib.st_generate_path.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
-    lib.st_generate_path.restype = c_int
-    lib.st_align.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.st_align.restype = c_int
-    lib.st_cfm_loss_prep.argtypes = [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.st_cfm_loss_prep.restype = c_int
-    lib.st_cfm_loss.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
-    lib.st_cfm_loss.restype = c_int
-    lib.st_cfm_loss_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
-    lib.st_cfm_loss_backward.restype = c_int
-    lib.st_cfm_loss_scratch_floats.argtypes = []
-    lib.st_cfm_loss_scratch_floats.restype = c_int
-    lib.st_create_vocoder.argtypes = [ctypes.POINTER(StVocosConfig), c_int, ctypes.POINTER(c_void_p)]
-    lib.st_create_vocoder.restype = c_int
-    lib.st_vocos_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]
-    lib.st_vocos_forward.restype = c_int
-    lib.st_set_option.argtypes = [c_void_p, ctypes.c_char_p, c_int]
-    lib.st_set_option.restype = c_int
-    lib.st_get_option.argtypes = [c_void_p, ctypes.c_char_p, ctypes.POINTER(c_int)]
-    lib.st_get_option.restype = c_int
-    lib.st_attention_stats.argtypes = [c_void_p, c_void_p, ctypes.POINTER(c_float)]
-    lib.st_attention_stats.restype = c_int
-    lib.st_create_style_encoder.argtypes = [ctypes.POINTER(StStyleEncoderConfig), c_int, ctypes.POINTER(c_void_p)]
-    lib.st_create_style_encoder.restype = c_int
-    lib.st_style_encoder_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]
-    lib.st_style_encoder_forward.restype = c_int
-    lib.st_create_duration_predictor.argtypes = [ctypes.POINTER(StDurationPredictorConfig), c_int, ctypes.POINTER(c_void_p)]
-    lib.st_create_duration_predictor.restype = c_int
-    lib.st_duration_predictor_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]
-    lib.st_duration_predictor_forward.restype = c_int
-    lib.st_style_encoder_train_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, ctypes.c_uint64, c_void_p]
-    lib.st_style_encoder_train_forward.restype = c_int
-    lib.st_style_encoder_train_backward.argtypes = [c_void_p, ctypes.c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]
-    lib.st_style_encoder_train_backward.restype = c_int
-    lib.st_duration_predictor_train_forward.argtypes = [c_void_p] + [c_void_p] * 4 + [c_int, c_int, c_float, ctypes.c_uint64, c_void_p]
-    lib.st_duration_predictor_train_forward.restype = c_int
-    lib.st_duration_predictor_train_backward.argtypes = [c_void_p, ctypes.c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]
-    lib.st_duration_predictor_train_backward.restype = c_int
-    lib.st_maximum_path.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.st_maximum_path.restype = c_int
-    lib.st_maximum_path_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    lib.st_maximum_path_workspace_bytes.restype = ctypes.c_int64
-    lib.st_mas_neg_cent.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
-    lib.st_mas_neg_cent.restype = c_int
-    lib.st_create_mel_extractor.argtypes = [ctypes.POINTER(StMelConfig), c_int, ctypes.POINTER(c_void_p)]
-    lib.st_create_mel_extractor.restype = c_int
-    lib.st_mel_frames.argtypes = [c_void_p, ctypes.c_int64]
-    lib.st_mel_frames.restype = ctypes.c_int64
-    lib.st_mel_forward.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_int64, c_void_p, c_void_p]
-    lib.st_mel_forward.restype = c_int
-    lib.st_mel_forward_ragged.argtypes = [c_void_p, c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_int,
-                                          c_int, c_void_p, c_void_p]
-    lib.st_mel_forward_ragged.restype = c_int
-    lib.st_mel_backward_workspace_bytes.argtypes = [c_void_p, c_int, ctypes.c_int64]
-    lib.st_mel_backward_workspace_bytes.restype = ctypes.c_int64
-    lib.st_mel_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_int64, c_int, c_void_p, c_void_p, c_void_p]
-    lib.st_mel_backward.restype = c_int
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype = restype
+        fn.argtypes = argtypes
     if lib.st_abi_version() != 4:
         raise ImportError("libstabletts_hip.so ABI version mismatch; rebuild it")
     _lib = lib
@@ -252,26 +185,20 @@ class Engine:
         if operand_dtype not in OPERAND_DTYPES:
             raise ValueError(f"operand_dtype must be one of {sorted(OPERAND_DTYPES)}")
         self.operand_dtype = operand_dtype
-        cfg = StConfig(noise_channels, hidden_channels, filter_channels, n_heads, n_layers, kernel_size,
-                       gin_channels, OPERAND_DTYPES[operand_dtype])
         h = ctypes.c_void_p()
-        if mel is not None:
-            mc = StMelConfig(*(int(mel[n]) for n, _ in StMelConfig._fields_))
-            rc = self.lib.st_create_mel_extractor(ctypes.byref(mc), int(device), ctypes.byref(h))
-        elif style_encoder is not None:
-            sc = StStyleEncoderConfig(*(int(style_encoder[n]) for n, _ in StStyleEncoderConfig._fields_))
-            rc = self.lib.st_create_style_encoder(ctypes.byref(sc), int(device), ctypes.byref(h))
-        elif duration_predictor is not None:
-            dc = StDurationPredictorConfig(*(int(duration_predictor[n]) for n, _ in StDurationPredictorConfig._fields_))
-            rc = self.lib.st_create_duration_predictor(ctypes.byref(dc), int(device), ctypes.byref(h))
-        elif vocoder is not None:
-            vc = StVocosConfig(vocoder["input_channels"], vocoder["dim"], vocoder["intermediate_dim"], vocoder["num_layers"],
-                               vocoder["n_fft"], vocoder["hop_length"], OPERAND_DTYPES[operand_dtype])
-            rc = self.lib.st_create_vocoder(ctypes.byref(vc), int(device), ctypes.byref(h))
-        elif text_encoder_vocab is None:
-            rc = self.lib.st_create(ctypes.byref(cfg), int(device), ctypes.byref(h))
+        dicts = dict(mel=mel, style_encoder=style_encoder, duration_predictor=duration_predictor, vocoder=vocoder)
+        kw = next((k for k in CREATORS if dicts[k] is not None), None)
+        if kw:          # a configuration dict: its struct's fields by name (operand_dtype, where the struct has one, from the argument)
+            (struct, creator), d = CREATORS[kw], dicts[kw]
+            cfg = struct(*(OPERAND_DTYPES[operand_dtype] if n == "operand_dtype" else int(d[n]) for n, _ in struct._fields_))
+            rc = getattr(self.lib, creator)(ctypes.byref(cfg), int(device), ctypes.byref(h))
         else:
-            rc = self.lib.st_create_text_encoder(ctypes.byref(cfg), int(text_encoder_vocab), int(device), ctypes.byref(h))
+            cfg = StConfig(noise_channels, hidden_channels, filter_channels, n_heads, n_layers, kernel_size,
+                           gin_channels, OPERAND_DTYPES[operand_dtype])
+            if text_encoder_vocab is None:
+                rc = self.lib.st_create(ctypes.byref(cfg), int(device), ctypes.byref(h))
+            else:
+                rc = self.lib.st_create_text_encoder(ctypes.byref(cfg), int(text_encoder_vocab), int(device), ctypes.byref(h))
         if rc != ST_OK:
             raise NativeError(rc, self.lib.st_last_error(None).decode())
         self.handle = h

@@ -25,6 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._native_module import hip_device_index
 
 _PAD_MODES = ("constant", "reflect", "replicate", "circular")
 
@@ -146,11 +147,7 @@ class _Extractor:
         return {"cfg": self.cfg, "engine": None, "key": None}
 
     def get(self, buffers):
-        t0 = next(iter(buffers.values()))
-        if t0.device.type != "cuda":
-            raise RuntimeError("stabletts_amd: the spectrogram runs only on a HIP device (move the module with .to('cuda')); "
-                               "there is no CPU fallback")
-        dev = t0.device.index if t0.device.index is not None else torch.cuda.current_device()
+        dev = hip_device_index(next(iter(buffers.values())).device, "spectrogram")
         if self.engine is None or self.engine.device != dev:
             if self.engine is not None:
                 self.engine.close()
@@ -170,9 +167,7 @@ def _waveform(x, dev, grad_ok=False):
     if not grad_ok and torch.is_grad_enabled() and x.requires_grad:
         raise NotImplementedError("the native spectrogram is inference-only here (native_training = False, or a ragged batch): "
                                   "call it under torch.no_grad(), or use stabletts_amd.audio_train (install(audio=\"train\"))")
-    if dev.type != "cuda":
-        raise RuntimeError("stabletts_amd: the spectrogram runs only on a HIP device (move the module with .to('cuda')); "
-                           "there is no CPU fallback")
+    hip_device_index(dev, "spectrogram")
     if x.device != dev:
         raise ValueError(f"the waveform is on {x.device}, the module's buffers are on {dev}")
     if x.dim() == 3:

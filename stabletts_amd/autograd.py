@@ -9,6 +9,8 @@ seed is drawn from torch's CPU generator per forward, so ``torch.manual_seed`` m
 """
 import torch
 
+from ._native_module import check_activations_live, dropout_seed, param_grad_views
+
 
 # Set to a list to record the order of host-side events of the training path: ("backward_part", k) when part k of a native
 # backward is enqueued (tests assert that DDP launches its first bucket before the last part is enqueued).
@@ -26,26 +28,8 @@ class _Shared:
 
 
 def _check_live(sh):
-    decoder, eng = sh.decoder, sh.engine
-    if eng is not decoder._engine or eng.handle is None or eng.train_serial() != sh.serial:
-        raise RuntimeError(
-            "stabletts_amd: this backward's activations are gone -- the engine keeps the activations of ONE "
-            "grad-enabled estimator forward, and another grad-enabled forward, an optimizer step / parameter update "
-            "or a device move happened since.  Call backward() before the next grad-enabled forward (for "
-            "loss_a + loss_b or gradient accumulation: backward each loss separately, gradients accumulate in .grad).")
-
-
-def _param_grads(sh, names, params, need):
-    """Views of the flat gradient buffer the native backward wrote into (no copy): one storage for all parameters of this
-    backward, each slice 64-byte aligned; a parameter's .grad keeps that storage alive until it is replaced."""
-    out = []
-    for name, p, nd in zip(names, params, need):
-        if not nd:
-            out.append(None)
-            continue
-        off, n, _ = sh.lay[name]
-        out.append(sh.flat[off:off + n].view(p.shape))
-    return out
+    check_activations_live(sh.decoder, sh.engine, sh.serial, advice="(for loss_a + loss_b or gradient accumulation: "
+                           "backward each loss separately, gradients accumulate in .grad).")
 
 
 class _BottomFn(torch.autograd.Function):
@@ -69,7 +53,7 @@ class _BottomFn(torch.autograd.Function):
             raise ValueError("shape mismatch: x/mu (B,M,T), mask (B,1,T), c (B,gin)")
         out = torch.empty_like(x32)
         p_drop = float(decoder.p_dropout) if decoder.training else 0.0
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p_drop > 0.0 else 0
+        seed = dropout_seed(p_drop)
         with torch.cuda.device(dev):
             eng.train_forward(t32, x32, mu32, m32, c32, out, p_drop, seed, torch.cuda.current_stream(dev).cuda_stream)
         sh.engine, sh.serial = eng, eng.train_serial()     # the engine keeps the activations of ONE forward: its serial
@@ -92,7 +76,7 @@ class _BottomFn(torch.autograd.Function):
         with torch.cuda.device(dev):
             _trace("backward_part", 2)
             sh.engine.train_backward_part(sh.serial, 2, B, T, None, None, gx, gmu, gc, torch.cuda.current_stream(dev).cuda_stream)
-        pg = _param_grads(sh, ctx.names, ctx.params, need[7:])
+        pg = param_grad_views(sh.flat, sh.lay, ctx.names, ctx.params, need[7:])
         sh.flat = None
         return (None, None, None, gx, None, gmu, gc, *pg)
 
@@ -114,7 +98,7 @@ class _MidFn(torch.autograd.Function):
         with torch.cuda.device(dev):
             _trace("backward_part", 1)
             sh.engine.train_backward_part(sh.serial, 1, B, T, None, None, None, None, None, torch.cuda.current_stream(dev).cuda_stream)
-        return (None, None, torch.zeros((), device=dev), *_param_grads(sh, ctx.names, ctx.params, ctx.needs_input_grad[3:]))
+        return (None, None, torch.zeros((), device=dev), *param_grad_views(sh.flat, sh.lay, ctx.names, ctx.params, ctx.needs_input_grad[3:]))
 
 
 class _TopFn(torch.autograd.Function):
@@ -141,7 +125,7 @@ class _TopFn(torch.autograd.Function):
             sh.flat = torch.zeros(sh.lay[None], device=dev, dtype=torch.float32)
             _trace("backward_part", 0)
             sh.engine.train_backward_part(sh.serial, 0, B, T, g, sh.flat, None, None, None, torch.cuda.current_stream(dev).cuda_stream)
-        return (None, None, torch.zeros((), device=dev), *_param_grads(sh, ctx.names, ctx.params, ctx.needs_input_grad[3:]))
+        return (None, None, torch.zeros((), device=dev), *param_grad_views(sh.flat, sh.lay, ctx.names, ctx.params, ctx.needs_input_grad[3:]))
 
 
 def estimator_apply(decoder, t, x, mask, mu, c):

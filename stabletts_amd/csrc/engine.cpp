@@ -37,7 +37,7 @@ void expect(st_engine* e, const std::string& name, std::vector<int64_t> shape) {
 
 void build_param_table(st_engine* e) {
     const int C = e->C, F = e->F, M = e->M, K = e->K, G = e->G;
-    if (e->kind == 1) {     // TextEncoder state_dict (models/text_encoder.py:22-26)
+    if (e->kind == KIND_TEXT_ENCODER) {     // TextEncoder state_dict (models/text_encoder.py:22-26)
         expect(e, "emb.weight", {e->n_vocab, C});
         for (int i = 0; i < e->L; ++i) {
             const std::string p = e->blk(i);
@@ -317,7 +317,7 @@ ConvGemmArgs base_args(const st_engine* e, const Plan& p, const Conv& cv, int n_
     // ragged batches: tiles past an utterance's last needed frame are skipped (every frame is computed under debug
     // capture, whose taps are compared over the whole padded tensor).  The shared uncond prenet item (index B of B + 1)
     // is needed as far as the longest utterance: entry B of t_lim.
-    if (e->ragged_skip && !e->capture && e->kind == 0) { a.t_lim = p.t_lim; a.t_lim_mod = (n_items == p.B + 1) ? p.B + 1 : p.B; }
+    if (e->ragged_skip && !e->capture && e->kind == KIND_DECODER) { a.t_lim = p.t_lim; a.t_lim_mod = (n_items == p.B + 1) ? p.B + 1 : p.B; }
     return a;
 }
 
@@ -595,11 +595,54 @@ int run_text_blocks(st_engine* e, const Plan& p, const float* mask, hipStream_t 
     return ST_OK;
 }
 
+int check_handle(st_engine* e, Kind kind) {
+    if (!e) return ST_ERR_INVALID;
+    if (e->kind != kind)
+        return e->fail(ST_ERR_STATE, std::string("this handle is not a ") + kKinds[kind].what + " (" + kKinds[kind].creator + ")");
+    return ST_OK;
+}
+
+int check_finalized(st_engine* e) {
+    return e->finalized ? ST_OK : e->fail(ST_ERR_STATE, "st_finalize() has not been called after loading parameters");
+}
+
+int check_sizes(st_engine* e, int B, int T, const char* t_name) {
+    return B >= 1 && T >= 1 ? ST_OK : e->fail(ST_ERR_INVALID, std::string("B and ") + t_name + " must be >= 1");
+}
+
+int check_dropout(st_engine* e, float p_dropout) {
+    return p_dropout >= 0.0f && p_dropout < 1.0f ? ST_OK : e->fail(ST_ERR_INVALID, "p_dropout must be in [0, 1)");
+}
+
 int check_ready(st_engine* e, int B, int T) {
     if (!e) return ST_ERR_INVALID;
-    if (!e->finalized) return e->fail(ST_ERR_STATE, "st_finalize() has not been called after loading parameters");
-    if (B < 1 || T < 1) return e->fail(ST_ERR_INVALID, "B and T must be >= 1");
+    int rc = check_finalized(e); if (rc) return rc;
+    if ((rc = check_sizes(e, B, T))) return rc;
     if ((int64_t)2 * B * T * e->F >= (int64_t)1 << 31) return e->fail(ST_ERR_INVALID, "B*T too large for 32-bit row indexing");
+    return ST_OK;
+}
+
+int new_handle(Kind kind, int device, st_engine** out) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { g_create_error = "no such HIP device"; return ST_ERR_HIP; }
+    if (hipSetDevice(device) != hipSuccess) { g_create_error = "hipSetDevice failed"; return ST_ERR_HIP; }
+    st_engine* e = new st_engine();
+    e->device = device; e->kind = kind;
+    *out = e;
+    return ST_OK;
+}
+
+// st_load_param / st_bind_param: the table row of `name`, if the caller's shape is the expected one
+static int find_param(st_engine* e, const char* name, const float* data, const int64_t* shape, int ndim, Param** out) {
+    if (!e) return ST_ERR_INVALID;
+    if (!name || !data || !shape) return e->fail(ST_ERR_INVALID, "null argument");
+    auto it = e->params.find(name);
+    if (it == e->params.end()) return e->fail(ST_ERR_INVALID, std::string("unexpected parameter name: ") + name);
+    Param& p = it->second;
+    bool ok = (int)p.shape.size() == ndim;
+    for (int i = 0; ok && i < ndim; ++i) ok = p.shape[i] == shape[i];
+    if (!ok) return e->fail(ST_ERR_INVALID, std::string("shape mismatch for ") + name);
+    *out = &p;
     return ST_OK;
 }
 
@@ -610,14 +653,14 @@ extern "C" {
 
 int st_abi_version(void) { return ST_ABI_VERSION; }
 
-static int create_engine(const st_config* cfg, int kind, int n_vocab, int device, st_engine** out) {
+static int create_engine(const st_config* cfg, Kind kind, int n_vocab, int device, st_engine** out) {
     if (!cfg || !out) { g_create_error = "null argument"; return ST_ERR_INVALID; }
     auto bad = [&](const char* m) { g_create_error = m; return ST_ERR_INVALID; };
     // the reference's own assertions
-    if (kind == 0 && (cfg->n_layers % 2 != 0 || cfg->n_layers < 2 || cfg->n_layers > 16))
+    if (kind == KIND_DECODER && (cfg->n_layers % 2 != 0 || cfg->n_layers < 2 || cfg->n_layers > 16))
         return bad("n_layers must be even (estimator.py:92) and in [2, 16]");
-    if (kind == 1 && (cfg->n_layers < 1 || cfg->n_layers > 16)) return bad("n_layers must be in [1, 16]");
-    if (kind == 1 && n_vocab < 1) return bad("n_vocab must be >= 1");
+    if (kind == KIND_TEXT_ENCODER && (cfg->n_layers < 1 || cfg->n_layers > 16)) return bad("n_layers must be in [1, 16]");
+    if (kind == KIND_TEXT_ENCODER && n_vocab < 1) return bad("n_vocab must be >= 1");
     if (cfg->hidden_channels % 2 != 0) return bad("SinusoidalPosEmb requires dim to be even (estimator.py:39)");
     if (cfg->n_heads < 1 || cfg->hidden_channels % cfg->n_heads != 0)
         return bad("channels % n_heads != 0 (diffusion_transformer.py:35)");
@@ -629,19 +672,14 @@ static int create_engine(const st_config* cfg, int kind, int n_vocab, int device
     if (cfg->noise_channels < 1 || cfg->noise_channels > 1024) return bad("noise_channels out of range");
     if (cfg->gin_channels < 4 || cfg->gin_channels % 4 != 0) return bad("gin_channels must be a positive multiple of 4");
     if (cfg->operand_dtype != ST_OPERAND_BF16 && cfg->operand_dtype != ST_OPERAND_F16) return bad("operand_dtype");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        g_create_error = "no such HIP device";
-        return ST_ERR_HIP;
-    }
-    if (hipSetDevice(device) != hipSuccess) { g_create_error = "hipSetDevice failed"; return ST_ERR_HIP; }
-    st_engine* e = new st_engine();
-    e->cfg = *cfg; e->device = device;
+    st_engine* e = nullptr;
+    if (int rc = new_handle(kind, device, &e)) return rc;
+    e->cfg = *cfg;
     e->dt = cfg->operand_dtype == ST_OPERAND_BF16 ? DT_BF16 : DT_F16;
     e->M = cfg->noise_channels; e->Mp = (e->M + 127) / 128 * 128;
     e->C = cfg->hidden_channels; e->F = cfg->filter_channels; e->H = cfg->n_heads; e->L = cfg->n_layers;
     e->K = cfg->kernel_size; e->G = cfg->gin_channels;
-    e->kind = kind; e->n_vocab = n_vocab;
+    e->n_vocab = n_vocab;
     if (const char* mb = getenv("ST_BIG_MIN_BLOCKS")) e->big_min_blocks = atoi(mb);
     if (const char* v = getenv("ST_PHASED")) e->phased = atoi(v);
     if (const char* v = getenv("ST_FUSED_FFN")) e->fused_ffn = atoi(v);
@@ -682,10 +720,10 @@ static int create_engine(const st_config* cfg, int kind, int n_vocab, int device
     return ST_OK;
 }
 
-int st_create(const st_config* cfg, int device, st_engine** out) { return create_engine(cfg, 0, 0, device, out); }
+int st_create(const st_config* cfg, int device, st_engine** out) { return create_engine(cfg, KIND_DECODER, 0, device, out); }
 
 int st_create_text_encoder(const st_config* cfg, int n_vocab, int device, st_engine** out) {
-    return create_engine(cfg, 1, n_vocab, device, out);
+    return create_engine(cfg, KIND_TEXT_ENCODER, n_vocab, device, out);
 }
 
 void st_destroy(st_engine* e) {
@@ -734,14 +772,9 @@ int st_param_info(const st_engine* e, int index, const char** name, int64_t* sha
 }
 
 int st_load_param(st_engine* e, const char* name, const float* data, const int64_t* shape, int ndim) {
-    if (!e) return ST_ERR_INVALID;
-    if (!name || !data || !shape) return e->fail(ST_ERR_INVALID, "null argument");
-    auto it = e->params.find(name);
-    if (it == e->params.end()) return e->fail(ST_ERR_INVALID, std::string("unexpected parameter name: ") + name);
-    Param& p = it->second;
-    bool ok = (int)p.shape.size() == ndim;
-    for (int i = 0; ok && i < ndim; ++i) ok = p.shape[i] == shape[i];
-    if (!ok) return e->fail(ST_ERR_INVALID, std::string("shape mismatch for ") + name);
+    Param* pp = nullptr;
+    if (int rc = find_param(e, name, data, shape, ndim, &pp)) return rc;
+    Param& p = *pp;
     HIPCHK(e, hipSetDevice(e->device));
     if (p.borrowed) { p.dev = nullptr; p.borrowed = false; }
     if (!p.dev) {       // new pointer: the recorded re-pack jobs are stale, and so are instantiated graphs (they bake the fp32
@@ -754,14 +787,9 @@ int st_load_param(st_engine* e, const char* name, const float* data, const int64
 }
 
 int st_bind_param(st_engine* e, const char* name, const float* data, const int64_t* shape, int ndim) {
-    if (!e) return ST_ERR_INVALID;
-    if (!name || !data || !shape) return e->fail(ST_ERR_INVALID, "null argument");
-    auto it = e->params.find(name);
-    if (it == e->params.end()) return e->fail(ST_ERR_INVALID, std::string("unexpected parameter name: ") + name);
-    Param& p = it->second;
-    bool ok = (int)p.shape.size() == ndim;
-    for (int i = 0; ok && i < ndim; ++i) ok = p.shape[i] == shape[i];
-    if (!ok) return e->fail(ST_ERR_INVALID, std::string("shape mismatch for ") + name);
+    Param* pp = nullptr;
+    if (int rc = find_param(e, name, data, shape, ndim, &pp)) return rc;
+    Param& p = *pp;
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, data) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->device) {
         (void)hipGetLastError();
@@ -779,9 +807,9 @@ int st_bind_param(st_engine* e, const char* name, const float* data, const int64
 
 int st_repack(st_engine* e, void* stream) {
     if (!e) return ST_ERR_INVALID;
-    if (e->kind == 2) return e->fail(ST_ERR_UNSUPPORTED, "st_repack: vocoder handles re-pack through st_finalize");
-    if (e->kind == 5) return e->fail(ST_ERR_UNSUPPORTED, "st_repack: mel-extractor handles re-read their filter bank through st_finalize");
-    if (e->kind >= 3) return e->fail(ST_ERR_UNSUPPORTED, "st_repack: style-encoder / duration-predictor handles read their parameters in place");
+    if (e->kind == KIND_VOCODER) return e->fail(ST_ERR_UNSUPPORTED, "st_repack: vocoder handles re-pack through st_finalize");
+    if (e->kind == KIND_MEL_EXTRACTOR) return e->fail(ST_ERR_UNSUPPORTED, "st_repack: mel-extractor handles re-read their filter bank through st_finalize");
+    if (reads_params_in_place(e->kind)) return e->fail(ST_ERR_UNSUPPORTED, "st_repack: style-encoder / duration-predictor handles read their parameters in place");
     if (!e->packed_once) return e->fail(ST_ERR_STATE, "st_repack needs one earlier st_finalize (it allocates the packed buffers)");
     // A re-bind / re-load since the last st_finalize may have moved fp32 tensors: st_repack is for in-place updates only.
     if (!e->finalized && !e->pk_fwd.ready)
@@ -801,13 +829,13 @@ int st_finalize(st_engine* e) {
     for (auto& kv : e->params)
         if (!kv.second.loaded) return e->fail(ST_ERR_STATE, "parameter not loaded: " + kv.first);
     HIPCHK(e, hipDeviceSynchronize());
-    if (e->kind == 5) return mel_finalize(e);      // the filter bank's band table
-    if (e->kind >= 3) {      // fp32 kernels read the loaded tensors in place: nothing to pack
+    if (e->kind == KIND_MEL_EXTRACTOR) return mel_finalize(e);      // the filter bank's band table
+    if (reads_params_in_place(e->kind)) {
         if (e->sdt) e->sdt->have = false;      // a re-bind / re-load: the held training activations are of other weights
         e->finalized = true;
         return ST_OK;
     }
-    if (e->kind == 2) {
+    if (e->kind == KIND_VOCODER) {
         e->drop_graphs();
         for (void* p : e->owned) hipFree(p);
         e->owned.clear(); e->weight_bytes = 0;
@@ -895,7 +923,7 @@ int pack_all(st_engine* e, hipStream_t s) {
         return ST_OK;
     };
     int rc;
-    if (e->kind == 1) {
+    if (e->kind == KIND_TEXT_ENCODER) {
         if ((rc = pack(e->fin, "proj.weight", P(e, "proj.bias"), M, Mp, C, 1, 0, C, C, true))) return rc;      // split precision: its error reaches mu_x un-gated
     } else {
     if (e->pre.size() != 3) e->pre.assign(3, Conv());
@@ -945,7 +973,7 @@ int pack_all(st_engine* e, hipStream_t s) {
         }
         if ((rc = pack(e->ffn1[i], b + "mlp.conv_1.weight", P(e, b + "mlp.conv_1.bias"), F, F, C, K, 0, C, C, false))) return rc;
         if ((rc = pack(e->ffn2[i], b + "mlp.conv_2.weight", P(e, b + "mlp.conv_2.bias"), C, C, F, K, 0, F, F, false))) return rc;
-        if (e->kind == 0 && C == 256 && K == 3 && F % 256 == 0 && F <= 2048) {      // the fused FFN kernel's weight stream (ffn_fused.h)
+        if (e->kind == KIND_DECODER && C == 256 && K == 3 && F % 256 == 0 && F <= 2048) {      // the fused FFN kernel's weight stream (ffn_fused.h)
             if ((int)e->ffn_stream.size() != L) e->ffn_stream.assign(L, nullptr);
             if (!e->ffn_stream[i] && (rc = dev_alloc(e, &e->ffn_stream[i], (size_t)2 * F * C * K * 2))) return rc;
             for (int st = 0; st < 2; ++st) {
@@ -970,7 +998,7 @@ extern "C" {
 int st_estimator_forward(st_engine* e, const float* t, int t_len, const float* x, const float* mu,
                          const float* mask, const float* c, float* out, int B, int T, void* stream) {
     int rc = check_ready(e, B, T); if (rc) return rc;
-    if (e->kind != 0) return e->fail(ST_ERR_STATE, "this handle is not a CFM decoder (st_create)");
+    if ((rc = check_handle(e, KIND_DECODER))) return rc;
     if (!t || !x || !mu || !mask || !c || !out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if (t_len != 1 && t_len != B) return e->fail(ST_ERR_INVALID, "t must have 1 or B elements");
     HIPCHK(e, hipSetDevice(e->device));
@@ -1004,7 +1032,7 @@ int st_estimator_forward(st_engine* e, const float* t, int t_len, const float* x
 int st_text_encoder_forward(st_engine* e, const int64_t* tokens, const int64_t* lengths, const float* c,
                             float* x_out, float* mu_out, float* mask_out, int B, int T, void* stream) {
     int rc = check_ready(e, B, T); if (rc) return rc;
-    if (e->kind != 1) return e->fail(ST_ERR_STATE, "this handle is not a text encoder (st_create_text_encoder)");
+    if ((rc = check_handle(e, KIND_TEXT_ENCODER))) return rc;
     if (!tokens || !lengths || !c || !x_out || !mu_out || !mask_out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
@@ -1141,7 +1169,7 @@ int st_set_option(st_engine* e, const char* name, int value) {
     const std::string n(name);
     if (n == "attention_precision") {
         if (value != 0 && value != 1) return e->fail(ST_ERR_INVALID, "attention_precision: 0 (16-bit q / k operands) or 1 (split hi + lo operands)");
-        if (e->kind != 0) return e->fail(ST_ERR_UNSUPPORTED, "attention_precision: CFM decoder handles only");
+        if (e->kind != KIND_DECODER) return e->fail(ST_ERR_UNSUPPORTED, "attention_precision: CFM decoder handles only");
         if (value != e->attn_split) { e->drop_graphs(); e->attn_split = value; }
         return ST_OK;
     }

@@ -1,5 +1,5 @@
 // Feature front end behind the C ABI (st_create_mel_extractor / st_mel_forward / st_mel_forward_ragged / st_mel_backward):
-// handle kind 5.
+// handle kind KIND_MEL_EXTRACTOR.
 // Reference: utils/audio.py:6-52 (LinearSpectrogram, LogMelSpectrogram), config.py:4-19.  The window and the filter bank
 // are the module's buffers ("spectrogram.window", "mel_scale.fb"), loaded like parameters; st_finalize derives each
 // filter's nonzero bin range from the loaded fb and packs those weights, and the same table bin-major for the backward.  The
@@ -102,7 +102,7 @@ static int64_t frames_of(const st_mel_config& c, int64_t L) {
 }
 
 static int mel_check(st_engine* e, const float* wave, float* out) {
-    if (e->kind != 5) return e->fail(ST_ERR_STATE, "this handle is not a mel extractor (st_create_mel_extractor)");
+    int rc = check_handle(e, KIND_MEL_EXTRACTOR); if (rc) return rc;
     if (!e->finalized) return e->fail(ST_ERR_STATE, "st_finalize() has not been called after loading the window / filter bank");
     if (!wave || !out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     return ST_OK;
@@ -135,27 +135,22 @@ int st_create_mel_extractor(const st_mel_config* cfg, int device, st_engine** ou
     if (cfg->win_length != cfg->n_fft) return bad("native kernels are built for win_length == n_fft", ST_ERR_UNSUPPORTED);
     if (cfg->n_fft < kMelMinNfft || cfg->n_fft > kMelMaxNfft || (cfg->n_fft & (cfg->n_fft - 1)))
         return bad("native kernels are built for n_fft a power of two in [32, 2048]", ST_ERR_UNSUPPORTED);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return bad("no such HIP device", ST_ERR_HIP);
-    if (hipSetDevice(device) != hipSuccess) return bad("hipSetDevice failed", ST_ERR_HIP);
-    st_engine* e = new st_engine();
-    e->device = device; e->kind = 5;
+    st_engine* e = nullptr;
+    if (int rc = new_handle(KIND_MEL_EXTRACTOR, device, &e)) return rc;
     e->mel = new MelState();
     e->mel->cfg = *cfg;
-    auto expect = [&](const std::string& n, std::vector<int64_t> shape) { Param p; p.shape = std::move(shape); e->params[n] = p; };
-    expect("spectrogram.window", {cfg->win_length});                                        // utils/audio.py:17
-    if (cfg->n_mels > 0) expect("mel_scale.fb", {cfg->n_fft / 2 + 1, cfg->n_mels});         // :45 (MelScale's buffer)
+    expect(e, "spectrogram.window", {cfg->win_length});                                        // utils/audio.py:17
+    if (cfg->n_mels > 0) expect(e, "mel_scale.fb", {cfg->n_fft / 2 + 1, cfg->n_mels});         // :45 (MelScale's buffer)
     *out = e;
     return ST_OK;
 }
 
 int64_t st_mel_frames(const st_engine* e, int64_t L) {
-    if (!e || e->kind != 5) return ST_ERR_INVALID;
+    if (!e || e->kind != KIND_MEL_EXTRACTOR) return ST_ERR_INVALID;
     return frames_of(e->mel->cfg, L);
 }
 
 int st_mel_forward(st_engine* e, const float* wave, int B, int64_t L, float* out, void* stream) {
-    if (!e) return ST_ERR_INVALID;
     int rc = mel_check(e, wave, out); if (rc) return rc;
     const st_mel_config& c = e->mel->cfg;
     if (c.n_mels < 1) return e->fail(ST_ERR_STATE, "a linear-spectrogram extractor (n_mels = 0) has no mel output: st_mel_forward_ragged with ST_MEL_LINEAR");
@@ -174,7 +169,6 @@ int st_mel_forward(st_engine* e, const float* wave, int B, int64_t L, float* out
 
 int st_mel_forward_ragged(st_engine* e, const float* wave, const int64_t* sample_offsets, const int64_t* frame_offsets, int B,
                           int output, float* out, void* stream) {
-    if (!e) return ST_ERR_INVALID;
     int rc = mel_check(e, wave, out); if (rc) return rc;
     if (!sample_offsets || !frame_offsets) return e->fail(ST_ERR_INVALID, "null offsets");
     if (B < 1) return e->fail(ST_ERR_INVALID, "B must be >= 1");
@@ -234,7 +228,7 @@ int st_mel_forward_ragged(st_engine* e, const float* wave, const int64_t* sample
 }
 
 int64_t st_mel_backward_workspace_bytes(const st_engine* e, int B, int64_t L) {
-    if (!e || e->kind != 5 || B < 1) return ST_ERR_INVALID;
+    if (!e || e->kind != KIND_MEL_EXTRACTOR || B < 1) return ST_ERR_INVALID;
     const st_mel_config& c = e->mel->cfg;
     const int64_t T = frames_of(c, L);
     if (T < 0) return ST_ERR_INVALID;
@@ -243,7 +237,6 @@ int64_t st_mel_backward_workspace_bytes(const st_engine* e, int B, int64_t L) {
 
 int st_mel_backward(st_engine* e, const float* wave, const float* grad_out, int B, int64_t L, int output, float* grad_wave,
                     void* workspace, void* stream) {
-    if (!e) return ST_ERR_INVALID;
     int rc = mel_check(e, wave, grad_wave); if (rc) return rc;
     if (!grad_out || !workspace) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if (output != ST_MEL_LOG && output != ST_MEL_LINEAR) return e->fail(ST_ERR_INVALID, "output must be ST_MEL_LOG or ST_MEL_LINEAR");

@@ -17,14 +17,13 @@ struct DurState {
 };
 
 static void duration_build_params(st_engine* e, const st_duration_predictor_config& c) {
-    auto expect = [&](const std::string& n, std::vector<int64_t> shape) { Param p; p.shape = std::move(shape); e->params[n] = p; };
     const int64_t Ci = c.in_channels, F = c.filter_channels, K = c.kernel_size, G = c.gin_channels;
-    expect("conv1.weight", {F, Ci, K}); expect("conv1.bias", {F});                // duration_predictor.py:16-21
-    expect("norm1.weight", {F}); expect("norm1.bias", {F});
-    expect("conv2.weight", {F, F, K}); expect("conv2.bias", {F});
-    expect("norm2.weight", {F}); expect("norm2.bias", {F});
-    expect("proj.weight", {1, F, 1}); expect("proj.bias", {1});
-    expect("cond.weight", {Ci, G, 1}); expect("cond.bias", {Ci});                  // :22
+    expect(e, "conv1.weight", {F, Ci, K}); expect(e, "conv1.bias", {F});                // duration_predictor.py:16-21
+    expect(e, "norm1.weight", {F}); expect(e, "norm1.bias", {F});
+    expect(e, "conv2.weight", {F, F, K}); expect(e, "conv2.bias", {F});
+    expect(e, "norm2.weight", {F}); expect(e, "norm2.bias", {F});
+    expect(e, "proj.weight", {1, F, 1}); expect(e, "proj.bias", {1});
+    expect(e, "cond.weight", {Ci, G, 1}); expect(e, "cond.bias", {Ci});                  // :22
 }
 
 void duration_destroy(st_engine* e) { delete e->dur; e->dur = nullptr; }
@@ -41,11 +40,8 @@ int st_create_duration_predictor(const st_duration_predictor_config* cfg, int de
     // limits of this native build
     if (cfg->filter_channels % 128 != 0) return bad("filter_channels must be a multiple of 128", ST_ERR_UNSUPPORTED);
     if (cfg->kernel_size != 1 && cfg->kernel_size != 3 && cfg->kernel_size != 5) return bad("native convolutions are built for kernel_size 1, 3 or 5", ST_ERR_UNSUPPORTED);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return bad("no such HIP device", ST_ERR_HIP);
-    if (hipSetDevice(device) != hipSuccess) return bad("hipSetDevice failed", ST_ERR_HIP);
-    st_engine* e = new st_engine();
-    e->device = device; e->kind = 4;
+    st_engine* e = nullptr;
+    if (int rc = new_handle(KIND_DURATION_PREDICTOR, device, &e)) return rc;
     e->dur = new DurState();
     e->dur->cfg = *cfg;
     duration_build_params(e, *cfg);
@@ -55,11 +51,10 @@ int st_create_duration_predictor(const st_duration_predictor_config* cfg, int de
 
 int st_duration_predictor_forward(st_engine* e, const float* x, const float* x_mask, const float* g, float* logw_out,
                                   int B, int Tx, void* stream) {
-    if (!e) return ST_ERR_INVALID;
-    if (e->kind != 4) return e->fail(ST_ERR_STATE, "this handle is not a duration predictor (st_create_duration_predictor)");
-    if (!e->finalized) return e->fail(ST_ERR_STATE, "st_finalize() has not been called after loading parameters");
+    int rc = check_handle(e, KIND_DURATION_PREDICTOR); if (rc) return rc;
+    if ((rc = check_finalized(e))) return rc;
     if (!x || !x_mask || !g || !logw_out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
-    if (B < 1 || Tx < 1) return e->fail(ST_ERR_INVALID, "B and Tx must be >= 1");
+    if ((rc = check_sizes(e, B, Tx, "Tx"))) return rc;
     const st_duration_predictor_config& c = e->dur->cfg;
     const int Ci = c.in_channels, F = c.filter_channels, K = c.kernel_size, G = c.gin_channels;
     const int64_t R = (int64_t)B * Tx;
@@ -70,7 +65,7 @@ int st_duration_predictor_forward(st_engine* e, const float* x, const float* x_m
     size_t off = 0;
     auto want = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
     const size_t o_gb = want((size_t)B * Ci * 4), o_h1 = want((size_t)R * F * 4), o_h2 = want((size_t)R * F * 4);
-    int rc = ensure_ws(e, off); if (rc) return rc;
+    if ((rc = ensure_ws(e, off))) return rc;
     float* gb = (float*)(e->ws + o_gb); float* h1 = (float*)(e->ws + o_h1); float* h2 = (float*)(e->ws + o_h2);
 
     {   // cond(g) (:26): a k = 1 conv over a one-frame input -> per-item bias of in_channels
@@ -100,7 +95,7 @@ int st_duration_predictor_forward(st_engine* e, const float* x, const float* x_m
 
 }  // extern "C"
 
-// ---- training (kind 4): the forward above with its activations kept and dropout after norm1 / norm2 (salts 72, 73), and the
+// ---- training: the forward above with its activations kept and dropout after norm1 / norm2 (salts 72, 73), and the
 // backward.  x and g get no gradient (the reference detaches them, :25-26); cond's gradient comes from conv1's data gradient.
 namespace {
 
@@ -126,23 +121,20 @@ extern "C" {
 
 int st_duration_predictor_train_forward(st_engine* e, const float* x, const float* x_mask, const float* g, float* logw_out,
                                         int B, int Tx, float p_dropout, uint64_t seed, void* stream) {
-    if (!e) return ST_ERR_INVALID;
-    if (e->kind != 4) return e->fail(ST_ERR_STATE, "this handle is not a duration predictor (st_create_duration_predictor)");
-    if (!e->finalized) return e->fail(ST_ERR_STATE, "st_finalize() has not been called after loading parameters");
+    int rc = check_handle(e, KIND_DURATION_PREDICTOR); if (rc) return rc;
+    if ((rc = check_finalized(e))) return rc;
     if (!x || !x_mask || !g || !logw_out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
-    if (B < 1 || Tx < 1) return e->fail(ST_ERR_INVALID, "B and Tx must be >= 1");
-    if (!(p_dropout >= 0.0f && p_dropout < 1.0f)) return e->fail(ST_ERR_INVALID, "p_dropout must be in [0, 1)");
+    if ((rc = check_sizes(e, B, Tx, "Tx"))) return rc;
+    if ((rc = check_dropout(e, p_dropout))) return rc;
     const st_duration_predictor_config& c = e->dur->cfg;
     const int Ci = c.in_channels, F = c.filter_channels, K = c.kernel_size, Gc = c.gin_channels;
     const int64_t R = (int64_t)B * Tx;
     if (R * F >= ((int64_t)1 << 31) || R * Ci >= ((int64_t)1 << 31)) return e->fail(ST_ERR_INVALID, "B*Tx too large");
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    if (!e->sdt) e->sdt = new SdTrain();
-    SdTrain* st = e->sdt;
-    st->have = false;
+    SdTrain* st = sd_train_begin(e);
     const DurActs A = dur_acts(c, B, Tx);
-    int rc = sd_train_grow(e, &st->act, &st->act_cap, A.end * 4); if (rc) return rc;
+    if ((rc = sd_train_grow(e, &st->act, &st->act_cap, A.end * 4))) return rc;
     float* act = (float*)st->act;
     auto at = [&](size_t o) { return act + o; };
     HIPCHK(e, hipMemcpyAsync(at(A.x), x, (size_t)R * Ci * 4, hipMemcpyDeviceToDevice, s));
@@ -172,21 +164,16 @@ int st_duration_predictor_train_forward(st_engine* e, const float* x, const floa
         a.out = logw_out; a.Cout = 1; a.B = B; a.T = Tx; a.taps = 1;
         HIPCHK(e, launch_sd_conv(a, s));
     }
-    st->serial += 1; st->have = true; st->B = B; st->T = Tx; st->p = p_dropout; st->seed = seed; st->masked = true;
+    sd_train_commit(st, B, Tx, p_dropout, seed, true);
     return ST_OK;
 }
 
 int st_duration_predictor_train_backward(st_engine* e, int64_t serial, int B, int Tx, const float* grad_logw, float* grad_flat,
                                          void* stream) {
-    if (!e) return ST_ERR_INVALID;
-    if (e->kind != 4) return e->fail(ST_ERR_STATE, "this handle is not a duration predictor (st_create_duration_predictor)");
+    int rc = check_handle(e, KIND_DURATION_PREDICTOR); if (rc) return rc;
     if (!grad_logw || !grad_flat) return e->fail(ST_ERR_INVALID, "null tensor pointer");
+    if ((rc = sd_train_check(e, "st_duration_predictor_train", "Tx", serial, B, Tx))) return rc;
     SdTrain* st = e->sdt;
-    if (!st || !st->have) return e->fail(ST_ERR_STATE, "st_duration_predictor_train_backward needs a preceding st_duration_predictor_train_forward");
-    if (serial != st->serial || B != st->B || Tx != st->T)
-        return e->fail(ST_ERR_STATE, "st_duration_predictor_train_backward: the engine holds the activations of forward #" + std::to_string(st->serial) +
-                       " (B=" + std::to_string(st->B) + ", Tx=" + std::to_string(st->T) + "), not of #" + std::to_string(serial) +
-                       " (B=" + std::to_string(B) + ", Tx=" + std::to_string(Tx) + ")");
     const st_duration_predictor_config& c = e->dur->cfg;
     const int Ci = c.in_channels, F = c.filter_channels, K = c.kernel_size, Gc = c.gin_channels;
     const int64_t R = (int64_t)B * Tx;
@@ -206,7 +193,7 @@ int st_duration_predictor_train_backward(st_engine* e, int64_t serial, int B, in
     size_t off = 0;
     auto want = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
     const size_t o_dy = want(R), o_a = want(R * F), o_b = want(R * F), o_dx = want(R * Ci), o_dc = want((size_t)B * Ci), o_ws = want(ws);
-    int rc = sd_train_grow(e, &st->scr, &st->scr_cap, off * 4); if (rc) return rc;
+    if ((rc = sd_train_grow(e, &st->scr, &st->scr_cap, off * 4))) return rc;
     float* scr = (float*)st->scr;
     float* dY = scr + o_dy; float* Pa = scr + o_a; float* Pb = scr + o_b; float* dX = scr + o_dx; float* dC = scr + o_dc; float* wsp = scr + o_ws;
 

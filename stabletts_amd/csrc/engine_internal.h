@@ -37,13 +37,28 @@ struct ProfEvent { int cls; hipEvent_t a, b; double flops; };
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// What a handle is (st_engine::kind), in the order the creators were added.  kKinds names each for the message of an entry
+// point that is handed another kind's handle (check_handle).
+enum Kind { KIND_DECODER = 0, KIND_TEXT_ENCODER, KIND_VOCODER, KIND_STYLE_ENCODER, KIND_DURATION_PREDICTOR, KIND_MEL_EXTRACTOR, KIND_COUNT };
+struct KindName { const char* what; const char* creator; };
+constexpr KindName kKinds[KIND_COUNT] = {
+    {"CFM decoder", "st_create"},                                     // the estimator of the CFM decoder
+    {"text encoder", "st_create_text_encoder"},                       // TextEncoder: the decoder's DiT block kernels
+    {"vocoder", "st_create_vocoder"},                                 // Vocos
+    {"style encoder", "st_create_style_encoder"},                     // MelStyleEncoder
+    {"duration predictor", "st_create_duration_predictor"},           // DurationPredictor
+    {"mel extractor", "st_create_mel_extractor"},                     // the feature front end (utils/audio.py)
+};
+// The style encoder and the duration predictor run fp32 kernels that read the loaded parameters in place: nothing to pack.
+constexpr bool reads_params_in_place(Kind k) { return k == KIND_STYLE_ENCODER || k == KIND_DURATION_PREDICTOR; }
+
 struct TrainState;     // engine_train.cpp
 struct VocosState;     // engine_vocos.cpp
 struct StyleState;     // engine_style.cpp
 struct DurState;       // engine_duration.cpp
 struct MelState;       // engine_audio.cpp
 
-// Training state of a style-encoder / duration-predictor handle (kinds 3 / 4): the activations of ONE grad-enabled forward
+// Training state of a style-encoder / duration-predictor handle: the activations of ONE grad-enabled forward
 // (serial, B, T; inputs copied in) and the backward's scratch, in two device buffers that grow on demand and are then reused.
 struct SdTrain {
     char* act = nullptr; size_t act_cap = 0;
@@ -56,6 +71,11 @@ struct SdTrain {
 };
 int sd_train_grow(st_engine* e, char** buf, size_t* cap, size_t bytes);     // engine_style.cpp
 void sd_train_destroy(st_engine* e);
+// The protocol around a training forward / backward of those two kinds.  `entry`: "st_<kind>_train", the common stem of the two entry
+// points' names; `t_name`: what they call the length ("T" / "Tx").
+SdTrain* sd_train_begin(st_engine* e);                                                          // the forward's state, nothing held
+void sd_train_commit(SdTrain* st, int B, int T, float p_dropout, unsigned long long seed, bool masked);      // forward #serial + 1 is held
+int sd_train_check(st_engine* e, const char* entry, const char* t_name, int64_t serial, int B, int T);         // the backward of that forward?
 
 }  // namespace sthost
 
@@ -68,13 +88,11 @@ struct st_engine {
     int device = 0;
     int dt = st::DT_BF16;
     int M = 0, Mp = 0, C = 0, F = 0, H = 0, L = 0, K = 0, G = 0;
-    int kind = 0;                       // 0: CFM decoder estimator, 1: TextEncoder (same DiT block kernels), 2: Vocos vocoder,
-                                        // 3: MelStyleEncoder, 4: DurationPredictor (fp32 kernels reading the loaded parameters in place),
-                                        // 5: mel extractor (the feature front end, utils/audio.py)
+    sthost::Kind kind = sthost::KIND_DECODER;
     int n_vocab = 0;
     // parameter-name prefix of DiT block i: estimator.py:13,79 "blocks.i.block." / text_encoder.py:25 "encoder.i."
     std::string blk(int i) const {
-        return kind == 0 ? "blocks." + std::to_string(i) + ".block." : "encoder." + std::to_string(i) + ".";
+        return kind == sthost::KIND_DECODER ? "blocks." + std::to_string(i) + ".block." : "encoder." + std::to_string(i) + ".";
     }
     std::map<std::string, sthost::Param> params;
     bool finalized = false;
@@ -166,11 +184,11 @@ struct st_engine {
 
     // training (engine_train.cpp): transposed dgrad weights, saved activations, gradient buffers
     sthost::TrainState* train = nullptr;
-    sthost::VocosState* voc = nullptr;  // kind == 2 (engine_vocos.cpp)
-    sthost::StyleState* sty = nullptr;  // kind == 3 (engine_style.cpp)
-    sthost::SdTrain* sdt = nullptr;     // kinds 3 / 4 after their first training forward
-    sthost::DurState* dur = nullptr;    // kind == 4 (engine_duration.cpp)
-    sthost::MelState* mel = nullptr;    // kind == 5 (engine_audio.cpp)
+    sthost::VocosState* voc = nullptr;  // KIND_VOCODER (engine_vocos.cpp)
+    sthost::StyleState* sty = nullptr;  // KIND_STYLE_ENCODER (engine_style.cpp)
+    sthost::SdTrain* sdt = nullptr;     // style encoder / duration predictor after their first training forward
+    sthost::DurState* dur = nullptr;    // KIND_DURATION_PREDICTOR (engine_duration.cpp)
+    sthost::MelState* mel = nullptr;    // KIND_MEL_EXTRACTOR (engine_audio.cpp)
 
     int fail(int code, const std::string& msg) { err = msg; return code; }
 };
@@ -198,8 +216,16 @@ int ensure_ws(st_engine* e, size_t bytes);
 // CFG, part count, entry point) the bytes would be re-interpreted under another type, so the used range is zeroed once, on `s`.
 int arena_fresh(st_engine* e, uint64_t sig, size_t used_bytes, hipStream_t s);
 int ensure_rope(st_engine* e, int T, hipStream_t s);
-int check_ready(st_engine* e, int B, int T);
+// Entry checks, each with ONE message.  check_handle: ST_ERR_INVALID for a null handle, ST_ERR_STATE for a handle of another kind.
+int check_handle(st_engine* e, Kind kind);
+int check_finalized(st_engine* e);
+int check_sizes(st_engine* e, int B, int T, const char* t_name = "T");      // B and T >= 1
+int check_dropout(st_engine* e, float p_dropout);
+int check_ready(st_engine* e, int B, int T);       // null handle, finalized, sizes, 32-bit row indexing (kind-independent: runs BEFORE check_handle)
 extern std::string g_create_error;
+// The end of every st_create*: validates `device`, makes it current and returns a new handle of `kind` (code + g_create_error otherwise).
+int new_handle(Kind kind, int device, st_engine** out);
+void expect(st_engine* e, const std::string& name, std::vector<int64_t> shape);      // one row of the parameter table
 int vocos_finalize(st_engine* e);
 int pack_all(st_engine* e, hipStream_t s);
 // recorder / replayer of a PackList: begin -> the pk_* calls (individual launch + record) -> end (upload); replay = one launch

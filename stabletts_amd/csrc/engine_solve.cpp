@@ -494,7 +494,7 @@ extern "C" int st_cfm_solve(st_engine* e, const float* mu, const float* mask, co
                             const float* fake_speaker, const float* fake_content,
                             float* out, int B, int T, void* stream) {
     int rc = check_ready(e, B, T); if (rc) return rc;
-    if (e->kind != 0) return e->fail(ST_ERR_STATE, "this handle is not a CFM decoder (st_create)");
+    if ((rc = check_handle(e, KIND_DECODER))) return rc;
     if (!mu || !mask || !z || !c || !out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if (n_steps < 1 || n_steps > 4096) return e->fail(ST_ERR_INVALID, "n_steps out of range");
     if (solver < ST_SOLVER_EULER || solver > ST_SOLVER_IMPLICIT_ADAMS)

@@ -17,17 +17,16 @@ struct StyleState {
 };
 
 static void style_build_params(st_engine* e, const st_style_encoder_config& c) {
-    auto expect = [&](const std::string& n, std::vector<int64_t> shape) { Param p; p.shape = std::move(shape); e->params[n] = p; };
     const int64_t I = c.n_mel_channels, Hd = c.style_hidden, O = c.style_vector_dim, K = c.style_kernel_size;
-    expect("spectral.0.weight", {Hd, I}); expect("spectral.0.bias", {Hd});             // reference_encoder.py:44-51
-    expect("spectral.3.weight", {Hd, Hd}); expect("spectral.3.bias", {Hd});
+    expect(e, "spectral.0.weight", {Hd, I}); expect(e, "spectral.0.bias", {Hd});             // reference_encoder.py:44-51
+    expect(e, "spectral.3.weight", {Hd, Hd}); expect(e, "spectral.3.bias", {Hd});
     for (int i = 0; i < 2; ++i) {                                                      // :53-56, Conv1dGLU :13
         const std::string p = "temporal." + std::to_string(i) + ".conv1.";
-        expect(p + "weight", {2 * Hd, Hd, K}); expect(p + "bias", {2 * Hd});
+        expect(e, p + "weight", {2 * Hd, Hd, K}); expect(e, p + "bias", {2 * Hd});
     }
-    expect("slf_attn.in_proj_weight", {3 * Hd, Hd}); expect("slf_attn.in_proj_bias", {3 * Hd});     // :58-63
-    expect("slf_attn.out_proj.weight", {Hd, Hd}); expect("slf_attn.out_proj.bias", {Hd});
-    expect("fc.weight", {O, Hd}); expect("fc.bias", {O});                              // :65
+    expect(e, "slf_attn.in_proj_weight", {3 * Hd, Hd}); expect(e, "slf_attn.in_proj_bias", {3 * Hd});     // :58-63
+    expect(e, "slf_attn.out_proj.weight", {Hd, Hd}); expect(e, "slf_attn.out_proj.bias", {Hd});
+    expect(e, "fc.weight", {O, Hd}); expect(e, "fc.bias", {O});                              // :65
 }
 
 void style_destroy(st_engine* e) { delete e->sty; e->sty = nullptr; }
@@ -47,6 +46,29 @@ void sd_train_destroy(st_engine* e) {
     delete e->sdt; e->sdt = nullptr;
 }
 
+SdTrain* sd_train_begin(st_engine* e) {
+    if (!e->sdt) e->sdt = new SdTrain();
+    e->sdt->have = false;
+    return e->sdt;
+}
+
+void sd_train_commit(SdTrain* st, int B, int T, float p_dropout, unsigned long long seed, bool masked) {
+    st->serial += 1; st->have = true; st->B = B; st->T = T; st->p = p_dropout; st->seed = seed; st->masked = masked;
+}
+
+int sd_train_check(st_engine* e, const char* entry, const char* t_name, int64_t serial, int B, int T) {
+    const SdTrain* st = e->sdt;
+    const std::string fn(entry);
+    if (!st || !st->have) return e->fail(ST_ERR_STATE, fn + "_backward needs a preceding " + fn + "_forward");
+    if (serial != st->serial || B != st->B || T != st->T) {
+        const std::string t = std::string(", ") + t_name + "=";
+        return e->fail(ST_ERR_STATE, fn + "_backward: the engine holds the activations of forward #" + std::to_string(st->serial) +
+                       " (B=" + std::to_string(st->B) + t + std::to_string(st->T) + "), not of #" + std::to_string(serial) +
+                       " (B=" + std::to_string(B) + t + std::to_string(T) + ")");
+    }
+    return ST_OK;
+}
+
 }  // namespace sthost
 
 extern "C" {
@@ -61,11 +83,8 @@ int st_create_style_encoder(const st_style_encoder_config* cfg, int device, st_e
     if (cfg->style_hidden / cfg->style_head != 64) return bad("native attention is built for head_dim == 64", ST_ERR_UNSUPPORTED);
     if (cfg->style_kernel_size != 1 && cfg->style_kernel_size != 3 && cfg->style_kernel_size != 5)
         return bad("native convolutions are built for style_kernel_size 1, 3 or 5", ST_ERR_UNSUPPORTED);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return bad("no such HIP device", ST_ERR_HIP);
-    if (hipSetDevice(device) != hipSuccess) return bad("hipSetDevice failed", ST_ERR_HIP);
-    st_engine* e = new st_engine();
-    e->device = device; e->kind = 3;
+    st_engine* e = nullptr;
+    if (int rc = new_handle(KIND_STYLE_ENCODER, device, &e)) return rc;
     e->sty = new StyleState();
     e->sty->cfg = *cfg;
     style_build_params(e, *cfg);
@@ -74,11 +93,10 @@ int st_create_style_encoder(const st_style_encoder_config* cfg, int device, st_e
 }
 
 int st_style_encoder_forward(st_engine* e, const float* mel, const float* mask, float* c_out, int B, int T, void* stream) {
-    if (!e) return ST_ERR_INVALID;
-    if (e->kind != 3) return e->fail(ST_ERR_STATE, "this handle is not a style encoder (st_create_style_encoder)");
-    if (!e->finalized) return e->fail(ST_ERR_STATE, "st_finalize() has not been called after loading parameters");
+    int rc = check_handle(e, KIND_STYLE_ENCODER); if (rc) return rc;
+    if ((rc = check_finalized(e))) return rc;
     if (!mel || !c_out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
-    if (B < 1 || T < 1) return e->fail(ST_ERR_INVALID, "B and T must be >= 1");
+    if ((rc = check_sizes(e, B, T))) return rc;
     const st_style_encoder_config& c = e->sty->cfg;
     const int I = c.n_mel_channels, Hd = c.style_hidden, O = c.style_vector_dim, K = c.style_kernel_size, NH = c.style_head;
     const int64_t R = (int64_t)B * T;
@@ -90,7 +108,7 @@ int st_style_encoder_forward(st_engine* e, const float* mel, const float* mask, 
     size_t off = 0;
     auto want = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
     const size_t o_h1 = want((size_t)R * Hd * 4), o_h2 = want((size_t)R * Hd * 4), o_u = want((size_t)R * 3 * Hd * 4), o_f = want((size_t)R * O * 4);
-    int rc = ensure_ws(e, off); if (rc) return rc;
+    if ((rc = ensure_ws(e, off))) return rc;
     float* h1 = (float*)(e->ws + o_h1); float* h2 = (float*)(e->ws + o_h2); float* u = (float*)(e->ws + o_u); float* f = (float*)(e->ws + o_f);
 
     auto conv = [&](const float* in, int cin, const std::string& w, const std::string& b, int cout, int taps, int epi, float* out) {
@@ -119,7 +137,7 @@ int st_style_encoder_forward(st_engine* e, const float* mel, const float* mask, 
 
 }  // extern "C"
 
-// ---- training (kind 3): the forward above with its activations kept, dropout at the five sites of the reference in train
+// ---- training: the forward above with its activations kept, dropout at the five sites of the reference in train
 // mode, and the backward.  Salts 64 .. 68 (include/stabletts_hip.h).
 namespace {
 
@@ -147,23 +165,20 @@ extern "C" {
 
 int st_style_encoder_train_forward(st_engine* e, const float* mel, const float* mask, float* c_out, int B, int T,
                                    float p_dropout, uint64_t seed, void* stream) {
-    if (!e) return ST_ERR_INVALID;
-    if (e->kind != 3) return e->fail(ST_ERR_STATE, "this handle is not a style encoder (st_create_style_encoder)");
-    if (!e->finalized) return e->fail(ST_ERR_STATE, "st_finalize() has not been called after loading parameters");
+    int rc = check_handle(e, KIND_STYLE_ENCODER); if (rc) return rc;
+    if ((rc = check_finalized(e))) return rc;
     if (!mel || !c_out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
-    if (B < 1 || T < 1) return e->fail(ST_ERR_INVALID, "B and T must be >= 1");
-    if (!(p_dropout >= 0.0f && p_dropout < 1.0f)) return e->fail(ST_ERR_INVALID, "p_dropout must be in [0, 1)");
+    if ((rc = check_sizes(e, B, T))) return rc;
+    if ((rc = check_dropout(e, p_dropout))) return rc;
     const st_style_encoder_config& c = e->sty->cfg;
     const int I = c.n_mel_channels, Hd = c.style_hidden, O = c.style_vector_dim, K = c.style_kernel_size, NH = c.style_head;
     const int64_t R = (int64_t)B * T;
     if (R * 3 * Hd >= ((int64_t)1 << 31) || R * O >= ((int64_t)1 << 31) || R * I >= ((int64_t)1 << 31)) return e->fail(ST_ERR_INVALID, "B*T too large");
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    if (!e->sdt) e->sdt = new SdTrain();
-    SdTrain* st = e->sdt;
-    st->have = false;
+    SdTrain* st = sd_train_begin(e);
     const StyleActs A = style_acts(c, B, T);
-    int rc = sd_train_grow(e, &st->act, &st->act_cap, A.end * 4); if (rc) return rc;
+    if ((rc = sd_train_grow(e, &st->act, &st->act_cap, A.end * 4))) return rc;
     float* act = (float*)st->act;
     auto at = [&](size_t o) { return act + o; };
     HIPCHK(e, hipMemcpyAsync(at(A.mel), mel, (size_t)R * I * 4, hipMemcpyDeviceToDevice, s));
@@ -196,20 +211,15 @@ int st_style_encoder_train_forward(st_engine* e, const float* mel, const float* 
     HIPCHK(e, conv(at(A.att), Hd, "slf_attn.out_proj.weight", "slf_attn.out_proj.bias", Hd, 1, at(A.ao)));
     HIPCHK(e, conv(at(A.ao), Hd, "fc.weight", "fc.bias", O, 1, at(A.f)));
     HIPCHK(e, launch_sd_mean_pool(at(A.f), kmask, c_out, B, O, T, s));
-    st->serial += 1; st->have = true; st->B = B; st->T = T; st->p = p_dropout; st->seed = seed; st->masked = mask != nullptr;
+    sd_train_commit(st, B, T, p_dropout, seed, mask != nullptr);
     return ST_OK;
 }
 
 int st_style_encoder_train_backward(st_engine* e, int64_t serial, int B, int T, const float* grad_c, float* grad_flat, void* stream) {
-    if (!e) return ST_ERR_INVALID;
-    if (e->kind != 3) return e->fail(ST_ERR_STATE, "this handle is not a style encoder (st_create_style_encoder)");
+    int rc = check_handle(e, KIND_STYLE_ENCODER); if (rc) return rc;
     if (!grad_c || !grad_flat) return e->fail(ST_ERR_INVALID, "null tensor pointer");
+    if ((rc = sd_train_check(e, "st_style_encoder_train", "T", serial, B, T))) return rc;
     SdTrain* st = e->sdt;
-    if (!st || !st->have) return e->fail(ST_ERR_STATE, "st_style_encoder_train_backward needs a preceding st_style_encoder_train_forward");
-    if (serial != st->serial || B != st->B || T != st->T)
-        return e->fail(ST_ERR_STATE, "st_style_encoder_train_backward: the engine holds the activations of forward #" + std::to_string(st->serial) +
-                       " (B=" + std::to_string(st->B) + ", T=" + std::to_string(st->T) + "), not of #" + std::to_string(serial) +
-                       " (B=" + std::to_string(B) + ", T=" + std::to_string(T) + ")");
     const st_style_encoder_config& c = e->sty->cfg;
     const int I = c.n_mel_channels, Hd = c.style_hidden, O = c.style_vector_dim, K = c.style_kernel_size, NH = c.style_head;
     const int64_t R = (int64_t)B * T;
@@ -233,7 +243,7 @@ int st_style_encoder_train_backward(st_engine* e, int64_t serial, int B, int T, 
     auto want = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
     const size_t o_dF = want(R * O), o_x = want(R * Hd), o_y = want(R * Hd), o_z = want(R * Hd), o_d3 = want(R * 3 * Hd),
                  o_ds = want(R * NH), o_ws = want(ws);
-    int rc = sd_train_grow(e, &st->scr, &st->scr_cap, off * 4); if (rc) return rc;
+    if ((rc = sd_train_grow(e, &st->scr, &st->scr_cap, off * 4))) return rc;
     float* scr = (float*)st->scr;
     float* dF = scr + o_dF; float* X = scr + o_x; float* Y = scr + o_y; float* Z = scr + o_z; float* D3 = scr + o_d3;
     float* dsum = scr + o_ds; float* wsp = scr + o_ws;

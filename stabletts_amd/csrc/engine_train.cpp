@@ -2,7 +2,7 @@
 // matching backward pass, both as launch sequences of hand-written gfx950 kernels.  Autograd counterpart of
 // models/estimator.py:103-138 (Decoder.forward) + models/diffusion_transformer.py:98-121 as exercised by
 // CFMDecoder.compute_loss (models/flow_matching.py:69-100) under DDP in train.py:78-81, and of TextEncoder.forward
-// (models/text_encoder.py:34-44, kind 1): the same blocks without FiLM or long skips, proj, and the embedding (emb_bwd.hip).
+// (models/text_encoder.py:34-44): the same blocks without FiLM or long skips, proj, and the embedding (emb_bwd.hip).
 //
 // Structure of the backward pass:
 //   * data gradients of every convolution run through the FORWARD implicit-GEMM kernel with transposed, tap-flipped
@@ -104,7 +104,7 @@ struct TrainState {
     bool use_side = true, side_prio = false;     // ST_TRAIN_SIDE=2: side streams at the device's lowest stream priority (0: no side streams)
     size_t partial_cap = 0, xt_cap = 0, dyt_cap = 0;
     size_t wg_max_frames = 0, wg_max_cout = 0, wg_max_prod = 0;   // layout_train's largest taps*Cin, Cout and product: wgrad() refuses more
-    // text encoder (kind 1): the forward's clamped token id per row (-1: padded), the embedding backward's scratch, and {1, 1}: the
+    // text encoder: the forward's clamped token id per row (-1: padded), the embedding backward's scratch, and {1, 1}: the
     // scale pair a caller's d x is written at (launch_add_rescaled's sc_b)
     int* ids = nullptr; void* emb_ws = nullptr; float* unit_sc = nullptr;
 };
@@ -154,7 +154,7 @@ void train_invalidate(st_engine* e) {
 
 // (re)packs the transposed weights after a parameter update; lazy: inference-only users never pay for it
 int train_prepare(st_engine* e, hipStream_t s) {
-    if (e->kind != 0 && e->kind != 1) return ST_OK;
+    if (e->kind != KIND_DECODER && e->kind != KIND_TEXT_ENCODER) return ST_OK;
     if (!e->train) {
         e->train = new TrainState();
         if (const char* v = getenv("ST_FUSE_SILU")) e->train->fuse_silu = atoi(v) != 0;
@@ -183,7 +183,7 @@ int train_prepare(st_engine* e, hipStream_t s) {
         return ST_OK;
     }
     pk_begin(e->pk_T);
-    if (e->kind == 1) {      // text encoder: proj is the only convolution outside the blocks
+    if (e->kind == KIND_TEXT_ENCODER) {      // text encoder: proj is the only convolution outside the blocks
         if ((rc = pack_T(e, ts, ts->finT, "proj.weight", M, C, 1, 0, C, C, Mp, s))) return rc;
     } else {
         if ((rc = pack_T(e, ts, ts->finT, "final_proj.weight", M, C, 1, 0, C, C, Mp, s))) return rc;
@@ -193,7 +193,7 @@ int train_prepare(st_engine* e, hipStream_t s) {
         if ((rc = pack_T(e, ts, ts->preT[1], "cond_proj.2.weight", F, F, K, 0, F, F, F, s))) return rc;
         if ((rc = pack_T(e, ts, ts->preT[2], "cond_proj.4.weight", C, F, K, 0, F, F, C, s))) return rc;
     }
-    const int n_lsc = e->kind == 0 ? L / 2 : 0;
+    const int n_lsc = e->kind == KIND_DECODER ? L / 2 : 0;
     ts->ffn1T.resize(L); ts->ffn2T.resize(L); ts->oprojT.resize(L); ts->qkvT.resize(L);
     ts->lscTa.resize(n_lsc); ts->lscTb.resize(n_lsc);
     for (int i = 0; i < L; ++i) {
@@ -274,8 +274,8 @@ int layout_train(st_engine* e, TrainState* ts, int B, int T) {
     struct Slot { void** dst; size_t off; };
     std::vector<Slot> slots;
     auto want = [&](void** dst, size_t bytes) { slots.push_back({dst, off}); off = align_up(off + bytes, 256); };
-    // dec: tensors of the decoder's own layers (in_proj, cond prenet, time MLP, FiLM, long skips); the text encoder (kind 1) has none
-    const bool dec = e->kind == 0;
+    // dec: tensors of the decoder's own layers (in_proj, cond prenet, time MLP, FiLM, long skips); the text encoder has none
+    const bool dec = e->kind == KIND_DECODER;
     auto want_dec = [&](void** dst, size_t bytes) { if (dec) want(dst, bytes); else *dst = nullptr; };
     ts->L.assign(L, LayerAct());
     want_dec(&ts->mu16, R * Mp * 2); want_dec(&ts->x16, R * Mp * 2); want_dec(&ts->x16lo, R * Mp * 2);
@@ -405,7 +405,7 @@ int fwd_blocks(st_engine* e, TrainState* ts, const float* m, float p_dropout, un
     for (int i = 0; i < L; ++i) {
         LayerAct& A = ts->L[i];
         const float* ada_i = ts->ada + (size_t)i * N * 6 * C;
-        if (e->kind == 0 && i >= L / 2) {   // long-skip merge (estimator.py:131-132)
+        if (e->kind == KIND_DECODER && i >= L / 2) {   // long-skip merge (estimator.py:131-132)
             const int j = i - L / 2;
             const int src = L - 1 - i;      // 2, 1, 0 -> x3[1], x3[0], h0
             ConvGemmArgs a = cargs(e, e->lsc[j], N, T, B);
@@ -415,7 +415,7 @@ int fwd_blocks(st_engine* e, TrainState* ts, const float* m, float p_dropout, un
         {   // FiLM * mask -> x1 (decoder) ; LN1 + modulate -> h1
             TrainLnArgs a; memset(&a, 0, sizeof(a));
             a.xin = xpre_of(ts, i, L); a.h16 = A.h1; a.h16lo = A.h1lo;
-            if (e->kind == 0) { a.xout = A.x1; a.film = ts->film + (size_t)i * N * 2 * C; a.film_stride = 2 * C; a.film_mod = N; }
+            if (e->kind == KIND_DECODER) { a.xout = A.x1; a.film = ts->film + (size_t)i * N * 2 * C; a.film_stride = 2 * C; a.film_mod = N; }
             // (text encoder: x1 = xpre * mask = xpre -- the embedding kernel and every block leave padded frames at zero -- and A.x1 IS xpre)
             a.ada = ada_i; a.ada_stride = 6 * C; a.shift_off = 0; a.scale_off = C;
             a.mask = m; a.mask_mod = B; a.mask_out = 0; a.T = T; a.rows = (int)R;
@@ -502,9 +502,9 @@ extern "C" {
 int st_train_forward(st_engine* e, const float* t, const float* x, const float* mu, const float* mask, const float* c,
                      float* out, int B, int T, float p_dropout, uint64_t seed, void* stream) {
     int rc = check_ready(e, B, T); if (rc) return rc;
-    if (e->kind != 0) return e->fail(ST_ERR_STATE, "this handle is not a CFM decoder (st_create)");
+    if ((rc = check_handle(e, KIND_DECODER))) return rc;
     if (!t || !x || !mu || !mask || !c || !out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
-    if (!(p_dropout >= 0.f && p_dropout < 1.f)) return e->fail(ST_ERR_INVALID, "p_dropout must be in [0, 1)");
+    if ((rc = check_dropout(e, p_dropout))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
     if ((rc = train_prepare(e, s))) return rc;
@@ -598,7 +598,7 @@ int st_train_forward(st_engine* e, const float* t, const float* x, const float* 
 }
 
 int64_t st_train_serial(const st_engine* e) {
-    if (e && (e->kind == 3 || e->kind == 4)) return e->sdt && e->sdt->have ? e->sdt->serial : 0;
+    if (e && reads_params_in_place(e->kind)) return e->sdt && e->sdt->have ? e->sdt->serial : 0;
     if (!e || !e->train || !e->train->have_fwd) return 0;
     return e->train->serial;
 }
@@ -608,9 +608,9 @@ int64_t st_train_serial(const st_engine* e) {
 int st_text_encoder_train_forward(st_engine* e, const int64_t* tokens, const int64_t* lengths, const float* c, float* x_out,
                                   float* mu_out, float* mask_out, int B, int T, float p_dropout, uint64_t seed, void* stream) {
     int rc = check_ready(e, B, T); if (rc) return rc;
-    if (e->kind != 1) return e->fail(ST_ERR_STATE, "this handle is not a text encoder (st_create_text_encoder)");
+    if ((rc = check_handle(e, KIND_TEXT_ENCODER))) return rc;
     if (!tokens || !lengths || !c || !x_out || !mu_out || !mask_out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
-    if (!(p_dropout >= 0.f && p_dropout < 1.f)) return e->fail(ST_ERR_INVALID, "p_dropout must be in [0, 1)");
+    if ((rc = check_dropout(e, p_dropout))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
     if ((rc = train_prepare(e, s))) return rc;
@@ -851,7 +851,7 @@ int bwd_block(st_engine* e, TrainState* ts, int i, hipStream_t s) {
         // long-skip gradient remembers the scale it was written at (skip_sc) and is converted when it is added.
         // (block i + 1 wrote dX last through add_rescaled -- which published the maximum -- when it lies in the first half, else through a GEMM;
         // in the text encoder through mask_bwd, which publishes it too)
-        const bool dec = e->kind == 0;
+        const bool dec = e->kind == KIND_DECODER;
         if (i < L - 1 && (rc = recentre(e, ts, d, !dec || i + 1 < L / 2, s))) return rc;
         if (cap) capture(e, "g.scale_" + std::to_string(i), ts->gsc, 2, false, s);      // the scale block i's captured tensors carry
         RedSites sites; memset(&sites, 0, sizeof(sites));      // the block's per-(item, channel) sums: ONE reduce launch at its end
@@ -982,7 +982,7 @@ int bwd_block(st_engine* e, TrainState* ts, int i, hipStream_t s) {
             HIPCHK(e, launch_linear_bwd_w(ts->cvec, ts->dada_pre, N, e->G, C, 0, g0w, g0b, 0, s));
             HIPCHK(e, launch_linear_bwd_in(ts->cvec, ts->dada_pre, P(e, p0 + "weight"), N, e->G, C, 0, ts->dcvec, acc, s));
         }
-        if (e->kind != 0) return ST_OK;      // (the text encoder's blocks have no FiLM)
+        if (e->kind != KIND_DECODER) return ST_OK;      // (the text encoder's blocks have no FiLM)
         const std::string pf = "blocks." + std::to_string(i) + ".time_fusion.film.";
         gw = G(ts, pf + "weight"); gb = G(ts, pf + "bias");
         const float* dfo = ts->dfilm + (size_t)i * N * 2 * C;
@@ -1004,7 +1004,7 @@ int bwd_linears(st_engine* e, TrainState* ts, int lo, int hi, int acc, hipStream
             const std::string pa = e->blk(i) + "adaLN_modulation.2.";
             ja.in[ja.n] = ts->cvec; ja.dout[ja.n] = ts->dada + (size_t)i * N * 6 * C; ja.W[ja.n] = P(e, pa + "weight");
             ja.dW[ja.n] = G(ts, pa + "weight"); ja.db[ja.n] = G(ts, pa + "bias"); ja.n += 1;
-            if (e->kind != 0) continue;      // (the text encoder's blocks have no FiLM)
+            if (e->kind != KIND_DECODER) continue;      // (the text encoder's blocks have no FiLM)
             const std::string pf = "blocks." + std::to_string(i) + ".time_fusion.film.";
             jf.in[jf.n] = ts->tau; jf.dout[jf.n] = ts->dfilm + (size_t)i * N * 2 * C; jf.W[jf.n] = P(e, pf + "weight");
             jf.dW[jf.n] = G(ts, pf + "weight"); jf.db[jf.n] = G(ts, pf + "bias"); jf.n += 1;
@@ -1081,9 +1081,9 @@ int bwd_tail(st_engine* e, TrainState* ts, float* grad_x, float* grad_mu, float*
     return ST_OK;
 }
 
-int bwd_check(st_engine* e, int kind, int64_t serial, int B_, int T_, const char* who) {
+int bwd_check(st_engine* e, Kind kind, int64_t serial, int B_, int T_, const char* who) {
     if (e->kind != kind || !e->train || !e->train->have_fwd)
-        return e->fail(ST_ERR_STATE, std::string(who) + (kind == 0 ? " needs a preceding st_train_forward" : " needs a preceding st_text_encoder_train_forward") +
+        return e->fail(ST_ERR_STATE, std::string(who) + (kind == KIND_DECODER ? " needs a preceding st_train_forward" : " needs a preceding st_text_encoder_train_forward") +
                        " (none held: never run, or invalidated by a parameter update)");
     if (serial != e->train->serial || B_ != e->train->B || T_ != e->train->T)
         return e->fail(ST_ERR_STATE, std::string(who) + ": the engine holds the activations of forward #" + std::to_string(e->train->serial) +
@@ -1092,7 +1092,7 @@ int bwd_check(st_engine* e, int kind, int64_t serial, int B_, int T_, const char
     return ST_OK;
 }
 
-// ---- text encoder (kind 1): d mu_x through proj and / or d x straight into the last block's output, the L blocks, d emb.weight
+// ---- text encoder: d mu_x through proj and / or d x straight into the last block's output, the L blocks, d emb.weight
 int bwd_head_text(st_engine* e, TrainState* ts, const float* grad_x, const float* grad_mu, hipStream_t s) {
     const BwdDims d = bwd_dims(e, ts);
     const int C = d.C, M = d.M, B = d.B, T = d.T;
@@ -1160,7 +1160,7 @@ extern "C" {
 int st_train_backward(st_engine* e, int64_t serial, int B_, int T_, const float* grad_out, float* grad_x, float* grad_mu,
                       float* grad_c, void* stream) {
     if (!e) return ST_ERR_INVALID;
-    int rc = bwd_check(e, 0, serial, B_, T_, "st_train_backward"); if (rc) return rc;
+    int rc = bwd_check(e, KIND_DECODER, serial, B_, T_, "st_train_backward"); if (rc) return rc;
     if (!grad_out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     HIPCHK(e, hipSetDevice(e->device));
     TrainState* ts = e->train;
@@ -1174,7 +1174,7 @@ int st_train_backward(st_engine* e, int64_t serial, int B_, int T_, const float*
 int st_train_backward_part(st_engine* e, int64_t serial, int B_, int T_, int part, const float* grad_out, float* grad_flat,
                            int64_t grad_numel, float* grad_x, float* grad_mu, float* grad_c, void* stream) {
     if (!e) return ST_ERR_INVALID;
-    int rc = bwd_check(e, 0, serial, B_, T_, "st_train_backward_part"); if (rc) return rc;
+    int rc = bwd_check(e, KIND_DECODER, serial, B_, T_, "st_train_backward_part"); if (rc) return rc;
     TrainState* ts = e->train;
     if (part < 0 || part > 2) return e->fail(ST_ERR_INVALID, "st_train_backward_part: part must be 0, 1 or 2");
     if (part == 0) {
@@ -1197,7 +1197,7 @@ int st_train_backward_part(st_engine* e, int64_t serial, int B_, int T_, int par
 int st_text_encoder_train_backward(st_engine* e, int64_t serial, int B_, int T_, const float* grad_x, const float* grad_mu,
                                    float* grad_flat, float* grad_c, void* stream) {
     if (!e) return ST_ERR_INVALID;
-    int rc = bwd_check(e, 1, serial, B_, T_, "st_text_encoder_train_backward"); if (rc) return rc;
+    int rc = bwd_check(e, KIND_TEXT_ENCODER, serial, B_, T_, "st_text_encoder_train_backward"); if (rc) return rc;
     if (!grad_x && !grad_mu) return e->fail(ST_ERR_INVALID, "st_text_encoder_train_backward: grad_x and grad_mu are both null");
     HIPCHK(e, hipSetDevice(e->device));
     TrainState* ts = e->train;
@@ -1209,10 +1209,10 @@ int st_text_encoder_train_backward(st_engine* e, int64_t serial, int B_, int T_,
 }
 
 int st_train_param_part(const st_engine* e, const char* name) {
-    if (!e || !name || (e->kind != 0 && e->kind != 1)) return ST_ERR_INVALID;
+    if (!e || !name || (e->kind != KIND_DECODER && e->kind != KIND_TEXT_ENCODER)) return ST_ERR_INVALID;
     const std::string n(name);
     if (!e->params.count(n)) return ST_ERR_INVALID;
-    if (e->kind == 1) return 0;      // the text encoder's backward is one part
+    if (e->kind == KIND_TEXT_ENCODER) return 0;      // the text encoder's backward is one part
     if (n.rfind("blocks.", 0) == 0) return atoi(n.c_str() + 7) >= e->L / 2 ? 0 : 1;
     if (n.rfind("final_proj.", 0) == 0 || n.rfind("lsc_layers.", 0) == 0) return 0;
     return 2;

@@ -24,21 +24,20 @@ struct VocosState {
 static std::string vblk(int i) { return "backbone.convnext." + std::to_string(i) + "."; }
 
 void vocos_build_params(st_engine* e, const st_vocos_config& c) {
-    auto expect = [&](const std::string& n, std::vector<int64_t> shape) { Param p; p.shape = std::move(shape); e->params[n] = p; };
     const int64_t C = c.dim, F = c.intermediate_dim, M = c.input_channels;
-    expect("backbone.embed.weight", {C, M, 7}); expect("backbone.embed.bias", {C});                 // backbone.py:28
-    expect("backbone.norm.weight", {C}); expect("backbone.norm.bias", {C});                        // :29
+    expect(e, "backbone.embed.weight", {C, M, 7}); expect(e, "backbone.embed.bias", {C});                 // backbone.py:28
+    expect(e, "backbone.norm.weight", {C}); expect(e, "backbone.norm.bias", {C});                        // :29
     for (int i = 0; i < c.num_layers; ++i) {                                                       // module.py:22-31
         const std::string p = vblk(i);
-        expect(p + "dwconv.weight", {C, 1, 7}); expect(p + "dwconv.bias", {C});
-        expect(p + "norm.weight", {C}); expect(p + "norm.bias", {C});
-        expect(p + "pwconv1.weight", {F, C}); expect(p + "pwconv1.bias", {F});
-        expect(p + "pwconv2.weight", {C, F}); expect(p + "pwconv2.bias", {C});
-        expect(p + "gamma", {C});
+        expect(e, p + "dwconv.weight", {C, 1, 7}); expect(e, p + "dwconv.bias", {C});
+        expect(e, p + "norm.weight", {C}); expect(e, p + "norm.bias", {C});
+        expect(e, p + "pwconv1.weight", {F, C}); expect(e, p + "pwconv1.bias", {F});
+        expect(e, p + "pwconv2.weight", {C, F}); expect(e, p + "pwconv2.bias", {C});
+        expect(e, p + "gamma", {C});
     }
-    expect("backbone.final_layer_norm.weight", {C}); expect("backbone.final_layer_norm.bias", {C});   // backbone.py:41
-    expect("head.out.weight", {c.n_fft + 2, C}); expect("head.out.bias", {c.n_fft + 2});            // head.py:88-89
-    expect("head.istft.window", {c.n_fft});                                                         // head.py:27-28
+    expect(e, "backbone.final_layer_norm.weight", {C}); expect(e, "backbone.final_layer_norm.bias", {C});   // backbone.py:41
+    expect(e, "head.out.weight", {c.n_fft + 2, C}); expect(e, "head.out.bias", {c.n_fft + 2});            // head.py:88-89
+    expect(e, "head.istft.window", {c.n_fft});                                                         // head.py:27-28
 }
 
 // st_finalize of a vocoder handle: 16-bit GEMM weights.  Linear weights (out, in) are k = 1 convolutions; the k = 7
@@ -117,11 +116,8 @@ int st_create_vocoder(const st_vocos_config* cfg, int device, st_engine** out) {
     if (cfg->n_fft != kVocNfft || cfg->hop_length != kVocHop) return bad("native ISTFT is built for n_fft == 2048, hop_length == 512", ST_ERR_UNSUPPORTED);
     if (cfg->input_channels % 64 != 0 || cfg->input_channels > 192) return bad("input_channels must be 64, 128 or 192", ST_ERR_UNSUPPORTED);
     if (cfg->intermediate_dim % 256 != 0) return bad("intermediate_dim must be a multiple of 256", ST_ERR_UNSUPPORTED);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return bad("no such HIP device", ST_ERR_HIP);
-    if (hipSetDevice(device) != hipSuccess) return bad("hipSetDevice failed", ST_ERR_HIP);
-    st_engine* e = new st_engine();
-    e->device = device; e->kind = 2;
+    st_engine* e = nullptr;
+    if (int rc = new_handle(KIND_VOCODER, device, &e)) return rc;
     e->dt = cfg->operand_dtype == ST_OPERAND_BF16 ? DT_BF16 : DT_F16;
     e->voc = new VocosState();
     e->voc->cfg = *cfg;
@@ -204,11 +200,10 @@ static int vocos_forward_chunk(st_engine* e, const float* mel, float* audio, int
 }
 
 int st_vocos_forward(st_engine* e, const float* mel, float* audio, int B, int T, void* stream) {
-    if (!e) return ST_ERR_INVALID;
-    if (e->kind != 2) return e->fail(ST_ERR_STATE, "this handle is not a vocoder (st_create_vocoder)");
-    if (!e->finalized) return e->fail(ST_ERR_STATE, "st_finalize() has not been called after loading parameters");
+    int rc = check_handle(e, KIND_VOCODER); if (rc) return rc;
+    if ((rc = check_finalized(e))) return rc;
     if (!mel || !audio) return e->fail(ST_ERR_INVALID, "null tensor pointer");
-    if (B < 1 || T < 1) return e->fail(ST_ERR_INVALID, "B and T must be >= 1");
+    if ((rc = check_sizes(e, B, T))) return rc;
     const st_vocos_config& c = e->voc->cfg;
     // rows per chunk: 32-bit GEMM operand offsets (widest operand row: the im2col rows, C or F) and head output indices
     const int64_t widest = std::max({7 * (int64_t)c.input_channels, (int64_t)c.dim, (int64_t)c.intermediate_dim, (int64_t)kVocHeadPlane});
@@ -222,7 +217,7 @@ int st_vocos_forward(st_engine* e, const float* mel, float* audio, int B, int T,
     hipStream_t s = (hipStream_t)stream;
     const size_t mel_item = (size_t)c.input_channels * T, audio_item = (size_t)T * c.hop_length;
     for (int b0 = 0; b0 < B; b0 += chunk) {
-        const int rc = vocos_forward_chunk(e, mel + b0 * mel_item, audio + b0 * audio_item, std::min(chunk, B - b0), T, s);
+        rc = vocos_forward_chunk(e, mel + b0 * mel_item, audio + b0 * audio_item, std::min(chunk, B - b0), T, s);
         if (rc) return rc;
     }
     return ST_OK;

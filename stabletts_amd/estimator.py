@@ -11,48 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-
-
-def _param_key(module):
-    """(storage identity, version counters) of the parameters.  The first changes when a tensor moves (``.to()``,
-    ``.half()``, re-assignment), the second whenever autograd-visible code rewrites a weight in place (optimizer step,
-    ``load_state_dict``).  Inference tensors (a module built or moved under torch.inference_mode) carry no version
-    counter; they key on the address alone and need sync_weights() after an in-place update."""
-    ptrs, vers = [], []
-    for p in module.parameters():
-        try:
-            ver = p._version
-        except RuntimeError:
-            ver = -1
-        ptrs.append((p.data_ptr(), p.dtype, p.is_contiguous()))
-        vers.append(ver)
-    return tuple(ptrs), tuple(vers)
-
-
-def sync_engine_params(module, dev):
-    """Brings ``module._engine``'s view of the parameters up to date (shared by the decoder's and the text encoder's engine()).
-    A change of storage (first use, ``.to()``, dtype change) binds the fp32 tensors in place (st_bind_param, or fp32 staging
-    copies for a non-fp32 module) and packs the 16-bit copies (st_finalize); an in-place update (optimizer step) only re-packs,
-    as kernels on the current stream (st_repack).  Uses / sets ``_engine_key``, ``_engine_vers``, ``_staging``."""
-    key, vers = module._param_key()
-    if key != module._engine_key:
-        with torch.no_grad():
-            named = list(module.named_parameters())
-            if all(p.dtype == torch.float32 and p.is_contiguous() for _, p in named):
-                module._staging = None
-                bound = [(n, p.detach()) for n, p in named]
-            else:       # e.g. a .half() module: the engine reads fp32 staging copies
-                module._staging = [p.detach().to(dtype=torch.float32).contiguous() for _, p in named]
-                bound = [(n, s) for (n, _), s in zip(named, module._staging)]
-            module._engine.bind_parameters(bound)        # st_finalize synchronises the device: pending writes have landed
-        module._engine_key, module._engine_vers = key, vers
-    elif vers != module._engine_vers:
-        with torch.no_grad(), torch.cuda.device(dev):
-            if module._staging is not None:
-                for s, p in zip(module._staging, module.parameters()):
-                    s.copy_(p)
-            module._engine.repack(torch.cuda.current_stream(dev).cuda_stream)
-        module._engine_vers = vers
+from ._native_module import NativeModule
 
 
 class _ParamsOnly(nn.Module):
@@ -116,14 +75,20 @@ class TimestepEmbedding(_ParamsOnly):
                                    nn.Linear(filter_channels, out_channels))
 
 
-class Decoder(nn.Module):
+class Decoder(NativeModule):
     """Same constructor as the reference Decoder (models/estimator.py:66); forward is native.
 
     forward(t, x, mask, mu, c) -> (B, out_channels, T): one vector-field evaluation
     (models/estimator.py:103-138).  Under torch.no_grad()/inference_mode it is the plain native launch sequence;
     when gradients are required it goes through stabletts_amd/autograd.py (native forward that keeps the
     activations + native backward), so DDP / AdamW see ordinary parameter gradients.
+
+    engine(): the engine READS the fp32 parameters where torch keeps them (st_bind_param: no copy); what it owns are the
+    packed 16-bit MFMA operand copies.  After an in-place update (every optimizer step of a training loop) those
+    are re-packed by kernels on the current stream (st_repack): no allocation, no host copy, no synchronisation.
+    Only a change of storage (first use, ``.to()``, dtype change) takes the slow path (bind + st_finalize).
     """
+    _what = "estimator"
 
     def __init__(self, noise_channels, cond_channels, hidden_channels, out_channels, filter_channels,
                  dropout=0.1, n_layers=1, n_heads=4, kernel_size=3, gin_channels=0, use_lsc=True,
@@ -163,10 +128,6 @@ class Decoder(nn.Module):
         self.lsc_layers = nn.ModuleList([nn.Conv1d(2 * hidden_channels, hidden_channels, kernel_size,
                                                    padding=kernel_size // 2) for _ in range(self.n_lsc_layers)])
         self.initialize_weights()
-        self._engine = None
-        self._engine_key = None        # storage identity of the parameters the engine is bound to
-        self._engine_vers = None       # their version counters at the last (re)pack
-        self._staging = None           # fp32 copies the engine reads when the parameters themselves are not fp32
 
     def initialize_weights(self):
         """adaLN-Zero (models/estimator.py:98-101)."""
@@ -174,23 +135,7 @@ class Decoder(nn.Module):
             nn.init.constant_(block.block.adaLN_modulation[-1].weight, 0)
             nn.init.constant_(block.block.adaLN_modulation[-1].bias, 0)
 
-    def __getstate__(self):
-        st = self.__dict__.copy()      # the ctypes engine handle is per-process, never copied/pickled
-        st["_engine"] = None
-        st["_engine_key"] = st["_engine_vers"] = st["_staging"] = None
-        return st
-
-    # ------------------------------------------------------------------ native engine plumbing
-    def _param_key(self):
-        return _param_key(self)
-
-    def sync_weights(self):
-        """Force the engine to re-pack its 16-bit weight copies at the next call.  Needed only after writes that bypass
-        autograd's version counter (``p.data.copy_(ema)``, ``m.weight.data.normal_()``, as some EMA / weight-swap
-        utilities do); in-place ops on the parameters themselves, optimizer steps, ``load_state_dict`` and
-        ``.to()`` are detected automatically."""
-        self._engine_vers = None
-
+    # ------------------------------------------------------------------ native engine plumbing (NativeModule)
     def release_engine(self):
         """Destroy the native engine (device arena, packed weights, streams); the next call builds a fresh one.  For a process that is
         done with this module for a while -- e.g. a synthesis model kept next to a training run."""
@@ -200,36 +145,12 @@ class Decoder(nn.Module):
         self._engine_key = None
         self._engine_vers = None
 
-    def _apply(self, fn, *a, **k):            # .to() / .cuda() / .half(): storage changes
-        self._engine_key = None
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._engine_key = None
-        return super()._load_from_state_dict(*a, **k)
-
-    def engine(self):
-        """The st_engine bound to the device of the parameters, with weights in sync.
-
-        The engine READS the fp32 parameters where torch keeps them (st_bind_param: no copy); what it owns are the
-        packed 16-bit MFMA operand copies.  After an in-place update (every optimizer step of a training loop) those
-        are re-packed by kernels on the current stream (st_repack): no allocation, no host copy, no synchronisation.
-        Only a change of storage (first use, ``.to()``, dtype change) takes the slow path (bind + st_finalize)."""
-        p0 = next(self.parameters())
-        if p0.device.type != "cuda":
-            raise RuntimeError("stabletts_amd: the estimator runs only on a HIP device (move the module with "
-                               ".to('cuda')); there is no CPU fallback")
-        dev = p0.device.index if p0.device.index is not None else torch.cuda.current_device()
-        if self._engine is None or self._engine.device != dev or self._engine.operand_dtype != self.operand_dtype:
-            if self._engine is not None:
-                self._engine.close()
-            self._engine = _lib.Engine(self.noise_channels, self.hidden_channels, self.filter_channels, self.n_heads,
-                                       self.n_layers, self.kernel_size, self.gin_channels, self.operand_dtype, dev)
-            self._engine_key = None
-            if getattr(self, "_attn_split", False):
-                self._engine.set_option("attention_precision", 1)
-        sync_engine_params(self, dev)
-        return self._engine
+    def _create_engine(self, dev):
+        eng = _lib.Engine(self.noise_channels, self.hidden_channels, self.filter_channels, self.n_heads,
+                          self.n_layers, self.kernel_size, self.gin_channels, self.operand_dtype, dev)
+        if getattr(self, "_attn_split", False):
+            eng.set_option("attention_precision", 1)
+        return eng
 
     AUTO_SPLIT_LSE = 50.0      # natural units; seeded / initialised weights give ~10, the arg-max regime of DESIGN.md section 2 80-200
 

@@ -16,10 +16,16 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .estimator import DiTConVBlock, _param_key, sync_engine_params
+from ._native_module import NativeModule, check_activations_live, dropout_seed, param_grad_views
+from .estimator import DiTConVBlock
 
 
-class TextEncoder(nn.Module):
+class TextEncoder(NativeModule):
+    """engine(): as the decoder's (estimator.py): the engine reads the fp32 parameters in place (st_bind_param) and, after an
+    in-place update such as an optimizer step, re-packs its 16-bit copies on the current stream (st_repack): no re-upload, no
+    allocation."""
+    _what = "text encoder"
+
     def __init__(self, n_vocab, out_channels, hidden_channels, filter_channels, n_heads, n_layers, kernel_size,
                  p_dropout, gin_channels, operand_dtype="f16"):
         super().__init__()
@@ -35,10 +41,6 @@ class TextEncoder(nn.Module):
                                       for _ in range(n_layers)])
         self.proj = nn.Conv1d(hidden_channels, out_channels, 1)
         self.initialize_weights()
-        self._engine = None
-        self._engine_key = None
-        self._engine_vers = None
-        self._staging = None
 
     def initialize_weights(self):
         """adaLN-Zero (models/text_encoder.py:29-32)."""
@@ -46,45 +48,9 @@ class TextEncoder(nn.Module):
             nn.init.constant_(block.adaLN_modulation[-1].weight, 0)
             nn.init.constant_(block.adaLN_modulation[-1].bias, 0)
 
-    def __getstate__(self):
-        st = self.__dict__.copy()      # the ctypes engine handle is per-process, never copied/pickled
-        st["_engine"] = None
-        st["_engine_key"] = st["_engine_vers"] = st["_staging"] = None
-        return st
-
-    def _param_key(self):
-        return _param_key(self)
-
-    def sync_weights(self):
-        """Force a weight re-pack at the next call (after writes through ``p.data`` that bypass the version counter)."""
-        self._engine_vers = None
-
-    def _apply(self, fn, *a, **k):
-        self._engine_key = None
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._engine_key = None
-        return super()._load_from_state_dict(*a, **k)
-
-    def engine(self):
-        """The native handle bound to the device of the parameters, with weights in sync.  As the decoder's
-        (estimator.py): the engine reads the fp32 parameters in place (st_bind_param) and, after an in-place update such
-        as an optimizer step, re-packs its 16-bit copies on the current stream (st_repack): no re-upload, no allocation."""
-        p0 = next(self.parameters())
-        if p0.device.type != "cuda":
-            raise RuntimeError("stabletts_amd: the text encoder runs only on a HIP device (move the module with "
-                               ".to('cuda')); there is no CPU fallback")
-        dev = p0.device.index if p0.device.index is not None else torch.cuda.current_device()
-        if self._engine is None or self._engine.device != dev or self._engine.operand_dtype != self.operand_dtype:
-            if self._engine is not None:
-                self._engine.close()
-            self._engine = _lib.Engine(self.out_channels, self.hidden_channels, self.filter_channels, self.n_heads,
-                                       self.n_layers, self.kernel_size, self.gin_channels, self.operand_dtype, dev,
-                                       text_encoder_vocab=self.n_vocab)
-            self._engine_key = None
-        sync_engine_params(self, dev)
-        return self._engine
+    def _create_engine(self, dev):
+        return _lib.Engine(self.out_channels, self.hidden_channels, self.filter_channels, self.n_heads, self.n_layers,
+                           self.kernel_size, self.gin_channels, self.operand_dtype, dev, text_encoder_vocab=self.n_vocab)
 
     def forward(self, x: torch.Tensor, c: torch.Tensor, x_lengths: torch.Tensor):
         """x: (B, T) phoneme ids, c: (B, gin) speaker vectors, x_lengths: (B,) ->
@@ -136,7 +102,7 @@ class _TextEncoderFn(torch.autograd.Function):
         mu_x = torch.empty(B, mod.out_channels, T, **f32)
         mask = torch.empty(B, 1, T, **f32)
         p_drop = float(mod.p_dropout) if mod.training else 0.0
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p_drop > 0.0 else 0
+        seed = dropout_seed(p_drop)
         with torch.cuda.device(dev):
             eng.text_encoder_train_forward(tok, lens, cc, h, mu_x, mask, p_drop, seed, torch.cuda.current_stream(dev).cuda_stream)
         ctx.mod, ctx.eng, ctx.serial, ctx.vers = mod, eng, eng.train_serial(), mod._param_key()[1]
@@ -148,12 +114,7 @@ class _TextEncoderFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_x, grad_mu, _grad_mask):
         mod, eng = ctx.mod, ctx.eng
-        if (eng is not mod._engine or eng.handle is None or eng.train_serial() != ctx.serial
-                or mod._param_key()[1] != ctx.vers):
-            raise RuntimeError(
-                "stabletts_amd: this backward's activations are gone -- the text encoder's engine keeps the activations of ONE "
-                "grad-enabled forward, and another grad-enabled forward, an optimizer step / parameter update or a device move "
-                "happened since.  Call backward() before the next grad-enabled forward or parameter update.")
+        check_activations_live(mod, eng, ctx.serial, ctx.vers)
         need = ctx.needs_input_grad          # (mod, names, x, c, x_lengths, *params)
         if grad_x is None and grad_mu is None:
             return (None,) * len(need)
@@ -167,11 +128,4 @@ class _TextEncoderFn(torch.autograd.Function):
             flat = torch.zeros(lay[None], device=dev, dtype=torch.float32)
             gc = torch.empty(ctx.c_shape, device=dev, dtype=torch.float32) if need[3] else None
             eng.text_encoder_train_backward(ctx.serial, B, T, gx, gmu, flat, gc, torch.cuda.current_stream(dev).cuda_stream)
-        pg = []
-        for name, p, nd in zip(ctx.names, ctx.params, need[5:]):
-            if not nd:
-                pg.append(None)
-                continue
-            off, n, _ = lay[name]
-            pg.append(flat[off:off + n].view(p.shape))
-        return (None, None, None, gc, None, *pg)
+        return (None, None, None, gc, None, *param_grad_views(flat, lay, ctx.names, ctx.params, need[5:]))

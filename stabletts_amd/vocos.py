@@ -10,7 +10,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .estimator import _ParamsOnly, _param_key
+from ._native_module import NativeModule, _param_key
+from .estimator import _ParamsOnly
 
 
 class ConvNeXtBlock(_ParamsOnly):
@@ -63,9 +64,11 @@ class ISTFTHead(_ParamsOnly):
         self.istft = ISTFT(n_fft=n_fft, hop_length=hop_length, win_length=n_fft, padding=padding)
 
 
-class Vocos(nn.Module):
+class Vocos(NativeModule):
     """Same constructor as the reference: ``Vocos(VocosConfig(), MelConfig())`` -- any objects with the attributes
     input_channels / dim / intermediate_dim / num_layers and n_fft / hop_length (config.py:4-19,46-50)."""
+    _what = "vocoder"
+    _rebind = False             # st_finalize packs a vocoder's weights: every change re-loads
 
     def __init__(self, vocos_config, mel_config, operand_dtype="f16"):
         super().__init__()
@@ -80,45 +83,12 @@ class Vocos(nn.Module):
         # its parameters do not ask for gradients, so a plain ``voc(mel)`` is legal in any grad mode; asking for them
         # (requires_grad_(True) or a mel that requires grad) raises in forward instead of silently training nothing
         self.requires_grad_(False)
-        self._engine = None
-        self._engine_key = None
 
-    def __getstate__(self):
-        st = self.__dict__.copy()
-        st["_engine"] = None
-        st["_engine_key"] = None
-        return st
+    def _param_key(self):       # the ISTFT window is a buffer the engine reads too
+        return (_param_key(self), self.head.istft.window.data_ptr(), self.head.istft.window._version)
 
-    def sync_weights(self):
-        """Force a re-read of the parameters (after writes that bypass autograd's version counter)."""
-        self._engine_key = None
-
-    def _apply(self, fn, *a, **k):
-        self._engine_key = None
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._engine_key = None
-        return super()._load_from_state_dict(*a, **k)
-
-    def engine(self):
-        p0 = next(self.parameters())
-        if p0.device.type != "cuda":
-            raise RuntimeError("stabletts_amd: the vocoder runs only on a HIP device (move the module with .to('cuda')); "
-                               "there is no CPU fallback")
-        dev = p0.device.index if p0.device.index is not None else torch.cuda.current_device()
-        if self._engine is None or self._engine.device != dev or self._engine.operand_dtype != self.operand_dtype:
-            if self._engine is not None:
-                self._engine.close()
-            self._engine = _lib.Engine(0, 0, 0, 0, 0, 0, 0, self.operand_dtype, dev, vocoder=self.cfg)
-            self._engine_key = None
-        key = (_param_key(self), self.head.istft.window.data_ptr(), self.head.istft.window._version)
-        if key != self._engine_key:
-            with torch.no_grad():
-                torch.cuda.synchronize(dev)
-                self._engine.load_state_dict(self.state_dict())
-            self._engine_key = key
-        return self._engine
+    def _create_engine(self, dev):
+        return _lib.Engine(0, 0, 0, 0, 0, 0, 0, self.operand_dtype, dev, vocoder=self.cfg)
 
     def forward(self, x):
         """mel (B, input_channels, T) -> audio (B, T * hop_length)  (model.py:17-20)."""

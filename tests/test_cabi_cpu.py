@@ -291,3 +291,37 @@ def test_design_md_numbers_come_from_the_committed_evidence():
     after = open(os.path.join(ROOT, "DESIGN.md")).read()
     assert after == before, "DESIGN.md is stale: run python tools/fill_design.py"
     assert len(after.splitlines()) <= 400 and "\u27e8" not in after.encode("unicode_escape").decode()
+
+
+def _creators(lib):
+    """name -> (valid configuration, call(cfg or None, out or None)) of the six st_create* entry points."""
+    from stabletts_amd import _lib
+    dit = dict(noise_channels=128, hidden_channels=256, filter_channels=1024, n_heads=4, n_layers=6, kernel_size=3,
+               gin_channels=256, operand_dtype=0)
+    table = {
+        "st_create": (_lib.StConfig(**dit), lambda c, o: lib.st_create(c, 0, o)),
+        "st_create_text_encoder": (_lib.StConfig(**dit), lambda c, o: lib.st_create_text_encoder(c, 401, 0, o)),
+        "st_create_vocoder": (_lib.StVocosConfig(input_channels=128, dim=512, intermediate_dim=1536, num_layers=8, n_fft=2048,
+                                                 hop_length=512, operand_dtype=0), lambda c, o: lib.st_create_vocoder(c, 0, o)),
+        "st_create_style_encoder": (_lib.StStyleEncoderConfig(n_mel_channels=100, style_hidden=128, style_vector_dim=256,
+                                                              style_kernel_size=5, style_head=2),
+                                    lambda c, o: lib.st_create_style_encoder(c, 0, o)),
+        "st_create_duration_predictor": (_lib.StDurationPredictorConfig(in_channels=256, filter_channels=256, kernel_size=3,
+                                                                        gin_channels=256),
+                                         lambda c, o: lib.st_create_duration_predictor(c, 0, o)),
+        "st_create_mel_extractor": (_lib.StMelConfig(n_fft=1024, win_length=1024, hop_length=256, pad=384, n_mels=100, center=0,
+                                                     pad_mode=0), lambda c, o: lib.st_create_mel_extractor(c, 0, o)),
+    }
+    return table
+
+
+def test_every_creator_rejects_null_arguments_and_needs_a_device(lib):
+    """Each st_create* checks its arguments, then its configuration, then the device: a null configuration or output pointer is
+    ST_ERR_INVALID "null argument"; a valid configuration on a machine without a GPU is ST_ERR_HIP "no such HIP device"."""
+    for name, (cfg, call) in _creators(lib).items():
+        h = ctypes.c_void_p()
+        assert (call(None, ctypes.byref(h)), lib.st_last_error(None).decode()) == (-1, "null argument"), name
+        assert (call(ctypes.byref(cfg), None), lib.st_last_error(None).decode()) == (-1, "null argument"), name
+        if not torch.cuda.is_available():
+            assert (call(ctypes.byref(cfg), ctypes.byref(h)), lib.st_last_error(None).decode()) == (-2, "no such HIP device"), name
+            assert not h.value, name
