@@ -29,6 +29,22 @@ def sample_index(numel, seed, k=512):
     return np.unique(rng.integers(0, numel, size=min(k, numel)))
 
 
+def grad_digest(grads, seed, full_max=4096):
+    """What tests/golden/style_dp_configs.npz keeps of a case's gradients {name: array}: the sorted names, per name the
+    float64 norm and max |g|, and two flat float arrays in name order: every tensor of at most full_max elements whole, and
+    sample_index(numel, seed + position) of each larger one."""
+    names = sorted(grads)
+    flat = [np.asarray(grads[n]).reshape(-1) for n in names]
+    full = [g for g in flat if g.size <= full_max]
+    samp = [g[sample_index(g.size, seed + i)] for i, g in enumerate(flat) if g.size > full_max]
+    cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, np.float32)      # noqa: E731
+    return dict(names=np.array(names), norms=np.array([float(np.linalg.norm(g.astype(np.float64))) for g in flat]),
+                absmax=np.array([float(np.abs(g).max()) for g in flat]), full=cat(full), sample=cat(samp),
+                owner_full=np.concatenate([np.full(g.size, i) for i, g in enumerate(flat) if g.size <= full_max] or [np.zeros(0, int)]),
+                owner_sample=np.concatenate([np.full(sample_index(g.size, seed + i).size, i) for i, g in enumerate(flat) if g.size > full_max]
+                                            or [np.zeros(0, int)]))
+
+
 def style_forward(sd, x, x_mask=None, drop=None, n_head=2):
     drop = drop or {}
     f = lambda site, t: t * drop[site] if site in drop else t      # noqa: E731
@@ -59,16 +75,74 @@ def style_forward(sd, x, x_mask=None, drop=None, n_head=2):
     return (o * valid[:, :, None]).sum(dim=1) / valid.sum(dim=1, keepdim=True)
 
 
-def dp_forward(sd, x, x_mask, g, drop=None):
+def dp_forward(sd, x, x_mask, g, drop=None, return_pre=False):
+    """return_pre: also the two ReLU pre-activations (conv1's and conv2's outputs), for the tests that check that none of
+    them is close enough to 0 for a rounding difference to flip it."""
     drop = drop or {}
     f = lambda site, t: t * drop[site] if site in drop else t      # noqa: E731
     x = x.detach() + F.conv1d(g.detach().unsqueeze(2), sd["cond.weight"], sd["cond.bias"])
     k = sd["conv1.weight"].shape[2]
-    x = torch.relu(F.conv1d(x * x_mask, sd["conv1.weight"], sd["conv1.bias"], padding=k // 2))
+    pre1 = F.conv1d(x * x_mask, sd["conv1.weight"], sd["conv1.bias"], padding=k // 2)
+    x = torch.relu(pre1)
     x = f("norm1", F.layer_norm(x.transpose(1, 2), (x.shape[1],), sd["norm1.weight"], sd["norm1.bias"]).transpose(1, 2))
-    x = torch.relu(F.conv1d(x * x_mask, sd["conv2.weight"], sd["conv2.bias"], padding=k // 2))
+    pre2 = F.conv1d(x * x_mask, sd["conv2.weight"], sd["conv2.bias"], padding=k // 2)
+    x = torch.relu(pre2)
     x = f("norm2", F.layer_norm(x.transpose(1, 2), (x.shape[1],), sd["norm2.weight"], sd["norm2.bias"]).transpose(1, 2))
-    return F.conv1d(x * x_mask, sd["proj.weight"], sd["proj.bias"]) * x_mask
+    logw = F.conv1d(x * x_mask, sd["proj.weight"], sd["proj.bias"]) * x_mask
+    return (logw, (pre1, pre2)) if return_pre else logw
+
+
+def kink_margin(pre64, pre32, x_mask):
+    """(min |float64 pre-activation|, max |fp32 - float64| pre-activation) over both ReLU sites, valid tokens only: a padded
+    token's activations are multiplied by x_mask before anything reads them, so a flip there changes nothing."""
+    v = (torch.as_tensor(x_mask) != 0).reshape(x_mask.shape[0], 1, -1).cpu()
+    lo, diff = float("inf"), 0.0
+    for a, b in zip(pre64, pre32):
+        a = a.detach().double(); b = b.detach().double()
+        lo = min(lo, float(a.abs().masked_fill(~v, float("inf")).min()))
+        diff = max(diff, float((a - b).abs().masked_fill(~v, 0.0).max()))
+    return lo, diff
+
+
+# ---- the float64 runs the tests compare with: output, loss against the seeded projection, parameter gradients
+def _as(sd, dtype):
+    return {k: v.detach().cpu().to(dtype).clone().requires_grad_(True) for k, v in sd.items()}
+
+
+def run_style(sd, y, mask, seed, n_head=2, drop=None, dtype=torch.float64):
+    """(c, loss, {name: gradient}) of style_forward in `dtype` on the CPU; y / mask numpy or tensors, mask may be None."""
+    p = _as(sd, dtype)
+    t = lambda a: None if a is None else torch.as_tensor(a).detach().cpu().to(dtype)      # noqa: E731
+    c = style_forward(p, t(y), t(mask), drop={k: v.to(dtype) for k, v in (drop or {}).items()}, n_head=n_head)
+    loss = (c * loss_weights(tuple(c.shape), seed).to(dtype)).sum()
+    loss.backward()
+    return c.detach().numpy(), float(loss.detach()), {k: v.grad.numpy() for k, v in p.items()}
+
+
+def run_dp(sd, x, mask, g, seed, drop=None, dtype=torch.float64):
+    """(logw, loss, {name: gradient}, (pre1, pre2)) of dp_forward in `dtype` on the CPU."""
+    p = _as(sd, dtype)
+    t = lambda a: torch.as_tensor(a).detach().cpu().to(dtype)      # noqa: E731
+    logw, pre = dp_forward(p, t(x), t(mask), t(g), drop={k: v.to(dtype) for k, v in (drop or {}).items()}, return_pre=True)
+    loss = (logw * loss_weights(tuple(logw.shape), seed).to(dtype)).sum()
+    loss.backward()
+    return logw.detach().numpy(), float(loss.detach()), {k: v.grad.numpy() for k, v in p.items()}, tuple(a.detach() for a in pre)
+
+
+def digest_errors(ref, grads, seed):
+    """{name: (max |g - ref| / max |ref| over the kept elements, |norm - ref norm| / ref norm)} of gradients {name: array}
+    against a stored or computed grad_digest `ref` (a mapping with names, norms, absmax, full, sample)."""
+    d = grad_digest(grads, seed)
+    names = [str(n) for n in ref["names"]]
+    assert [str(n) for n in d["names"]] == names, (d["names"], names)
+    assert d["full"].shape == ref["full"].shape and d["sample"].shape == ref["sample"].shape
+    err = np.zeros(len(names))
+    for part in ("full", "sample"):
+        diff = np.abs(d[part].astype(np.float64) - np.asarray(ref[part], dtype=np.float64))
+        np.maximum.at(err, d["owner_" + part], diff)
+    scale = np.maximum(np.asarray(ref["absmax"], dtype=np.float64), 1e-30)
+    nref = np.asarray(ref["norms"], dtype=np.float64)
+    return {n: (float(err[i] / scale[i]), float(abs(d["norms"][i] - nref[i]) / max(nref[i], 1e-30))) for i, n in enumerate(names)}
 
 
 # ---- the native keep masks in numpy (csrc/common.h, csrc/train_kernels.hip make_drop, csrc/style_dp_drop.h)
