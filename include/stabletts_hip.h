@@ -219,6 +219,21 @@ int st_create_vocoder(const st_vocos_config* cfg, int device, st_engine** out);
  * own is rejected (ST_ERR_INVALID), as is a batch that needs more than one chunk while debug capture is on. */
 int st_vocos_forward(st_engine* e, const float* mel, float* audio, int B, int T, void* stream);
 
+/* ---- Vocos generator training: autograd counterpart of Vocos.forward on a vocoder handle (the generator step of
+ * vocoders/vocos/train.py:94,115,128).  fp32 values and accumulation throughout (fp32-input MFMA): the parameters are read
+ * IN PLACE from the tensors st_bind_param holds (or st_load_param's copies), so an optimizer step needs no re-pack for these two
+ * entries; "head.istft.window" is a buffer and gets no gradient.  The waveform is therefore not bitwise st_vocos_forward's
+ * (16-bit GEMM operands); it is closer to the fp32 reference.
+ * st_vocos_train_forward: mel (B, input_channels, T) -> audio (B, T * hop_length), keeping the activations of this ONE forward in the
+ * handle (st_train_serial counts the forwards; st_finalize drops them).
+ * st_vocos_train_backward: d_audio (B, T * hop_length) = d loss / d audio -> EVERY parameter gradient into grad_flat
+ * (st_train_grad_numel() floats in the layout of st_train_grad_offset: 64-byte aligned slices, the gaps and the window's slice are
+ * not written) and, unless d_mel is NULL, d loss / d mel (B, input_channels, T).  B and T must be the forward's; without a held
+ * forward the call fails with ST_ERR_STATE.  No atomics, every reduction in a fixed order: gradients are bitwise repeatable.
+ * One batch per call (no chunking): B * T * max(7 input_channels, intermediate_dim, 2304) < 2^31 and B <= 65535, else ST_ERR_INVALID. */
+int st_vocos_train_forward(st_engine* e, const float* mel, float* audio, int B, int T, void* stream);
+int st_vocos_train_backward(st_engine* e, const float* d_audio, float* d_mel /* nullable */, float* grad_flat, int B, int T, void* stream);
+
 /* ---- MelStyleEncoder and DurationPredictor: stages 1 and 3 of StableTTS.synthesise (models/model.py:79-81) ------- */
 /* Both run in fp32 (fp32-input MFMA for every convolution and linear): the durations they feed are ceil()ed
  * (model.py:83-84), so a 16-bit logw error would add or drop whole frames.  Inference only (eval mode: no dropout). */

@@ -16,7 +16,10 @@ so the reference's training ``forward`` imports and runs its alignment search on
 ``install(audio=True)`` registers ``stabletts_amd.audio`` as ``utils.audio`` (``api.py:6,17``, ``preprocess.py:11``): the
 native ``LogMelSpectrogram`` feature front end, which needs no torchaudio; ``install(audio="train")`` registers
 ``stabletts_amd.audio_train`` instead, whose spectrograms are also differentiable in the waveform (``native_training = True``),
-for the Vocos multi-scale mel loss (``vocoders/vocos/models/loss.py:6``).
+for the Vocos multi-scale mel loss (``vocoders/vocos/models/loss.py:6``);
+``install(vocoder=True)`` registers ``stabletts_amd.vocos`` as ``vocoders.vocos.models.model`` (``api.py:26-28``), inference-only;
+``install(vocoder="train")`` registers ``stabletts_amd.vocos_train`` instead, whose ``Vocos`` also trains natively in fp32
+(``vocoders/vocos/train.py:94``: the generator).
 """
 import sys
 
@@ -33,7 +36,10 @@ def install(text_encoder=False, vocoder=False, reference_encoder=False, duration
     if text_encoder:
         from . import text_encoder as te
         sys.modules["models.text_encoder"] = te
-    if vocoder:
+    if vocoder == "train":                                       # Vocos with native_training = True: the generator of vocoders/vocos/train.py
+        from . import vocos_train
+        sys.modules["vocoders.vocos.models.model"] = vocos_train
+    elif vocoder:
         from . import vocos
         sys.modules["vocoders.vocos.models.model"] = vocos      # api.py:26-28: from vocoders.vocos.models.model import Vocos
     if reference_encoder == "train":                             # MelStyleEncoder with native_training = True

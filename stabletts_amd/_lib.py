@@ -111,6 +111,8 @@ PROTOTYPES = {
     "st_cfm_loss_scratch_floats": (i32, []),
     "st_create_vocoder": (i32, [P(StVocosConfig), i32, P(vp)]),
     "st_vocos_forward": (i32, [vp, vp, vp, i32, i32, vp]),
+    "st_vocos_train_forward": (i32, [vp, vp, vp, i32, i32, vp]),
+    "st_vocos_train_backward": (i32, [vp, vp, vp, vp, i32, i32, vp]),
     "st_set_option": (i32, [vp, c_char_p, i32]),
     "st_get_option": (i32, [vp, c_char_p, P(i32)]),
     "st_attention_stats": (i32, [vp, vp, P(f32)]),
@@ -278,6 +280,22 @@ class Engine:
     def vocos_forward(self, mel, audio, stream):
         B, _, T = mel.shape
         self._check(self.lib.st_vocos_forward(self.handle, mel.data_ptr(), audio.data_ptr(), B, T, ctypes.c_void_p(stream)))
+
+    def vocos_train_forward(self, mel, audio, stream):
+        """st_vocos_forward in fp32 that keeps the activations for vocos_train_backward (vocoder handles)."""
+        B, _, T = mel.shape
+        self._check(self.lib.st_vocos_train_forward(self.handle, mel.data_ptr(), audio.data_ptr(), B, T, ctypes.c_void_p(stream)))
+
+    def vocos_train_backward(self, B, T, d_audio, d_mel, grad_flat, stream):
+        """Every parameter gradient into grad_flat (grad_layout()[None] floats) and d mel (None: not wanted) from d loss / d audio."""
+        if grad_flat.numel() != self.grad_layout()[None]:
+            raise ValueError("grad_flat must hold grad_layout()[None] floats")
+        self._check(self.lib.st_vocos_train_backward(self.handle, d_audio.data_ptr(), d_mel.data_ptr() if d_mel is not None else None,
+                                                     grad_flat.data_ptr(), B, T, ctypes.c_void_p(stream)))
+
+    def finalize(self):
+        """st_finalize on the parameters already loaded / bound: a vocoder handle packs its 16-bit inference copies again."""
+        self._check(self.lib.st_finalize(self.handle))
 
     def mel_frames(self, L):
         """Frames of an utterance of L samples (mel-extractor handles); raises NativeError where the reference raises."""

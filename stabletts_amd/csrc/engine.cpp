@@ -836,6 +836,7 @@ int st_finalize(st_engine* e) {
         return ST_OK;
     }
     if (e->kind == KIND_VOCODER) {
+        if (e->sdt) e->sdt->have = false;      // st_vocos_train_forward's activations are of the weights before this re-bind / re-load
         e->drop_graphs();
         for (void* p : e->owned) hipFree(p);
         e->owned.clear(); e->weight_bytes = 0;
