@@ -12,6 +12,9 @@
  *     16-bit weight copies and its workspace.
  *   - work is enqueued on the caller's HIP stream (`stream` = hipStream_t, e.g.
  *     torch.cuda.current_stream().cuda_stream) with no implicit device synchronisation.
+ *   - a handle is one of seven kinds, each with its own creator: the CFM decoder, the text encoder, the Vocos vocoder, the style
+ *     encoder, the duration predictor, the mel extractor and the period discriminator of the Vocos training step; an entry point
+ *     handed a handle of another kind returns ST_ERR_STATE.
  *   - one engine per device per process; an engine is not thread-safe (the reference is
  *     single-threaded per process: train.py:101-102, webui.py:128).
  */
@@ -233,6 +236,43 @@ int st_vocos_forward(st_engine* e, const float* mel, float* audio, int B, int T,
  * One batch per call (no chunking): B * T * max(7 input_channels, intermediate_dim, 2304) < 2^31 and B <= 65535, else ST_ERR_INVALID. */
 int st_vocos_train_forward(st_engine* e, const float* mel, float* audio, int B, int T, void* stream);
 int st_vocos_train_backward(st_engine* e, const float* d_audio, float* d_mel /* nullable */, float* grad_flat, int B, int T, void* stream);
+
+/* ---- period discriminator of the Vocos training step (vocoders/vocos/models/discriminator.py:32-75, train.py:98-128) ---- */
+/* One handle serves one DiscriminatorP(period, in_channels = 1, kernel_size = 5, stride = 3, lrelu_slope); the five of a
+ * MultiPeriodDiscriminator are five handles.  fp32 throughout, the reference's (B, C, H, period) layout, no atomics: every value
+ * and gradient is bitwise repeatable, and an item's values do not depend on the rest of the batch.  Layers 1-4 are GEMMs on the
+ * fp32-input MFMA (forward, data gradient, weight gradient); layer 0, conv_post and the weight norm are vector kernels. */
+typedef struct st_period_disc_config {
+    int32_t period;       /* >= 1 */
+    float lrelu_slope;    /* > 0: the backward takes the pre-activation's sign from the kept post-activation */
+} st_period_disc_config;
+
+/* The handle takes the reference's state-dict entries through st_load_param / st_bind_param / st_finalize:
+ * "convs.{i}.parametrizations.weight.original0" (g: Cout, 1, 1, 1), "...original1" (v: Cout, Cin, 5, 1), "convs.{i}.bias" for
+ * i = 0..4 and the same three under "conv_post." (v: 1, 1024, 3, 1).  st_finalize computes the effective weights v g / ||v||
+ * once; after an in-place update of bound tensors st_repack(e, stream) computes them again as kernels on `stream`.  Either
+ * drops the activations a training forward left.  Destroyed with st_destroy. */
+int st_create_period_discriminator(const st_period_disc_config* cfg, int device, st_engine** out);
+
+/* Feature map `index` (0..3: after convs.1..4, 4: conv_post's output, the logits) of a T-sample input is (B, *channels, *rows,
+ * period).  ST_ERR_INVALID for a bad index or a T the forward rejects. */
+int st_period_disc_fmap_shape(const st_engine* e, int T, int index, int64_t* channels, int64_t* rows);
+
+/* Replaces DiscriminatorP.forward:  x (B, 1, T) -> the five feature maps, fp32 device pointers in fmaps[0..4] (shapes above); the
+ * module's first return value is fmaps[4] flattened.  T % period != 0 pads the tail by reflection as the reference does, which
+ * needs T > period - T % period (ST_ERR_INVALID otherwise, where F.pad raises).  st_period_disc_forward keeps nothing.
+ * st_period_disc_train_forward keeps x and the post-activations of this ONE forward in the handle (st_train_serial counts it). */
+int st_period_disc_forward(st_engine* e, const float* x, float* const* fmaps, int B, int T, void* stream);
+int st_period_disc_train_forward(st_engine* e, const float* x, float* const* fmaps, int B, int T, void* stream);
+
+/* Backward of the held forward.  d_fmaps[0..4]: d loss / d feature map, each entry may be NULL (no gradient reaches that map).
+ * d_x (nullable): receives d loss / d x (B, 1, T), the padded samples' share folded onto the samples they mirror; NULL skips
+ * layer 0's data gradient.  grad_flat (nullable): st_train_grad_numel() floats that receive every parameter gradient at
+ * st_train_grad_offset(name) (the gaps are not written; with d_fmaps[4] == NULL neither are conv_post's slices); NULL skips every
+ * weight-gradient and weight-norm kernel.  B and T must be the forward's: ST_ERR_STATE without a held forward or with another
+ * shape, before any caller memory is touched. */
+int st_period_disc_train_backward(st_engine* e, const float* const* d_fmaps, float* d_x /* nullable */, float* grad_flat /* nullable */,
+                                  int B, int T, void* stream);
 
 /* ---- MelStyleEncoder and DurationPredictor: stages 1 and 3 of StableTTS.synthesise (models/model.py:79-81) ------- */
 /* Both run in fp32 (fp32-input MFMA for every convolution and linear): the durations they feed are ceil()ed

@@ -19,7 +19,10 @@ native ``LogMelSpectrogram`` feature front end, which needs no torchaudio; ``ins
 for the Vocos multi-scale mel loss (``vocoders/vocos/models/loss.py:6``);
 ``install(vocoder=True)`` registers ``stabletts_amd.vocos`` as ``vocoders.vocos.models.model`` (``api.py:26-28``), inference-only;
 ``install(vocoder="train")`` registers ``stabletts_amd.vocos_train`` instead, whose ``Vocos`` also trains natively in fp32
-(``vocoders/vocos/train.py:94``: the generator).
+(``vocoders/vocos/train.py:94``: the generator);
+``install(discriminator="train")`` rebinds ``MultiPeriodDiscriminator`` and ``DiscriminatorP`` of the user's own
+``vocoders.vocos.models.discriminator`` (``vocoders/vocos/train.py:19,54``) to the native classes of ``stabletts_amd.discriminator``;
+the multi-resolution discriminator of that module is left as it is.
 """
 import sys
 
@@ -27,7 +30,7 @@ __all__ = ["install", "CFMDecoder", "TextEncoder", "MelStyleEncoder", "DurationP
 
 
 def install(text_encoder=False, vocoder=False, reference_encoder=False, duration_predictor=False, monotonic_align=False,
-            audio=False):
+            audio=False, discriminator=False):
     """Make ``models.flow_matching`` (and optionally ``models.text_encoder`` / ``vocoders.vocos.models.model`` /
     ``models.reference_encoder`` / ``models.duration_predictor`` / ``monotonic_align`` / ``utils.audio``) resolve to the native drop-ins
     (call before importing models.model / api.get_vocoder)."""
@@ -63,6 +66,19 @@ def install(text_encoder=False, vocoder=False, reference_encoder=False, duration
     elif audio:
         from . import audio as au
         sys.modules["utils.audio"] = au                          # api.py:6, preprocess.py:11, vocoders/vocos/models/loss.py:6
+    if discriminator:
+        if discriminator != "train":
+            raise ValueError('install(discriminator=...) takes "train": the discriminators exist for training only')
+        import importlib
+        from . import discriminator as nd
+        try:                                                     # the user's module: its multi-resolution classes stay
+            ref = importlib.import_module("vocoders.vocos.models.discriminator")
+        except ImportError as exc:
+            raise ImportError('install(discriminator="train") rebinds MultiPeriodDiscriminator and DiscriminatorP inside '
+                              "vocoders.vocos.models.discriminator, which could not be imported (is the StableTTS checkout on "
+                              f"sys.path, and are its own imports such as torchaudio installed?): {exc}") from exc
+        ref.MultiPeriodDiscriminator = nd.MultiPeriodDiscriminator      # vocoders/vocos/train.py:19,54
+        ref.DiscriminatorP = nd.DiscriminatorP
     return flow_matching
 
 
@@ -85,6 +101,9 @@ def __getattr__(name):
     if name == "LogMelSpectrogram":
         from .audio import LogMelSpectrogram
         return LogMelSpectrogram
+    if name == "MultiPeriodDiscriminator":
+        from .discriminator import MultiPeriodDiscriminator
+        return MultiPeriodDiscriminator
     if name == "maximum_path":
         from .monotonic_align import maximum_path
         return maximum_path

@@ -600,6 +600,7 @@ int st_train_forward(st_engine* e, const float* t, const float* x, const float* 
 int64_t st_train_serial(const st_engine* e) {
     if (e && reads_params_in_place(e->kind)) return e->sdt && e->sdt->have ? e->sdt->serial : 0;
     if (e && e->kind == KIND_VOCODER) return e->sdt && e->sdt->have ? e->sdt->serial : 0;      // st_vocos_train_forward
+    if (e && e->kind == KIND_PERIOD_DISC) return e->sdt && e->sdt->have ? e->sdt->serial : 0;  // st_period_disc_train_forward
     if (!e || !e->train || !e->train->have_fwd) return 0;
     return e->train->serial;
 }
