@@ -62,11 +62,11 @@ int st_duration_predictor_forward(st_engine* e, const float* x, const float* x_m
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
 
-    size_t off = 0;
-    auto want = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_gb = want((size_t)B * Ci * 4), o_h1 = want((size_t)R * F * 4), o_h2 = want((size_t)R * F * 4);
-    if ((rc = ensure_ws(e, off))) return rc;
-    float* gb = (float*)(e->ws + o_gb); float* h1 = (float*)(e->ws + o_h1); float* h2 = (float*)(e->ws + o_h2);
+    FloatArena ar;
+    const size_t o_gb = ar.want((size_t)B * Ci), o_h1 = ar.want((size_t)R * F), o_h2 = ar.want((size_t)R * F);
+    if ((rc = ensure_ws(e, ar.off * 4))) return rc;
+    float* ws = (float*)e->ws;
+    float* gb = ws + o_gb; float* h1 = ws + o_h1; float* h2 = ws + o_h2;
 
     {   // cond(g) (:26): a k = 1 conv over a one-frame input -> per-item bias of in_channels
         SdConvArgs a; a.in = g; a.Cin = G; a.w = P(e, "cond.weight"); a.bias = P(e, "cond.bias"); a.out = gb; a.Cout = Ci;
@@ -106,12 +106,11 @@ struct DurActs {        // float offsets into SdTrain::act; R = B * Tx
 DurActs dur_acts(const st_duration_predictor_config& c, int B, int T) {
     const size_t R = (size_t)B * T, F = c.filter_channels;
     DurActs a{};
-    size_t off = 0;
-    auto want = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
-    a.x = want(R * c.in_channels); a.mask = want(R); a.g = want((size_t)B * c.gin_channels); a.gb = want((size_t)B * c.in_channels);
-    a.r1 = want(R * F); a.m1 = want(R); a.s1 = want(R); a.d1 = want(R * F);
-    a.r2 = want(R * F); a.m2 = want(R); a.s2 = want(R); a.d2 = want(R * F);
-    a.end = off;
+    FloatArena ar;
+    a.x = ar.want(R * c.in_channels); a.mask = ar.want(R); a.g = ar.want((size_t)B * c.gin_channels); a.gb = ar.want((size_t)B * c.in_channels);
+    a.r1 = ar.want(R * F); a.m1 = ar.want(R); a.s1 = ar.want(R); a.d1 = ar.want(R * F);
+    a.r2 = ar.want(R * F); a.m2 = ar.want(R); a.s2 = ar.want(R); a.d2 = ar.want(R * F);
+    a.end = ar.off;
     return a;
 }
 
@@ -190,10 +189,9 @@ int st_duration_predictor_train_backward(st_engine* e, int64_t serial, int B, in
     ws = std::max(ws, sd_wgrad_scratch_floats(B, F, F, Tx, K));
     ws = std::max(ws, sd_wgrad_scratch_floats(B, Ci, F, Tx, K));
     ws = std::max(ws, sd_wgrad_scratch_floats(B, Gc, Ci, 1, 1));
-    size_t off = 0;
-    auto want = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
-    const size_t o_dy = want(R), o_a = want(R * F), o_b = want(R * F), o_dx = want(R * Ci), o_dc = want((size_t)B * Ci), o_ws = want(ws);
-    if ((rc = sd_train_grow(e, &st->scr, &st->scr_cap, off * 4))) return rc;
+    FloatArena ar;
+    const size_t o_dy = ar.want(R), o_a = ar.want(R * F), o_b = ar.want(R * F), o_dx = ar.want(R * Ci), o_dc = ar.want((size_t)B * Ci), o_ws = ar.want(ws);
+    if ((rc = sd_train_grow(e, &st->scr, &st->scr_cap, ar.off * 4))) return rc;
     float* scr = (float*)st->scr;
     float* dY = scr + o_dy; float* Pa = scr + o_a; float* Pb = scr + o_b; float* dX = scr + o_dx; float* dC = scr + o_dc; float* wsp = scr + o_ws;
 

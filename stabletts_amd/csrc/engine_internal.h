@@ -37,6 +37,12 @@ struct ProfEvent { int cls; hipEvent_t a, b; double flops; };
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Float offsets into one device buffer, handed out in order, each on a 64-float (256-byte) boundary; off: the floats used so far
+struct FloatArena {
+    size_t off = 0;
+    size_t want(size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; }
+};
+
 // What a handle is (st_engine::kind), in the order the creators were added.  kKinds names each for the message of an entry
 // point that is handed another kind's handle (check_handle).
 enum Kind { KIND_DECODER = 0, KIND_TEXT_ENCODER, KIND_VOCODER, KIND_STYLE_ENCODER, KIND_DURATION_PREDICTOR, KIND_MEL_EXTRACTOR, KIND_PERIOD_DISC, KIND_COUNT };

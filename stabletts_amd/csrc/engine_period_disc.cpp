@@ -52,6 +52,22 @@ static PdGeom pd_geom(int p, int T) {
     return g;
 }
 
+// float offsets into SdTrain::act of what a training forward keeps: the waveform and the post-activations a0 .. a4
+struct PdActs { size_t x, a[kPdLayers], widest, end; };
+
+static PdActs pd_acts(int B, const PdGeom& g) {
+    PdActs A{};
+    FloatArena ar;
+    A.x = ar.want((size_t)B * g.T);
+    for (int i = 0; i < kPdLayers; ++i) {
+        const size_t n = (size_t)B * kPdCh[i + 1] * g.H[i + 1] * g.p;
+        A.a[i] = ar.want(n);
+        A.widest = std::max(A.widest, n);
+    }
+    A.end = ar.off;
+    return A;
+}
+
 void period_disc_destroy(st_engine* e) {
     if (!e->pd) return;
     for (float* w : e->pd->w) if (w) hipFree(w);
@@ -90,16 +106,12 @@ static int pd_forward(st_engine* e, const float* x, float* const* fmaps, int B, 
     float* a[kPdLayers] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     const float* xin = x;
     if (keep) {
-        size_t off = 0;
-        auto want = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
-        size_t o_a[kPdLayers];
-        const size_t o_x = want((size_t)B * g.T);
-        for (int i = 0; i < kPdLayers; ++i) o_a[i] = want((size_t)B * kPdCh[i + 1] * g.H[i + 1] * p);
-        if ((rc = sd_train_grow(e, &keep->act, &keep->act_cap, off * 4))) return rc;
+        const PdActs A = pd_acts(B, g);
+        if ((rc = sd_train_grow(e, &keep->act, &keep->act_cap, A.end * 4))) return rc;
         float* act = (float*)keep->act;
-        HIPCHK(e, hipMemcpyAsync(act + o_x, x, (size_t)B * g.T * 4, hipMemcpyDeviceToDevice, s));
-        xin = act + o_x;
-        for (int i = 0; i < kPdLayers; ++i) a[i] = act + o_a[i];
+        HIPCHK(e, hipMemcpyAsync(act + A.x, x, (size_t)B * g.T * 4, hipMemcpyDeviceToDevice, s));
+        xin = act + A.x;
+        for (int i = 0; i < kPdLayers; ++i) a[i] = act + A.a[i];
     } else {
         if ((rc = ensure_ws(e, (size_t)B * kPdCh[1] * g.H[1] * p * 4))) return rc;
         a[0] = (float*)e->ws;
@@ -194,28 +206,21 @@ int st_period_disc_train_backward(st_engine* e, const float* const* d_fmaps, flo
     const int p = g.p;
     const float slope = e->pd->cfg.lrelu_slope;
 
-    // the kept activations, laid out as pd_forward laid them out
-    size_t off = 0;
-    auto want = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
-    float* act = (float*)st->act;
-    const float* x = act + want((size_t)B * g.T);
+    const PdActs A = pd_acts(B, g);
+    const float* act = (const float*)st->act;
+    const float* x = act + A.x;
     const float* a[kPdLayers];
-    size_t a_numel[kPdLayers], widest = 0;
-    for (int i = 0; i < kPdLayers; ++i) {
-        a_numel[i] = (size_t)B * kPdCh[i + 1] * g.H[i + 1] * p;
-        a[i] = act + want(a_numel[i]);
-        widest = std::max(widest, a_numel[i]);
-    }
+    for (int i = 0; i < kPdLayers; ++i) a[i] = act + A.a[i];
     // scratch: two gradient planes, one weight-shaped plane, the split-K planes, layer 0's partial sums
     size_t ws = 0, wmax = 0;
     if (grad_flat) {
         for (int i = 1; i < kPdLayers; ++i) ws = std::max(ws, pd_wgrad_scratch_floats(B, kPdCh[i], kPdCh[i + 1], g.H[i + 1], p));
         for (int i = 0; i <= kPdLayers; ++i) wmax = std::max(wmax, (size_t)pd_wnumel(i));
     }
-    off = 0;
-    const size_t o_d0 = want(widest), o_d1 = want(widest), o_dw = want(wmax), o_ws = want(ws),
-                 o_l0 = want(grad_flat ? pd_l0_scratch_floats(B, g.H[1], p) : 0);
-    if ((rc = sd_train_grow(e, &st->scr, &st->scr_cap, off * 4))) return rc;
+    FloatArena ar;
+    const size_t o_d0 = ar.want(A.widest), o_d1 = ar.want(A.widest), o_dw = ar.want(wmax), o_ws = ar.want(ws),
+                 o_l0 = ar.want(grad_flat ? pd_l0_scratch_floats(B, g.H[1], p) : 0);
+    if ((rc = sd_train_grow(e, &st->scr, &st->scr_cap, ar.off * 4))) return rc;
     float* scr = (float*)st->scr;
     float* D = scr + o_d0; float* Dn = scr + o_d1; float* dW = scr + o_dw; float* wsp = scr + o_ws; float* l0p = scr + o_l0;
 

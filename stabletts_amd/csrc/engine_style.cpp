@@ -105,11 +105,11 @@ int st_style_encoder_forward(st_engine* e, const float* mel, const float* mask, 
     hipStream_t s = (hipStream_t)stream;
 
     // workspace: two hidden planes, the GLU / q-k-v plane, the fc output (all (B, C, T) fp32)
-    size_t off = 0;
-    auto want = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_h1 = want((size_t)R * Hd * 4), o_h2 = want((size_t)R * Hd * 4), o_u = want((size_t)R * 3 * Hd * 4), o_f = want((size_t)R * O * 4);
-    if ((rc = ensure_ws(e, off))) return rc;
-    float* h1 = (float*)(e->ws + o_h1); float* h2 = (float*)(e->ws + o_h2); float* u = (float*)(e->ws + o_u); float* f = (float*)(e->ws + o_f);
+    FloatArena ar;
+    const size_t o_h1 = ar.want((size_t)R * Hd), o_h2 = ar.want((size_t)R * Hd), o_u = ar.want((size_t)R * 3 * Hd), o_f = ar.want((size_t)R * O);
+    if ((rc = ensure_ws(e, ar.off * 4))) return rc;
+    float* ws = (float*)e->ws;
+    float* h1 = ws + o_h1; float* h2 = ws + o_h2; float* u = ws + o_u; float* f = ws + o_f;
 
     auto conv = [&](const float* in, int cin, const std::string& w, const std::string& b, int cout, int taps, int epi, float* out) {
         SdConvArgs a; a.in = in; a.Cin = cin; a.w = P(e, w); a.bias = P(e, b); a.out = out; a.Cout = cout;
@@ -148,14 +148,13 @@ struct StyleActs {      // float offsets into SdTrain::act; R = B * T
 StyleActs style_acts(const st_style_encoder_config& c, int B, int T) {
     const size_t R = (size_t)B * T, Hd = c.style_hidden;
     StyleActs a{};
-    size_t off = 0;
-    auto want = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
-    a.mel = want(R * c.n_mel_channels); a.mask = want(R);
-    a.pre1 = want(R * Hd); a.h1 = want(R * Hd); a.pre2 = want(R * Hd); a.g0 = want(R * Hd);
-    a.u0 = want(R * 2 * Hd); a.g1 = want(R * Hd); a.u1 = want(R * 2 * Hd); a.g2 = want(R * Hd);
-    a.qkv = want(R * 3 * Hd); a.att = want(R * Hd); a.stats = want(2 * R * c.style_head); a.ao = want(R * Hd);
-    a.f = want(R * c.style_vector_dim);
-    a.end = off;
+    FloatArena ar;
+    a.mel = ar.want(R * c.n_mel_channels); a.mask = ar.want(R);
+    a.pre1 = ar.want(R * Hd); a.h1 = ar.want(R * Hd); a.pre2 = ar.want(R * Hd); a.g0 = ar.want(R * Hd);
+    a.u0 = ar.want(R * 2 * Hd); a.g1 = ar.want(R * Hd); a.u1 = ar.want(R * 2 * Hd); a.g2 = ar.want(R * Hd);
+    a.qkv = ar.want(R * 3 * Hd); a.att = ar.want(R * Hd); a.stats = ar.want(2 * R * c.style_head); a.ao = ar.want(R * Hd);
+    a.f = ar.want(R * c.style_vector_dim);
+    a.end = ar.off;
     return a;
 }
 
@@ -239,11 +238,10 @@ int st_style_encoder_train_backward(st_engine* e, int64_t serial, int B, int T, 
     ws = std::max(ws, sd_wgrad_scratch_floats(B, Hd, 2 * Hd, T, K));
     ws = std::max(ws, sd_wgrad_scratch_floats(B, Hd, Hd, T, 1));
     ws = std::max(ws, sd_wgrad_scratch_floats(B, I, Hd, T, 1));
-    size_t off = 0;
-    auto want = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
-    const size_t o_dF = want(R * O), o_x = want(R * Hd), o_y = want(R * Hd), o_z = want(R * Hd), o_d3 = want(R * 3 * Hd),
-                 o_ds = want(R * NH), o_ws = want(ws);
-    if ((rc = sd_train_grow(e, &st->scr, &st->scr_cap, off * 4))) return rc;
+    FloatArena ar;
+    const size_t o_dF = ar.want(R * O), o_x = ar.want(R * Hd), o_y = ar.want(R * Hd), o_z = ar.want(R * Hd), o_d3 = ar.want(R * 3 * Hd),
+                 o_ds = ar.want(R * NH), o_ws = ar.want(ws);
+    if ((rc = sd_train_grow(e, &st->scr, &st->scr_cap, ar.off * 4))) return rc;
     float* scr = (float*)st->scr;
     float* dF = scr + o_dF; float* X = scr + o_x; float* Y = scr + o_y; float* Z = scr + o_z; float* D3 = scr + o_d3;
     float* dsum = scr + o_ds; float* wsp = scr + o_ws;

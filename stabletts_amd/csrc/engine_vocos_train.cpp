@@ -41,16 +41,15 @@ struct VtActs {         // float offsets into SdTrain::act
 
 VtActs vt_acts(const VtCfg& c, int64_t R) {
     VtActs a{};
-    size_t off = 0;
-    auto want = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
-    a.cols = want((size_t)7 * c.M * R); a.e0 = want((size_t)c.C * R); a.st0 = want(2 * R);
-    a.x = want((size_t)(c.L + 1) * c.C * R);          // x_0 .. x_L, C * R apart
-    a.blk = off;
-    a.b_st = want(2 * R) - a.blk; a.b_h = want((size_t)c.C * R) - a.blk; a.b_u = want((size_t)c.F * R) - a.blk; a.b_y2 = want((size_t)c.C * R) - a.blk;
-    a.blk_stride = off - a.blk;
-    off = a.blk + a.blk_stride * c.L;
-    a.stf = want(2 * R); a.hf = want((size_t)c.C * R); a.hrows = want((size_t)R * 2 * kVocHeadPlane);
-    a.end = off;
+    FloatArena ar;
+    a.cols = ar.want((size_t)7 * c.M * R); a.e0 = ar.want((size_t)c.C * R); a.st0 = ar.want(2 * R);
+    a.x = ar.want((size_t)(c.L + 1) * c.C * R);          // x_0 .. x_L, C * R apart
+    a.blk = ar.off;
+    a.b_st = ar.want(2 * R) - a.blk; a.b_h = ar.want((size_t)c.C * R) - a.blk; a.b_u = ar.want((size_t)c.F * R) - a.blk; a.b_y2 = ar.want((size_t)c.C * R) - a.blk;
+    a.blk_stride = ar.off - a.blk;
+    ar.off = a.blk + a.blk_stride * c.L;
+    a.stf = ar.want(2 * R); a.hf = ar.want((size_t)c.C * R); a.hrows = ar.want((size_t)R * 2 * kVocHeadPlane);
+    a.end = ar.off;
     return a;
 }
 
@@ -83,10 +82,9 @@ int st_vocos_train_forward(st_engine* e, const float* mel, float* audio, int B, 
     float* act = (float*)st->act;
     auto at = [&](size_t o) { return act + o; };
     // transients: the dwconv output, the GELU output, the channel-major head output, the windowed frames
-    size_t off = 0;
-    auto want = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
-    const size_t o_z = want((size_t)C * R), o_g = want((size_t)F * R), o_o = want((size_t)c.NB * R), o_fr = want((size_t)R * kVocNfft);
-    if ((rc = sd_train_grow(e, &st->scr, &st->scr_cap, off * 4))) return rc;
+    FloatArena ar;
+    const size_t o_z = ar.want((size_t)C * R), o_g = ar.want((size_t)F * R), o_o = ar.want((size_t)c.NB * R), o_fr = ar.want((size_t)R * kVocNfft);
+    if ((rc = sd_train_grow(e, &st->scr, &st->scr_cap, ar.off * 4))) return rc;
     float* scr = (float*)st->scr;
     float* z = scr + o_z; float* g = scr + o_g; float* o = scr + o_o; float* frames = scr + o_fr;
 
@@ -149,14 +147,13 @@ int st_vocos_train_backward(st_engine* e, const float* d_audio, float* d_mel, fl
     ws = std::max(ws, sd_wgrad_scratch_floats(1, F, C, Ri, 1));
     ws = std::max(ws, sd_wgrad_scratch_floats(1, C, F, Ri, 1));
     ws = std::max(ws, sd_wgrad_scratch_floats(1, 7 * M, C, Ri, 1));
-    size_t off = 0;
-    auto want = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
+    FloatArena ar;
     // d head rows and (later) d cols share one region; d head output channel-major; GELU output; d u, which later takes the C-wide
     // d z as well (so max(F, C) rows: intermediate_dim may be below dim); three C-wide planes; the split-K planes
     const size_t big = std::max((size_t)R * 2 * kVocHeadPlane, d_mel ? (size_t)7 * M * R : 0);
-    const size_t o_dh = want(big), o_do = want((size_t)NB * R), o_g = want((size_t)F * R), o_du = want((size_t)std::max(F, C) * R),
-                 o_x = want((size_t)C * R), o_y = want((size_t)C * R), o_z = want((size_t)C * R), o_ws = want(ws);
-    if ((rc = sd_train_grow(e, &st->scr, &st->scr_cap, off * 4))) return rc;
+    const size_t o_dh = ar.want(big), o_do = ar.want((size_t)NB * R), o_g = ar.want((size_t)F * R), o_du = ar.want((size_t)std::max(F, C) * R),
+                 o_x = ar.want((size_t)C * R), o_y = ar.want((size_t)C * R), o_z = ar.want((size_t)C * R), o_ws = ar.want(ws);
+    if ((rc = sd_train_grow(e, &st->scr, &st->scr_cap, ar.off * 4))) return rc;
     float* scr = (float*)st->scr;
     float* dH = scr + o_dh; float* dO = scr + o_do; float* g = scr + o_g; float* dU = scr + o_du;
     float* X = scr + o_x; float* Y = scr + o_y; float* Z = scr + o_z; float* wsp = scr + o_ws;

@@ -1,46 +1,37 @@
 // Period-discriminator kernels (vocoders/vocos/models/discriminator.py:32-75): forward, data gradient and weight gradient of the
 // (5, 1) convs with stride (3, 1) / (1, 1) on (B, C, H, p) tensors, layer 0 with the reflect tail padding, conv_post and the
 // weight norm.  fp32 throughout.  Layers 1-4 are GEMMs (M = Cout, K = Cin x taps, N = B Hout p) on the fp32-input MFMA
-// (v_mfma_f32_32x32x2_f32: a k-ordered fp32 FMA chain) with the 64 x 64 tile and the wave / lane mapping of sd_conv_kernel and
-// sd_wgrad_kernel (style_dp_kernels.hip, style_dp_bwd.hip); what differs is the operand staging, which gathers the strided rows
-// of the period view into an im2col chunk in LDS.  No atomics anywhere: every reduction has a fixed order.
+// (v_mfma_f32_32x32x2_f32: a k-ordered fp32 FMA chain) on the 64 x 64 tile of fp32_tile.h, which sd_conv_kernel
+// (style_dp_kernels.hip) shares; the operand staging is this file's own: it gathers the strided rows of the period view into an
+// im2col chunk in LDS.  No atomics anywhere: every reduction has a fixed order.
+#include "fp32_tile.h"
 #include "period_disc_launch.h"
 
 #include <math.h>
 
 namespace st {
 
-typedef __attribute__((ext_vector_type(16))) float pd_f32x16;
-
-constexpr int kPdTile = 64, kPdChunk = 16;      // output tile 64 channels x 64 frames, 16 input channels per K step
 enum PdMode { PD_FWD = 0, PD_DGRAD = 1 };
 
 // Tile families of one launch: family c owns blockIdx.x in [tile0[c], tile0[c + 1]).  Forward: one family.  Data gradient: one
 // per residue class q = (hi + 2) % stride of the input rows; its rows are hi = hi0 + stride m and its taps j = q + stride u.
 struct PdFamilies { int n = 0; int tile0[4] = {0, 0, 0, 0}; int q[3] = {0, 0, 0}; int hi0[3] = {0, 0, 0}; int rows[3] = {0, 0, 0}; };
 
-static unsigned pd_grid(int64_t n) {
-    const int64_t b = (n + 255) / 256;
-    return (unsigned)(b < 4096 ? (b > 0 ? b : 1) : 4096);
-}
-
-// One block = 4 waves = a 64 (channel) x 64 (frame) output tile of one item; wave w owns channels 32 (w & 1), frames 32 (w >> 1).
-// K = (input channel, tap) pairs, 16 channels x NT taps per LDS chunk, in the weight's own order.  MFMA operands as
-// sd_conv_kernel: lane l holds A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31]; D: row (r & 3) + 8 (r >> 2) + 4 (l >> 5).
-// Xs is the im2col chunk [k][frame]: a thread stages one frame column (256 % 64 == 0), so the frame -> (row, w) division
-// happens once per thread.
+// One block = a 64 (channel) x 64 (frame) output tile of one item on fp32_tile.h's wave / lane mapping.  K = (input channel, tap)
+// pairs, 16 channels x NT taps per LDS chunk, in the weight's own order.  Xs is the im2col chunk [k][frame]: a thread stages one
+// frame column (256 % 64 == 0), so the frame -> (row, w) division happens once per thread.
 template <int NT, int MODE>
 __global__ __launch_bounds__(256) void pd_conv_kernel(PdConvArgs a, PdFamilies fam) {
-    constexpr int KC = kPdChunk * NT, WS = KC + 1;
-    __shared__ float Ws[kPdTile * WS];
-    __shared__ float Xs[KC * kPdTile];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, hh = lane >> 5, wco = wave & 1, wt = wave >> 1;
-    const int co0 = blockIdx.y * kPdTile, b = blockIdx.z;
+    constexpr int KC = kTileChunk * NT, WS = KC + 1;
+    __shared__ float Ws[kTile * WS];
+    __shared__ float Xs[KC * kTile];
+    const int tid = threadIdx.x;
+    const TileLane l = tile_lane();
+    const int co0 = blockIdx.y * kTile, b = blockIdx.z;
     const int Cin = a.Cin, Cout = a.Cout, Hin = a.Hin, Hout = a.Hout, p = a.p, st = a.stride;
     int c = 0;
     while (c + 1 < fam.n && (int)blockIdx.x >= fam.tile0[c + 1]) ++c;
-    const int q = fam.q[c], n0 = ((int)blockIdx.x - fam.tile0[c]) * kPdTile;
+    const int q = fam.q[c], n0 = ((int)blockIdx.x - fam.tile0[c]) * kTile;
     const int rows = MODE == PD_FWD ? Hout : fam.rows[c];         // rows of this family, p frames each
     // the frame this thread stages: output row (forward) / input-gradient row of the family (data gradient)
     const int fs = tid & 63;
@@ -50,19 +41,18 @@ __global__ __launch_bounds__(256) void pd_conv_kernel(PdConvArgs a, PdFamilies f
     const int src0 = MODE == PD_FWD ? st * ms - kPdTaps / 2 : (fam.hi0[c] + st * ms + kPdTaps / 2 - q) / st;
     const int dsrc = MODE == PD_FWD ? 1 : -1;
     const float* inb = a.in + (size_t)b * Cin * Hin * p;
-    pd_f32x16 acc;
-    for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-    for (int ci0 = 0; ci0 < Cin; ci0 += kPdChunk) {
+    f32x16 acc = tile_zero();
+    for (int ci0 = 0; ci0 < Cin; ci0 += kTileChunk) {
         if constexpr (MODE == PD_FWD) {
-            for (int i = tid; i < kPdTile * KC; i += 256) {
+            for (int i = tid; i < kTile * KC; i += 256) {
                 const int row = i / KC, kk = i - row * KC;
                 const int co = co0 + row, ci = ci0 + kk / NT;
                 Ws[row * WS + kk] = (co < Cout && ci < Cin) ? a.w[((size_t)co * Cin + ci0) * kPdTaps + kk] : 0.0f;
             }
         } else {
             // w[co_fwd = ci][ci_fwd = co][j], j = q + stride u; the output channel runs fastest across the lanes
-            for (int i = tid; i < kPdTile * KC; i += 256) {
-                const int kk = i / kPdTile, row = i - kk * kPdTile;
+            for (int i = tid; i < kTile * KC; i += 256) {
+                const int kk = i / kTile, row = i - kk * kTile;
                 const int cl = kk / NT, u = kk - cl * NT;
                 const int co = co0 + row, ci = ci0 + cl;
                 Ws[row * WS + kk] = (co < Cout && ci < Cin) ? a.w[((size_t)ci * Cout + co) * kPdTaps + q + st * u] : 0.0f;
@@ -73,36 +63,30 @@ __global__ __launch_bounds__(256) void pd_conv_kernel(PdConvArgs a, PdFamilies f
             const int ci = ci0 + cl, src = src0 + dsrc * u;
             float v = 0.0f;
             if (s_ok && ci < Cin && src >= 0 && src < Hin) v = inb[((size_t)ci * Hin + src) * p + wsx];
-            Xs[kk * kPdTile + fs] = v;
+            Xs[kk * kTile + fs] = v;
         }
         __syncthreads();
-#pragma unroll 8
-        for (int kk = 0; kk < KC; kk += 2) {
-            const float av = Ws[(wco * 32 + r) * WS + kk + hh];
-            const float bv = Xs[(kk + hh) * kPdTile + wt * 32 + r];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
-        }
+        tile_mfma<KC, 8>(acc, Ws, WS, l, [&](int k, int col) { return Xs[k * kTile + col]; });
         __syncthreads();
     }
-    const int n = n0 + wt * 32 + r, m = n / p, w = n - m * p;
+    const int n = n0 + l.wt * 32 + l.r, m = n / p, w = n - m * p;
     if (m >= rows) return;
     const int orow = MODE == PD_FWD ? m : fam.hi0[c] + st * m;
-    for (int i = 0; i < 16; ++i) {
-        const int co = co0 + wco * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
-        if (co >= Cout) continue;
+    tile_for_each(acc, l, [&](int row, float v) {
+        const int co = co0 + row;
+        if (co >= Cout) return;
         const size_t o = (((size_t)b * Cout + co) * Hout + orow) * p + w;
         if constexpr (MODE == PD_FWD) {
-            float v = acc[i] + a.bias[co];
+            v += a.bias[co];
             v = v > 0.0f ? v : v * a.slope;
             a.out[o] = v;
             if (a.out2) a.out2[o] = v;
         } else {
-            float v = acc[i];
             if (a.addg) v += a.addg[o];
             if (a.act) v *= a.act[o] > 0.0f ? 1.0f : a.slope;
             a.out[o] = v;
         }
-    }
+    });
 }
 
 static bool pd_conv_args_ok(const PdConvArgs& a) {
@@ -115,8 +99,8 @@ hipError_t launch_pd_conv(const PdConvArgs& a, hipStream_t s) {
     if (a.Hout != (a.Hin - 1) / a.stride + 1) return hipErrorInvalidValue;
     PdFamilies fam;
     fam.n = 1;
-    fam.tile0[1] = (a.Hout * a.p + kPdTile - 1) / kPdTile;
-    const dim3 grid(fam.tile0[1], (a.Cout + kPdTile - 1) / kPdTile, a.B), blk(256);
+    fam.tile0[1] = (a.Hout * a.p + kTile - 1) / kTile;
+    const dim3 grid(fam.tile0[1], (a.Cout + kTile - 1) / kTile, a.B), blk(256);
     hipLaunchKernelGGL((pd_conv_kernel<kPdTaps, PD_FWD>), grid, blk, 0, s, a, fam);
     return hipGetLastError();
 }
@@ -124,11 +108,11 @@ hipError_t launch_pd_conv(const PdConvArgs& a, hipStream_t s) {
 hipError_t launch_pd_conv_dgrad(const PdConvArgs& a, hipStream_t s) {
     if (!pd_conv_args_ok(a)) return hipErrorInvalidValue;
     if (a.Hin != (a.Hout - 1) / a.stride + 1) return hipErrorInvalidValue;       // a.Hin = the forward's output rows
-    const int st = a.stride, cy = (a.Cout + kPdTile - 1) / kPdTile;
+    const int st = a.stride, cy = (a.Cout + kTile - 1) / kTile;
     if (st == 1) {
         PdFamilies fam;
         fam.n = 1; fam.rows[0] = a.Hout;
-        fam.tile0[1] = (a.Hout * a.p + kPdTile - 1) / kPdTile;
+        fam.tile0[1] = (a.Hout * a.p + kTile - 1) / kTile;
         hipLaunchKernelGGL((pd_conv_kernel<kPdTaps, PD_DGRAD>), dim3(fam.tile0[1], cy, a.B), dim3(256), 0, s, a, fam);
         return hipGetLastError();
     }
@@ -140,7 +124,7 @@ hipError_t launch_pd_conv_dgrad(const PdConvArgs& a, hipStream_t s) {
         PdFamilies& f = q < 2 ? two : one;
         const int k = f.n++;
         f.q[k] = q; f.hi0[k] = hi0; f.rows[k] = rows;
-        f.tile0[k + 1] = f.tile0[k] + (rows * a.p + kPdTile - 1) / kPdTile;
+        f.tile0[k + 1] = f.tile0[k] + (rows * a.p + kTile - 1) / kTile;
     }
     if (two.tile0[two.n] > 0) hipLaunchKernelGGL((pd_conv_kernel<2, PD_DGRAD>), dim3(two.tile0[two.n], cy, a.B), dim3(256), 0, s, a, two);
     if (one.tile0[one.n] > 0) hipLaunchKernelGGL((pd_conv_kernel<1, PD_DGRAD>), dim3(one.tile0[one.n], cy, a.B), dim3(256), 0, s, a, one);
@@ -148,108 +132,37 @@ hipError_t launch_pd_conv_dgrad(const PdConvArgs& a, hipStream_t s) {
 }
 
 // ---- weight gradient: dW[co][n] = sum_f dY[f][co] X'[f][n], n = ci * 5 + j, f = (b, h, w) --------------------------------
-// One block = a 64 (co) x 64 (n) tile of one split (blockIdx.z): frames [s * fs, min((s + 1) * fs, B Hout p)), 32 per LDS chunk;
-// the tile, wave and lane mapping of sd_wgrad_kernel.  A thread stages one frame column of both operands (256 % 32 == 0).
-constexpr int kPdWgChunk = 32, kPdWgMaxSplits = 32;
-
-static int pd_wgrad_split(int64_t frames, int tiles, int* fs) {
-    // fixed by the shape alone (deterministic), the rule of sd_wgrad_split: ~256 blocks, each split >= 128 frames
-    int S = (int)((256 + tiles - 1) / tiles);
-    const int64_t by_len = (frames + 127) / 128;
-    if (S > by_len) S = (int)by_len;
-    if (S > kPdWgMaxSplits) S = kPdWgMaxSplits;
-    if (S < 1) S = 1;
-    int64_t f = (frames + S - 1) / S;
-    f = (f + kPdWgChunk - 1) / kPdWgChunk * kPdWgChunk;
-    *fs = (int)f;
-    return (int)((frames + f - 1) / f);
-}
+// fp32_tile.h's split-K kernel on the frames (b, h, w) of the period view; X' gathers the strided rows, zero outside [0, Hin).
+struct PdWgradSrc {
+    PdWgradArgs a;
+    struct Frame { int b, n, h, w; };
+    __host__ __device__ int cout() const { return a.Cout; }
+    __host__ __device__ int n() const { return a.Cin * kPdTaps; }
+    __host__ __device__ int No() const { return a.Hout * a.p; }      // frames of one item
+    __host__ __device__ int64_t frames() const { return (int64_t)a.B * No(); }
+    __device__ Frame frame(int64_t f) const {
+        const int b = (int)(f / No()), nf = (int)(f - (int64_t)b * No()), h = nf / a.p;
+        return {b, nf, h, nf - h * a.p};
+    }
+    __device__ float dy(Frame f, int co) const { return a.dy[((size_t)f.b * a.Cout + co) * No() + f.n]; }
+    __device__ float x(Frame f, int nn) const {
+        const int ci = nn / kPdTaps, src = a.stride * f.h + (nn - ci * kPdTaps) - kPdTaps / 2;
+        return src >= 0 && src < a.Hin ? a.in[(((size_t)f.b * a.Cin + ci) * a.Hin + src) * a.p + f.w] : 0.0f;
+    }
+};
 
 int pd_wgrad_planes(int B, int Cin, int Cout, int Hout, int p) {
-    const int N = Cin * kPdTaps;
-    const int tiles = ((Cout + 63) / 64) * ((N + 63) / 64);
     int fs = 0;
-    return pd_wgrad_split((int64_t)B * Hout * p, tiles, &fs);
+    return wgrad_split((int64_t)B * Hout * p, Cout, Cin * kPdTaps, &fs);
 }
 
-size_t pd_wgrad_scratch_floats(int B, int Cin, int Cout, int Hout, int p) {
-    const int S = pd_wgrad_planes(B, Cin, Cout, Hout, p);
-    return S > 1 ? (size_t)S * Cout * Cin * kPdTaps : 0;
-}
-
-__global__ __launch_bounds__(256) void pd_wgrad_kernel(PdWgradArgs a, int fs, float* __restrict__ dst) {
-    constexpr int LS = kPdWgChunk + 1;
-    __shared__ float Ys[64 * LS];
-    __shared__ float Xs[64 * LS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, hh = lane >> 5, wco = wave & 1, wn = wave >> 1;
-    const int n0 = blockIdx.x * 64, co0 = blockIdx.y * 64, s = blockIdx.z;
-    const int Cin = a.Cin, Cout = a.Cout, Hin = a.Hin, p = a.p, N = Cin * kPdTaps, No = a.Hout * p;
-    const int64_t F = (int64_t)a.B * No, f_lo = (int64_t)s * fs, f_hi = f_lo + fs < F ? f_lo + fs : F;
-    const int kf = tid & 31;
-    pd_f32x16 acc;
-    for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-    for (int64_t f0 = f_lo; f0 < f_hi; f0 += kPdWgChunk) {
-        const int64_t f = f0 + kf;
-        const bool ok = f < f_hi;
-        const int b = ok ? (int)(f / No) : 0, n = ok ? (int)(f - (int64_t)b * No) : 0;
-        const int h = n / p, w = n - h * p;
-        for (int row = tid >> 5; row < 64; row += 8) {
-            float yv = 0.0f, xv = 0.0f;
-            if (ok) {
-                const int co = co0 + row;
-                if (co < Cout) yv = a.dy[((size_t)b * Cout + co) * No + n];
-                const int nn = n0 + row;
-                if (nn < N) {
-                    const int ci = nn / kPdTaps, src = a.stride * h + (nn - ci * kPdTaps) - kPdTaps / 2;
-                    if (src >= 0 && src < Hin) xv = a.in[(((size_t)b * Cin + ci) * Hin + src) * p + w];
-                }
-            }
-            Ys[row * LS + kf] = yv;
-            Xs[row * LS + kf] = xv;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < kPdWgChunk; kk += 2) {
-            const float av = Ys[(wco * 32 + r) * LS + kk + hh];
-            const float bv = Xs[(wn * 32 + r) * LS + kk + hh];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    const int n = n0 + wn * 32 + r;
-    if (n >= N) return;
-    float* out = dst + (size_t)s * Cout * N;
-    for (int i = 0; i < 16; ++i) {
-        const int co = co0 + wco * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
-        if (co < Cout) out[(size_t)co * N + n] = acc[i];
-    }
-}
-
-__global__ __launch_bounds__(256) void pd_sum_planes_kernel(const float* __restrict__ planes, float* __restrict__ out, int S, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        float v = planes[i];
-        for (int s = 1; s < S; ++s) v += planes[(size_t)s * n + i];
-        out[i] = v;
-    }
-}
+size_t pd_wgrad_scratch_floats(int B, int Cin, int Cout, int Hout, int p) { return wgrad_scratch_floats((int64_t)B * Hout * p, Cout, Cin * kPdTaps); }
 
 hipError_t launch_pd_wgrad(const PdWgradArgs& a, hipStream_t st) {
     if (a.B < 1 || a.Cin < 1 || a.Cout < 1 || a.Hin < 1 || a.Hout < 1 || a.p < 1 || (a.stride != 1 && a.stride != 3) || !a.dy || !a.in || !a.dw)
         return hipErrorInvalidValue;
     if (a.Hout != (a.Hin - 1) / a.stride + 1 || (int64_t)a.Hout * a.p >= ((int64_t)1 << 30)) return hipErrorInvalidValue;
-    const int N = a.Cin * kPdTaps;
-    const int tiles = ((a.Cout + 63) / 64) * ((N + 63) / 64);
-    int fs = 0;
-    const int S = pd_wgrad_split((int64_t)a.B * a.Hout * a.p, tiles, &fs);
-    if (S > 1 && !a.scratch) return hipErrorInvalidValue;
-    float* dst = S > 1 ? a.scratch : a.dw;
-    hipLaunchKernelGGL(pd_wgrad_kernel, dim3((N + 63) / 64, (a.Cout + 63) / 64, S), dim3(256), 0, st, a, fs, dst);
-    if (S > 1) {
-        const int64_t n = (int64_t)a.Cout * N;
-        hipLaunchKernelGGL(pd_sum_planes_kernel, dim3(pd_grid(n)), dim3(256), 0, st, a.scratch, a.dw, S, n);
-    }
-    return hipGetLastError();
+    return launch_wgrad(PdWgradSrc{a}, a.dw, a.scratch, st);
 }
 
 // ---- layer 0 ---------------------------------------------------------------------------------------------------------------
@@ -457,7 +370,7 @@ hipError_t launch_pd_post_dgrad(const float* dy, const float* w, const float* ac
                                 float slope, hipStream_t s) {
     if (!w || !act || !dpre || B < 1 || C < 1 || H < 1 || p < 1) return hipErrorInvalidValue;
     const int64_t total = (int64_t)B * C * H * p;
-    hipLaunchKernelGGL(pd_post_dgrad_kernel, dim3(pd_grid(total)), dim3(256), 0, s, dy, w, act, addg, dpre, C, H, p, slope, total);
+    hipLaunchKernelGGL(pd_post_dgrad_kernel, dim3(grid_1d(total, 4096)), dim3(256), 0, s, dy, w, act, addg, dpre, C, H, p, slope, total);
     return hipGetLastError();
 }
 
@@ -507,13 +420,7 @@ __global__ __launch_bounds__(256) void pd_weight_norm_kernel(const float* __rest
     const float* vr = v + (size_t)co * n;
     float ss = 0.0f;
     for (int i = tid; i < n; i += 256) ss = fmaf(vr[i], vr[i], ss);
-    red[tid] = ss;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (tid < k) red[tid] += red[tid + k];
-        __syncthreads();
-    }
-    const float scale = g[co] / sqrtf(red[0]);
+    const float scale = g[co] / sqrtf(block_sum256(red, ss));
     for (int i = tid; i < n; i += 256) w[(size_t)co * n + i] = vr[i] * scale;
 }
 

@@ -1,16 +1,15 @@
 // Training kernels of the MelStyleEncoder and the DurationPredictor (models/reference_encoder.py:22-93,
 // models/duration_predictor.py:5-37): the row work of the training forward (activations kept, dropout applied) and the backward.
 // fp32 throughout, as the inference forward (style_dp_kernels.hip); the data gradients of the convs are that file's tile kernel
-// (launch_sd_conv_dgrad), the weight gradients a split-K TN GEMM on the fp32 MFMA here.  No atomics anywhere: every reduction
+// (launch_sd_conv_dgrad), the weight gradients fp32_tile.h's split-K TN GEMM on the fp32 MFMA.  No atomics anywhere: every reduction
 // has a fixed order, so gradients are bitwise reproducible from run to run.
+#include "fp32_tile.h"
 #include "style_dp_drop.h"
 #include "train_launch.h"
 
 #include <math.h>
 
 namespace st {
-
-typedef __attribute__((ext_vector_type(16))) float sd_f32x16;
 
 SdDrop sd_make_drop(float p, unsigned long long seed, int salt) {
     const DropCfg c = make_drop(p, seed, salt);
@@ -19,117 +18,37 @@ SdDrop sd_make_drop(float p, unsigned long long seed, int salt) {
     return d;
 }
 
-static unsigned sd_grid(int64_t n) {
-    const int64_t b = (n + 255) / 256;
-    return (unsigned)(b < 4096 ? (b > 0 ? b : 1) : 4096);
-}
-
 // ---- weight gradient: dW[co][n] = sum_f dY[f][co] X'[f][n], n = ci * taps + j, f = (b, t) -----------------------------------
-// One block = a 64 (co) x 64 (n) tile of one split s (blockIdx.z): frames [s * fs, min((s + 1) * fs, B * T)), 32 per LDS chunk.
-// Wave w owns co 32 (w & 1), n 32 (w >> 1); MFMA 32x32x2 f32 as sd_conv_kernel: A[i = co][k = frame], B[k = frame][j = n].
-constexpr int kWgChunk = 32, kWgMaxSplits = 32;
-
-static int sd_wgrad_split(int64_t frames, int tiles, int* fs) {
-    // fixed by the shape alone (deterministic): enough splits to give ~256 blocks, each split >= 128 frames
-    int S = (int)((256 + tiles - 1) / tiles);
-    const int64_t by_len = (frames + 127) / 128;
-    if (S > by_len) S = (int)by_len;
-    if (S > kWgMaxSplits) S = kWgMaxSplits;
-    if (S < 1) S = 1;
-    int64_t f = (frames + S - 1) / S;
-    f = (f + kWgChunk - 1) / kWgChunk * kWgChunk;
-    *fs = (int)f;
-    return (int)((frames + f - 1) / f);
-}
-
-size_t sd_wgrad_scratch_floats(int B, int Cin, int Cout, int T, int taps) {
-    const int N = Cin * taps;
-    const int tiles = ((Cout + 63) / 64) * ((N + 63) / 64);
-    int fs = 0;
-    const int S = sd_wgrad_split((int64_t)B * T, tiles, &fs);
-    return S > 1 ? (size_t)S * Cout * N : 0;
-}
-
+// fp32_tile.h's split-K kernel on the frames (b, t) of (B, C, T) tensors; X' = (in + addv) * imask, zero outside [0, T).
 template <int TAPS>
-__global__ __launch_bounds__(256) void sd_wgrad_kernel(SdWgradArgs a, int fs, float* __restrict__ dst) {
-    constexpr int PAD = TAPS / 2, LS = kWgChunk + 1;
-    __shared__ float Ys[64 * LS];
-    __shared__ float Xs[64 * LS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5, wco = wave & 1, wn = wave >> 1;
-    const int n0 = blockIdx.x * 64, co0 = blockIdx.y * 64, s = blockIdx.z;
-    const int Cin = a.Cin, Cout = a.Cout, T = a.T, N = Cin * TAPS;
-    const int64_t F = (int64_t)a.B * T, f_lo = (int64_t)s * fs, f_hi = f_lo + fs < F ? f_lo + fs : F;
-    sd_f32x16 acc;
-    for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-    for (int64_t f0 = f_lo; f0 < f_hi; f0 += kWgChunk) {
-        for (int i = tid; i < 64 * kWgChunk; i += 256) {
-            const int row = i / kWgChunk, kf = i - row * kWgChunk;
-            const int64_t f = f0 + kf;
-            float yv = 0.0f, xv = 0.0f;
-            if (f < f_hi) {
-                const int b = (int)(f / T), t = (int)(f - (int64_t)b * T);
-                const int co = co0 + row;
-                if (co < Cout) yv = a.dy[((size_t)b * Cout + co) * T + t];
-                const int n = n0 + row;
-                if (n < N) {
-                    const int ci = n / TAPS, tt = t + (n - ci * TAPS) - PAD;
-                    if (tt >= 0 && tt < T) {
-                        xv = a.in[((size_t)b * Cin + ci) * T + tt];
-                        if (a.addv) xv += a.addv[(size_t)b * Cin + ci];
-                        if (a.imask) xv *= a.imask[(size_t)b * T + tt];
-                    }
-                }
-            }
-            Ys[row * LS + kf] = yv;
-            Xs[row * LS + kf] = xv;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < kWgChunk; kk += 2) {
-            const float av = Ys[(wco * 32 + r) * LS + kk + h];
-            const float bv = Xs[(wn * 32 + r) * LS + kk + h];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
-        }
-        __syncthreads();
+struct SdWgradSrc {
+    SdWgradArgs a;
+    struct Frame { int b, t; };
+    __host__ __device__ int cout() const { return a.Cout; }
+    __host__ __device__ int n() const { return a.Cin * TAPS; }
+    __host__ __device__ int64_t frames() const { return (int64_t)a.B * a.T; }
+    __device__ Frame frame(int64_t f) const { const int b = (int)(f / a.T); return {b, (int)(f - (int64_t)b * a.T)}; }
+    __device__ float dy(Frame f, int co) const { return a.dy[((size_t)f.b * a.Cout + co) * a.T + f.t]; }
+    __device__ float x(Frame f, int nn) const {
+        const int ci = nn / TAPS, tt = f.t + (nn - ci * TAPS) - TAPS / 2;
+        if (tt < 0 || tt >= a.T) return 0.0f;
+        float xv = a.in[((size_t)f.b * a.Cin + ci) * a.T + tt];
+        if (a.addv) xv += a.addv[(size_t)f.b * a.Cin + ci];
+        if (a.imask) xv *= a.imask[(size_t)f.b * a.T + tt];
+        return xv;
     }
-    const int n = n0 + wn * 32 + r;
-    if (n >= N) return;
-    float* out = dst + (size_t)s * Cout * N;
-    for (int i = 0; i < 16; ++i) {
-        const int co = co0 + wco * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-        if (co < Cout) out[(size_t)co * N + n] = acc[i];
-    }
-}
+};
 
-__global__ __launch_bounds__(256) void sd_sum_planes_kernel(const float* __restrict__ planes, float* __restrict__ out, int S, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        float v = planes[i];
-        for (int s = 1; s < S; ++s) v += planes[(size_t)s * n + i];
-        out[i] = v;
-    }
-}
+size_t sd_wgrad_scratch_floats(int B, int Cin, int Cout, int T, int taps) { return wgrad_scratch_floats((int64_t)B * T, Cout, Cin * taps); }
 
 hipError_t launch_sd_wgrad(const SdWgradArgs& a, hipStream_t st) {
     if (a.B < 1 || a.T < 1 || a.Cin < 1 || a.Cout < 1 || !a.dy || !a.in || !a.dw) return hipErrorInvalidValue;
-    const int N = a.Cin * a.taps;
-    const int tiles = ((a.Cout + 63) / 64) * ((N + 63) / 64);
-    int fs = 0;
-    const int S = sd_wgrad_split((int64_t)a.B * a.T, tiles, &fs);
-    if (S > 1 && !a.scratch) return hipErrorInvalidValue;
-    float* dst = S > 1 ? a.scratch : a.dw;
-    const dim3 grid((N + 63) / 64, (a.Cout + 63) / 64, S), blk(256);
     switch (a.taps) {
-        case 1: hipLaunchKernelGGL(sd_wgrad_kernel<1>, grid, blk, 0, st, a, fs, dst); break;
-        case 3: hipLaunchKernelGGL(sd_wgrad_kernel<3>, grid, blk, 0, st, a, fs, dst); break;
-        case 5: hipLaunchKernelGGL(sd_wgrad_kernel<5>, grid, blk, 0, st, a, fs, dst); break;
+        case 1: return launch_wgrad(SdWgradSrc<1>{a}, a.dw, a.scratch, st);
+        case 3: return launch_wgrad(SdWgradSrc<3>{a}, a.dw, a.scratch, st);
+        case 5: return launch_wgrad(SdWgradSrc<5>{a}, a.dw, a.scratch, st);
         default: return hipErrorInvalidValue;
     }
-    if (S > 1) {
-        const int64_t n = (int64_t)a.Cout * N;
-        hipLaunchKernelGGL(sd_sum_planes_kernel, dim3(sd_grid(n)), dim3(256), 0, st, a.scratch, a.dw, S, n);
-    }
-    return hipGetLastError();
 }
 
 // ---- reductions over frames ----------------------------------------------------------------------------------------------
@@ -143,13 +62,8 @@ __global__ __launch_bounds__(256) void sd_sum_frames_kernel(const float* __restr
         const float* xr = x + ((size_t)b * C + c) * T;
         for (int t = tid; t < T; t += 256) v += xr[t];
     }
-    red[tid] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) out[per_item ? (size_t)blockIdx.y * C + c : (size_t)c] = red[0];
+    const float sum = block_sum256(red, v);
+    if (tid == 0) out[per_item ? (size_t)blockIdx.y * C + c : (size_t)c] = sum;
 }
 
 hipError_t launch_sd_sum_frames(const float* x, float* out, int B, int C, int T, int per_item, hipStream_t s) {
@@ -167,7 +81,7 @@ __global__ __launch_bounds__(256) void sd_mul_mask_kernel(const float* __restric
 
 hipError_t launch_sd_mul_mask(const float* x, const float* mask, float* y, int B, int C, int T, hipStream_t s) {
     const int64_t n = (int64_t)B * C * T;
-    hipLaunchKernelGGL(sd_mul_mask_kernel, dim3(sd_grid(n)), dim3(256), 0, s, x, mask, y, C, T, n);
+    hipLaunchKernelGGL(sd_mul_mask_kernel, dim3(grid_1d(n, 4096)), dim3(256), 0, s, x, mask, y, C, T, n);
     return hipGetLastError();
 }
 
@@ -189,12 +103,12 @@ __global__ __launch_bounds__(256) void sd_mish_bwd_kernel(const float* __restric
 
 hipError_t launch_sd_drop(float* x, const SdDrop& d, int64_t n, hipStream_t s) {
     if (!d.thresh16) return hipSuccess;      // p = 0: factor 1 everywhere
-    hipLaunchKernelGGL(sd_drop_kernel, dim3(sd_grid(n)), dim3(256), 0, s, x, d, n);
+    hipLaunchKernelGGL(sd_drop_kernel, dim3(grid_1d(n, 4096)), dim3(256), 0, s, x, d, n);
     return hipGetLastError();
 }
 
 hipError_t launch_sd_mish_bwd(const float* dout, const float* pre, float* dpre, const SdDrop& d, int64_t n, hipStream_t s) {
-    hipLaunchKernelGGL(sd_mish_bwd_kernel, dim3(sd_grid(n)), dim3(256), 0, s, dout, pre, dpre, d, n);
+    hipLaunchKernelGGL(sd_mish_bwd_kernel, dim3(grid_1d(n, 4096)), dim3(256), 0, s, dout, pre, dpre, d, n);
     return hipGetLastError();
 }
 
@@ -228,13 +142,13 @@ __global__ __launch_bounds__(256) void sd_glu_bwd_kernel(const float* __restrict
 
 hipError_t launch_sd_glu_train(const float* hin, const float* u, float* hout, const SdDrop& d, int B, int C, int T, hipStream_t s) {
     const int64_t n = (int64_t)B * C * T;
-    hipLaunchKernelGGL(sd_glu_train_kernel, dim3(sd_grid(n)), dim3(256), 0, s, hin, u, hout, d, C, T, n);
+    hipLaunchKernelGGL(sd_glu_train_kernel, dim3(grid_1d(n, 4096)), dim3(256), 0, s, hin, u, hout, d, C, T, n);
     return hipGetLastError();
 }
 
 hipError_t launch_sd_glu_bwd(const float* dh, const float* u, float* du, const SdDrop& d, int B, int C, int T, hipStream_t s) {
     const int64_t n = (int64_t)B * C * T;
-    hipLaunchKernelGGL(sd_glu_bwd_kernel, dim3(sd_grid(n)), dim3(256), 0, s, dh, u, du, d, C, T, n);
+    hipLaunchKernelGGL(sd_glu_bwd_kernel, dim3(grid_1d(n, 4096)), dim3(256), 0, s, dh, u, du, d, C, T, n);
     return hipGetLastError();
 }
 
@@ -473,13 +387,8 @@ __global__ __launch_bounds__(256) void sd_mean_pool_bwd_kernel(const float* __re
     const float* mb = mask ? mask + (size_t)b * T : nullptr;
     float n = 0.0f;
     for (int t = tid; t < T; t += 256) if (!mb || mb[t] != 0.0f) n += 1.0f;
-    scnt[tid] = n;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) scnt[tid] += scnt[tid + w];
-        __syncthreads();
-    }
-    const float g = scnt[0] > 0.0f ? dc[(size_t)b * O + o] / scnt[0] : 0.0f;
+    const float cnt = block_sum256(scnt, n);
+    const float g = cnt > 0.0f ? dc[(size_t)b * O + o] / cnt : 0.0f;
     float* xo = dx + ((size_t)b * O + o) * T;
     for (int t = tid; t < T; t += 256) xo[t] = (!mb || mb[t] != 0.0f) ? g : 0.0f;
 }

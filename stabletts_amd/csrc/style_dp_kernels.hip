@@ -3,37 +3,32 @@
 // one frame per 200-token utterance; the convolutions and linears therefore run on the fp32-input MFMA
 // (v_mfma_f32_32x32x2_f32: bit-for-bit a k-ordered fp32 FMA chain) instead of the 16-bit operands of the DiT blocks.
 // Tensors stay in the reference's channel-major layout (B, C, T); both modules run once per utterance and are small.
+#include "fp32_tile.h"
 #include "style_dp_drop.h"
 
 #include <math.h>
 
 namespace st {
 
-typedef __attribute__((ext_vector_type(16))) float sd_f32x16;
-
-constexpr int kSdTileCo = 64, kSdTileT = 64, kSdChunk = 16;     // output tile 64 channels x 64 frames, 16 input channels per K step
-
-// One block = 4 waves = a 64 x 64 output tile; wave w owns the 32 x 32 sub-tile (channels 32 (w & 1), frames 32 (w >> 1)).
-// K = (input channel, tap) pairs in the weight's own order, 16 channels x TAPS per LDS chunk; MFMA 32x32x2 f32 operands:
-// lane l holds A[i = l & 31][k = l >> 5] (weight row) and B[k = l >> 5][j = l & 31] (input frame); D: row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31.
+// One block = a 64 (channel) x 64 (frame) output tile on fp32_tile.h's wave / lane mapping.  K = (input channel, tap) pairs in
+// the weight's own order, 16 channels x TAPS per LDS chunk; the B operand is a halo tile [16][64 + TAPS - 1] of the input.
 // MODE (training, style_dp_bwd.hip) -- SD_MODE_FWD: the inference kernel.  SD_MODE_DGRAD: the data gradient of a conv whose
 // nn.Conv1d weight is W (Cin_fwd = a.Cout, Cout_fwd = a.Cin, TAPS): A is staged straight from W, transposed and tap-flipped,
 // W'[ci][co][j] = W[co][ci][TAPS - 1 - j]; no bias, no epilogue activation, a.res (if set) is added after the output mask.
 // SD_MODE_FWD_PRE: the inference kernel that also writes the pre-activation (acc + bias) to a.pre for the backward.
 template <int TAPS, int MODE>
 __global__ __launch_bounds__(256) void sd_conv_kernel(SdConvArgs a) {
-    constexpr int KC = kSdChunk * TAPS, WS = KC + 1, PAD = TAPS / 2, XS = kSdTileT + TAPS - 1;
-    __shared__ float Ws[kSdTileCo * WS];
-    __shared__ float Xs[kSdChunk * XS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5, wco = wave & 1, wt = wave >> 1;
-    const int t0 = blockIdx.x * kSdTileT, co0 = blockIdx.y * kSdTileCo, b = blockIdx.z;
+    constexpr int KC = kTileChunk * TAPS, WS = KC + 1, PAD = TAPS / 2, XS = kTile + TAPS - 1;
+    __shared__ float Ws[kTile * WS];
+    __shared__ float Xs[kTileChunk * XS];
+    const int tid = threadIdx.x;
+    const TileLane l = tile_lane();
+    const int t0 = blockIdx.x * kTile, co0 = blockIdx.y * kTile, b = blockIdx.z;
     const int Cin = a.Cin, Cout = a.Cout, T = a.T;
     const float* inb = a.in + (size_t)b * Cin * T;
-    sd_f32x16 acc;
-    for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-    for (int ci0 = 0; ci0 < Cin; ci0 += kSdChunk) {
-        for (int i = tid; i < kSdTileCo * KC; i += 256) {
+    f32x16 acc = tile_zero();
+    for (int ci0 = 0; ci0 < Cin; ci0 += kTileChunk) {
+        for (int i = tid; i < kTile * KC; i += 256) {
             const int row = i / KC, kk = i - row * KC;
             const int co = co0 + row, ci = ci0 + kk / TAPS;
             if constexpr (MODE == SD_MODE_DGRAD) {
@@ -43,7 +38,7 @@ __global__ __launch_bounds__(256) void sd_conv_kernel(SdConvArgs a) {
                 Ws[row * WS + kk] = (co < Cout && ci < Cin) ? a.w[((size_t)co * Cin + ci0) * TAPS + kk] : 0.0f;
             }
         }
-        for (int i = tid; i < kSdChunk * XS; i += 256) {
+        for (int i = tid; i < kTileChunk * XS; i += 256) {
             const int row = i / XS, j = i - row * XS;
             const int ci = ci0 + row, t = t0 + j - PAD;
             float v = 0.0f;
@@ -55,41 +50,35 @@ __global__ __launch_bounds__(256) void sd_conv_kernel(SdConvArgs a) {
             Xs[row * XS + j] = v;
         }
         __syncthreads();
-#pragma unroll 8
-        for (int kk = 0; kk < KC; kk += 2) {
-            const int k = kk + h, cil = k / TAPS, tap = k - cil * TAPS;
-            const float av = Ws[(wco * 32 + r) * WS + k];
-            const float bv = Xs[cil * XS + wt * 32 + r + tap];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
-        }
+        tile_mfma<KC, 8>(acc, Ws, WS, l, [&](int k, int col) { const int cil = k / TAPS; return Xs[cil * XS + col + (k - cil * TAPS)]; });
         __syncthreads();
     }
-    const int t = t0 + wt * 32 + r;
+    const int t = t0 + l.wt * 32 + l.r;
     if (t >= T) return;
     const float om = a.omask ? a.omask[(size_t)b * T + t] : 1.0f;
-    for (int i = 0; i < 16; ++i) {
-        const int co = co0 + wco * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-        if (co >= Cout) continue;
+    tile_for_each(acc, l, [&](int row, float sum) {
+        const int co = co0 + row;
+        if (co >= Cout) return;
+        const size_t o = ((size_t)b * Cout + co) * T + t;
         if constexpr (MODE == SD_MODE_DGRAD) {
-            const size_t o = ((size_t)b * Cout + co) * T + t;
-            a.out[o] = a.res ? acc[i] * om + a.res[o] : acc[i] * om;
-            continue;
+            a.out[o] = a.res ? sum * om + a.res[o] : sum * om;
+            return;
         }
-        float v = acc[i] + a.bias[co];
-        if constexpr (MODE == SD_MODE_FWD_PRE) a.pre[((size_t)b * Cout + co) * T + t] = v;
+        float v = sum + a.bias[co];
+        if constexpr (MODE == SD_MODE_FWD_PRE) a.pre[o] = v;
         if (a.epi == SD_EPI_MISH) {          // x * tanh(softplus(x)), softplus at torch's threshold 20
             const float sp = v > 20.0f ? v : log1pf(expf(v));
             v = v * tanhf(sp);
         } else if (a.epi == SD_EPI_RELU) {
             v = fmaxf(v, 0.0f);
         }
-        a.out[((size_t)b * Cout + co) * T + t] = v * om;
-    }
+        a.out[o] = v * om;
+    });
 }
 
 hipError_t launch_sd_conv(const SdConvArgs& a, hipStream_t s) {
     if (a.B < 1 || a.T < 1 || a.Cin < 1 || a.Cout < 1 || !a.in || !a.w || !a.bias || !a.out) return hipErrorInvalidValue;
-    const dim3 grid((a.T + kSdTileT - 1) / kSdTileT, (a.Cout + kSdTileCo - 1) / kSdTileCo, a.B), blk(256);
+    const dim3 grid((a.T + kTile - 1) / kTile, (a.Cout + kTile - 1) / kTile, a.B), blk(256);
     switch (a.taps) {
         case 1: hipLaunchKernelGGL((sd_conv_kernel<1, SD_MODE_FWD>), grid, blk, 0, s, a); break;
         case 3: hipLaunchKernelGGL((sd_conv_kernel<3, SD_MODE_FWD>), grid, blk, 0, s, a); break;
@@ -101,7 +90,7 @@ hipError_t launch_sd_conv(const SdConvArgs& a, hipStream_t s) {
 
 hipError_t launch_sd_conv_pre(const SdConvArgs& a, hipStream_t s) {
     if (a.B < 1 || a.T < 1 || a.Cin < 1 || a.Cout < 1 || !a.in || !a.w || !a.bias || !a.out || !a.pre) return hipErrorInvalidValue;
-    const dim3 grid((a.T + kSdTileT - 1) / kSdTileT, (a.Cout + kSdTileCo - 1) / kSdTileCo, a.B), blk(256);
+    const dim3 grid((a.T + kTile - 1) / kTile, (a.Cout + kTile - 1) / kTile, a.B), blk(256);
     switch (a.taps) {
         case 1: hipLaunchKernelGGL((sd_conv_kernel<1, SD_MODE_FWD_PRE>), grid, blk, 0, s, a); break;
         case 3: hipLaunchKernelGGL((sd_conv_kernel<3, SD_MODE_FWD_PRE>), grid, blk, 0, s, a); break;
@@ -113,7 +102,7 @@ hipError_t launch_sd_conv_pre(const SdConvArgs& a, hipStream_t s) {
 
 hipError_t launch_sd_conv_dgrad(const SdConvArgs& a, hipStream_t s) {
     if (a.B < 1 || a.T < 1 || a.Cin < 1 || a.Cout < 1 || !a.in || !a.w || !a.out || a.addv || a.imask) return hipErrorInvalidValue;
-    const dim3 grid((a.T + kSdTileT - 1) / kSdTileT, (a.Cout + kSdTileCo - 1) / kSdTileCo, a.B), blk(256);
+    const dim3 grid((a.T + kTile - 1) / kTile, (a.Cout + kTile - 1) / kTile, a.B), blk(256);
     switch (a.taps) {
         case 1: hipLaunchKernelGGL((sd_conv_kernel<1, SD_MODE_DGRAD>), grid, blk, 0, s, a); break;
         case 3: hipLaunchKernelGGL((sd_conv_kernel<3, SD_MODE_DGRAD>), grid, blk, 0, s, a); break;

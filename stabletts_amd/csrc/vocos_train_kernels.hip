@@ -3,16 +3,12 @@
 // Tensors are fp32 and channel-major over the flattened frames of the batch, (C, R) with R = B * T and r = b * T + t, so that
 // the lanes of a wave read consecutive frames.  The kernels that mix frames (embed im2col, depthwise conv, ISTFT) take T and
 // stay inside an item.  No atomics: every reduction is a per-thread strided sum followed by a fixed LDS tree.
+#include "fp32_tile.h"
 #include "vocos_train_launch.h"
 
 #include <math.h>
 
 namespace st {
-
-static unsigned vt_grid(int64_t n) {
-    const int64_t b = (n + 255) / 256;
-    return (unsigned)(b < 8192 ? (b > 0 ? b : 1) : 8192);
-}
 
 // ---------------------------------------------------------------- embed: im2col of the k = 7 conv and its transpose
 __global__ __launch_bounds__(256) void vt_im2col7_kernel(const float* __restrict__ mel, float* __restrict__ cols, int M, int T, int64_t R, int64_t n) {
@@ -42,13 +38,13 @@ __global__ __launch_bounds__(256) void vt_col2im7_kernel(const float* __restrict
 
 hipError_t launch_vt_im2col7(const float* mel, float* cols, int B, int M, int T, hipStream_t s) {
     const int64_t R = (int64_t)B * T, n = 7 * (int64_t)M * R;
-    hipLaunchKernelGGL(vt_im2col7_kernel, dim3(vt_grid(n)), dim3(256), 0, s, mel, cols, M, T, R, n);
+    hipLaunchKernelGGL(vt_im2col7_kernel, dim3(grid_1d(n, 8192)), dim3(256), 0, s, mel, cols, M, T, R, n);
     return hipGetLastError();
 }
 
 hipError_t launch_vt_col2im7(const float* dcols, float* dmel, int B, int M, int T, hipStream_t s) {
     const int64_t R = (int64_t)B * T, n = (int64_t)M * R;
-    hipLaunchKernelGGL(vt_col2im7_kernel, dim3(vt_grid(n)), dim3(256), 0, s, dcols, dmel, M, T, R, n);
+    hipLaunchKernelGGL(vt_col2im7_kernel, dim3(grid_1d(n, 8192)), dim3(256), 0, s, dcols, dmel, M, T, R, n);
     return hipGetLastError();
 }
 
@@ -119,14 +115,14 @@ __global__ __launch_bounds__(256) void vt_dwconv7_param_kernel(const float* __re
 
 hipError_t launch_vt_dwconv7(const float* x, const float* w, const float* bias, float* z, int C, int B, int T, hipStream_t s) {
     const int64_t R = (int64_t)B * T, n = (int64_t)C * R;
-    hipLaunchKernelGGL(vt_dwconv7_kernel, dim3(vt_grid(n)), dim3(256), 0, s, x, w, bias, z, T, R, n);
+    hipLaunchKernelGGL(vt_dwconv7_kernel, dim3(grid_1d(n, 8192)), dim3(256), 0, s, x, w, bias, z, T, R, n);
     return hipGetLastError();
 }
 
 hipError_t launch_vt_dwconv7_bwd(const float* dz, const float* x, const float* w, const float* dres, float* dx, float* dw, float* db,
                                  int C, int B, int T, hipStream_t s) {
     const int64_t R = (int64_t)B * T, n = (int64_t)C * R;
-    hipLaunchKernelGGL(vt_dwconv7_dx_kernel, dim3(vt_grid(n)), dim3(256), 0, s, dz, w, dres, dx, T, R, n);
+    hipLaunchKernelGGL(vt_dwconv7_dx_kernel, dim3(grid_1d(n, 8192)), dim3(256), 0, s, dz, w, dres, dx, T, R, n);
     hipLaunchKernelGGL(vt_dwconv7_param_kernel, dim3(C), dim3(256), 0, s, dz, x, dw, db, T, R);
     return hipGetLastError();
 }
@@ -150,12 +146,12 @@ __global__ __launch_bounds__(256) void vt_gelu_bwd_kernel(const float* dg, const
 }
 
 hipError_t launch_vt_gelu(const float* u, float* g, int64_t n, hipStream_t s) {
-    hipLaunchKernelGGL(vt_gelu_kernel, dim3(vt_grid(n)), dim3(256), 0, s, u, g, n);
+    hipLaunchKernelGGL(vt_gelu_kernel, dim3(grid_1d(n, 8192)), dim3(256), 0, s, u, g, n);
     return hipGetLastError();
 }
 
 hipError_t launch_vt_gelu_bwd(const float* dg, const float* u, float* du, int64_t n, hipStream_t s) {
-    hipLaunchKernelGGL(vt_gelu_bwd_kernel, dim3(vt_grid(n)), dim3(256), 0, s, dg, u, du, n);
+    hipLaunchKernelGGL(vt_gelu_bwd_kernel, dim3(grid_1d(n, 8192)), dim3(256), 0, s, dg, u, du, n);
     return hipGetLastError();
 }
 
@@ -178,18 +174,13 @@ __global__ __launch_bounds__(256) void vt_scale_bwd_kernel(const float* __restri
         acc = fmaf(g, y2[base + r], acc);
         dy2[base + r] = gm * g;
     }
-    red[tid] = acc;
-    __syncthreads();
-    for (int wd = 128; wd > 0; wd >>= 1) {
-        if (tid < wd) red[tid] += red[tid + wd];
-        __syncthreads();
-    }
-    if (tid == 0) dgamma[c] = red[0];
+    const float sum = block_sum256(red, acc);
+    if (tid == 0) dgamma[c] = sum;
 }
 
 hipError_t launch_vt_scale_residual(const float* xi, const float* y2, const float* gamma, float* xo, int C, int64_t R, hipStream_t s) {
     const int64_t n = (int64_t)C * R;
-    hipLaunchKernelGGL(vt_scale_residual_kernel, dim3(vt_grid(n)), dim3(256), 0, s, xi, y2, gamma, xo, R, n);
+    hipLaunchKernelGGL(vt_scale_residual_kernel, dim3(grid_1d(n, 8192)), dim3(256), 0, s, xi, y2, gamma, xo, R, n);
     return hipGetLastError();
 }
 

@@ -227,3 +227,20 @@ def dp_config_state_dict(case):
 def dp_config_inputs(case):
     cfg, B, T, lengths, seed, wseed = DP_ALL_CASES[case]
     return dp_inputs(B, T, lengths, seed, hidden=cfg[0], gin=cfg[3])
+
+
+# ---- the split-K rule of the fp32 weight gradients ---------------------------------------------------------------------------
+def wgrad_split(frames, cin_taps, cout):
+    """Python port of wgrad_split (csrc/fp32_tile.h), ONLY for tests to assert which shapes of the split logic their cases reach;
+    never a reference for values.  Returns (tiles, count fs was computed from, frames per split, returned count, whether the
+    32-split cap cut the count)."""
+    tiles = ((cout + 63) // 64) * ((cin_taps + 63) // 64)
+    want = min((256 + tiles - 1) // tiles, (frames + 127) // 128)
+    S = max(min(want, 32), 1)
+    fs = -(-(-(-frames // S)) // 32) * 32
+    return tiles, S, fs, -(-frames // fs), want > 32
+
+
+def wgrad_planes(frames, cin_taps, cout):
+    """Planes of one weight-gradient launch (launch_sd_wgrad, launch_pd_wgrad)."""
+    return wgrad_split(frames, cin_taps, cout)[3]

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from tests import mpd_restatement as R
+from tests import synth_weights as sw
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = [pytest.mark.gpu, pytest.mark.grad]
@@ -134,14 +135,6 @@ def test_gradients_linear_cases_against_the_real_module(gold, case):
     assert not fails and err <= 4 * own, fails
 
 
-def _wgrad_planes(frames, cin, cout):
-    """period_disc_kernels.hip's split rule (pd_wgrad_split): planes of one weight-gradient launch."""
-    tiles = ((cout + 63) // 64) * ((cin * 5 + 63) // 64)
-    s = max(1, min((256 + tiles - 1) // tiles, (frames + 127) // 128, 32))
-    fs = ((frames + s - 1) // s + 31) // 32 * 32
-    return (frames + fs - 1) // fs
-
-
 # (period, B, T): the smallest shapes at which the kernels can go wrong
 SHAPES = [
     (11, 2, 12),        # n_pad = 10; H = 2 -> 1 at every layer
@@ -157,14 +150,14 @@ SHAPES = [
 @pytest.mark.parametrize("p,B,T", SHAPES)
 def test_gradients_linear_mode_at_the_edge_shapes(gold, p, B, T):
     """Slope 1.0 and the linear loss against the float64 restatement.  The last shape crosses the split-K plane of the weight
-    gradient: at p = 2, B = 2, T = 4099 layers 1 and 2 see 912 and 304 frames, which pd_wgrad_split cuts into 8 and 3 planes
-    (asserted below on a restatement of the rule); every smaller shape of the list runs one plane."""
+    gradient: at p = 2, B = 2, T = 4099 layers 1 and 2 see 912 and 304 frames, which wgrad_split cuts into 8 and 3 planes
+    (asserted below on synth_weights' restatement of the rule); every smaller shape of the list runs one plane."""
     wseed, aseed = 400 + p, 500 + T
     if T == 4099:
         h = [(T + p - 1) // p]
         for s in R.STRIDES:
             h.append((h[-1] - 1) // s + 1)
-        assert _wgrad_planes(B * h[2] * p, 32, 128) > 1 and _wgrad_planes(B * h[3] * p, 128, 512) > 1
+        assert sw.wgrad_planes(B * h[2] * p, 32 * 5, 128) > 1 and sw.wgrad_planes(B * h[3] * p, 128 * 5, 512) > 1
     d = _dp(p, R.make_dp_state_dict(wseed), 1.0)
     fm, grads, dx = _native_linear(d, R.make_audio(B, T, aseed), wseed)
     rf, rg, rdx = _ref_linear(p, B, T, wseed, aseed)

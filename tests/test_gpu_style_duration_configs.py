@@ -11,7 +11,7 @@ What the cases reach that the default point (style 128/128/256/k5/2 heads, predi
 of sd_conv_kernel's 16-channel chunk (Cin 100, 17, 24), partial 64-channel output tiles (Cout 100, 65), 1, 3 and 5 taps on both
 modules' convs in the forward and the tap-flipped data gradient, 1, 3 and 4 attention heads, T on both sides of the 64-frame
 tiles, key tiles that are masked before the first valid key, holes and a single valid frame, LayerNorm / GLU / mean-pool /
-dropout layouts 64 to 768 channels wide, and sd_wgrad_split's shapes (test_split_k_shapes_are_all_covered lists them).
+dropout layouts 64 to 768 channels wide, and wgrad_split's shapes (test_split_k_shapes_are_all_covered lists them).
 
 ReLU kinks: the predictor cases either use kink-free weights or a weight seed whose pre-activations keep 32 x the fp32 rounding
 error away from 0 (asserted on the CPU, test_style_dp_restatement_cpu.py), so a difference here is the kernels', not a flipped ReLU.
@@ -233,17 +233,7 @@ def test_duration_predictor_dropout_matches_restatement_with_same_masks():
     _dropout_errors(mod, losses[0], loss64, g64, case)
 
 
-# ---- 4. the split-K weight gradient: which shapes of sd_wgrad_split the cases above take
-def _wgrad_split(frames, tiles):
-    """Python port of sd_wgrad_split (csrc/style_dp_bwd.hip), ONLY to assert below that the cases reach every shape of the
-    split logic; never a reference for values.  Returns (count fs was computed from, frames per split, returned count,
-    whether the 32-split cap cut the count)."""
-    want = min((256 + tiles - 1) // tiles, (frames + 127) // 128)
-    S = max(min(want, 32), 1)
-    fs = -(-(-(-frames // S)) // 32) * 32
-    return S, fs, -(-frames // fs), want > 32
-
-
+# ---- 4. the split-K weight gradient: which shapes of wgrad_split (synth_weights.wgrad_split) the cases above take
 def _wgrad_convs():
     """(case, conv, Cin, Cout, taps, B, T) of every weight gradient the gradient tests above launch (engine_style.cpp /
     engine_duration.cpp: *_train_backward)."""
@@ -261,8 +251,8 @@ def _wgrad_convs():
 def test_split_k_shapes_are_all_covered():
     seen = {}
     for case, name, cin, cout, taps, B, T in _wgrad_convs():
-        frames, tiles = B * T, ((cout + 63) // 64) * ((cin * taps + 63) // 64)
-        S, fs, ret, capped = _wgrad_split(frames, tiles)
+        frames = B * T
+        tiles, S, fs, ret, capped = sw.wgrad_split(frames, cin * taps, cout)
         chunks = [(f0, min(f0 + 32, lo + fs, frames) - 1) for lo in range(0, ret * fs, fs) for f0 in range(lo, min(lo + fs, frames), 32)]
         shapes = {"one split": ret == 1, "more than one split, below the cap": 1 < ret < 32, "the 32-split cap": capped and S == 32,
                   "a returned count below the first estimate": ret < S, "a last split shorter than 32 frames": 0 < frames - (ret - 1) * fs < 32 and ret > 1,
