@@ -75,6 +75,45 @@ def test_restatement_matches_the_reference_modules_float64_gradients(gold, name)
     assert lerr <= BAR and de <= BAR
 
 
+@pytest.fixture(scope="module")
+def gold_frames():
+    return dict(np.load(os.path.join(ROOT, "tests", "golden", "vocos_grads_frames.npz")))
+
+
+@pytest.mark.parametrize("name", list(R.FRAME_CASES))
+def test_restatement_matches_the_reference_modules_float64_gradients_above_128_frames(gold_frames, name):
+    """The same pin for the cases of vocos_grads_frames.npz (R = 1100 and the preset at R = 260, where the native weight gradients
+    take several split-K planes); d mel and the audio are compared on the fixture's sampled elements.  At 25 x 44 the head's clip
+    IS reached: no log-magnitude within 1e-4 of it."""
+    gold = gold_frames
+    fields, B, T, wseed, mseed, _ = R.FRAME_CASES[name]
+    cfg = vo.vocos_config(**fields)
+    sd, mel = vo.make_vocos_state_dict(wseed, cfg), vo.make_mel(B, T, mseed, M=cfg.input_channels)
+    audio, kept = R.forward(sd, mel, cfg)
+    assert np.abs(kept["o"][..., :cfg.n_fft // 2 + 1] - np.log(100.0)).min() > 1e-4
+    W = R.loss_weights(audio.shape, wseed).astype(np.float64)
+    G, dmel = R.backward(sd, kept, W, cfg)
+    names = list(gold[name + "/names"])
+    assert names == R.param_names(sd) and sorted(G) == names and len(names) == 9 * cfg.num_layers + 8
+    l64 = float(gold[name + "/loss64"].reshape(-1)[0])
+    lerr = abs(float((audio * W).sum()) - l64) / abs(l64)
+    worst = ("", 0.0)
+    for i, n in enumerate(names):
+        assert G[n].shape == sd[n].shape
+        e = _rel_l2(R.stored_elements(i, G[n], wseed), gold[f"{name}/grad/{n}"])
+        worst = max(worst, (n, e), key=lambda v: v[1])
+        assert e <= BAR, (n, e)
+        assert abs(np.linalg.norm(G[n]) - gold[name + "/norms"][i]) <= 1e-9 * gold[name + "/norms"][i]
+    de, ea = _rel_l2(R.sampled(dmel, wseed, 0), gold[name + "/dmel64"]), _rel_l2(R.sampled(audio, wseed, 1), gold[name + "/audio64"])
+    print(f"{name}: loss rel {lerr:.1e}, audio {ea:.1e}, worst parameter {worst[0]} {worst[1]:.1e}, d mel {de:.1e} (bar {BAR:.0e})")
+    assert lerr <= BAR and de <= BAR and ea <= BAR
+    # the fp32 module's own errors, the GPU test's yardsticks: fp32 rounding, not zero and not large
+    for k in ("err32", "dmel_err32", "audio_err32"):
+        assert 0 < np.min(gold[f"{name}/{k}"]) and np.max(gold[f"{name}/{k}"]) < 1e-4, k
+    assert gold[name + "/dmel64"].shape == gold[name + "/audio64"].shape == (R.FRAMES_SAMPLE,)
+    assert os.path.getsize(os.path.join(ROOT, "tests", "golden", "vocos_grads_frames.npz")) < 1000 * 1000
+
+
 def test_fixture_is_what_the_generator_says(gold):
     for name, (fields, B, T, *_rest) in R.CASES.items():
         cfg = vo.vocos_config(**fields)

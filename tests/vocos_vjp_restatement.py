@@ -4,7 +4,9 @@ d audio to every parameter and to the mel, written out by hand -- the formulas t
 "Vocos training").  tests/test_vocos_backward_cpu.py pins it to the float64 gradients of the REAL module under torch autograd
 (tests/golden/vocos_grads.npz, tools/make_golden_vocos_grads.py); the GPU tests use it at shapes the fixture lacks.
 
-Also here: the fixture's cases, its sampled-element rule, and ``torch_vocos``, a functional torch statement of the same
+The contractions over the frames go through ``optimize=True`` (BLAS): the reference of a 4100-frame case takes seconds.
+
+Also here: the fixtures' cases, its sampled-element rule, and ``torch_vocos``, a functional torch statement of the same
 forward on a dict of tensors, which the GPU trajectory test and tools/vocos_train_bench.py differentiate with torch autograd.
 """
 import numpy as np
@@ -20,6 +22,13 @@ CASES = {
     "small_linear": (dict(input_channels=64, intermediate_dim=256, num_layers=2), 3, 7, 21, 22, "linear"),
     "preset_mel_loss": (dict(), 2, 16, 31, 32, "mel_loss"),
 }
+# cases above 128 frames per batch (tests/golden/vocos_grads_frames.npz): the split-K weight gradients take several planes.  The
+# same layout, except that d mel and the audio are stored as FRAMES_SAMPLE sampled elements too (sampled())
+FRAME_CASES = {
+    "R1100": (dict(input_channels=64, intermediate_dim=256, num_layers=2), 25, 44, 41, 42, "linear"),
+    "preset_R260": (dict(), 4, 65, 41, 42, "linear"),
+}
+FRAMES_SAMPLE = 4096
 
 
 def loss_weights(shape, seed):
@@ -38,6 +47,13 @@ def stored_elements(name_index, g, seed):
     """What the fixture keeps of gradient ``g``: all of it up to FULL_MAX elements, else the sampled elements."""
     g = np.asarray(g).reshape(-1)
     return g if g.size <= FULL_MAX else g[sample_index(g.size, seed + name_index)]
+
+
+def sampled(x, seed, which):
+    """What the frames fixture keeps of d mel (which = 0) and of the audio (which = 1): FRAMES_SAMPLE fixed sampled elements."""
+    x = np.asarray(x).reshape(-1)
+    rng = np.random.Generator(np.random.PCG64(seed + 9500 + which))
+    return x[np.sort(rng.choice(x.size, size=min(FRAMES_SAMPLE, x.size), replace=False))]
 
 
 def param_names(sd):
@@ -80,7 +96,7 @@ def forward(sd, mel, cfg=vo.VocosConfig):
     """-> (audio (B, T * hop) float64, kept).  The same arithmetic as vocos_oracle.vocos_forward(dtype=float64)."""
     g = lambda k: sd[k].astype(np.float64)      # noqa: E731
     kept = {"mel_cols": _cols(mel.astype(np.float64))}
-    e0 = np.einsum("bctk,ock->bot", kept["mel_cols"], g("backbone.embed.weight")) + g("backbone.embed.bias")[None, :, None]
+    e0 = np.einsum("bctk,ock->bot", kept["mel_cols"], g("backbone.embed.weight"), optimize=True) + g("backbone.embed.bias")[None, :, None]
     x, kept["ln0"] = _ln_fwd(e0.transpose(0, 2, 1), g("backbone.norm.weight"), g("backbone.norm.bias"))
     x = x.transpose(0, 2, 1)                                                  # (B, C, T)
     for i in range(cfg.num_layers):
@@ -139,7 +155,7 @@ def backward(sd, kept, d_audio, cfg=vo.VocosConfig):
     g = lambda k: sd[k].astype(np.float64)      # noqa: E731
     G = {}
     do = istft_head_backward(d_audio.astype(np.float64), kept["o"], g("head.istft.window"), cfg.n_fft, cfg.hop_length)
-    G["head.out.weight"] = np.einsum("btn,btc->nc", do, kept["hf"])
+    G["head.out.weight"] = np.einsum("btn,btc->nc", do, kept["hf"], optimize=True)
     G["head.out.bias"] = do.sum((0, 1))
     dhf = do @ g("head.out.weight")
     dx, G["backbone.final_layer_norm.weight"], G["backbone.final_layer_norm.bias"] = _ln_bwd(dhf, kept["lnf"], g("backbone.final_layer_norm.weight"))
@@ -150,10 +166,10 @@ def backward(sd, kept, d_audio, cfg=vo.VocosConfig):
         dxt = dx.transpose(0, 2, 1)                                           # (B, T, C)
         G[p + "gamma"] = (dxt * k["y2"]).sum((0, 1))
         dy2 = dxt * g(p + "gamma")
-        G[p + "pwconv2.weight"] = np.einsum("btc,btf->cf", dy2, k["g"])
+        G[p + "pwconv2.weight"] = np.einsum("btc,btf->cf", dy2, k["g"], optimize=True)
         G[p + "pwconv2.bias"] = dy2.sum((0, 1))
         du = (dy2 @ g(p + "pwconv2.weight")) * gelu_grad(k["u"])
-        G[p + "pwconv1.weight"] = np.einsum("btf,btc->fc", du, k["h"])
+        G[p + "pwconv1.weight"] = np.einsum("btf,btc->fc", du, k["h"], optimize=True)
         G[p + "pwconv1.bias"] = du.sum((0, 1))
         dh = du @ g(p + "pwconv1.weight")
         dz, G[p + "norm.weight"], G[p + "norm.bias"] = _ln_bwd(dh, k["ln"], g(p + "norm.weight"))
@@ -163,9 +179,9 @@ def backward(sd, kept, d_audio, cfg=vo.VocosConfig):
         dx = dx + _cols_T(dz[..., None] * g(p + "dwconv.weight")[None, :, 0, None, :])
     de0, G["backbone.norm.weight"], G["backbone.norm.bias"] = _ln_bwd(dx.transpose(0, 2, 1), kept["ln0"], g("backbone.norm.weight"))
     de0 = de0.transpose(0, 2, 1)
-    G["backbone.embed.weight"] = np.einsum("bot,bctk->ock", de0, kept["mel_cols"])
+    G["backbone.embed.weight"] = np.einsum("bot,bctk->ock", de0, kept["mel_cols"], optimize=True)
     G["backbone.embed.bias"] = de0.sum((0, 2))
-    dmel = _cols_T(np.einsum("bot,ock->bctk", de0, g("backbone.embed.weight")))
+    dmel = _cols_T(np.einsum("bot,ock->bctk", de0, g("backbone.embed.weight"), optimize=True))
     return G, dmel
 
 

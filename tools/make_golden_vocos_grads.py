@@ -1,4 +1,4 @@
-"""Generates tests/golden/vocos_grads.npz: gradients of the REAL reference Vocos generator (vocoders/vocos/models/model.py,
+"""Generates tests/golden/vocos_grads.npz and vocos_grads_frames.npz: gradients of the REAL reference Vocos generator (vocoders/vocos/models/model.py,
 unmodified, CPU, one thread) under torch autograd, for the native training path (stabletts_amd/vocos_train.py).  Run where a
 checkout of the reference StableTTS is available:
 
@@ -16,6 +16,12 @@ d mel, err32 = the relative L2 distance of its stored elements from the float64 
 gradients themselves are not kept (with them, or with whole tensors up to 4096 elements, the file passes 1 MB).
 The generator asserts that no exp(a) reaches the head's clip at 100 in any case.  Fixed zip timestamps: regenerating the file
 reproduces it byte for byte.
+
+A second table (vocos_vjp_restatement.FRAME_CASES: the small config at 25 x 44 and the preset at 4 x 65 frames, where the split-K
+weight gradients of the native path take several planes) goes to tests/golden/vocos_grads_frames.npz with the same keys.  Two
+differences: d mel is stored as 4096 sampled elements (vocos_vjp_restatement.sampled; whole it would be 563 KB at 25 x 64 x 44)
+and so is the audio (audio64, audio_err32), and the clip IS reached at 25 x 44, so the generator asserts instead that no
+log-magnitude lies within 1e-4 of ln 100, in either precision.
 """
 import importlib.util
 import os
@@ -26,6 +32,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "tests", "golden", "vocos_grads.npz")
+OUT_FRAMES = os.path.join(ROOT, "tests", "golden", "vocos_grads_frames.npz")
 
 
 def _rel_l2(a, ref):
@@ -47,12 +54,23 @@ def main():
     spec = importlib.util.spec_from_file_location("vocos_loss", os.path.join(ref_dir, "vocoders", "vocos", "models", "loss.py"))
     loss_mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(loss_mod)                                 # reference, unmodified
-    from oracle import vocos_oracle as vo
     from tests import vocos_vjp_restatement as R
     y_np = np.load(os.path.join(ROOT, "tests", "golden", "mel_loss_grads.npz"))["y"]
 
+    for out, cases, frames in ((OUT, R.CASES, False), (OUT_FRAMES, R.FRAME_CASES, True)):
+        res = _run_cases(cases, frames, Vocos, VocosConfig, MelConfig, loss_mod, y_np)
+        _save(out, res)
+        print("wrote", out, os.path.getsize(out), "bytes")
+        assert os.path.getsize(out) < 1000 * 1000
+
+
+def _run_cases(cases, frames, Vocos, VocosConfig, MelConfig, loss_mod, y_np):
+    """frames: the cases of vocos_grads_frames.npz -- the clip may be reached but not within 1e-4 of it, d mel and the audio are
+    stored as sampled elements."""
+    from oracle import vocos_oracle as vo
+    from tests import vocos_vjp_restatement as R
     res = {}
-    for case, (fields, B, T, wseed, mseed, loss_kind) in R.CASES.items():
+    for case, (fields, B, T, wseed, mseed, loss_kind) in cases.items():
         cfg = vo.vocos_config(**fields)
         sd = vo.make_vocos_state_dict(wseed, cfg)
         mel_np = vo.make_mel(B, T, mseed, M=cfg.input_channels)
@@ -61,12 +79,21 @@ def main():
             voc = Vocos(VocosConfig(cfg.input_channels, cfg.dim, cfg.intermediate_dim, cfg.num_layers), MelConfig())
             voc.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
             voc = voc.to(dt)
-            peak = []
-            hook = voc.head.out.register_forward_hook(lambda m, i, o: peak.append(float(o[..., :o.shape[-1] // 2].max())))
+            peak, near = [], []
+
+            def watch(m, i, o):
+                a = o[..., :o.shape[-1] // 2].detach()
+                peak.append(float(a.max()))
+                near.append(float((a - np.log(100.0)).abs().min()))
+
+            hook = voc.head.out.register_forward_hook(watch)
             mel = torch.from_numpy(mel_np).to(dt).requires_grad_(True)
             audio = voc(mel)
             hook.remove()
-            assert np.exp(peak[0]) < 100.0, f"{case}: exp(a) reaches the clip ({np.exp(peak[0]):.1f})"
+            if frames:      # the two precisions must take the same branch of the clip everywhere
+                assert near[0] > 1e-4, f"{case}: a log-magnitude lies {near[0]:.1e} from the clip"
+            else:
+                assert np.exp(peak[0]) < 100.0, f"{case}: exp(a) reaches the clip ({np.exp(peak[0]):.1f})"
             if loss_kind == "linear":
                 loss = (audio * torch.from_numpy(R.loss_weights(tuple(audio.shape), wseed)).to(dt)).sum()
             else:
@@ -74,10 +101,10 @@ def main():
                 loss = loss_mod.MultiScaleMelSpectrogramLoss().to(dt)(torch.from_numpy(y_np).to(dt), audio.unsqueeze(1))
             loss.backward()
             grads = {n: p.grad.numpy() for n, p in voc.named_parameters()}
-            runs[tag] = (float(loss.item()), grads, mel.grad.numpy())
-            print(case, tag, "loss", loss.item(), "max a", peak[0])
-        l64, g64, dm64 = runs["64"]
-        l32, g32, dm32 = runs["32"]
+            runs[tag] = (float(loss.item()), grads, mel.grad.numpy(), audio.detach().numpy())
+            print(case, tag, "loss", loss.item(), "max a", peak[0], "nearest to the clip", near[0])
+        l64, g64, dm64, au64 = runs["64"]
+        l32, g32, dm32, au32 = runs["32"]
         names = sorted(g64)
         assert names == R.param_names(sd)
         res[f"{case}/names"] = np.array(names)
@@ -91,13 +118,15 @@ def main():
             res[f"{case}/grad/{n}"] = ref
             err.append(_rel_l2(R.stored_elements(i, g32[n], wseed), ref))
         res[f"{case}/err32"] = np.array(err)
+        if frames:
+            dm64, dm32 = R.sampled(dm64, wseed, 0), R.sampled(dm32, wseed, 0)
+            res[f"{case}/audio64"] = R.sampled(au64, wseed, 1)
+            res[f"{case}/audio_err32"] = np.float64(_rel_l2(R.sampled(au32, wseed, 1), res[f"{case}/audio64"]))
         res[f"{case}/dmel64"] = dm64
         res[f"{case}/dmel_err32"] = np.float64(_rel_l2(dm32, dm64))
         print(case, "fp32 vs float64: loss", abs(l32 - l64) / abs(l64), "grad rel L2 max", max(err), "median", float(np.median(err)),
               "dmel", float(res[f"{case}/dmel_err32"]))
-    _save(OUT, res)
-    print("wrote", OUT, os.path.getsize(OUT), "bytes")
-    assert os.path.getsize(OUT) < 1000 * 1000
+    return res
 
 
 if __name__ == "__main__":
