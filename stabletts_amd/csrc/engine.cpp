@@ -391,24 +391,39 @@ int run_time_tables(st_engine* e, const Plan& p, hipStream_t s) {
     return ST_OK;
 }
 
-// One vector-field evaluation over N items given x16/x16lo (B items), cpart, ada, film.  Output p.v32.
-// ev: index into the time tables (scalar t shared by all items) or -1 for per-item t (n_t == B).
+// The L DiT blocks and the output projection, for both kinds that are made of them.
+// Decoder: one vector-field evaluation over N items given x16/x16lo (B items), cpart, ada, film; output p.v32.
+//   ev: index into the time tables (scalar t shared by all items) or -1 for per-item t (n_t == B).
+// Text encoder (models/text_encoder.py:40-42): the residual stream p.X comes masked from the embedding kernel; outputs p.X
+//   and p.v32 (proj); ev is not read.
 // Every FiLM + LayerNorm + modulate runs inside the epilogue of the GEMM that produces its input (row-complete
 // tiles): in_proj -> LN1 of block 0, FFN conv_2 -> LN1 of the next block, long-skip conv -> LN1, out-proj -> LN2.
 int run_estimator(st_engine* e, const Plan& p, const float* mask, int ev, hipStream_t s) {
     const int C = e->C, F = e->F, L = e->L, N = p.N, T = p.T;
     const int64_t rowsC = (int64_t)N * T * C;
     const bool cap = e->capture;
+    // What the text encoder's blocks leave out of the decoder's, said once:
+    const bool dec = e->kind == KIND_DECODER;
+    const bool film = dec;       // FiLM in front of every LN1, and in_proj to carry block 0's (else: the stand-alone LN kernel)
+    const bool skips = dec;      // U-Net long skips: skip16 copies out of the first half, long-skip convs into the second
+    const bool dec_fast_paths = dec;      // decoder-only paths not yet passed for the text encoder: the weight-stationary out-projection,
+                                          // the fused FFN, split q / k operands, the lse statistic, ragged tile skipping, x3's dead fp32 copy
+    const bool split_qk = dec_fast_paths && e->attn_split;
+    const bool ragged = dec_fast_paths && e->ragged_skip && !cap;
+    const int ln1_by_ffn = skips ? L / 2 : L;      // blocks below this take their LN1 from the previous block's conv_2 (the others from their long-skip conv)
     auto ada_of = [&](int i) { return p.ada + (size_t)i * N * 6 * C; };
-    // FiLM_i + LN1_i + modulate (start of block i) fused into the producing GEMM
+    // [FiLM_i +] LN1_i + modulate (start of block i) fused into the producing GEMM
     auto fuse_ln1 = [&](ConvGemmArgs& a, int i) {
-        const float* fb = p.film + (size_t)i * p.n_t * 2 * C;
-        if (ev >= 0) { a.ln_film = fb + (size_t)ev * 2 * C; a.ln_film_stride = 0; a.ln_film_mod = 1; }
-        else         { a.ln_film = fb; a.ln_film_stride = 2 * C; a.ln_film_mod = p.B; }
+        a.ln_film = nullptr; a.ln_film_stride = 0; a.ln_film_mod = 1;
+        if (film) {
+            const float* fb = p.film + (size_t)i * p.n_t * 2 * C;
+            if (ev >= 0) a.ln_film = fb + (size_t)ev * 2 * C;
+            else         { a.ln_film = fb; a.ln_film_stride = 2 * C; a.ln_film_mod = p.B; }
+        }
         a.ln_ada = ada_of(i); a.ln_ada_stride = 6 * C; a.ln_shift_off = 0; a.ln_scale_off = C;
         a.ln_mask_out = 0; a.ln_h16 = p.h16; a.mask = mask;
     };
-    {   // in_proj: X = Wx.x + (Wc.cond + b); also the first long-skip (estimator.py:120-121,129).  The fp32 ODE state
+    if (film) {   // in_proj: X = Wx.x + (Wc.cond + b); also the first long-skip (estimator.py:120-121,129).  The fp32 ODE state
         // enters as the operand pair (x_hi, x_lo): K = [x_hi | x_lo | x_hi] against [W_hi | W_hi | W_lo]
         ConvGemmArgs a = base_args(e, p, e->inx, N);
         a.a0 = p.x16; a.c0 = e->Mp; a.a0_mod = p.B; a.a1 = p.x16lo; a.c1 = e->Mp; a.a1_mod = p.B; a.c2 = e->Mp;
@@ -418,12 +433,19 @@ int run_estimator(st_engine* e, const Plan& p, const float* mask, int ev, hipStr
         fuse_ln1(a, 0);
         ProfScope ps(e, s, PC_INPROJ, conv_flops(p, e->inx, N));
         HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
+    } else {      // no GEMM in front of block 0: its LN1 + modulate as a kernel of its own
+        FilmLnArgs a; memset(&a, 0, sizeof(a));
+        a.X = p.X; a.h16 = p.h16; a.film = nullptr; a.film_mod = 1;
+        a.ada = ada_of(0); a.ada_stride = 6 * C; a.shift_off = 0; a.scale_off = C;
+        a.mask = mask; a.mask_mod = p.B; a.mask_out = 0; a.T = T; a.rows = N * T;
+        ProfScope ps(e, s, PC_FILM_LN1, 0);
+        HIPCHK(e, launch_film_ln(e->dt, a, s));
     }
-    if (cap) capture(e, "h0", p.skip16[0], rowsC, true, s);
+    if (film && cap) capture(e, "h0", p.skip16[0], rowsC, true, s);
     for (int i = 0; i < L; ++i) {
         const std::string bn = "b" + std::to_string(i) + ".";
         const float* ada_i = ada_of(i);
-        if (i >= L / 2) {   // U-Net long skip merge (estimator.py:131-132)
+        if (skips && i >= L / 2) {   // U-Net long skip merge (estimator.py:131-132)
             const int j = i - L / 2;
             ConvGemmArgs a = base_args(e, p, e->lsc[j], N);
             a.a0 = p.cur16; a.c0 = C; a.a1 = p.skip16[L - 1 - i]; a.c1 = C;
@@ -437,7 +459,7 @@ int run_estimator(st_engine* e, const Plan& p, const float* mask, int ev, hipStr
             ConvGemmArgs a = base_args(e, p, e->qkv[i], N);
             a.a0 = p.h16; a.c0 = C;
             a.q = p.q16; a.k = p.k16; a.vt = p.vt16; a.rope_cos = e->rope_cos; a.rope_sin = e->rope_sin;
-            if (e->attn_split) { a.q_lo = p.q16lo; a.k_lo = p.k16lo; }      // (the generic tile writes the residual planes; the weight-stationary kernel has no room for them)
+            if (split_qk) { a.q_lo = p.q16lo; a.k_lo = p.k16lo; }      // (the generic tile writes the residual planes; the weight-stationary kernel has no room for them)
             a.Tp = p.Tp; a.n_heads = e->H;
             if ((int)e->qkv_frag.size() == L) a.w_frag = e->qkv_frag[i];
             a.qscale = 1.4426950408889634f / sqrtf((float)(C / e->H));
@@ -453,16 +475,16 @@ int run_estimator(st_engine* e, const Plan& p, const float* mask, int ev, hipStr
             a.q = p.q16; a.k = p.k16; a.vt = p.vt16; a.out = p.ao16; a.kbias = p.kbias; a.mask_mod = p.B; a.zeros = e->zeros;
             a.kv_end = p.kv_end; a.n_full = p.n_full; a.T = T; a.Tp = p.Tp; a.H = e->H; a.n_items = N;
             a.small_max_blocks = e->conc == 1 ? e->attn_small_blocks : 0;
-            if (e->attn_split) { a.q_lo = p.q16lo; a.k_lo = p.k16lo; }
-            a.lse_max = e->lse_cells;
-            if (e->ragged_skip && !cap) a.t_lim = p.t_lim;
+            if (split_qk) { a.q_lo = p.q16lo; a.k_lo = p.k16lo; }
+            if (dec_fast_paths) a.lse_max = e->lse_cells;
+            if (ragged) a.t_lim = p.t_lim;
             ProfScope ps(e, s, PC_ATTN, 4.0 * (double)N * e->H * (double)T * T * (C / e->H));
             if (!(e->skip_mask >> PC_ATTN & 1)) HIPCHK(e, launch_attention(e->dt, a, s));
         }
         if (cap) capture(e, bn + "attn", p.ao16, rowsC, true, s);
         // Big grids: the whole FFN as ONE kernel, u never leaves the CU (ffn_fused.h; bit-identical to the two launches below).
         // Debug capture keeps the two-kernel path (it taps u).
-        const bool fused = e->fused_ffn && !cap && (int)e->ffn_stream.size() == L && e->ffn_stream[i] &&
+        const bool fused = dec_fast_paths && e->fused_ffn && !cap && (int)e->ffn_stream.size() == L && e->ffn_stream[i] &&
                            (int64_t)e->conc * N * ((T + kFfnFusedFrames - 1) / kFfnFusedFrames) >= e->big_min_blocks;
         void* h2buf = fused ? p.h2_16 : p.h16;
         {   // out projection, gate, mask, residual (diffusion_transformer.py:65,111) + LN2, modulate, mask (:112,26)
@@ -470,7 +492,7 @@ int run_estimator(st_engine* e, const Plan& p, const float* mask, int ev, hipStr
             a.a0 = p.ao16; a.c0 = C; a.mask = mask; a.gate = ada_i + 2 * C; a.gate_stride = 6 * C; a.out32 = p.X;
             a.ln_h16 = h2buf; a.ln_film = nullptr; a.ln_film_mod = 1;
             a.ln_ada = ada_i; a.ln_ada_stride = 6 * C; a.ln_shift_off = 3 * C; a.ln_scale_off = 4 * C; a.ln_mask_out = 1;
-            if ((int)e->oproj_frag.size() == L && !cap) a.w_frag = e->oproj_frag[i];
+            if (dec_fast_paths && (int)e->oproj_frag.size() == L && !cap) a.w_frag = e->oproj_frag[i];
             ProfScope ps(e, s, PC_OPROJ, conv_flops(p, e->oproj[i], N));
             if (!(e->skip_mask >> PC_OPROJ & 1)) HIPCHK(e, gemm(e, 1, EPI_RESGATE, a, s));
         }
@@ -482,17 +504,17 @@ int run_estimator(st_engine* e, const Plan& p, const float* mask, int ev, hipStr
             HIPCHK(e, gemm(e, 3, EPI_ACT16, a, s));
         }
         if (cap) capture(e, bn + "u", p.u16, (int64_t)N * T * F, true, s);
-        void* copy16 = (i + 1 < L / 2) ? p.skip16[i + 1] : p.cur16;
+        void* copy16 = (skips && i + 1 < L / 2) ? p.skip16[i + 1] : p.cur16;
         {   // FFN conv_2, mask, gate, residual (diffusion_transformer.py:29-30,112) [+ FiLM/LN1 of block i+1]
             ConvGemmArgs a = base_args(e, p, e->ffn2[i], N);
             a.a0 = p.u16; a.c0 = F; a.mask = mask; a.gate = ada_i + 5 * C; a.gate_stride = 6 * C; a.out32 = p.X;
             if (fused) { a.a0 = h2buf; a.c0 = C; a.w = e->ffn_stream[i]; a.bias1 = e->ffn1[i].bias; a.cmid = F; a.flags = GF_SILU | GF_MASK; }
             a.out16 = copy16;
-            if (i + 1 == L) a.out16_lo = p.cur16lo;        // operand pair of final_proj
-            if (i + 1 < L / 2) fuse_ln1(a, i + 1);         // blocks >= L/2 start with the long-skip conv instead
+            if (i + 1 == L) a.out16_lo = p.cur16lo;        // operand pair of final_proj / proj
+            if (i + 1 < ln1_by_ffn) fuse_ln1(a, i + 1);    // the decoder's blocks >= L/2 start with the long-skip conv instead
             // ... which rebuilds the residual stream from the 16-bit operands (and final_proj reads only those): from
             // block L/2 - 1 on the fp32 copy of x3 is dead, so it is not written (40 % of this epilogue's HBM bytes)
-            else if (!cap) a.out32_readonly = 1;
+            else if (dec_fast_paths && !cap) a.out32_readonly = 1;
             ProfScope ps(e, s, PC_FFN2, conv_flops(p, e->ffn2[i], N) + (fused ? conv_flops(p, e->ffn1[i], N) : 0.0));
             if (e->skip_mask >> PC_FFN2 & 1) {}
             else if (fused && e->fused_ffn == 3) HIPCHK(e, launch_ffn_wino_f16(a, s));
@@ -500,98 +522,17 @@ int run_estimator(st_engine* e, const Plan& p, const float* mask, int ev, hipStr
             else HIPCHK(e, gemm(e, 3, EPI_RESGATE, a, s));
         }
         if (cap) {
-            if (i + 1 < L / 2) capture(e, bn + "x3", copy16, rowsC, true, s);   // X already holds the FiLM'd value
+            if (film && i + 1 < ln1_by_ffn) capture(e, bn + "x3", copy16, rowsC, true, s);   // X already holds the FiLM'd value
             else capture(e, bn + "x3", p.X, rowsC, false, s);
         }
     }
-    {   // final projection (estimator.py:136-138); block output is already zero on padded frames
+    {   // final_proj (estimator.py:136-138) / mu_x = proj(x) * x_mask (text_encoder.py:42); block output is already zero on padded frames
         ConvGemmArgs a = base_args(e, p, e->fin, N);
         a.a0 = p.cur16; a.c0 = C; a.a1 = p.cur16lo; a.c1 = C; a.c2 = C; a.mask = mask; a.flags = GF_MASK; a.out32 = p.v32;
         ProfScope ps(e, s, PC_FINAL, conv_flops(p, e->fin, N));
         HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
     }
     if (cap) capture(e, "v", p.v32, (int64_t)N * T * e->Mp, false, s);
-    return ST_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// TextEncoder body (models/text_encoder.py:40-42): L DiTConVBlocks WITHOUT the FiLM wrapper on the residual
-// stream p.X (already masked by the embedding kernel), then proj.  Same kernels and the same fused-LayerNorm
-// epilogues as run_estimator: out-proj carries LN2, FFN conv_2 carries the next block's LN1.
-int run_text_blocks(st_engine* e, const Plan& p, const float* mask, hipStream_t s) {
-    const int C = e->C, F = e->F, L = e->L, N = p.N, T = p.T;
-    const int64_t rowsC = (int64_t)N * T * C;
-    const bool cap = e->capture;
-    auto ada_of = [&](int i) { return p.ada + (size_t)i * N * 6 * C; };
-    auto ln_launch = [&](int i, int shift_off, int scale_off, int mask_out, int cls) -> int {
-        FilmLnArgs a; memset(&a, 0, sizeof(a));
-        a.X = p.X; a.h16 = p.h16; a.film = nullptr; a.film_mod = 1;
-        a.ada = ada_of(i); a.ada_stride = 6 * C; a.shift_off = shift_off; a.scale_off = scale_off;
-        a.mask = mask; a.mask_mod = p.B; a.mask_out = mask_out; a.T = T; a.rows = N * T;
-        ProfScope ps(e, s, cls, 0);
-        HIPCHK(e, launch_film_ln(e->dt, a, s));
-        return ST_OK;
-    };
-    int rc;
-    for (int i = 0; i < L; ++i) {
-        const std::string bn = "b" + std::to_string(i) + ".";
-        const float* ada_i = ada_of(i);
-        if (i == 0 && (rc = ln_launch(i, 0, C, 0, PC_FILM_LN1))) return rc;     // LN1 + modulate (later blocks: fused)
-        if (cap) { capture(e, bn + "x1", p.X, rowsC, false, s); capture(e, bn + "h1", p.h16, rowsC, true, s); }
-        {
-            ConvGemmArgs a = base_args(e, p, e->qkv[i], N);
-            a.a0 = p.h16; a.c0 = C;
-            a.q = p.q16; a.k = p.k16; a.vt = p.vt16; a.rope_cos = e->rope_cos; a.rope_sin = e->rope_sin;
-            a.Tp = p.Tp; a.n_heads = e->H;
-            if ((int)e->qkv_frag.size() == L) a.w_frag = e->qkv_frag[i];
-            a.qscale = 1.4426950408889634f / sqrtf((float)(C / e->H));
-            ProfScope ps(e, s, PC_QKV, conv_flops(p, e->qkv[i], N));
-            HIPCHK(e, gemm(e, 1, EPI_QKV, a, s));
-        }
-        {
-            AttnArgs a; memset(&a, 0, sizeof(a));
-            a.q = p.q16; a.k = p.k16; a.vt = p.vt16; a.out = p.ao16; a.kbias = p.kbias; a.mask_mod = p.B; a.zeros = e->zeros;
-            a.kv_end = p.kv_end; a.n_full = p.n_full; a.T = T; a.Tp = p.Tp; a.H = e->H; a.n_items = N;
-            a.small_max_blocks = e->conc == 1 ? e->attn_small_blocks : 0;
-            ProfScope ps(e, s, PC_ATTN, 4.0 * (double)N * e->H * (double)T * T * (C / e->H));
-            HIPCHK(e, launch_attention(e->dt, a, s));
-        }
-        if (cap) capture(e, bn + "attn", p.ao16, rowsC, true, s);
-        {
-            ConvGemmArgs a = base_args(e, p, e->oproj[i], N);
-            a.a0 = p.ao16; a.c0 = C; a.mask = mask; a.gate = ada_i + 2 * C; a.gate_stride = 6 * C; a.out32 = p.X;
-            a.ln_h16 = p.h16; a.ln_film = nullptr; a.ln_film_mod = 1;       // + LN2, modulate, mask
-            a.ln_ada = ada_i; a.ln_ada_stride = 6 * C; a.ln_shift_off = 3 * C; a.ln_scale_off = 4 * C; a.ln_mask_out = 1;
-            ProfScope ps(e, s, PC_OPROJ, conv_flops(p, e->oproj[i], N));
-            HIPCHK(e, gemm(e, 1, EPI_RESGATE, a, s));
-        }
-        if (cap) capture(e, bn + "x2", p.X, rowsC, false, s);
-        {
-            ConvGemmArgs a = base_args(e, p, e->ffn1[i], N);
-            a.a0 = p.h16; a.c0 = C; a.mask = mask; a.flags = GF_SILU | GF_MASK; a.out16 = p.u16;
-            ProfScope ps(e, s, PC_FFN1, conv_flops(p, e->ffn1[i], N));
-            HIPCHK(e, gemm(e, 3, EPI_ACT16, a, s));
-        }
-        {
-            ConvGemmArgs a = base_args(e, p, e->ffn2[i], N);
-            a.a0 = p.u16; a.c0 = F; a.mask = mask; a.gate = ada_i + 5 * C; a.gate_stride = 6 * C; a.out32 = p.X;
-            a.out16 = p.cur16;
-            if (i + 1 == L) a.out16_lo = p.cur16lo;      // operand pair of proj (split precision, like the decoder's final_proj)
-            if (i + 1 < L) {      // LN1 + modulate of block i+1 (no FiLM, not masked)
-                a.ln_h16 = p.h16; a.ln_film = nullptr; a.ln_film_mod = 1;
-                a.ln_ada = ada_of(i + 1); a.ln_ada_stride = 6 * C; a.ln_shift_off = 0; a.ln_scale_off = C; a.ln_mask_out = 0;
-            }
-            ProfScope ps(e, s, PC_FFN2, conv_flops(p, e->ffn2[i], N));
-            HIPCHK(e, gemm(e, 3, EPI_RESGATE, a, s));
-        }
-        if (cap) capture(e, bn + "x3", p.X, rowsC, false, s);
-    }
-    {   // mu_x = proj(x) * x_mask (text_encoder.py:42)
-        ConvGemmArgs a = base_args(e, p, e->fin, N);
-        a.a0 = p.cur16; a.c0 = C; a.a1 = p.cur16lo; a.c1 = C; a.c2 = C; a.mask = mask; a.flags = GF_MASK; a.out32 = p.v32;
-        ProfScope ps(e, s, PC_FINAL, conv_flops(p, e->fin, N));
-        HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
-    }
     return ST_OK;
 }
 
@@ -1062,7 +1003,7 @@ int st_text_encoder_forward(st_engine* e, const int64_t* tokens, const int64_t* 
         HIPCHK(e, launch_cvec_prep(c, nullptr, B, e->G, p.cvec, s));
     }
     if ((rc = run_adaln(e, p, s))) return rc;
-    if ((rc = run_text_blocks(e, p, mask_out, s))) return rc;
+    if ((rc = run_estimator(e, p, mask_out, 0, s))) return rc;
     {
         ProfScope ps(e, s, PC_PREP, 0);
         HIPCHK(e, launch_from_time_major(p.X, B, e->C, T, e->C, x_out, s));

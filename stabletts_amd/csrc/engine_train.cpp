@@ -43,7 +43,6 @@ struct TrainState {
     // fp32 parameter gradients, reference shapes, in ONE flat buffer: parameter-name order (st_param_info's), every slice starting
     // on a 64-byte boundary (goff; st_train_grad_offset).  gbase = where the running backward writes them: the engine's own
     // grad_flat (st_train_backward + st_param_grad) or a buffer of the caller (st_train_backward_part: no staging copy).
-    std::map<std::string, float*> grads;       // slices of grad_flat
     std::map<std::string, int64_t> goff;
     float* grad_flat = nullptr; int64_t grad_numel = 0;
     float* gbase = nullptr;
@@ -56,33 +55,45 @@ struct TrainState {
     bool have_fwd = false;
     int64_t serial = 0;                        // of the forward whose activations are held (have_fwd); counts st_train_forward calls
     bool packed = false;                       // dgrad weights match the current parameters
-    // saved tensors
+    // saved tensors: 16-bit operands of the decoder's own layers (time-major inputs, cond prenet pre-activations a* and
+    // activations p*, cond, the in_proj output) and the rounding residuals of the last block's output (the output projection's operand pair)
     void *mu16, *x16, *x16lo, *a1, *p1, *a2, *p2, *cond16, *cond16lo, *h0_16, *x3lo;
-    float *ada_pre, *dada_pre;                  // gin != hidden: output of adaLN_modulation.0 per block [L][N][C], and its gradient [N][C]
-    float *maskbuf, *kbias, *cvec, *tvals, *emb, *th_pre, *tau, *film, *ada, *cpart, *h0, *v32;
+    // gin != hidden: output of adaLN_modulation.0 per block [L][N][C], and its gradient [N][C]
+    float *ada_pre, *dada_pre;
+    // the mask and what mask_prep derives from it; per-item vectors (speaker, time MLP, FiLM and adaLN rows of every block)
+    float *maskbuf, *kbias, *cvec, *tvals, *emb, *th_pre, *tau, *film, *ada;
     int *n_full, *kv_end;
+    // fp32: the cond half of in_proj, the input of block 0, the output projection's result
+    float *cpart, *h0, *v32;
     std::vector<LayerAct> L;
-    // backward scratch
-    float *dX, *dskip[8], *tmpC, *tmpF, *Dbuf, *Fbuf, *abuf, *alphabuf, *vmean, *qmean, *kmean, *dq, *dk, *dv, *partial, *part_b, *red, *dada, *dfilm, *dtau, *dth, *demb, *dcvec,
-          *gin, *gsc;
-    unsigned *gbits, *dsmax, *qbits;
-    // one zeroed region per backward (a single memset in bwd_head): the maximum cells of every re-centring point (a group of
+    // backward scratch: the running gradient and the long-skip gradients, fp32 dgrad outputs (C / F / Mp wide)
+    float *dX, *dskip[8], *tmpC, *tmpF, *gin;
+    // attention backward: row statistics, the means q / k / v are centred on, d q / d k / d v
+    float *Dbuf, *Fbuf, *abuf, *alphabuf, *vmean, *qmean, *kmean, *dq, *dk, *dv;
+    // weight gradients: split-K partial planes and bias partials
+    float *partial, *part_b;
+    // gradients of the per-item vectors
+    float *dada, *dfilm, *dtau, *dth, *dcvec;
+    float* gsc = nullptr;                       // the pass-wide {scale, 1 / scale} pair current NOW: a slot of gsc_ring (bwd_begin: the first)
+    unsigned* gbits;                            // launch_grad_scale's maximum cell
+    // one zeroed region per backward (a single memset in bwd_begin): the maximum cells of every re-centring point (a group of
     // kMaxCellWords each), max |dq|, |dk|, |dv| per block (qbits_all + 4 i) and the dS bounds per block (dsmax_all + i N H)
     unsigned *zero_region = nullptr, *cells_ring = nullptr, *qbits_all = nullptr, *dsmax_all = nullptr; size_t zero_bytes = 0;
     int cell_idx = 0;
     float* gsc_ring = nullptr; int gsc_slots = 0;     // the pass-wide scale pair lives in a ring of slots: a re-centring point writes the NEXT slot (ts->gsc moves on)
     const float* skip_gsc[8] = {};                    // the slot each long-skip gradient was written under
     float* red_site[5] = {};                          // per-(item, chunk) partial sums of a block's five row kernels (one reduce launch per block)
-    unsigned *drop_rowh_all = nullptr, *drop_colh_all = nullptr; size_t drop_row_stride = 0, drop_col_stride = 0;   // dropout tables of every attention site
+    // dropout hash tables of every attention site (launch_drop_tables_multi): block i's at i * stride
+    unsigned *drop_rowh_all = nullptr, *drop_colh_all = nullptr; size_t drop_row_stride = 0, drop_col_stride = 0;
     bool fuse_ln = true;                        // ST_FUSE_TRAIN_LN=0: stand-alone residual / LayerNorm kernels after out-proj and FFN conv_2 (A/B)
     bool fuse_silu = true;                      // ST_FUSE_SILU=0: stand-alone silu_drop / silu_bwd kernels (A/B and the bit-identity test)
-    unsigned *drop_rowh, *drop_colh;            // dropout hash tables of the attention site being processed (launch_drop_tables)
-    float* skip_sc;                             // {scale, 1 / scale} each long-skip gradient was written at
     float* qs;                                  // local scales of the attention-input gradients (launch_qkv_grad_scales)
     // 16-bit gradient operands.  Every tensor a weight-gradient GEMM reads has its OWN buffer: the weight gradients run on a side
     // stream (below) and may still be reading when the main chain produces the next operand.
     enum { DY_FFN2, DY_FFN1, DY_OPROJ, DY_DATTN, DY_QKVD, DY_QKVW, DY_LSC, DY_HEAD, DY_T0, DY_T1, DY_T2, DY_T3, DY_COUNT };
     void* dy[DY_COUNT] = {};
+    // attention backward operands: v in natural rows (centred hi + lo pair), T-layout copies of q, k and d O; the
+    // transposed-copy weight-gradient path's X^T and dY^T
     void *vnat, *vnat_lo, *qT, *kT, *dOT, *xt, *dyt;
     // Side streams of the backward (ST_TRAIN_SIDE=0: everything on the caller's stream; results are bitwise identical either way):
     //   side  -- every weight-gradient GEMM + its reduction.  Nothing on the main chain reads their outputs; they only have to be
@@ -234,7 +245,6 @@ int train_prepare(st_engine* e, hipStream_t s) {
         HIPCHK(e, hipMalloc((void**)&ts->grad_flat, (size_t)total * 4)); ts->owned.push_back(ts->grad_flat);
         HIPCHK(e, hipMemsetAsync(ts->grad_flat, 0, (size_t)total * 4, s));      // (the alignment gaps are never written)
         ts->grad_numel = total;
-        for (auto& kv : ts->goff) ts->grads[kv.first] = ts->grad_flat + kv.second;
         ts->gbase = ts->grad_flat;
     }
     if ((rc = pk_end(e, e->pk_T, s))) return rc;
@@ -315,9 +325,8 @@ int layout_train(st_engine* e, TrainState* ts, int B, int T) {
                                                 (size_t)C, (size_t)C, (size_t)F, (size_t)F};
         for (int k = 0; k < TrainState::DY_COUNT; ++k) want(&ts->dy[k], R * w[k] * 2);
     }
-    want((void**)&ts->qs, (size_t)L * 64); want((void**)&ts->qbits, 16);      // qs: one 16-float record per block (the side stream's reduce reads it after the main chain has moved on)
-    want((void**)&ts->drop_rowh, (N * H * TT + 64) * 4); want((void**)&ts->drop_colh, (size_t)(Tp / 2 + 64) * 4);
-    want(&ts->vnat, R * C * 2); want(&ts->vnat_lo, R * C * 2); want((void**)&ts->dsmax, N * H * 4); want(&ts->qT, N * C * Tp * 2); want(&ts->kT, N * C * Tp * 2); want(&ts->dOT, N * C * Tp * 2);
+    want((void**)&ts->qs, (size_t)L * 64);      // one 16-float record per block (the side stream's reduce reads it after the main chain has moved on)
+    want(&ts->vnat, R * C * 2); want(&ts->vnat_lo, R * C * 2); want(&ts->qT, N * C * Tp * 2); want(&ts->kT, N * C * Tp * 2); want(&ts->dOT, N * C * Tp * 2);
     want((void**)&ts->Dbuf, N * H * TT * 4); want((void**)&ts->Fbuf, N * H * TT * 4); want((void**)&ts->abuf, N * H * TT * 4);
     want((void**)&ts->alphabuf, N * H * TT * 4);
     want((void**)&ts->vmean, N * H * 64 * 4); want((void**)&ts->qmean, N * H * 64 * 4); want((void**)&ts->kmean, N * H * 64 * 4);
@@ -347,7 +356,6 @@ int layout_train(st_engine* e, TrainState* ts, int B, int T) {
     ts->partial_cap = (size_t)16 * max_prod * 4;               // S * taps*Cin * Cout fp32 with S chosen to fit (see wgrad())
     want((void**)&ts->partial, ts->partial_cap);
     want((void**)&ts->part_b, (Rpad / 64) * max_cout * 4);
-    want((void**)&ts->red, N * (size_t)red_chunks(T) * 2 * 256 * 4);
     for (int k = 0; k < 5; ++k) want((void**)&ts->red_site[k], N * (size_t)red_chunks(T) * 2 * 256 * 4);
     ts->gsc_slots = 4 * L + 8;
     want((void**)&ts->gsc_ring, (size_t)ts->gsc_slots * 16);
@@ -359,9 +367,9 @@ int layout_train(st_engine* e, TrainState* ts, int B, int T) {
     ts->drop_row_stride = (size_t)N * H * TT + 64; ts->drop_col_stride = (size_t)(Tp / 2 + 64);
     want((void**)&ts->drop_rowh_all, (size_t)L * ts->drop_row_stride * 4); want((void**)&ts->drop_colh_all, (size_t)L * ts->drop_col_stride * 4);
     want((void**)&ts->dada, (size_t)L * N * 6 * C * 4); want_dec((void**)&ts->dfilm, (size_t)L * N * 2 * C * 4);
-    want_dec((void**)&ts->dtau, N * C * 4); want_dec((void**)&ts->dth, N * F * 4); want_dec((void**)&ts->demb, N * C * 4);
+    want_dec((void**)&ts->dtau, N * C * 4); want_dec((void**)&ts->dth, N * F * 4);
     want((void**)&ts->dcvec, N * G * 4);
-    want((void**)&ts->gsc, 16); want((void**)&ts->gbits, 16); want((void**)&ts->skip_sc, 64);
+    want((void**)&ts->gbits, 16);
     if (off > ts->ws_cap) {
         if (ts->ws) { HIPCHK(e, hipDeviceSynchronize()); HIPCHK(e, hipFree(ts->ws)); ts->ws = nullptr; ts->ws_cap = 0; }
         HIPCHK(e, hipMalloc((void**)&ts->ws, off));
@@ -369,6 +377,7 @@ int layout_train(st_engine* e, TrainState* ts, int B, int T) {
     }
     for (auto& sl : slots) *sl.dst = ts->ws + sl.off;
     if (!dec) for (int i = 0; i < L; ++i) ts->L[i].x1 = i == 0 ? ts->h0 : ts->L[i - 1].x3;
+    ts->gsc = nullptr;      // (a slot of the ring just laid out: bwd_begin points it at the first)
     ts->cells_ring = ts->zero_region;
     ts->qbits_all = ts->zero_region + (size_t)(4 * L + 8) * kMaxCellWords;
     ts->dsmax_all = ts->qbits_all + (size_t)4 * L;
@@ -395,6 +404,22 @@ void capture_train(st_engine* e, TrainState* ts, hipStream_t s) {
             capture(e, bn + "u", ts->L[i].u16, R * F, true, s);
         }
     }
+}
+
+// pre16 = conv(a), act16 = SiLU(pre16) [dropped out by dc, * mask]: the activation in the GEMM's epilogue where the phased tile runs
+// (bit-identical), else the stand-alone kernel.  mask: (mask_B, T), or nullptr for a site without mask and dropout (the cond prenet:
+// dc = no dropout, and the epilogue's dropout fields stay zero).
+int conv_silu(st_engine* e, TrainState* ts, ConvGemmArgs a, void* pre16, void* act16, const float* mask, int mask_B, const DropCfg& dc, hipStream_t s) {
+    a.out16 = pre16;
+    if (ts->fuse_silu && gemm_is_phased(e, 3, a)) {
+        a.act16 = act16;
+        if (mask) { a.mask = mask; a.drop_seed = dc.seed; a.drop_thresh16 = dc.thresh16; a.drop_scale = dc.scale; }
+        HIPCHK(e, gemm(e, 3, EPI_SILU, a, s));
+    } else {
+        HIPCHK(e, gemm(e, 3, EPI_F32, a, s));
+        HIPCHK(e, launch_silu_drop(e->dt, pre16, act16, mask, mask_B, ts->T, e->F, (int64_t)ts->B * ts->T, dc, s));
+    }
+    return ST_OK;
 }
 
 // The L DiT blocks of a training forward (diffusion_transformer.py:98-117), activations kept: the decoder's with FiLM on the
@@ -461,15 +486,8 @@ int fwd_blocks(st_engine* e, TrainState* ts, const float* m, float p_dropout, un
             }
         }
         {   // FFN (diffusion_transformer.py:25-30)
-            ConvGemmArgs a = cargs(e, e->ffn1[i], N, T, B); a.a0 = A.h2; a.c0 = C; a.out16 = A.a16;
-            const DropCfg dc = make_drop(p_dropout, seed, 2 * i);
-            if (ts->fuse_silu && gemm_is_phased(e, 3, a)) {      // SiLU + dropout + mask in the GEMM's epilogue (bit-identical)
-                a.act16 = A.u16; a.mask = m; a.drop_seed = dc.seed; a.drop_thresh16 = dc.thresh16; a.drop_scale = dc.scale;
-                HIPCHK(e, gemm(e, 3, EPI_SILU, a, s));
-            } else {
-                HIPCHK(e, gemm(e, 3, EPI_F32, a, s));
-                HIPCHK(e, launch_silu_drop(e->dt, A.a16, A.u16, m, B, T, F, R, dc, s));
-            }
+            ConvGemmArgs a = cargs(e, e->ffn1[i], N, T, B); a.a0 = A.h2; a.c0 = C;
+            if (int rc = conv_silu(e, ts, a, A.a16, A.u16, m, B, make_drop(p_dropout, seed, 2 * i), s)) return rc;
             a = cargs(e, e->ffn2[i], N, T, B); a.a0 = A.u16; a.c0 = F; a.mask = m;
             if (ts->fuse_ln) {      // f = (W2 u + b) * mask ; x3 = x2 + g_mlp * f (+ its 16-bit copies) in the GEMM's epilogue
                 a.gate = ada_i + 5 * C; a.gate_stride = 6 * C; a.res32 = A.x2; a.out32 = A.x3; a.branch32 = A.f32b;
@@ -491,6 +509,75 @@ int fwd_blocks(st_engine* e, TrainState* ts, const float* m, float p_dropout, un
     return ST_OK;
 }
 
+// ---- the frame both training forwards put around their own input staging and fwd_blocks
+// begin: dgrad weights, the arena for (B, T), the RoPE table; nothing is held until fwd_commit
+int fwd_begin(st_engine* e, int B, int T, float p_dropout, unsigned long long seed, hipStream_t s) {
+    int rc = train_prepare(e, s); if (rc) return rc;
+    TrainState* ts = e->train;
+    ts->have_fwd = false;
+    if ((rc = layout_train(e, ts, B, T))) return rc;
+    if ((rc = ensure_rope(e, T, s))) return rc;
+    ts->p_drop = p_dropout; ts->seed = seed;
+    return ST_OK;
+}
+
+// adaLN modulation of every block from c (diffusion_transformer.py:92-96: [Linear(gin, hidden) if gin != hidden else Identity,
+// SiLU, Linear(hidden, 6 hidden)]) and, for the decoder, FiLM (gamma, beta) from tau: per-item vectors, one launch per family and 8 blocks
+int fwd_modulation(st_engine* e, TrainState* ts, hipStream_t s) {
+    const int C = e->C, L = e->L, N = ts->B;
+    const bool dec = e->kind == KIND_DECODER;
+    for (int i0 = 0; i0 < L; i0 += 8) {
+        LinearJobs jf; memset(&jf, 0, sizeof(jf));
+        LinearJobs ja; memset(&ja, 0, sizeof(ja));
+        for (int i = i0; i < std::min(L, i0 + 8); ++i) {
+            if (dec) {
+                const std::string pf = "blocks." + std::to_string(i) + ".time_fusion.film.";
+                jf.in[jf.n] = ts->tau; jf.W[jf.n] = P(e, pf + "weight"); jf.bias[jf.n] = P(e, pf + "bias"); jf.out[jf.n] = ts->film + (size_t)i * N * 2 * C; jf.n += 1;
+            }
+            const std::string pa = e->blk(i) + "adaLN_modulation.2.";
+            const float* ain = ts->cvec;
+            if (e->G != C) {
+                const std::string p0 = e->blk(i) + "adaLN_modulation.0.";
+                float* pre = ts->ada_pre + (size_t)i * N * C;
+                HIPCHK(e, launch_linear(ts->cvec, N, e->G, P(e, p0 + "weight"), P(e, p0 + "bias"), C, pre, 0, 0, s));
+                ain = pre;
+            }
+            ja.in[ja.n] = ain; ja.W[ja.n] = P(e, pa + "weight"); ja.bias[ja.n] = P(e, pa + "bias"); ja.out[ja.n] = ts->ada + (size_t)i * N * 6 * C; ja.n += 1;
+        }
+        if (dec) HIPCHK(e, launch_linear_multi(jf, N, C, 2 * C, 0, 0, s));
+        HIPCHK(e, launch_linear_multi(ja, N, C, 6 * C, 1, 0, s));
+    }
+    return ST_OK;
+}
+
+// the dropout hash tables of all L attention sites, once: forward and backward read them.  Salts: attention site 2i + 1, FFN site 2i
+// (DropSeeds holds 16: st_create* admits no more blocks)
+int fwd_drop_tables(st_engine* e, TrainState* ts, hipStream_t s) {
+    const int L = e->L;
+    if (!make_drop(ts->p_drop, ts->seed, 1).thresh16) return ST_OK;
+    DropSeeds sd; memset(&sd, 0, sizeof(sd));
+    for (int i = 0; i < L; ++i) sd.seed[i] = make_drop(ts->p_drop, ts->seed, 2 * i + 1).seed;
+    HIPCHK(e, launch_drop_tables_multi(sd, L, ts->B * e->H * ts->T + 64, ts->Tp / 2, ts->drop_rowh_all, ts->drop_colh_all, ts->drop_row_stride, ts->drop_col_stride, s));
+    return ST_OK;
+}
+
+// v32 = (W x3 + b) * mask on the split-precision pair of the last block's output: final_proj (estimator.py:136-138) / proj (text_encoder.py:42)
+int fwd_out_proj(st_engine* e, TrainState* ts, hipStream_t s) {
+    const int C = e->C;
+    ConvGemmArgs a = cargs(e, e->fin, ts->B, ts->T, ts->B);
+    a.a0 = ts->L[e->L - 1].x3_16; a.c0 = C; a.a1 = ts->x3lo; a.c1 = C; a.c2 = C; a.mask = ts->maskbuf; a.flags = GF_MASK; a.out32 = ts->v32;
+    HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
+    return ST_OK;
+}
+
+// commit: forward #serial + 1 is held
+void fwd_commit(st_engine* e, TrainState* ts, hipStream_t s) {
+    capture_train(e, ts, s);
+    ts->have_fwd = true;
+    ts->serial += 1;
+    ts->gbase = ts->grad_flat; ts->next_part = 0;      // a pruned / abandoned multi-part backward of the previous forward leaves no state behind
+}
+
 }  // namespace
 
 }  // namespace sthost
@@ -507,15 +594,10 @@ int st_train_forward(st_engine* e, const float* t, const float* x, const float* 
     if ((rc = check_dropout(e, p_dropout))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = train_prepare(e, s))) return rc;
+    if ((rc = fwd_begin(e, B, T, p_dropout, seed, s))) return rc;
     TrainState* ts = e->train;
-    ts->have_fwd = false;
-    if ((rc = layout_train(e, ts, B, T))) return rc;
-    if ((rc = ensure_rope(e, T, s))) return rc;
     ProfScope prof(e, s, PC_TRAIN_FWD, 0);
-    const int C = e->C, F = e->F, Mp = e->Mp, L = e->L, H = e->H, N = B, Tp = ts->Tp;
-    const int64_t R = (int64_t)N * T;
-    ts->p_drop = p_dropout; ts->seed = seed;
+    const int C = e->C, F = e->F, Mp = e->Mp, N = B, Tp = ts->Tp;
     HIPCHK(e, launch_mask_prep(mask, B, T, Tp, ts->n_full, ts->kv_end, ts->kbias, nullptr, s));
     HIPCHK(e, launch_cvec_prep(mask, nullptr, B, T, ts->maskbuf, s));
     const float* m = ts->maskbuf;
@@ -527,51 +609,14 @@ int st_train_forward(st_engine* e, const float* t, const float* x, const float* 
     HIPCHK(e, launch_time_embed(ts->tvals, B, C, ts->emb, s));
     HIPCHK(e, launch_linear(ts->emb, B, C, P(e, "time_mlp.layer.0.weight"), P(e, "time_mlp.layer.0.bias"), F, ts->th_pre, 0, 0, s));
     HIPCHK(e, launch_linear(ts->th_pre, B, F, P(e, "time_mlp.layer.2.weight"), P(e, "time_mlp.layer.2.bias"), C, ts->tau, 1, 0, s));
-    // FiLM (gamma, beta) and adaLN modulation of every block: per-item vectors, one launch per family and 8 blocks (were 2 L launches)
-    for (int i0 = 0; i0 < L; i0 += 8) {
-        LinearJobs jf; memset(&jf, 0, sizeof(jf));
-        LinearJobs ja; memset(&ja, 0, sizeof(ja));
-        for (int i = i0; i < std::min(L, i0 + 8); ++i) {
-            const std::string pf = "blocks." + std::to_string(i) + ".time_fusion.film.";
-            jf.in[jf.n] = ts->tau; jf.W[jf.n] = P(e, pf + "weight"); jf.bias[jf.n] = P(e, pf + "bias"); jf.out[jf.n] = ts->film + (size_t)i * N * 2 * C; jf.n += 1;
-            const std::string pa = e->blk(i) + "adaLN_modulation.2.";
-            const float* ain = ts->cvec;       // adaLN_modulation = [Linear(gin, hidden) if gin != hidden else Identity, SiLU, Linear(hidden, 6 hidden)]
-            if (e->G != C) {                   // (diffusion_transformer.py:92-96)
-                const std::string p0 = e->blk(i) + "adaLN_modulation.0.";
-                float* pre = ts->ada_pre + (size_t)i * N * C;
-                HIPCHK(e, launch_linear(ts->cvec, N, e->G, P(e, p0 + "weight"), P(e, p0 + "bias"), C, pre, 0, 0, s));
-                ain = pre;
-            }
-            ja.in[ja.n] = ain; ja.W[ja.n] = P(e, pa + "weight"); ja.bias[ja.n] = P(e, pa + "bias"); ja.out[ja.n] = ts->ada + (size_t)i * N * 6 * C; ja.n += 1;
-        }
-        HIPCHK(e, launch_linear_multi(jf, B, C, 2 * C, 0, 0, s));
-        HIPCHK(e, launch_linear_multi(ja, N, C, 6 * C, 1, 0, s));
-    }
-    const DropCfg nodrop = make_drop(0.f, 0, 0);
-    if (make_drop(p_dropout, seed, 1).thresh16) {      // the hash tables of all L attention sites, once: forward and backward read them
-        DropSeeds sd; memset(&sd, 0, sizeof(sd));
-        if (L > 16) return e->fail(ST_ERR_INVALID, "training supports up to 16 blocks");
-        for (int i = 0; i < L; ++i) sd.seed[i] = make_drop(p_dropout, seed, 2 * i + 1).seed;
-        HIPCHK(e, launch_drop_tables_multi(sd, L, N * H * T + 64, Tp / 2, ts->drop_rowh_all, ts->drop_colh_all, ts->drop_row_stride, ts->drop_col_stride, s));
-    }
-    // cond prenet (estimator.py:83-89,118): pre-activations kept for SiLU'
-    {
-        // conv -> SiLU twice: the activation in the GEMM's epilogue where the phased kernel runs (as the FFN's, bit-identical)
-        auto conv_silu = [&](ConvGemmArgs a, void* pre16, void* act16) -> int {
-            a.out16 = pre16;
-            if (ts->fuse_silu && gemm_is_phased(e, 3, a)) {
-                a.act16 = act16;
-                HIPCHK(e, gemm(e, 3, EPI_SILU, a, s));
-            } else {
-                HIPCHK(e, gemm(e, 3, EPI_F32, a, s));
-                HIPCHK(e, launch_silu_drop(e->dt, pre16, act16, nullptr, 1, T, F, R, nodrop, s));
-            }
-            return ST_OK;
-        };
+    if ((rc = fwd_modulation(e, ts, s))) return rc;
+    if ((rc = fwd_drop_tables(e, ts, s))) return rc;
+    {   // cond prenet (estimator.py:83-89,118): conv -> SiLU twice, pre-activations kept for SiLU'
+        const DropCfg nodrop = make_drop(0.f, 0, 0);
         ConvGemmArgs a = cargs(e, e->pre[0], N, T, B); a.a0 = ts->mu16; a.c0 = Mp;
-        if ((rc = conv_silu(a, ts->a1, ts->p1))) return rc;
+        if ((rc = conv_silu(e, ts, a, ts->a1, ts->p1, nullptr, 1, nodrop, s))) return rc;
         a = cargs(e, e->pre[1], N, T, B); a.a0 = ts->p1; a.c0 = F;
-        if ((rc = conv_silu(a, ts->a2, ts->p2))) return rc;
+        if ((rc = conv_silu(e, ts, a, ts->a2, ts->p2, nullptr, 1, nodrop, s))) return rc;
         a = cargs(e, e->pre[2], N, T, B); a.a0 = ts->p2; a.c0 = F; a.out16 = ts->cond16; a.out16_lo = ts->cond16lo;
         HIPCHK(e, gemm(e, 3, EPI_F32, a, s));
         a = cargs(e, e->inc, N, T, B); a.a0 = ts->cond16; a.c0 = C; a.a1 = ts->cond16lo; a.c1 = C; a.c2 = C; a.out32 = ts->cpart;
@@ -584,25 +629,17 @@ int st_train_forward(st_engine* e, const float* t, const float* x, const float* 
         HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
     }
     if ((rc = fwd_blocks(e, ts, m, p_dropout, seed, s))) return rc;
-    {
-        ConvGemmArgs a = cargs(e, e->fin, N, T, B);
-        a.a0 = ts->L[L - 1].x3_16; a.c0 = C; a.a1 = ts->x3lo; a.c1 = C; a.c2 = C; a.mask = m; a.flags = GF_MASK; a.out32 = ts->v32;
-        HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
-    }
+    if ((rc = fwd_out_proj(e, ts, s))) return rc;
     HIPCHK(e, launch_from_time_major(ts->v32, B, e->M, T, Mp, out, s));
-    capture_train(e, ts, s);
-    ts->have_fwd = true;
-    ts->serial += 1;
-    ts->gbase = ts->grad_flat; ts->next_part = 0;      // a pruned / abandoned multi-part backward of the previous forward leaves no state behind
+    fwd_commit(e, ts, s);
     return ST_OK;
 }
 
 int64_t st_train_serial(const st_engine* e) {
-    if (e && reads_params_in_place(e->kind)) return e->sdt && e->sdt->have ? e->sdt->serial : 0;
-    if (e && e->kind == KIND_VOCODER) return e->sdt && e->sdt->have ? e->sdt->serial : 0;      // st_vocos_train_forward
-    if (e && e->kind == KIND_PERIOD_DISC) return e->sdt && e->sdt->have ? e->sdt->serial : 0;  // st_period_disc_train_forward
-    if (!e || !e->train || !e->train->have_fwd) return 0;
-    return e->train->serial;
+    if (!e) return 0;
+    // style encoder, duration predictor, vocoder (st_vocos_train_forward), period discriminator: the SdTrain protocol
+    if (e->kind != KIND_DECODER && e->kind != KIND_TEXT_ENCODER) return e->sdt && e->sdt->have ? e->sdt->serial : 0;
+    return e->train && e->train->have_fwd ? e->train->serial : 0;
 }
 
 // TextEncoder.forward (models/text_encoder.py:34-44) keeping the activations for st_text_encoder_train_backward: the embedding,
@@ -615,55 +652,24 @@ int st_text_encoder_train_forward(st_engine* e, const int64_t* tokens, const int
     if ((rc = check_dropout(e, p_dropout))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = train_prepare(e, s))) return rc;
+    if ((rc = fwd_begin(e, B, T, p_dropout, seed, s))) return rc;
     TrainState* ts = e->train;
-    ts->have_fwd = false;
-    if ((rc = layout_train(e, ts, B, T))) return rc;
-    if ((rc = ensure_rope(e, T, s))) return rc;
     ProfScope prof(e, s, PC_TRAIN_FWD, 0);
-    const int C = e->C, Mp = e->Mp, L = e->L, H = e->H, N = B, Tp = ts->Tp;
-    ts->p_drop = p_dropout; ts->seed = seed;
+    const int C = e->C, L = e->L;
     // x = emb[token] * sqrt(C) * mask (time-major fp32: block 0's input), the (B,1,T) mask, the ids the embedding backward sums by
     HIPCHK(e, launch_embed_tokens((const long long*)tokens, (const long long*)lengths, P(e, "emb.weight"), e->n_vocab, C,
                                   sqrtf((float)C), B, T, ts->h0, ts->maskbuf, s));
     HIPCHK(e, launch_emb_ids((const long long*)tokens, (const long long*)lengths, e->n_vocab, B, T, ts->ids, s));
-    HIPCHK(e, launch_mask_prep(ts->maskbuf, B, T, Tp, ts->n_full, ts->kv_end, ts->kbias, nullptr, s));
+    HIPCHK(e, launch_mask_prep(ts->maskbuf, B, T, ts->Tp, ts->n_full, ts->kv_end, ts->kbias, nullptr, s));
     HIPCHK(e, launch_cvec_prep(c, nullptr, B, e->G, ts->cvec, s));
-    const float* m = ts->maskbuf;
-    // adaLN modulation of every block (diffusion_transformer.py:92-96): one launch per 8 blocks
-    for (int i0 = 0; i0 < L; i0 += 8) {
-        LinearJobs ja; memset(&ja, 0, sizeof(ja));
-        for (int i = i0; i < std::min(L, i0 + 8); ++i) {
-            const std::string pa = e->blk(i) + "adaLN_modulation.2.";
-            const float* ain = ts->cvec;
-            if (e->G != C) {
-                const std::string p0 = e->blk(i) + "adaLN_modulation.0.";
-                float* pre = ts->ada_pre + (size_t)i * N * C;
-                HIPCHK(e, launch_linear(ts->cvec, N, e->G, P(e, p0 + "weight"), P(e, p0 + "bias"), C, pre, 0, 0, s));
-                ain = pre;
-            }
-            ja.in[ja.n] = ain; ja.W[ja.n] = P(e, pa + "weight"); ja.bias[ja.n] = P(e, pa + "bias"); ja.out[ja.n] = ts->ada + (size_t)i * N * 6 * C; ja.n += 1;
-        }
-        HIPCHK(e, launch_linear_multi(ja, N, C, 6 * C, 1, 0, s));
-    }
-    if (make_drop(p_dropout, seed, 1).thresh16) {      // the decoder's salt scheme: attention site 2i + 1, FFN site 2i
-        DropSeeds sd; memset(&sd, 0, sizeof(sd));
-        for (int i = 0; i < L; ++i) sd.seed[i] = make_drop(p_dropout, seed, 2 * i + 1).seed;
-        HIPCHK(e, launch_drop_tables_multi(sd, L, N * H * T + 64, Tp / 2, ts->drop_rowh_all, ts->drop_colh_all, ts->drop_row_stride, ts->drop_col_stride, s));
-    }
-    if ((rc = fwd_blocks(e, ts, m, p_dropout, seed, s))) return rc;
-    {   // mu_x = proj(x) * x_mask (text_encoder.py:42)
-        ConvGemmArgs a = cargs(e, e->fin, N, T, B);
-        a.a0 = ts->L[L - 1].x3_16; a.c0 = C; a.a1 = ts->x3lo; a.c1 = C; a.c2 = C; a.mask = m; a.flags = GF_MASK; a.out32 = ts->v32;
-        HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
-    }
+    if ((rc = fwd_modulation(e, ts, s))) return rc;
+    if ((rc = fwd_drop_tables(e, ts, s))) return rc;
+    if ((rc = fwd_blocks(e, ts, ts->maskbuf, p_dropout, seed, s))) return rc;
+    if ((rc = fwd_out_proj(e, ts, s))) return rc;
     HIPCHK(e, launch_from_time_major(ts->L[L - 1].x3, B, C, T, C, x_out, s));
-    HIPCHK(e, launch_from_time_major(ts->v32, B, e->M, T, Mp, mu_out, s));
+    HIPCHK(e, launch_from_time_major(ts->v32, B, e->M, T, e->Mp, mu_out, s));
     HIPCHK(e, hipMemcpyAsync(mask_out, ts->maskbuf, (size_t)B * T * 4, hipMemcpyDeviceToDevice, s));
-    capture_train(e, ts, s);
-    ts->have_fwd = true;
-    ts->serial += 1;
-    ts->gbase = ts->grad_flat; ts->next_part = 0;
+    fwd_commit(e, ts, s);
     return ST_OK;
 }
 
@@ -785,6 +791,31 @@ int recentre(st_engine* e, TrainState* ts, const BwdDims& d, bool have_max, hipS
 }
 inline unsigned* next_cells(TrainState* ts) { return ts->cells_ring + (size_t)ts->cell_idx * kMaxCellWords; }
 
+// Start of a backward.  ONE memset: the maximum cells of the re-centring points, the attention kernels' max / bound cells of every
+// block; the rings of cells and scale slots start over.  (d ada / d film rows, the per-item linears' gradients and d c / d tau are
+// WRITTEN by their first producer: no zero fills.)
+int bwd_begin(st_engine* e, TrainState* ts, hipStream_t s) {
+    HIPCHK(e, hipMemsetAsync(ts->zero_region, 0, ts->zero_bytes, s));
+    ts->cell_idx = 0; ts->gsc = ts->gsc_ring;
+    return ST_OK;
+}
+
+// dpre16 = dgrad(a) x SiLU'(pre16) [x the dropout of dc, * mask]: straight from the dgrad's epilogue where the phased tile runs, else
+// through fp32 tmpF and the stand-alone kernel.  mask as conv_silu's.
+int dgrad_silu(st_engine* e, TrainState* ts, ConvGemmArgs a, const void* pre16, void* dpre16, const float* mask, int mask_B, const DropCfg& dc, hipStream_t s) {
+    const int K = e->K;
+    if (ts->fuse_silu && K == 3 && gemm_is_phased(e, 3, a) && !a.bias) {
+        a.out16 = dpre16; a.dact16 = pre16;
+        if (mask) { a.mask = mask; a.drop_seed = dc.seed; a.drop_thresh16 = dc.thresh16; a.drop_scale = dc.scale; }
+        HIPCHK(e, gemm(e, K, EPI_SILU, a, s));
+    } else {
+        a.out32 = ts->tmpF;
+        HIPCHK(e, gemm(e, K, EPI_F32, a, s));
+        HIPCHK(e, launch_silu_bwd(e->dt, ts->tmpF, pre16, mask, mask_B, ts->T, e->F, (int64_t)ts->B * ts->T, dc, dpre16, s));
+    }
+    return ST_OK;
+}
+
 // out = (W x + b) * mask, the last layer of both trained modules (the decoder's final_proj, the text encoder's proj): the pass-wide
 // gradient scale from d out, d out as the masked 16-bit operand, its weight gradient on the side stream and dX = W^T d out.
 int bwd_out_proj(st_engine* e, TrainState* ts, const float* grad_out, const char* name, hipStream_t s) {
@@ -810,10 +841,7 @@ int bwd_head(st_engine* e, TrainState* ts, const float* grad_out, hipStream_t s)
     const int64_t R = d.R;
     int rc;
     const bool cap = e->capture;
-    // ONE memset per backward: the maximum cells of the re-centring points, the attention kernels' max / bound cells of every block.
-    // (d ada / d film rows, the per-item linears' gradients and d c / d tau are WRITTEN by their first producer: no zero fills.)
-    HIPCHK(e, hipMemsetAsync(ts->zero_region, 0, ts->zero_bytes, s));
-    ts->cell_idx = 0; ts->gsc = ts->gsc_ring;
+    if ((rc = bwd_begin(e, ts, s))) return rc;
     if ((rc = bwd_out_proj(e, ts, grad_out, "final_proj", s))) return rc;
     if (cap) { capture(e, "g.scale", ts->gsc, 2, false, s); capture(e, "g.x3_" + std::to_string(L - 1), ts->dX, R * C, false, s); }
     return ST_OK;
@@ -841,164 +869,149 @@ int bwd_block(st_engine* e, TrainState* ts, int i, hipStream_t s) {
         if ((rc = attn_prep(e, ts, i, ts->side2.on(s)))) return rc;
         HIPCHK(e, ts->side2.record_join());
     }
-    {
-        LayerAct& A = ts->L[i];
-        const std::string b = e->blk(i);
-        const float* ada_i = ts->ada + (size_t)i * N * 6 * C;
-        float* dada_i = ts->dada + (size_t)i * N * 6 * C;
-        // The gradient's magnitude changes by orders of magnitude from block to block (FiLM's gamma multiplies the whole residual
-        // stream: ~0.05 at initialisation) and, with trained-like weights, inside a block: the pass-wide power-of-two scale is
-        // re-centred on the running gradient here and after each LayerNorm backward (recentre), so that every 16-bit operand
-        // derived from it sits in f16's range.  Every fp32 result is un-scaled by the pair current at the time it is written; a
-        // long-skip gradient remembers the scale it was written at (skip_sc) and is converted when it is added.
-        // (block i + 1 wrote dX last through add_rescaled -- which published the maximum -- when it lies in the first half, else through a GEMM;
-        // in the text encoder through mask_bwd, which publishes it too)
-        const bool dec = e->kind == KIND_DECODER;
-        if (i < L - 1 && (rc = recentre(e, ts, d, !dec || i + 1 < L / 2, s))) return rc;
-        if (cap) capture(e, "g.scale_" + std::to_string(i), ts->gsc, 2, false, s);      // the scale block i's captured tensors carry
-        RedSites sites; memset(&sites, 0, sizeof(sites));      // the block's per-(item, channel) sums: ONE reduce launch at its end
-        auto site = [&](int k, int K, float* out, int out_stride, int off0, int off1) {
-            sites.s[sites.n] = RedSite{ts->red_site[k], K, out, out_stride, {off0, off1}, ts->gsc};      // the pair current NOW un-scales these sums
-            sites.n += 1;
-            return ts->red_site[k];
-        };
-        // ---- x3 = x2 + g_mlp * f
-        HIPCHK(e, ts->side.wait_site(TrainState::DY_FFN2, s));
-        HIPCHK(e, launch_gate_bwd(e->dt, ts->dX, A.f32b, ada_i + 5 * C, 6 * C, m, B, T, N, ts->dy[TrainState::DY_FFN2], site(0, 1, dada_i, 6 * C, 5 * C, 0), s));
-        {   // conv_2
-            WgradOut o = {G(ts, b + "mlp.conv_2.weight"), F, 0, F, 0, C, G(ts, b + "mlp.conv_2.bias")};
-            if ((rc = wgrad_side(e, ts, TrainState::DY_FFN2, A.u16, F, nullptr, 0, C, K, &o, 1, s))) return rc;
-            HIPCHK(e, ts->side.wait_site(TrainState::DY_FFN1, s));
-            ConvGemmArgs a = cargs(e, ts->ffn2T[i], N, T, B); a.a0 = ts->dy[TrainState::DY_FFN2]; a.c0 = C;
-            const DropCfg dc = make_drop(ts->p_drop, ts->seed, 2 * i);
-            if (ts->fuse_silu && K == 3 && gemm_is_phased(e, 3, a) && !a.bias) {      // d pre-activation straight from the dgrad's epilogue
-                a.out16 = ts->dy[TrainState::DY_FFN1]; a.dact16 = A.a16; a.mask = m; a.drop_seed = dc.seed; a.drop_thresh16 = dc.thresh16; a.drop_scale = dc.scale;
-                HIPCHK(e, gemm(e, K, EPI_SILU, a, s));
-            } else {
-                a.out32 = ts->tmpF;
-                HIPCHK(e, gemm(e, K, EPI_F32, a, s));
-                HIPCHK(e, launch_silu_bwd(e->dt, ts->tmpF, A.a16, m, B, T, F, R, dc, ts->dy[TrainState::DY_FFN1], s));
-            }
-        }
-        {   // conv_1
-            WgradOut o = {G(ts, b + "mlp.conv_1.weight"), C, 0, C, 0, F, G(ts, b + "mlp.conv_1.bias")};
-            if ((rc = wgrad_side(e, ts, TrainState::DY_FFN1, A.h2, C, nullptr, 0, F, K, &o, 1, s))) return rc;
-            ConvGemmArgs a = cargs(e, ts->ffn1T[i], N, T, B); a.a0 = ts->dy[TrainState::DY_FFN1]; a.c0 = F; a.out32 = ts->tmpC;
-            HIPCHK(e, gemm(e, K, EPI_F32, a, s));
-        }
-        HIPCHK(e, launch_ln_bwd(A.x2, ts->tmpC, ada_i, 6 * C, 4 * C, m, B, 1, T, N, ts->dX, site(1, 2, dada_i, 6 * C, 4 * C, 3 * C), nullptr, next_cells(ts), s));
-        if (cap) capture(e, "g.x2_" + std::to_string(i), ts->dX, R * C, false, s);
-        if ((rc = recentre(e, ts, d, true, s))) return rc;
-        if (cap) capture(e, "g.scale_a" + std::to_string(i), ts->gsc, 2, false, s);      // the scale of this block's attention-part tensors
-        // ---- x2 = x1 + g_msa * o
-        HIPCHK(e, ts->side.wait_site(TrainState::DY_OPROJ, s));
-        HIPCHK(e, launch_gate_bwd(e->dt, ts->dX, A.o32, ada_i + 2 * C, 6 * C, m, B, T, N, ts->dy[TrainState::DY_OPROJ], site(2, 1, dada_i, 6 * C, 2 * C, 0), s));
-        {   // out projection
-            WgradOut o = {G(ts, b + "attn.conv_o.weight"), C, 0, C, 0, C, G(ts, b + "attn.conv_o.bias")};
-            if ((rc = wgrad_side(e, ts, TrainState::DY_OPROJ, A.attn16, C, nullptr, 0, C, 1, &o, 1, s))) return rc;
-            ConvGemmArgs a = cargs(e, ts->oprojT[i], N, T, B); a.a0 = ts->dy[TrainState::DY_OPROJ]; a.c0 = C; a.out16 = ts->dy[TrainState::DY_DATTN];      // d attn (16 bit)
-            HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
-        }
-        {   // attention
-            if (ts->use_side) HIPCHK(e, ts->side2.join(s));      // the operand copies forked at the start of the block
-            else if ((rc = attn_prep(e, ts, i, s))) return rc;
-            HIPCHK(e, launch_attn_to_T(e->dt, ts->dy[TrainState::DY_DATTN], (int64_t)T * C, 64, C, N, H, T, Tp, nullptr, ts->dOT, s));
-            AttnBwdArgs a; memset(&a, 0, sizeof(a));
-            a.q = A.q; a.k = A.k; a.v = ts->vnat; a.vlo = ts->vnat_lo; a.dsmax = ts->dsmax; a.qT = ts->qT; a.kT = ts->kT; a.dOT = ts->dOT;
-            a.dO = ts->dy[TrainState::DY_DATTN]; a.dO_row_stride = C; a.lse = A.lse; a.vmean = ts->vmean; a.qmean = ts->qmean; a.kmean = ts->kmean;
-            a.Dq = ts->Dbuf; a.Fq = ts->Fbuf; a.aq = ts->abuf; a.alphaq = ts->alphabuf; a.kbias = ts->kbias; a.mask_mod = B;
-            a.kv_end = ts->kv_end; a.dq = ts->dq; a.dk = ts->dk; a.dv = ts->dv; a.T = T; a.Tp = Tp; a.H = H; a.n_items = N;
-            a.drop = make_drop(ts->p_drop, ts->seed, 2 * i + 1); a.zeros = e->zeros;
-            if (a.drop.thresh16) { a.drop.rowh = ts->drop_rowh_all + (size_t)i * ts->drop_row_stride; a.drop.colh = ts->drop_colh_all + (size_t)i * ts->drop_col_stride; }
-            unsigned* qbits = ts->qbits_all + 4 * i;      // (zeroed with the rest of zero_region in bwd_head)
-            a.dsmax = ts->dsmax_all + (size_t)i * N * H;
-            a.gmax = qbits;              // the kernels publish max |dq|, |dk|, |dv| themselves
-            HIPCHK(e, launch_attn_bwd_dq(e->dt, a, s));
-            HIPCHK(e, launch_attn_bwd_dkv(e->dt, a, s));
-            // d q, d k are ~1/T of d v: each gets its own power-of-two factor before the rounding to 16 bits (f16's normal
-            // range ends at 6e-5); the fused dgrad GEMM takes the copy with one common factor
-            float* qs = ts->qs + 16 * i;
-            HIPCHK(e, launch_qkv_grad_scales(ts->dq, ts->dk, ts->dv, R * C, ts->gsc, qbits, qs, s, true));
-            HIPCHK(e, ts->side.wait_site(TrainState::DY_QKVW, s));
-            HIPCHK(e, launch_qkv_grad_pack(e->dt, ts->dq, ts->dk, ts->dv, e->rope_cos, e->rope_sin, N, H, T, qs, ts->dy[TrainState::DY_QKVD], ts->dy[TrainState::DY_QKVW], s));
-        }
-        if (cap) { capture(e, "g.dq_" + std::to_string(i), ts->dq, R * C, false, s); capture(e, "g.dk_" + std::to_string(i), ts->dk, R * C, false, s);
-                   capture(e, "g.dv_" + std::to_string(i), ts->dv, R * C, false, s); capture(e, "g.dattn_" + std::to_string(i), ts->dy[TrainState::DY_DATTN], R * C, true, s); }
-        {   // fused q/k/v projection
-            WgradOut o[3];
-            int r = 0;
-            for (const char* nm : {"q", "k", "v"}) {
-                o[r] = {G(ts, b + "attn.conv_" + nm + ".weight"), C, 0, C, r * C, C, G(ts, b + "attn.conv_" + nm + ".bias"), ts->qs + 16 * i + 2 + 2 * r};
-                ++r;
-            }
-            if ((rc = wgrad_side(e, ts, TrainState::DY_QKVW, A.h1, C, nullptr, 0, 3 * C, 1, o, 3, s))) return rc;
-            ConvGemmArgs a = cargs(e, ts->qkvT[i], N, T, B); a.a0 = ts->dy[TrainState::DY_QKVD]; a.c0 = 3 * C; a.out32 = ts->tmpC;
-            HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
-        }
-        HIPCHK(e, launch_ln_bwd(A.x1, ts->tmpC, ada_i, 6 * C, C, m, B, 0, T, N, ts->dX, site(3, 2, dada_i, 6 * C, C, 0), ts->qs + 16 * i, next_cells(ts), s));
-        if (cap) capture(e, "g.x1_" + std::to_string(i), ts->dX, R * C, false, s);
-        if ((rc = recentre(e, ts, d, true, s))) return rc;
-        if (cap) capture(e, "g.scale_b" + std::to_string(i), ts->gsc, 2, false, s);      // ... and of what follows (g.xin_i)
-        // ---- x1 = (gamma * xpre + beta) * mask  (text encoder: x1 = xpre * mask)
-        if (!dec) {
-            HIPCHK(e, launch_mask_bwd(m, B, T, N, ts->dX, i > 0 ? next_cells(ts) : nullptr, s));
-        } else {
-            if (i >= L / 2) HIPCHK(e, ts->side.wait_site(TrainState::DY_LSC, s));
-            HIPCHK(e, launch_film_bwd(e->dt, xpre_of(ts, i, L), ts->film + (size_t)i * N * 2 * C, 2 * C, N, m, B, T, N, ts->dX,
-                                      i >= L / 2 ? ts->dy[TrainState::DY_LSC] : nullptr, site(4, 2, ts->dfilm + (size_t)i * N * 2 * C, 2 * C, 0, C), s));
-        }
-        HIPCHK(e, launch_reduce_sites(sites, N, chunks, s));
-        if (dec && i >= L / 2) {   // long-skip conv: xpre_i = W [x3_{i-1} ; skip] + b
-            const int j = i - L / 2, src = L - 1 - i;
-            const std::string n = "lsc_layers." + std::to_string(j);
-            const void* skip16 = src == 0 ? ts->h0_16 : ts->L[src - 1].x3_16;
-            WgradOut o = {G(ts, n + ".weight"), 2 * C, 0, 2 * C, 0, C, G(ts, n + ".bias")};
-            if ((rc = wgrad_side(e, ts, TrainState::DY_LSC, ts->L[i - 1].x3_16, C, skip16, C, C, K, &o, 1, s))) return rc;
-            ConvGemmArgs a = cargs(e, ts->lscTb[j], N, T, B); a.a0 = ts->dy[TrainState::DY_LSC]; a.c0 = C; a.out32 = ts->dskip[src];
-            ts->skip_gsc[src] = ts->gsc;      // the slot this long-skip gradient is written under (slots are never rewritten within a backward)
-            HIPCHK(e, gemm(e, K, EPI_F32, a, s));
-            a = cargs(e, ts->lscTa[j], N, T, B); a.a0 = ts->dy[TrainState::DY_LSC]; a.c0 = C; a.out32 = ts->dX;
-            HIPCHK(e, gemm(e, K, EPI_F32, a, s));
-        }
-        // x3_{i-1} (or the in_proj output) is also a long-skip source of a later block: add that gradient
-        if (dec && i < L / 2) HIPCHK(e, launch_add_rescaled(ts->dX, ts->dskip[i], R * C, ts->gsc, ts->skip_gsc[i], i > 0 ? next_cells(ts) : nullptr, s));
-        if (cap) capture(e, "g.xin_" + std::to_string(i), ts->dX, R * C, false, s);
+    LayerAct& A = ts->L[i];
+    const std::string b = e->blk(i);
+    const float* ada_i = ts->ada + (size_t)i * N * 6 * C;
+    float* dada_i = ts->dada + (size_t)i * N * 6 * C;
+    // The gradient's magnitude changes by orders of magnitude from block to block (FiLM's gamma multiplies the whole residual
+    // stream: ~0.05 at initialisation) and, with trained-like weights, inside a block: the pass-wide power-of-two scale is
+    // re-centred on the running gradient here and after each LayerNorm backward (recentre), so that every 16-bit operand
+    // derived from it sits in f16's range.  Every fp32 result is un-scaled by the pair current at the time it is written; a
+    // long-skip gradient remembers the slot of the scale it was written at (skip_gsc) and is converted when it is added.
+    // (block i + 1 wrote dX last through add_rescaled -- which published the maximum -- when it lies in the first half, else through a GEMM;
+    // in the text encoder through mask_bwd, which publishes it too)
+    const bool dec = e->kind == KIND_DECODER;
+    if (i < L - 1 && (rc = recentre(e, ts, d, !dec || i + 1 < L / 2, s))) return rc;
+    if (cap) capture(e, "g.scale_" + std::to_string(i), ts->gsc, 2, false, s);      // the scale block i's captured tensors carry
+    RedSites sites; memset(&sites, 0, sizeof(sites));      // the block's per-(item, channel) sums: ONE reduce launch at its end
+    auto site = [&](int k, int K, float* out, int out_stride, int off0, int off1) {
+        sites.s[sites.n] = RedSite{ts->red_site[k], K, out, out_stride, {off0, off1}, ts->gsc};      // the pair current NOW un-scales these sums
+        sites.n += 1;
+        return ts->red_site[k];
+    };
+    // ---- x3 = x2 + g_mlp * f
+    HIPCHK(e, ts->side.wait_site(TrainState::DY_FFN2, s));
+    HIPCHK(e, launch_gate_bwd(e->dt, ts->dX, A.f32b, ada_i + 5 * C, 6 * C, m, B, T, N, ts->dy[TrainState::DY_FFN2], site(0, 1, dada_i, 6 * C, 5 * C, 0), s));
+    {   // conv_2
+        WgradOut o = {G(ts, b + "mlp.conv_2.weight"), F, 0, F, 0, C, G(ts, b + "mlp.conv_2.bias")};
+        if ((rc = wgrad_side(e, ts, TrainState::DY_FFN2, A.u16, F, nullptr, 0, C, K, &o, 1, s))) return rc;
+        HIPCHK(e, ts->side.wait_site(TrainState::DY_FFN1, s));
+        ConvGemmArgs a = cargs(e, ts->ffn2T[i], N, T, B); a.a0 = ts->dy[TrainState::DY_FFN2]; a.c0 = C;
+        if ((rc = dgrad_silu(e, ts, a, A.a16, ts->dy[TrainState::DY_FFN1], m, B, make_drop(ts->p_drop, ts->seed, 2 * i), s))) return rc;
     }
-    {   // this block's per-item linears: adaLN modulation (-> d c), FiLM (-> d tau); its d ada / d film rows are complete now.
-        // Every weight / bias gradient here has ONE producer (written, not accumulated: no zero fills); d c and d tau add up over
-        // the blocks: the first block of a backward (L - 1) writes them, the others accumulate.
-        if (e->G == C) return ST_OK;      // the usual case: the linears of all blocks of a backward part run batched at its end (bwd_linears)
-        const int acc = i == L - 1 ? 0 : 1;
-        const std::string pa = e->blk(i) + "adaLN_modulation.2.";
-        float* gw = G(ts, pa + "weight"); float* gb = G(ts, pa + "bias");
-        const float* dout = ts->dada + (size_t)i * N * 6 * C;
-        if (e->G == C) {
-            HIPCHK(e, launch_linear_bwd_w(ts->cvec, dout, N, C, 6 * C, 1, gw, gb, 0, s));
-            HIPCHK(e, launch_linear_bwd_in(ts->cvec, dout, P(e, pa + "weight"), N, C, 6 * C, 1, ts->dcvec, acc, s));
-        } else {        // through SiLU into adaLN_modulation.0, then into c
-            const std::string p0 = e->blk(i) + "adaLN_modulation.0.";
-            const float* pre = ts->ada_pre + (size_t)i * N * C;
-            float* g0w = G(ts, p0 + "weight"); float* g0b = G(ts, p0 + "bias");
-            HIPCHK(e, launch_linear_bwd_w(pre, dout, N, C, 6 * C, 1, gw, gb, 0, s));
-            HIPCHK(e, launch_linear_bwd_in(pre, dout, P(e, pa + "weight"), N, C, 6 * C, 1, ts->dada_pre, 0, s));
-            HIPCHK(e, launch_linear_bwd_w(ts->cvec, ts->dada_pre, N, e->G, C, 0, g0w, g0b, 0, s));
-            HIPCHK(e, launch_linear_bwd_in(ts->cvec, ts->dada_pre, P(e, p0 + "weight"), N, e->G, C, 0, ts->dcvec, acc, s));
-        }
-        if (e->kind != KIND_DECODER) return ST_OK;      // (the text encoder's blocks have no FiLM)
-        const std::string pf = "blocks." + std::to_string(i) + ".time_fusion.film.";
-        gw = G(ts, pf + "weight"); gb = G(ts, pf + "bias");
-        const float* dfo = ts->dfilm + (size_t)i * N * 2 * C;
-        HIPCHK(e, launch_linear_bwd_w(ts->tau, dfo, N, C, 2 * C, 0, gw, gb, 0, s));
-        HIPCHK(e, launch_linear_bwd_in(ts->tau, dfo, P(e, pf + "weight"), N, C, 2 * C, 0, ts->dtau, acc, s));
+    {   // conv_1
+        WgradOut o = {G(ts, b + "mlp.conv_1.weight"), C, 0, C, 0, F, G(ts, b + "mlp.conv_1.bias")};
+        if ((rc = wgrad_side(e, ts, TrainState::DY_FFN1, A.h2, C, nullptr, 0, F, K, &o, 1, s))) return rc;
+        ConvGemmArgs a = cargs(e, ts->ffn1T[i], N, T, B); a.a0 = ts->dy[TrainState::DY_FFN1]; a.c0 = F; a.out32 = ts->tmpC;
+        HIPCHK(e, gemm(e, K, EPI_F32, a, s));
     }
+    HIPCHK(e, launch_ln_bwd(A.x2, ts->tmpC, ada_i, 6 * C, 4 * C, m, B, 1, T, N, ts->dX, site(1, 2, dada_i, 6 * C, 4 * C, 3 * C), nullptr, next_cells(ts), s));
+    if (cap) capture(e, "g.x2_" + std::to_string(i), ts->dX, R * C, false, s);
+    if ((rc = recentre(e, ts, d, true, s))) return rc;
+    if (cap) capture(e, "g.scale_a" + std::to_string(i), ts->gsc, 2, false, s);      // the scale of this block's attention-part tensors
+    // ---- x2 = x1 + g_msa * o
+    HIPCHK(e, ts->side.wait_site(TrainState::DY_OPROJ, s));
+    HIPCHK(e, launch_gate_bwd(e->dt, ts->dX, A.o32, ada_i + 2 * C, 6 * C, m, B, T, N, ts->dy[TrainState::DY_OPROJ], site(2, 1, dada_i, 6 * C, 2 * C, 0), s));
+    {   // out projection
+        WgradOut o = {G(ts, b + "attn.conv_o.weight"), C, 0, C, 0, C, G(ts, b + "attn.conv_o.bias")};
+        if ((rc = wgrad_side(e, ts, TrainState::DY_OPROJ, A.attn16, C, nullptr, 0, C, 1, &o, 1, s))) return rc;
+        ConvGemmArgs a = cargs(e, ts->oprojT[i], N, T, B); a.a0 = ts->dy[TrainState::DY_OPROJ]; a.c0 = C; a.out16 = ts->dy[TrainState::DY_DATTN];      // d attn (16 bit)
+        HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
+    }
+    {   // attention
+        if (ts->use_side) HIPCHK(e, ts->side2.join(s));      // the operand copies forked at the start of the block
+        else if ((rc = attn_prep(e, ts, i, s))) return rc;
+        HIPCHK(e, launch_attn_to_T(e->dt, ts->dy[TrainState::DY_DATTN], (int64_t)T * C, 64, C, N, H, T, Tp, nullptr, ts->dOT, s));
+        AttnBwdArgs a; memset(&a, 0, sizeof(a));
+        a.q = A.q; a.k = A.k; a.v = ts->vnat; a.vlo = ts->vnat_lo; a.qT = ts->qT; a.kT = ts->kT; a.dOT = ts->dOT;
+        a.dO = ts->dy[TrainState::DY_DATTN]; a.dO_row_stride = C; a.lse = A.lse; a.vmean = ts->vmean; a.qmean = ts->qmean; a.kmean = ts->kmean;
+        a.Dq = ts->Dbuf; a.Fq = ts->Fbuf; a.aq = ts->abuf; a.alphaq = ts->alphabuf; a.kbias = ts->kbias; a.mask_mod = B;
+        a.kv_end = ts->kv_end; a.dq = ts->dq; a.dk = ts->dk; a.dv = ts->dv; a.T = T; a.Tp = Tp; a.H = H; a.n_items = N;
+        a.drop = make_drop(ts->p_drop, ts->seed, 2 * i + 1); a.zeros = e->zeros;
+        if (a.drop.thresh16) { a.drop.rowh = ts->drop_rowh_all + (size_t)i * ts->drop_row_stride; a.drop.colh = ts->drop_colh_all + (size_t)i * ts->drop_col_stride; }
+        unsigned* qbits = ts->qbits_all + 4 * i;      // (zeroed with the rest of zero_region in bwd_begin)
+        a.dsmax = ts->dsmax_all + (size_t)i * N * H;
+        a.gmax = qbits;              // the kernels publish max |dq|, |dk|, |dv| themselves
+        HIPCHK(e, launch_attn_bwd_dq(e->dt, a, s));
+        HIPCHK(e, launch_attn_bwd_dkv(e->dt, a, s));
+        // d q, d k are ~1/T of d v: each gets its own power-of-two factor before the rounding to 16 bits (f16's normal
+        // range ends at 6e-5); the fused dgrad GEMM takes the copy with one common factor
+        float* qs = ts->qs + 16 * i;
+        HIPCHK(e, launch_qkv_grad_scales(ts->dq, ts->dk, ts->dv, R * C, ts->gsc, qbits, qs, s, true));
+        HIPCHK(e, ts->side.wait_site(TrainState::DY_QKVW, s));
+        HIPCHK(e, launch_qkv_grad_pack(e->dt, ts->dq, ts->dk, ts->dv, e->rope_cos, e->rope_sin, N, H, T, qs, ts->dy[TrainState::DY_QKVD], ts->dy[TrainState::DY_QKVW], s));
+    }
+    if (cap) { capture(e, "g.dq_" + std::to_string(i), ts->dq, R * C, false, s); capture(e, "g.dk_" + std::to_string(i), ts->dk, R * C, false, s);
+               capture(e, "g.dv_" + std::to_string(i), ts->dv, R * C, false, s); capture(e, "g.dattn_" + std::to_string(i), ts->dy[TrainState::DY_DATTN], R * C, true, s); }
+    {   // fused q/k/v projection
+        WgradOut o[3];
+        int r = 0;
+        for (const char* nm : {"q", "k", "v"}) {
+            o[r] = {G(ts, b + "attn.conv_" + nm + ".weight"), C, 0, C, r * C, C, G(ts, b + "attn.conv_" + nm + ".bias"), ts->qs + 16 * i + 2 + 2 * r};
+            ++r;
+        }
+        if ((rc = wgrad_side(e, ts, TrainState::DY_QKVW, A.h1, C, nullptr, 0, 3 * C, 1, o, 3, s))) return rc;
+        ConvGemmArgs a = cargs(e, ts->qkvT[i], N, T, B); a.a0 = ts->dy[TrainState::DY_QKVD]; a.c0 = 3 * C; a.out32 = ts->tmpC;
+        HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
+    }
+    HIPCHK(e, launch_ln_bwd(A.x1, ts->tmpC, ada_i, 6 * C, C, m, B, 0, T, N, ts->dX, site(3, 2, dada_i, 6 * C, C, 0), ts->qs + 16 * i, next_cells(ts), s));
+    if (cap) capture(e, "g.x1_" + std::to_string(i), ts->dX, R * C, false, s);
+    if ((rc = recentre(e, ts, d, true, s))) return rc;
+    if (cap) capture(e, "g.scale_b" + std::to_string(i), ts->gsc, 2, false, s);      // ... and of what follows (g.xin_i)
+    // ---- x1 = (gamma * xpre + beta) * mask  (text encoder: x1 = xpre * mask)
+    if (!dec) {
+        HIPCHK(e, launch_mask_bwd(m, B, T, N, ts->dX, i > 0 ? next_cells(ts) : nullptr, s));
+    } else {
+        if (i >= L / 2) HIPCHK(e, ts->side.wait_site(TrainState::DY_LSC, s));
+        HIPCHK(e, launch_film_bwd(e->dt, xpre_of(ts, i, L), ts->film + (size_t)i * N * 2 * C, 2 * C, N, m, B, T, N, ts->dX,
+                                  i >= L / 2 ? ts->dy[TrainState::DY_LSC] : nullptr, site(4, 2, ts->dfilm + (size_t)i * N * 2 * C, 2 * C, 0, C), s));
+    }
+    HIPCHK(e, launch_reduce_sites(sites, N, chunks, s));
+    if (dec && i >= L / 2) {   // long-skip conv: xpre_i = W [x3_{i-1} ; skip] + b
+        const int j = i - L / 2, src = L - 1 - i;
+        const std::string n = "lsc_layers." + std::to_string(j);
+        const void* skip16 = src == 0 ? ts->h0_16 : ts->L[src - 1].x3_16;
+        WgradOut o = {G(ts, n + ".weight"), 2 * C, 0, 2 * C, 0, C, G(ts, n + ".bias")};
+        if ((rc = wgrad_side(e, ts, TrainState::DY_LSC, ts->L[i - 1].x3_16, C, skip16, C, C, K, &o, 1, s))) return rc;
+        ConvGemmArgs a = cargs(e, ts->lscTb[j], N, T, B); a.a0 = ts->dy[TrainState::DY_LSC]; a.c0 = C; a.out32 = ts->dskip[src];
+        ts->skip_gsc[src] = ts->gsc;      // the slot this long-skip gradient is written under (slots are never rewritten within a backward)
+        HIPCHK(e, gemm(e, K, EPI_F32, a, s));
+        a = cargs(e, ts->lscTa[j], N, T, B); a.a0 = ts->dy[TrainState::DY_LSC]; a.c0 = C; a.out32 = ts->dX;
+        HIPCHK(e, gemm(e, K, EPI_F32, a, s));
+    }
+    // x3_{i-1} (or the in_proj output) is also a long-skip source of a later block: add that gradient
+    if (dec && i < L / 2) HIPCHK(e, launch_add_rescaled(ts->dX, ts->dskip[i], R * C, ts->gsc, ts->skip_gsc[i], i > 0 ? next_cells(ts) : nullptr, s));
+    if (cap) capture(e, "g.xin_" + std::to_string(i), ts->dX, R * C, false, s);
+    return ST_OK;
+}
+
+// gin != hidden: block i's per-item linears right after bwd_block(i), whose d ada / d film rows are complete then -- adaLN modulation
+// through SiLU into adaLN_modulation.0 and on into d c, FiLM into d tau.  (gin == hidden: batched per backward part, bwd_linears.)
+// Every weight / bias gradient here has ONE producer (written, not accumulated: no zero fills); d c and d tau add up over
+// the blocks: the first block of a backward (L - 1) writes them, the others accumulate.
+int bwd_block_linears(st_engine* e, TrainState* ts, int i, hipStream_t s) {
+    const int C = e->C, L = e->L, N = ts->B;
+    const int acc = i == L - 1 ? 0 : 1;
+    const std::string pa = e->blk(i) + "adaLN_modulation.2.", p0 = e->blk(i) + "adaLN_modulation.0.";
+    const float* dout = ts->dada + (size_t)i * N * 6 * C;
+    const float* pre = ts->ada_pre + (size_t)i * N * C;
+    HIPCHK(e, launch_linear_bwd_w(pre, dout, N, C, 6 * C, 1, G(ts, pa + "weight"), G(ts, pa + "bias"), 0, s));
+    HIPCHK(e, launch_linear_bwd_in(pre, dout, P(e, pa + "weight"), N, C, 6 * C, 1, ts->dada_pre, 0, s));
+    HIPCHK(e, launch_linear_bwd_w(ts->cvec, ts->dada_pre, N, e->G, C, 0, G(ts, p0 + "weight"), G(ts, p0 + "bias"), 0, s));
+    HIPCHK(e, launch_linear_bwd_in(ts->cvec, ts->dada_pre, P(e, p0 + "weight"), N, e->G, C, 0, ts->dcvec, acc, s));
+    if (e->kind != KIND_DECODER) return ST_OK;      // (the text encoder's blocks have no FiLM)
+    const std::string pf = "blocks." + std::to_string(i) + ".time_fusion.film.";
+    const float* dfo = ts->dfilm + (size_t)i * N * 2 * C;
+    HIPCHK(e, launch_linear_bwd_w(ts->tau, dfo, N, C, 2 * C, 0, G(ts, pf + "weight"), G(ts, pf + "bias"), 0, s));
+    HIPCHK(e, launch_linear_bwd_in(ts->tau, dfo, P(e, pf + "weight"), N, C, 2 * C, 0, ts->dtau, acc, s));
     return ST_OK;
 }
 
 // The per-item linears (adaLN modulation -> d c, FiLM -> d tau) of blocks [lo, hi) in four launches: every block's d ada / d film rows
-// are complete when its backward part ends.  `acc`: add to d c / d tau (the first part of a backward writes them).
+// are complete when its backward part ends.  `acc`: add to d c / d tau (the first part of a backward writes them).  gin == hidden only:
+// with adaLN_modulation.0 in front, bwd_block_linears runs per block.
 int bwd_linears(st_engine* e, TrainState* ts, int lo, int hi, int acc, hipStream_t s) {
     const int C = e->C, N = ts->B;
-    if (e->G != C) return ST_OK;          // (handled per block)
     for (int i0 = lo; i0 < hi; i0 += 8) {
         LinBwdJobs ja; memset(&ja, 0, sizeof(ja));
         LinBwdJobs jf; memset(&jf, 0, sizeof(jf));
@@ -1019,6 +1032,17 @@ int bwd_linears(st_engine* e, TrainState* ts, int lo, int hi, int acc, hipStream
         HIPCHK(e, launch_linear_bwd_in_multi(jf, ts->tau, N, C, 2 * C, 0, ts->dtau, a, s));
     }
     return ST_OK;
+}
+
+// The blocks hi - 1 .. lo of a backward, last first, then their per-item linears; `acc` as bwd_linears'
+int bwd_blocks(st_engine* e, TrainState* ts, int lo, int hi, int acc, hipStream_t s) {
+    const bool per_block = e->G != e->C;
+    int rc;
+    for (int i = hi - 1; i >= lo; --i) {
+        if ((rc = bwd_block(e, ts, i, s))) return rc;
+        if (per_block && (rc = bwd_block_linears(e, ts, i, s))) return rc;
+    }
+    return per_block ? ST_OK : bwd_linears(e, ts, lo, hi, acc, s);
 }
 
 int bwd_tail(st_engine* e, TrainState* ts, float* grad_x, float* grad_mu, float* grad_c, hipStream_t s) {
@@ -1053,24 +1077,12 @@ int bwd_tail(st_engine* e, TrainState* ts, float* grad_x, float* grad_mu, float*
         const DropCfg nodrop = make_drop(0.f, 0, 0);
         WgradOut o2 = {G(ts, "cond_proj.4.weight"), F, 0, F, 0, C, G(ts, "cond_proj.4.bias")};
         if ((rc = wgrad_side(e, ts, TrainState::DY_T1, ts->p2, F, nullptr, 0, C, K, &o2, 1, s))) return rc;
-        // d pre-activation = dgrad x SiLU': in the dgrad's epilogue where the phased kernel runs (as the FFN's)
-        auto dgrad_silu = [&](ConvGemmArgs a, const void* pre16, void* dpre16) -> int {
-            if (ts->fuse_silu && K == 3 && gemm_is_phased(e, 3, a) && !a.bias) {
-                a.out16 = dpre16; a.dact16 = pre16;
-                HIPCHK(e, gemm(e, K, EPI_SILU, a, s));
-            } else {
-                a.out32 = ts->tmpF;
-                HIPCHK(e, gemm(e, K, EPI_F32, a, s));
-                HIPCHK(e, launch_silu_bwd(e->dt, ts->tmpF, pre16, nullptr, 1, T, F, R, nodrop, dpre16, s));
-            }
-            return ST_OK;
-        };
         ConvGemmArgs a = cargs(e, ts->preT[2], N, T, B); a.a0 = t1; a.c0 = C;
-        if ((rc = dgrad_silu(a, ts->a2, t2))) return rc;
+        if ((rc = dgrad_silu(e, ts, a, ts->a2, t2, nullptr, 1, nodrop, s))) return rc;
         WgradOut o1 = {G(ts, "cond_proj.2.weight"), F, 0, F, 0, F, G(ts, "cond_proj.2.bias")};
         if ((rc = wgrad_side(e, ts, TrainState::DY_T2, ts->p1, F, nullptr, 0, F, K, &o1, 1, s))) return rc;
         a = cargs(e, ts->preT[1], N, T, B); a.a0 = t2; a.c0 = F;
-        if ((rc = dgrad_silu(a, ts->a1, t3))) return rc;
+        if ((rc = dgrad_silu(e, ts, a, ts->a1, t3, nullptr, 1, nodrop, s))) return rc;
         WgradOut o0 = {G(ts, "cond_proj.0.weight"), M, 0, M, 0, F, G(ts, "cond_proj.0.bias")};
         if ((rc = wgrad_side(e, ts, TrainState::DY_T3, ts->mu16, Mp, nullptr, 0, F, K, &o0, 1, s))) return rc;
         if (grad_mu) {
@@ -1100,8 +1112,7 @@ int bwd_head_text(st_engine* e, TrainState* ts, const float* grad_x, const float
     const int C = d.C, M = d.M, B = d.B, T = d.T;
     const int64_t R = d.R;
     int rc;
-    HIPCHK(e, hipMemsetAsync(ts->zero_region, 0, ts->zero_bytes, s));
-    ts->cell_idx = 0; ts->gsc = ts->gsc_ring;
+    if ((rc = bwd_begin(e, ts, s))) return rc;
     if (grad_mu) {      // mu_x = (W x + b) * mask
         if ((rc = bwd_out_proj(e, ts, grad_mu, "proj", s))) return rc;
     } else {            // only d x: proj gets no gradient
@@ -1125,8 +1136,7 @@ int bwd_text(st_engine* e, TrainState* ts, const float* grad_x, const float* gra
     const int L = e->L, C = e->C;
     int rc;
     if ((rc = bwd_head_text(e, ts, grad_x, grad_mu, s))) return rc;
-    for (int i = L - 1; i >= 0; --i) if ((rc = bwd_block(e, ts, i, s))) return rc;
-    if ((rc = bwd_linears(e, ts, 0, L, 0, s))) return rc;
+    if ((rc = bwd_blocks(e, ts, 0, L, 0, s))) return rc;
     // x = emb[token] * sqrt(C): dX is d (block 0's input), masked by its entry, in units of the current scale pair
     HIPCHK(e, launch_emb_bwd(ts->dX, C, ts->ids, (int64_t)ts->B * ts->T, e->n_vocab, sqrtf((float)C), ts->gsc, ts->emb_ws,
                              G(ts, "emb.weight"), s));
@@ -1142,11 +1152,9 @@ int bwd_part(st_engine* e, TrainState* ts, int part, const float* grad_out, floa
     int rc;
     if (part == 0) {
         if ((rc = bwd_head(e, ts, grad_out, s))) return rc;
-        for (int i = L - 1; i >= L / 2; --i) if ((rc = bwd_block(e, ts, i, s))) return rc;
-        if ((rc = bwd_linears(e, ts, L / 2, L, 0, s))) return rc;
+        if ((rc = bwd_blocks(e, ts, L / 2, L, 0, s))) return rc;
     } else if (part == 1) {
-        for (int i = L / 2 - 1; i >= 0; --i) if ((rc = bwd_block(e, ts, i, s))) return rc;
-        if ((rc = bwd_linears(e, ts, 0, L / 2, 1, s))) return rc;
+        if ((rc = bwd_blocks(e, ts, 0, L / 2, 1, s))) return rc;
     } else {
         if ((rc = bwd_tail(e, ts, grad_x, grad_mu, grad_c, s))) return rc;
     }
@@ -1243,13 +1251,13 @@ int st_param_grads_flat(st_engine* e, float* dst, int64_t numel, void* stream) {
 int st_param_grad(st_engine* e, const char* name, float* dst, int64_t numel, void* stream) {
     if (!e || !name || !dst) return ST_ERR_INVALID;
     if (!e->train) return e->fail(ST_ERR_STATE, "no training state");
-    auto it = e->train->grads.find(name);
+    auto it = e->train->goff.find(name);
     auto pit = e->params.find(name);
-    if (it == e->train->grads.end() || pit == e->params.end()) return e->fail(ST_ERR_INVALID, std::string("unknown parameter: ") + name);
+    if (it == e->train->goff.end() || pit == e->params.end()) return e->fail(ST_ERR_INVALID, std::string("unknown parameter: ") + name);
     if (pit->second.numel() != numel) return e->fail(ST_ERR_INVALID, std::string("size mismatch for gradient of ") + name);
     if (!e->train->own_grads_valid) return e->fail(ST_ERR_STATE, "st_param_grad: the last backward did not complete into the engine's own gradient buffer (it wrote into the caller's, or was abandoned)");
     HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, hipMemcpyAsync(dst, it->second, (size_t)numel * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIPCHK(e, hipMemcpyAsync(dst, e->train->grad_flat + it->second, (size_t)numel * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return ST_OK;
 }
 
