@@ -19,11 +19,10 @@ import torch
 import oracle
 from oracle.make_golden_text_encoder import text_inputs
 from oracle.weights import TextEncoderConfig
+from text_encoder_checks import TOL, TOL_QK, loss_weights as _loss_weights, oracle_grads as _oracle
 
 pytestmark = [pytest.mark.gpu, pytest.mark.grad]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOL = {"f16": 3e-3, "bf16": 2e-2}
-TOL_QK = {"f16": 1e-2, "bf16": 1e-1}
 
 
 def _rel(a, b):
@@ -33,13 +32,6 @@ def _rel(a, b):
 
 def _tol(name, dt):
     return (TOL_QK if (".attn.conv_q." in name or ".attn.conv_k." in name) else TOL)[dt]
-
-
-def _loss_weights(B, T, seed, out_channels=128, hidden=256):      # = tools/make_golden_text_encoder_grads.py: loss_weights
-    rng = np.random.Generator(np.random.PCG64(seed + 1000))
-    w_mu = rng.standard_normal((B, out_channels, T)).astype(np.float32)
-    w_x = (rng.standard_normal((B, hidden, T)) * 0.1).astype(np.float32)
-    return torch.from_numpy(w_mu), torch.from_numpy(w_x)
 
 
 def _module(sd, dt, gin=256, train=False):
@@ -59,18 +51,6 @@ def _native(m, tok, c, lens, w_mu, w_x):
     loss = (mu_x * w_mu.cuda()).sum() + (x * w_x.cuda()).sum()
     loss.backward()
     return float(loss.detach()), cc.grad.cpu(), {n: p.grad.detach().cpu().clone() for n, p in m.named_parameters()}
-
-
-def _oracle(sd, tok, c, lens, w_mu, w_x, fwd=None):
-    pr = {k: v.clone().double().requires_grad_(True) for k, v in sd.items()}
-    cc = c.clone().double().requires_grad_(True)
-    if fwd is None:
-        x, mu_x, _ = oracle.text_encoder_forward(pr, tok, cc, lens)
-    else:
-        x, mu_x = fwd(pr, cc)
-    loss = (mu_x * w_mu.double()).sum() + (x * w_x.double()).sum()
-    loss.backward()
-    return float(loss.detach()), cc.grad, {n: p.grad for n, p in pr.items()}
 
 
 def _check(dt, got, ref, label):
