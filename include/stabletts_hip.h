@@ -184,6 +184,50 @@ int64_t st_maximum_path_workspace_bytes(int B, int Ty, int Tx);
  *   mu_x (B, D, Tx), y (B, D, Ty) fp32 -> neg_cent (B, Ty, Tx) fp32 (the cross term on the fp32-input MFMA). */
 int st_mas_neg_cent(const float* mu_x, const float* y, int B, int D, int Tx, int Ty, float* neg_cent, void* stream);
 
+/* ---- the step between the alignment search and the decoder in training (models/model.py:160-176), stateless ------------ */
+/* The alignment has one token per frame and contiguous frames per token, so these take the per-token frame counts
+ * st_maximum_path writes and never a dense (B, Ty, Tx) tensor.  fp32 tensors; the sums behind a loss or a gradient accumulate
+ * in fp64 in one fixed order (no atomics): results do not depend on the batch, the grid or the neighbouring tokens.
+ *
+ * st_align_train_forward replaces model.py:166-168, :171-172 and :175-176.
+ *   durations    : (B, Tx) int32.  A token counts only where x_mask != 0, a negative count is 0, and the running sum is
+ *                  clipped to [0, Ty] before use: no durations tensor can index outside a buffer.
+ *   x_mask, y_mask : (B, 1, Tx), (B, 1, Ty);  mu_x (B, M, Tx);  y (B, M, Ty).
+ *   fake_content : (M) or NULL (= 0);  keep: (B), the cfg_mask of :138 as 0 / non-zero, or NULL (every item kept).
+ *   frame_token  : (B, Ty) int32, the token of each frame, -1 where no token covers it.
+ *   mu_y         : (B, M, Ty) or NULL: mu_x gathered by frame_token, 0 where frame_token < 0 (= attn^T mu_x, exactly).
+ *   mu_y_masked  : (B, M, Ty): mu_y * keep + (1 - keep) * fake_content; a dropped item holds fake_content in every frame.
+ *   scratch      : st_align_train_scratch_floats(B, M, Ty) floats; keeps the denominator sum(y_mask) * M for the backward.
+ *   prior_loss   : device scalar, sum(0.5 ((y - mu_y)^2 + log 2 pi) y_mask) / (sum(y_mask) * M).
+ * Tx <= 4096; a wider Tx returns ST_ERR_UNSUPPORTED before any launch.
+ *
+ * st_align_train_backward: for token i of item b with frames [s, s + d), ascending t,
+ *   grad_mu_x[b][m][i] = sum_t keep_b g_masked[b][m][t] + g_mu_y[b][m][t] + g_prior y_mask[b][t] (mu_x[b][m][i] - y[b][m][t]) / denom
+ *   (every element written; 0 for a token without frames);  grad_fake_content[m] = sum over items with keep == 0 and every
+ *   frame t in [0, Ty) of g_masked[b][m][t] (NULL to skip).  grad_mu_y_masked, grad_mu_y (B, M, Ty) and grad_prior (device
+ *   scalar) may each be NULL: that term is 0.  y, y_mask and scratch are read only with grad_prior. */
+int st_align_train_scratch_floats(int B, int M, int Ty);
+int st_align_train_forward(const int32_t* durations, const float* x_mask, const float* y_mask, const float* mu_x, const float* y,
+                           const float* fake_content, const float* keep, int B, int M, int Tx, int Ty, int32_t* frame_token,
+                           float* mu_y, float* mu_y_masked, float* scratch, float* prior_loss, void* stream);
+int st_align_train_backward(const int32_t* durations, const float* x_mask, const float* y_mask, const float* mu_x, const float* y,
+                            const float* keep, const float* scratch, const float* grad_mu_y_masked, const float* grad_mu_y,
+                            const float* grad_prior, int B, int M, int Tx, int Ty, float* grad_mu_x, float* grad_fake_content,
+                            void* stream);
+
+/* Replaces model.py:162-163 and duration_loss (models/duration_predictor.py:38-40).
+ * st_duration_loss: logw_ = log(1e-8 + durations) * x_mask -> logw_target (B, 1, Tx), or NULL to skip;
+ *   loss = sum((logw - logw_)^2) / sum(x_lengths) -> *loss (device), over every element as the reference sums it.
+ *   logw, x_mask: (B, 1, Tx); durations (B, Tx) int32 (a negative count is 0); x_lengths (B) int64;
+ *   scratch: st_duration_loss_scratch_floats() floats, keeps the denominator for the backward.
+ *   The difference logw - logw_ is formed in fp64: it cancels where the prediction is good.
+ * st_duration_loss_backward: grad_logw = grad_loss[0] * 2 (logw - logw_) / sum(x_lengths)  (grad_loss: device scalar). */
+int st_duration_loss(const float* logw, const int32_t* durations, const float* x_mask, const int64_t* x_lengths, int B, int Tx,
+                     float* logw_target, float* scratch, float* loss, void* stream);
+int st_duration_loss_backward(const float* logw, const int32_t* durations, const float* x_mask, const float* scratch,
+                              const float* grad_loss, int B, int Tx, float* grad_logw, void* stream);
+int st_duration_loss_scratch_floats(void);
+
 /* ---- CFMDecoder.compute_loss's own arithmetic (models/flow_matching.py:86-100), stateless like the alignment helpers ------
  * st_cfm_loss_prep: t = 1 - cos(t_rand pi / 2) (:88), y = (1 - (1 - sigma) t) z + t x1 (:93), u = x1 - (1 - sigma) z (:96).
  *   x1, z, y, u: (B, M, T); t_rand, t: (B).

@@ -22,15 +22,18 @@ for the Vocos multi-scale mel loss (``vocoders/vocos/models/loss.py:6``);
 (``vocoders/vocos/train.py:94``: the generator);
 ``install(discriminator="train")`` rebinds ``MultiPeriodDiscriminator`` and ``DiscriminatorP`` of the user's own
 ``vocoders.vocos.models.discriminator`` (``vocoders/vocos/train.py:19,54``) to the native classes of ``stabletts_amd.discriminator``;
-the multi-resolution discriminator of that module is left as it is.
+the multi-resolution discriminator of that module is left as it is;
+``install(model=True)`` registers ``stabletts_amd.model`` as ``models.model`` (``train.py:18``, ``api.py``): a ``StableTTS`` built
+from the native classes whose ``forward`` runs the alignment search, ``mu_y``, the prior and duration losses and their gradients
+on the device (``alignment.align_and_losses``), so that the reference's ``train.py`` needs no edit and no other registration.
 """
 import sys
 
-__all__ = ["install", "CFMDecoder", "TextEncoder", "MelStyleEncoder", "DurationPredictor", "maximum_path", "LogMelSpectrogram"]
+__all__ = ["install", "CFMDecoder", "TextEncoder", "MelStyleEncoder", "DurationPredictor", "maximum_path", "LogMelSpectrogram", "StableTTS"]
 
 
 def install(text_encoder=False, vocoder=False, reference_encoder=False, duration_predictor=False, monotonic_align=False,
-            audio=False, discriminator=False):
+            audio=False, discriminator=False, model=False):
     """Make ``models.flow_matching`` (and optionally ``models.text_encoder`` / ``vocoders.vocos.models.model`` /
     ``models.reference_encoder`` / ``models.duration_predictor`` / ``monotonic_align`` / ``utils.audio``) resolve to the native drop-ins
     (call before importing models.model / api.get_vocoder)."""
@@ -79,6 +82,9 @@ def install(text_encoder=False, vocoder=False, reference_encoder=False, duration
                               f"sys.path, and are its own imports such as torchaudio installed?): {exc}") from exc
         ref.MultiPeriodDiscriminator = nd.MultiPeriodDiscriminator      # vocoders/vocos/train.py:19,54
         ref.DiscriminatorP = nd.DiscriminatorP
+    if model:
+        from . import model as md
+        sys.modules["models.model"] = md                         # train.py:18, api.py: from models.model import StableTTS
     return flow_matching
 
 
@@ -104,6 +110,9 @@ def __getattr__(name):
     if name == "MultiPeriodDiscriminator":
         from .discriminator import MultiPeriodDiscriminator
         return MultiPeriodDiscriminator
+    if name == "StableTTS":
+        from .model import StableTTS
+        return StableTTS
     if name == "maximum_path":
         from .monotonic_align import maximum_path
         return maximum_path

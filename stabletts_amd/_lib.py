@@ -137,6 +137,12 @@ PROTOTYPES = {
     "st_maximum_path": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "st_maximum_path_workspace_bytes": (i64, [i32, i32, i32]),
     "st_mas_neg_cent": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
+    "st_align_train_scratch_floats": (i32, [i32, i32, i32]),
+    "st_align_train_forward": (i32, [vp] * 7 + [i32] * 4 + [vp] * 5 + [vp]),
+    "st_align_train_backward": (i32, [vp] * 10 + [i32] * 4 + [vp] * 2 + [vp]),
+    "st_duration_loss": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "st_duration_loss_backward": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp]),
+    "st_duration_loss_scratch_floats": (i32, []),
     "st_create_mel_extractor": (i32, [P(StMelConfig), i32, P(vp)]),
     "st_mel_frames": (i64, [vp, i64]),
     "st_mel_forward": (i32, [vp, vp, i32, i64, vp, vp]),

@@ -9,6 +9,10 @@ one 1 per mel frame).  Integer / index results are bit-exact with the reference 
 The training side of the same step, monotonic alignment search (models/model.py:148-162): ``maximum_path(neg_cent, t_y,
 t_x)`` runs monotonic_align's dynamic program and backtrack on the device (bit-exact), and
 ``monotonic_alignment(mu_x, x_mask, y, y_mask)`` adds the fused ``neg_cent`` in front and ``logw_`` behind it.
+``align_and_losses(...)`` is everything behind the search (models/model.py:160-176 without the decoder call): ``mu_y`` as a
+gather, ``mu_y_masked``, ``prior_loss``, ``logw_`` and ``dur_loss`` from the per-token frame counts, differentiable in
+``mu_x``, ``logw`` and ``fake_content`` (d ``mu_x`` is a segmented sum); no dense alignment exists on that path, and
+``dense_alignment(frame_token, Tx)`` builds one only for a caller who wants to look at it.
 There is no CPU fallback.
 """
 import ctypes
@@ -111,8 +115,9 @@ def mas_neg_cent(mu_x, y):
 def monotonic_alignment(mu_x, x_mask, y, y_mask):
     """models/model.py:148-162 without the host round trip.  mu_x (B, D, Tx), x_mask (B, 1, Tx), y (B, D, Ty),
     y_mask (B, 1, Ty) -> dict(attn (B, 1, Ty, Tx) fp32 0/1, durations (B, 1, Tx) fp32 = attn.sum(2),
-    logw_ (B, 1, Tx) = log(1e-8 + durations) * x_mask).  mu_y stays the caller's matmul (gradients reach mu_x through it):
-    mu_y = torch.matmul(attn.squeeze(1).transpose(1, 2), mu_x.transpose(1, 2)).transpose(1, 2)."""
+    logw_ (B, 1, Tx) = log(1e-8 + durations) * x_mask).  mu_y is either the caller's matmul (gradients reach mu_x through it),
+    mu_y = torch.matmul(attn.squeeze(1).transpose(1, 2), mu_x.transpose(1, 2)).transpose(1, 2), or, without the dense
+    alignment, ``align_and_losses(..., durations=out["durations"])``."""
     _dev(mu_x, "mu_x")
     neg_cent = mas_neg_cent(mu_x, y)
     # the reference's attn_mask = x_mask[:, :, None] * y_mask[..., None] summed over one axis (model.py:157, core.py
@@ -124,3 +129,114 @@ def monotonic_alignment(mu_x, x_mask, y, y_mask):
     durations = dur.to(torch.float32).unsqueeze(1)
     logw_ = torch.log(1e-8 + durations) * x_mask
     return dict(attn=path.unsqueeze(1), durations=durations, logw_=logw_)
+
+
+def _stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+class _AlignLossFn(torch.autograd.Function):
+    """models/model.py:162-163, 166-168, 171-172 and 175-176 on st_align_train_forward / st_duration_loss, and their
+    gradients on st_align_train_backward / st_duration_loss_backward.  Inputs (mu_x, logw, fake_content or None, then data:
+    x_mask, x_lengths, y, y_mask, durations int32, keep or None); outputs (mu_y, mu_y_masked, prior_loss, dur_loss, logw_,
+    frame_token), the last two not differentiable."""
+
+    @staticmethod
+    def forward(ctx, mu_x, logw, fake_content, x_mask, x_lengths, y, y_mask, dur, keep):
+        lib = _lib.load()
+        dev = mu_x.device
+        B, M, Tx = mu_x.shape
+        Ty = y.shape[2]
+        f32 = dict(device=dev, dtype=torch.float32)
+        mx = mu_x.detach().to(torch.float32).contiguous()
+        lw = logw.detach().to(**f32).contiguous()
+        fc = fake_content.detach().to(**f32).reshape(-1).contiguous() if fake_content is not None else None
+        xm, ym = x_mask.detach().to(**f32).contiguous(), y_mask.detach().to(**f32).contiguous()
+        yy = y.detach().to(**f32).contiguous()
+        xl = x_lengths.detach().to(device=dev, dtype=torch.long).contiguous()
+        kp = keep.detach().to(**f32).reshape(-1).contiguous() if keep is not None else None
+        if (yy.shape != (B, M, Ty) or lw.numel() != B * Tx or xm.numel() != B * Tx or ym.numel() != B * Ty or dur.shape != (B, Tx)
+                or xl.numel() != B or (fc is not None and fc.numel() != M) or (kp is not None and kp.numel() != B)):
+            raise ValueError("shape mismatch: mu_x (B, M, Tx), y (B, M, Ty), logw / x_mask (B, 1, Tx), y_mask (B, 1, Ty), "
+                             "durations (B, Tx), x_lengths (B), fake_content M values, keep B values")
+        nscr = int(lib.st_align_train_scratch_floats(B, M, Ty))
+        if nscr < 0:
+            raise ValueError("shape out of range")
+        frame_token = torch.empty(B, Ty, device=dev, dtype=torch.int32)
+        mu_y, mu_y_masked = torch.empty(B, M, Ty, **f32), torch.empty(B, M, Ty, **f32)
+        scratch = torch.empty(nscr, **f32)
+        dscratch = torch.empty(int(lib.st_duration_loss_scratch_floats()), **f32)
+        prior, dloss = torch.empty((), **f32), torch.empty((), **f32)
+        logw_ = torch.empty(B, 1, Tx, **f32)
+        with torch.cuda.device(dev):
+            s = _stream(dev)
+            _check(lib.st_align_train_forward(dur.data_ptr(), xm.data_ptr(), ym.data_ptr(), mx.data_ptr(), yy.data_ptr(), _ptr(fc),
+                                              _ptr(kp), B, M, Tx, Ty, frame_token.data_ptr(), mu_y.data_ptr(), mu_y_masked.data_ptr(),
+                                              scratch.data_ptr(), prior.data_ptr(), s))
+            _check(lib.st_duration_loss(lw.data_ptr(), dur.data_ptr(), xm.data_ptr(), xl.data_ptr(), B, Tx, logw_.data_ptr(),
+                                        dscratch.data_ptr(), dloss.data_ptr(), s))
+        ctx.save_for_backward(mx, lw, xm, ym, yy, dur, kp, scratch, dscratch)
+        ctx.fake_shape = tuple(fake_content.shape) if fake_content is not None else None
+        ctx.mark_non_differentiable(logw_, frame_token)
+        ctx.set_materialize_grads(False)
+        return mu_y, mu_y_masked, prior, dloss, logw_, frame_token
+
+    @staticmethod
+    def backward(ctx, g_mu_y, g_masked, g_prior, g_dur, _g_logw_, _g_tok):
+        lib = _lib.load()
+        mx, lw, xm, ym, yy, dur, kp, scratch, dscratch = ctx.saved_tensors
+        dev = mx.device
+        B, M, Tx = mx.shape
+        Ty = yy.shape[2]
+        f32 = dict(device=dev, dtype=torch.float32)
+        prep = lambda g, n: g.detach().to(**f32).reshape(n).contiguous() if g is not None else None      # noqa: E731
+        g_mu_y, g_masked = prep(g_mu_y, (B, M, Ty)), prep(g_masked, (B, M, Ty))
+        g_prior, g_dur = prep(g_prior, 1), prep(g_dur, 1)
+        need_mu, need_logw, need_fc = ctx.needs_input_grad[:3]
+        grad_mu_x = grad_logw = grad_fc = None
+        with torch.cuda.device(dev):
+            s = _stream(dev)
+            if (need_mu or need_fc) and (g_mu_y is not None or g_masked is not None or g_prior is not None):
+                grad_mu_x = torch.empty_like(mx)
+                grad_fc = torch.empty(M, **f32) if need_fc and ctx.fake_shape is not None else None
+                _check(lib.st_align_train_backward(dur.data_ptr(), xm.data_ptr(), ym.data_ptr(), mx.data_ptr(), yy.data_ptr(), _ptr(kp),
+                                                   scratch.data_ptr(), _ptr(g_masked), _ptr(g_mu_y), _ptr(g_prior), B, M, Tx, Ty,
+                                                   grad_mu_x.data_ptr(), _ptr(grad_fc), s))
+                if grad_fc is not None:
+                    grad_fc = grad_fc.reshape(ctx.fake_shape)
+                if not need_mu:
+                    grad_mu_x = None
+            if need_logw and g_dur is not None:
+                grad_logw = torch.empty_like(lw)
+                _check(lib.st_duration_loss_backward(lw.data_ptr(), dur.data_ptr(), xm.data_ptr(), dscratch.data_ptr(), g_dur.data_ptr(),
+                                                     B, Tx, grad_logw.data_ptr(), s))
+        return grad_mu_x, grad_logw, grad_fc, None, None, None, None, None, None
+
+
+def align_and_losses(mu_x, x_mask, logw, x_lengths, y, y_mask, durations, keep=None, fake_content=None):
+    """models/model.py:160-176 around the decoder call, from the frame counts of the alignment search.  mu_x (B, M, Tx),
+    x_mask / logw (B, 1, Tx), x_lengths (B), y (B, M, Ty), y_mask (B, 1, Ty); durations (B, Tx) or (B, 1, Tx), int32 as
+    maximum_path(..., durations=True) returns them or the fp32 ``durations`` of monotonic_alignment; keep: the cfg_mask of
+    :138 (B values, non-zero keeps the content; None keeps all); fake_content (1, M, 1) or None (= 0).
+    -> dict(mu_y, mu_y_masked (B, M, Ty), prior_loss, dur_loss (scalars), logw_ (B, 1, Tx), frame_token (B, Ty) int32, -1
+    where no token covers the frame).  Gradients reach mu_x (through mu_y, mu_y_masked and prior_loss), logw and fake_content.
+    No host synchronisation, no dense alignment."""
+    dev = _dev(mu_x, "mu_x")
+    B, _, Tx = mu_x.shape
+    dur = durations.detach().to(device=dev).reshape(B, Tx).to(torch.int32).contiguous()
+    mu_y, mu_y_masked, prior, dloss, logw_, frame_token = _AlignLossFn.apply(mu_x, logw, fake_content, x_mask, x_lengths, y, y_mask,
+                                                                             dur, keep)
+    return dict(mu_y=mu_y, mu_y_masked=mu_y_masked, prior_loss=prior, dur_loss=dloss, logw_=logw_, frame_token=frame_token)
+
+
+def dense_alignment(frame_token, Tx):
+    """frame_token (B, Ty) as align_and_losses returns it -> the 0/1 alignment (B, Tx, Ty) fp32, the fourth value
+    StableTTS.forward returns (models/model.py:166, 178).  Only for callers who want to look at it: nothing computes with it."""
+    B, Ty = frame_token.shape
+    attn = torch.zeros(B, Tx + 1, Ty, device=frame_token.device, dtype=torch.float32)
+    idx = torch.where(frame_token < 0, Tx, frame_token).to(torch.long).unsqueeze(1)      # uncovered frames go to a spare row
+    return attn.scatter_(1, idx, 1.0)[:, :Tx]

@@ -3,6 +3,7 @@
 #include "engine_internal.h"
 #include "train_launch.h"
 #include "mas_launch.h"
+#include "align_train_launch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1062,6 +1063,65 @@ int st_mas_neg_cent(const float* mu_x, const float* y, int B, int D, int Tx, int
     if (B < 1 || D < 1 || Tx < 1 || Ty < 1 || B > 65535 || (Ty + 63) / 64 > 65535) return align_fail(ST_ERR_INVALID, "shape out of range");
     if (launch_mas_neg_cent(mu_x, y, B, D, Tx, Ty, neg_cent, (hipStream_t)stream) != hipSuccess)
         return align_fail(ST_ERR_HIP, "neg_cent kernel launch failed");
+    return ST_OK;
+}
+
+// ---- training side of the alignment step: stateless helpers (errors through st_last_error(NULL))
+int st_align_train_scratch_floats(int B, int M, int Ty) {
+    if (B < 1 || M < 1 || Ty < 1) return ST_ERR_INVALID;
+    return align_train_scratch_floats(B, M, Ty);
+}
+
+static int align_train_shape(int B, int M, int Tx, int Ty) {
+    if (B < 1 || M < 1 || Tx < 1 || Ty < 1 || B > 65535 || (M + kAlignTrainChannels - 1) / kAlignTrainChannels > 65535 ||
+        align_train_scratch_floats(B, M, Ty) < 0)
+        return align_fail(ST_ERR_INVALID, "shape out of range");
+    if (Tx > kAlignTrainMaxTx) return align_fail(ST_ERR_UNSUPPORTED, "the alignment training kernels support Tx <= 4096 (one item's running sum in LDS)");
+    return ST_OK;
+}
+
+int st_align_train_forward(const int32_t* durations, const float* x_mask, const float* y_mask, const float* mu_x, const float* y,
+                           const float* fake_content, const float* keep, int B, int M, int Tx, int Ty, int32_t* frame_token,
+                           float* mu_y, float* mu_y_masked, float* scratch, float* prior_loss, void* stream) {
+    if (!durations || !x_mask || !y_mask || !mu_x || !y || !frame_token || !mu_y_masked || !scratch || !prior_loss)
+        return align_fail(ST_ERR_INVALID, "null tensor pointer");
+    if (int rc = align_train_shape(B, M, Tx, Ty)) return rc;
+    if (launch_align_train_forward(durations, x_mask, y_mask, mu_x, y, fake_content, keep, B, M, Tx, Ty, frame_token, mu_y, mu_y_masked,
+                                   scratch, prior_loss, (hipStream_t)stream) != hipSuccess)
+        return align_fail(ST_ERR_HIP, "align_train_forward kernel launch failed");
+    return ST_OK;
+}
+
+int st_align_train_backward(const int32_t* durations, const float* x_mask, const float* y_mask, const float* mu_x, const float* y,
+                            const float* keep, const float* scratch, const float* grad_mu_y_masked, const float* grad_mu_y,
+                            const float* grad_prior, int B, int M, int Tx, int Ty, float* grad_mu_x, float* grad_fake_content,
+                            void* stream) {
+    if (!durations || !x_mask || !mu_x || !grad_mu_x) return align_fail(ST_ERR_INVALID, "null tensor pointer");
+    if (grad_prior && (!y || !y_mask || !scratch)) return align_fail(ST_ERR_INVALID, "grad_prior needs y, y_mask and the forward's scratch");
+    if (int rc = align_train_shape(B, M, Tx, Ty)) return rc;
+    if (launch_align_train_backward(durations, x_mask, y_mask, mu_x, y, keep, scratch, grad_mu_y_masked, grad_mu_y, grad_prior, B, M, Tx,
+                                    Ty, grad_mu_x, grad_fake_content, (hipStream_t)stream) != hipSuccess)
+        return align_fail(ST_ERR_HIP, "align_train_backward kernel launch failed");
+    return ST_OK;
+}
+
+int st_duration_loss_scratch_floats(void) { return kDurLossScratchFloats; }
+
+int st_duration_loss(const float* logw, const int32_t* durations, const float* x_mask, const int64_t* x_lengths, int B, int Tx,
+                     float* logw_target, float* scratch, float* loss, void* stream) {
+    if (!logw || !durations || !x_mask || !x_lengths || !scratch || !loss) return align_fail(ST_ERR_INVALID, "null tensor pointer");
+    if (B < 1 || Tx < 1) return align_fail(ST_ERR_INVALID, "shape out of range");
+    if (launch_duration_loss(logw, durations, x_mask, (const long long*)x_lengths, B, Tx, logw_target, scratch, loss, (hipStream_t)stream) != hipSuccess)
+        return align_fail(ST_ERR_HIP, "duration_loss kernel launch failed");
+    return ST_OK;
+}
+
+int st_duration_loss_backward(const float* logw, const int32_t* durations, const float* x_mask, const float* scratch,
+                              const float* grad_loss, int B, int Tx, float* grad_logw, void* stream) {
+    if (!logw || !durations || !x_mask || !scratch || !grad_loss || !grad_logw) return align_fail(ST_ERR_INVALID, "null tensor pointer");
+    if (B < 1 || Tx < 1) return align_fail(ST_ERR_INVALID, "shape out of range");
+    if (launch_duration_loss_bwd(logw, durations, x_mask, scratch, grad_loss, B, Tx, grad_logw, (hipStream_t)stream) != hipSuccess)
+        return align_fail(ST_ERR_HIP, "duration_loss_bwd kernel launch failed");
     return ST_OK;
 }
 
