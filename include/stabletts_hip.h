@@ -261,10 +261,26 @@ int st_create_vocoder(const st_vocos_config* cfg, int device, st_engine** out);
 
 /* Replaces Vocos.forward(x) (model.py:17-20) = ISTFTHead(VocosBackbone(x)) (backbone.py:50-56, head.py:93-117 with
  * padding="same"):  mel (B, input_channels, T) fp32 -> audio (B, T * hop_length) fp32, device pointers.  Like the
- * reference there is no mask: every utterance is vocoded at the padded length T.  Large batches run in chunks of whole
- * utterances (32-bit row offsets inside the GEMMs, the device's grid-y limit); only a T that exceeds the row bound on its
- * own is rejected (ST_ERR_INVALID), as is a batch that needs more than one chunk while debug capture is on. */
+ * reference there is no mask: every utterance is vocoded at the padded length T (a batch of different lengths:
+ * st_vocos_forward_ragged).  Large batches run in chunks of whole utterances (32-bit row offsets inside the GEMMs, the
+ * device's grid-y limit); only a T that exceeds the row bound on its own is rejected (ST_ERR_INVALID), as is a batch that
+ * needs more than one chunk while debug capture is on. */
 int st_vocos_forward(st_engine* e, const float* mel, float* audio, int B, int T, void* stream);
+
+/* st_vocos_forward on a ragged batch: utterance b has lengths[b] frames, and its audio equals that utterance vocoded alone
+ * (the padded frames of st_vocos_forward are not zero activations: they reach back through the k = 7 convolutions and the
+ * ISTFT overlap into the last ~12 frames of every shorter utterance).
+ *   mel     : (B, input_channels, T) fp32, device; frames from lengths[b] on are never read
+ *   lengths : B entries in HOST memory, each in [1, T]  (e.g. length_regulate's y_lengths)
+ *   audio   : (B, T * hop_length) fp32, device; every sample is written, those from lengths[b] * hop_length on as 0.0
+ * Every activation between the two is packed: the GEMMs run over sum(lengths) rows, not B * T.  With every length equal to
+ * T the audio is bitwise st_vocos_forward's (same kernels' arithmetic, same row count).  Everything is validated before the
+ * device is touched (a null pointer or a length outside [1, T]: ST_ERR_INVALID naming the index).  Chunks are whole
+ * utterances bounded by their PACKED rows (the 32-bit row bound of st_vocos_forward) and by 2^23 padded frames; an
+ * utterance that exceeds the row bound on its own is rejected, as is a multi-chunk batch while debug capture is on (a
+ * single-chunk call captures packed (sum(lengths), .) tensors).  Enqueued on `stream`; the length table travels through
+ * one of four pinned slots guarded by events, so back-to-back calls do not wait on each other. */
+int st_vocos_forward_ragged(st_engine* e, const float* mel, const int64_t* lengths, float* audio, int B, int T, void* stream);
 
 /* ---- Vocos generator training: autograd counterpart of Vocos.forward on a vocoder handle (the generator step of
  * vocoders/vocos/train.py:94,115,128).  fp32 values and accumulation throughout (fp32-input MFMA): the parameters are read

@@ -116,6 +116,7 @@ PROTOTYPES = {
     "st_cfm_loss_scratch_floats": (i32, []),
     "st_create_vocoder": (i32, [P(StVocosConfig), i32, P(vp)]),
     "st_vocos_forward": (i32, [vp, vp, vp, i32, i32, vp]),
+    "st_vocos_forward_ragged": (i32, [vp, vp, P(i64), vp, i32, i32, vp]),
     "st_vocos_train_forward": (i32, [vp, vp, vp, i32, i32, vp]),
     "st_vocos_train_backward": (i32, [vp, vp, vp, vp, i32, i32, vp]),
     "st_create_period_discriminator": (i32, [P(StPeriodDiscConfig), i32, P(vp)]),
@@ -299,6 +300,14 @@ class Engine:
     def vocos_forward(self, mel, audio, stream):
         B, _, T = mel.shape
         self._check(self.lib.st_vocos_forward(self.handle, mel.data_ptr(), audio.data_ptr(), B, T, ctypes.c_void_p(stream)))
+
+    def vocos_forward_ragged(self, mel, lengths, audio, stream):
+        """st_vocos_forward with utterance b at its own length lengths[b] (a sequence of B ints, host side)."""
+        B, _, T = mel.shape
+        if len(lengths) != B:
+            raise NativeError(ST_ERR_INVALID, f"lengths has {len(lengths)} entries, the batch has B = {B} utterances")
+        arr = (ctypes.c_int64 * B)(*lengths)
+        self._check(self.lib.st_vocos_forward_ragged(self.handle, mel.data_ptr(), arr, audio.data_ptr(), B, T, ctypes.c_void_p(stream)))
 
     def vocos_train_forward(self, mel, audio, stream):
         """st_vocos_forward in fp32 that keeps the activations for vocos_train_backward (vocoder handles)."""

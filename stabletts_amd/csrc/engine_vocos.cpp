@@ -1,5 +1,5 @@
-// Vocos vocoder behind the C ABI (st_create_vocoder / st_vocos_forward): parameter table, weight packing and the
-// launch sequence.  Reference: vocoders/vocos/models/model.py:11-20, backbone.py:21-56, module.py:16-46,
+// Vocos vocoder behind the C ABI (st_create_vocoder / st_vocos_forward / st_vocos_forward_ragged): parameter table, weight
+// packing and the launch sequence.  Reference: vocoders/vocos/models/model.py:11-20, backbone.py:21-56, module.py:16-46,
 // head.py:17-117; config.py:4-19,46-50.  The five GEMM shapes (embed as an im2col GEMM, pwconv1 + GELU, pwconv2 +
 // layer scale + residual, head) run on the implicit-GEMM kernels of the decoder over the FLATTENED rows of the batch
 // (taps = 1: rows are independent); everything between them is in vocos_kernels.hip.
@@ -19,6 +19,21 @@ struct VocosState {
     st_vocos_config cfg{};
     Conv embed, head;
     std::vector<Conv> pw1, pw2;
+    // ragged calls: utterance tables in pinned host memory, copied to device slots; a slot is refilled only after the event
+    // of its previous call, so a call never waits for the one before it (as MelState, engine_audio.cpp)
+    static constexpr int kSlots = 4;
+    VocUtt* host[kSlots] = {};
+    VocUtt* dev[kSlots] = {};
+    hipEvent_t ev[kSlots] = {};
+    bool used[kSlots] = {};
+    int cap = 0, next = 0;
+};
+
+// One chunk of a ragged batch: its utterance table (device, chunk-relative entries) and the sizes the host summed from it.
+struct VocRagged {
+    const VocUtt* utt;
+    int64_t rows;
+    int n_tiles, n_groups, dw_frames;
 };
 
 static std::string vblk(int i) { return "backbone.convnext." + std::to_string(i) + "."; }
@@ -99,7 +114,16 @@ int vocos_finalize(st_engine* e) {
     return ST_OK;
 }
 
-void vocos_destroy(st_engine* e) { delete e->voc; e->voc = nullptr; }
+void vocos_destroy(st_engine* e) {
+    VocosState* v = e->voc;
+    if (!v) return;
+    for (int i = 0; i < VocosState::kSlots; ++i) {
+        if (v->host[i]) hipHostFree(v->host[i]);
+        if (v->dev[i]) hipFree(v->dev[i]);
+        if (v->ev[i]) hipEventDestroy(v->ev[i]);
+    }
+    delete v; e->voc = nullptr;
+}
 
 }  // namespace sthost
 
@@ -131,21 +155,24 @@ int st_create_vocoder(const st_vocos_config* cfg, int device, st_engine** out) {
     return ST_OK;
 }
 
-// One chunk of whole utterances: every GEMM runs over its R = B * T flattened rows.  The K loop of the conv GEMM forms an
-// activation row's byte offset as a 32-bit value (t * cin * 2, conv_gemm2_impl.h), so st_vocos_forward sizes chunks to
-// keep R * max(7 * M, C, F) * 2 below 2^31.
-static int vocos_forward_chunk(st_engine* e, const float* mel, float* audio, int B, int T, hipStream_t s) {
+// One chunk of whole utterances: every GEMM runs over its R flattened rows, R = B * T, or the packed rows of a ragged chunk
+// (rg: mel and audio stay padded to T; only the im2col, the depthwise conv and the overlap-add know utterances and take the
+// ragged launcher).  The K loop of the conv GEMM forms an activation row's byte offset as a 32-bit value (t * cin * 2,
+// conv_gemm2_impl.h), so the callers size chunks to keep R * max(7 * M, C, F) * 2 below 2^31.
+static int vocos_forward_chunk(st_engine* e, const float* mel, float* audio, int B, int T, const VocRagged* rg, hipStream_t s) {
     VocosState* v = e->voc;
     const st_vocos_config& c = v->cfg;
     const int C = c.dim, F = c.intermediate_dim, M = c.input_channels, L = c.num_layers;
-    const int64_t R = (int64_t)B * T;
+    const int64_t R = rg ? rg->rows : (int64_t)B * T;
 
     // workspace: im2col rows, fp32 residual stream, 16-bit operands, head output, windowed frames
     size_t off = 0;
     auto want = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
     const size_t o_a16 = want((size_t)R * 7 * M * 2), o_x = want((size_t)R * C * 4), o_h16 = want((size_t)R * C * 2), o_h16lo = want((size_t)R * C * 2);
     const size_t o_u16 = want((size_t)R * F * 2), o_head = want((size_t)R * 2 * kVocHeadPlane * 4), o_fr = want((size_t)R * kVocNfft * 4);
+    const size_t o_tiles = rg ? want((size_t)rg->n_tiles * sizeof(VocSeg)) : 0, o_groups = rg ? want((size_t)rg->n_groups * sizeof(VocSeg)) : 0;
     int rc = ensure_ws(e, off); if (rc) return rc;
+    VocSeg* tiles = (VocSeg*)(e->ws + o_tiles); VocSeg* groups = (VocSeg*)(e->ws + o_groups);
     void* a16 = e->ws + o_a16; float* x = (float*)(e->ws + o_x); void* h16 = e->ws + o_h16; void* h16lo = e->ws + o_h16lo; void* u16 = e->ws + o_u16;
     float* head = (float*)(e->ws + o_head); float* frames = (float*)(e->ws + o_fr);
 
@@ -158,7 +185,12 @@ static int vocos_forward_chunk(st_engine* e, const float* mel, float* audio, int
     const bool cap = e->capture;
     {   // embed (backbone.py:51) + LayerNorm (:52)
         ProfScope ps(e, s, PC_PRENET, 2.0 * R * C * 7.0 * M);
-        HIPCHK(e, launch_voc_im2col7(e->dt, mel, B, M, T, a16, s));
+        if (rg) {
+            HIPCHK(e, launch_voc_segments(rg->utt, B, rg->dw_frames, tiles, groups, s));
+            HIPCHK(e, launch_voc_im2col7_ragged(e->dt, mel, tiles, rg->n_tiles, M, T, a16, s));
+        } else {
+            HIPCHK(e, launch_voc_im2col7(e->dt, mel, B, M, T, a16, s));
+        }
         ConvGemmArgs a = args(v->embed); a.a0 = a16; a.c0 = 7 * M; a.out32 = x;
         HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
         HIPCHK(e, launch_voc_ln(e->dt, x, P(e, "backbone.norm.weight"), P(e, "backbone.norm.bias"), R, x, nullptr, nullptr, s));
@@ -168,8 +200,9 @@ static int vocos_forward_chunk(st_engine* e, const float* mel, float* audio, int
         const std::string p = vblk(i);
         {
             ProfScope ps(e, s, PC_FILM_LN1, 0);
-            HIPCHK(e, launch_voc_dwconv_ln(e->dt, x, P(e, p + "dwconv.weight"), P(e, p + "dwconv.bias"), P(e, p + "norm.weight"),
-                                           P(e, p + "norm.bias"), B, T, h16, s));
+            const float *dw = P(e, p + "dwconv.weight"), *db = P(e, p + "dwconv.bias"), *nw = P(e, p + "norm.weight"), *nb = P(e, p + "norm.bias");
+            if (rg) HIPCHK(e, launch_voc_dwconv_ln_ragged(e->dt, x, dw, db, nw, nb, groups, rg->n_groups, rg->dw_frames, h16, s));
+            else    HIPCHK(e, launch_voc_dwconv_ln(e->dt, x, dw, db, nw, nb, B, T, h16, s));
         }
         {
             ProfScope ps(e, s, PC_FFN1, 2.0 * R * C * (double)F);
@@ -194,9 +227,16 @@ static int vocos_forward_chunk(st_engine* e, const float* mel, float* audio, int
     {   // ISTFT (head.py:104-116)
         ProfScope ps(e, s, PC_ODE, 0);
         HIPCHK(e, launch_voc_spec_ifft(head, P(e, "head.istft.window"), R, frames, s));
-        HIPCHK(e, launch_voc_overlap_add(frames, P(e, "head.istft.window"), B, T, audio, s));
+        if (rg) HIPCHK(e, launch_voc_overlap_add_ragged(frames, P(e, "head.istft.window"), rg->utt, B, T, audio, s));
+        else    HIPCHK(e, launch_voc_overlap_add(frames, P(e, "head.istft.window"), B, T, audio, s));
     }
     return ST_OK;
+}
+
+// rows per chunk: 32-bit GEMM operand offsets (widest operand row: the im2col rows, C or F) and head output indices
+static int64_t vocos_max_rows(const st_vocos_config& c) {
+    const int64_t widest = std::max({7 * (int64_t)c.input_channels, (int64_t)c.dim, (int64_t)c.intermediate_dim, (int64_t)kVocHeadPlane});
+    return (((int64_t)1 << 31) - 1) / (widest * 2);
 }
 
 int st_vocos_forward(st_engine* e, const float* mel, float* audio, int B, int T, void* stream) {
@@ -205,9 +245,7 @@ int st_vocos_forward(st_engine* e, const float* mel, float* audio, int B, int T,
     if (!mel || !audio) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if ((rc = check_sizes(e, B, T))) return rc;
     const st_vocos_config& c = e->voc->cfg;
-    // rows per chunk: 32-bit GEMM operand offsets (widest operand row: the im2col rows, C or F) and head output indices
-    const int64_t widest = std::max({7 * (int64_t)c.input_channels, (int64_t)c.dim, (int64_t)c.intermediate_dim, (int64_t)kVocHeadPlane});
-    const int64_t max_rows = (((int64_t)1 << 31) - 1) / (widest * 2);
+    const int64_t max_rows = vocos_max_rows(c);
     if (T > max_rows) return e->fail(ST_ERR_INVALID, "T too large: one utterance exceeds the vocoder's 32-bit row indexing");
     HIPCHK(e, hipSetDevice(e->device));
     int grid_y = 0;       // the im2col and overlap-add kernels put the utterance on grid.y
@@ -217,9 +255,82 @@ int st_vocos_forward(st_engine* e, const float* mel, float* audio, int B, int T,
     hipStream_t s = (hipStream_t)stream;
     const size_t mel_item = (size_t)c.input_channels * T, audio_item = (size_t)T * c.hop_length;
     for (int b0 = 0; b0 < B; b0 += chunk) {
-        rc = vocos_forward_chunk(e, mel + b0 * mel_item, audio + b0 * audio_item, std::min(chunk, B - b0), T, s);
+        rc = vocos_forward_chunk(e, mel + b0 * mel_item, audio + b0 * audio_item, std::min(chunk, B - b0), T, nullptr, s);
         if (rc) return rc;
     }
+    return ST_OK;
+}
+
+int st_vocos_forward_ragged(st_engine* e, const float* mel, const int64_t* lengths, float* audio, int B, int T, void* stream) {
+    int rc = check_handle(e, KIND_VOCODER); if (rc) return rc;
+    if ((rc = check_finalized(e))) return rc;
+    if (!mel || !audio) return e->fail(ST_ERR_INVALID, "null tensor pointer");
+    if (!lengths) return e->fail(ST_ERR_INVALID, "null lengths");
+    if ((rc = check_sizes(e, B, T))) return rc;
+    VocosState* v = e->voc;
+    const st_vocos_config& c = v->cfg;
+    const int64_t max_rows = vocos_max_rows(c);
+    // validate everything and plan the chunks before touching the device: whole utterances, as many as keep the packed rows
+    // within max_rows (and the padded frames within one overlap-add launch)
+    for (int b = 0; b < B; ++b)
+        if (lengths[b] < 1 || lengths[b] > T)
+            return e->fail(ST_ERR_INVALID, "lengths[" + std::to_string(b) + "] = " + std::to_string(lengths[b]) + " must be in [1, T = " + std::to_string(T) + "]");
+    for (int b = 0; b < B; ++b)
+        if (lengths[b] > max_rows)
+            return e->fail(ST_ERR_INVALID, "lengths[" + std::to_string(b) + "] too large: one utterance exceeds the vocoder's 32-bit row indexing");
+    if (T > kVocMaxPaddedFrames) return e->fail(ST_ERR_INVALID, "T too large: the padded audio of one utterance exceeds one launch");
+    std::vector<int> starts;          // first utterance of every chunk, then B
+    int64_t rows = 0;
+    for (int b = 0; b < B; ++b) {
+        if (b == 0 || rows + lengths[b] > max_rows || (int64_t)(b - starts.back() + 1) * T > kVocMaxPaddedFrames) { starts.push_back(b); rows = 0; }
+        rows += lengths[b];
+    }
+    starts.push_back(B);
+    const int n_chunks = (int)starts.size() - 1;
+    if (n_chunks > 1 && e->capture) return e->fail(ST_ERR_INVALID, "debug capture holds whole-batch tensors: this batch runs in chunks");
+    HIPCHK(e, hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (B > v->cap) {       // grow every slot (after their calls)
+        for (int i = 0; i < VocosState::kSlots; ++i) {
+            if (v->used[i]) HIPCHK(e, hipEventSynchronize(v->ev[i]));
+            if (v->host[i]) { hipHostFree(v->host[i]); v->host[i] = nullptr; }
+            if (v->dev[i]) { hipFree(v->dev[i]); v->dev[i] = nullptr; }
+            v->used[i] = false;
+        }
+        v->cap = 0;
+        const int cap = B > 64 ? B : 64;
+        for (int i = 0; i < VocosState::kSlots; ++i) {
+            HIPCHK(e, hipHostMalloc((void**)&v->host[i], (size_t)cap * sizeof(VocUtt)));
+            HIPCHK(e, hipMalloc((void**)&v->dev[i], (size_t)cap * sizeof(VocUtt)));
+            if (!v->ev[i]) HIPCHK(e, hipEventCreateWithFlags(&v->ev[i], hipEventDisableTiming));
+        }
+        v->cap = cap;
+    }
+    const int slot = v->next;
+    v->next = (v->next + 1) % VocosState::kSlots;
+    if (v->used[slot]) HIPCHK(e, hipEventSynchronize(v->ev[slot]));
+    VocUtt* u = v->host[slot];
+    std::vector<VocRagged> chunks(n_chunks);
+    for (int k = 0; k < n_chunks; ++k) {      // entries relative to their chunk: its rows, tables, mel and audio start at 0
+        VocRagged& rg = chunks[k];
+        rg.utt = v->dev[slot] + starts[k]; rg.rows = 0; rg.n_tiles = 0; rg.n_groups = 0;
+        for (int b = starts[k]; b < starts[k + 1]; ++b) rg.rows += lengths[b];
+        rg.dw_frames = voc_dw_frames(rg.rows);
+        int row0 = 0;
+        for (int b = starts[k]; b < starts[k + 1]; ++b) {
+            const int Tb = (int)lengths[b];
+            u[b] = VocUtt{row0, Tb, rg.n_tiles, rg.n_groups};
+            row0 += Tb; rg.n_tiles += (Tb + 63) / 64; rg.n_groups += (Tb + rg.dw_frames - 1) / rg.dw_frames;
+        }
+    }
+    HIPCHK(e, hipMemcpyAsync(v->dev[slot], u, (size_t)B * sizeof(VocUtt), hipMemcpyHostToDevice, s));
+    v->used[slot] = true;
+    const size_t mel_item = (size_t)c.input_channels * T, audio_item = (size_t)T * c.hop_length;
+    for (int k = 0; k < n_chunks && rc == ST_OK; ++k)
+        rc = vocos_forward_chunk(e, mel + starts[k] * mel_item, audio + starts[k] * audio_item, starts[k + 1] - starts[k], T, &chunks[k], s);
+    hipError_t he = hipEventRecord(v->ev[slot], s);       // also after a failed chunk: the copy and the launches before it read the slot
+    if (rc) return rc;
+    HIPCHK(e, he);
     return ST_OK;
 }
 

@@ -8,24 +8,38 @@ namespace st {
 
 // ---------------------------------------------------------------- embed: im2col of the k = 7 convolution (backbone.py:28,51)
 // One block = 64 frames of one utterance: the (M x 70) mel tile is read with frames contiguous and written as
-// 16-bit rows [frame][tap][channel].
+// 16-bit rows [frame][tap][channel].  src: the utterance's mel (M, ld), T <= ld of its frames valid; rows: its frame 0.
 template <class P>
-__global__ __launch_bounds__(256) void voc_im2col7_kernel(const float* __restrict__ mel, int M, int T, typename P::elem* __restrict__ a16) {
-    extern __shared__ float tile[];           // [M][72]
-    const int b = blockIdx.y, t0 = blockIdx.x * 64;
-    const float* src = mel + (size_t)b * M * T;
+__device__ __forceinline__ void voc_im2col7_tile(const float* __restrict__ src, int M, int ld, int T, int t0,
+                                                 typename P::elem* __restrict__ rows, float* tile /* [M][72] */) {
     for (int i = threadIdx.x; i < M * 70; i += 256) {
         const int c = i / 70, k = i - c * 70;
         const int t = t0 + k - 3;
-        tile[c * 72 + k] = (t >= 0 && t < T) ? src[(size_t)c * T + t] : 0.0f;
+        tile[c * 72 + k] = (t >= 0 && t < T) ? src[(size_t)c * ld + t] : 0.0f;
     }
     __syncthreads();
     const int K = 7 * M;
     for (int i = threadIdx.x; i < 64 * K; i += 256) {
         const int f = i / K, r = i - f * K;
         const int j = r / M, c = r - j * M;
-        if (t0 + f < T) a16[((size_t)b * T + t0 + f) * K + r] = to16<P>(tile[c * 72 + f + j]);
+        if (t0 + f < T) rows[((size_t)t0 + f) * K + r] = to16<P>(tile[c * 72 + f + j]);
     }
+}
+
+template <class P>
+__global__ __launch_bounds__(256) void voc_im2col7_kernel(const float* __restrict__ mel, int M, int T, typename P::elem* __restrict__ a16) {
+    extern __shared__ float tile[];           // [M][72]
+    const int b = blockIdx.y;
+    voc_im2col7_tile<P>(mel + (size_t)b * M * T, M, T, T, blockIdx.x * 64, a16 + (size_t)b * T * 7 * M, tile);
+}
+
+// Ragged batch: block = one entry of the tile table (voc_segments_kernel); mel is padded (B, M, Tmax), the rows are packed.
+template <class P>
+__global__ __launch_bounds__(256) void voc_im2col7_ragged_kernel(const float* __restrict__ mel, const VocSeg* __restrict__ tiles, int M, int Tmax,
+                                                                 typename P::elem* __restrict__ a16) {
+    extern __shared__ float tile[];           // [M][72]
+    const VocSeg sg = tiles[blockIdx.x];
+    voc_im2col7_tile<P>(mel + (size_t)sg.item * M * Tmax, M, Tmax, sg.T, sg.t0, a16 + (size_t)sg.row0 * 7 * M, tile);
 }
 
 hipError_t launch_voc_im2col7(int dtype, const float* mel, int B, int M, int T, void* a16, hipStream_t s) {
@@ -34,6 +48,31 @@ hipError_t launch_voc_im2col7(int dtype, const float* mel, int B, int M, int T, 
     if (lds > 64 * 1024) return hipErrorInvalidValue;
     if (dtype == DT_BF16) hipLaunchKernelGGL((voc_im2col7_kernel<OpBF16>), grid, blk, lds, s, mel, M, T, (OpBF16::elem*)a16);
     else                  hipLaunchKernelGGL((voc_im2col7_kernel<OpF16>), grid, blk, lds, s, mel, M, T, (OpF16::elem*)a16);
+    return hipGetLastError();
+}
+
+hipError_t launch_voc_im2col7_ragged(int dtype, const float* mel, const VocSeg* tiles, int n_tiles, int M, int Tmax, void* a16, hipStream_t s) {
+    const dim3 grid(n_tiles), blk(256);
+    const size_t lds = (size_t)M * 72 * 4;
+    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    if (dtype == DT_BF16) hipLaunchKernelGGL((voc_im2col7_ragged_kernel<OpBF16>), grid, blk, lds, s, mel, tiles, M, Tmax, (OpBF16::elem*)a16);
+    else                  hipLaunchKernelGGL((voc_im2col7_ragged_kernel<OpF16>), grid, blk, lds, s, mel, tiles, M, Tmax, (OpF16::elem*)a16);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- ragged batches: the tables of the three kernels that know utterances
+// One block per utterance expands its VocUtt (host table) into the 64-frame tiles of the im2col kernel and the dw_frames-frame
+// groups of the depthwise kernel: a block / wave of those kernels reads one entry and never searches.
+__global__ __launch_bounds__(256) void voc_segments_kernel(const VocUtt* __restrict__ utt, int dw_frames, VocSeg* __restrict__ tiles,
+                                                           VocSeg* __restrict__ groups) {
+    const int b = blockIdx.x;
+    const VocUtt u = utt[b];
+    for (int i = threadIdx.x; i * 64 < u.T; i += 256) tiles[u.tile0 + i] = VocSeg{u.row0, i * 64, u.T, b};
+    for (int i = threadIdx.x; (long long)i * dw_frames < u.T; i += 256) groups[u.grp0 + i] = VocSeg{u.row0, i * dw_frames, u.T, b};
+}
+
+hipError_t launch_voc_segments(const VocUtt* utt, int B, int dw_frames, VocSeg* tiles, VocSeg* groups, hipStream_t s) {
+    hipLaunchKernelGGL(voc_segments_kernel, dim3(B), dim3(256), 0, s, utt, dw_frames, tiles, groups);
     return hipGetLastError();
 }
 
@@ -86,17 +125,10 @@ hipError_t launch_voc_ln(int dtype, const float* x, const float* w, const float*
 // One wave per R consecutive frames of one utterance (R = 4; 1 for small batches), lane = 8 channels: the R + 6 fp32 residual
 // rows of the window are requested up front and the 56 taps of the lane's channels loaded once per wave.
 template <class P, int R>
-__global__ __launch_bounds__(256) void voc_dwconv_ln_kernel(const float* __restrict__ x, const float* __restrict__ dw,
-                                                            const float* __restrict__ dbias, const float* __restrict__ w,
-                                                            const float* __restrict__ b, int T, int groups_per_item, long long n_groups,
-                                                            void* h16) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long grp = (long long)blockIdx.x * 4 + wave;
-    if (grp >= n_groups) return;
-    const int item = (int)(grp / groups_per_item);
-    const int t0 = (int)(grp - (long long)item * groups_per_item) * R;
-    const int ch = lane * 8;
-    const float* xi = x + (size_t)item * T * 512 + ch;
+__device__ __forceinline__ void voc_dwconv_ln_group(const float* __restrict__ xi /* the utterance's frame 0, + ch */, int T, int t0,
+                                                    const float* __restrict__ dw, const float* __restrict__ dbias,
+                                                    const float* __restrict__ w, const float* __restrict__ b, int ch,
+                                                    unsigned char* hi /* h16 of the utterance's frame 0, + ch */) {
     const Row8 zero = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
     Row8 win[R + 6];          // every row of the window is requested before anything is computed: one exposed latency per wave
 #pragma unroll
@@ -122,8 +154,39 @@ __global__ __launch_bounds__(256) void voc_dwconv_ln_kernel(const float* __restr
             acc.b.x += wt[4][j] * v.b.x; acc.b.y += wt[5][j] * v.b.y; acc.b.z += wt[6][j] * v.b.z; acc.b.w += wt[7][j] * v.b.w;
         }
         voc_ln8(acc, lw, lb);
-        st16x8<P>((unsigned char*)h16 + (((size_t)item * T + t) * 512 + ch) * 2, acc);
+        st16x8<P>(hi + (size_t)t * 512 * 2, acc);
     }
+}
+
+template <class P, int R>
+__global__ __launch_bounds__(256) void voc_dwconv_ln_kernel(const float* __restrict__ x, const float* __restrict__ dw,
+                                                            const float* __restrict__ dbias, const float* __restrict__ w,
+                                                            const float* __restrict__ b, int T, int groups_per_item, long long n_groups,
+                                                            void* h16) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long grp = (long long)blockIdx.x * 4 + wave;
+    if (grp >= n_groups) return;
+    const int item = (int)(grp / groups_per_item);
+    const int t0 = (int)(grp - (long long)item * groups_per_item) * R;
+    const int ch = lane * 8;
+    voc_dwconv_ln_group<P, R>(x + (size_t)item * T * 512 + ch, T, t0, dw, dbias, w, b, ch,
+                              (unsigned char*)h16 + ((size_t)item * T * 512 + ch) * 2);
+}
+
+// Ragged batch: wave = one entry of the group table (R frames of ONE utterance, voc_segments_kernel), read through scalar
+// registers; x and h16 are packed rows.
+template <class P, int R>
+__global__ __launch_bounds__(256) void voc_dwconv_ln_ragged_kernel(const float* __restrict__ x, const float* __restrict__ dw,
+                                                                   const float* __restrict__ dbias, const float* __restrict__ w,
+                                                                   const float* __restrict__ b, const VocSeg* __restrict__ groups,
+                                                                   int n_groups, void* h16) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long grp = (long long)blockIdx.x * 4 + wave;
+    if (grp >= n_groups) return;
+    const VocSeg sg = groups[grp];
+    const int ch = lane * 8;
+    voc_dwconv_ln_group<P, R>(x + (size_t)sg.row0 * 512 + ch, sg.T, sg.t0, dw, dbias, w, b, ch,
+                              (unsigned char*)h16 + ((size_t)sg.row0 * 512 + ch) * 2);
 }
 
 template <class P, int R>
@@ -135,9 +198,26 @@ static void launch_dw(const float* x, const float* dw, const float* dbias, const
 
 hipError_t launch_voc_dwconv_ln(int dtype, const float* x, const float* dw, const float* dbias, const float* w, const float* b,
                                 int B, int T, void* h16, hipStream_t s) {
-    const bool big = (long long)B * T >= 8192;      // small batches: one frame per wave (more waves than a few CUs' worth)
+    const bool big = voc_dw_frames((int64_t)B * T) == 4;      // small batches: one frame per wave (more waves than a few CUs' worth)
     if (dtype == DT_BF16) { if (big) launch_dw<OpBF16, 4>(x, dw, dbias, w, b, B, T, h16, s); else launch_dw<OpBF16, 1>(x, dw, dbias, w, b, B, T, h16, s); }
     else                  { if (big) launch_dw<OpF16, 4>(x, dw, dbias, w, b, B, T, h16, s); else launch_dw<OpF16, 1>(x, dw, dbias, w, b, B, T, h16, s); }
+    return hipGetLastError();
+}
+
+template <class P, int R>
+static void launch_dw_ragged(const float* x, const float* dw, const float* dbias, const float* w, const float* b, const VocSeg* groups,
+                             int n_groups, void* h16, hipStream_t s) {
+    hipLaunchKernelGGL((voc_dwconv_ln_ragged_kernel<P, R>), dim3((unsigned)(((long long)n_groups + 3) / 4)), dim3(256), 0, s, x, dw, dbias, w, b,
+                       groups, n_groups, h16);
+}
+
+int voc_dw_frames(int64_t rows) { return rows >= 8192 ? 4 : 1; }
+
+hipError_t launch_voc_dwconv_ln_ragged(int dtype, const float* x, const float* dw, const float* dbias, const float* w, const float* b,
+                                       const VocSeg* groups, int n_groups, int dw_frames, void* h16, hipStream_t s) {
+    const bool big = dw_frames == 4;
+    if (dtype == DT_BF16) { if (big) launch_dw_ragged<OpBF16, 4>(x, dw, dbias, w, b, groups, n_groups, h16, s); else launch_dw_ragged<OpBF16, 1>(x, dw, dbias, w, b, groups, n_groups, h16, s); }
+    else                  { if (big) launch_dw_ragged<OpF16, 4>(x, dw, dbias, w, b, groups, n_groups, h16, s); else launch_dw_ragged<OpF16, 1>(x, dw, dbias, w, b, groups, n_groups, h16, s); }
     return hipGetLastError();
 }
 
@@ -212,12 +292,8 @@ hipError_t launch_voc_spec_ifft(const float* head, const float* window, int64_t 
 // Overlap-add (fold, head.py:60-63), "same" trim (:48,63), window envelope (:66-69) and normalisation (:73).
 // Output sample s of utterance b sits at q = s + 768 of the untrimmed signal; frames floor((q - 2047 + 511) / 512) ..
 // floor(q / 512) cover it (at most 4), added in ascending frame order.
-__global__ __launch_bounds__(256) void voc_overlap_add_kernel(const float* __restrict__ frames, const float* __restrict__ window,
-                                                              int T, float* __restrict__ audio) {
-    const long long len = (long long)T * kVocHop;
-    const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (s >= len) return;
-    const int b = blockIdx.y;
+__device__ __forceinline__ float voc_ola_sample(const float* __restrict__ fr /* the utterance's frames */, const float* __restrict__ window,
+                                                int T, long long s) {
     const long long q = s + (kVocNfft - kVocHop) / 2;
     int f1 = (int)(q / kVocHop); if (f1 > T - 1) f1 = T - 1;
     long long f0l = (q - (kVocNfft - 1) + kVocHop - 1) / kVocHop; if (q - (kVocNfft - 1) < 0) f0l = 0;
@@ -225,15 +301,42 @@ __global__ __launch_bounds__(256) void voc_overlap_add_kernel(const float* __res
     for (int f = (int)f0l; f <= f1; ++f) {
         const int off = (int)(q - (long long)f * kVocHop);
         const float wv = window[off];
-        y += frames[((size_t)b * T + f) * kVocNfft + off];
+        y += fr[(size_t)f * kVocNfft + off];
         env += wv * wv;
     }
-    audio[(size_t)b * len + s] = y / env;
+    return y / env;
+}
+
+__global__ __launch_bounds__(256) void voc_overlap_add_kernel(const float* __restrict__ frames, const float* __restrict__ window,
+                                                              int T, float* __restrict__ audio) {
+    const long long len = (long long)T * kVocHop;
+    const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (s >= len) return;
+    const int b = blockIdx.y;
+    audio[(size_t)b * len + s] = voc_ola_sample(frames + (size_t)b * T * kVocNfft, window, T, s);
+}
+
+// Ragged batch: packed frames -> padded audio (B, Tmax * 512); 2 * Tmax blocks per utterance on a 1-D grid, zeros from
+// sample T_b * 512 on.
+__global__ __launch_bounds__(256) void voc_overlap_add_ragged_kernel(const float* __restrict__ frames, const float* __restrict__ window,
+                                                                     const VocUtt* __restrict__ utt, int Tmax, float* __restrict__ audio) {
+    const int per = 2 * Tmax;                 // blocks per utterance (kVocHop / 256 per frame)
+    const int b = blockIdx.x / per;
+    const long long s = (long long)(blockIdx.x - b * per) * 256 + threadIdx.x;
+    const VocUtt u = utt[b];
+    audio[(size_t)b * Tmax * kVocHop + s] = s < (long long)u.T * kVocHop ? voc_ola_sample(frames + (size_t)u.row0 * kVocNfft, window, u.T, s) : 0.0f;
 }
 
 hipError_t launch_voc_overlap_add(const float* frames, const float* window, int B, int T, float* audio, hipStream_t s) {
     const long long len = (long long)T * kVocHop;
     hipLaunchKernelGGL(voc_overlap_add_kernel, dim3((unsigned)((len + 255) / 256), B), dim3(256), 0, s, frames, window, T, audio);
+    return hipGetLastError();
+}
+
+hipError_t launch_voc_overlap_add_ragged(const float* frames, const float* window, const VocUtt* utt, int B, int Tmax, float* audio, hipStream_t s) {
+    static_assert(kVocHop == 512, "two 256-sample blocks per frame");
+    if ((long long)B * Tmax > kVocMaxPaddedFrames) return hipErrorInvalidValue;      // grid.x * 256 threads stays below 2^32
+    hipLaunchKernelGGL(voc_overlap_add_ragged_kernel, dim3((unsigned)(2ll * B * Tmax)), dim3(256), 0, s, frames, window, utt, Tmax, audio);
     return hipGetLastError();
 }
 

@@ -25,4 +25,22 @@ hipError_t launch_voc_spec_ifft(const float* head, const float* window, int64_t 
 // overlap-add with hop 512, "same" trim, envelope normalisation: audio[b][T*512]
 hipError_t launch_voc_overlap_add(const float* frames, const float* window, int B, int T, float* audio, hipStream_t s);
 
+// ---- ragged batches: utterance b owns the packed rows row0 .. row0 + T of every row tensor (R = sum of T_b rows); the mel and
+// the audio stay padded, (B, M, Tmax) and (B, Tmax * 512).  The host writes one VocUtt per utterance; launch_voc_segments
+// expands them on the device into the block table of the im2col kernel and the wave table of the depthwise kernel.
+struct VocUtt { int row0, T, tile0, grp0; };     // first packed row, frames, first 64-frame tile, first depthwise group
+struct VocSeg { int row0, t0, T, item; };        // frames t0 .. of utterance `item`, whose T frames start at packed row row0
+constexpr long long kVocMaxPaddedFrames = (1ll << 23) - 1;      // B * Tmax of one ragged overlap-add launch
+
+int voc_dw_frames(int64_t rows);      // frames per wave of the depthwise kernel (4 from 8192 rows, else 1): the group length
+// tiles: sum ceil(T_b / 64) entries, groups: sum ceil(T_b / dw_frames) entries
+hipError_t launch_voc_segments(const VocUtt* utt, int B, int dw_frames, VocSeg* tiles, VocSeg* groups, hipStream_t s);
+// launch_voc_im2col7 on frames 0 .. T_b - 1 of each utterance (taps outside are zero), into packed rows
+hipError_t launch_voc_im2col7_ragged(int dtype, const float* mel, const VocSeg* tiles, int n_tiles, int M, int Tmax, void* a16, hipStream_t s);
+// launch_voc_dwconv_ln on packed rows: a window never leaves its utterance; same arithmetic as the dense kernel
+hipError_t launch_voc_dwconv_ln_ragged(int dtype, const float* x, const float* dw, const float* dbias, const float* w, const float* b,
+                                       const VocSeg* groups, int n_groups, int dw_frames, void* h16, hipStream_t s);
+// launch_voc_overlap_add on packed frames; audio[b][s] = 0 for s >= T_b * 512 (every sample of the padded audio is written)
+hipError_t launch_voc_overlap_add_ragged(const float* frames, const float* window, const VocUtt* utt, int B, int Tmax, float* audio, hipStream_t s);
+
 }  // namespace st

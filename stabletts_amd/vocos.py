@@ -4,7 +4,7 @@
 Same module tree as the reference (``backbone.embed``, ``backbone.norm``, ``backbone.convnext.<i>.{dwconv,norm,
 pwconv1,pwconv2,gamma}``, ``backbone.final_layer_norm``, ``head.out``, ``head.istft.window``), so a released
 ``vocos.pt`` loads with ``load_state_dict`` unchanged.  The modules hold parameters only: the forward pass runs in
-libstabletts_hip.so (st_vocos_forward); there is no PyTorch fallback.  Inference only, like the reference's use of it.
+libstabletts_hip.so (st_vocos_forward, st_vocos_forward_ragged); there is no PyTorch fallback.  Inference only, like the reference's use of it.
 """
 import torch
 import torch.nn as nn
@@ -92,6 +92,27 @@ class Vocos(NativeModule):
 
     def forward(self, x):
         """mel (B, input_channels, T) -> audio (B, T * hop_length)  (model.py:17-20)."""
+        return self._vocode(x, None)
+
+    def forward_ragged(self, x, lengths):
+        """``forward`` for a padded batch whose utterance b has ``lengths[b]`` frames (e.g. ``length_regulate(...)["y_lengths"]``):
+        mel (B, input_channels, T), lengths B ints in [1, T] (a sequence, or an integer tensor: a device tensor costs one
+        ``.tolist()`` sync) -> audio (B, T * hop_length).  Each utterance's audio is what ``forward`` gives for it alone;
+        ``audio[b, lengths[b] * hop_length:]`` is 0.  ``forward`` has no mask (like the reference), so there the padding reaches
+        the last ~12 frames of every shorter utterance."""
+        if isinstance(lengths, torch.Tensor):
+            if lengths.dtype.is_floating_point or lengths.dtype in (torch.bool, torch.complex64, torch.complex128):
+                raise ValueError(f"lengths must be an integer tensor, got {lengths.dtype}")
+            if lengths.device.type != "cpu" and lengths.device != x.device:
+                raise ValueError(f"lengths is on {lengths.device}, the mel is on {x.device}")
+            if lengths.dim() != 1:
+                raise ValueError("lengths must be one-dimensional (B,)")
+            lengths = lengths.tolist()
+        else:
+            lengths = [int(n) for n in lengths]
+        return self._vocode(x, lengths)
+
+    def _vocode(self, x, lengths):
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             raise NotImplementedError("the native vocoder is inference-only (SURVEY 8f-4): it has no backward, so a mel or "
                                       "parameters that require grad would silently train nothing; run it under torch.no_grad()")
@@ -106,5 +127,9 @@ class Vocos(NativeModule):
             B, _, T = mel.shape
             audio = torch.empty(B, T * self.cfg["hop_length"], device=dev, dtype=torch.float32)
             with torch.cuda.device(dev):
-                eng.vocos_forward(mel, audio, torch.cuda.current_stream(dev).cuda_stream)
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                if lengths is None:
+                    eng.vocos_forward(mel, audio, stream)
+                else:
+                    eng.vocos_forward_ragged(mel, lengths, audio, stream)
             return audio

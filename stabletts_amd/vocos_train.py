@@ -106,3 +106,13 @@ class Vocos(_Vocos):
             return _VocosFn.apply(self, [n for n, _ in named], x, *[p for _, p in named])
         finally:
             self._want_packed = True
+
+    def forward_ragged(self, x, lengths):
+        """``vocos.Vocos.forward_ragged`` on the inference kernels (under ``no_grad``).  The native training forward has no
+        ragged form: a call that would have to be differentiated (train mode, grad enabled, something requires grad) raises."""
+        if self.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("the native training forward has no ragged form (st_vocos_train_forward vocodes at the padded "
+                                      "length): call forward_ragged in eval mode or under torch.no_grad()")
+        self._want_packed = True
+        with torch.no_grad():
+            return super().forward_ragged(x, lengths)
