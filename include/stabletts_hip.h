@@ -12,9 +12,9 @@
  *     16-bit weight copies and its workspace.
  *   - work is enqueued on the caller's HIP stream (`stream` = hipStream_t, e.g.
  *     torch.cuda.current_stream().cuda_stream) with no implicit device synchronisation.
- *   - a handle is one of seven kinds, each with its own creator: the CFM decoder, the text encoder, the Vocos vocoder, the style
- *     encoder, the duration predictor, the mel extractor and the period discriminator of the Vocos training step; an entry point
- *     handed a handle of another kind returns ST_ERR_STATE.
+ *   - a handle is one of eight kinds, each with its own creator: the CFM decoder, the text encoder, the Vocos vocoder, the style
+ *     encoder, the duration predictor, the mel extractor and the period and resolution discriminators of the Vocos training step; an
+ *     entry point handed a handle of another kind returns ST_ERR_STATE.
  *   - one engine per device per process; an engine is not thread-safe (the reference is
  *     single-threaded per process: train.py:101-102, webui.py:128).
  */
@@ -333,6 +333,52 @@ int st_period_disc_train_forward(st_engine* e, const float* x, float* const* fma
  * shape, before any caller memory is touched. */
 int st_period_disc_train_backward(st_engine* e, const float* const* d_fmaps, float* d_x /* nullable */, float* grad_flat /* nullable */,
                                   int B, int T, void* stream);
+
+/* ---- resolution discriminator of the Vocos training step (vocoders/vocos/models/discriminator.py:112-171, train.py:98-128) ---- */
+/* One handle serves one DiscriminatorR(window_length, channels = 32, hop_factor = 0.25, bands); the three of a
+ * MultiResolutionDiscriminator are three handles.  fp32 throughout, the reference's (B, C, frames, F) layout, no atomics: every
+ * value and gradient is bitwise repeatable, and an item's values do not depend on the rest of the batch.  The complex STFT
+ * (hann window, hop window_length / 4, reflect padding) is written as the two input channels of layer 0; a band is the column range
+ * [band_lo, band_hi) of its window_length / 2 + 1 bins.  The band convs are GEMMs on the fp32-input MFMA (forward, data gradient of
+ * the 32 -> 32 layers, weight gradient); the STFT, layer 0's data gradient, conv_post and the weight norm are vector kernels. */
+typedef struct st_resolution_disc_config {
+    int32_t window_length;    /* a power of two in [32, 2048] (ST_ERR_UNSUPPORTED otherwise) */
+    int32_t band_lo[5];       /* the bands as bin ranges, int(b * (window_length / 2 + 1)) of the reference's fractions; */
+    int32_t band_hi[5];       /* an empty one is ST_ERR_UNSUPPORTED (the reference fails there), one outside the bins ST_ERR_INVALID */
+    float lrelu_slope;        /* > 0 (the reference: 0.1): the backward takes the pre-activation's sign from the kept post-activation */
+} st_resolution_disc_config;
+
+/* The handle takes the reference's state-dict entries through st_load_param / st_bind_param / st_finalize:
+ * "band_convs.{c}.{i}.parametrizations.weight.original0" (g: 32, 1, 1, 1), "...original1" (v: 32, 2 or 32, 3, 9; i = 4: 32, 32, 3, 3),
+ * "band_convs.{c}.{i}.bias" for c, i = 0..4 and the same three under "conv_post." (v: 1, 32, 3, 3).  st_finalize computes the
+ * effective weights v g / ||v|| once; after an in-place update of bound tensors st_repack(e, stream) computes them again as kernels
+ * on `stream`.  Either drops the activations a training forward left.  Destroyed with st_destroy. */
+int st_create_resolution_discriminator(const st_resolution_disc_config* cfg, int device, st_engine** out);
+
+/* Feature map `index` (band-major: 4 c + i - 1 after band_convs.c.i, i = 1..4; 20: conv_post's output, the logits) of a T-sample
+ * input is (B, *channels, *frames, *width), frames = 1 + T / (window_length / 4).  ST_ERR_INVALID for a bad index or a T the
+ * forward rejects. */
+int st_resolution_disc_fmap_shape(const st_engine* e, int T, int index, int64_t* channels, int64_t* frames, int64_t* width);
+
+/* Split-K planes of the weight-gradient launch of band_convs.{band}.{layer} at (B, T): a figure for tests and tools (>= 1), or
+ * ST_ERR_INVALID. */
+int st_resolution_disc_wgrad_planes(const st_engine* e, int B, int T, int band, int layer);
+
+/* Replaces DiscriminatorR.forward:  x (B, 1, T) -> the 21 feature maps, fp32 device pointers in fmaps[0..20] (shapes above); the
+ * module's first return value is fmaps[20] itself.  The reflect padding needs T > window_length / 2 (ST_ERR_INVALID otherwise, where
+ * torch.stft raises).  st_resolution_disc_forward keeps nothing.  st_resolution_disc_train_forward keeps the spectrum and the
+ * post-activations of this ONE forward in the handle (st_train_serial counts it). */
+int st_resolution_disc_forward(st_engine* e, const float* x, float* const* fmaps, int B, int T, void* stream);
+int st_resolution_disc_train_forward(st_engine* e, const float* x, float* const* fmaps, int B, int T, void* stream);
+
+/* Backward of the held forward.  d_fmaps[0..20]: d loss / d feature map, each entry may be NULL (no gradient reaches that map).
+ * d_x (nullable): receives d loss / d x (B, 1, T), the reflected samples' share folded onto the samples they mirror; NULL skips
+ * layer 0's data gradient and the whole STFT backward.  grad_flat (nullable): st_train_grad_numel floats, each parameter's gradient
+ * at st_train_grad_offset(name) (the gaps are not written; with d_fmaps[20] == NULL neither are conv_post's slices); NULL skips
+ * every weight-gradient and weight-norm kernel.  B and T must be the forward's: ST_ERR_STATE without a held forward or with another
+ * shape, before any caller memory is touched. */
+int st_resolution_disc_train_backward(st_engine* e, const float* const* d_fmaps, float* d_x /* nullable */, float* grad_flat /* nullable */,
+                                      int B, int T, void* stream);
 
 /* ---- MelStyleEncoder and DurationPredictor: stages 1 and 3 of StableTTS.synthesise (models/model.py:79-81) ------- */
 /* Both run in fp32 (fp32-input MFMA for every convolution and linear): the durations they feed are ceil()ed

@@ -22,7 +22,8 @@ for the Vocos multi-scale mel loss (``vocoders/vocos/models/loss.py:6``);
 (``vocoders/vocos/train.py:94``: the generator);
 ``install(discriminator="train")`` rebinds ``MultiPeriodDiscriminator`` and ``DiscriminatorP`` of the user's own
 ``vocoders.vocos.models.discriminator`` (``vocoders/vocos/train.py:19,54``) to the native classes of ``stabletts_amd.discriminator``;
-the multi-resolution discriminator of that module is left as it is;
+and ``install(resolution_discriminator="train")`` rebinds ``MultiResolutionDiscriminator`` and ``DiscriminatorR`` of that same
+module (``vocoders/vocos/train.py:19,55``), which need no torchaudio; each keyword leaves the other pair of names as it is;
 ``install(model=True)`` registers ``stabletts_amd.model`` as ``models.model`` (``train.py:18``, ``api.py``): a ``StableTTS`` built
 from the native classes whose ``forward`` runs the alignment search, ``mu_y``, the prior and duration losses and their gradients
 on the device (``alignment.align_and_losses``), so that the reference's ``train.py`` needs no edit and no other registration.
@@ -33,7 +34,7 @@ __all__ = ["install", "CFMDecoder", "TextEncoder", "MelStyleEncoder", "DurationP
 
 
 def install(text_encoder=False, vocoder=False, reference_encoder=False, duration_predictor=False, monotonic_align=False,
-            audio=False, discriminator=False, model=False):
+            audio=False, discriminator=False, model=False, resolution_discriminator=False):
     """Make ``models.flow_matching`` (and optionally ``models.text_encoder`` / ``vocoders.vocos.models.model`` /
     ``models.reference_encoder`` / ``models.duration_predictor`` / ``monotonic_align`` / ``utils.audio``) resolve to the native drop-ins
     (call before importing models.model / api.get_vocoder)."""
@@ -82,6 +83,19 @@ def install(text_encoder=False, vocoder=False, reference_encoder=False, duration
                               f"sys.path, and are its own imports such as torchaudio installed?): {exc}") from exc
         ref.MultiPeriodDiscriminator = nd.MultiPeriodDiscriminator      # vocoders/vocos/train.py:19,54
         ref.DiscriminatorP = nd.DiscriminatorP
+    if resolution_discriminator:
+        if resolution_discriminator != "train":
+            raise ValueError('install(resolution_discriminator=...) takes "train": the discriminators exist for training only')
+        import importlib
+        from . import discriminator as nd
+        try:                                                     # the user's module: its multi-period classes stay
+            ref = importlib.import_module("vocoders.vocos.models.discriminator")
+        except ImportError as exc:
+            raise ImportError('install(resolution_discriminator="train") rebinds MultiResolutionDiscriminator and DiscriminatorR inside '
+                              "vocoders.vocos.models.discriminator, which could not be imported (is the StableTTS checkout on "
+                              f"sys.path, and are its own imports such as torchaudio installed?): {exc}") from exc
+        ref.MultiResolutionDiscriminator = nd.MultiResolutionDiscriminator      # vocoders/vocos/train.py:19,55
+        ref.DiscriminatorR = nd.DiscriminatorR
     if model:
         from . import model as md
         sys.modules["models.model"] = md                         # train.py:18, api.py: from models.model import StableTTS
@@ -110,6 +124,9 @@ def __getattr__(name):
     if name == "MultiPeriodDiscriminator":
         from .discriminator import MultiPeriodDiscriminator
         return MultiPeriodDiscriminator
+    if name == "MultiResolutionDiscriminator":
+        from .discriminator import MultiResolutionDiscriminator
+        return MultiResolutionDiscriminator
     if name == "StableTTS":
         from .model import StableTTS
         return StableTTS

@@ -53,11 +53,18 @@ class StPeriodDiscConfig(ctypes.Structure):
     _fields_ = [("period", ctypes.c_int32), ("lrelu_slope", ctypes.c_float)]
 
 
+class StResolutionDiscConfig(ctypes.Structure):
+    """st_resolution_disc_config: band_lo[5] / band_hi[5] as ten named fields (the same layout)."""
+    _fields_ = ([("window_length", ctypes.c_int32)] + [(f"band_lo{c}", ctypes.c_int32) for c in range(5)]
+                + [(f"band_hi{c}", ctypes.c_int32) for c in range(5)] + [("lrelu_slope", ctypes.c_float)])
+
+
 # Engine(...) keyword whose value is a configuration dict -> (its struct, the creator it goes to); in the order Engine looks
 CREATORS = {"mel": (StMelConfig, "st_create_mel_extractor"), "style_encoder": (StStyleEncoderConfig, "st_create_style_encoder"),
             "duration_predictor": (StDurationPredictorConfig, "st_create_duration_predictor"),
             "vocoder": (StVocosConfig, "st_create_vocoder"),
-            "period_discriminator": (StPeriodDiscConfig, "st_create_period_discriminator")}
+            "period_discriminator": (StPeriodDiscConfig, "st_create_period_discriminator"),
+            "resolution_discriminator": (StResolutionDiscConfig, "st_create_resolution_discriminator")}
 
 
 class NativeError(RuntimeError):
@@ -124,6 +131,12 @@ PROTOTYPES = {
     "st_period_disc_forward": (i32, [vp, vp, P(vp), i32, i32, vp]),
     "st_period_disc_train_forward": (i32, [vp, vp, P(vp), i32, i32, vp]),
     "st_period_disc_train_backward": (i32, [vp, P(vp), vp, vp, i32, i32, vp]),
+    "st_create_resolution_discriminator": (i32, [P(StResolutionDiscConfig), i32, P(vp)]),
+    "st_resolution_disc_fmap_shape": (i32, [vp, i32, i32, P(i64), P(i64), P(i64)]),
+    "st_resolution_disc_wgrad_planes": (i32, [vp, i32, i32, i32, i32]),
+    "st_resolution_disc_forward": (i32, [vp, vp, P(vp), i32, i32, vp]),
+    "st_resolution_disc_train_forward": (i32, [vp, vp, P(vp), i32, i32, vp]),
+    "st_resolution_disc_train_backward": (i32, [vp, P(vp), vp, vp, i32, i32, vp]),
     "st_set_option": (i32, [vp, c_char_p, i32]),
     "st_get_option": (i32, [vp, c_char_p, P(i32)]),
     "st_attention_stats": (i32, [vp, vp, P(f32)]),
@@ -190,7 +203,7 @@ class Engine:
 
     def __init__(self, noise_channels, hidden_channels, filter_channels, n_heads, n_layers, kernel_size,
                  gin_channels, operand_dtype="f16", device=0, text_encoder_vocab=None, vocoder=None,
-                 style_encoder=None, duration_predictor=None, mel=None, period_discriminator=None):
+                 style_encoder=None, duration_predictor=None, mel=None, period_discriminator=None, resolution_discriminator=None):
         """text_encoder_vocab: None -> CFM decoder estimator (st_create); n_vocab -> TextEncoder handle
         (st_create_text_encoder; noise_channels is then the encoder's out_channels).
         vocoder: dict(input_channels, dim, intermediate_dim, num_layers, n_fft, hop_length) -> Vocos handle
@@ -200,14 +213,16 @@ class Engine:
         -> DurationPredictor handle (st_create_duration_predictor).  Both fp32: the decoder arguments are ignored.
         mel: dict(n_fft, win_length, hop_length, pad, n_mels, center, pad_mode) -> mel-extractor handle (st_create_mel_extractor;
         pad_mode an ST_PAD_* value, n_mels 0 for a linear spectrogram).
-        period_discriminator: dict(period, lrelu_slope) -> DiscriminatorP handle (st_create_period_discriminator), fp32."""
+        period_discriminator: dict(period, lrelu_slope) -> DiscriminatorP handle (st_create_period_discriminator), fp32.
+        resolution_discriminator: dict(window_length, band_lo0..4, band_hi0..4, lrelu_slope) -> DiscriminatorR handle
+        (st_create_resolution_discriminator), fp32."""
         self.lib = load()
         if operand_dtype not in OPERAND_DTYPES:
             raise ValueError(f"operand_dtype must be one of {sorted(OPERAND_DTYPES)}")
         self.operand_dtype = operand_dtype
         h = ctypes.c_void_p()
         dicts = dict(mel=mel, style_encoder=style_encoder, duration_predictor=duration_predictor, vocoder=vocoder,
-                     period_discriminator=period_discriminator)
+                     period_discriminator=period_discriminator, resolution_discriminator=resolution_discriminator)
         kw = next((k for k in CREATORS if dicts[k] is not None), None)
         if kw:          # a configuration dict: its struct's fields by name (operand_dtype, where the struct has one, from the argument)
             (struct, creator), d = CREATORS[kw], dicts[kw]
@@ -347,6 +362,38 @@ class Engine:
         ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
         ptrs = (ctypes.c_void_p * 5)(*[ptr(f) for f in d_fmaps])
         self._check(self.lib.st_period_disc_train_backward(self.handle, ptrs, ptr(d_x), ptr(grad_flat), B, T, ctypes.c_void_p(stream)))
+
+    def resolution_disc_fmap_shapes(self, B, T):
+        """The 21 feature-map shapes (B, C, frames, width) of a (B, 1, T) input (resolution-discriminator handles)."""
+        out = []
+        for i in range(21):
+            c, f, w = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+            if self.lib.st_resolution_disc_fmap_shape(self.handle, int(T), i, ctypes.byref(c), ctypes.byref(f), ctypes.byref(w)) != ST_OK:
+                raise NativeError(ST_ERR_INVALID, f"T = {T} is too short for this window length: the reflect padding needs T > window_length / 2")
+            out.append((B, c.value, f.value, w.value))
+        return out
+
+    def resolution_disc_wgrad_planes(self, B, T, band, layer):
+        """Split-K planes of the weight-gradient launch of band_convs.{band}.{layer} at (B, T) (tests / tools)."""
+        n = int(self.lib.st_resolution_disc_wgrad_planes(self.handle, int(B), int(T), int(band), int(layer)))
+        if n < 1:
+            raise NativeError(n, f"st_resolution_disc_wgrad_planes(B={B}, T={T}, band={band}, layer={layer})")
+        return n
+
+    def resolution_disc_forward(self, x, fmaps, train, stream):
+        """x (B, 1, T) -> the 21 feature maps; train: keep the activations for resolution_disc_train_backward."""
+        B, _, T = x.shape
+        ptrs = (ctypes.c_void_p * 21)(*[f.data_ptr() for f in fmaps])
+        fn = self.lib.st_resolution_disc_train_forward if train else self.lib.st_resolution_disc_forward
+        self._check(fn(self.handle, x.data_ptr(), ptrs, B, T, ctypes.c_void_p(stream)))
+
+    def resolution_disc_train_backward(self, B, T, d_fmaps, d_x, grad_flat, stream):
+        """d_fmaps: 21 tensors or None each; d x (None: not wanted) and every parameter gradient into grad_flat (None: none wanted)."""
+        if grad_flat is not None and grad_flat.numel() != self.grad_layout()[None]:
+            raise ValueError("grad_flat must hold grad_layout()[None] floats")
+        ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+        ptrs = (ctypes.c_void_p * 21)(*[ptr(f) for f in d_fmaps])
+        self._check(self.lib.st_resolution_disc_train_backward(self.handle, ptrs, ptr(d_x), ptr(grad_flat), B, T, ctypes.c_void_p(stream)))
 
     def finalize(self):
         """st_finalize on the parameters already loaded / bound: a vocoder handle packs its 16-bit inference copies again."""

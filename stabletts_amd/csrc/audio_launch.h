@@ -63,5 +63,8 @@ int mel_tile_frames(int n_fft);
 hipError_t launch_mel(const MelArgs& a, hipStream_t s);
 // mel_bwd_kernel<n_fft> over total_tiles blocks, then the gather kernel over B * L samples, on one stream
 hipError_t launch_mel_backward(const MelBwdArgs& a, hipStream_t s);
+// step 5 alone: the gather of a (B, frames, n_fft) workspace of windowed frame gradients onto the samples (reads ws, n_fft, hop, pad,
+// B, L, frames; writes out), for a caller that fills the workspace itself (resolution_disc_kernels.hip)
+hipError_t launch_mel_gather(const MelBwdArgs& a, hipStream_t s);
 
 }  // namespace st

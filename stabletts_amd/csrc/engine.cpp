@@ -679,6 +679,7 @@ void st_destroy(st_engine* e) {
     duration_destroy(e);
     mel_destroy(e);
     period_disc_destroy(e);
+    resolution_disc_destroy(e);
     sd_train_destroy(e);
     if (e->gstream) hipStreamDestroy(e->gstream);
     e->part_streams.destroy();
@@ -753,10 +754,10 @@ int st_repack(st_engine* e, void* stream) {
     if (e->kind == KIND_VOCODER) return e->fail(ST_ERR_UNSUPPORTED, "st_repack: vocoder handles re-pack through st_finalize");
     if (e->kind == KIND_MEL_EXTRACTOR) return e->fail(ST_ERR_UNSUPPORTED, "st_repack: mel-extractor handles re-read their filter bank through st_finalize");
     if (reads_params_in_place(e->kind)) return e->fail(ST_ERR_UNSUPPORTED, "st_repack: style-encoder / duration-predictor handles read their parameters in place");
-    if (e->kind == KIND_PERIOD_DISC) {      // the weight norm again, on the caller's stream
+    if (e->kind == KIND_PERIOD_DISC || e->kind == KIND_RESOLUTION_DISC) {      // the weight norm again, on the caller's stream
         if (!e->finalized) return e->fail(ST_ERR_STATE, "st_repack after st_bind_param / st_load_param of a new pointer: call st_finalize");
         HIPCHK(e, hipSetDevice(e->device));
-        return period_disc_weights(e, (hipStream_t)stream);
+        return e->kind == KIND_PERIOD_DISC ? period_disc_weights(e, (hipStream_t)stream) : resolution_disc_weights(e, (hipStream_t)stream);
     }
     if (!e->packed_once) return e->fail(ST_ERR_STATE, "st_repack needs one earlier st_finalize (it allocates the packed buffers)");
     // A re-bind / re-load since the last st_finalize may have moved fp32 tensors: st_repack is for in-place updates only.
@@ -778,8 +779,8 @@ int st_finalize(st_engine* e) {
         if (!kv.second.loaded) return e->fail(ST_ERR_STATE, "parameter not loaded: " + kv.first);
     HIPCHK(e, hipDeviceSynchronize());
     if (e->kind == KIND_MEL_EXTRACTOR) return mel_finalize(e);      // the filter bank's band table
-    if (e->kind == KIND_PERIOD_DISC) {                               // the weight norm of the new tensors
-        if (int rc = period_disc_weights(e, nullptr)) return rc;
+    if (e->kind == KIND_PERIOD_DISC || e->kind == KIND_RESOLUTION_DISC) {      // the weight norm of the new tensors
+        if (int rc = e->kind == KIND_PERIOD_DISC ? period_disc_weights(e, nullptr) : resolution_disc_weights(e, nullptr)) return rc;
         HIPCHK(e, hipDeviceSynchronize());
         e->finalized = true;
         return ST_OK;

@@ -1,7 +1,8 @@
 // The fp32 MFMA tile (v_mfma_f32_32x32x2_f32: bit-for-bit a k-ordered fp32 FMA chain) behind the style-encoder, duration-
-// predictor, Vocos-training and period-discriminator kernels, written once: the lane / wave mapping, the K loop, the walk over
-// the D fragment, the split-K weight-gradient kernel with its split rule, plane sum and launcher, and two small helpers
-// (grid_1d, block_sum256).  The conv kernels (sd_conv_kernel, pd_conv_kernel) keep their own operand staging and epilogues.
+// predictor, Vocos-training and discriminator kernels, written once: the lane / wave mapping (64 x 64, and 32 x 128 for GEMMs of
+// 32 rows), the K loop, the walk over the D fragment, the split-K weight-gradient kernel with its split rule, plane sum and
+// launcher, and two small helpers (grid_1d, block_sum256).  The conv kernels (sd_conv_kernel, pd_conv_kernel, rd_conv_kernel) keep
+// their own operand staging and epilogues.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -42,6 +43,15 @@ __device__ __forceinline__ void tile_mfma(f32x16& acc, const float* As, int a_st
 template <typename F>
 __device__ __forceinline__ void tile_for_each(const f32x16& acc, const TileLane& l, F f) {
     for (int i = 0; i < 16; ++i) f(l.wco * 32 + (i & 3) + 8 * (i >> 2) + 4 * l.h, acc[i]);
+}
+
+// The same MFMA on a 32 x 128 tile, for GEMMs whose M is 32 (the band convs of the resolution discriminator): four waves side by
+// side, wave w owns rows 0..31 x columns 32 w .. 32 w + 31.  Operand and D layout as above with wco = 0, wt = the wave.
+constexpr int kWideRows = 32, kWideCols = 128;
+
+__device__ __forceinline__ TileLane wide_lane() {
+    const int lane = threadIdx.x & 63;
+    return {lane & 31, lane >> 5, 0, (int)(threadIdx.x >> 6)};
 }
 
 inline unsigned grid_1d(int64_t n, int64_t cap) {      // blocks of 256 threads for a grid-stride loop over n elements
