@@ -380,6 +380,38 @@ int st_resolution_disc_train_forward(st_engine* e, const float* x, float* const*
 int st_resolution_disc_train_backward(st_engine* e, const float* const* d_fmaps, float* d_x /* nullable */, float* grad_flat /* nullable */,
                                       int B, int T, void* stream);
 
+/* ---- the three scalar GAN losses of a Vocos step (vocoders/vocos/models/loss.py:37-66), stateless ------------------------- */
+/* Each loss is a sum over a LIST of tensors of per-tensor means.  The list is given as host arrays of n_pairs fp32 device
+ * pointers (4-byte aligned: an entry may start anywhere inside a larger tensor) and element counts (each >= 1); a launch covers
+ * up to st_gan_loss_max_pairs() entries, whose table travels as a kernel argument, and a block sums st_gan_loss_chunk() elements.
+ * Every sum is fp64 in one fixed order without atomics: an entry's mean is the same bits alone, at any list position and at any
+ * address, and two runs agree bit for bit.
+ *   out     : 1 + n_pairs floats (device).  out[0] = the loss, out[1 + i] = the mean of entry i.
+ *   scratch : st_gan_loss_scratch_bytes(numels, n_pairs) bytes (device, 8-byte aligned), not needed after the call; the function
+ *             returns a negative ST_ERR_* for a bad list.  scratch_bytes: what the caller provides.
+ * st_feature_loss_forward (:37-43): out[1 + i] = mean|real_i - fake_i|, out[0] = 2 sum_i out[1 + i].
+ * st_lsgan_loss_forward, by mode: ST_LSGAN_REAL mean((1 - x_i)^2) (generator_loss, :58-66); ST_LSGAN_FAKE mean(x_i^2);
+ *   ST_LSGAN_REAL_FAKE the first for the even entries and the second for the odd ones, for discriminator_loss's (:45-56) list
+ *   r_0, g_0, r_1, g_1, ...;  out[0] = sum_i out[1 + i].
+ * Backward, elementwise from the same inputs; grad_loss: device scalar (d / d out[0]), read on the device:
+ *   st_feature_loss_backward: grad_fake_i = -grad_loss 2 / numel_i sign(real_i - fake_i), grad_real_i = -grad_fake_i (sign(0) = 0);
+ *     each entry of grad_real / grad_fake may be NULL (that tensor gets no gradient).
+ *   st_lsgan_loss_backward: grad_x_i = grad_loss 2 (x_i - 1) / numel_i, or grad_loss 2 x_i / numel_i; entries may be NULL.
+ * A null array or required pointer, n_pairs < 0, a count < 1, a misaligned pointer, an unknown mode or a scratch that is too small
+ * is ST_ERR_INVALID before anything touches the device.  n_pairs == 0 writes out[0] = 0. */
+enum { ST_LSGAN_REAL = 0, ST_LSGAN_FAKE = 1, ST_LSGAN_REAL_FAKE = 2 };
+int st_gan_loss_chunk(void);
+int st_gan_loss_max_pairs(void);
+int64_t st_gan_loss_scratch_bytes(const int64_t* numels, int n_pairs);
+int st_feature_loss_forward(const void* const* real, const void* const* fake, const int64_t* numels, int n_pairs, float* out,
+                            void* scratch, int64_t scratch_bytes, void* stream);
+int st_feature_loss_backward(const void* const* real, const void* const* fake, const int64_t* numels, int n_pairs,
+                             const float* grad_loss, void* const* grad_real, void* const* grad_fake, void* stream);
+int st_lsgan_loss_forward(const void* const* x, const int64_t* numels, int n_pairs, int mode, float* out, void* scratch,
+                          int64_t scratch_bytes, void* stream);
+int st_lsgan_loss_backward(const void* const* x, const int64_t* numels, int n_pairs, int mode, const float* grad_loss,
+                           void* const* grad_x, void* stream);
+
 /* ---- MelStyleEncoder and DurationPredictor: stages 1 and 3 of StableTTS.synthesise (models/model.py:79-81) ------- */
 /* Both run in fp32 (fp32-input MFMA for every convolution and linear): the durations they feed are ceil()ed
  * (model.py:83-84), so a 16-bit logw error would add or drop whole frames.  Inference only (eval mode: no dropout). */

@@ -24,6 +24,9 @@ for the Vocos multi-scale mel loss (``vocoders/vocos/models/loss.py:6``);
 ``vocoders.vocos.models.discriminator`` (``vocoders/vocos/train.py:19,54``) to the native classes of ``stabletts_amd.discriminator``;
 and ``install(resolution_discriminator="train")`` rebinds ``MultiResolutionDiscriminator`` and ``DiscriminatorR`` of that same
 module (``vocoders/vocos/train.py:19,55``), which need no torchaudio; each keyword leaves the other pair of names as it is;
+``install(gan_losses=True)`` rebinds ``feature_loss``, ``discriminator_loss`` and ``generator_loss`` of the user's own
+``vocoders.vocos.models.loss`` (``vocoders/vocos/train.py:20``) to the fused ones of ``stabletts_amd.gan_loss`` and leaves the two
+mel-loss classes of that module as they are;
 ``install(model=True)`` registers ``stabletts_amd.model`` as ``models.model`` (``train.py:18``, ``api.py``): a ``StableTTS`` built
 from the native classes whose ``forward`` runs the alignment search, ``mu_y``, the prior and duration losses and their gradients
 on the device (``alignment.align_and_losses``), so that the reference's ``train.py`` needs no edit and no other registration.
@@ -34,7 +37,7 @@ __all__ = ["install", "CFMDecoder", "TextEncoder", "MelStyleEncoder", "DurationP
 
 
 def install(text_encoder=False, vocoder=False, reference_encoder=False, duration_predictor=False, monotonic_align=False,
-            audio=False, discriminator=False, model=False, resolution_discriminator=False):
+            audio=False, discriminator=False, model=False, resolution_discriminator=False, gan_losses=False):
     """Make ``models.flow_matching`` (and optionally ``models.text_encoder`` / ``vocoders.vocos.models.model`` /
     ``models.reference_encoder`` / ``models.duration_predictor`` / ``monotonic_align`` / ``utils.audio``) resolve to the native drop-ins
     (call before importing models.model / api.get_vocoder)."""
@@ -96,6 +99,18 @@ def install(text_encoder=False, vocoder=False, reference_encoder=False, duration
                               f"sys.path, and are its own imports such as torchaudio installed?): {exc}") from exc
         ref.MultiResolutionDiscriminator = nd.MultiResolutionDiscriminator      # vocoders/vocos/train.py:19,55
         ref.DiscriminatorR = nd.DiscriminatorR
+    if gan_losses:
+        import importlib
+        from . import gan_loss as gl
+        try:                                                     # the user's module: its two mel-loss classes stay
+            ref = importlib.import_module("vocoders.vocos.models.loss")
+        except ImportError as exc:
+            raise ImportError("install(gan_losses=True) rebinds feature_loss, discriminator_loss and generator_loss inside "
+                              "vocoders.vocos.models.loss, which could not be imported (is the StableTTS checkout on "
+                              f"sys.path, and are its own imports such as torchaudio installed?): {exc}") from exc
+        ref.feature_loss = gl.feature_loss                       # vocoders/vocos/train.py: the three loss lines of a step
+        ref.discriminator_loss = gl.discriminator_loss
+        ref.generator_loss = gl.generator_loss
     if model:
         from . import model as md
         sys.modules["models.model"] = md                         # train.py:18, api.py: from models.model import StableTTS

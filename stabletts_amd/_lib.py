@@ -23,6 +23,7 @@ SOLVERS = {"euler": ST_SOLVER_EULER, "midpoint": ST_SOLVER_MIDPOINT, "rk4": ST_S
 
 ST_PAD_MODES = {"reflect": 0, "constant": 1, "replicate": 2, "circular": 3}
 ST_MEL_LOG, ST_MEL_LINEAR = 0, 1
+ST_LSGAN_REAL, ST_LSGAN_FAKE, ST_LSGAN_REAL_FAKE = 0, 1, 2
 
 
 class StConfig(ctypes.Structure):
@@ -157,6 +158,13 @@ PROTOTYPES = {
     "st_duration_loss": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
     "st_duration_loss_backward": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp]),
     "st_duration_loss_scratch_floats": (i32, []),
+    "st_gan_loss_chunk": (i32, []),
+    "st_gan_loss_max_pairs": (i32, []),
+    "st_gan_loss_scratch_bytes": (i64, [P(i64), i32]),
+    "st_feature_loss_forward": (i32, [P(vp), P(vp), P(i64), i32, vp, vp, i64, vp]),
+    "st_feature_loss_backward": (i32, [P(vp), P(vp), P(i64), i32, vp, P(vp), P(vp), vp]),
+    "st_lsgan_loss_forward": (i32, [P(vp), P(i64), i32, i32, vp, vp, i64, vp]),
+    "st_lsgan_loss_backward": (i32, [P(vp), P(i64), i32, i32, vp, P(vp), vp]),
     "st_create_mel_extractor": (i32, [P(StMelConfig), i32, P(vp)]),
     "st_mel_frames": (i64, [vp, i64]),
     "st_mel_forward": (i32, [vp, vp, i32, i64, vp, vp]),

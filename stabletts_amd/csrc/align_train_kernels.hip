@@ -4,6 +4,7 @@
 // Sums that decide a gradient or a loss accumulate in fp64 in one fixed order (per thread ascending, then a fixed tree):
 // no atomics, nothing depends on the grid, the batch or the neighbouring tokens.
 #include "common.h"
+#include "block_reduce.h"
 #include "align_train_launch.h"
 
 namespace st {
@@ -11,18 +12,6 @@ namespace st {
 namespace {
 
 constexpr float kLog2Pi = 1.8378770664093453f;
-
-// sum of v over the 256 threads of the block, same tree every time; red: 256 doubles of LDS.  Every thread gets the sum.
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
-    return red[0];
-}
 
 // frames of token j as the kernels count them: only where x_mask != 0, a negative count is 0, never more than Ty
 __device__ __forceinline__ long long clipped_count(const int32_t* dur, const float* xm, int j, int Ty) {
