@@ -12,8 +12,9 @@
  *     16-bit weight copies and its workspace.
  *   - work is enqueued on the caller's HIP stream (`stream` = hipStream_t, e.g.
  *     torch.cuda.current_stream().cuda_stream) with no implicit device synchronisation.
- *   - a handle is one of eight kinds, each with its own creator: the CFM decoder, the text encoder, the Vocos vocoder, the style
- *     encoder, the duration predictor, the mel extractor and the period and resolution discriminators of the Vocos training step; an
+ *   - a handle is one of nine kinds, each with its own creator: the CFM decoder, the text encoder, the Vocos vocoder, the style
+ *     encoder, the duration predictor, the mel extractor, the period and resolution discriminators of the Vocos training step and the
+ *     FireflyGAN vocoder; an
  *     entry point handed a handle of another kind returns ST_ERR_STATE.
  *   - one engine per device per process; an engine is not thread-safe (the reference is
  *     single-threaded per process: train.py:101-102, webui.py:128).
@@ -296,6 +297,58 @@ int st_vocos_forward_ragged(st_engine* e, const float* mel, const int64_t* lengt
  * One batch per call (no chunking): B * T * max(7 input_channels, intermediate_dim, 2304) < 2^31 and B <= 65535, else ST_ERR_INVALID. */
 int st_vocos_train_forward(st_engine* e, const float* mel, float* audio, int B, int T, void* stream);
 int st_vocos_train_backward(st_engine* e, const float* d_audio, float* d_mel /* nullable */, float* grad_flat, int B, int T, void* stream);
+
+/* ---- FireflyGAN vocoder (vocoders/ffgan, the default vocoder of api.py:19-24,39): mel -> waveform, inference only -------- */
+
+#define ST_FFGAN_MAX_STAGES 8
+#define ST_FFGAN_MAX_UPSAMPLES 8
+#define ST_FFGAN_MAX_RESBLOCKS 4
+#define ST_FFGAN_MAX_DILATIONS 4
+
+/* Replaces FireflyGANBase.__init__ (vocoders/ffgan/model.py:7-29,44-50): ConvNeXtEncoder(**config_dict["backbone"]) and
+ * HiFiGANGenerator(**config_dict["head"]).  The head's num_mels is the encoder's last width.
+ * What the native kernels implement -- anything else is ST_ERR_INVALID with a message from st_create_ffgan, before the device is touched:
+ *   - use_template == 0 (no noise convolutions);
+ *   - input_channels 64, 128 or 192; encoder kernel_size 7; 1..8 stages of depth >= 1 whose widths are multiples of 128 up to 1024;
+ *   - 1..8 upsamples, each with an even rate u in [2, 16] and kernel size 2u; the head's widths upsample_initial_channel / 2^i are
+ *     16 * 2^n with the last one >= 16, and upsample_initial_channel is 16, 32, 64 or a multiple of 128;
+ *   - 1..4 resblocks with odd kernel sizes <= 13 and 1..4 dilations each (one conv pair per dilation), every halo
+ *     (kernel / 2) * dilation <= 25 rows (the LDS patch of the convolution kernel holds 128 + 2 * 25 rows);
+ *   - odd pre / post conv kernel sizes <= 13. */
+typedef struct st_ffgan_config {
+    int32_t input_channels;                                   /* mel channels, model.py:10 */
+    int32_t n_stages;
+    int32_t depths[ST_FFGAN_MAX_STAGES];                      /* model.py:11 */
+    int32_t dims[ST_FFGAN_MAX_STAGES];                        /* model.py:12 */
+    int32_t kernel_size;                                      /* model.py:14 */
+    int32_t n_upsamples;
+    int32_t upsample_rates[ST_FFGAN_MAX_UPSAMPLES];           /* model.py:19; their product is the hop length */
+    int32_t upsample_kernel_sizes[ST_FFGAN_MAX_UPSAMPLES];    /* model.py:20 */
+    int32_t n_resblocks;
+    int32_t resblock_kernel_sizes[ST_FFGAN_MAX_RESBLOCKS];    /* model.py:21 */
+    int32_t n_dilations;
+    int32_t resblock_dilation_sizes[ST_FFGAN_MAX_RESBLOCKS][ST_FFGAN_MAX_DILATIONS];      /* model.py:22 */
+    int32_t upsample_initial_channel;                         /* model.py:24 */
+    int32_t pre_conv_kernel_size, post_conv_kernel_size;      /* model.py:26-27 */
+    int32_t use_template;                                     /* model.py:25; native: 0 */
+    int32_t operand_dtype;     /* ST_OPERAND_* of the MFMA operands (accumulation, LayerNorms, residual streams, conv_post, tanh: fp32) */
+} st_ffgan_config;
+
+/* The handle takes the parameters of FireflyGANBase.state_dict() under their reference names ("backbone.downsample_layers.0.0.weight",
+ * ..., "head.conv_pre.parametrizations.weight.original0" / "original1" (the g and v of a weight-normed conv), ...,
+ * "head.resblocks.<i>.blocks.<b>.convs1.<p>.bias", ...) through st_load_param / st_finalize, which folds w = g v / ||v|| (the norm over
+ * all dims but 0: the input channel of a ConvTranspose1d) and packs the 16-bit weights.  The other entry points reject the handle
+ * and vice versa. */
+int st_create_ffgan(const st_ffgan_config* cfg, int device, st_engine** out);
+
+/* Replaces FireflyGANBase.forward(x) (model.py:52-57): mel (B, input_channels, T) fp32 -> audio (B, T * hop) fp32, device pointers,
+ * hop = the product of the upsample rates.  No mask, as in the reference: every utterance is vocoded at the padded length T, and no
+ * kernel reads a neighbouring utterance.  The ParralelBlock mean is accumulated in block order on one stream, without atomics: two
+ * calls agree bit for bit.  Every tensor offset in the head kernels is 64-bit; large batches run in chunks of whole utterances so that
+ * the head's workspace (three fp32 tensors and one 16-bit tensor of the widest level, 14 bytes per channel-sample) stays below
+ * 1 GiB (one utterance if that alone is more) and the encoder's GEMM rows within 32-bit offsets.  T up to 2^20; a T whose encoder rows
+ * exceed the row bound on its own, and a batch that needs more than one chunk while debug capture is on, are ST_ERR_INVALID. */
+int st_ffgan_forward(st_engine* e, const float* mel, float* audio, int B, int T, void* stream);
 
 /* ---- period discriminator of the Vocos training step (vocoders/vocos/models/discriminator.py:32-75, train.py:98-128) ---- */
 /* One handle serves one DiscriminatorP(period, in_channels = 1, kernel_size = 5, stride = 3, lrelu_slope); the five of a

@@ -20,6 +20,8 @@ for the Vocos multi-scale mel loss (``vocoders/vocos/models/loss.py:6``);
 ``install(vocoder=True)`` registers ``stabletts_amd.vocos`` as ``vocoders.vocos.models.model`` (``api.py:26-28``), inference-only;
 ``install(vocoder="train")`` registers ``stabletts_amd.vocos_train`` instead, whose ``Vocos`` also trains natively in fp32
 (``vocoders/vocos/train.py:94``: the generator);
+``install(ffgan=True)`` registers ``stabletts_amd.ffgan`` as ``vocoders.ffgan.model`` (``api.py:21-23``: the default vocoder,
+``FireflyGANBaseWrapper``), inference-only like the reference;
 ``install(discriminator="train")`` rebinds ``MultiPeriodDiscriminator`` and ``DiscriminatorP`` of the user's own
 ``vocoders.vocos.models.discriminator`` (``vocoders/vocos/train.py:19,54``) to the native classes of ``stabletts_amd.discriminator``;
 and ``install(resolution_discriminator="train")`` rebinds ``MultiResolutionDiscriminator`` and ``DiscriminatorR`` of that same
@@ -33,11 +35,11 @@ on the device (``alignment.align_and_losses``), so that the reference's ``train.
 """
 import sys
 
-__all__ = ["install", "CFMDecoder", "TextEncoder", "MelStyleEncoder", "DurationPredictor", "maximum_path", "LogMelSpectrogram", "StableTTS"]
+__all__ = ["install", "CFMDecoder", "TextEncoder", "MelStyleEncoder", "DurationPredictor", "maximum_path", "LogMelSpectrogram", "StableTTS", "FireflyGANBase"]
 
 
 def install(text_encoder=False, vocoder=False, reference_encoder=False, duration_predictor=False, monotonic_align=False,
-            audio=False, discriminator=False, model=False, resolution_discriminator=False, gan_losses=False):
+            audio=False, discriminator=False, model=False, resolution_discriminator=False, gan_losses=False, ffgan=False):
     """Make ``models.flow_matching`` (and optionally ``models.text_encoder`` / ``vocoders.vocos.models.model`` /
     ``models.reference_encoder`` / ``models.duration_predictor`` / ``monotonic_align`` / ``utils.audio``) resolve to the native drop-ins
     (call before importing models.model / api.get_vocoder)."""
@@ -52,6 +54,9 @@ def install(text_encoder=False, vocoder=False, reference_encoder=False, duration
     elif vocoder:
         from . import vocos
         sys.modules["vocoders.vocos.models.model"] = vocos      # api.py:26-28: from vocoders.vocos.models.model import Vocos
+    if ffgan:
+        from . import ffgan as fg
+        sys.modules["vocoders.ffgan.model"] = fg                 # api.py:21-23: from vocoders.ffgan.model import FireflyGANBaseWrapper
     if reference_encoder == "train":                             # MelStyleEncoder with native_training = True
         from . import reference_encoder_train as re_
         sys.modules["models.reference_encoder"] = re_            # models/model.py:8
@@ -124,6 +129,9 @@ def __getattr__(name):
     if name == "Vocos":
         from .vocos import Vocos
         return Vocos
+    if name == "FireflyGANBase":
+        from .ffgan import FireflyGANBase
+        return FireflyGANBase
     if name == "TextEncoder":
         from .text_encoder import TextEncoder
         return TextEncoder

@@ -60,12 +60,56 @@ class StResolutionDiscConfig(ctypes.Structure):
                 + [(f"band_hi{c}", ctypes.c_int32) for c in range(5)] + [("lrelu_slope", ctypes.c_float)])
 
 
+class StFfganConfig(ctypes.Structure):
+    """st_ffgan_config with its arrays as named fields (the same layout): depths0..7, dims0..7, upsample_rates0..7,
+    upsample_kernel_sizes0..7, resblock_kernel_sizes0..3, resblock_dilation_sizes<block>_<pair>."""
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        ["input_channels", "n_stages"] + [f"depths{i}" for i in range(8)] + [f"dims{i}" for i in range(8)] + ["kernel_size", "n_upsamples"]
+        + [f"upsample_rates{i}" for i in range(8)] + [f"upsample_kernel_sizes{i}" for i in range(8)] + ["n_resblocks"]
+        + [f"resblock_kernel_sizes{i}" for i in range(4)] + ["n_dilations"]
+        + [f"resblock_dilation_sizes{b}_{p}" for b in range(4) for p in range(4)]
+        + ["upsample_initial_channel", "pre_conv_kernel_size", "post_conv_kernel_size", "use_template", "operand_dtype"])]
+
+
+def ffgan_config_fields(backbone, head):
+    """The reference's ``config_dict["backbone"]`` / ``["head"]`` (vocoders/ffgan/model.py:7-29) as StFfganConfig's fields;
+    ValueError where the lists do not fit the struct's arrays or each other (the native limits themselves: st_create_ffgan)."""
+    depths, dims = list(backbone["depths"]), list(backbone["dims"])
+    rates, kernels = list(head["upsample_rates"]), list(head["upsample_kernel_sizes"])
+    rk, rd = list(head["resblock_kernel_sizes"]), [list(d) for d in head["resblock_dilation_sizes"]]
+    if len(depths) != len(dims) or not 1 <= len(dims) <= 8:
+        raise ValueError("backbone depths and dims must have the same length, 1..8")
+    if len(rates) != len(kernels) or not 1 <= len(rates) <= 8:
+        raise ValueError("head upsample_rates and upsample_kernel_sizes must have the same length, 1..8")
+    if len(rk) != len(rd) or not 1 <= len(rk) <= 4:
+        raise ValueError("head resblock_kernel_sizes and resblock_dilation_sizes must have the same length, 1..4")
+    if len({len(d) for d in rd}) != 1 or not 1 <= len(rd[0]) <= 4:
+        raise ValueError("every resblock needs the same number of dilations, 1..4")
+    if int(head["num_mels"]) != dims[-1]:
+        raise ValueError("the head's num_mels must be the encoder's last width")
+    f = {n: 0 for n, _ in StFfganConfig._fields_}
+    f.update(input_channels=backbone["input_channels"], n_stages=len(dims), kernel_size=backbone.get("kernel_size", 7),
+             n_upsamples=len(rates), n_resblocks=len(rk), n_dilations=len(rd[0]),
+             upsample_initial_channel=head["upsample_initial_channel"], pre_conv_kernel_size=head["pre_conv_kernel_size"],
+             post_conv_kernel_size=head["post_conv_kernel_size"], use_template=int(bool(head.get("use_template", True))))
+    for i, (a, b) in enumerate(zip(depths, dims)):
+        f[f"depths{i}"], f[f"dims{i}"] = a, b
+    for i, (a, b) in enumerate(zip(rates, kernels)):
+        f[f"upsample_rates{i}"], f[f"upsample_kernel_sizes{i}"] = a, b
+    for b, (k, ds) in enumerate(zip(rk, rd)):
+        f[f"resblock_kernel_sizes{b}"] = k
+        for p, d in enumerate(ds):
+            f[f"resblock_dilation_sizes{b}_{p}"] = d
+    return f
+
+
 # Engine(...) keyword whose value is a configuration dict -> (its struct, the creator it goes to); in the order Engine looks
 CREATORS = {"mel": (StMelConfig, "st_create_mel_extractor"), "style_encoder": (StStyleEncoderConfig, "st_create_style_encoder"),
             "duration_predictor": (StDurationPredictorConfig, "st_create_duration_predictor"),
             "vocoder": (StVocosConfig, "st_create_vocoder"),
             "period_discriminator": (StPeriodDiscConfig, "st_create_period_discriminator"),
-            "resolution_discriminator": (StResolutionDiscConfig, "st_create_resolution_discriminator")}
+            "resolution_discriminator": (StResolutionDiscConfig, "st_create_resolution_discriminator"),
+            "ffgan": (StFfganConfig, "st_create_ffgan")}
 
 
 class NativeError(RuntimeError):
@@ -127,6 +171,8 @@ PROTOTYPES = {
     "st_vocos_forward_ragged": (i32, [vp, vp, P(i64), vp, i32, i32, vp]),
     "st_vocos_train_forward": (i32, [vp, vp, vp, i32, i32, vp]),
     "st_vocos_train_backward": (i32, [vp, vp, vp, vp, i32, i32, vp]),
+    "st_create_ffgan": (i32, [P(StFfganConfig), i32, P(vp)]),
+    "st_ffgan_forward": (i32, [vp, vp, vp, i32, i32, vp]),
     "st_create_period_discriminator": (i32, [P(StPeriodDiscConfig), i32, P(vp)]),
     "st_period_disc_fmap_shape": (i32, [vp, i32, i32, P(i64), P(i64)]),
     "st_period_disc_forward": (i32, [vp, vp, P(vp), i32, i32, vp]),
@@ -211,7 +257,8 @@ class Engine:
 
     def __init__(self, noise_channels, hidden_channels, filter_channels, n_heads, n_layers, kernel_size,
                  gin_channels, operand_dtype="f16", device=0, text_encoder_vocab=None, vocoder=None,
-                 style_encoder=None, duration_predictor=None, mel=None, period_discriminator=None, resolution_discriminator=None):
+                 style_encoder=None, duration_predictor=None, mel=None, period_discriminator=None, resolution_discriminator=None,
+                 ffgan=None):
         """text_encoder_vocab: None -> CFM decoder estimator (st_create); n_vocab -> TextEncoder handle
         (st_create_text_encoder; noise_channels is then the encoder's out_channels).
         vocoder: dict(input_channels, dim, intermediate_dim, num_layers, n_fft, hop_length) -> Vocos handle
@@ -223,14 +270,15 @@ class Engine:
         pad_mode an ST_PAD_* value, n_mels 0 for a linear spectrogram).
         period_discriminator: dict(period, lrelu_slope) -> DiscriminatorP handle (st_create_period_discriminator), fp32.
         resolution_discriminator: dict(window_length, band_lo0..4, band_hi0..4, lrelu_slope) -> DiscriminatorR handle
-        (st_create_resolution_discriminator), fp32."""
+        (st_create_resolution_discriminator), fp32.
+        ffgan: the fields of StFfganConfig (ffgan_config_fields) -> FireflyGAN vocoder handle (st_create_ffgan)."""
         self.lib = load()
         if operand_dtype not in OPERAND_DTYPES:
             raise ValueError(f"operand_dtype must be one of {sorted(OPERAND_DTYPES)}")
         self.operand_dtype = operand_dtype
         h = ctypes.c_void_p()
         dicts = dict(mel=mel, style_encoder=style_encoder, duration_predictor=duration_predictor, vocoder=vocoder,
-                     period_discriminator=period_discriminator, resolution_discriminator=resolution_discriminator)
+                     period_discriminator=period_discriminator, resolution_discriminator=resolution_discriminator, ffgan=ffgan)
         kw = next((k for k in CREATORS if dicts[k] is not None), None)
         if kw:          # a configuration dict: its struct's fields by name (operand_dtype, where the struct has one, from the argument)
             (struct, creator), d = CREATORS[kw], dicts[kw]
@@ -323,6 +371,11 @@ class Engine:
     def vocos_forward(self, mel, audio, stream):
         B, _, T = mel.shape
         self._check(self.lib.st_vocos_forward(self.handle, mel.data_ptr(), audio.data_ptr(), B, T, ctypes.c_void_p(stream)))
+
+    def ffgan_forward(self, mel, audio, stream):
+        """mel (B, input_channels, T) -> audio (B, T * hop) (FireflyGAN vocoder handles)."""
+        B, _, T = mel.shape
+        self._check(self.lib.st_ffgan_forward(self.handle, mel.data_ptr(), audio.data_ptr(), B, T, ctypes.c_void_p(stream)))
 
     def vocos_forward_ragged(self, mel, lengths, audio, stream):
         """st_vocos_forward with utterance b at its own length lengths[b] (a sequence of B ints, host side)."""

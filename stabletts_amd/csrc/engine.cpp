@@ -680,6 +680,7 @@ void st_destroy(st_engine* e) {
     mel_destroy(e);
     period_disc_destroy(e);
     resolution_disc_destroy(e);
+    ffgan_destroy(e);
     sd_train_destroy(e);
     if (e->gstream) hipStreamDestroy(e->gstream);
     e->part_streams.destroy();
@@ -751,7 +752,7 @@ int st_bind_param(st_engine* e, const char* name, const float* data, const int64
 
 int st_repack(st_engine* e, void* stream) {
     if (!e) return ST_ERR_INVALID;
-    if (e->kind == KIND_VOCODER) return e->fail(ST_ERR_UNSUPPORTED, "st_repack: vocoder handles re-pack through st_finalize");
+    if (e->kind == KIND_VOCODER || e->kind == KIND_FFGAN) return e->fail(ST_ERR_UNSUPPORTED, "st_repack: vocoder handles re-pack through st_finalize");
     if (e->kind == KIND_MEL_EXTRACTOR) return e->fail(ST_ERR_UNSUPPORTED, "st_repack: mel-extractor handles re-read their filter bank through st_finalize");
     if (reads_params_in_place(e->kind)) return e->fail(ST_ERR_UNSUPPORTED, "st_repack: style-encoder / duration-predictor handles read their parameters in place");
     if (e->kind == KIND_PERIOD_DISC || e->kind == KIND_RESOLUTION_DISC) {      // the weight norm again, on the caller's stream
@@ -796,6 +797,11 @@ int st_finalize(st_engine* e) {
         for (void* p : e->owned) hipFree(p);
         e->owned.clear(); e->weight_bytes = 0;
         return vocos_finalize(e);
+    }
+    if (e->kind == KIND_FFGAN) {
+        for (void* p : e->owned) hipFree(p);
+        e->owned.clear(); e->weight_bytes = 0;
+        return ffgan_finalize(e);
     }
     e->drop_graphs();          // instantiated graphs hold fp32 parameter pointers that a re-bind may have changed
     pk_drop(e);                // ... and so do the recorded re-pack jobs

@@ -1,0 +1,353 @@
+// FireflyGAN vocoder behind the C ABI (st_create_ffgan / st_ffgan_forward): parameter table, weight-norm fold and packing, and the
+// launch sequence.  Reference: vocoders/ffgan/model.py:7-29,44-57, backbone.py:78-214, head.py:25-133,136-249 (use_template=False).
+// The ConvNeXt encoder runs like the Vocos backbone (engine_vocos.cpp): its GEMMs on the implicit-GEMM kernels of the decoder over
+// the flattened rows of the batch, the row kernels at a run-time width.  The HiFi-GAN head runs on the convolution family of
+// ffgan_kernels.hip, every level a time-major [item][L][C] tensor.
+#include "engine_internal.h"
+#include "ffgan_launch.h"
+#include "vocos_launch.h"
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+
+using namespace st;
+using namespace sthost;
+
+namespace sthost {
+
+struct FfConv {             // one convolution of the head: fragment-ordered 16-bit weights + fp32 bias
+    void* wfrag = nullptr;
+    const float* bias = nullptr;
+    int cin = 0, cout = 0, taps = 0, dil = 1;
+};
+
+struct FfganState {
+    st_ffgan_config cfg{};
+    int hop = 1;
+    Conv stem;
+    std::vector<Conv> down;                           // the k = 1 downsample convs of stages 1..
+    std::vector<std::vector<Conv>> pw1, pw2;          // [stage][block]
+    FfConv pre;
+    std::vector<FfConv> ups;
+    std::vector<std::vector<std::vector<FfConv>>> c1, c2;      // [level][resblock][pair]
+    float* post_w = nullptr;                          // [taps][C] fp32
+};
+
+static const std::string kWn0 = "parametrizations.weight.original0", kWn1 = "parametrizations.weight.original1";
+static std::string ds(int i, int j) { return "backbone.downsample_layers." + std::to_string(i) + "." + std::to_string(j) + "."; }
+static std::string blk(int i, int j) { return "backbone.stages." + std::to_string(i) + "." + std::to_string(j) + "."; }
+static std::string rb(int i, int b, int which, int p) {
+    return "head.resblocks." + std::to_string(i) + ".blocks." + std::to_string(b) + ".convs" + std::to_string(which) + "." + std::to_string(p) + ".";
+}
+static int head_width(const st_ffgan_config& c, int level) { return c.upsample_initial_channel >> level; }      // level 0: conv_pre's output
+
+// The limits of the native kernels (include/stabletts_hip.h: st_ffgan_config); nullptr: supported
+static const char* ffgan_unsupported(const st_ffgan_config& c) {
+    if (c.operand_dtype != ST_OPERAND_BF16 && c.operand_dtype != ST_OPERAND_F16) return "operand_dtype";
+    if (c.use_template) return "use_template: the native head is built without the noise convolutions (use_template=False)";
+    if (c.input_channels % 64 != 0 || c.input_channels < 64 || c.input_channels > 192) return "input_channels must be 64, 128 or 192";
+    if (c.kernel_size != 7) return "the native encoder kernels are built for kernel_size == 7";
+    if (c.n_stages < 1 || c.n_stages > ST_FFGAN_MAX_STAGES) return "the encoder has 1..8 stages";
+    for (int i = 0; i < c.n_stages; ++i) {
+        if (c.depths[i] < 1 || c.depths[i] > 64) return "encoder depths must be in [1, 64]";
+        if (c.dims[i] < 128 || c.dims[i] % 128 != 0 || c.dims[i] > kFfgMaxDim) return "encoder widths must be multiples of 128 up to 1024 (the GEMM and row kernels)";
+    }
+    if (c.n_upsamples < 1 || c.n_upsamples > ST_FFGAN_MAX_UPSAMPLES) return "the head has 1..8 upsamples";
+    const int c0 = c.upsample_initial_channel;
+    if (c0 < 16 || c0 > 1024 || (c0 & (c0 - 1)) != 0) return "head widths must be 16 * 2^n: upsample_initial_channel is a power of two in [16, 1024]";
+    if ((c0 >> c.n_upsamples) < 16) return "head widths must be 16 * 2^n: the last level has fewer than 16 channels";
+    for (int i = 0; i < c.n_upsamples; ++i) {
+        const int u = c.upsample_rates[i], k = c.upsample_kernel_sizes[i];
+        if (u < 2 || u > 16 || (u & 1)) return "upsample rates must be even, in [2, 16]";
+        if (k != 2 * u) return "the native transposed convolution is built for upsample_kernel_size == 2 * upsample_rate";
+    }
+    if (c.n_resblocks < 1 || c.n_resblocks > ST_FFGAN_MAX_RESBLOCKS) return "a ParralelBlock has 1..4 resblocks";
+    if (c.n_dilations < 1 || c.n_dilations > ST_FFGAN_MAX_DILATIONS) return "a resblock has 1..4 dilations";
+    for (int b = 0; b < c.n_resblocks; ++b) {
+        const int k = c.resblock_kernel_sizes[b];
+        if (k < 1 || !(k & 1) || k > kFfgMaxTaps) return "resblock kernel sizes must be odd and <= 13";
+        for (int p = 0; p < c.n_dilations; ++p) {
+            const int d = c.resblock_dilation_sizes[b][p];
+            if (d < 1) return "resblock dilations must be >= 1";
+            if ((k / 2) * d > kFfgMaxHalo) return "resblock halo (kernel_size / 2) * dilation exceeds the 25 rows of the convolution kernel's LDS patch";
+        }
+    }
+    for (int k : {c.pre_conv_kernel_size, c.post_conv_kernel_size})
+        if (k < 1 || !(k & 1) || k > kFfgMaxTaps) return "pre / post conv kernel sizes must be odd and <= 13";
+    return nullptr;
+}
+
+static void wn_expect(st_engine* e, const std::string& p, int64_t d0, int64_t d1, int64_t k, int64_t nbias) {
+    expect(e, p + "bias", {nbias});
+    expect(e, p + kWn0, {d0, 1, 1});
+    expect(e, p + kWn1, {d0, d1, k});
+}
+
+static void ffgan_build_params(st_engine* e, const st_ffgan_config& c) {
+    const int64_t M = c.input_channels;
+    for (int i = 0; i < c.n_stages; ++i) {
+        const int64_t C = c.dims[i];
+        if (i == 0) {                                                                               // backbone.py:160-169
+            expect(e, ds(0, 0) + "weight", {C, M, 7}); expect(e, ds(0, 0) + "bias", {C});
+            expect(e, ds(0, 1) + "weight", {C}); expect(e, ds(0, 1) + "bias", {C});
+        } else {                                                                                    // :173-176
+            const int64_t Cp = c.dims[i - 1];
+            expect(e, ds(i, 0) + "weight", {Cp}); expect(e, ds(i, 0) + "bias", {Cp});
+            expect(e, ds(i, 1) + "weight", {C, Cp, 1}); expect(e, ds(i, 1) + "bias", {C});
+        }
+        for (int j = 0; j < c.depths[i]; ++j) {                                                     // :104-121
+            const std::string p = blk(i, j);
+            expect(e, p + "dwconv.weight", {C, 1, 7}); expect(e, p + "dwconv.bias", {C});
+            expect(e, p + "norm.weight", {C}); expect(e, p + "norm.bias", {C});
+            expect(e, p + "pwconv1.weight", {4 * C, C}); expect(e, p + "pwconv1.bias", {4 * C});
+            expect(e, p + "pwconv2.weight", {C, 4 * C}); expect(e, p + "pwconv2.bias", {C});
+            expect(e, p + "gamma", {C});
+        }
+    }
+    const int64_t D = c.dims[c.n_stages - 1];
+    expect(e, "backbone.norm.weight", {D}); expect(e, "backbone.norm.bias", {D});                 // :198
+    const int64_t C0 = c.upsample_initial_channel;
+    wn_expect(e, "head.conv_pre.", C0, D, c.pre_conv_kernel_size, C0);                             // head.py:158-166
+    for (int i = 0; i < c.n_upsamples; ++i) {
+        const int64_t ci = head_width(c, i), co = head_width(c, i + 1);
+        wn_expect(e, "head.ups." + std::to_string(i) + ".", ci, co, c.upsample_kernel_sizes[i], co);      // :177-187: (in, out, k), g over dim 0
+        for (int b = 0; b < c.n_resblocks; ++b)
+            for (int p = 0; p < c.n_dilations; ++p)
+                for (int which = 1; which <= 2; ++which) wn_expect(e, rb(i, b, which, p), co, co, c.resblock_kernel_sizes[b], co);      // :29-99
+    }
+    wn_expect(e, "head.conv_post.", 1, head_width(c, c.n_upsamples), c.post_conv_kernel_size, 1);  // :214-222
+}
+
+// st_finalize of an ffgan handle: 16-bit GEMM weights of the encoder, w = g v / ||v|| of the head's convs in fragment order
+int ffgan_finalize(st_engine* e) {
+    FfganState* v = e->ffg;
+    const st_ffgan_config& c = v->cfg;
+    hipStream_t s = nullptr;
+    auto pack = [&](Conv& cv, const std::string& wname, const std::string& bname, int cout, int cin, int taps) -> int {
+        cv.cout = cout; cv.cin = cin * taps; cv.taps = 1; cv.split = false;      // consumed as a k = 1 GEMM (the stem over im2col rows)
+        int rc = dev_alloc(e, &cv.w, (size_t)cout * taps * cin * 2); if (rc) return rc;
+        HIPCHK(e, launch_pack_weight(e->dt, P(e, wname), cout, cin, taps, 0, cin, cv.w, 0, cin, 0, cin, 0, s));
+        cv.bias = const_cast<float*>(P(e, bname));
+        return ST_OK;
+    };
+    int rc;
+    v->down.assign(c.n_stages, Conv()); v->pw1.assign(c.n_stages, {}); v->pw2.assign(c.n_stages, {});
+    for (int i = 0; i < c.n_stages; ++i) {
+        const int C = c.dims[i];
+        if (i == 0) { if ((rc = pack(v->stem, ds(0, 0) + "weight", ds(0, 0) + "bias", C, c.input_channels, 7))) return rc; }
+        else if ((rc = pack(v->down[i], ds(i, 1) + "weight", ds(i, 1) + "bias", C, c.dims[i - 1], 1))) return rc;
+        v->pw1[i].assign(c.depths[i], Conv()); v->pw2[i].assign(c.depths[i], Conv());
+        for (int j = 0; j < c.depths[i]; ++j) {
+            if ((rc = pack(v->pw1[i][j], blk(i, j) + "pwconv1.weight", blk(i, j) + "pwconv1.bias", 4 * C, C, 1))) return rc;
+            if ((rc = pack(v->pw2[i][j], blk(i, j) + "pwconv2.weight", blk(i, j) + "pwconv2.bias", C, 4 * C, 1))) return rc;
+        }
+    }
+    // weight norm: one scale per row of dim 0, then the fold inside the packing kernel
+    auto wn_scale = [&](const std::string& p, int rows, int inner, float** scale) -> int {
+        int rc2 = dev_alloc(e, (void**)scale, (size_t)rows * 4); if (rc2) return rc2;
+        HIPCHK(e, launch_ffg_wn_scale(P(e, p + kWn1), P(e, p + kWn0), rows, inner, *scale, s));
+        return ST_OK;
+    };
+    auto conv = [&](FfConv& cv, const std::string& p, int cout, int cin, int taps, int dil) -> int {
+        float* scale = nullptr;
+        int rc2 = wn_scale(p, cout, cin * taps, &scale); if (rc2) return rc2;
+        cv.cin = cin; cv.cout = cout; cv.taps = taps; cv.dil = dil; cv.bias = P(e, p + "bias");
+        if ((rc2 = dev_alloc(e, &cv.wfrag, ffg_frag_bytes(cout, cin, taps)))) return rc2;
+        HIPCHK(e, launch_ffg_pack_conv(e->dt, P(e, p + kWn1), scale, cout, cin, taps, 0, cv.wfrag, s));
+        return ST_OK;
+    };
+    const int D = c.dims[c.n_stages - 1];
+    if ((rc = conv(v->pre, "head.conv_pre.", c.upsample_initial_channel, D, c.pre_conv_kernel_size, 1))) return rc;
+    v->ups.assign(c.n_upsamples, FfConv()); v->c1.assign(c.n_upsamples, {}); v->c2.assign(c.n_upsamples, {});
+    for (int i = 0; i < c.n_upsamples; ++i) {
+        const int ci = head_width(c, i), co = head_width(c, i + 1), u = c.upsample_rates[i];
+        const std::string p = "head.ups." + std::to_string(i) + ".";
+        FfConv& up = v->ups[i];
+        float *scale = nullptr, *bias = nullptr;
+        if ((rc = wn_scale(p, ci, co * 2 * u, &scale))) return rc;
+        up.cin = ci; up.cout = u * co; up.taps = 3; up.dil = 1;
+        if ((rc = dev_alloc(e, &up.wfrag, ffg_frag_bytes(up.cout, ci, 3)))) return rc;
+        HIPCHK(e, launch_ffg_pack_conv(e->dt, P(e, p + kWn1), scale, up.cout, ci, 3, u, up.wfrag, s));
+        if ((rc = dev_alloc(e, (void**)&bias, (size_t)up.cout * 4))) return rc;
+        HIPCHK(e, launch_ffg_tile_bias(P(e, p + "bias"), co, u, bias, s));
+        up.bias = bias;
+        v->c1[i].assign(c.n_resblocks, std::vector<FfConv>(c.n_dilations)); v->c2[i].assign(c.n_resblocks, std::vector<FfConv>(c.n_dilations));
+        for (int b = 0; b < c.n_resblocks; ++b)
+            for (int q = 0; q < c.n_dilations; ++q) {
+                if ((rc = conv(v->c1[i][b][q], rb(i, b, 1, q), co, co, c.resblock_kernel_sizes[b], c.resblock_dilation_sizes[b][q]))) return rc;
+                if ((rc = conv(v->c2[i][b][q], rb(i, b, 2, q), co, co, c.resblock_kernel_sizes[b], 1))) return rc;
+            }
+    }
+    {
+        const int cl = head_width(c, c.n_upsamples), k = c.post_conv_kernel_size;
+        float* scale = nullptr;
+        if ((rc = wn_scale("head.conv_post.", 1, cl * k, &scale))) return rc;
+        if ((rc = dev_alloc(e, (void**)&v->post_w, (size_t)cl * k * 4))) return rc;
+        HIPCHK(e, launch_ffg_pack_post(P(e, "head.conv_post." + kWn1), scale, cl, k, v->post_w, s));
+    }
+    HIPCHK(e, hipDeviceSynchronize());
+    e->finalized = true;
+    return ST_OK;
+}
+
+void ffgan_destroy(st_engine* e) {
+    if (!e->ffg) return;
+    delete e->ffg; e->ffg = nullptr;
+}
+
+// widest level of one utterance, in channel-samples per mel frame: max over the levels of (product of the rates so far) * width
+static int64_t ffgan_level_elems(const st_ffgan_config& c) {
+    int64_t up = 1, widest = head_width(c, 0);
+    for (int i = 0; i < c.n_upsamples; ++i) { up *= c.upsample_rates[i]; widest = std::max(widest, up * head_width(c, i + 1)); }
+    return widest;
+}
+static int ffgan_max_dim(const st_ffgan_config& c) { return *std::max_element(c.dims, c.dims + c.n_stages); }
+// rows per chunk: 32-bit operand offsets of the encoder's GEMMs (widest operand row: the im2col rows or 4 * dim)
+static int64_t ffgan_max_rows(const st_ffgan_config& c) {
+    const int64_t widest = std::max<int64_t>(7 * (int64_t)c.input_channels, 4 * (int64_t)ffgan_max_dim(c));
+    return (((int64_t)1 << 31) - 1) / (widest * 2);
+}
+constexpr int64_t kFfganHeadBytes = (int64_t)1 << 30;      // bound of the head's level tensors per chunk (stabletts_hip.h: st_ffgan_forward)
+constexpr int kFfganMaxT = 1 << 20;
+
+static int ffgan_forward_chunk(st_engine* e, const float* mel, float* audio, int B, int T, hipStream_t s) {
+    FfganState* v = e->ffg;
+    const st_ffgan_config& c = v->cfg;
+    const int M = c.input_channels, Dmax = ffgan_max_dim(c), D = c.dims[c.n_stages - 1], C0 = c.upsample_initial_channel;
+    const int64_t R = (int64_t)B * T, lvl = ffgan_level_elems(c) * R;
+    const bool cap = e->capture;
+
+    size_t off = 0;
+    auto want = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
+    const size_t o_a16 = want((size_t)R * 7 * M * 2), o_xa = want((size_t)R * Dmax * 4), o_xb = want((size_t)R * Dmax * 4), o_h16 = want((size_t)R * Dmax * 2);
+    const size_t o_u16 = want((size_t)R * 4 * Dmax * 2), o_enc32 = want((size_t)R * D * 4), o_enc16 = want((size_t)R * D * 2), o_pre = want((size_t)R * C0 * 4);
+    const size_t o_X = want((size_t)lvl * 4), o_Y = want((size_t)lvl * 4), o_Mn = want((size_t)lvl * 4), o_U = want((size_t)lvl * 2);
+    const size_t o_pt = cap ? want((size_t)R * v->hop * 4) : 0;
+    int rc = ensure_ws(e, off); if (rc) return rc;
+    void* a16 = e->ws + o_a16; float* x = (float*)(e->ws + o_xa); float* xn = (float*)(e->ws + o_xb); void* h16 = e->ws + o_h16; void* u16 = e->ws + o_u16;
+    float* enc32 = (float*)(e->ws + o_enc32); void* enc16 = e->ws + o_enc16; float* pre32 = (float*)(e->ws + o_pre);
+    float* X = (float*)(e->ws + o_X); float* Y = (float*)(e->ws + o_Y); float* Mn = (float*)(e->ws + o_Mn); void* U = e->ws + o_U;
+    float* pretanh = cap ? (float*)(e->ws + o_pt) : nullptr;
+
+    auto args = [&](const Conv& cv) {
+        ConvGemmArgs a; memset(&a, 0, sizeof(a));
+        a.w = cv.w; a.bias = cv.bias; a.cout = cv.cout; a.T = (int)R; a.n_items = 1;     // flattened rows
+        a.a0_mod = 1; a.a1_mod = 1; a.mask_mod = 1; a.zeros = e->zeros;
+        return a;
+    };
+    // ---- ConvNeXtEncoder.forward (backbone.py:206-214)
+    for (int i = 0; i < c.n_stages; ++i) {
+        const int C = c.dims[i];
+        if (i == 0) {       // stem: k = 7 conv as an im2col GEMM, then the per-frame LayerNorm
+            HIPCHK(e, launch_voc_im2col7(e->dt, mel, B, M, T, a16, s));
+            ConvGemmArgs a = args(v->stem); a.a0 = a16; a.c0 = 7 * M; a.out32 = x;
+            HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
+            HIPCHK(e, launch_ffg_ln(e->dt, x, P(e, ds(0, 1) + "weight"), P(e, ds(0, 1) + "bias"), R, C, x, nullptr, s));
+        } else {            // LayerNorm, then the k = 1 conv to the next width
+            const int Cp = c.dims[i - 1];
+            HIPCHK(e, launch_ffg_ln(e->dt, x, P(e, ds(i, 0) + "weight"), P(e, ds(i, 0) + "bias"), R, Cp, nullptr, h16, s));
+            ConvGemmArgs a = args(v->down[i]); a.a0 = h16; a.c0 = Cp; a.out32 = xn;
+            HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
+            std::swap(x, xn);
+        }
+        for (int j = 0; j < c.depths[i]; ++j) {      // ConvNeXtBlock.forward (backbone.py:124-143); DropPath is the identity in eval
+            const std::string p = blk(i, j);
+            HIPCHK(e, launch_ffg_dwconv_ln(e->dt, x, P(e, p + "dwconv.weight"), P(e, p + "dwconv.bias"), P(e, p + "norm.weight"), P(e, p + "norm.bias"),
+                                           B, T, C, h16, s));
+            {
+                ConvGemmArgs a = args(v->pw1[i][j]); a.a0 = h16; a.c0 = C; a.out16 = u16;
+                HIPCHK(e, gemm(e, 1, EPI_GELU16, a, s));
+            }
+            {       // x += gamma * (W u + b)
+                ConvGemmArgs a = args(v->pw2[i][j]); a.a0 = u16; a.c0 = 4 * C; a.out32 = x; a.gate = P(e, p + "gamma"); a.gate_stride = 0;
+                HIPCHK(e, gemm(e, 1, EPI_RESGATE, a, s));
+            }
+        }
+    }
+    HIPCHK(e, launch_ffg_ln(e->dt, x, P(e, "backbone.norm.weight"), P(e, "backbone.norm.bias"), R, D, enc32, enc16, s));
+    if (cap) capture(e, "ffgan.encoder", enc32, R * D, false, s);
+
+    // ---- HiFiGANGenerator.forward (head.py:226-249)
+    auto run = [&](const FfConv& cv, int L, FfgConvArgs a) -> hipError_t {
+        a.wfrag = cv.wfrag; a.bias = cv.bias; a.cin = cv.cin; a.cout = cv.cout; a.taps = cv.taps; a.dil = cv.dil; a.L = L; a.n_items = B;
+        return launch_ffg_conv(e->dt, a, s);
+    };
+    {
+        FfgConvArgs a{}; a.in16 = enc16; a.epi = FFG_F32; a.out32 = pre32;
+        HIPCHK(e, run(v->pre, T, a));
+    }
+    const float* cur = pre32;
+    int L = T;
+    const int nb = c.n_resblocks, np = c.n_dilations;
+    for (int i = 0; i < c.n_upsamples; ++i) {
+        {       // silu + ConvTranspose1d: [L][u * C] rows = the upsampled [L * u][C]
+            FfgConvArgs a{}; a.in32 = cur; a.epi = FFG_F32; a.out32 = X;
+            HIPCHK(e, run(v->ups[i], L, a));
+        }
+        L *= c.upsample_rates[i];
+        for (int b = 0; b < nb; ++b)             // ParralelBlock (head.py:132-133): every ResBlock1 starts from X
+            for (int p = 0; p < np; ++p) {       // ResBlock1.forward (head.py:101-108)
+                const float* xin = p == 0 ? X : Y;
+                {
+                    FfgConvArgs a{}; a.in32 = xin; a.epi = FFG_SILU16; a.out16 = U;
+                    HIPCHK(e, run(v->c1[i][b][p], L, a));
+                }
+                FfgConvArgs a{}; a.in16 = U; a.epi = FFG_RES; a.res32 = xin;
+                if (p + 1 < np) a.out32 = Y;
+                else { a.mean = Mn; a.mean_first = b == 0; a.mean_scale = b + 1 == nb ? 1.0f / (float)nb : 1.0f; }
+                HIPCHK(e, run(v->c2[i][b][p], L, a));
+            }
+        cur = Mn;
+    }
+    HIPCHK(e, launch_ffg_post(cur, v->post_w, P(e, "head.conv_post.bias"), B, L, head_width(c, c.n_upsamples), c.post_conv_kernel_size, pretanh, audio, s));
+    if (cap) capture(e, "ffgan.pre_tanh", pretanh, (int64_t)B * L, false, s);
+    return ST_OK;
+}
+
+}  // namespace sthost
+
+extern "C" {
+
+int st_create_ffgan(const st_ffgan_config* cfg, int device, st_engine** out) {
+    if (!cfg || !out) { g_create_error = "null argument"; return ST_ERR_INVALID; }
+    if (const char* why = ffgan_unsupported(*cfg)) { g_create_error = why; return ST_ERR_INVALID; }
+    st_engine* e = nullptr;
+    if (int rc = new_handle(KIND_FFGAN, device, &e)) return rc;
+    e->dt = cfg->operand_dtype == ST_OPERAND_BF16 ? DT_BF16 : DT_F16;
+    e->ffg = new FfganState();
+    e->ffg->cfg = *cfg;
+    for (int i = 0; i < cfg->n_upsamples; ++i) e->ffg->hop *= cfg->upsample_rates[i];
+    e->splitk_target = 0; e->attn_small_blocks = 0;      // decoder-only small-grid paths
+    ffgan_build_params(e, *cfg);
+    if (hipMalloc(&e->zeros, 256) != hipSuccess || hipMemset(e->zeros, 0, 256) != hipSuccess) {
+        ffgan_destroy(e); delete e;
+        g_create_error = "hipMalloc failed";
+        return ST_ERR_HIP;
+    }
+    *out = e;
+    return ST_OK;
+}
+
+int st_ffgan_forward(st_engine* e, const float* mel, float* audio, int B, int T, void* stream) {
+    int rc = check_handle(e, KIND_FFGAN); if (rc) return rc;
+    if ((rc = check_finalized(e))) return rc;
+    if (!mel || !audio) return e->fail(ST_ERR_INVALID, "null tensor pointer");
+    if ((rc = check_sizes(e, B, T))) return rc;
+    const st_ffgan_config& c = e->ffg->cfg;
+    const int64_t max_rows = ffgan_max_rows(c);
+    if (T > max_rows || T > kFfganMaxT) return e->fail(ST_ERR_INVALID, "T too large: one utterance exceeds the vocoder's row indexing");
+    const int64_t head_item = ffgan_level_elems(c) * T * 14;      // three fp32 level tensors and one 16-bit
+    const int chunk = (int)std::min<int64_t>({(int64_t)B, std::max<int64_t>(1, kFfganHeadBytes / head_item), max_rows / T, (int64_t)65535});
+    if (chunk < B && e->capture) return e->fail(ST_ERR_INVALID, "debug capture holds whole-batch tensors: this batch runs in chunks");
+    HIPCHK(e, hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t mel_item = (size_t)c.input_channels * T, audio_item = (size_t)T * e->ffg->hop;
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        rc = ffgan_forward_chunk(e, mel + b0 * mel_item, audio + b0 * audio_item, std::min(chunk, B - b0), T, s);
+        if (rc) return rc;
+    }
+    return ST_OK;
+}
+
+}  // extern "C"

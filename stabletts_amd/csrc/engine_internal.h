@@ -46,7 +46,7 @@ struct FloatArena {
 // What a handle is (st_engine::kind), in the order the creators were added.  kKinds names each for the message of an entry
 // point that is handed another kind's handle (check_handle).
 enum Kind { KIND_DECODER = 0, KIND_TEXT_ENCODER, KIND_VOCODER, KIND_STYLE_ENCODER, KIND_DURATION_PREDICTOR, KIND_MEL_EXTRACTOR, KIND_PERIOD_DISC, KIND_RESOLUTION_DISC,
-            KIND_COUNT };
+            KIND_FFGAN, KIND_COUNT };
 struct KindName { const char* what; const char* creator; };
 constexpr KindName kKinds[KIND_COUNT] = {
     {"CFM decoder", "st_create"},                                     // the estimator of the CFM decoder
@@ -57,6 +57,7 @@ constexpr KindName kKinds[KIND_COUNT] = {
     {"mel extractor", "st_create_mel_extractor"},                     // the feature front end (utils/audio.py)
     {"period discriminator", "st_create_period_discriminator"},       // DiscriminatorP of the Vocos training step
     {"resolution discriminator", "st_create_resolution_discriminator"},      // DiscriminatorR of the Vocos training step
+    {"FireflyGAN vocoder", "st_create_ffgan"},                        // FireflyGANBase (vocoders/ffgan)
 };
 // The style encoder and the duration predictor run fp32 kernels that read the loaded parameters in place: nothing to pack.
 constexpr bool reads_params_in_place(Kind k) { return k == KIND_STYLE_ENCODER || k == KIND_DURATION_PREDICTOR; }
@@ -68,6 +69,7 @@ struct DurState;       // engine_duration.cpp
 struct MelState;       // engine_audio.cpp
 struct PdState;        // engine_period_disc.cpp
 struct RdState;        // engine_resolution_disc.cpp
+struct FfganState;     // engine_ffgan.cpp
 
 // Training state of a style-encoder / duration-predictor handle: the activations of ONE grad-enabled forward
 // (serial, B, T; inputs copied in) and the backward's scratch, in two device buffers that grow on demand and are then reused.
@@ -202,6 +204,7 @@ struct st_engine {
     sthost::MelState* mel = nullptr;    // KIND_MEL_EXTRACTOR (engine_audio.cpp)
     sthost::PdState* pd = nullptr;      // KIND_PERIOD_DISC (engine_period_disc.cpp)
     sthost::RdState* rd = nullptr;      // KIND_RESOLUTION_DISC (engine_resolution_disc.cpp)
+    sthost::FfganState* ffg = nullptr;  // KIND_FFGAN (engine_ffgan.cpp)
 
     int fail(int code, const std::string& msg) { err = msg; return code; }
 };
@@ -260,6 +263,8 @@ int period_disc_weights(st_engine* e, hipStream_t s);      // w = v g / ||v|| of
 void period_disc_destroy(st_engine* e);
 int resolution_disc_weights(st_engine* e, hipStream_t s);  // the same for the 26 convs of a resolution discriminator
 void resolution_disc_destroy(st_engine* e);
+int ffgan_finalize(st_engine* e);                          // weight norm + packing of a FireflyGAN handle
+void ffgan_destroy(st_engine* e);
 
 // HIP-event bracket around the launches of one kernel class (st_profile_*)
 struct ProfScope {

@@ -1,0 +1,364 @@
+// FireflyGAN vocoder (vocoders/ffgan): the row kernels of the ConvNeXt encoder at a run-time width and the kernels of the
+// HiFi-GAN head -- one implicit-GEMM convolution family on the 16x16x32 MFMA (conv_pre, the 90 ResBlock convs, the five
+// transposed convs as 3-tap convs with a pixel-shuffle store that the time-major layout makes a plain store), the weight-norm
+// fold and fragment packing of st_finalize, and the fp32 SiLU -> conv_post -> tanh vector kernel.
+#include "common.h"
+#include "ffgan_launch.h"
+
+namespace st {
+
+// ---------------------------------------------------------------- LayerNorm(C, eps 1e-6, affine): one wave per frame, lane = 2 channels of every 128
+constexpr int kFfgNi = kFfgMaxDim / 128;
+
+__device__ __forceinline__ void ffg_ln_rows(float2 (&v)[kFfgNi], int ni, int C) {      // v -> (v - mean) * rstd
+    float sum = 0.0f;
+#pragma unroll
+    for (int i = 0; i < kFfgNi; ++i) if (i < ni) sum += v[i].x + v[i].y;
+    const float mean = wave_sum(sum) / (float)C;
+    float sq = 0.0f;
+#pragma unroll
+    for (int i = 0; i < kFfgNi; ++i) if (i < ni) { v[i].x -= mean; v[i].y -= mean; sq += v[i].x * v[i].x + v[i].y * v[i].y; }
+    const float rs = 1.0f / sqrtf(wave_sum(sq) / (float)C + 1e-6f);
+#pragma unroll
+    for (int i = 0; i < kFfgNi; ++i) if (i < ni) { v[i].x *= rs; v[i].y *= rs; }
+}
+
+template <class P>
+__device__ __forceinline__ void ffg_ln_store(const float2 (&v)[kFfgNi], int ni, int lane, const float* __restrict__ w, const float* __restrict__ b,
+                                             float* out32 /* row */, typename P::elem* out16 /* row */) {
+#pragma unroll
+    for (int i = 0; i < kFfgNi; ++i) {
+        if (i < ni) {
+            const int c = i * 128 + lane * 2;
+            const float2 lw = *(const float2*)(w + c), lb = *(const float2*)(b + c);
+            const float y0 = v[i].x * lw.x + lb.x, y1 = v[i].y * lw.y + lb.y;
+            if (out32) *(float2*)(out32 + c) = make_float2(y0, y1);
+            if (out16) { out16[c] = to16<P>(y0); out16[c + 1] = to16<P>(y1); }
+        }
+    }
+}
+
+template <class P>
+__global__ __launch_bounds__(256) void ffg_ln_kernel(const float* x, const float* __restrict__ w, const float* __restrict__ b, long long rows, int C,
+                                                     float* out32, typename P::elem* out16) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long row = (long long)blockIdx.x * 4 + wave;
+    if (row >= rows) return;
+    const int ni = C >> 7;
+    float2 v[kFfgNi];
+#pragma unroll
+    for (int i = 0; i < kFfgNi; ++i) v[i] = i < ni ? *(const float2*)(x + (size_t)row * C + i * 128 + lane * 2) : make_float2(0.f, 0.f);
+    ffg_ln_rows(v, ni, C);
+    ffg_ln_store<P>(v, ni, lane, w, b, out32 ? out32 + (size_t)row * C : nullptr, out16 ? out16 + (size_t)row * C : nullptr);
+}
+
+hipError_t launch_ffg_ln(int dtype, const float* x, const float* w, const float* b, int64_t rows, int C, float* out32, void* out16, hipStream_t s) {
+    if (C < 128 || C > kFfgMaxDim || (C & 127)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((rows + 3) / 4)), blk(256);
+    if (dtype == DT_BF16) hipLaunchKernelGGL((ffg_ln_kernel<OpBF16>), grid, blk, 0, s, x, w, b, (long long)rows, C, out32, (OpBF16::elem*)out16);
+    else                  hipLaunchKernelGGL((ffg_ln_kernel<OpF16>), grid, blk, 0, s, x, w, b, (long long)rows, C, out32, (OpF16::elem*)out16);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- ConvNeXt block prologue: depthwise k = 7 conv + LayerNorm (backbone.py:127-129)
+template <class P>
+__global__ __launch_bounds__(256) void ffg_dwconv_ln_kernel(const float* __restrict__ x, const float* __restrict__ dw, const float* __restrict__ dbias,
+                                                            const float* __restrict__ w, const float* __restrict__ b, int T, long long rows, int C,
+                                                            typename P::elem* __restrict__ h16) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long row = (long long)blockIdx.x * 4 + wave;
+    if (row >= rows) return;
+    const long long item = row / T;
+    const int t = (int)(row - item * T);
+    const float* xi = x + (size_t)item * T * C;
+    const int ni = C >> 7;
+    float2 v[kFfgNi];
+#pragma unroll
+    for (int i = 0; i < kFfgNi; ++i) {
+        v[i] = make_float2(0.f, 0.f);
+        if (i < ni) {
+            const int c = i * 128 + lane * 2;
+            float2 acc = *(const float2*)(dbias + c);
+#pragma unroll
+            for (int j = 0; j < 7; ++j) {
+                const int tt = t + j - 3;
+                if (tt >= 0 && tt < T) {      // zero padding of nn.Conv1d(padding=3); wave-uniform
+                    const float2 xv = *(const float2*)(xi + (size_t)tt * C + c);
+                    acc.x += dw[(size_t)c * 7 + j] * xv.x;
+                    acc.y += dw[(size_t)(c + 1) * 7 + j] * xv.y;
+                }
+            }
+            v[i] = acc;
+        }
+    }
+    ffg_ln_rows(v, ni, C);
+    ffg_ln_store<P>(v, ni, lane, w, b, nullptr, h16 + (size_t)row * C);
+}
+
+hipError_t launch_ffg_dwconv_ln(int dtype, const float* x, const float* dw, const float* dbias, const float* w, const float* b,
+                                int B, int T, int C, void* h16, hipStream_t s) {
+    if (C < 128 || C > kFfgMaxDim || (C & 127)) return hipErrorInvalidValue;
+    const long long rows = (long long)B * T;
+    const dim3 grid((unsigned)((rows + 3) / 4)), blk(256);
+    if (dtype == DT_BF16) hipLaunchKernelGGL((ffg_dwconv_ln_kernel<OpBF16>), grid, blk, 0, s, x, dw, dbias, w, b, T, rows, C, (OpBF16::elem*)h16);
+    else                  hipLaunchKernelGGL((ffg_dwconv_ln_kernel<OpF16>), grid, blk, 0, s, x, dw, dbias, w, b, T, rows, C, (OpF16::elem*)h16);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- head: implicit-GEMM convolution (ffgan_launch.h)
+// 4 waves; wave w owns frames 32 w .. 32 w + 31 of the tile (two 16-frame B operands) and all CW * 16 output channels of the block.
+// Fragment maps of the 16x16x32 MFMA (common.h): A = weights, lane l holds W[co = l & 15][k = 8 (l >> 4) .. + 8]; B = patch rows, lane l
+// holds a[frame = l & 15][the same k]; D: lane l, register r = out[co = 4 (l >> 4) + r][frame = l & 15] -- four consecutive output
+// channels of one frame, one 16-byte store.
+template <class P, bool IN16, int EPI, int CW>
+__global__ __launch_bounds__(256) void ffg_conv_kernel(FfgConvArgs a) {
+    extern __shared__ __align__(16) unsigned char patch[];      // [rows][kc * 2 + 16 bytes]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = lane >> 4, fl = lane & 15;
+    const int t0 = blockIdx.x * kFfgFrames, item = blockIdx.z, ct0 = blockIdx.y * CW;
+    const int cin = a.cin, cout = a.cout, taps = a.taps, dil = a.dil, L = a.L;
+    const int kc = cin < 128 ? cin : 128, lg = 31 - __builtin_clz(kc);
+    const int S = kc * 2 + 16, halo = (taps >> 1) * dil, rows = kFfgFrames + 2 * halo;
+    const int nchunks = cin / kc, ksc = (taps * kc + 31) >> 5;
+    const size_t in_base = (size_t)item * L * cin;
+
+    f32x4_t acc[2][CW];
+#pragma unroll
+    for (int fw = 0; fw < 2; ++fw)
+#pragma unroll
+        for (int cw = 0; cw < CW; ++cw) acc[fw][cw] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+    const uint4* wf = (const uint4*)a.wfrag + ((size_t)ct0 * nchunks * ksc) * 64 + lane;
+    const size_t wf_tile = (size_t)nchunks * ksc * 64;      // uint4 per 16-channel tile
+
+    for (int ch = 0; ch < nchunks; ++ch) {
+        if (ch) __syncthreads();
+        if (IN16) {
+            const int per = kc >> 3, n = rows * per;
+            const typename P::elem* src = (const typename P::elem*)a.in16 + in_base + (size_t)ch * kc;
+            for (int i = threadIdx.x; i < n; i += 256) {
+                const int r = i / per, c8 = i - r * per, t = t0 - halo + r;
+                uint4 v = make_uint4(0u, 0u, 0u, 0u);
+                if (t >= 0 && t < L) v = *(const uint4*)(src + (size_t)t * cin + c8 * 8);
+                *(uint4*)(patch + r * S + c8 * 16) = v;
+            }
+        } else {
+            const int per = kc >> 2, n = rows * per;
+            const float* src = a.in32 + in_base + (size_t)ch * kc;
+            for (int i = threadIdx.x; i < n; i += 256) {
+                const int r = i / per, c4 = i - r * per, t = t0 - halo + r;
+                uint2 v = make_uint2(0u, 0u);
+                if (t >= 0 && t < L) {
+                    const float4 x = *(const float4*)(src + (size_t)t * cin + c4 * 4);
+                    v = pack4<P>(silu_fast(x.x), silu_fast(x.y), silu_fast(x.z), silu_fast(x.w));
+                }
+                *(uint2*)(patch + r * S + c4 * 8) = v;
+            }
+        }
+        __syncthreads();
+        const uint4* wc = wf + (size_t)ch * ksc * 64;
+        for (int ks = 0; ks < ksc; ++ks) {
+            const int kk = ks * 32 + 8 * g;
+            int tap = kk >> lg;
+            const int ci = kk & (kc - 1);
+            tap = tap < taps ? tap : taps - 1;      // zero-weight padding of K: any finite row
+            uint4 wv[CW];
+#pragma unroll
+            for (int cw = 0; cw < CW; ++cw) wv[cw] = wc[(size_t)cw * wf_tile + (size_t)ks * 64];
+            const unsigned char* prow = patch + (wave * 32 + fl + tap * dil) * S + ci * 2;
+#pragma unroll
+            for (int fw = 0; fw < 2; ++fw) {
+                const uint4 bv = *(const uint4*)(prow + fw * 16 * S);
+#pragma unroll
+                for (int cw = 0; cw < CW; ++cw) acc[fw][cw] = P::mfma16(as_vec8<P>(wv[cw]), as_vec8<P>(bv), acc[fw][cw]);
+            }
+        }
+    }
+
+#pragma unroll
+    for (int fw = 0; fw < 2; ++fw) {
+        const int t = t0 + wave * 32 + fw * 16 + fl;
+        if (t >= L) continue;
+#pragma unroll
+        for (int cw = 0; cw < CW; ++cw) {
+            const int co = (ct0 + cw) * 16 + 4 * g;
+            const size_t o = ((size_t)item * L + t) * cout + co;
+            const float4 bb = *(const float4*)(a.bias + co);
+            float4 y = make_float4(acc[fw][cw][0] + bb.x, acc[fw][cw][1] + bb.y, acc[fw][cw][2] + bb.z, acc[fw][cw][3] + bb.w);
+            if (EPI == FFG_F32) {
+                *(float4*)(a.out32 + o) = y;
+            } else if (EPI == FFG_SILU16) {
+                *(uint2*)((typename P::elem*)a.out16 + o) = pack4<P>(silu_fast(y.x), silu_fast(y.y), silu_fast(y.z), silu_fast(y.w));
+            } else {
+                const float4 r = *(const float4*)(a.res32 + o);
+                y.x += r.x; y.y += r.y; y.z += r.z; y.w += r.w;
+                if (a.out32) *(float4*)(a.out32 + o) = y;
+                if (a.mean) {
+                    float4 m = y;
+                    if (!a.mean_first) { const float4 p = *(const float4*)(a.mean + o); m.x += p.x; m.y += p.y; m.z += p.z; m.w += p.w; }
+                    const float sc = a.mean_scale;
+                    *(float4*)(a.mean + o) = make_float4(m.x * sc, m.y * sc, m.z * sc, m.w * sc);
+                }
+            }
+        }
+    }
+}
+
+bool ffg_conv_supported(int cin, int cout, int taps, int dil) {
+    const bool cin_ok = cin == 16 || cin == 32 || cin == 64 || (cin >= 128 && cin % 128 == 0);
+    return cin_ok && cout >= 16 && cout % 16 == 0 && taps >= 1 && (taps & 1) && taps <= kFfgMaxTaps && dil >= 1 && (taps / 2) * dil <= kFfgMaxHalo;
+}
+
+template <class P, bool IN16, int EPI>
+static hipError_t ffg_conv_cw(const FfgConvArgs& a, hipStream_t s) {
+    const int tiles = a.cout / 16, cw = tiles % 4 == 0 ? 4 : tiles % 2 == 0 ? 2 : 1;
+    const int kc = ffg_kc(a.cin), rows = kFfgFrames + 2 * (a.taps / 2) * a.dil;
+    const size_t lds = (size_t)rows * (kc * 2 + 16);
+    const dim3 grid((unsigned)((a.L + kFfgFrames - 1) / kFfgFrames), (unsigned)(tiles / cw), (unsigned)a.n_items), blk(256);
+    if (cw == 4)      hipLaunchKernelGGL((ffg_conv_kernel<P, IN16, EPI, 4>), grid, blk, lds, s, a);
+    else if (cw == 2) hipLaunchKernelGGL((ffg_conv_kernel<P, IN16, EPI, 2>), grid, blk, lds, s, a);
+    else              hipLaunchKernelGGL((ffg_conv_kernel<P, IN16, EPI, 1>), grid, blk, lds, s, a);
+    return hipGetLastError();
+}
+
+template <class P>
+static hipError_t ffg_conv_dt(const FfgConvArgs& a, hipStream_t s) {
+    const bool in16 = a.in16 != nullptr;
+    if (a.epi == FFG_F32 && a.out32) return in16 ? ffg_conv_cw<P, true, FFG_F32>(a, s) : ffg_conv_cw<P, false, FFG_F32>(a, s);
+    if (a.epi == FFG_SILU16 && a.out16 && !in16) return ffg_conv_cw<P, false, FFG_SILU16>(a, s);
+    if (a.epi == FFG_RES && a.res32 && (a.out32 || a.mean) && in16) return ffg_conv_cw<P, true, FFG_RES>(a, s);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_ffg_conv(int dtype, const FfgConvArgs& a, hipStream_t s) {
+    if (!ffg_conv_supported(a.cin, a.cout, a.taps, a.dil) || (a.in32 != nullptr) == (a.in16 != nullptr) || !a.wfrag || !a.bias) return hipErrorInvalidValue;
+    if (a.L < 1 || a.n_items < 1 || a.n_items > 65535) return hipErrorInvalidValue;
+    return dtype == DT_BF16 ? ffg_conv_dt<OpBF16>(a, s) : ffg_conv_dt<OpF16>(a, s);
+}
+
+// ---------------------------------------------------------------- st_finalize: weight norm and packing
+__global__ __launch_bounds__(256) void ffg_wn_scale_kernel(const float* __restrict__ v, const float* __restrict__ g, int inner, float* __restrict__ scale) {
+    __shared__ double part[256];
+    const float* row = v + (size_t)blockIdx.x * inner;
+    double sq = 0.0;
+    for (int i = threadIdx.x; i < inner; i += 256) sq += (double)row[i] * (double)row[i];
+    part[threadIdx.x] = sq;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) part[threadIdx.x] += part[threadIdx.x + st];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) scale[blockIdx.x] = (float)((double)g[blockIdx.x] / sqrt(part[0]));
+}
+
+hipError_t launch_ffg_wn_scale(const float* v, const float* g, int rows, int inner, float* scale, hipStream_t s) {
+    hipLaunchKernelGGL(ffg_wn_scale_kernel, dim3(rows), dim3(256), 0, s, v, g, inner, scale);
+    return hipGetLastError();
+}
+
+// one thread per 16-bit element of the fragment stream: [tile = co / 16][chunk][k-step][lane][8]
+template <class P>
+__global__ __launch_bounds__(256) void ffg_pack_conv_kernel(const float* __restrict__ v, const float* __restrict__ scale, int cout, int cin, int taps,
+                                                            int u, long long n, typename P::elem* __restrict__ dst) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    const int kc = cin < 128 ? cin : 128, nchunks = cin / kc, ksc = (taps * kc + 31) >> 5;
+    const int e = (int)(idx & 7), lane = (int)((idx >> 3) & 63);
+    long long rest = idx >> 9;
+    const int ks = (int)(rest % ksc); rest /= ksc;
+    const int ch = (int)(rest % nchunks);
+    const int tile = (int)(rest / nchunks);
+    const int co = tile * 16 + (lane & 15), kk = ks * 32 + 8 * (lane >> 4) + e;
+    const int tap = kk / kc, ci = ch * kc + kk % kc;
+    float val = 0.0f;
+    if (tap < taps) {
+        if (u == 0) {
+            val = v[((size_t)co * cin + ci) * taps + tap] * (scale ? scale[co] : 1.0f);
+        } else {      // ConvTranspose1d (cin, Cout, 2u) as a 3-tap conv to u * Cout rows
+            const int Co = cout / u, r = co / Co, c = co - r * Co;
+            const int j = r + u / 2 - u * (tap - 1);
+            if (j >= 0 && j < 2 * u) val = v[((size_t)ci * Co + c) * (2 * u) + j] * (scale ? scale[ci] : 1.0f);
+        }
+    }
+    dst[idx] = to16<P>(val);
+}
+
+hipError_t launch_ffg_pack_conv(int dtype, const float* v, const float* scale, int cout, int cin, int taps, int transposed, void* wfrag, hipStream_t s) {
+    if (!ffg_conv_supported(cin, cout, taps, 1) || (transposed && (taps != 3 || cout % transposed != 0))) return hipErrorInvalidValue;
+    const long long n = (long long)(ffg_frag_bytes(cout, cin, taps) / 2);
+    const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
+    if (dtype == DT_BF16) hipLaunchKernelGGL((ffg_pack_conv_kernel<OpBF16>), grid, blk, 0, s, v, scale, cout, cin, taps, transposed, n, (OpBF16::elem*)wfrag);
+    else                  hipLaunchKernelGGL((ffg_pack_conv_kernel<OpF16>), grid, blk, 0, s, v, scale, cout, cin, taps, transposed, n, (OpF16::elem*)wfrag);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void ffg_pack_post_kernel(const float* __restrict__ v, const float* __restrict__ scale, int cin, int taps, float* __restrict__ dst) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= cin * taps) return;
+    const int j = idx / cin, ci = idx - j * cin;
+    dst[idx] = v[(size_t)ci * taps + j] * scale[0];
+}
+
+hipError_t launch_ffg_pack_post(const float* v, const float* scale, int cin, int taps, float* dst, hipStream_t s) {
+    hipLaunchKernelGGL(ffg_pack_post_kernel, dim3((cin * taps + 255) / 256), dim3(256), 0, s, v, scale, cin, taps, dst);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void ffg_tile_bias_kernel(const float* __restrict__ bias, int cout, int n, float* __restrict__ dst) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx < n) dst[idx] = bias[idx % cout];
+}
+
+hipError_t launch_ffg_tile_bias(const float* bias, int cout, int u, float* dst, hipStream_t s) {
+    hipLaunchKernelGGL(ffg_tile_bias_kernel, dim3((cout * u + 255) / 256), dim3(256), 0, s, bias, cout, cout * u, dst);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- SiLU -> conv_post (C -> 1) -> tanh, fp32 (head.py:245-247)
+// One block = 256 samples of one item; 16 channels at a time: silu(x) of the 256 + taps - 1 rows in LDS (row pitch 20 floats: the
+// 16-byte reads of 16 consecutive rows fall into 16 different bank slots), one thread per sample.
+constexpr int kFfgPostPitch = 20;
+__global__ __launch_bounds__(256) void ffg_post_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                       int L, int C, int taps, float* __restrict__ pre, float* __restrict__ audio) {
+    __shared__ __align__(16) float tile[(256 + kFfgMaxTaps - 1) * kFfgPostPitch];
+    __shared__ __align__(16) float wl[kFfgMaxTaps * 16];
+    const int t0 = blockIdx.x * 256, item = blockIdx.y, halo = taps >> 1, rows = 256 + taps - 1;
+    const float* xi = x + (size_t)item * L * C;
+    float acc = 0.0f;
+    for (int c0 = 0; c0 < C; c0 += 16) {
+        if (c0) __syncthreads();
+        for (int i = threadIdx.x; i < rows * 4; i += 256) {
+            const int r = i >> 2, q = i & 3, t = t0 - halo + r;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (t >= 0 && t < L) {
+                const float4 xv = *(const float4*)(xi + (size_t)t * C + c0 + q * 4);
+                v = make_float4(silu_f(xv.x), silu_f(xv.y), silu_f(xv.z), silu_f(xv.w));
+            }
+            *(float4*)(tile + r * kFfgPostPitch + q * 4) = v;
+        }
+        for (int i = threadIdx.x; i < taps * 16; i += 256) wl[i] = w[(size_t)(i >> 4) * C + c0 + (i & 15)];
+        __syncthreads();
+        for (int j = 0; j < taps; ++j) {
+            const float* row = tile + (threadIdx.x + j) * kFfgPostPitch;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float4 xv = *(const float4*)(row + q * 4), wv = *(const float4*)(wl + j * 16 + q * 4);
+                acc += xv.x * wv.x + xv.y * wv.y + xv.z * wv.z + xv.w * wv.w;
+            }
+        }
+    }
+    const int t = t0 + threadIdx.x;
+    if (t < L) {
+        const float y = acc + bias[0];
+        if (pre) pre[(size_t)item * L + t] = y;
+        audio[(size_t)item * L + t] = tanhf(y);
+    }
+}
+
+hipError_t launch_ffg_post(const float* x, const float* w, const float* bias, int n_items, int L, int C, int taps, float* pre, float* audio, hipStream_t s) {
+    if (C < 16 || (C & 15) || taps < 1 || !(taps & 1) || taps > kFfgMaxTaps || n_items < 1 || n_items > 65535 || L < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ffg_post_kernel, dim3((unsigned)((L + 255) / 256), (unsigned)n_items), dim3(256), 0, s, x, w, bias, L, C, taps, pre, audio);
+    return hipGetLastError();
+}
+
+}  // namespace st
