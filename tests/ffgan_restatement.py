@@ -37,7 +37,15 @@ def small_config(rates=(4, 2), kernels=(8, 4), rk=(3, 5), rd=((1, 2), (1, 3)), c
 SEED, MEL_SEED = 20240, 100
 CASES = ((1, 24), (2, 13), (2, 1), (1, 2))
 
-WN0, WN1 = "parametrizations.weight.original0", "parametrizations.weight.original1"
+# tests/golden/ffgan_config_outputs.npz (the same tool): the reference's own ConvNeXtEncoder and HiFiGANGenerator at two further
+# configurations, name -> (config, B, T, mel seed) with make_state_dict(config, SEED).  Its ResBlock1 always has three dilations.
+REF_CASES = {
+    "ref_a": (small_config(rates=(6, 10), kernels=(12, 20), rk=(5, 13), rd=((1, 2, 4), (1, 3, 4)), mels=192, dims=(768, 640)), 2, 11, 41),
+    "ref_b": (small_config(rates=(16, 2), kernels=(32, 4), rk=(1, 9, 3), rd=((1, 1, 1), (1, 2, 6), (2, 9, 25)), dims=(1024,), depths=(2,),
+                           pre=1, post=13), 2, 30, 41),      # head 64 -> 32 -> 16 channels (the last level needs 16)
+}
+
+WN0, WN1 ="parametrizations.weight.original0", "parametrizations.weight.original1"
 
 
 def param_shapes(cfg):

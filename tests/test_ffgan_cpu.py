@@ -43,6 +43,27 @@ def test_restatement_equals_the_reference_module(gold, seeded, ci):
         assert R.rel_max(out[name], ref) <= 1e-10, name
 
 
+@pytest.mark.parametrize("name", list(R.REF_CASES))
+def test_restatement_equals_the_reference_modules_at_other_configurations(name):
+    """tests/golden/ffgan_config_outputs.npz: the reference's own encoder and head at two non-default configurations."""
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "ffgan_config_outputs.npz"))
+    cfg, B, T, mel_seed = R.REF_CASES[name]
+    sd = R.make_state_dict(cfg, R.SEED)
+    mel = R.make_mel(B, T, cfg["backbone"]["input_channels"], mel_seed)
+    out = R.forward(sd, cfg, mel)
+    for tensor in ("audio", "encoder", "pre_tanh"):
+        ref = gold[f"{name}/{tensor}"]
+        assert out[tensor].shape == ref.shape and ref.dtype == np.float64
+        assert R.rel_max(out[tensor], ref) <= 1e-10, tensor
+    assert out["audio"].shape == (B, T * cfg["head"]["hop_length"])
+    for dt in ("f16", "bf16"):      # the recorded e_emul of the GPU gate is the restatement's
+        em = R.forward(sd, cfg, mel, dt, dt)
+        got = [R.rel_max(em[n], out[n]) for n in ("audio", "encoder", "pre_tanh")]
+        want = gold[f"{name}/emul_{dt}"][0]
+        assert np.allclose(got, want, rtol=1e-6, atol=0), (dt, got, want)
+        assert all(1e-5 < g < 2e-2 for g in got)
+
+
 def test_emulation_switches_round_and_the_fixture_records_them(gold, seeded):
     """The operand-rounded restatement differs from float64 by what the fixture recorded (case 1x2: the cheapest)."""
     ci, (B, T) = 3, R.CASES[3]
@@ -56,7 +77,7 @@ def test_emulation_switches_round_and_the_fixture_records_them(gold, seeded):
         assert all(1e-5 < g < 2e-2 for g in got)
 
 
-@pytest.mark.parametrize("u,k", [(8, 16), (2, 4), (4, 8)])
+@pytest.mark.parametrize("u,k", [(8, 16), (2, 4), (4, 8), (6, 12), (10, 20), (12, 24), (14, 28), (16, 32)])
 def test_polyphase_map_equals_conv_transpose(u, k):
     gen = torch.Generator().manual_seed(u)
     x = torch.randn(2, 6, 9, generator=gen, dtype=torch.float64)
@@ -204,7 +225,10 @@ def test_cabi_rejects_unsupported_configurations_without_a_device(lib, case):
 
 def test_cabi_accepts_supported_configurations(lib):
     """A supported configuration passes the checks: without a device the next failure is the device's (ST_ERR_HIP)."""
-    for cfg in (R.DEFAULT, R.small_config(), R.small_config(rates=(2, 2), kernels=(4, 4), rk=(11, 3), rd=((5, 1), (1, 2)), pre=3, post=5)):
+    from tests.ffgan_checks import CONFIGS      # every configuration of the GPU tests (test_gpu_ffgan.py, test_gpu_ffgan_configs.py)
+    assert set(R.REF_CASES) <= set(CONFIGS) and len(CONFIGS) == 15
+    for cfg in (R.DEFAULT, R.small_config(), R.small_config(rates=(2, 2), kernels=(4, 4), rk=(11, 3), rd=((5, 1), (1, 2)), pre=3, post=5),
+                *CONFIGS.values()):
         rc, msg = _create(lib, cfg)
         if torch.cuda.is_available():
             assert rc == 0, msg

@@ -14,11 +14,10 @@ import pytest
 import torch
 
 from tests import ffgan_restatement as R
+from tests.ffgan_checks import against_restatement, build, gate, run_captured, small_model
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = R.small_config()                  # rates (4, 2), kernels (8, 4), resblock kernels (3, 5), dilations ((1, 2), (1, 3)), pre / post 7
-DEEP16 = R.small_config(rates=(2, 2), kernels=(4, 4), rk=(11, 3), rd=((5, 1), (1, 2)), c0=64, pre=3, post=5)      # 64 -> 32 -> 16 channels, k = 11, d = 5
 
 
 @pytest.fixture(scope="module")
@@ -26,55 +25,9 @@ def gold():
     return dict(np.load(os.path.join(ROOT, "tests", "golden", "ffgan_outputs.npz")))
 
 
-def build(cfg, dt, seed=R.SEED):
-    from stabletts_amd.ffgan import FireflyGANBase
-    m = FireflyGANBase(operand_dtype=dt, config=cfg)
-    sd = R.make_state_dict(cfg, seed)
-    m.load_state_dict(sd, strict=True)
-    return m.cuda().eval(), sd
-
-
 @pytest.fixture(scope="module")
 def default_models():
     return {dt: build(R.DEFAULT, dt)[0] for dt in ("f16", "bf16")}
-
-
-_small = {}
-
-
-def small_model(name, dt):
-    if (name, dt) not in _small:
-        _small[(name, dt)] = build({"small": SMALL, "deep16": DEEP16}[name], dt)
-    return _small[(name, dt)]
-
-
-def run_captured(m, mel):
-    """-> audio (B, T * hop), encoder (B, D, T), pre_tanh (B, T * hop) as float64 CPU tensors, through debug_capture."""
-    B = mel.shape[0]
-    eng = m.engine()
-    eng.debug_capture(True)
-    try:
-        audio = m(mel.cuda())
-        torch.cuda.synchronize()
-        D = m.config["backbone"]["dims"][-1]
-        enc = torch.from_numpy(eng.debug_fetch("ffgan.encoder").astype(np.float64)).view(B, -1, D).permute(0, 2, 1)
-        pre = torch.from_numpy(eng.debug_fetch("ffgan.pre_tanh").astype(np.float64)).view(B, -1)
-    finally:
-        eng.debug_capture(False)
-    return {"audio": audio.double().cpu(), "encoder": enc, "pre_tanh": pre}
-
-
-def gate(tag, got, ref, e_emul):
-    bad = []
-    for name in ("audio", "encoder", "pre_tanh"):
-        assert tuple(got[name].shape) == tuple(ref[name].shape), (name, got[name].shape, ref[name].shape)
-        assert bool(torch.isfinite(got[name]).all()), name
-        e_native = R.rel_max(got[name], ref[name])
-        print(f"ffgan_parity {tag:<28} {name:<9} e_native {e_native:.3e}   e_emul {e_emul[name]:.3e}")
-        assert e_emul[name] < 2e-2, (name, e_emul[name])
-        if not e_native <= 2 * e_emul[name]:
-            bad.append((name, e_native, e_emul[name]))
-    assert not bad, bad
 
 
 @pytest.mark.parametrize("dt", ["f16", "bf16"])
@@ -87,16 +40,6 @@ def test_default_config_matches_the_reference_fixture(default_models, gold, ci, 
     ref = {n: torch.from_numpy(gold[f"{B}x{T}/{n}"]) for n in ("audio", "encoder", "pre_tanh")}
     em = gold[f"{B}x{T}/emul_{dt}"][0]
     gate(f"default {B}x{T} {dt}", got, ref, {"audio": em[0], "encoder": em[1], "pre_tanh": em[2]})
-
-
-def against_restatement(name, dt, B, T, mel_seed):
-    m, sd = small_model(name, dt)
-    cfg = m.config
-    mel = R.make_mel(B, T, cfg["backbone"]["input_channels"], mel_seed)
-    ref = R.forward(sd, cfg, mel)
-    em = R.forward(sd, cfg, mel, dt, dt)
-    got = run_captured(m, mel)
-    gate(f"{name} {B}x{T} {dt}", got, ref, {n: R.rel_max(em[n], ref[n]) for n in ("audio", "encoder", "pre_tanh")})
 
 
 @pytest.mark.parametrize("dt", ["f16", "bf16"])
