@@ -342,13 +342,31 @@ typedef struct st_ffgan_config {
 int st_create_ffgan(const st_ffgan_config* cfg, int device, st_engine** out);
 
 /* Replaces FireflyGANBase.forward(x) (model.py:52-57): mel (B, input_channels, T) fp32 -> audio (B, T * hop) fp32, device pointers,
- * hop = the product of the upsample rates.  No mask, as in the reference: every utterance is vocoded at the padded length T, and no
- * kernel reads a neighbouring utterance.  The ParralelBlock mean is accumulated in block order on one stream, without atomics: two
+ * hop = the product of the upsample rates.  No mask, as in the reference: every utterance is vocoded at the padded length T (a batch of
+ * different lengths: st_ffgan_forward_ragged), and no kernel reads a neighbouring utterance.  The ParralelBlock mean is accumulated in block order on one stream, without atomics: two
  * calls agree bit for bit.  Every tensor offset in the head kernels is 64-bit; large batches run in chunks of whole utterances so that
  * the head's workspace (three fp32 tensors and one 16-bit tensor of the widest level, 14 bytes per channel-sample) stays below
  * 1 GiB (one utterance if that alone is more) and the encoder's GEMM rows within 32-bit offsets.  T up to 2^20; a T whose encoder rows
  * exceed the row bound on its own, and a batch that needs more than one chunk while debug capture is on, are ST_ERR_INVALID. */
 int st_ffgan_forward(st_engine* e, const float* mel, float* audio, int B, int T, void* stream);
+
+/* st_ffgan_forward on a ragged batch: utterance b has lengths[b] frames, and its audio equals that utterance vocoded alone (the
+ * padded frames of st_ffgan_forward are not zero activations: they reach back through the encoder's k = 7 convolutions and the
+ * head's dilated ones into the end of every shorter utterance).
+ *   mel     : (B, input_channels, T) fp32, device; frames from lengths[b] on are never read
+ *   lengths : B entries in HOST memory, each in [1, T]  (e.g. length_regulate's y_lengths)
+ *   audio   : (B, T * hop) fp32, device; every sample is written, those from lengths[b] * hop on as 0.0
+ * Every activation between the two is packed: sum(lengths) rows in the encoder and sum(lengths) * up rows at a head level, not
+ * B * T.  A head tile runs the arithmetic of st_ffgan_forward on its utterance alone, so with every length equal to T the audio is
+ * bitwise st_ffgan_forward's, and an utterance's audio does not depend on its neighbours' mel, lengths or order as long as the
+ * encoder's GEMMs select the same tile for the row count.  Everything is validated before the device is touched (a null pointer or
+ * a length outside [1, T]: ST_ERR_INVALID naming the index).  Chunks are whole utterances bounded by their PACKED rows -- the 1 GiB
+ * head workspace at 14 bytes per channel-sample of the widest level (one utterance if that alone is more), the encoder's 32-bit row
+ * bound -- and by 65535 utterances; an utterance that exceeds the row bound on its own is rejected, as is a multi-chunk batch while
+ * debug capture is on (a single-chunk call captures packed tensors: "ffgan.encoder" (sum(lengths), D), "ffgan.pre_tanh"
+ * (sum(lengths) * hop)).  Enqueued on `stream`; the length table travels through one of four pinned slots guarded by events, as
+ * for st_vocos_forward_ragged, so back-to-back calls do not wait on each other. */
+int st_ffgan_forward_ragged(st_engine* e, const float* mel, const int64_t* lengths, float* audio, int B, int T, void* stream);
 
 /* ---- period discriminator of the Vocos training step (vocoders/vocos/models/discriminator.py:32-75, train.py:98-128) ---- */
 /* One handle serves one DiscriminatorP(period, in_channels = 1, kernel_size = 5, stride = 3, lrelu_slope); the five of a

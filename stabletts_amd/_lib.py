@@ -173,6 +173,7 @@ PROTOTYPES = {
     "st_vocos_train_backward": (i32, [vp, vp, vp, vp, i32, i32, vp]),
     "st_create_ffgan": (i32, [P(StFfganConfig), i32, P(vp)]),
     "st_ffgan_forward": (i32, [vp, vp, vp, i32, i32, vp]),
+    "st_ffgan_forward_ragged": (i32, [vp, vp, P(i64), vp, i32, i32, vp]),
     "st_create_period_discriminator": (i32, [P(StPeriodDiscConfig), i32, P(vp)]),
     "st_period_disc_fmap_shape": (i32, [vp, i32, i32, P(i64), P(i64)]),
     "st_period_disc_forward": (i32, [vp, vp, P(vp), i32, i32, vp]),
@@ -376,6 +377,14 @@ class Engine:
         """mel (B, input_channels, T) -> audio (B, T * hop) (FireflyGAN vocoder handles)."""
         B, _, T = mel.shape
         self._check(self.lib.st_ffgan_forward(self.handle, mel.data_ptr(), audio.data_ptr(), B, T, ctypes.c_void_p(stream)))
+
+    def ffgan_forward_ragged(self, mel, lengths, audio, stream):
+        """st_ffgan_forward with utterance b at its own length lengths[b] (a sequence of B ints, host side)."""
+        B, _, T = mel.shape
+        if len(lengths) != B:
+            raise NativeError(ST_ERR_INVALID, f"lengths has {len(lengths)} entries, the batch has B = {B} utterances")
+        arr = (ctypes.c_int64 * B)(*lengths)
+        self._check(self.lib.st_ffgan_forward_ragged(self.handle, mel.data_ptr(), arr, audio.data_ptr(), B, T, ctypes.c_void_p(stream)))
 
     def vocos_forward_ragged(self, mel, lengths, audio, stream):
         """st_vocos_forward with utterance b at its own length lengths[b] (a sequence of B ints, host side)."""

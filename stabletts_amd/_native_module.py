@@ -55,6 +55,21 @@ def hip_device_index(device, what):
     return device.index if device.index is not None else torch.cuda.current_device()
 
 
+def host_lengths(lengths, x):
+    """The ``lengths`` of a ragged vocoder call (``forward_ragged`` of Vocos and FireflyGANBase) as a list of Python ints: a
+    sequence, or a one-dimensional integer tensor on the CPU or on the device of the mel ``x`` (a device tensor costs one
+    ``.tolist()`` sync).  Their count and range are checked by the native entry point."""
+    if isinstance(lengths, torch.Tensor):
+        if lengths.dtype.is_floating_point or lengths.dtype in (torch.bool, torch.complex64, torch.complex128):
+            raise ValueError(f"lengths must be an integer tensor, got {lengths.dtype}")
+        if lengths.device.type != "cpu" and lengths.device != x.device:
+            raise ValueError(f"lengths is on {lengths.device}, the mel is on {x.device}")
+        if lengths.dim() != 1:
+            raise ValueError("lengths must be one-dimensional (B,)")
+        return lengths.tolist()
+    return [int(n) for n in lengths]
+
+
 class NativeModule(nn.Module):
     """A parameter container whose forward runs on a handle of libstabletts_hip.so.  A subclass says how the handle is
     created (``_create_engine``), sets ``_what`` and ``operand_dtype``, and picks one of the two sync policies:

@@ -1,10 +1,11 @@
-// FireflyGAN vocoder behind the C ABI (st_create_ffgan / st_ffgan_forward): parameter table, weight-norm fold and packing, and the
+// FireflyGAN vocoder behind the C ABI (st_create_ffgan / st_ffgan_forward / st_ffgan_forward_ragged): parameter table, weight-norm fold and packing, and the
 // launch sequence.  Reference: vocoders/ffgan/model.py:7-29,44-57, backbone.py:78-214, head.py:25-133,136-249 (use_template=False).
 // The ConvNeXt encoder runs like the Vocos backbone (engine_vocos.cpp): its GEMMs on the implicit-GEMM kernels of the decoder over
 // the flattened rows of the batch, the row kernels at a run-time width.  The HiFi-GAN head runs on the convolution family of
 // ffgan_kernels.hip, every level a time-major [item][L][C] tensor.
 #include "engine_internal.h"
 #include "ffgan_launch.h"
+#include "utt_slots.h"
 #include "vocos_launch.h"
 
 #include <algorithm>
@@ -32,6 +33,7 @@ struct FfganState {
     std::vector<FfConv> ups;
     std::vector<std::vector<std::vector<FfConv>>> c1, c2;      // [level][resblock][pair]
     float* post_w = nullptr;                          // [taps][C] fp32
+    UttSlots slots;                                   // ragged calls: the utterance tables (utt_slots.h)
 };
 
 static const std::string kWn0 = "parametrizations.weight.original0", kWn1 = "parametrizations.weight.original1";
@@ -193,6 +195,7 @@ int ffgan_finalize(st_engine* e) {
 
 void ffgan_destroy(st_engine* e) {
     if (!e->ffg) return;
+    e->ffg->slots.destroy();
     delete e->ffg; e->ffg = nullptr;
 }
 
@@ -211,11 +214,14 @@ static int64_t ffgan_max_rows(const st_ffgan_config& c) {
 constexpr int64_t kFfganHeadBytes = (int64_t)1 << 30;      // bound of the head's level tensors per chunk (stabletts_hip.h: st_ffgan_forward)
 constexpr int kFfganMaxT = 1 << 20;
 
-static int ffgan_forward_chunk(st_engine* e, const float* mel, float* audio, int B, int T, hipStream_t s) {
+// One chunk of whole utterances: the encoder's GEMMs and LayerNorms run over its R flattened rows, R = B * T, or the packed rows of a
+// ragged chunk (rg: mel and audio stay padded to T; the im2col, the depthwise conv, the head's convolutions and the post kernel know
+// utterances and take their ragged form -- every level tensor of the head then holds R * up packed rows).
+static int ffgan_forward_chunk(st_engine* e, const float* mel, float* audio, int B, int T, const RaggedChunk* rg, hipStream_t s) {
     FfganState* v = e->ffg;
     const st_ffgan_config& c = v->cfg;
     const int M = c.input_channels, Dmax = ffgan_max_dim(c), D = c.dims[c.n_stages - 1], C0 = c.upsample_initial_channel;
-    const int64_t R = (int64_t)B * T, lvl = ffgan_level_elems(c) * R;
+    const int64_t R = rg ? rg->rows : (int64_t)B * T, lvl = ffgan_level_elems(c) * R;
     const bool cap = e->capture;
 
     size_t off = 0;
@@ -224,7 +230,9 @@ static int ffgan_forward_chunk(st_engine* e, const float* mel, float* audio, int
     const size_t o_u16 = want((size_t)R * 4 * Dmax * 2), o_enc32 = want((size_t)R * D * 4), o_enc16 = want((size_t)R * D * 2), o_pre = want((size_t)R * C0 * 4);
     const size_t o_X = want((size_t)lvl * 4), o_Y = want((size_t)lvl * 4), o_Mn = want((size_t)lvl * 4), o_U = want((size_t)lvl * 2);
     const size_t o_pt = cap ? want((size_t)R * v->hop * 4) : 0;
+    const size_t o_tiles = rg ? want((size_t)rg->n_tiles * sizeof(VocSeg)) : 0, o_frames = rg ? want((size_t)rg->n_groups * sizeof(VocSeg)) : 0;
     int rc = ensure_ws(e, off); if (rc) return rc;
+    VocSeg* tiles = (VocSeg*)(e->ws + o_tiles); VocSeg* frames = (VocSeg*)(e->ws + o_frames);      // im2col tiles; one entry per packed row
     void* a16 = e->ws + o_a16; float* x = (float*)(e->ws + o_xa); float* xn = (float*)(e->ws + o_xb); void* h16 = e->ws + o_h16; void* u16 = e->ws + o_u16;
     float* enc32 = (float*)(e->ws + o_enc32); void* enc16 = e->ws + o_enc16; float* pre32 = (float*)(e->ws + o_pre);
     float* X = (float*)(e->ws + o_X); float* Y = (float*)(e->ws + o_Y); float* Mn = (float*)(e->ws + o_Mn); void* U = e->ws + o_U;
@@ -240,7 +248,12 @@ static int ffgan_forward_chunk(st_engine* e, const float* mel, float* audio, int
     for (int i = 0; i < c.n_stages; ++i) {
         const int C = c.dims[i];
         if (i == 0) {       // stem: k = 7 conv as an im2col GEMM, then the per-frame LayerNorm
-            HIPCHK(e, launch_voc_im2col7(e->dt, mel, B, M, T, a16, s));
+            if (rg) {
+                HIPCHK(e, launch_voc_segments(rg->utt, B, 1, tiles, frames, s));
+                HIPCHK(e, launch_voc_im2col7_ragged(e->dt, mel, tiles, rg->n_tiles, M, T, a16, s));
+            } else {
+                HIPCHK(e, launch_voc_im2col7(e->dt, mel, B, M, T, a16, s));
+            }
             ConvGemmArgs a = args(v->stem); a.a0 = a16; a.c0 = 7 * M; a.out32 = x;
             HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
             HIPCHK(e, launch_ffg_ln(e->dt, x, P(e, ds(0, 1) + "weight"), P(e, ds(0, 1) + "bias"), R, C, x, nullptr, s));
@@ -253,8 +266,9 @@ static int ffgan_forward_chunk(st_engine* e, const float* mel, float* audio, int
         }
         for (int j = 0; j < c.depths[i]; ++j) {      // ConvNeXtBlock.forward (backbone.py:124-143); DropPath is the identity in eval
             const std::string p = blk(i, j);
-            HIPCHK(e, launch_ffg_dwconv_ln(e->dt, x, P(e, p + "dwconv.weight"), P(e, p + "dwconv.bias"), P(e, p + "norm.weight"), P(e, p + "norm.bias"),
-                                           B, T, C, h16, s));
+            const float *dw = P(e, p + "dwconv.weight"), *db = P(e, p + "dwconv.bias"), *nw = P(e, p + "norm.weight"), *nb = P(e, p + "norm.bias");
+            if (rg) HIPCHK(e, launch_ffg_dwconv_ln_ragged(e->dt, x, dw, db, nw, nb, frames, R, C, h16, s));
+            else    HIPCHK(e, launch_ffg_dwconv_ln(e->dt, x, dw, db, nw, nb, B, T, C, h16, s));
             {
                 ConvGemmArgs a = args(v->pw1[i][j]); a.a0 = h16; a.c0 = C; a.out16 = u16;
                 HIPCHK(e, gemm(e, 1, EPI_GELU16, a, s));
@@ -269,16 +283,19 @@ static int ffgan_forward_chunk(st_engine* e, const float* mel, float* audio, int
     if (cap) capture(e, "ffgan.encoder", enc32, R * D, false, s);
 
     // ---- HiFiGANGenerator.forward (head.py:226-249)
+    // L: the level length of the chunk's longest utterance (ragged: it sizes the grid; up = L / its frames scales the utterance table)
+    const int Tmax = rg ? rg->t_max : T;
     auto run = [&](const FfConv& cv, int L, FfgConvArgs a) -> hipError_t {
         a.wfrag = cv.wfrag; a.bias = cv.bias; a.cin = cv.cin; a.cout = cv.cout; a.taps = cv.taps; a.dil = cv.dil; a.L = L; a.n_items = B;
+        if (rg) { a.utt = rg->utt; a.up = L / Tmax; }
         return launch_ffg_conv(e->dt, a, s);
     };
     {
         FfgConvArgs a{}; a.in16 = enc16; a.epi = FFG_F32; a.out32 = pre32;
-        HIPCHK(e, run(v->pre, T, a));
+        HIPCHK(e, run(v->pre, Tmax, a));
     }
     const float* cur = pre32;
-    int L = T;
+    int L = Tmax;
     const int nb = c.n_resblocks, np = c.n_dilations;
     for (int i = 0; i < c.n_upsamples; ++i) {
         {       // silu + ConvTranspose1d: [L][u * C] rows = the upsampled [L * u][C]
@@ -300,8 +317,10 @@ static int ffgan_forward_chunk(st_engine* e, const float* mel, float* audio, int
             }
         cur = Mn;
     }
-    HIPCHK(e, launch_ffg_post(cur, v->post_w, P(e, "head.conv_post.bias"), B, L, head_width(c, c.n_upsamples), c.post_conv_kernel_size, pretanh, audio, s));
-    if (cap) capture(e, "ffgan.pre_tanh", pretanh, (int64_t)B * L, false, s);
+    const int Cl = head_width(c, c.n_upsamples), kpost = c.post_conv_kernel_size;
+    if (rg) HIPCHK(e, launch_ffg_post_ragged(cur, v->post_w, P(e, "head.conv_post.bias"), rg->utt, v->hop, B, T * v->hop, Cl, kpost, pretanh, audio, s));
+    else    HIPCHK(e, launch_ffg_post(cur, v->post_w, P(e, "head.conv_post.bias"), B, L, Cl, kpost, pretanh, audio, s));
+    if (cap) capture(e, "ffgan.pre_tanh", pretanh, R * v->hop, false, s);
     return ST_OK;
 }
 
@@ -344,9 +363,54 @@ int st_ffgan_forward(st_engine* e, const float* mel, float* audio, int B, int T,
     hipStream_t s = (hipStream_t)stream;
     const size_t mel_item = (size_t)c.input_channels * T, audio_item = (size_t)T * e->ffg->hop;
     for (int b0 = 0; b0 < B; b0 += chunk) {
-        rc = ffgan_forward_chunk(e, mel + b0 * mel_item, audio + b0 * audio_item, std::min(chunk, B - b0), T, s);
+        rc = ffgan_forward_chunk(e, mel + b0 * mel_item, audio + b0 * audio_item, std::min(chunk, B - b0), T, nullptr, s);
         if (rc) return rc;
     }
+    return ST_OK;
+}
+
+int st_ffgan_forward_ragged(st_engine* e, const float* mel, const int64_t* lengths, float* audio, int B, int T, void* stream) {
+    int rc = check_handle(e, KIND_FFGAN); if (rc) return rc;
+    if ((rc = check_finalized(e))) return rc;
+    if (!mel || !audio) return e->fail(ST_ERR_INVALID, "null tensor pointer");
+    if (!lengths) return e->fail(ST_ERR_INVALID, "null lengths");
+    if ((rc = check_sizes(e, B, T))) return rc;
+    FfganState* v = e->ffg;
+    const st_ffgan_config& c = v->cfg;
+    const int64_t max_rows = ffgan_max_rows(c);
+    // validate everything and plan the chunks before touching the device: whole utterances, as many as keep the head's level tensors
+    // of the packed rows within kFfganHeadBytes (one utterance always runs), the packed rows within max_rows and the grid within 65535 items
+    if (T > kFfganMaxT) return e->fail(ST_ERR_INVALID, "T too large: one utterance exceeds the vocoder's row indexing");
+    for (int b = 0; b < B; ++b)
+        if (lengths[b] < 1 || lengths[b] > T)
+            return e->fail(ST_ERR_INVALID, "lengths[" + std::to_string(b) + "] = " + std::to_string(lengths[b]) + " must be in [1, T = " + std::to_string(T) + "]");
+    for (int b = 0; b < B; ++b)
+        if (lengths[b] > max_rows)
+            return e->fail(ST_ERR_INVALID, "lengths[" + std::to_string(b) + "] too large: one utterance exceeds the vocoder's row indexing");
+    const int64_t head_rows = std::max<int64_t>(1, kFfganHeadBytes / (ffgan_level_elems(c) * 14));      // three fp32 level tensors and one 16-bit
+    std::vector<int> starts;          // first utterance of every chunk, then B
+    int64_t rows = 0;
+    for (int b = 0; b < B; ++b) {
+        if (b == 0 || rows + lengths[b] > head_rows || rows + lengths[b] > max_rows || b - starts.back() >= 65535) { starts.push_back(b); rows = 0; }
+        rows += lengths[b];
+    }
+    starts.push_back(B);
+    const int n_chunks = (int)starts.size() - 1;
+    if (n_chunks > 1 && e->capture) return e->fail(ST_ERR_INVALID, "debug capture holds whole-batch tensors: this batch runs in chunks");
+    HIPCHK(e, hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    int slot = 0;
+    if ((rc = v->slots.acquire(e, B, &slot))) return rc;
+    std::vector<RaggedChunk> chunks(n_chunks);
+    for (int k = 0; k < n_chunks; ++k)      // one depthwise group per packed row
+        chunks[k] = v->slots.fill(slot, lengths, starts[k], starts[k + 1], [](int64_t) { return 1; });
+    if ((rc = v->slots.upload(e, slot, B, s))) return rc;
+    const size_t mel_item = (size_t)c.input_channels * T, audio_item = (size_t)T * v->hop;
+    for (int k = 0; k < n_chunks && rc == ST_OK; ++k)
+        rc = ffgan_forward_chunk(e, mel + starts[k] * mel_item, audio + starts[k] * audio_item, starts[k + 1] - starts[k], T, &chunks[k], s);
+    hipError_t he = v->slots.record(slot, s);       // also after a failed chunk: the copy and the launches before it read the slot
+    if (rc) return rc;
+    HIPCHK(e, he);
     return ST_OK;
 }
 

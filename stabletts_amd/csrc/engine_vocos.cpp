@@ -4,6 +4,7 @@
 // layer scale + residual, head) run on the implicit-GEMM kernels of the decoder over the FLATTENED rows of the batch
 // (taps = 1: rows are independent); everything between them is in vocos_kernels.hip.
 #include "engine_internal.h"
+#include "utt_slots.h"
 #include "vocos_launch.h"
 
 #include <algorithm>
@@ -19,21 +20,7 @@ struct VocosState {
     st_vocos_config cfg{};
     Conv embed, head;
     std::vector<Conv> pw1, pw2;
-    // ragged calls: utterance tables in pinned host memory, copied to device slots; a slot is refilled only after the event
-    // of its previous call, so a call never waits for the one before it (as MelState, engine_audio.cpp)
-    static constexpr int kSlots = 4;
-    VocUtt* host[kSlots] = {};
-    VocUtt* dev[kSlots] = {};
-    hipEvent_t ev[kSlots] = {};
-    bool used[kSlots] = {};
-    int cap = 0, next = 0;
-};
-
-// One chunk of a ragged batch: its utterance table (device, chunk-relative entries) and the sizes the host summed from it.
-struct VocRagged {
-    const VocUtt* utt;
-    int64_t rows;
-    int n_tiles, n_groups, dw_frames;
+    UttSlots slots;      // ragged calls: the utterance tables (utt_slots.h)
 };
 
 static std::string vblk(int i) { return "backbone.convnext." + std::to_string(i) + "."; }
@@ -117,11 +104,7 @@ int vocos_finalize(st_engine* e) {
 void vocos_destroy(st_engine* e) {
     VocosState* v = e->voc;
     if (!v) return;
-    for (int i = 0; i < VocosState::kSlots; ++i) {
-        if (v->host[i]) hipHostFree(v->host[i]);
-        if (v->dev[i]) hipFree(v->dev[i]);
-        if (v->ev[i]) hipEventDestroy(v->ev[i]);
-    }
+    v->slots.destroy();
     delete v; e->voc = nullptr;
 }
 
@@ -159,7 +142,7 @@ int st_create_vocoder(const st_vocos_config* cfg, int device, st_engine** out) {
 // (rg: mel and audio stay padded to T; only the im2col, the depthwise conv and the overlap-add know utterances and take the
 // ragged launcher).  The K loop of the conv GEMM forms an activation row's byte offset as a 32-bit value (t * cin * 2,
 // conv_gemm2_impl.h), so the callers size chunks to keep R * max(7 * M, C, F) * 2 below 2^31.
-static int vocos_forward_chunk(st_engine* e, const float* mel, float* audio, int B, int T, const VocRagged* rg, hipStream_t s) {
+static int vocos_forward_chunk(st_engine* e, const float* mel, float* audio, int B, int T, const RaggedChunk* rg, hipStream_t s) {
     VocosState* v = e->voc;
     const st_vocos_config& c = v->cfg;
     const int C = c.dim, F = c.intermediate_dim, M = c.input_channels, L = c.num_layers;
@@ -290,45 +273,15 @@ int st_vocos_forward_ragged(st_engine* e, const float* mel, const int64_t* lengt
     if (n_chunks > 1 && e->capture) return e->fail(ST_ERR_INVALID, "debug capture holds whole-batch tensors: this batch runs in chunks");
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    if (B > v->cap) {       // grow every slot (after their calls)
-        for (int i = 0; i < VocosState::kSlots; ++i) {
-            if (v->used[i]) HIPCHK(e, hipEventSynchronize(v->ev[i]));
-            if (v->host[i]) { hipHostFree(v->host[i]); v->host[i] = nullptr; }
-            if (v->dev[i]) { hipFree(v->dev[i]); v->dev[i] = nullptr; }
-            v->used[i] = false;
-        }
-        v->cap = 0;
-        const int cap = B > 64 ? B : 64;
-        for (int i = 0; i < VocosState::kSlots; ++i) {
-            HIPCHK(e, hipHostMalloc((void**)&v->host[i], (size_t)cap * sizeof(VocUtt)));
-            HIPCHK(e, hipMalloc((void**)&v->dev[i], (size_t)cap * sizeof(VocUtt)));
-            if (!v->ev[i]) HIPCHK(e, hipEventCreateWithFlags(&v->ev[i], hipEventDisableTiming));
-        }
-        v->cap = cap;
-    }
-    const int slot = v->next;
-    v->next = (v->next + 1) % VocosState::kSlots;
-    if (v->used[slot]) HIPCHK(e, hipEventSynchronize(v->ev[slot]));
-    VocUtt* u = v->host[slot];
-    std::vector<VocRagged> chunks(n_chunks);
-    for (int k = 0; k < n_chunks; ++k) {      // entries relative to their chunk: its rows, tables, mel and audio start at 0
-        VocRagged& rg = chunks[k];
-        rg.utt = v->dev[slot] + starts[k]; rg.rows = 0; rg.n_tiles = 0; rg.n_groups = 0;
-        for (int b = starts[k]; b < starts[k + 1]; ++b) rg.rows += lengths[b];
-        rg.dw_frames = voc_dw_frames(rg.rows);
-        int row0 = 0;
-        for (int b = starts[k]; b < starts[k + 1]; ++b) {
-            const int Tb = (int)lengths[b];
-            u[b] = VocUtt{row0, Tb, rg.n_tiles, rg.n_groups};
-            row0 += Tb; rg.n_tiles += (Tb + 63) / 64; rg.n_groups += (Tb + rg.dw_frames - 1) / rg.dw_frames;
-        }
-    }
-    HIPCHK(e, hipMemcpyAsync(v->dev[slot], u, (size_t)B * sizeof(VocUtt), hipMemcpyHostToDevice, s));
-    v->used[slot] = true;
+    int slot = 0;
+    if ((rc = v->slots.acquire(e, B, &slot))) return rc;
+    std::vector<RaggedChunk> chunks(n_chunks);
+    for (int k = 0; k < n_chunks; ++k) chunks[k] = v->slots.fill(slot, lengths, starts[k], starts[k + 1], voc_dw_frames);
+    if ((rc = v->slots.upload(e, slot, B, s))) return rc;
     const size_t mel_item = (size_t)c.input_channels * T, audio_item = (size_t)T * c.hop_length;
     for (int k = 0; k < n_chunks && rc == ST_OK; ++k)
         rc = vocos_forward_chunk(e, mel + starts[k] * mel_item, audio + starts[k] * audio_item, starts[k + 1] - starts[k], T, &chunks[k], s);
-    hipError_t he = hipEventRecord(v->ev[slot], s);       // also after a failed chunk: the copy and the launches before it read the slot
+    hipError_t he = v->slots.record(slot, s);       // also after a failed chunk: the copy and the launches before it read the slot
     if (rc) return rc;
     HIPCHK(e, he);
     return ST_OK;

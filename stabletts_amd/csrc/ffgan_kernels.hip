@@ -61,16 +61,25 @@ hipError_t launch_ffg_ln(int dtype, const float* x, const float* w, const float*
 }
 
 // ---------------------------------------------------------------- ConvNeXt block prologue: depthwise k = 7 conv + LayerNorm (backbone.py:127-129)
-template <class P>
+// RG (ragged batch): packed row r is frame frames[r].t0 of an utterance of frames[r].T frames whose frame 0 is packed row frames[r].row0
+// (one table entry per row, read through scalar registers); T is then unused.  The arithmetic per row is the same.
+template <class P, bool RG>
 __global__ __launch_bounds__(256) void ffg_dwconv_ln_kernel(const float* __restrict__ x, const float* __restrict__ dw, const float* __restrict__ dbias,
                                                             const float* __restrict__ w, const float* __restrict__ b, int T, long long rows, int C,
-                                                            typename P::elem* __restrict__ h16) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+                                                            const VocSeg* __restrict__ frames, typename P::elem* __restrict__ h16) {
+    const int lane = threadIdx.x & 63, wave = RG ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
     const long long row = (long long)blockIdx.x * 4 + wave;
     if (row >= rows) return;
-    const long long item = row / T;
-    const int t = (int)(row - item * T);
-    const float* xi = x + (size_t)item * T * C;
+    long long item = 0;
+    int t = 0;
+    if (RG) {
+        const VocSeg sg = frames[row];
+        item = sg.row0; t = sg.t0; T = sg.T;      // item: the utterance's first packed row
+    } else {
+        item = row / T;
+        t = (int)(row - item * T);
+    }
+    const float* xi = x + (RG ? (size_t)item * C : (size_t)item * T * C);
     const int ni = C >> 7;
     float2 v[kFfgNi];
 #pragma unroll
@@ -100,8 +109,18 @@ hipError_t launch_ffg_dwconv_ln(int dtype, const float* x, const float* dw, cons
     if (C < 128 || C > kFfgMaxDim || (C & 127)) return hipErrorInvalidValue;
     const long long rows = (long long)B * T;
     const dim3 grid((unsigned)((rows + 3) / 4)), blk(256);
-    if (dtype == DT_BF16) hipLaunchKernelGGL((ffg_dwconv_ln_kernel<OpBF16>), grid, blk, 0, s, x, dw, dbias, w, b, T, rows, C, (OpBF16::elem*)h16);
-    else                  hipLaunchKernelGGL((ffg_dwconv_ln_kernel<OpF16>), grid, blk, 0, s, x, dw, dbias, w, b, T, rows, C, (OpF16::elem*)h16);
+    const VocSeg* none = nullptr;
+    if (dtype == DT_BF16) hipLaunchKernelGGL((ffg_dwconv_ln_kernel<OpBF16, false>), grid, blk, 0, s, x, dw, dbias, w, b, T, rows, C, none, (OpBF16::elem*)h16);
+    else                  hipLaunchKernelGGL((ffg_dwconv_ln_kernel<OpF16, false>), grid, blk, 0, s, x, dw, dbias, w, b, T, rows, C, none, (OpF16::elem*)h16);
+    return hipGetLastError();
+}
+
+hipError_t launch_ffg_dwconv_ln_ragged(int dtype, const float* x, const float* dw, const float* dbias, const float* w, const float* b,
+                                       const VocSeg* frames, int64_t rows, int C, void* h16, hipStream_t s) {
+    if (C < 128 || C > kFfgMaxDim || (C & 127) || !frames || rows < 1) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((rows + 3) / 4)), blk(256);
+    if (dtype == DT_BF16) hipLaunchKernelGGL((ffg_dwconv_ln_kernel<OpBF16, true>), grid, blk, 0, s, x, dw, dbias, w, b, 0, (long long)rows, C, frames, (OpBF16::elem*)h16);
+    else                  hipLaunchKernelGGL((ffg_dwconv_ln_kernel<OpF16, true>), grid, blk, 0, s, x, dw, dbias, w, b, 0, (long long)rows, C, frames, (OpF16::elem*)h16);
     return hipGetLastError();
 }
 
@@ -110,17 +129,27 @@ hipError_t launch_ffg_dwconv_ln(int dtype, const float* x, const float* dw, cons
 // Fragment maps of the 16x16x32 MFMA (common.h): A = weights, lane l holds W[co = l & 15][k = 8 (l >> 4) .. + 8]; B = patch rows, lane l
 // holds a[frame = l & 15][the same k]; D: lane l, register r = out[co = 4 (l >> 4) + r][frame = l & 15] -- four consecutive output
 // channels of one frame, one 16-byte store.
-template <class P, bool IN16, int EPI, int CW>
+// RG (ragged batch, a.utt): the block's item owns the packed rows row0 .. row0 + L of its own length L; a block past that end exits
+// before anything else (block-uniform).  Everything after that is the dense kernel on that item alone.
+template <class P, bool IN16, int EPI, int CW, bool RG>
 __global__ __launch_bounds__(256) void ffg_conv_kernel(FfgConvArgs a) {
     extern __shared__ __align__(16) unsigned char patch[];      // [rows][kc * 2 + 16 bytes]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane >> 4, fl = lane & 15;
     const int t0 = blockIdx.x * kFfgFrames, item = blockIdx.z, ct0 = blockIdx.y * CW;
-    const int cin = a.cin, cout = a.cout, taps = a.taps, dil = a.dil, L = a.L;
+    const int cin = a.cin, cout = a.cout, taps = a.taps, dil = a.dil;
+    int L = a.L;
+    size_t row0 = (size_t)item * L;      // the item's first row
+    if (RG) {
+        const VocUtt u = a.utt[item];
+        L = u.T * a.up;
+        row0 = (size_t)u.row0 * a.up;
+        if (t0 >= L) return;
+    }
     const int kc = cin < 128 ? cin : 128, lg = 31 - __builtin_clz(kc);
     const int S = kc * 2 + 16, halo = (taps >> 1) * dil, rows = kFfgFrames + 2 * halo;
     const int nchunks = cin / kc, ksc = (taps * kc + 31) >> 5;
-    const size_t in_base = (size_t)item * L * cin;
+    const size_t in_base = row0 * cin;
 
     f32x4_t acc[2][CW];
 #pragma unroll
@@ -182,7 +211,7 @@ __global__ __launch_bounds__(256) void ffg_conv_kernel(FfgConvArgs a) {
 #pragma unroll
         for (int cw = 0; cw < CW; ++cw) {
             const int co = (ct0 + cw) * 16 + 4 * g;
-            const size_t o = ((size_t)item * L + t) * cout + co;
+            const size_t o = (row0 + t) * cout + co;
             const float4 bb = *(const float4*)(a.bias + co);
             float4 y = make_float4(acc[fw][cw][0] + bb.x, acc[fw][cw][1] + bb.y, acc[fw][cw][2] + bb.z, acc[fw][cw][3] + bb.w);
             if (EPI == FFG_F32) {
@@ -209,16 +238,21 @@ bool ffg_conv_supported(int cin, int cout, int taps, int dil) {
     return cin_ok && cout >= 16 && cout % 16 == 0 && taps >= 1 && (taps & 1) && taps <= kFfgMaxTaps && dil >= 1 && (taps / 2) * dil <= kFfgMaxHalo;
 }
 
-template <class P, bool IN16, int EPI>
-static hipError_t ffg_conv_cw(const FfgConvArgs& a, hipStream_t s) {
+template <class P, bool IN16, int EPI, bool RG>
+static hipError_t ffg_conv_rg(const FfgConvArgs& a, hipStream_t s) {
     const int tiles = a.cout / 16, cw = tiles % 4 == 0 ? 4 : tiles % 2 == 0 ? 2 : 1;
     const int kc = ffg_kc(a.cin), rows = kFfgFrames + 2 * (a.taps / 2) * a.dil;
     const size_t lds = (size_t)rows * (kc * 2 + 16);
     const dim3 grid((unsigned)((a.L + kFfgFrames - 1) / kFfgFrames), (unsigned)(tiles / cw), (unsigned)a.n_items), blk(256);
-    if (cw == 4)      hipLaunchKernelGGL((ffg_conv_kernel<P, IN16, EPI, 4>), grid, blk, lds, s, a);
-    else if (cw == 2) hipLaunchKernelGGL((ffg_conv_kernel<P, IN16, EPI, 2>), grid, blk, lds, s, a);
-    else              hipLaunchKernelGGL((ffg_conv_kernel<P, IN16, EPI, 1>), grid, blk, lds, s, a);
+    if (cw == 4)      hipLaunchKernelGGL((ffg_conv_kernel<P, IN16, EPI, 4, RG>), grid, blk, lds, s, a);
+    else if (cw == 2) hipLaunchKernelGGL((ffg_conv_kernel<P, IN16, EPI, 2, RG>), grid, blk, lds, s, a);
+    else              hipLaunchKernelGGL((ffg_conv_kernel<P, IN16, EPI, 1, RG>), grid, blk, lds, s, a);
     return hipGetLastError();
+}
+
+template <class P, bool IN16, int EPI>
+static hipError_t ffg_conv_cw(const FfgConvArgs& a, hipStream_t s) {
+    return a.utt ? ffg_conv_rg<P, IN16, EPI, true>(a, s) : ffg_conv_rg<P, IN16, EPI, false>(a, s);
 }
 
 template <class P>
@@ -232,7 +266,7 @@ static hipError_t ffg_conv_dt(const FfgConvArgs& a, hipStream_t s) {
 
 hipError_t launch_ffg_conv(int dtype, const FfgConvArgs& a, hipStream_t s) {
     if (!ffg_conv_supported(a.cin, a.cout, a.taps, a.dil) || (a.in32 != nullptr) == (a.in16 != nullptr) || !a.wfrag || !a.bias) return hipErrorInvalidValue;
-    if (a.L < 1 || a.n_items < 1 || a.n_items > 65535) return hipErrorInvalidValue;
+    if (a.L < 1 || a.n_items < 1 || a.n_items > 65535 || (a.utt && a.up < 1)) return hipErrorInvalidValue;
     return dtype == DT_BF16 ? ffg_conv_dt<OpBF16>(a, s) : ffg_conv_dt<OpF16>(a, s);
 }
 
@@ -317,13 +351,29 @@ hipError_t launch_ffg_tile_bias(const float* bias, int cout, int u, float* dst, 
 // ---------------------------------------------------------------- SiLU -> conv_post (C -> 1) -> tanh, fp32 (head.py:245-247)
 // One block = 256 samples of one item; 16 channels at a time: silu(x) of the 256 + taps - 1 rows in LDS (row pitch 20 floats: the
 // 16-byte reads of 16 consecutive rows fall into 16 different bank slots), one thread per sample.
+// RG (ragged batch): x and pre hold packed rows, the item's own L = utt[item].T * hop samples from row utt[item].row0 * hop; the audio is
+// padded to Lpad samples per item and a block past the item's end writes its zeros and exits before anything else (block-uniform).
 constexpr int kFfgPostPitch = 20;
+template <bool RG>
 __global__ __launch_bounds__(256) void ffg_post_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                                       int L, int C, int taps, float* __restrict__ pre, float* __restrict__ audio) {
+                                                       const VocUtt* __restrict__ utt, int hop, int Lpad, int C, int taps,
+                                                       float* __restrict__ pre, float* __restrict__ audio) {
     __shared__ __align__(16) float tile[(256 + kFfgMaxTaps - 1) * kFfgPostPitch];
     __shared__ __align__(16) float wl[kFfgMaxTaps * 16];
     const int t0 = blockIdx.x * 256, item = blockIdx.y, halo = taps >> 1, rows = 256 + taps - 1;
-    const float* xi = x + (size_t)item * L * C;
+    int L = Lpad;
+    size_t row0 = (size_t)item * L;
+    if (RG) {
+        const VocUtt u = utt[item];
+        L = u.T * hop;
+        row0 = (size_t)u.row0 * hop;
+        if (t0 >= L) {
+            const int t = t0 + threadIdx.x;
+            if (t < Lpad) audio[(size_t)item * Lpad + t] = 0.0f;
+            return;
+        }
+    }
+    const float* xi = x + row0 * C;
     float acc = 0.0f;
     for (int c0 = 0; c0 < C; c0 += 16) {
         if (c0) __syncthreads();
@@ -350,14 +400,24 @@ __global__ __launch_bounds__(256) void ffg_post_kernel(const float* __restrict__
     const int t = t0 + threadIdx.x;
     if (t < L) {
         const float y = acc + bias[0];
-        if (pre) pre[(size_t)item * L + t] = y;
-        audio[(size_t)item * L + t] = tanhf(y);
+        if (pre) pre[row0 + t] = y;
+        audio[(size_t)item * Lpad + t] = tanhf(y);
+    } else if (RG && t < Lpad) {
+        audio[(size_t)item * Lpad + t] = 0.0f;
     }
 }
 
 hipError_t launch_ffg_post(const float* x, const float* w, const float* bias, int n_items, int L, int C, int taps, float* pre, float* audio, hipStream_t s) {
     if (C < 16 || (C & 15) || taps < 1 || !(taps & 1) || taps > kFfgMaxTaps || n_items < 1 || n_items > 65535 || L < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(ffg_post_kernel, dim3((unsigned)((L + 255) / 256), (unsigned)n_items), dim3(256), 0, s, x, w, bias, L, C, taps, pre, audio);
+    hipLaunchKernelGGL(ffg_post_kernel<false>, dim3((unsigned)((L + 255) / 256), (unsigned)n_items), dim3(256), 0, s, x, w, bias, (const VocUtt*)nullptr, 1, L, C,
+                       taps, pre, audio);
+    return hipGetLastError();
+}
+
+hipError_t launch_ffg_post_ragged(const float* x, const float* w, const float* bias, const VocUtt* utt, int hop, int n_items, int L, int C, int taps,
+                                  float* pre, float* audio, hipStream_t s) {
+    if (C < 16 || (C & 15) || taps < 1 || !(taps & 1) || taps > kFfgMaxTaps || n_items < 1 || n_items > 65535 || L < 1 || !utt || hop < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ffg_post_kernel<true>, dim3((unsigned)((L + 255) / 256), (unsigned)n_items), dim3(256), 0, s, x, w, bias, utt, hop, L, C, taps, pre, audio);
     return hipGetLastError();
 }
 

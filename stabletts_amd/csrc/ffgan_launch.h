@@ -4,6 +4,7 @@
 // Activations are time-major [item][L][C]; fp32 residual stream, 16-bit MFMA operands, fp32 accumulation.
 #pragma once
 #include "launch.h"
+#include "vocos_launch.h"
 
 namespace st {
 
@@ -14,6 +15,11 @@ hipError_t launch_ffg_ln(int dtype, const float* x, const float* w, const float*
 // h16 = LayerNorm_C(dwconv7(x) + bias) * w + b per utterance (zero padding, rows of different items never mix); dw: [C][7]
 hipError_t launch_ffg_dwconv_ln(int dtype, const float* x, const float* dw, const float* dbias, const float* w, const float* b,
                                 int B, int T, int C, void* h16, hipStream_t s);
+// launch_ffg_dwconv_ln on the packed rows of a ragged batch (vocos_launch.h): frames[r] names packed row r's utterance (the group
+// table of launch_voc_segments at one frame per group), so a window never leaves its utterance; the arithmetic per row is the
+// dense kernel's
+hipError_t launch_ffg_dwconv_ln_ragged(int dtype, const float* x, const float* dw, const float* dbias, const float* w, const float* b,
+                                       const VocSeg* frames, int64_t rows, int C, void* h16, hipStream_t s);
 
 // ---------------------------------------------------------------- head: implicit-GEMM convolution on the 16x16x32 MFMA
 //   out[t][co] = bias[co] + sum_j sum_ci W[co][j][ci] * a[t + (j - taps/2) * dil][ci],   a = 0 outside [0, L) of its own item
@@ -40,6 +46,10 @@ struct FfgConvArgs {
     // FFG_RES, the last c2 of a ResBlock: its share of the ParralelBlock mean, in block order on one stream.
     // mean = (mean_first ? y : mean + y) * mean_scale  (mean_scale = 1 / n_blocks at the last block, else 1)
     float* mean; int mean_first; float mean_scale;
+    // Ragged batch (utt set): every tensor holds packed rows, item b its frames utt[b].row0 * up .. + utt[b].T * up (up: the product
+    // of the upsample rates before this level) and L is the level length of the LONGEST item: it sizes the grid, a block past its own
+    // item's end exits, and the patch is zero outside its own item.  Each tile then runs the arithmetic of the dense call on its item alone.
+    const VocUtt* utt; int up;
 };
 inline int ffg_kc(int cin) { return cin < 128 ? cin : 128; }
 inline int ffg_ksteps(int cin, int taps) { const int kc = ffg_kc(cin); return (cin / kc) * ((taps * kc + 31) / 32); }
@@ -64,5 +74,9 @@ hipError_t launch_ffg_tile_bias(const float* bias, int cout, int u, float* dst, 
 // audio[item][t] = tanh(pre), pre = bias + sum_j sum_ci w[j][ci] * silu(x[t + j - taps/2][ci]), all fp32 (head.py:245-247); x: [items][L][C],
 // C a multiple of 16, taps odd <= kFfgMaxTaps; pre (optional) receives the pre-tanh signal
 hipError_t launch_ffg_post(const float* x, const float* w, const float* bias, int n_items, int L, int C, int taps, float* pre, float* audio, hipStream_t s);
+// The same on packed rows: item b's utt[b].T * hop samples start at packed row utt[b].row0 * hop of x (and of pre); the audio stays padded,
+// (n_items, L) with L = Tmax * hop, and audio[b][t] = 0 from utt[b].T * hop on (every sample is written)
+hipError_t launch_ffg_post_ragged(const float* x, const float* w, const float* bias, const VocUtt* utt, int hop, int n_items, int L, int C, int taps,
+                                  float* pre, float* audio, hipStream_t s);
 
 }  // namespace st

@@ -5,7 +5,7 @@ Same module tree as the reference (``backbone.downsample_layers.<i>.<j>``, ``bac
 pwconv2,gamma}``, ``backbone.norm``, ``head.conv_pre``, ``head.ups.<i>``, ``head.resblocks.<i>.blocks.<b>.convs{1,2}.<p>``,
 ``head.conv_post``, the weight-normed convs as ``parametrizations.weight.original0`` / ``original1``), so the released
 ``firefly-gan-base-generator.ckpt`` loads with ``load_state_dict(strict=True)``.  The modules hold parameters only: the forward
-pass runs in libstabletts_hip.so (st_ffgan_forward); there is no PyTorch fallback.  Inference only, like the reference.
+pass runs in libstabletts_hip.so (st_ffgan_forward, st_ffgan_forward_ragged); there is no PyTorch fallback.  Inference only, like the reference.
 
 The reference's ``remove_parametrizations`` helpers (head.py:110-114,251-256) raise TypeError and are not mirrored: the
 engine folds the weight norm itself when it packs the weights.
@@ -17,7 +17,7 @@ import torch.nn as nn
 from torch.nn.utils.parametrizations import weight_norm
 
 from . import _lib
-from ._native_module import NativeModule
+from ._native_module import NativeModule, host_lengths
 from .estimator import _ParamsOnly
 
 config_dict = {                 # vocoders/ffgan/model.py:7-29
@@ -168,6 +168,17 @@ class FireflyGANBase(NativeModule):
 
     def forward(self, x):
         """mel (B, input_channels, T) -> audio (B, T * hop_length)  (model.py:52-57)."""
+        return self._vocode(x, None)
+
+    def forward_ragged(self, x, lengths):
+        """``forward`` for a padded batch whose utterance b has ``lengths[b]`` frames (e.g. ``synthesise``'s mel with its
+        ``y_lengths``): mel (B, input_channels, T), lengths B ints in [1, T] (a sequence, or an integer tensor: a device tensor
+        costs one ``.tolist()`` sync) -> audio (B, T * hop_length).  Each utterance's audio is what ``forward`` gives for it alone;
+        ``audio[b, lengths[b] * hop_length:]`` is 0.  ``forward`` has no mask (like the reference), so there the padding reaches
+        back through the encoder's and the head's convolutions into the end of every shorter utterance."""
+        return self._vocode(x, host_lengths(lengths, x))
+
+    def _vocode(self, x, lengths):
         if x.device.type != "cuda":
             raise ValueError(f"mel is on {x.device}: the native FireflyGAN vocoder runs only on a HIP device (there is no CPU fallback)")
         if x.dim() != 3 or x.shape[1] != self.input_channels:
@@ -184,7 +195,11 @@ class FireflyGANBase(NativeModule):
             B, _, T = mel.shape
             audio = torch.empty(B, T * self.hop_length, device=dev, dtype=torch.float32)
             with torch.cuda.device(dev):
-                eng.ffgan_forward(mel, audio, torch.cuda.current_stream(dev).cuda_stream)
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                if lengths is None:
+                    eng.ffgan_forward(mel, audio, stream)
+                else:
+                    eng.ffgan_forward_ragged(mel, lengths, audio, stream)
             return audio
 
 
@@ -199,3 +214,7 @@ class FireflyGANBaseWrapper(nn.Module):
     @torch.inference_mode()
     def forward(self, x):
         return self.model(x)
+
+    @torch.inference_mode()
+    def forward_ragged(self, x, lengths):
+        return self.model.forward_ragged(x, lengths)

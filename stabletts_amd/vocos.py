@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._native_module import NativeModule, _param_key
+from ._native_module import NativeModule, _param_key, host_lengths
 from .estimator import _ParamsOnly
 
 
@@ -100,17 +100,7 @@ class Vocos(NativeModule):
         ``.tolist()`` sync) -> audio (B, T * hop_length).  Each utterance's audio is what ``forward`` gives for it alone;
         ``audio[b, lengths[b] * hop_length:]`` is 0.  ``forward`` has no mask (like the reference), so there the padding reaches
         the last ~12 frames of every shorter utterance."""
-        if isinstance(lengths, torch.Tensor):
-            if lengths.dtype.is_floating_point or lengths.dtype in (torch.bool, torch.complex64, torch.complex128):
-                raise ValueError(f"lengths must be an integer tensor, got {lengths.dtype}")
-            if lengths.device.type != "cpu" and lengths.device != x.device:
-                raise ValueError(f"lengths is on {lengths.device}, the mel is on {x.device}")
-            if lengths.dim() != 1:
-                raise ValueError("lengths must be one-dimensional (B,)")
-            lengths = lengths.tolist()
-        else:
-            lengths = [int(n) for n in lengths]
-        return self._vocode(x, lengths)
+        return self._vocode(x, host_lengths(lengths, x))
 
     def _vocode(self, x, lengths):
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):

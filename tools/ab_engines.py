@@ -5,7 +5,8 @@ thermal drift hits both alike.  ONLY for configurations with the same number of 
 process's hardware queues, and a 4-part engine next to a 2-part one measured 30.7 ms instead of its 24.4 -- compare part counts in
 separate processes, alternating (tools/r04b_session10.sh).  A configuration may also name its own BUILD of the library
 (STABLETTS_HIP_LIB=/path/variant.so, e.g. ST_BUILD_DEFS=-DST_NT_DMA=1 ST_BUILD_OUT=... python -m stabletts_amd.build): both libraries are
-loaded into the one process.     usage: python tools/ab_engines.py "" "ST_FUSED_FFN=3" [rounds] [per_round]"""
+loaded into the one process.     usage: python tools/ab_engines.py "" "ST_FUSED_FFN=3" [rounds] [per_round]
+AB_WORKLOAD=ffgan:BxT times FireflyGANBase.forward (st_ffgan_forward, default configuration, f16) on a (B, 128, T) mel instead of the solve."""
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -17,6 +18,13 @@ cfgs = [dict(kv.split("=") for kv in a.split()) if a.strip() else {} for a in sy
 rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 30
 per = int(sys.argv[4]) if len(sys.argv) > 4 else 3
 RAGGED = os.environ.get("AB_RAGGED") == "1"
+WORKLOAD = os.environ.get("AB_WORKLOAD", "solve")
+FFGAN = WORKLOAD.startswith("ffgan:")
+if FFGAN:
+    from tests import ffgan_restatement as ffr
+    from stabletts_amd.ffgan import FireflyGANBase
+    ff_sd = ffr.make_state_dict(ffr.DEFAULT, ffr.SEED)
+    ff_mel = ffr.make_mel(*(int(v) for v in WORKLOAD[6:].split("x")), 128, 9).cuda()
 sd = oracle.make_state_dict(1234)
 fs, fc = oracle.make_cfg_params(4321)
 g = {k: v.cuda() for k, v in make_inputs(32, 1000, seed=0, ragged=RAGGED).items() if k != "lengths"}
@@ -28,14 +36,17 @@ for c in cfgs:
     for k, v in c.items(): os.environ[k] = v
     # a configuration may name its own build of the library (STABLETTS_HIP_LIB=path): an Engine keeps the CDLL it was created with
     _stlib.LIB_PATH, _stlib._lib = c.get("STABLETTS_HIP_LIB", _default_lib), None
-    d = CFMDecoder(128, 128, 256, 128, 1024, 4, 6, 3, 0.1, 256).cuda()
-    d.estimator.load_state_dict(sd); d.estimator.engine()
+    if FFGAN:
+        d = FireflyGANBase(); d.load_state_dict(ff_sd); d = d.cuda().eval(); d.engine()
+    else:
+        d = CFMDecoder(128, 128, 256, 128, 1024, 4, 6, 3, 0.1, 256).cuda()
+        d.estimator.load_state_dict(sd); d.estimator.engine()
     for k in c: del os.environ[k]
     decs.append(d)
 def run(d):
     c = cfgs[decs.index(d)]          # the configuration's variables are also visible at solve time (ST_SPLIT is read per call)
     for k, v in c.items(): os.environ[k] = v
-    out = d(g["mu"], g["mask"], 10, 1.0, g["c"], "euler", kw, z=g["z"])
+    out = d(ff_mel) if FFGAN else d(g["mu"], g["mask"], 10, 1.0, g["c"], "euler", kw, z=g["z"])
     for k in c: del os.environ[k]
     return out
 outs = [run(d) for d in decs]
@@ -50,6 +61,6 @@ for r in range(rounds):
         torch.cuda.synchronize(); ts[i].append((time.perf_counter() - t0) / per * 1e3)
 import statistics as st
 for i in range(2):
-    print(f"[{sys.argv[1 + i]}] {st.mean(ts[i]):.3f} ms  +- {st.stdev(ts[i]) / len(ts[i]) ** 0.5:.3f} (sem, {len(ts[i])} rounds x {per} solves)  median {st.median(ts[i]):.3f}")
+    print(f"[{sys.argv[1 + i]}] {st.mean(ts[i]):.3f} ms  +- {st.stdev(ts[i]) / len(ts[i]) ** 0.5:.3f} (sem, {len(ts[i])} rounds x {per} calls)  median {st.median(ts[i]):.3f}")
 d = [a - b for a, b in zip(ts[0], ts[1])]
 print(f"paired difference A - B: {st.mean(d):+.3f} ms +- {st.stdev(d) / len(d) ** 0.5:.3f}  ({st.mean(d) / st.mean(ts[0]) * 100:+.2f} %)")

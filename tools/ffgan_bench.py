@@ -2,16 +2,23 @@
 restatement of tests/ffgan_restatement.py run as a torch module on the same GPU: in fp32, and under fp16 autocast.
 
     python tools/ffgan_bench.py [--out profiles/ffgan_bench.txt]
+    python tools/ffgan_bench.py --ragged [--out profiles/ffgan_ragged_bench.txt]
 
 Shapes: B = 1 x T = 1000 and B = 32 x T = 1000 mel frames (512 samples each).  Per shape and implementation: the median of the timed
 calls (HIP events around each call, after warm-up), the achieved TFLOP/s on the model's FLOPs (2 x multiply-adds of every conv and
 linear; the zero taps of the polyphase transposed convs are not counted) and, for the native path, the TB/s on the bytes its
 launches must move at least (every launch reads its inputs and writes its outputs once; weights not counted).
+
+--ragged: one bucket of 32 utterances of U{600..1000} frames (seed 4), f16, as the padded dense call, the ragged call
+(FireflyGANBase.forward_ragged) and a loop of 32 single-utterance calls, and the ragged call with every length equal to T beside two
+runs of the dense call (their difference is the run-to-run spread).  Legs in turn within a round, median over the rounds.
 """
 import argparse
+import json
 import os
 import statistics
 import sys
+import time
 
 import torch
 
@@ -78,11 +85,70 @@ def timed(fn, warmup, iters):
     return statistics.median(ms), min(ms), max(ms)
 
 
+def ragged_bucket(out):
+    """Host clock around CALLS calls that end in a device synchronise; in a round every leg runs in turn, so that drift of a shared
+    machine lands on all of them."""
+    import numpy as np
+    from tests import ffgan_restatement as R
+    from stabletts_amd.ffgan import FireflyGANBase
+    ROUNDS, CALLS, NB, dt = 9, 2, 32, "f16"
+    m = FireflyGANBase(operand_dtype=dt)
+    m.load_state_dict(R.make_state_dict(R.DEFAULT, R.SEED), strict=True)
+    m = m.cuda().eval()
+    lengths = np.random.default_rng(4).integers(600, 1001, NB).tolist()
+    Tmax, rows = max(lengths), sum(lengths)
+    mel = R.make_mel(NB, Tmax, 128, 3).cuda()
+    for b, n in enumerate(lengths):
+        mel[b, :, n:] = 0.0
+    solo = [mel[b:b + 1, :, :n].contiguous() for b, n in enumerate(lengths)]
+    full = [Tmax] * NB
+    legs = {"dense_padded": lambda: m(mel), "ragged": lambda: m.forward_ragged(mel, lengths),
+            "solo_loop": lambda: [m(x) for x in solo],
+            "dense_a": lambda: m(mel), "ragged_equal_lengths": lambda: m.forward_ragged(mel, full), "dense_b": lambda: m(mel)}
+    for fn in legs.values():          # every shape of the timed window, twice
+        fn(); fn()
+    ms = {k: [] for k in legs}
+    for _ in range(ROUNDS):
+        for k, fn in legs.items():
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for _ in range(CALLS):
+                fn()
+            torch.cuda.synchronize(); ms[k].append((time.perf_counter() - t0) / CALLS * 1e3)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    spread = abs(med["dense_a"] - med["dense_b"]) / med["dense_a"]
+    lines = [
+        {"workload": "ffgan_bucket", "dtype": dt, "B": NB, "Tmax": Tmax, "packed_rows": rows, "padded_rows": NB * Tmax,
+         "rows_ratio": round(rows / (NB * Tmax), 3), "rounds": ROUNDS, "calls_per_round": CALLS,
+         "dense_padded_ms_median": round(med["dense_padded"], 3), "ragged_ms_median": round(med["ragged"], 3),
+         "solo_loop_ms_median": round(med["solo_loop"], 3), "ragged_over_dense": round(med["ragged"] / med["dense_padded"], 3),
+         "ragged_over_solo_loop": round(med["ragged"] / med["solo_loop"], 3)},
+        {"workload": "ffgan_equal_lengths", "dtype": dt, "B": NB, "T": Tmax, "rows": NB * Tmax,
+         "dense_a_ms_median": round(med["dense_a"], 3), "dense_b_ms_median": round(med["dense_b"], 3),
+         "ragged_equal_lengths_ms_median": round(med["ragged_equal_lengths"], 3),
+         "dense_run_to_run": round(spread, 4), "ragged_over_dense_a": round(med["ragged_equal_lengths"] / med["dense_a"], 4)},
+    ]
+    head = ("# tools/ffgan_bench.py --ragged on one MI355X: one bucket of 32 utterances of U{600..1000} frames (seed 4) through the native\n"
+            "# FireflyGAN vocoder (default configuration) as the padded dense call (FireflyGANBase.forward: wrong for every utterance shorter\n"
+            "# than the longest), the ragged call (forward_ragged) and a loop of 32 single-utterance dense calls; and the ragged call with every\n"
+            "# length equal to T beside two runs of the dense call at the same rows (their difference is the run-to-run spread).  ms per call,\n"
+            "# host clock around calls_per_round calls ending in a device synchronise, legs in turn within a round, median over the rounds.\n")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(head)
+        for ln in lines:
+            f.write(json.dumps(ln) + "\n")
+            print(json.dumps(ln))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ffgan_bench.txt"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--shapes", default="1x1000,32x1000")
+    ap.add_argument("--ragged", action="store_true")
     args = ap.parse_args()
+    if args.ragged:
+        return ragged_bucket(args.out or os.path.join(ROOT, "profiles", "ffgan_ragged_bench.txt"))
+    args.out = args.out or os.path.join(ROOT, "profiles", "ffgan_bench.txt")
     from tests import ffgan_restatement as R
     from stabletts_amd.ffgan import FireflyGANBase
     cfg = R.DEFAULT
