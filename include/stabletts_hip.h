@@ -40,7 +40,12 @@ enum {
 
 /* MFMA operand type of the dense contractions (accumulation, residual stream, LayerNorm,
  * softmax statistics and the ODE state are always fp32). */
-enum { ST_OPERAND_BF16 = 0, ST_OPERAND_F16 = 1 };
+enum { ST_OPERAND_BF16 = 0, ST_OPERAND_F16 = 1,
+       /* split-precision operands, st_create_ffgan only (every other st_create_* answers ST_ERR_INVALID): each MFMA operand x is the
+        * pair hi = fl16(x), lo = fl16(x - hi) of the named format and each product w_hi x_hi + w_hi x_lo + w_lo x_hi -- about 22 bits
+        * of the fp32 operand at three times the MFMA work.  A bf16 pair carries 16 bits, so ST_OPERAND_BF16_SPLIT keeps the fourth product
+        * w_lo x_lo in the encoder, and its head (about 40 sequential convolutions) carries three bf16 parts per operand and six products */
+       ST_OPERAND_BF16_SPLIT = 2, ST_OPERAND_F16_SPLIT = 3 };
 
 /* Fixed-grid solvers of torchdiffeq.odeint as used at models/flow_matching.py:54. */
 enum { ST_SOLVER_EULER = 0, ST_SOLVER_MIDPOINT = 1, ST_SOLVER_RK4 = 2,
@@ -331,21 +336,25 @@ typedef struct st_ffgan_config {
     int32_t upsample_initial_channel;                         /* model.py:24 */
     int32_t pre_conv_kernel_size, post_conv_kernel_size;      /* model.py:26-27 */
     int32_t use_template;                                     /* model.py:25; native: 0 */
-    int32_t operand_dtype;     /* ST_OPERAND_* of the MFMA operands (accumulation, LayerNorms, residual streams, conv_post, tanh: fp32) */
+    int32_t operand_dtype;     /* ST_OPERAND_* of the MFMA operands, the two _SPLIT values included (accumulation, LayerNorms, residual streams,
+                                  conv_post, tanh: fp32) */
 } st_ffgan_config;
 
 /* The handle takes the parameters of FireflyGANBase.state_dict() under their reference names ("backbone.downsample_layers.0.0.weight",
  * ..., "head.conv_pre.parametrizations.weight.original0" / "original1" (the g and v of a weight-normed conv), ...,
  * "head.resblocks.<i>.blocks.<b>.convs1.<p>.bias", ...) through st_load_param / st_finalize, which folds w = g v / ||v|| (the norm over
  * all dims but 0: the input channel of a ConvTranspose1d) and packs the 16-bit weights.  The other entry points reject the handle
- * and vice versa. */
+ * and vice versa.  A split-precision handle (ST_OPERAND_*_SPLIT) takes the same parameters and serves the same two forward calls with
+ * the same guarantees; its weights are packed as hi / lo pairs and its head keeps the tensor between the two convs of a ResBlock pair
+ * in fp32, which makes the head's workspace 16 bytes per channel-sample of the widest level in place of 14. */
 int st_create_ffgan(const st_ffgan_config* cfg, int device, st_engine** out);
 
 /* Replaces FireflyGANBase.forward(x) (model.py:52-57): mel (B, input_channels, T) fp32 -> audio (B, T * hop) fp32, device pointers,
  * hop = the product of the upsample rates.  No mask, as in the reference: every utterance is vocoded at the padded length T (a batch of
  * different lengths: st_ffgan_forward_ragged), and no kernel reads a neighbouring utterance.  The ParralelBlock mean is accumulated in block order on one stream, without atomics: two
  * calls agree bit for bit.  Every tensor offset in the head kernels is 64-bit; large batches run in chunks of whole utterances so that
- * the head's workspace (three fp32 tensors and one 16-bit tensor of the widest level, 14 bytes per channel-sample) stays below
+ * the head's workspace (three fp32 tensors and one 16-bit tensor of the widest level, 14 bytes per channel-sample; a split-precision
+ * handle: four fp32 tensors, 16 bytes) stays below
  * 1 GiB (one utterance if that alone is more) and the encoder's GEMM rows within 32-bit offsets.  T up to 2^20; a T whose encoder rows
  * exceed the row bound on its own, and a batch that needs more than one chunk while debug capture is on, are ST_ERR_INVALID. */
 int st_ffgan_forward(st_engine* e, const float* mel, float* audio, int B, int T, void* stream);
@@ -361,7 +370,7 @@ int st_ffgan_forward(st_engine* e, const float* mel, float* audio, int B, int T,
  * bitwise st_ffgan_forward's, and an utterance's audio does not depend on its neighbours' mel, lengths or order as long as the
  * encoder's GEMMs select the same tile for the row count.  Everything is validated before the device is touched (a null pointer or
  * a length outside [1, T]: ST_ERR_INVALID naming the index).  Chunks are whole utterances bounded by their PACKED rows -- the 1 GiB
- * head workspace at 14 bytes per channel-sample of the widest level (one utterance if that alone is more), the encoder's 32-bit row
+ * head workspace at 14 bytes (split-precision handle: 16) per channel-sample of the widest level (one utterance if that alone is more), the encoder's 32-bit row
  * bound -- and by 65535 utterances; an utterance that exceeds the row bound on its own is rejected, as is a multi-chunk batch while
  * debug capture is on (a single-chunk call captures packed tensors: "ffgan.encoder" (sum(lengths), D), "ffgan.pre_tanh"
  * (sum(lengths) * hop)).  Enqueued on `stream`; the length table travels through one of four pinned slots guarded by events, as

@@ -21,7 +21,8 @@ for the Vocos multi-scale mel loss (``vocoders/vocos/models/loss.py:6``);
 ``install(vocoder="train")`` registers ``stabletts_amd.vocos_train`` instead, whose ``Vocos`` also trains natively in fp32
 (``vocoders/vocos/train.py:94``: the generator);
 ``install(ffgan=True)`` registers ``stabletts_amd.ffgan`` as ``vocoders.ffgan.model`` (``api.py:21-23``: the default vocoder,
-``FireflyGANBaseWrapper``), inference-only like the reference;
+``FireflyGANBaseWrapper``), inference-only like the reference (its ``operand_dtype="f16_split"`` / ``"bf16_split"`` carry every
+MFMA operand as a hi + lo pair: the waveform at fp32 distance from float64, ``"f16_split"`` at 1.5 x the time of the default ``"f16"``);
 ``install(discriminator="train")`` rebinds ``MultiPeriodDiscriminator`` and ``DiscriminatorP`` of the user's own
 ``vocoders.vocos.models.discriminator`` (``vocoders/vocos/train.py:19,54``) to the native classes of ``stabletts_amd.discriminator``;
 and ``install(resolution_discriminator="train")`` rebinds ``MultiResolutionDiscriminator`` and ``DiscriminatorR`` of that same

@@ -11,10 +11,13 @@ LIB_PATH = os.environ.get("STABLETTS_HIP_LIB") or os.path.join(HERE, "libstablet
 
 ST_OK = 0
 ST_ERR_INVALID, ST_ERR_HIP, ST_ERR_STATE, ST_ERR_UNSUPPORTED = -1, -2, -3, -4
-ST_OPERAND_BF16, ST_OPERAND_F16 = 0, 1
+ST_OPERAND_BF16, ST_OPERAND_F16, ST_OPERAND_BF16_SPLIT, ST_OPERAND_F16_SPLIT = 0, 1, 2, 3
 ST_SOLVER_EULER, ST_SOLVER_MIDPOINT, ST_SOLVER_RK4, ST_SOLVER_DOPRI5 = 0, 1, 2, 3
 ST_SOLVER_BOSH3, ST_SOLVER_FEHLBERG2, ST_SOLVER_ADAPTIVE_HEUN, ST_SOLVER_IMPLICIT_ADAMS = 4, 5, 6, 7
-OPERAND_DTYPES = {"bf16": ST_OPERAND_BF16, "f16": ST_OPERAND_F16, "fp16": ST_OPERAND_F16}
+OPERAND_DTYPES = {"bf16": ST_OPERAND_BF16, "f16": ST_OPERAND_F16, "fp16": ST_OPERAND_F16,
+                  "bf16_split": ST_OPERAND_BF16_SPLIT, "f16_split": ST_OPERAND_F16_SPLIT}
+# hi + lo operand pairs (include/stabletts_hip.h): the FireflyGAN vocoder only
+SPLIT_OPERAND_DTYPES = ("bf16_split", "f16_split")
 # None is torchdiffeq's default method = dopri5 (models/flow_matching.py:54)
 SOLVERS = {"euler": ST_SOLVER_EULER, "midpoint": ST_SOLVER_MIDPOINT, "rk4": ST_SOLVER_RK4,
            "dopri5": ST_SOLVER_DOPRI5, None: ST_SOLVER_DOPRI5, "bosh3": ST_SOLVER_BOSH3,
@@ -281,6 +284,8 @@ class Engine:
         dicts = dict(mel=mel, style_encoder=style_encoder, duration_predictor=duration_predictor, vocoder=vocoder,
                      period_discriminator=period_discriminator, resolution_discriminator=resolution_discriminator, ffgan=ffgan)
         kw = next((k for k in CREATORS if dicts[k] is not None), None)
+        if operand_dtype in SPLIT_OPERAND_DTYPES and kw != "ffgan":      # no st_create_* but st_create_ffgan knows the value
+            raise ValueError(f"operand_dtype {operand_dtype!r} (hi + lo operand pairs) exists for the FireflyGAN vocoder only")
         if kw:          # a configuration dict: its struct's fields by name (operand_dtype, where the struct has one, from the argument)
             (struct, creator), d = CREATORS[kw], dicts[kw]
             cfg = struct(*(OPERAND_DTYPES[operand_dtype] if n == "operand_dtype" else (float if t is ctypes.c_float else int)(d[n])

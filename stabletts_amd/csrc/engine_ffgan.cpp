@@ -3,6 +3,13 @@
 // The ConvNeXt encoder runs like the Vocos backbone (engine_vocos.cpp): its GEMMs on the implicit-GEMM kernels of the decoder over
 // the flattened rows of the batch, the row kernels at a run-time width.  The HiFi-GAN head runs on the convolution family of
 // ffgan_kernels.hip, every level a time-major [item][L][C] tensor.
+// Split-precision handles (ST_OPERAND_*_SPLIT; FfganState::split): every MFMA operand is a hi + lo pair of the 16-bit format and every
+// product three MFMAs (f16: lo * lo dropped) or, in the encoder, four (bf16: its lo * lo is as large as what the pair loses; the head
+// goes further for bf16 and carries three parts, ffgan_launch.h).  An encoder operand is one
+// pair tensor [row][hi | lo], the GEMM source a0 with c0 = 2 K, and c2 re-reads it: K = [a_hi | a_lo | a_hi] against
+// [W_hi | W_hi | W_lo], or K = [a_hi | a_lo | a_hi | a_lo] against [W_hi | W_hi | W_lo | W_lo] (pwconv1 as an fp32-output GEMM, then the
+// GELU row kernel that writes the pair); the head runs the SPLIT instantiations of its convolution family on fp32 tensors: c1
+// stores its fp32 pre-activation and c2 applies the SiLU while it stages it.
 #include "engine_internal.h"
 #include "ffgan_launch.h"
 #include "utt_slots.h"
@@ -26,6 +33,8 @@ struct FfConv {             // one convolution of the head: fragment-ordered 16-
 struct FfganState {
     st_ffgan_config cfg{};
     int hop = 1;
+    bool split = false;                               // hi + lo operand pairs (e->dt names their 16-bit format)
+    int parts() const { return !split ? 1 : cfg.operand_dtype == ST_OPERAND_BF16_SPLIT ? 4 : 3; }      // K slices of an encoder GEMM
     Conv stem;
     std::vector<Conv> down;                           // the k = 1 downsample convs of stages 1..
     std::vector<std::vector<Conv>> pw1, pw2;          // [stage][block]
@@ -46,7 +55,9 @@ static int head_width(const st_ffgan_config& c, int level) { return c.upsample_i
 
 // The limits of the native kernels (include/stabletts_hip.h: st_ffgan_config); nullptr: supported
 static const char* ffgan_unsupported(const st_ffgan_config& c) {
-    if (c.operand_dtype != ST_OPERAND_BF16 && c.operand_dtype != ST_OPERAND_F16) return "operand_dtype";
+    if (c.operand_dtype != ST_OPERAND_BF16 && c.operand_dtype != ST_OPERAND_F16 && c.operand_dtype != ST_OPERAND_BF16_SPLIT &&
+        c.operand_dtype != ST_OPERAND_F16_SPLIT)
+        return "operand_dtype";
     if (c.use_template) return "use_template: the native head is built without the noise convolutions (use_template=False)";
     if (c.input_channels % 64 != 0 || c.input_channels < 64 || c.input_channels > 192) return "input_channels must be 64, 128 or 192";
     if (c.kernel_size != 7) return "the native encoder kernels are built for kernel_size == 7";
@@ -126,10 +137,19 @@ int ffgan_finalize(st_engine* e) {
     FfganState* v = e->ffg;
     const st_ffgan_config& c = v->cfg;
     hipStream_t s = nullptr;
+    const bool split = v->split;
+    const int parts = v->parts();
     auto pack = [&](Conv& cv, const std::string& wname, const std::string& bname, int cout, int cin, int taps) -> int {
-        cv.cout = cout; cv.cin = cin * taps; cv.taps = 1; cv.split = false;      // consumed as a k = 1 GEMM (the stem over im2col rows)
-        int rc = dev_alloc(e, &cv.w, (size_t)cout * taps * cin * 2); if (rc) return rc;
-        HIPCHK(e, launch_pack_weight(e->dt, P(e, wname), cout, cin, taps, 0, cin, cv.w, 0, cin, 0, cin, 0, s));
+        cv.cout = cout; cv.cin = cin * taps * parts; cv.taps = 1; cv.split = false;      // consumed as a k = 1 GEMM (the stem over im2col rows)
+        int rc = dev_alloc(e, &cv.w, (size_t)cout * cv.cin * 2); if (rc) return rc;
+        if (split && taps == 1) {        // [W_hi | W_hi | W_lo (| W_lo)] against K = [a_hi | a_lo | a_hi (| a_lo)]
+            for (int k = 0; k < parts; ++k)
+                HIPCHK(e, launch_pack_weight(e->dt, P(e, wname), cout, cin, 1, 0, cin, cv.w, 0, parts * cin, k * cin, cin, k >= 2, s));
+        } else if (split) {              // the stem: the same slices, each in the (tap, channel) order of the im2col rows
+            HIPCHK(e, launch_ffg_pack_rows_split(e->dt, P(e, wname), cout, cin, taps, parts, cv.w, s));
+        } else {
+            HIPCHK(e, launch_pack_weight(e->dt, P(e, wname), cout, cin, taps, 0, cin, cv.w, 0, cin, 0, cin, 0, s));
+        }
         cv.bias = const_cast<float*>(P(e, bname));
         return ST_OK;
     };
@@ -155,8 +175,8 @@ int ffgan_finalize(st_engine* e) {
         float* scale = nullptr;
         int rc2 = wn_scale(p, cout, cin * taps, &scale); if (rc2) return rc2;
         cv.cin = cin; cv.cout = cout; cv.taps = taps; cv.dil = dil; cv.bias = P(e, p + "bias");
-        if ((rc2 = dev_alloc(e, &cv.wfrag, ffg_frag_bytes(cout, cin, taps)))) return rc2;
-        HIPCHK(e, launch_ffg_pack_conv(e->dt, P(e, p + kWn1), scale, cout, cin, taps, 0, cv.wfrag, s));
+        if ((rc2 = dev_alloc(e, &cv.wfrag, ffg_frag_bytes(cout, cin, taps, split ? ffg_split_planes(e->dt) : 1)))) return rc2;
+        HIPCHK(e, launch_ffg_pack_conv(e->dt, P(e, p + kWn1), scale, cout, cin, taps, 0, cv.wfrag, s, split));
         return ST_OK;
     };
     const int D = c.dims[c.n_stages - 1];
@@ -169,8 +189,8 @@ int ffgan_finalize(st_engine* e) {
         float *scale = nullptr, *bias = nullptr;
         if ((rc = wn_scale(p, ci, co * 2 * u, &scale))) return rc;
         up.cin = ci; up.cout = u * co; up.taps = 3; up.dil = 1;
-        if ((rc = dev_alloc(e, &up.wfrag, ffg_frag_bytes(up.cout, ci, 3)))) return rc;
-        HIPCHK(e, launch_ffg_pack_conv(e->dt, P(e, p + kWn1), scale, up.cout, ci, 3, u, up.wfrag, s));
+        if ((rc = dev_alloc(e, &up.wfrag, ffg_frag_bytes(up.cout, ci, 3, split ? ffg_split_planes(e->dt) : 1)))) return rc;
+        HIPCHK(e, launch_ffg_pack_conv(e->dt, P(e, p + kWn1), scale, up.cout, ci, 3, u, up.wfrag, s, split));
         if ((rc = dev_alloc(e, (void**)&bias, (size_t)up.cout * 4))) return rc;
         HIPCHK(e, launch_ffg_tile_bias(P(e, p + "bias"), co, u, bias, s));
         up.bias = bias;
@@ -208,10 +228,13 @@ static int64_t ffgan_level_elems(const st_ffgan_config& c) {
 static int ffgan_max_dim(const st_ffgan_config& c) { return *std::max_element(c.dims, c.dims + c.n_stages); }
 // rows per chunk: 32-bit operand offsets of the encoder's GEMMs (widest operand row: the im2col rows or 4 * dim)
 static int64_t ffgan_max_rows(const st_ffgan_config& c) {
-    const int64_t widest = std::max<int64_t>(7 * (int64_t)c.input_channels, 4 * (int64_t)ffgan_max_dim(c));
+    const bool split = c.operand_dtype == ST_OPERAND_BF16_SPLIT || c.operand_dtype == ST_OPERAND_F16_SPLIT;      // a pair row is twice as wide
+    const int64_t widest = std::max<int64_t>(7 * (int64_t)c.input_channels, 4 * (int64_t)ffgan_max_dim(c)) * (split ? 2 : 1);
     return (((int64_t)1 << 31) - 1) / (widest * 2);
 }
 constexpr int64_t kFfganHeadBytes = (int64_t)1 << 30;      // bound of the head's level tensors per chunk (stabletts_hip.h: st_ffgan_forward)
+// bytes of head workspace per channel-sample of the widest level: three fp32 level tensors and c1's output, 16-bit or (split) fp32
+static int64_t ffgan_head_sample_bytes(const FfganState* v) { return v->split ? 16 : 14; }
 constexpr int kFfganMaxT = 1 << 20;
 
 // One chunk of whole utterances: the encoder's GEMMs and LayerNorms run over its R flattened rows, R = B * T, or the packed rows of a
@@ -222,21 +245,27 @@ static int ffgan_forward_chunk(st_engine* e, const float* mel, float* audio, int
     const st_ffgan_config& c = v->cfg;
     const int M = c.input_channels, Dmax = ffgan_max_dim(c), D = c.dims[c.n_stages - 1], C0 = c.upsample_initial_channel;
     const int64_t R = rg ? rg->rows : (int64_t)B * T, lvl = ffgan_level_elems(c) * R;
-    const bool cap = e->capture;
+    const bool cap = e->capture, split = v->split;
 
     size_t off = 0;
     auto want = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_a16 = want((size_t)R * 7 * M * 2), o_xa = want((size_t)R * Dmax * 4), o_xb = want((size_t)R * Dmax * 4), o_h16 = want((size_t)R * Dmax * 2);
-    const size_t o_u16 = want((size_t)R * 4 * Dmax * 2), o_enc32 = want((size_t)R * D * 4), o_enc16 = want((size_t)R * D * 2), o_pre = want((size_t)R * C0 * 4);
-    const size_t o_X = want((size_t)lvl * 4), o_Y = want((size_t)lvl * 4), o_Mn = want((size_t)lvl * 4), o_U = want((size_t)lvl * 2);
+    const size_t pr = split ? 2 : 1;       // split: a16, h16 and u16 are pair tensors [row][hi | lo]
+    const size_t o_a16 = want((size_t)R * 7 * M * 2 * pr), o_xa = want((size_t)R * Dmax * 4), o_xb = want((size_t)R * Dmax * 4), o_h16 = want((size_t)R * Dmax * 2 * pr);
+    const size_t o_u16 = want((size_t)R * 4 * Dmax * 2 * pr), o_enc32 = want((size_t)R * D * 4), o_enc16 = split ? 0 : want((size_t)R * D * 2), o_pre = want((size_t)R * C0 * 4);
+    const size_t o_X = want((size_t)lvl * 4), o_Y = want((size_t)lvl * 4), o_Mn = want((size_t)lvl * 4), o_U = want((size_t)lvl * (split ? 4 : 2));
+    const size_t o_u32 = split ? want((size_t)R * 4 * Dmax * 4) : 0;      // split: pwconv1's fp32 output (and no enc16: conv_pre reads enc32)
     const size_t o_pt = cap ? want((size_t)R * v->hop * 4) : 0;
     const size_t o_tiles = rg ? want((size_t)rg->n_tiles * sizeof(VocSeg)) : 0, o_frames = rg ? want((size_t)rg->n_groups * sizeof(VocSeg)) : 0;
     int rc = ensure_ws(e, off); if (rc) return rc;
     VocSeg* tiles = (VocSeg*)(e->ws + o_tiles); VocSeg* frames = (VocSeg*)(e->ws + o_frames);      // im2col tiles; one entry per packed row
     void* a16 = e->ws + o_a16; float* x = (float*)(e->ws + o_xa); float* xn = (float*)(e->ws + o_xb); void* h16 = e->ws + o_h16; void* u16 = e->ws + o_u16;
-    float* enc32 = (float*)(e->ws + o_enc32); void* enc16 = e->ws + o_enc16; float* pre32 = (float*)(e->ws + o_pre);
+    float* enc32 = (float*)(e->ws + o_enc32); void* enc16 = split ? nullptr : e->ws + o_enc16; float* pre32 = (float*)(e->ws + o_pre);
     float* X = (float*)(e->ws + o_X); float* Y = (float*)(e->ws + o_Y); float* Mn = (float*)(e->ws + o_Mn); void* U = e->ws + o_U;
     float* pretanh = cap ? (float*)(e->ws + o_pt) : nullptr;
+    float* u32 = (float*)(e->ws + o_u32);
+    // a split GEMM over the pair tensor `pair` of K values per half: c0 = both halves, c2 = the re-read (hi, or hi and lo)
+    const int parts = v->parts();
+    auto pair_src = [&](ConvGemmArgs& a, const void* pair, int K) { a.a0 = pair; a.c0 = 2 * K; a.c2 = (parts - 2) * K; };
 
     auto args = [&](const Conv& cv) {
         ConvGemmArgs a; memset(&a, 0, sizeof(a));
@@ -248,27 +277,38 @@ static int ffgan_forward_chunk(st_engine* e, const float* mel, float* audio, int
     for (int i = 0; i < c.n_stages; ++i) {
         const int C = c.dims[i];
         if (i == 0) {       // stem: k = 7 conv as an im2col GEMM, then the per-frame LayerNorm
-            if (rg) {
-                HIPCHK(e, launch_voc_segments(rg->utt, B, 1, tiles, frames, s));
-                HIPCHK(e, launch_voc_im2col7_ragged(e->dt, mel, tiles, rg->n_tiles, M, T, a16, s));
-            } else {
-                HIPCHK(e, launch_voc_im2col7(e->dt, mel, B, M, T, a16, s));
-            }
+            if (rg) HIPCHK(e, launch_voc_segments(rg->utt, B, 1, tiles, frames, s));
+            if (split)   HIPCHK(e, launch_ffg_im2col7_split(e->dt, mel, B, M, T, rg ? tiles : nullptr, rg ? rg->n_tiles : 0, a16, s));
+            else if (rg) HIPCHK(e, launch_voc_im2col7_ragged(e->dt, mel, tiles, rg->n_tiles, M, T, a16, s));
+            else         HIPCHK(e, launch_voc_im2col7(e->dt, mel, B, M, T, a16, s));
             ConvGemmArgs a = args(v->stem); a.a0 = a16; a.c0 = 7 * M; a.out32 = x;
+            if (split) pair_src(a, a16, 7 * M);
             HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
             HIPCHK(e, launch_ffg_ln(e->dt, x, P(e, ds(0, 1) + "weight"), P(e, ds(0, 1) + "bias"), R, C, x, nullptr, s));
         } else {            // LayerNorm, then the k = 1 conv to the next width
             const int Cp = c.dims[i - 1];
-            HIPCHK(e, launch_ffg_ln(e->dt, x, P(e, ds(i, 0) + "weight"), P(e, ds(i, 0) + "bias"), R, Cp, nullptr, h16, s));
+            if (split) HIPCHK(e, launch_ffg_ln_split(e->dt, x, P(e, ds(i, 0) + "weight"), P(e, ds(i, 0) + "bias"), R, Cp, nullptr, h16, s));
+            else       HIPCHK(e, launch_ffg_ln(e->dt, x, P(e, ds(i, 0) + "weight"), P(e, ds(i, 0) + "bias"), R, Cp, nullptr, h16, s));
             ConvGemmArgs a = args(v->down[i]); a.a0 = h16; a.c0 = Cp; a.out32 = xn;
+            if (split) pair_src(a, h16, Cp);
             HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
             std::swap(x, xn);
         }
         for (int j = 0; j < c.depths[i]; ++j) {      // ConvNeXtBlock.forward (backbone.py:124-143); DropPath is the identity in eval
             const std::string p = blk(i, j);
             const float *dw = P(e, p + "dwconv.weight"), *db = P(e, p + "dwconv.bias"), *nw = P(e, p + "norm.weight"), *nb = P(e, p + "norm.bias");
-            if (rg) HIPCHK(e, launch_ffg_dwconv_ln_ragged(e->dt, x, dw, db, nw, nb, frames, R, C, h16, s));
-            else    HIPCHK(e, launch_ffg_dwconv_ln(e->dt, x, dw, db, nw, nb, B, T, C, h16, s));
+            if (split)   HIPCHK(e, launch_ffg_dwconv_ln_split(e->dt, x, dw, db, nw, nb, B, T, rg ? frames : nullptr, R, C, h16, s));
+            else if (rg) HIPCHK(e, launch_ffg_dwconv_ln_ragged(e->dt, x, dw, db, nw, nb, frames, R, C, h16, s));
+            else         HIPCHK(e, launch_ffg_dwconv_ln(e->dt, x, dw, db, nw, nb, B, T, C, h16, s));
+            if (split) {     // pwconv1 to fp32, the GELU pair, then x += gamma * (W u + b) over the pair of u
+                ConvGemmArgs a = args(v->pw1[i][j]); pair_src(a, h16, C); a.out32 = u32;
+                HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
+                HIPCHK(e, launch_ffg_gelu_split(e->dt, u32, R, 4 * C, u16, s));
+                ConvGemmArgs b2 = args(v->pw2[i][j]); pair_src(b2, u16, 4 * C); b2.out32 = x;
+                b2.gate = P(e, p + "gamma"); b2.gate_stride = 0;
+                HIPCHK(e, gemm(e, 1, EPI_RESGATE, b2, s));
+                continue;
+            }
             {
                 ConvGemmArgs a = args(v->pw1[i][j]); a.a0 = h16; a.c0 = C; a.out16 = u16;
                 HIPCHK(e, gemm(e, 1, EPI_GELU16, a, s));
@@ -279,6 +319,7 @@ static int ffgan_forward_chunk(st_engine* e, const float* mel, float* audio, int
             }
         }
     }
+    // (split: conv_pre stages enc32 itself and splits it there, so no 16-bit copy is written)
     HIPCHK(e, launch_ffg_ln(e->dt, x, P(e, "backbone.norm.weight"), P(e, "backbone.norm.bias"), R, D, enc32, enc16, s));
     if (cap) capture(e, "ffgan.encoder", enc32, R * D, false, s);
 
@@ -288,10 +329,11 @@ static int ffgan_forward_chunk(st_engine* e, const float* mel, float* audio, int
     auto run = [&](const FfConv& cv, int L, FfgConvArgs a) -> hipError_t {
         a.wfrag = cv.wfrag; a.bias = cv.bias; a.cin = cv.cin; a.cout = cv.cout; a.taps = cv.taps; a.dil = cv.dil; a.L = L; a.n_items = B;
         if (rg) { a.utt = rg->utt; a.up = L / Tmax; }
-        return launch_ffg_conv(e->dt, a, s);
+        return split ? launch_ffg_conv_split(e->dt, a, s) : launch_ffg_conv(e->dt, a, s);
     };
     {
-        FfgConvArgs a{}; a.in16 = enc16; a.epi = FFG_F32; a.out32 = pre32;
+        FfgConvArgs a{}; a.epi = FFG_F32; a.out32 = pre32;
+        if (split) { a.in32 = enc32; a.in_raw = 1; } else a.in16 = enc16;
         HIPCHK(e, run(v->pre, Tmax, a));
     }
     const float* cur = pre32;
@@ -307,10 +349,12 @@ static int ffgan_forward_chunk(st_engine* e, const float* mel, float* audio, int
             for (int p = 0; p < np; ++p) {       // ResBlock1.forward (head.py:101-108)
                 const float* xin = p == 0 ? X : Y;
                 {
-                    FfgConvArgs a{}; a.in32 = xin; a.epi = FFG_SILU16; a.out16 = U;
+                    FfgConvArgs a{}; a.in32 = xin;
+                    if (split) { a.epi = FFG_F32; a.out32 = (float*)U; } else { a.epi = FFG_SILU16; a.out16 = U; }
                     HIPCHK(e, run(v->c1[i][b][p], L, a));
                 }
-                FfgConvArgs a{}; a.in16 = U; a.epi = FFG_RES; a.res32 = xin;
+                FfgConvArgs a{}; a.epi = FFG_RES; a.res32 = xin;
+                if (split) a.in32 = (const float*)U; else a.in16 = U;
                 if (p + 1 < np) a.out32 = Y;
                 else { a.mean = Mn; a.mean_first = b == 0; a.mean_scale = b + 1 == nb ? 1.0f / (float)nb : 1.0f; }
                 HIPCHK(e, run(v->c2[i][b][p], L, a));
@@ -333,9 +377,10 @@ int st_create_ffgan(const st_ffgan_config* cfg, int device, st_engine** out) {
     if (const char* why = ffgan_unsupported(*cfg)) { g_create_error = why; return ST_ERR_INVALID; }
     st_engine* e = nullptr;
     if (int rc = new_handle(KIND_FFGAN, device, &e)) return rc;
-    e->dt = cfg->operand_dtype == ST_OPERAND_BF16 ? DT_BF16 : DT_F16;
+    e->dt = (cfg->operand_dtype == ST_OPERAND_BF16 || cfg->operand_dtype == ST_OPERAND_BF16_SPLIT) ? DT_BF16 : DT_F16;
     e->ffg = new FfganState();
     e->ffg->cfg = *cfg;
+    e->ffg->split = cfg->operand_dtype == ST_OPERAND_BF16_SPLIT || cfg->operand_dtype == ST_OPERAND_F16_SPLIT;
     for (int i = 0; i < cfg->n_upsamples; ++i) e->ffg->hop *= cfg->upsample_rates[i];
     e->splitk_target = 0; e->attn_small_blocks = 0;      // decoder-only small-grid paths
     ffgan_build_params(e, *cfg);
@@ -356,7 +401,7 @@ int st_ffgan_forward(st_engine* e, const float* mel, float* audio, int B, int T,
     const st_ffgan_config& c = e->ffg->cfg;
     const int64_t max_rows = ffgan_max_rows(c);
     if (T > max_rows || T > kFfganMaxT) return e->fail(ST_ERR_INVALID, "T too large: one utterance exceeds the vocoder's row indexing");
-    const int64_t head_item = ffgan_level_elems(c) * T * 14;      // three fp32 level tensors and one 16-bit
+    const int64_t head_item = ffgan_level_elems(c) * T * ffgan_head_sample_bytes(e->ffg);
     const int chunk = (int)std::min<int64_t>({(int64_t)B, std::max<int64_t>(1, kFfganHeadBytes / head_item), max_rows / T, (int64_t)65535});
     if (chunk < B && e->capture) return e->fail(ST_ERR_INVALID, "debug capture holds whole-batch tensors: this batch runs in chunks");
     HIPCHK(e, hipSetDevice(e->device));
@@ -387,7 +432,7 @@ int st_ffgan_forward_ragged(st_engine* e, const float* mel, const int64_t* lengt
     for (int b = 0; b < B; ++b)
         if (lengths[b] > max_rows)
             return e->fail(ST_ERR_INVALID, "lengths[" + std::to_string(b) + "] too large: one utterance exceeds the vocoder's row indexing");
-    const int64_t head_rows = std::max<int64_t>(1, kFfganHeadBytes / (ffgan_level_elems(c) * 14));      // three fp32 level tensors and one 16-bit
+    const int64_t head_rows = std::max<int64_t>(1, kFfganHeadBytes / (ffgan_level_elems(c) * ffgan_head_sample_bytes(v)));
     std::vector<int> starts;          // first utterance of every chunk, then B
     int64_t rows = 0;
     for (int b = 0; b < B; ++b) {

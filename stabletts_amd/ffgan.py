@@ -146,7 +146,12 @@ class HiFiGANGenerator(_ParamsOnly):
 
 class FireflyGANBase(NativeModule):
     """``FireflyGANBase()`` as the reference builds it (model.py:44-50); ``config`` replaces ``config_dict`` for other
-    supported shapes (include/stabletts_hip.h: st_ffgan_config names the native limits; st_create_ffgan rejects the rest)."""
+    supported shapes (include/stabletts_hip.h: st_ffgan_config names the native limits; st_create_ffgan rejects the rest).
+
+    ``operand_dtype``: "f16" (default) or "bf16" round every MFMA operand once; "f16_split" / "bf16_split" carry each operand as a
+    hi + lo pair of that format (three MFMA products, fp32 accumulation; bf16 needs four in the encoder and three parts with six
+    products in the head): the waveform then sits at fp32 distance from float64 (bf16_split: 1e-5) in place of 1e-3 ... 2e-3 of
+    max |audio|, at three times the MFMA work and more (README: the FireflyGAN paragraph has the timings)."""
     _what = "FireflyGAN vocoder"
     _rebind = False             # st_finalize folds the weight norm and packs the weights: every change re-loads
 

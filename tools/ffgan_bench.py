@@ -12,6 +12,10 @@ launches must move at least (every launch reads its inputs and writes its output
 --ragged: one bucket of 32 utterances of U{600..1000} frames (seed 4), f16, as the padded dense call, the ragged call
 (FireflyGANBase.forward_ragged) and a loop of 32 single-utterance calls, and the ragged call with every length equal to T beside two
 runs of the dense call (their difference is the run-to-run spread).  Legs in turn within a round, median over the rounds.
+
+--operand-dtype (default f16; f16_split / bf16_split: the hi + lo operand pairs): without --ragged the named handle is timed beside
+the f16 and bf16 ones in the same run; with --ragged it is the bucket's handle and, if it is not f16, the dense and ragged legs of an
+f16 handle of the same build run in the same rounds.  Without the flag the output is what it was before the flag existed.
 """
 import argparse
 import json
@@ -85,13 +89,13 @@ def timed(fn, warmup, iters):
     return statistics.median(ms), min(ms), max(ms)
 
 
-def ragged_bucket(out):
+def ragged_bucket(out, dt="f16"):
     """Host clock around CALLS calls that end in a device synchronise; in a round every leg runs in turn, so that drift of a shared
     machine lands on all of them."""
     import numpy as np
     from tests import ffgan_restatement as R
     from stabletts_amd.ffgan import FireflyGANBase
-    ROUNDS, CALLS, NB, dt = 9, 2, 32, "f16"
+    ROUNDS, CALLS, NB = 9, 2, 32
     m = FireflyGANBase(operand_dtype=dt)
     m.load_state_dict(R.make_state_dict(R.DEFAULT, R.SEED), strict=True)
     m = m.cuda().eval()
@@ -105,6 +109,11 @@ def ragged_bucket(out):
     legs = {"dense_padded": lambda: m(mel), "ragged": lambda: m.forward_ragged(mel, lengths),
             "solo_loop": lambda: [m(x) for x in solo],
             "dense_a": lambda: m(mel), "ragged_equal_lengths": lambda: m.forward_ragged(mel, full), "dense_b": lambda: m(mel)}
+    if dt != "f16":                   # the default handle of the same build in the same rounds
+        f16 = FireflyGANBase(operand_dtype="f16")
+        f16.load_state_dict(R.make_state_dict(R.DEFAULT, R.SEED), strict=True)
+        f16 = f16.cuda().eval()
+        legs.update({"f16_dense_padded": lambda: f16(mel), "f16_ragged": lambda: f16.forward_ragged(mel, lengths)})
     for fn in legs.values():          # every shape of the timed window, twice
         fn(); fn()
     ms = {k: [] for k in legs}
@@ -127,6 +136,10 @@ def ragged_bucket(out):
          "ragged_equal_lengths_ms_median": round(med["ragged_equal_lengths"], 3),
          "dense_run_to_run": round(spread, 4), "ragged_over_dense_a": round(med["ragged_equal_lengths"] / med["dense_a"], 4)},
     ]
+    if dt != "f16":
+        lines.append({"workload": "ffgan_bucket_vs_f16", "dtype": dt, "f16_dense_padded_ms_median": round(med["f16_dense_padded"], 3),
+                      "f16_ragged_ms_median": round(med["f16_ragged"], 3), "dense_over_f16": round(med["dense_padded"] / med["f16_dense_padded"], 3),
+                      "ragged_over_f16": round(med["ragged"] / med["f16_ragged"], 3)})
     head = ("# tools/ffgan_bench.py --ragged on one MI355X: one bucket of 32 utterances of U{600..1000} frames (seed 4) through the native\n"
             "# FireflyGAN vocoder (default configuration) as the padded dense call (FireflyGANBase.forward: wrong for every utterance shorter\n"
             "# than the longest), the ragged call (forward_ragged) and a loop of 32 single-utterance dense calls; and the ragged call with every\n"
@@ -145,16 +158,19 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--shapes", default="1x1000,32x1000")
     ap.add_argument("--ragged", action="store_true")
+    ap.add_argument("--operand-dtype", default="f16", choices=["f16", "bf16", "f16_split", "bf16_split"])
     args = ap.parse_args()
+    tag = "" if args.operand_dtype == "f16" else "_" + args.operand_dtype
     if args.ragged:
-        return ragged_bucket(args.out or os.path.join(ROOT, "profiles", "ffgan_ragged_bench.txt"))
-    args.out = args.out or os.path.join(ROOT, "profiles", "ffgan_bench.txt")
+        return ragged_bucket(args.out or os.path.join(ROOT, "profiles", f"ffgan_ragged_bench{tag}.txt"), args.operand_dtype)
+    args.out = args.out or os.path.join(ROOT, "profiles", f"ffgan_bench{tag}.txt")
     from tests import ffgan_restatement as R
     from stabletts_amd.ffgan import FireflyGANBase
     cfg = R.DEFAULT
     sd = R.make_state_dict(cfg, R.SEED)
     native = {}
-    for dt in ("f16", "bf16"):
+    dts = ("f16", "bf16") + ((args.operand_dtype,) if args.operand_dtype not in ("f16", "bf16") else ())
+    for dt in dts:
         m = FireflyGANBase(operand_dtype=dt)
         m.load_state_dict(sd, strict=True)
         native[dt] = m.cuda().eval()
@@ -176,13 +192,13 @@ def main():
             with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
                 return R.forward(None, cfg, mel, prepared=W32)["audio"]
 
-        rows = [(f"native {dt}", (lambda m=native[dt]: m(mel))) for dt in ("f16", "bf16")] + [("torch fp32", torch32), ("torch fp16 autocast", torch16)]
+        rows = [(f"native {dt}", (lambda m=native[dt]: m(mel))) for dt in dts] + [("torch fp32", torch32), ("torch fp16 autocast", torch16)]
         ref = torch32().double()
         lines.append(f"B = {B} x T = {T}: {fl * B * T / 1e12:.2f} TFLOP")
         for name, fn in rows:
             med, lo, hi = timed(fn, warm, iters)
             err = float((fn().double() - ref).abs().max() / ref.abs().max())
-            extra = f"  {by * B * T / med / 1e9:6.2f} TB/s" if name.startswith("native") else ""
+            extra = f"  {by * B * T / med / 1e9:6.2f} TB/s" if name.startswith("native") and "split" not in name else ""      # (by: the 16-bit sequence's bytes)
             lines.append(f"  {name:<20} {med:9.2f} ms ({lo:.2f} .. {hi:.2f})  {fl * B * T / med / 1e9:7.1f} TFLOP/s{extra}   max |audio - torch fp32| / max = {err:.1e}")
         lines.append("")
     text = "\n".join(lines)
