@@ -492,6 +492,33 @@ int st_lsgan_loss_forward(const void* const* x, const int64_t* numels, int n_pai
 int st_lsgan_loss_backward(const void* const* x, const int64_t* numels, int n_pairs, int mode, const float* grad_loss,
                            void* const* grad_x, void* stream);
 
+/* ---- the optimizer step of both training loops (torch.optim.AdamW, torch.nn.utils.clip_grad_norm_), stateless -------------- */
+/* Each call works on a LIST of fp32 tensors, given as host arrays of n device pointers (4-byte aligned: an entry may start
+ * anywhere inside a flat buffer) and element counts (each >= 1).  A launch covers up to st_optim_max_tensors() entries, whose
+ * table travels as a kernel argument, and a block works on st_optim_chunk() elements of one entry; longer lists run as several
+ * launches inside the one call.  No device allocation, no copy, no host synchronisation.
+ * st_adamw_step: the decoupled-weight-decay Adam update (non-amsgrad, non-maximize), per element in fp32, each operation rounded
+ *   once:  p *= 1 - lr wd;  m += (g - m)(1 - beta1);  v = v beta2 + (1 - beta2) g g;  p -= step_size m / (sqrt(v) / bc2_sqrt + eps)
+ *   with step_size = lr / (1 - beta1^step) and bc2_sqrt = sqrt(1 - beta2^step) evaluated in double per tensor.  steps: n int64
+ *   step numbers, ALREADY incremented (each >= 1).  An element's new p, m, v are the same bits alone, at any list position and at
+ *   any address (16-byte accesses where an entry's four pointers are 16-byte aligned, 4-byte ones otherwise).
+ * st_grad_norm: total_norm_out[0] (device float) = (float)sqrt(sum of squares over the list), squares and sums in fp64 in one
+ *   fixed order without atomics: two runs agree bit for bit and an entry's contribution does not change with its address.
+ *   scratch: st_grad_norm_scratch_bytes(numels, n) bytes (device, 8-byte aligned), not needed after the call; that function
+ *   returns a negative ST_ERR_* for a bad list.  n == 0 writes 0.
+ * st_grad_clip: every gradient times coef = min(max_norm / (total_norm[0] + 1e-6f), 1.0f), formed in fp32 on the device
+ *   (total_norm: device float, e.g. st_grad_norm's).  A coef of exactly 1.0f loads and stores nothing; a NaN coef multiplies.
+ * A null array or required pointer, n < 0, a count < 1, a pointer that is not 4-byte aligned, a step < 1 or a scratch that is
+ * too small is ST_ERR_INVALID before anything touches the device. */
+int st_optim_chunk(void);
+int st_optim_max_tensors(void);
+int64_t st_grad_norm_scratch_bytes(const int64_t* numels, int n);
+int st_grad_norm(const void* const* grads, const int64_t* numels, int n, float* total_norm_out, void* scratch, int64_t scratch_bytes,
+                 void* stream);
+int st_grad_clip(void* const* grads, const int64_t* numels, int n, const float* total_norm, float max_norm, void* stream);
+int st_adamw_step(void* const* params, const void* const* grads, void* const* exp_avg, void* const* exp_avg_sq, const int64_t* numels,
+                  const int64_t* steps, int n, double lr, double beta1, double beta2, double eps, double weight_decay, void* stream);
+
 /* ---- MelStyleEncoder and DurationPredictor: stages 1 and 3 of StableTTS.synthesise (models/model.py:79-81) ------- */
 /* Both run in fp32 (fp32-input MFMA for every convolution and linear): the durations they feed are ceil()ed
  * (model.py:83-84), so a 16-bit logw error would add or drop whole frames.  Inference only (eval mode: no dropout). */
