@@ -519,6 +519,27 @@ int st_grad_clip(void* const* grads, const int64_t* numels, int n, const float* 
 int st_adamw_step(void* const* params, const void* const* grads, void* const* exp_avg, void* const* exp_avg_sq, const int64_t* numels,
                   const int64_t* steps, int n, double lr, double beta1, double beta2, double eps, double weight_decay, void* stream);
 
+/* ---- sinc resampling (torchaudio.functional.resample's polyphase filter over a list of waveforms), stateless ---------------- */
+/* x, y: host arrays of n device pointers (fp32, 4-byte aligned: an entry may start anywhere inside a flat buffer), in_len and
+ * out_len their lengths in samples, out_len[b] == ceil(new_ * in_len[b] / orig).  orig and new_ are the two rates divided by
+ * their greatest common divisor.  The filter is the caller's COMPACT table, on the device: of phase i (0 <= i < new_) only the
+ * taps inside the window, first[i] the signed offset of its first tap from j * orig, padded with zero taps to the longest
+ * phase's S and stored tap-major, taps[s * new_ + i].  Output sample q = j * new_ + i is
+ *     y[q] = sum over s = 0 .. S-1, ascending, of taps[s * new_ + i] * x[j * orig + first[i] + s]
+ * in fp32, one fused multiply-add per tap; a tap whose input index is outside [0, in_len) contributes exactly zero and is never
+ * read.  A sample's bits depend on its own inputs alone: not on the entry's position in the list, its address or alignment,
+ * its neighbours, or the launch it landed in.  A launch covers up to st_resample_max_tensors() non-empty entries, whose table
+ * travels as a kernel argument, and a block produces st_resample_chunk() consecutive output samples of one entry; longer
+ * lists run as several launches inside the one call.  No device allocation, no copy, no host synchronisation, no atomics.
+ * n == 0 launches nothing, and so does an entry of length 0 (its two pointers are not looked at).
+ * A null array, table or pointer of a non-empty entry, n < 0, orig, new_ or S < 1, a negative length, an out_len other than
+ * the one above or a pointer that is not 4-byte aligned is ST_ERR_INVALID, and new_ * S > 2^22 ST_ERR_UNSUPPORTED, for any
+ * entry of the list before anything touches the device. */
+int st_resample_chunk(void);
+int st_resample_max_tensors(void);
+int st_resample(const void* const* x, void* const* y, const int64_t* in_len, const int64_t* out_len, int n, int orig, int new_,
+                const float* taps, const int32_t* first, int S, void* stream);
+
 /* ---- MelStyleEncoder and DurationPredictor: stages 1 and 3 of StableTTS.synthesise (models/model.py:79-81) ------- */
 /* Both run in fp32 (fp32-input MFMA for every convolution and linear): the durations they feed are ceil()ed
  * (model.py:83-84), so a 16-bit logw error would add or drop whole frames.  Inference only (eval mode: no dropout). */

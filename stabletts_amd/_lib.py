@@ -221,6 +221,9 @@ PROTOTYPES = {
     "st_grad_norm": (i32, [P(vp), P(i64), i32, vp, vp, i64, vp]),
     "st_grad_clip": (i32, [P(vp), P(i64), i32, vp, f32, vp]),
     "st_adamw_step": (i32, [P(vp), P(vp), P(vp), P(vp), P(i64), P(i64), i32, f64, f64, f64, f64, f64, vp]),
+    "st_resample_chunk": (i32, []),
+    "st_resample_max_tensors": (i32, []),
+    "st_resample": (i32, [P(vp), P(vp), P(i64), P(i64), i32, i32, i32, vp, vp, i32, vp]),
     "st_create_mel_extractor": (i32, [P(StMelConfig), i32, P(vp)]),
     "st_mel_frames": (i64, [vp, i64]),
     "st_mel_forward": (i32, [vp, vp, i32, i64, vp, vp]),

@@ -17,12 +17,22 @@ gather), giving the waveform's gradient in its own shape and dtype.  There is no
 get no gradient, and ``forward_ragged`` stays inference-only.
 
 Native limits: ``center=False``, ``pad_mode="reflect"``, ``win_length == n_fft``, ``n_fft`` a power of two in [32, 2048].
-File decoding and resampling still need torchaudio (``load_and_resample_audio`` imports it when called).
+
+Resampling: ``resample``, ``resample_ragged`` and ``Resample`` are ``torchaudio.functional.resample`` /
+``torchaudio.transforms.Resample`` without torchaudio.  An fp32 waveform on a HIP device runs the polyphase filter in
+libstabletts_hip.so (``st_resample``) through a compact tap table built here in float64 (only the taps inside the window: 14 per
+phase at 48000 -> 44100 where the dense form has 174); CPU tensors, other dtypes and grad-enabled calls run the dense
+formulation in torch (``F.pad`` + strided ``conv1d``), which is differentiable.  ``load_and_resample_wav`` decodes RIFF/WAVE PCM
+with the standard library and resamples with ``resample``: file to log-mel needs no third-party library.  Other containers and
+codecs (flac, mp3, float WAV) still need torchaudio: ``load_and_resample_audio`` imports it when called.
 """
+import ctypes
 import math
+import wave
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import _lib
 from ._native_module import hip_device_index
@@ -360,4 +370,270 @@ def load_and_resample_audio(audio_path, target_sr, device="cpu"):
         y = y[0, :].unsqueeze(0)
     if sr != target_sr:
         y = torchaudio.functional.resample(y, sr, target_sr)
+    return y
+
+
+# ---------------------------------------------------------------- resampling (torchaudio.functional.resample)
+_RESAMPLING_METHODS = ("sinc_interp_hann", "sinc_interp_kaiser")
+_KAISER_BETA = 14.769656459379492
+RESAMPLE_MAX_TABLE = 1 << 22        # new * S entries of a compact table (st_resample's limit: 16 MB, 32-bit tap indices)
+_filters = {}                       # (key, "dense" | "compact", device, dtype) -> the cached filter
+
+
+def _resample_key(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, beta):
+    """The checked arguments as the cache key (orig, new, lowpass_filter_width, rolloff, method, beta), rates divided by
+    their greatest common divisor."""
+    for name, v in (("orig_freq", orig_freq), ("new_freq", new_freq)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or int(v) != v:
+            raise ValueError(f"{name} must be an integer sample rate, got {v!r} (torchaudio: frequencies must be of integer type "
+                             "to ensure quality resampling computation)")
+        if v <= 0:
+            raise ValueError(f"{name} must be positive, got {v!r}")
+    if lowpass_filter_width <= 0:
+        raise ValueError("Low pass filter width should be positive.")
+    if not rolloff > 0:
+        raise ValueError("rolloff must be positive")
+    if resampling_method not in _RESAMPLING_METHODS:
+        raise ValueError(f"Invalid resampling method: {resampling_method}")
+    orig_freq, new_freq = int(orig_freq), int(new_freq)
+    g = math.gcd(orig_freq, new_freq)
+    if resampling_method == "sinc_interp_hann":
+        beta = None
+    else:
+        beta = _KAISER_BETA if beta is None else float(beta)
+    return (orig_freq // g, new_freq // g, lowpass_filter_width, float(rolloff), resampling_method, beta)
+
+
+def _sinc_taps(t, lowpass_filter_width, method, beta, scale):
+    """The filter at the float64 times t (in periods of the cut-off, unclamped), in torchaudio's order of operations."""
+    t = t.clamp(-lowpass_filter_width, lowpass_filter_width)
+    if method == "sinc_interp_hann":
+        window = torch.cos(t * math.pi / lowpass_filter_width / 2) ** 2
+    else:
+        beta_t = torch.tensor(beta, dtype=torch.float64)
+        window = torch.i0(beta_t * torch.sqrt(1 - (t / lowpass_filter_width) ** 2)) / torch.i0(beta_t)
+    t = t * math.pi
+    taps = torch.where(t == 0, torch.ones((), dtype=torch.float64), t.sin() / t)
+    return taps * (window * scale)
+
+
+def _filter_geometry(key):
+    orig, new, lpw, rolloff = key[:4]
+    base = min(orig, new) * rolloff
+    return base, math.ceil(lpw * orig / base), base / orig
+
+
+def _dense_kernel(key, device, dtype):
+    """torchaudio's kernel (new, 1, 2 width + orig) built in float64 on the device and rounded once to dtype, and width."""
+    hit = _filters.get((key, "dense", device, dtype))
+    if hit is None:
+        orig, new, lpw, _, method, beta = key
+        base, width, scale = _filter_geometry(key)
+        idx = torch.arange(-width, width + orig, dtype=torch.float64, device=device)[None, None] / orig
+        t = torch.arange(0, -new, -1, dtype=torch.float64, device=device)[:, None, None] / new + idx
+        t *= base
+        hit = _filters[(key, "dense", device, dtype)] = (_sinc_taps(t, lpw, method, beta, scale).to(dtype), width)
+    return hit
+
+
+def _compact_table(key, device):
+    """The compact form of the dense kernel: of phase i only the taps with |t| < lowpass_filter_width (the others are zero in fp32
+    for the Hann window and below 2^-60 of the scale for Kaiser's), which are contiguous.  -> (taps (S, new) fp32 tap-major,
+    first (new) int32: the offset of a phase's first tap from j * orig, S).  Only the band is evaluated, in float64 and in the
+    dense kernel's order of operations, so a kept tap is the dense entry bit for bit."""
+    hit = _filters.get((key, "compact", device, None))
+    if hit is not None:
+        return hit
+    cpu = torch.device("cpu")
+    hit = _filters.get((key, "compact", cpu, None))
+    if hit is None:
+        orig, new, lpw, _, method, beta = key
+        base, width, scale = _filter_geometry(key)
+        half = lpw * orig / base                    # a phase keeps the offsets o with |o - i orig / new| < half
+        limit = f"the native resampler's tap table is limited to new * S <= 2^22 entries (RESAMPLE_MAX_TABLE), {orig} -> {new} needs "
+        if new * (math.ceil(2 * half) - 1) > RESAMPLE_MAX_TABLE:
+            raise NotImplementedError(limit + f"at least {new * (math.ceil(2 * half) - 1)}")
+        n_cand = 2 * math.ceil(half) + 4
+        phase = torch.arange(new, dtype=torch.int64)
+        start = (phase * orig) // new - math.ceil(half) - 1
+        o = start[:, None] + torch.arange(n_cand, dtype=torch.int64)[None]
+        t = (-phase).to(torch.float64)[:, None] / new + o.to(torch.float64) / orig
+        t *= base
+        kept = (t.abs() < lpw) & (o >= -width) & (o < width + orig)
+        count = kept.sum(1)
+        k0 = kept.to(torch.int32).argmax(1)
+        k1 = n_cand - 1 - kept.flip(1).to(torch.int32).argmax(1)
+        assert bool((count >= 1).all()) and bool((k1 - k0 + 1 == count).all()), "a phase's kept taps are contiguous"
+        S = int(count.max())
+        if new * S > RESAMPLE_MAX_TABLE:
+            raise NotImplementedError(limit + f"{new * S}")
+        s = torch.arange(S, dtype=torch.int64)[None]
+        vals = _sinc_taps(t, lpw, method, beta, scale).gather(1, (k0[:, None] + s).clamp(max=n_cand - 1)).to(torch.float32)
+        taps = torch.where(s < count[:, None], vals, torch.zeros((), dtype=torch.float32)).t().contiguous()
+        hit = _filters[(key, "compact", cpu, None)] = (taps, (start + k0).to(torch.int32), S)
+    if device != cpu:
+        hit = _filters[(key, "compact", device, None)] = (hit[0].to(device), hit[1].to(device), hit[2])
+    return hit
+
+
+def resample_table(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, resampling_method="sinc_interp_hann", beta=None,
+                   device="cpu"):
+    """The compact tap table st_resample reads, cached per (rates, filter arguments, device): dict(taps (S, new) fp32,
+    first (new) int32, S, orig, new, width).  NotImplementedError where new * S exceeds RESAMPLE_MAX_TABLE."""
+    key = _resample_key(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, beta)
+    taps, first, S = _compact_table(key, torch.device(device))
+    return dict(taps=taps, first=first, S=S, orig=key[0], new=key[1], width=_filter_geometry(key)[1])
+
+
+def _out_len(L, orig, new):
+    return -((-new * L) // orig)
+
+
+def _native_waveform(w):
+    return w.is_cuda and w.dtype is torch.float32 and not (torch.is_grad_enabled() and w.requires_grad)
+
+
+def _resample_dense(waveform, key):
+    """torchaudio's formulation in torch: the dense kernel in the waveform's dtype, F.pad and a strided conv1d."""
+    if not waveform.is_floating_point():
+        raise TypeError(f"Expected floating point type for waveform tensor, but received {waveform.dtype}.")
+    orig, new = key[:2]
+    kernel, width = _dense_kernel(key, waveform.device, waveform.dtype)
+    shape = waveform.shape
+    L = shape[-1]
+    x = F.pad(waveform.reshape(-1, L), (width, width + orig))
+    y = F.conv1d(x[:, None], kernel, stride=orig).transpose(1, 2).reshape(x.shape[0], -1)[..., :_out_len(L, orig, new)]
+    return y.reshape(shape[:-1] + y.shape[-1:])
+
+
+def _resample_native(key, xs, ys):
+    """xs, ys: fp32 1-D contiguous views on one HIP device, ys[b] of _out_len(xs[b]) samples -- one st_resample call."""
+    rows = [(x.data_ptr(), y.data_ptr(), x.numel(), y.numel()) for x, y in zip(xs, ys) if x.numel() > 0]
+    if not rows:
+        return
+    dev = xs[0].device
+    taps, first, S = _compact_table(key, dev)
+    n = len(rows)
+    cols = list(zip(*rows))
+    ptr_t, i64_t = ctypes.c_void_p * n, ctypes.c_int64 * n
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        rc = lib.st_resample(ptr_t(*cols[0]), ptr_t(*cols[1]), i64_t(*cols[2]), i64_t(*cols[3]), n, key[0], key[1],
+                             taps.data_ptr(), first.data_ptr(), S, stream)
+    if rc != _lib.ST_OK:
+        raise _lib.NativeError(rc, lib.st_last_error(None).decode())
+
+
+def _resample(waveform, key):
+    orig, new = key[:2]
+    if orig == new:
+        return waveform
+    shape = waveform.shape
+    L = shape[-1]
+    if waveform.numel() == 0:
+        return waveform.new_empty(shape[:-1] + (_out_len(L, orig, new),))
+    if not _native_waveform(waveform):
+        return _resample_dense(waveform, key)
+    x = waveform.detach().reshape(-1, L).contiguous()
+    y = torch.empty(x.shape[0], _out_len(L, orig, new), device=x.device, dtype=torch.float32)
+    _resample_native(key, list(x), list(y))
+    return y.view(shape[:-1] + y.shape[-1:])
+
+
+def resample(waveform, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, resampling_method="sinc_interp_hann", beta=None):
+    """``torchaudio.functional.resample``: waveform (..., L) at orig_freq -> (..., ceil(new L / orig)) at new_freq, with the
+    rates divided by their greatest common divisor.  An fp32 tensor on a HIP device runs natively (``st_resample``) unless it
+    requires grad with autograd enabled; anything else -- CPU tensors, other dtypes, grad-enabled calls -- runs torchaudio's
+    dense formulation in torch, differentiably.  Equal rates return the waveform itself."""
+    return _resample(waveform, _resample_key(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, beta))
+
+
+def resample_ragged(waves, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, resampling_method="sinc_interp_hann", beta=None):
+    """A list of 1-D waveforms of any lengths -> the list of their resampled waveforms, each bit for bit the one ``resample``
+    gives for it alone.  fp32 waveforms on one HIP device run as ONE native call without concatenation (64 waveforms per
+    launch; the results are views of one buffer); any other list is ``resample`` per waveform."""
+    key = _resample_key(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, beta)
+    waves = list(waves)
+    for w in waves:
+        if w.dim() != 1:
+            raise ValueError("resample_ragged takes 1-D waveforms")
+    orig, new = key[:2]
+    if orig == new:
+        return waves
+    if not waves or not all(_native_waveform(w) and w.device == waves[0].device for w in waves):
+        return [_resample(w, key) for w in waves]
+    xs = [w.detach().contiguous() for w in waves]
+    lens = [_out_len(x.numel(), orig, new) for x in xs]
+    ys = list(torch.empty(sum(lens), device=xs[0].device, dtype=torch.float32).split(lens))
+    _resample_native(key, xs, ys)
+    return ys
+
+
+class Resample(nn.Module):
+    """``torchaudio.transforms.Resample``: the constructor's filter applied by ``resample``.  The filter tables are built at the
+    first call on a device and cached there; like torchaudio's non-persistent ``kernel`` buffer they are no ``state_dict()``
+    entry."""
+
+    def __init__(self, orig_freq=16000, new_freq=16000, resampling_method="sinc_interp_hann", lowpass_filter_width=6, rolloff=0.99,
+                 beta=None):
+        super().__init__()
+        self._key = _resample_key(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, beta)
+        self.orig_freq = orig_freq
+        self.new_freq = new_freq
+        self.gcd = math.gcd(int(orig_freq), int(new_freq))
+        self.resampling_method = resampling_method
+        self.lowpass_filter_width = lowpass_filter_width
+        self.rolloff = rolloff
+        self.beta = beta
+
+    def forward(self, waveform):
+        return _resample(waveform, self._key)
+
+    def forward_ragged(self, waves):
+        """``resample_ragged`` with the constructor's filter."""
+        k = self._key
+        return resample_ragged(waves, self.orig_freq, self.new_freq, k[2], k[3], k[4], k[5])
+
+
+def _decode_wav(audio_path):
+    """RIFF/WAVE PCM through the standard library -> ((channels, frames) fp32 in [-1, 1), sample rate): 8-bit unsigned as
+    (v - 128) / 128, 16-, 24- and 32-bit signed as v / 2^(bits - 1)."""
+    with wave.open(audio_path, "rb") as f:          # wave.Error for anything but PCM (format tag 1)
+        channels, width, rate, frames = f.getnchannels(), f.getsampwidth(), f.getframerate(), f.getnframes()
+        raw = f.readframes(frames)
+    if width not in (1, 2, 3, 4):
+        raise ValueError(f"unsupported sample width of {width} bytes")
+    raw = raw[:len(raw) - len(raw) % (width * channels)]
+    if not raw:
+        return torch.zeros(channels, 0), rate
+    b = torch.frombuffer(bytearray(raw), dtype=torch.uint8)
+    if width == 1:
+        v = b.to(torch.float64) - 128.0
+    elif width == 2:
+        v = b.view(torch.int16).to(torch.float64)    # RIFF is little-endian, as every host this runs on
+    elif width == 4:
+        v = b.view(torch.int32).to(torch.float64)
+    else:
+        b = b.view(-1, 3).to(torch.int32)
+        v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+        v = ((v ^ 0x800000) - 0x800000).to(torch.float64)            # sign extension of the 24-bit value
+    v = (v / float(1 << (8 * width - 1))).to(torch.float32)
+    return v.view(-1, channels).t().contiguous(), rate
+
+
+def load_and_resample_wav(audio_path, target_sr, device="cpu"):
+    """The reference's ``load_and_resample_audio`` (utils/audio.py:59-74) for RIFF/WAVE PCM files without torchaudio: the first
+    channel as a (1, time) fp32 waveform at target_sr, or None -- with the error printed -- when the file cannot be read
+    (missing, not a WAVE file, not PCM).  Decoding is the standard library's ``wave``; resampling is ``resample`` ON
+    ``device``, natively where that is a HIP device.  Unlike the reference, whose ``y.to(device)`` discards its result and
+    returns a CPU tensor whatever ``device`` is, the waveform returned here is on ``device``."""
+    try:
+        y, sr = _decode_wav(audio_path)
+    except Exception as e:      # the reference reports the failure and returns None (preprocess.py:64 skips the file)
+        print(str(e))
+        return None
+    y = y[:1].to(device)        # first channel only
+    if sr != target_sr:
+        y = resample(y, sr, target_sr)
     return y

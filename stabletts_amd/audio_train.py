@@ -3,6 +3,7 @@ inference path -- but ``LinearSpectrogram`` and ``LogMelSpectrogram`` opt in to 
 under autograd, on a waveform that requires grad, they run the native forward and ``backward`` runs st_mel_backward instead of
 raising.  vocoders/vocos/models/loss.py:6 imports ``LogMelSpectrogram`` from here for the multi-scale mel loss."""
 from .audio import MelScale, frames, load_and_resample_audio, melscale_fbanks  # noqa: F401  (the names of audio)
+from .audio import Resample, load_and_resample_wav, resample, resample_ragged, resample_table  # noqa: F401
 from .audio import LinearSpectrogram as _LinearSpectrogram
 from .audio import LogMelSpectrogram as _LogMelSpectrogram
 
