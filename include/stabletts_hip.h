@@ -252,7 +252,7 @@ int st_cfm_loss_scratch_floats(void);
 /* Replaces Vocos.__init__(VocosConfig(), MelConfig()) (vocoders/vocos/models/model.py:11-15, config.py:4-19,46-50). */
 typedef struct st_vocos_config {
     int32_t input_channels;    /* n_mels, config.py:47 (multiple of 64) */
-    int32_t dim;               /* config.py:48; native kernels: 512 */
+    int32_t dim;               /* config.py:48; native kernels: 512, 768 (the Vocos trainer's, vocoders/vocos/config.py:23) or 1024 */
     int32_t intermediate_dim;  /* config.py:49 (multiple of 256) */
     int32_t num_layers;        /* config.py:50 (1..32) */
     int32_t n_fft;             /* MelConfig.n_fft, config.py:6; native kernels: 2048 */

@@ -119,7 +119,7 @@ int st_create_vocoder(const st_vocos_config* cfg, int device, st_engine** out) {
     if (cfg->input_channels < 1 || cfg->dim < 1 || cfg->intermediate_dim < 1) return bad("channel counts must be positive", ST_ERR_INVALID);
     if (cfg->operand_dtype != ST_OPERAND_BF16 && cfg->operand_dtype != ST_OPERAND_F16) return bad("operand_dtype", ST_ERR_INVALID);
     // limits of this native build
-    if (cfg->dim != kVocDim) return bad("native vocoder kernels are built for dim == 512", ST_ERR_UNSUPPORTED);
+    if (!voc_dim_supported(cfg->dim)) return bad("native vocoder kernels are built for dim == 512, 768 or 1024", ST_ERR_UNSUPPORTED);
     if (cfg->n_fft != kVocNfft || cfg->hop_length != kVocHop) return bad("native ISTFT is built for n_fft == 2048, hop_length == 512", ST_ERR_UNSUPPORTED);
     if (cfg->input_channels % 64 != 0 || cfg->input_channels > 192) return bad("input_channels must be 64, 128 or 192", ST_ERR_UNSUPPORTED);
     if (cfg->intermediate_dim % 256 != 0) return bad("intermediate_dim must be a multiple of 256", ST_ERR_UNSUPPORTED);
@@ -176,7 +176,7 @@ static int vocos_forward_chunk(st_engine* e, const float* mel, float* audio, int
         }
         ConvGemmArgs a = args(v->embed); a.a0 = a16; a.c0 = 7 * M; a.out32 = x;
         HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
-        HIPCHK(e, launch_voc_ln(e->dt, x, P(e, "backbone.norm.weight"), P(e, "backbone.norm.bias"), R, x, nullptr, nullptr, s));
+        HIPCHK(e, launch_voc_ln(e->dt, x, P(e, "backbone.norm.weight"), P(e, "backbone.norm.bias"), R, C, x, nullptr, nullptr, s));
     }
     if (cap) capture(e, "voc.embed", x, R * C, false, s);
     for (int i = 0; i < L; ++i) {       // ConvNeXtBlock.forward (module.py:33-46)
@@ -184,8 +184,8 @@ static int vocos_forward_chunk(st_engine* e, const float* mel, float* audio, int
         {
             ProfScope ps(e, s, PC_FILM_LN1, 0);
             const float *dw = P(e, p + "dwconv.weight"), *db = P(e, p + "dwconv.bias"), *nw = P(e, p + "norm.weight"), *nb = P(e, p + "norm.bias");
-            if (rg) HIPCHK(e, launch_voc_dwconv_ln_ragged(e->dt, x, dw, db, nw, nb, groups, rg->n_groups, rg->dw_frames, h16, s));
-            else    HIPCHK(e, launch_voc_dwconv_ln(e->dt, x, dw, db, nw, nb, B, T, h16, s));
+            if (rg) HIPCHK(e, launch_voc_dwconv_ln_ragged(e->dt, x, dw, db, nw, nb, groups, rg->n_groups, rg->dw_frames, C, h16, s));
+            else    HIPCHK(e, launch_voc_dwconv_ln(e->dt, x, dw, db, nw, nb, B, T, C, h16, s));
         }
         {
             ProfScope ps(e, s, PC_FFN1, 2.0 * R * C * (double)F);
@@ -201,7 +201,7 @@ static int vocos_forward_chunk(st_engine* e, const float* mel, float* audio, int
     }
     {   // final LayerNorm (backbone.py:55) + head projection (head.py:103)
         ProfScope ps(e, s, PC_FINAL, 2.0 * R * C * (double)(c.n_fft + 2));
-        HIPCHK(e, launch_voc_ln(e->dt, x, P(e, "backbone.final_layer_norm.weight"), P(e, "backbone.final_layer_norm.bias"), R,
+        HIPCHK(e, launch_voc_ln(e->dt, x, P(e, "backbone.final_layer_norm.weight"), P(e, "backbone.final_layer_norm.bias"), R, C,
                                 cap ? x : nullptr, h16, h16lo, s));
         ConvGemmArgs a = args(v->head); a.a0 = h16; a.c0 = C; a.a1 = h16lo; a.c1 = C; a.c2 = C; a.out32 = head;
         HIPCHK(e, gemm(e, 1, EPI_F32, a, s));

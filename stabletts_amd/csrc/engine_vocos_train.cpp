@@ -20,7 +20,13 @@ using namespace sthost;
 
 namespace {
 
-struct VtCfg { int C, F, M, L, NB; };       // NB = n_fft + 2 head rows
+struct VtCfg {
+    int C, F, M, L, NB;       // NB = n_fft + 2 head rows
+    // accumulation chains of the GEMMs (SdConvArgs::chains).  dim 512 keeps the arithmetic it was released with; the wider generators
+    // (the trainer's 768 / 2048 / 12) contract over up to 2048 terms through more blocks, and four chains hold their gradients
+    // within the bar of the 512 preset against the reference module (tests/test_gpu_vocos_dims_training.py)
+    int chains() const { return C > 512 ? 4 : 1; }
+};
 
 // the handle's configuration from its parameter table (st_create_vocoder built it from the st_vocos_config)
 VtCfg vt_cfg(const st_engine* e) {
@@ -55,7 +61,7 @@ VtActs vt_acts(const VtCfg& c, int64_t R) {
 
 int vt_check_shape(st_engine* e, const VtCfg& c, int B, int T) {
     const int64_t R = (int64_t)B * T;
-    const int64_t widest = std::max({(int64_t)7 * c.M, (int64_t)c.F, (int64_t)2 * kVocHeadPlane, (int64_t)kVocNfft});
+    const int64_t widest = std::max({(int64_t)7 * c.M, (int64_t)c.C, (int64_t)c.F, (int64_t)2 * kVocHeadPlane, (int64_t)kVocNfft});
     if (R * widest >= ((int64_t)1 << 31)) return e->fail(ST_ERR_INVALID, "B*T too large for the vocoder's training path (32-bit tile indexing)");
     if (B > 65535) return e->fail(ST_ERR_INVALID, "B too large for the vocoder's training path (at most 65535 items)");
     return ST_OK;
@@ -90,7 +96,7 @@ int st_vocos_train_forward(st_engine* e, const float* mel, float* audio, int B, 
 
     auto conv = [&](const float* in, int cin, const std::string& w, const std::string& b, int cout, float* out) {
         SdConvArgs a; a.in = in; a.Cin = cin; a.w = P(e, w); a.bias = P(e, b); a.out = out; a.Cout = cout;
-        a.B = 1; a.T = (int)R; a.taps = 1;
+        a.B = 1; a.T = (int)R; a.taps = 1; a.chains = c.chains();
         return launch_sd_conv(a, s);
     };
     auto ln = [&](const float* x, const std::string& p, float* stats, float* y) {
@@ -168,7 +174,7 @@ int st_vocos_train_backward(st_engine* e, const float* d_audio, float* d_mel, fl
         return launch_sd_sum_frames(dy, G(p + "bias"), 1, cout, Ri, 0, s);
     };
     auto dgrad = [&](const std::string& w, const float* dy, int cout, int cin, float* out) {
-        SdConvArgs a; a.in = dy; a.Cin = cout; a.w = P(e, w); a.out = out; a.Cout = cin; a.B = 1; a.T = Ri; a.taps = 1;
+        SdConvArgs a; a.in = dy; a.Cin = cout; a.w = P(e, w); a.out = out; a.Cout = cin; a.B = 1; a.T = Ri; a.taps = 1; a.chains = c.chains();
         return launch_sd_conv_dgrad(a, s);
     };
     auto ln_bwd = [&](const float* dy, const float* x, const float* stats, const std::string& p, float* dx) {

@@ -2,7 +2,7 @@
 // predictor, Vocos-training and discriminator kernels, written once: the lane / wave mapping (64 x 64, and 32 x 128 for GEMMs of
 // 32 rows), the K loop, the walk over the D fragment, the split-K weight-gradient kernel with its split rule, plane sum and
 // launcher, and two small helpers (grid_1d, block_sum256).  The conv kernels (sd_conv_kernel, pd_conv_kernel, rd_conv_kernel) keep
-// their own operand staging and epilogues.
+// their own operand staging and epilogues (sd_conv_kernel may run four such chains side by side over K: SdConvArgs::chains).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -16,7 +16,10 @@ namespace st {
 // nn.Conv1d weight is W (Cin_fwd = a.Cout, Cout_fwd = a.Cin, TAPS): A is staged straight from W, transposed and tap-flipped,
 // W'[ci][co][j] = W[co][ci][TAPS - 1 - j]; no bias, no epilogue activation, a.res (if set) is added after the output mask.
 // SD_MODE_FWD_PRE: the inference kernel that also writes the pre-activation (acc + bias) to a.pre for the backward.
-template <int TAPS, int MODE>
+// CHAINS: independent accumulators over the K loop, LDS chunk c into accumulator c % CHAINS, added in ascending order at the end.
+// 1 is the k-ordered chain; 4 (SdConvArgs::chains, taps = 1: the Vocos generator above dim 512, whose contractions run to 2048
+// terms through 12 blocks) quarters the length of every rounding chain.
+template <int TAPS, int MODE, int CHAINS = 1>
 __global__ __launch_bounds__(256) void sd_conv_kernel(SdConvArgs a) {
     constexpr int KC = kTileChunk * TAPS, WS = KC + 1, PAD = TAPS / 2, XS = kTile + TAPS - 1;
     __shared__ float Ws[kTile * WS];
@@ -26,8 +29,15 @@ __global__ __launch_bounds__(256) void sd_conv_kernel(SdConvArgs a) {
     const int t0 = blockIdx.x * kTile, co0 = blockIdx.y * kTile, b = blockIdx.z;
     const int Cin = a.Cin, Cout = a.Cout, T = a.T;
     const float* inb = a.in + (size_t)b * Cin * T;
-    f32x16 acc = tile_zero();
-    for (int ci0 = 0; ci0 < Cin; ci0 += kTileChunk) {
+    f32x16 accs[CHAINS];
+#pragma unroll
+    for (int q = 0; q < CHAINS; ++q) accs[q] = tile_zero();
+    for (int cq = 0; cq < Cin; cq += kTileChunk * CHAINS) {
+#pragma unroll
+      for (int q = 0; q < CHAINS; ++q) {
+        const int ci0 = cq + q * kTileChunk;
+        if (CHAINS > 1 && ci0 >= Cin) break;      // block-uniform
+        f32x16& acc = accs[q];
         for (int i = tid; i < kTile * KC; i += 256) {
             const int row = i / KC, kk = i - row * KC;
             const int co = co0 + row, ci = ci0 + kk / TAPS;
@@ -52,7 +62,11 @@ __global__ __launch_bounds__(256) void sd_conv_kernel(SdConvArgs a) {
         __syncthreads();
         tile_mfma<KC, 8>(acc, Ws, WS, l, [&](int k, int col) { const int cil = k / TAPS; return Xs[cil * XS + col + (k - cil * TAPS)]; });
         __syncthreads();
+      }
     }
+    f32x16 acc = accs[0];
+#pragma unroll
+    for (int q = 1; q < CHAINS; ++q) acc += accs[q];
     const int t = t0 + l.wt * 32 + l.r;
     if (t >= T) return;
     const float om = a.omask ? a.omask[(size_t)b * T + t] : 1.0f;
@@ -79,8 +93,11 @@ __global__ __launch_bounds__(256) void sd_conv_kernel(SdConvArgs a) {
 hipError_t launch_sd_conv(const SdConvArgs& a, hipStream_t s) {
     if (a.B < 1 || a.T < 1 || a.Cin < 1 || a.Cout < 1 || !a.in || !a.w || !a.bias || !a.out) return hipErrorInvalidValue;
     const dim3 grid((a.T + kTile - 1) / kTile, (a.Cout + kTile - 1) / kTile, a.B), blk(256);
+    if (a.chains != 1 && (a.chains != 4 || a.taps != 1)) return hipErrorInvalidValue;
     switch (a.taps) {
-        case 1: hipLaunchKernelGGL((sd_conv_kernel<1, SD_MODE_FWD>), grid, blk, 0, s, a); break;
+        case 1: if (a.chains == 4) hipLaunchKernelGGL((sd_conv_kernel<1, SD_MODE_FWD, 4>), grid, blk, 0, s, a);
+                else               hipLaunchKernelGGL((sd_conv_kernel<1, SD_MODE_FWD>), grid, blk, 0, s, a);
+                break;
         case 3: hipLaunchKernelGGL((sd_conv_kernel<3, SD_MODE_FWD>), grid, blk, 0, s, a); break;
         case 5: hipLaunchKernelGGL((sd_conv_kernel<5, SD_MODE_FWD>), grid, blk, 0, s, a); break;
         default: return hipErrorInvalidValue;
@@ -89,7 +106,7 @@ hipError_t launch_sd_conv(const SdConvArgs& a, hipStream_t s) {
 }
 
 hipError_t launch_sd_conv_pre(const SdConvArgs& a, hipStream_t s) {
-    if (a.B < 1 || a.T < 1 || a.Cin < 1 || a.Cout < 1 || !a.in || !a.w || !a.bias || !a.out || !a.pre) return hipErrorInvalidValue;
+    if (a.B < 1 || a.T < 1 || a.Cin < 1 || a.Cout < 1 || !a.in || !a.w || !a.bias || !a.out || !a.pre || a.chains != 1) return hipErrorInvalidValue;
     const dim3 grid((a.T + kTile - 1) / kTile, (a.Cout + kTile - 1) / kTile, a.B), blk(256);
     switch (a.taps) {
         case 1: hipLaunchKernelGGL((sd_conv_kernel<1, SD_MODE_FWD_PRE>), grid, blk, 0, s, a); break;
@@ -103,8 +120,11 @@ hipError_t launch_sd_conv_pre(const SdConvArgs& a, hipStream_t s) {
 hipError_t launch_sd_conv_dgrad(const SdConvArgs& a, hipStream_t s) {
     if (a.B < 1 || a.T < 1 || a.Cin < 1 || a.Cout < 1 || !a.in || !a.w || !a.out || a.addv || a.imask) return hipErrorInvalidValue;
     const dim3 grid((a.T + kTile - 1) / kTile, (a.Cout + kTile - 1) / kTile, a.B), blk(256);
+    if (a.chains != 1 && (a.chains != 4 || a.taps != 1)) return hipErrorInvalidValue;
     switch (a.taps) {
-        case 1: hipLaunchKernelGGL((sd_conv_kernel<1, SD_MODE_DGRAD>), grid, blk, 0, s, a); break;
+        case 1: if (a.chains == 4) hipLaunchKernelGGL((sd_conv_kernel<1, SD_MODE_DGRAD, 4>), grid, blk, 0, s, a);
+                else               hipLaunchKernelGGL((sd_conv_kernel<1, SD_MODE_DGRAD>), grid, blk, 0, s, a);
+                break;
         case 3: hipLaunchKernelGGL((sd_conv_kernel<3, SD_MODE_DGRAD>), grid, blk, 0, s, a); break;
         case 5: hipLaunchKernelGGL((sd_conv_kernel<5, SD_MODE_DGRAD>), grid, blk, 0, s, a); break;
         default: return hipErrorInvalidValue;

@@ -24,6 +24,7 @@ struct SdConvArgs {
     const float* w = nullptr; const float* bias = nullptr; const float* omask = nullptr;
     float* out = nullptr;
     int B = 0, Cin = 0, Cout = 0, T = 0, taps = 1, epi = SD_EPI_NONE;
+    int chains = 1;                  // launch_sd_conv / _dgrad, taps = 1: 4 = four interleaved accumulation chains over K (sd_conv_kernel)
     const float* res = nullptr;      // launch_sd_conv_dgrad only: added to the (masked) output, layout of out
     float* pre = nullptr;            // launch_sd_conv_pre only: receives bias + sum (the pre-activation), layout of out
 };

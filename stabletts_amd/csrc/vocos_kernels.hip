@@ -1,8 +1,10 @@
 // Vocos vocoder: the kernels around its GEMMs (vocoders/vocos/models/*.py; config.py:46-50 -> 128 -> 512, 8 ConvNeXt
-// blocks, ISTFT head n_fft 2048 / hop 512).  Everything here is row-wise HBM-bound work on time-major tensors
+// blocks, ISTFT head n_fft 2048 / hop 512; the Vocos trainer's vocoders/vocos/config.py:21-26 -> 128 -> 768, 12 blocks).  Everything here is row-wise HBM-bound work on time-major tensors
 // [utterance][frame][channel]; the five GEMM shapes run on the implicit-GEMM kernels of conv_gemm2_impl.h.
 #include "common.h"
 #include "vocos_launch.h"
+
+#include <type_traits>
 
 namespace st {
 
@@ -76,149 +78,218 @@ hipError_t launch_voc_segments(const VocUtt* utt, int B, int dw_frames, VocSeg* 
     return hipGetLastError();
 }
 
-// ---------------------------------------------------------------- LayerNorm(512, eps 1e-6, affine): one wave per row, lane = 8 channels
-struct Row8 { float4 a, b; };
-__device__ __forceinline__ Row8 ld8(const float* p) { Row8 r; r.a = *(const float4*)p; r.b = *(const float4*)(p + 4); return r; }
-__device__ __forceinline__ void voc_ln8(Row8& v, const Row8& w, const Row8& b) {
-    const float mean = wave_sum(v.a.x + v.a.y + v.a.z + v.a.w + v.b.x + v.b.y + v.b.z + v.b.w) * (1.0f / 512.0f);
-    v.a.x -= mean; v.a.y -= mean; v.a.z -= mean; v.a.w -= mean; v.b.x -= mean; v.b.y -= mean; v.b.z -= mean; v.b.w -= mean;
-    const float var = wave_sum(v.a.x * v.a.x + v.a.y * v.a.y + v.a.z * v.a.z + v.a.w * v.a.w +
-                               v.b.x * v.b.x + v.b.y * v.b.y + v.b.z * v.b.z + v.b.w * v.b.w) * (1.0f / 512.0f);
-    const float rs = 1.0f / sqrtf(var + 1e-6f);
-    v.a.x = v.a.x * rs * w.a.x + b.a.x; v.a.y = v.a.y * rs * w.a.y + b.a.y; v.a.z = v.a.z * rs * w.a.z + b.a.z; v.a.w = v.a.w * rs * w.a.w + b.a.w;
-    v.b.x = v.b.x * rs * w.b.x + b.b.x; v.b.y = v.b.y * rs * w.b.y + b.b.y; v.b.z = v.b.z * rs * w.b.z + b.b.z; v.b.w = v.b.w * rs * w.b.w + b.b.w;
-}
-template <class P>
-__device__ __forceinline__ void st16x8(void* p, const Row8& v) {
-    const uint2 lo = pack4<P>(v.a.x, v.a.y, v.a.z, v.a.w), hi = pack4<P>(v.b.x, v.b.y, v.b.z, v.b.w);
-    *(uint4*)p = make_uint4(lo.x, lo.y, hi.x, hi.y);
+// ---------------------------------------------------------------- row kernels: LayerNorm and depthwise conv + LayerNorm, one wave per row
+// A row of C = 64 * CPL channels (CPL = 8, 12, 16 channels per lane: dim 512, 768, 1024) lives in one wave as CPL / 4 float4 per lane.
+// Channel mapping.  CPL = 8 (dim 512) keeps the mapping it was written with: a contiguous run, lane = channels 8 lane .. 8 lane + 7,
+// one 16-byte store of its 8 16-bit outputs.  CPL = 12 and 16 take float4 j of a lane at channel (j * 64 + lane) * 4 instead: every
+// load of the wave is then one contiguous 1 KiB segment and every 16-bit store one contiguous 512 B segment, where a contiguous run of
+// 12 channels would make the lane's 24-byte output straddle 16-byte alignment and spread each load instruction over three times its
+// bytes.  The GEMM operand is row-major [row][C] either way, and the statistics are sums over the whole row.
+template <int CPL> struct VocRow { float v[CPL]; };
+
+// the lane's first channel, and the channel distance between its float4s: float4 j sits at voc_ch0 + j * voc_qs
+template <int CPL> __device__ __forceinline__ int voc_ch0(int lane) { return CPL == 8 ? lane * 8 : lane * 4; }
+template <int CPL> constexpr int voc_qs() { return CPL == 8 ? 4 : 256; }
+// channel of element i of a lane's VocRow, relative to voc_ch0
+template <int CPL> constexpr int voc_rel(int i) { return (i / 4) * voc_qs<CPL>() + (i & 3); }
+
+template <int CPL>
+__device__ __forceinline__ VocRow<CPL> voc_ld(const float* p /* the lane's first channel of the row */) {
+    VocRow<CPL> r;
+#pragma unroll
+    for (int j = 0; j < CPL / 4; ++j) {
+        const float4 q = *(const float4*)(p + j * voc_qs<CPL>());
+        r.v[4 * j] = q.x; r.v[4 * j + 1] = q.y; r.v[4 * j + 2] = q.z; r.v[4 * j + 3] = q.w;
+    }
+    return r;
 }
 
-template <class P>
-__global__ __launch_bounds__(256) void voc_ln_kernel(const float* x, const float* __restrict__ w, const float* __restrict__ b,
-                                                     long long rows, float* out32, void* out16, void* out16_lo) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long row = (long long)blockIdx.x * 4 + wave;
-    if (row >= rows) return;
-    const int ch = lane * 8;
-    Row8 v = ld8(x + (size_t)row * 512 + ch);
-    voc_ln8(v, ld8(w + ch), ld8(b + ch));
-    if (out32) { *(float4*)(out32 + (size_t)row * 512 + ch) = v.a; *(float4*)(out32 + (size_t)row * 512 + ch + 4) = v.b; }
-    if (out16) st16x8<P>((unsigned char*)out16 + ((size_t)row * 512 + ch) * 2, v);
-    if (out16_lo) {      // the low half of a split-precision operand pair: x - float(round16(x)), rounded once more
-        Row8 r;
-        r.a.x = v.a.x - (float)to16<P>(v.a.x); r.a.y = v.a.y - (float)to16<P>(v.a.y); r.a.z = v.a.z - (float)to16<P>(v.a.z); r.a.w = v.a.w - (float)to16<P>(v.a.w);
-        r.b.x = v.b.x - (float)to16<P>(v.b.x); r.b.y = v.b.y - (float)to16<P>(v.b.y); r.b.z = v.b.z - (float)to16<P>(v.b.z); r.b.w = v.b.w - (float)to16<P>(v.b.w);
-        st16x8<P>((unsigned char*)out16_lo + ((size_t)row * 512 + ch) * 2, r);
+// LayerNorm(C, eps 1e-6, affine) of the wave's row: mean and biased variance by two wave reductions
+template <int CPL>
+__device__ __forceinline__ void voc_ln_row(VocRow<CPL>& r, const VocRow<CPL>& w, const VocRow<CPL>& b) {
+    constexpr float inv_c = 1.0f / (64.0f * CPL);
+    float sum = r.v[0];
+#pragma unroll
+    for (int i = 1; i < CPL; ++i) sum = sum + r.v[i];
+    const float mean = wave_sum(sum) * inv_c;
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) r.v[i] -= mean;
+    float sq = r.v[0] * r.v[0];
+#pragma unroll
+    for (int i = 1; i < CPL; ++i) sq = sq + r.v[i] * r.v[i];
+    const float var = wave_sum(sq) * inv_c;
+    const float rs = 1.0f / sqrtf(var + 1e-6f);
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) r.v[i] = r.v[i] * rs * w.v[i] + b.v[i];
+}
+
+template <int CPL>
+__device__ __forceinline__ void voc_st32(float* p /* the lane's first channel of the row */, const VocRow<CPL>& r) {
+#pragma unroll
+    for (int j = 0; j < CPL / 4; ++j) *(float4*)(p + j * voc_qs<CPL>()) = make_float4(r.v[4 * j], r.v[4 * j + 1], r.v[4 * j + 2], r.v[4 * j + 3]);
+}
+
+template <class P, int CPL>
+__device__ __forceinline__ void voc_st16(void* p /* the lane's first channel of the 16-bit row */, const VocRow<CPL>& r) {
+    if (CPL == 8) {
+        const uint2 lo = pack4<P>(r.v[0], r.v[1], r.v[2], r.v[3]), hi = pack4<P>(r.v[4], r.v[5], r.v[6], r.v[7]);
+        *(uint4*)p = make_uint4(lo.x, lo.y, hi.x, hi.y);
+    } else {
+#pragma unroll
+        for (int j = 0; j < CPL / 4; ++j)
+            *(uint2*)((unsigned char*)p + j * voc_qs<CPL>() * 2) = pack4<P>(r.v[4 * j], r.v[4 * j + 1], r.v[4 * j + 2], r.v[4 * j + 3]);
     }
 }
 
-hipError_t launch_voc_ln(int dtype, const float* x, const float* w, const float* b, int64_t rows, float* out32, void* out16,
-                         void* out16_lo, hipStream_t s) {
-    const dim3 grid((unsigned)((rows + 3) / 4)), blk(256);
-    if (dtype == DT_BF16) hipLaunchKernelGGL((voc_ln_kernel<OpBF16>), grid, blk, 0, s, x, w, b, (long long)rows, out32, out16, out16_lo);
-    else                  hipLaunchKernelGGL((voc_ln_kernel<OpF16>), grid, blk, 0, s, x, w, b, (long long)rows, out32, out16, out16_lo);
+template <class P, int CPL>
+__global__ __launch_bounds__(256) void voc_ln_kernel(const float* x, const float* __restrict__ w, const float* __restrict__ b,
+                                                     long long rows, float* out32, void* out16, void* out16_lo) {
+    constexpr int C = 64 * CPL;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long row = (long long)blockIdx.x * 4 + wave;
+    if (row >= rows) return;
+    const int ch = voc_ch0<CPL>(lane);
+    VocRow<CPL> v = voc_ld<CPL>(x + (size_t)row * C + ch);
+    voc_ln_row<CPL>(v, voc_ld<CPL>(w + ch), voc_ld<CPL>(b + ch));
+    if (out32) voc_st32<CPL>(out32 + (size_t)row * C + ch, v);
+    if (out16) voc_st16<P, CPL>((unsigned char*)out16 + ((size_t)row * C + ch) * 2, v);
+    if (out16_lo) {      // the low half of a split-precision operand pair: x - float(round16(x)), rounded once more
+        VocRow<CPL> r;
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) r.v[i] = v.v[i] - (float)to16<P>(v.v[i]);
+        voc_st16<P, CPL>((unsigned char*)out16_lo + ((size_t)row * C + ch) * 2, r);
+    }
+}
+
+// C -> f(channels per lane) on the instantiation that runs it (st_create_vocoder admits no other width)
+template <class F>
+static hipError_t voc_for_cpl(int C, F&& f) {
+    switch (C) {
+        case 512:  f(std::integral_constant<int, 8>()); break;
+        case 768:  f(std::integral_constant<int, 12>()); break;
+        case 1024: f(std::integral_constant<int, 16>()); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 
+hipError_t launch_voc_ln(int dtype, const float* x, const float* w, const float* b, int64_t rows, int C, float* out32, void* out16,
+                         void* out16_lo, hipStream_t s) {
+    const dim3 grid((unsigned)((rows + 3) / 4)), blk(256);
+    return voc_for_cpl(C, [&](auto cpl) {
+        constexpr int CPL = decltype(cpl)::value;
+        if (dtype == DT_BF16) hipLaunchKernelGGL((voc_ln_kernel<OpBF16, CPL>), grid, blk, 0, s, x, w, b, (long long)rows, out32, out16, out16_lo);
+        else                  hipLaunchKernelGGL((voc_ln_kernel<OpF16, CPL>), grid, blk, 0, s, x, w, b, (long long)rows, out32, out16, out16_lo);
+    });
+}
+
 // ---------------------------------------------------------------- ConvNeXt block prologue: depthwise k = 7 conv + LayerNorm (module.py:35-37)
-// One wave per R consecutive frames of one utterance (R = 4; 1 for small batches), lane = 8 channels: the R + 6 fp32 residual
-// rows of the window are requested up front and the 56 taps of the lane's channels loaded once per wave.
-template <class P, int R>
+// One wave per R consecutive frames of one utterance (R = 4; 1 for small batches), lane = CPL channels: the R + 6 fp32 residual
+// rows of the window are requested up front and the 7 * CPL taps of the lane's channels loaded once per wave.  Live values per lane:
+// (R + 6) * CPL window + 7 * CPL taps + 3 * CPL bias / LayerNorm affine + CPL accumulators -- at R = 4 168 for CPL = 8, 252 for 12 and
+// 336 for 16, which the unified register file of one wave per SIMD (launch bound 256 threads: 512 registers) holds without scratch.
+template <class P, int CPL, int R>
 __device__ __forceinline__ void voc_dwconv_ln_group(const float* __restrict__ xi /* the utterance's frame 0, + ch */, int T, int t0,
                                                     const float* __restrict__ dw, const float* __restrict__ dbias,
                                                     const float* __restrict__ w, const float* __restrict__ b, int ch,
                                                     unsigned char* hi /* h16 of the utterance's frame 0, + ch */) {
-    const Row8 zero = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
-    Row8 win[R + 6];          // every row of the window is requested before anything is computed: one exposed latency per wave
+    constexpr int C = 64 * CPL;
+    VocRow<CPL> zero;
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) zero.v[i] = 0.0f;
+    VocRow<CPL> win[R + 6];   // every row of the window is requested before anything is computed: one exposed latency per wave
 #pragma unroll
     for (int j = 0; j < R + 6; ++j) {
         const int t = t0 - 3 + j;
-        win[j] = (t >= 0 && t < T) ? ld8(xi + (size_t)t * 512) : zero;      // zero padding of nn.Conv1d(padding=3)
+        win[j] = (t >= 0 && t < T) ? voc_ld<CPL>(xi + (size_t)t * C) : zero;      // zero padding of nn.Conv1d(padding=3)
     }
-    float wt[8][7];
+    float wt[CPL][7];
 #pragma unroll
-    for (int i = 0; i < 8; ++i)
+    for (int i = 0; i < CPL; ++i)
 #pragma unroll
-        for (int j = 0; j < 7; ++j) wt[i][j] = dw[(size_t)(ch + i) * 7 + j];
-    const Row8 bias = ld8(dbias + ch), lw = ld8(w + ch), lb = ld8(b + ch);
+        for (int j = 0; j < 7; ++j) wt[i][j] = dw[(size_t)(ch + voc_rel<CPL>(i)) * 7 + j];
+    const VocRow<CPL> bias = voc_ld<CPL>(dbias + ch), lw = voc_ld<CPL>(w + ch), lb = voc_ld<CPL>(b + ch);
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const int t = t0 + r;
         if (t >= T) break;                          // wave-uniform
-        Row8 acc = bias;
+        VocRow<CPL> acc = bias;
 #pragma unroll
-        for (int j = 0; j < 7; ++j) {
-            const Row8& v = win[r + j];
-            acc.a.x += wt[0][j] * v.a.x; acc.a.y += wt[1][j] * v.a.y; acc.a.z += wt[2][j] * v.a.z; acc.a.w += wt[3][j] * v.a.w;
-            acc.b.x += wt[4][j] * v.b.x; acc.b.y += wt[5][j] * v.b.y; acc.b.z += wt[6][j] * v.b.z; acc.b.w += wt[7][j] * v.b.w;
-        }
-        voc_ln8(acc, lw, lb);
-        st16x8<P>(hi + (size_t)t * 512 * 2, acc);
+        for (int j = 0; j < 7; ++j)
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) acc.v[i] += wt[i][j] * win[r + j].v[i];
+        voc_ln_row<CPL>(acc, lw, lb);
+        voc_st16<P, CPL>(hi + (size_t)t * C * 2, acc);
     }
 }
 
-template <class P, int R>
+template <class P, int CPL, int R>
 __global__ __launch_bounds__(256) void voc_dwconv_ln_kernel(const float* __restrict__ x, const float* __restrict__ dw,
                                                             const float* __restrict__ dbias, const float* __restrict__ w,
                                                             const float* __restrict__ b, int T, int groups_per_item, long long n_groups,
                                                             void* h16) {
+    constexpr int C = 64 * CPL;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long grp = (long long)blockIdx.x * 4 + wave;
     if (grp >= n_groups) return;
     const int item = (int)(grp / groups_per_item);
     const int t0 = (int)(grp - (long long)item * groups_per_item) * R;
-    const int ch = lane * 8;
-    voc_dwconv_ln_group<P, R>(x + (size_t)item * T * 512 + ch, T, t0, dw, dbias, w, b, ch,
-                              (unsigned char*)h16 + ((size_t)item * T * 512 + ch) * 2);
+    const int ch = voc_ch0<CPL>(lane);
+    voc_dwconv_ln_group<P, CPL, R>(x + (size_t)item * T * C + ch, T, t0, dw, dbias, w, b, ch,
+                                   (unsigned char*)h16 + ((size_t)item * T * C + ch) * 2);
 }
 
 // Ragged batch: wave = one entry of the group table (R frames of ONE utterance, voc_segments_kernel), read through scalar
 // registers; x and h16 are packed rows.
-template <class P, int R>
+template <class P, int CPL, int R>
 __global__ __launch_bounds__(256) void voc_dwconv_ln_ragged_kernel(const float* __restrict__ x, const float* __restrict__ dw,
                                                                    const float* __restrict__ dbias, const float* __restrict__ w,
                                                                    const float* __restrict__ b, const VocSeg* __restrict__ groups,
                                                                    int n_groups, void* h16) {
+    constexpr int C = 64 * CPL;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long long grp = (long long)blockIdx.x * 4 + wave;
     if (grp >= n_groups) return;
     const VocSeg sg = groups[grp];
-    const int ch = lane * 8;
-    voc_dwconv_ln_group<P, R>(x + (size_t)sg.row0 * 512 + ch, sg.T, sg.t0, dw, dbias, w, b, ch,
-                              (unsigned char*)h16 + ((size_t)sg.row0 * 512 + ch) * 2);
+    const int ch = voc_ch0<CPL>(lane);
+    voc_dwconv_ln_group<P, CPL, R>(x + (size_t)sg.row0 * C + ch, sg.T, sg.t0, dw, dbias, w, b, ch,
+                                   (unsigned char*)h16 + ((size_t)sg.row0 * C + ch) * 2);
 }
 
-template <class P, int R>
+template <class P, int CPL, int R>
 static void launch_dw(const float* x, const float* dw, const float* dbias, const float* w, const float* b, int B, int T, void* h16, hipStream_t s) {
     const int gpi = (T + R - 1) / R;
     const long long n_groups = (long long)B * gpi;
-    hipLaunchKernelGGL((voc_dwconv_ln_kernel<P, R>), dim3((unsigned)((n_groups + 3) / 4)), dim3(256), 0, s, x, dw, dbias, w, b, T, gpi, n_groups, h16);
+    hipLaunchKernelGGL((voc_dwconv_ln_kernel<P, CPL, R>), dim3((unsigned)((n_groups + 3) / 4)), dim3(256), 0, s, x, dw, dbias, w, b, T, gpi, n_groups, h16);
 }
 
 hipError_t launch_voc_dwconv_ln(int dtype, const float* x, const float* dw, const float* dbias, const float* w, const float* b,
-                                int B, int T, void* h16, hipStream_t s) {
+                                int B, int T, int C, void* h16, hipStream_t s) {
     const bool big = voc_dw_frames((int64_t)B * T) == 4;      // small batches: one frame per wave (more waves than a few CUs' worth)
-    if (dtype == DT_BF16) { if (big) launch_dw<OpBF16, 4>(x, dw, dbias, w, b, B, T, h16, s); else launch_dw<OpBF16, 1>(x, dw, dbias, w, b, B, T, h16, s); }
-    else                  { if (big) launch_dw<OpF16, 4>(x, dw, dbias, w, b, B, T, h16, s); else launch_dw<OpF16, 1>(x, dw, dbias, w, b, B, T, h16, s); }
-    return hipGetLastError();
+    return voc_for_cpl(C, [&](auto cpl) {
+        constexpr int CPL = decltype(cpl)::value;
+        if (dtype == DT_BF16) { if (big) launch_dw<OpBF16, CPL, 4>(x, dw, dbias, w, b, B, T, h16, s); else launch_dw<OpBF16, CPL, 1>(x, dw, dbias, w, b, B, T, h16, s); }
+        else                  { if (big) launch_dw<OpF16, CPL, 4>(x, dw, dbias, w, b, B, T, h16, s); else launch_dw<OpF16, CPL, 1>(x, dw, dbias, w, b, B, T, h16, s); }
+    });
 }
 
-template <class P, int R>
+template <class P, int CPL, int R>
 static void launch_dw_ragged(const float* x, const float* dw, const float* dbias, const float* w, const float* b, const VocSeg* groups,
                              int n_groups, void* h16, hipStream_t s) {
-    hipLaunchKernelGGL((voc_dwconv_ln_ragged_kernel<P, R>), dim3((unsigned)(((long long)n_groups + 3) / 4)), dim3(256), 0, s, x, dw, dbias, w, b,
+    hipLaunchKernelGGL((voc_dwconv_ln_ragged_kernel<P, CPL, R>), dim3((unsigned)(((long long)n_groups + 3) / 4)), dim3(256), 0, s, x, dw, dbias, w, b,
                        groups, n_groups, h16);
 }
 
 int voc_dw_frames(int64_t rows) { return rows >= 8192 ? 4 : 1; }
 
 hipError_t launch_voc_dwconv_ln_ragged(int dtype, const float* x, const float* dw, const float* dbias, const float* w, const float* b,
-                                       const VocSeg* groups, int n_groups, int dw_frames, void* h16, hipStream_t s) {
+                                       const VocSeg* groups, int n_groups, int dw_frames, int C, void* h16, hipStream_t s) {
     const bool big = dw_frames == 4;
-    if (dtype == DT_BF16) { if (big) launch_dw_ragged<OpBF16, 4>(x, dw, dbias, w, b, groups, n_groups, h16, s); else launch_dw_ragged<OpBF16, 1>(x, dw, dbias, w, b, groups, n_groups, h16, s); }
-    else                  { if (big) launch_dw_ragged<OpF16, 4>(x, dw, dbias, w, b, groups, n_groups, h16, s); else launch_dw_ragged<OpF16, 1>(x, dw, dbias, w, b, groups, n_groups, h16, s); }
-    return hipGetLastError();
+    return voc_for_cpl(C, [&](auto cpl) {
+        constexpr int CPL = decltype(cpl)::value;
+        if (dtype == DT_BF16) { if (big) launch_dw_ragged<OpBF16, CPL, 4>(x, dw, dbias, w, b, groups, n_groups, h16, s); else launch_dw_ragged<OpBF16, CPL, 1>(x, dw, dbias, w, b, groups, n_groups, h16, s); }
+        else                  { if (big) launch_dw_ragged<OpF16, CPL, 4>(x, dw, dbias, w, b, groups, n_groups, h16, s); else launch_dw_ragged<OpF16, CPL, 1>(x, dw, dbias, w, b, groups, n_groups, h16, s); }
+    });
 }
 
 // ---------------------------------------------------------------- ISTFT head (head.py:103-116, ISTFT.forward :50-57)

@@ -6,7 +6,8 @@
 
 namespace st {
 
-constexpr int kVocDim = 512;        // backbone width the row kernels are built for (config.py:48)
+// backbone widths the row kernels are built for: 64 lanes x 8, 12 or 16 channels (config.py:48 -> 512; vocoders/vocos/config.py:23 -> 768)
+constexpr bool voc_dim_supported(int C) { return C == 512 || C == 768 || C == 1024; }
 constexpr int kVocNfft = 2048;      // config.py:6
 constexpr int kVocHop = 512;        // config.py:8
 constexpr int kVocBins = kVocNfft / 2 + 1;
@@ -14,12 +15,12 @@ constexpr int kVocHeadPlane = 1152; // channel pitch of the magnitude / phase pl
 
 // A16[b*T + t][j*M + c] = mel[b][c][t + j - 3]  (0 outside [0, T)): the k = 7 embed convolution as one GEMM with K = 7*M
 hipError_t launch_voc_im2col7(int dtype, const float* mel, int B, int M, int T, void* a16, hipStream_t s);
-// y = LayerNorm_512(x) * w + b  (eps 1e-6): out32 and/or out16 (may alias x for out32)
-hipError_t launch_voc_ln(int dtype, const float* x, const float* w, const float* b, int64_t rows, float* out32, void* out16,
+// y = LayerNorm_C(x) * w + b  (eps 1e-6, C = 512, 768 or 1024; rows of C floats): out32 and/or out16 (may alias x for out32)
+hipError_t launch_voc_ln(int dtype, const float* x, const float* w, const float* b, int64_t rows, int C, float* out32, void* out16,
                          void* out16_lo, hipStream_t s);      // out16_lo (optional): x - float(round16(x)), the low half of a split-precision operand
-// h16 = LayerNorm_512(dwconv7(x) + bias) * w + b   per utterance (rows of different items never mix); dw: [512][7]
+// h16 = LayerNorm_C(dwconv7(x) + bias) * w + b   per utterance (rows of different items never mix); dw: [C][7]
 hipError_t launch_voc_dwconv_ln(int dtype, const float* x, const float* dw, const float* dbias, const float* w, const float* b,
-                                int B, int T, void* h16, hipStream_t s);
+                                int B, int T, int C, void* h16, hipStream_t s);
 // head output rows [rows][2 * kVocHeadPlane] fp32 (log-magnitude plane, phase plane) -> windowed frames [rows][2048]
 hipError_t launch_voc_spec_ifft(const float* head, const float* window, int64_t rows, float* frames, hipStream_t s);
 // overlap-add with hop 512, "same" trim, envelope normalisation: audio[b][T*512]
@@ -32,14 +33,14 @@ struct VocUtt { int row0, T, tile0, grp0; };     // first packed row, frames, fi
 struct VocSeg { int row0, t0, T, item; };        // frames t0 .. of utterance `item`, whose T frames start at packed row row0
 constexpr long long kVocMaxPaddedFrames = (1ll << 23) - 1;      // B * Tmax of one ragged overlap-add launch
 
-int voc_dw_frames(int64_t rows);      // frames per wave of the depthwise kernel (4 from 8192 rows, else 1): the group length
+int voc_dw_frames(int64_t rows);      // frames per wave of the depthwise kernel (4 from 8192 rows, else 1, at every width): the group length
 // tiles: sum ceil(T_b / 64) entries, groups: sum ceil(T_b / dw_frames) entries
 hipError_t launch_voc_segments(const VocUtt* utt, int B, int dw_frames, VocSeg* tiles, VocSeg* groups, hipStream_t s);
 // launch_voc_im2col7 on frames 0 .. T_b - 1 of each utterance (taps outside are zero), into packed rows
 hipError_t launch_voc_im2col7_ragged(int dtype, const float* mel, const VocSeg* tiles, int n_tiles, int M, int Tmax, void* a16, hipStream_t s);
 // launch_voc_dwconv_ln on packed rows: a window never leaves its utterance; same arithmetic as the dense kernel
 hipError_t launch_voc_dwconv_ln_ragged(int dtype, const float* x, const float* dw, const float* dbias, const float* w, const float* b,
-                                       const VocSeg* groups, int n_groups, int dw_frames, void* h16, hipStream_t s);
+                                       const VocSeg* groups, int n_groups, int dw_frames, int C, void* h16, hipStream_t s);
 // launch_voc_overlap_add on packed frames; audio[b][s] = 0 for s >= T_b * 512 (every sample of the padded audio is written)
 hipError_t launch_voc_overlap_add_ragged(const float* frames, const float* window, const VocUtt* utt, int B, int Tmax, float* audio, hipStream_t s);
 

@@ -2,7 +2,8 @@
 module tree, state_dict keys, inference path -- but ``Vocos.native_training = True``: its parameters require grad, and a
 grad-enabled call in train mode runs the native fp32 training forward (st_vocos_train_forward, which keeps its activations) with
 st_vocos_train_backward as its backward: d audio -> the gradient of every parameter and of the mel, with no torch kernel between
-the mel and the gradients.  This is the generator of vocoders/vocos/train.py:94,115,128; the discriminators (torch, or the native multi-period one of
+the mel and the gradients.  This is the generator of vocoders/vocos/train.py:94,115,128, at the trainer's own configuration
+(vocoders/vocos/config.py:21-26: dim 768, intermediate_dim 2048, 12 layers) as at the inference preset (dim 512, 768 or 1024); the discriminators (torch, or the native multi-period one of
 ``stabletts_amd.discriminator``) consume the returned waveform as an ordinary autograd tensor.
 
 The training path is fp32 throughout (fp32-input MFMA GEMMs), so its waveform is NOT bitwise the inference waveform, whose GEMMs

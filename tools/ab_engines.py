@@ -6,7 +6,9 @@ process's hardware queues, and a 4-part engine next to a 2-part one measured 30.
 separate processes, alternating (tools/r04b_session10.sh).  A configuration may also name its own BUILD of the library
 (STABLETTS_HIP_LIB=/path/variant.so, e.g. ST_BUILD_DEFS=-DST_NT_DMA=1 ST_BUILD_OUT=... python -m stabletts_amd.build): both libraries are
 loaded into the one process.     usage: python tools/ab_engines.py "" "ST_FUSED_FFN=3" [rounds] [per_round]
-AB_WORKLOAD=ffgan:BxT times FireflyGANBase.forward (st_ffgan_forward, default configuration, f16) on a (B, 128, T) mel instead of the solve."""
+AB_WORKLOAD=ffgan:BxT times FireflyGANBase.forward (st_ffgan_forward, default configuration, f16) on a (B, 128, T) mel instead of the solve.
+AB_WORKLOAD=vocos:BxT times Vocos.forward (st_vocos_forward, the preset 512 / 1536 / 8, f16) on a (B, 128, T) mel; AB_WORKLOAD=vocos:bucket
+times Vocos.forward_ragged on tools/vocos_bench.py's bucket of 32 utterances of U{600..1000} frames."""
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -20,6 +22,20 @@ per = int(sys.argv[4]) if len(sys.argv) > 4 else 3
 RAGGED = os.environ.get("AB_RAGGED") == "1"
 WORKLOAD = os.environ.get("AB_WORKLOAD", "solve")
 FFGAN = WORKLOAD.startswith("ffgan:")
+VOCOS = WORKLOAD.startswith("vocos:")
+if VOCOS:
+    import types
+    import numpy as np
+    from oracle import vocos_oracle as vo
+    from stabletts_amd.vocos import Vocos
+    vc = vo.VocosConfig
+    voc_sd = {k: torch.from_numpy(v) for k, v in vo.make_vocos_state_dict(77).items()}
+    if WORKLOAD[6:] == "bucket":
+        voc_len = np.random.default_rng(4).integers(600, 1001, 32).tolist()
+        voc_mel = torch.from_numpy(vo.make_mel(32, max(voc_len), 3)).cuda()
+    else:
+        voc_len = None
+        voc_mel = torch.from_numpy(vo.make_mel(*(int(v) for v in WORKLOAD[6:].split("x")), 3)).cuda()
 if FFGAN:
     from tests import ffgan_restatement as ffr
     from stabletts_amd.ffgan import FireflyGANBase
@@ -36,7 +52,11 @@ for c in cfgs:
     for k, v in c.items(): os.environ[k] = v
     # a configuration may name its own build of the library (STABLETTS_HIP_LIB=path): an Engine keeps the CDLL it was created with
     _stlib.LIB_PATH, _stlib._lib = c.get("STABLETTS_HIP_LIB", _default_lib), None
-    if FFGAN:
+    if VOCOS:
+        d = Vocos(types.SimpleNamespace(input_channels=vc.input_channels, dim=vc.dim, intermediate_dim=vc.intermediate_dim, num_layers=vc.num_layers),
+                  types.SimpleNamespace(n_fft=vc.n_fft, hop_length=vc.hop_length))
+        d.load_state_dict(voc_sd); d = d.cuda(); d.engine()
+    elif FFGAN:
         d = FireflyGANBase(); d.load_state_dict(ff_sd); d = d.cuda().eval(); d.engine()
     else:
         d = CFMDecoder(128, 128, 256, 128, 1024, 4, 6, 3, 0.1, 256).cuda()
@@ -46,7 +66,7 @@ for c in cfgs:
 def run(d):
     c = cfgs[decs.index(d)]          # the configuration's variables are also visible at solve time (ST_SPLIT is read per call)
     for k, v in c.items(): os.environ[k] = v
-    out = d(ff_mel) if FFGAN else d(g["mu"], g["mask"], 10, 1.0, g["c"], "euler", kw, z=g["z"])
+    out = (d.forward_ragged(voc_mel, voc_len) if voc_len else d(voc_mel)) if VOCOS else d(ff_mel) if FFGAN else d(g["mu"], g["mask"], 10, 1.0, g["c"], "euler", kw, z=g["z"])
     for k in c: del os.environ[k]
     return out
 outs = [run(d) for d in decs]

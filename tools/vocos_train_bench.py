@@ -6,7 +6,10 @@ train.py:94,115,128 -- forward, the seven-scale log-mel L1 loss (native spectrog
 backward.  The legs are paired and interleaved after a warm-up; prints one JSON line per (workload, B, T) with the medians and
 the per-pair ratio torch / native, and, with --kernels, the native leg's largest kernels (torch.profiler).
 
-    python tools/vocos_train_bench.py [--steps 30] [--kernels]
+    python tools/vocos_train_bench.py [--steps 30] [--kernels] [--dim D] [--intermediate-dim F] [--num-layers L]
+
+The default generator is the inference preset (512 / 1536 / 8); --dim 768 --intermediate-dim 2048 --num-layers 12 is the one the
+reference's trainer builds (vocoders/vocos/config.py:21-26).
 """
 import argparse
 import json
@@ -49,13 +52,17 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--dim", type=int)
+    ap.add_argument("--intermediate-dim", type=int)
+    ap.add_argument("--num-layers", type=int)
     a = ap.parse_args()
     from oracle import vocos_oracle as vo
     from stabletts_amd.audio_train import LogMelSpectrogram
     from stabletts_amd.vocos_train import Vocos
     from tests import vocos_vjp_restatement as R
-    c = vo.VocosConfig
-    sd = vo.make_vocos_state_dict(7)
+    c = vo.vocos_config(**{k: v for k, v in (("dim", a.dim), ("intermediate_dim", a.intermediate_dim), ("num_layers", a.num_layers)) if v})
+    sd = vo.make_vocos_state_dict(7, c)
+    gen = {"dim": c.dim, "intermediate_dim": c.intermediate_dim, "num_layers": c.num_layers}
     voc = Vocos(types.SimpleNamespace(input_channels=c.input_channels, dim=c.dim, intermediate_dim=c.intermediate_dim, num_layers=c.num_layers),
                 types.SimpleNamespace(n_fft=c.n_fft, hop_length=c.hop_length))
     voc.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
@@ -86,8 +93,8 @@ def main():
         def ref_step():
             zero(); mel_loss(y, R.torch_vocos(tp, mel, c.num_layers).unsqueeze(1)).backward()
 
-        print(json.dumps({"workload": "vocos_forward_backward", "B": B, "T": T, "steps": a.steps, **_pair(nat, ref, a.warmup, a.steps)}), flush=True)
-        print(json.dumps({"workload": "vocos_mel_loss_generator_step", "B": B, "T": T, "steps": a.steps,
+        print(json.dumps({"workload": "vocos_forward_backward", **gen, "B": B, "T": T, "steps": a.steps, **_pair(nat, ref, a.warmup, a.steps)}), flush=True)
+        print(json.dumps({"workload": "vocos_mel_loss_generator_step", **gen, "B": B, "T": T, "steps": a.steps,
                           **_pair(nat_step, ref_step, a.warmup, a.steps)}), flush=True)
         if a.kernels:
             from torch.profiler import ProfilerActivity, profile
