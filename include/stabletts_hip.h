@@ -251,18 +251,22 @@ int st_cfm_loss_scratch_floats(void);
 
 /* Replaces Vocos.__init__(VocosConfig(), MelConfig()) (vocoders/vocos/models/model.py:11-15, config.py:4-19,46-50). */
 typedef struct st_vocos_config {
-    int32_t input_channels;    /* n_mels, config.py:47 (multiple of 64) */
+    int32_t input_channels;    /* n_mels, config.py:47; native kernels: a multiple of 16 up to 192 (e.g. 80, 96, 128) */
     int32_t dim;               /* config.py:48; native kernels: 512, 768 (the Vocos trainer's, vocoders/vocos/config.py:23) or 1024 */
     int32_t intermediate_dim;  /* config.py:49 (multiple of 256) */
     int32_t num_layers;        /* config.py:50 (1..32) */
-    int32_t n_fft;             /* MelConfig.n_fft, config.py:6; native kernels: 2048 */
-    int32_t hop_length;        /* MelConfig.hop_length, config.py:8; native kernels: 512 */
+    int32_t n_fft;             /* MelConfig.n_fft, config.py:6; native kernels: 256, 512, 1024 or 2048 */
+    int32_t hop_length;        /* MelConfig.hop_length, config.py:8; native kernels: n_fft / 4 */
     int32_t operand_dtype;     /* ST_OPERAND_* of the GEMM operands (accumulation, LayerNorms, residual stream, ISTFT: fp32) */
 } st_vocos_config;
 
 /* The handle takes the parameters of Vocos.state_dict() under their reference names ("backbone.embed.weight", ...,
  * "backbone.convnext.<i>.gamma", ..., "head.out.bias", "head.istft.window") through st_load_param / st_finalize and
- * is destroyed with st_destroy.  The decoder / text-encoder entry points reject it and vice versa. */
+ * is destroyed with st_destroy.  The decoder / text-encoder entry points reject it and vice versa.
+ * Accepted: n_fft 256, 512, 1024 or 2048 with hop_length == n_fft / 4 (44.1 kHz: 2048 / 512; 22.05-24 kHz: 1024 / 256; 16 kHz:
+ * 512 / 128), input_channels a multiple of 16 up to 192, dim 512, 768 or 1024, intermediate_dim a multiple of 256.  Anything else
+ * -- another n_fft, hop_length != n_fft / 4, a width such as Vocos-24k's 100 -- is ST_ERR_UNSUPPORTED before a device is touched,
+ * with a message that states the rule. */
 int st_create_vocoder(const st_vocos_config* cfg, int device, st_engine** out);
 
 /* Replaces Vocos.forward(x) (model.py:17-20) = ISTFTHead(VocosBackbone(x)) (backbone.py:50-56, head.py:93-117 with
@@ -299,7 +303,9 @@ int st_vocos_forward_ragged(st_engine* e, const float* mel, const int64_t* lengt
  * (st_train_grad_numel() floats in the layout of st_train_grad_offset: 64-byte aligned slices, the gaps and the window's slice are
  * not written) and, unless d_mel is NULL, d loss / d mel (B, input_channels, T).  B and T must be the forward's; without a held
  * forward the call fails with ST_ERR_STATE.  No atomics, every reduction in a fixed order: gradients are bitwise repeatable.
- * One batch per call (no chunking): B * T * max(7 input_channels, intermediate_dim, 2304) < 2^31 and B <= 65535, else ST_ERR_INVALID. */
+ * One batch per call (no chunking): B * T * max(7 input_channels, intermediate_dim, 2304) < 2^31 and B <= 65535, else ST_ERR_INVALID.
+ * Training is built for n_fft == 2048, hop_length == 512 and input_channels 64, 128 or 192: on a handle of any other configuration
+ * (which st_create_vocoder accepts for inference) both entries return ST_ERR_UNSUPPORTED before any allocation or launch. */
 int st_vocos_train_forward(st_engine* e, const float* mel, float* audio, int B, int T, void* stream);
 int st_vocos_train_backward(st_engine* e, const float* d_audio, float* d_mel /* nullable */, float* grad_flat, int B, int T, void* stream);
 

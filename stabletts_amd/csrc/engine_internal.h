@@ -243,6 +243,7 @@ extern std::string g_create_error;
 int new_handle(Kind kind, int device, st_engine** out);
 void expect(st_engine* e, const std::string& name, std::vector<int64_t> shape);      // one row of the parameter table
 int vocos_finalize(st_engine* e);
+const st_vocos_config& vocos_config_of(const st_engine* e);      // the st_vocos_config of a KIND_VOCODER handle
 int pack_all(st_engine* e, hipStream_t s);
 // recorder / replayer of a PackList: begin -> the pk_* calls (individual launch + record) -> end (upload); replay = one launch
 bool pk_replay(st_engine* e, st_engine::PackList& L, hipStream_t s, int* rc);      // true: the list was replayed (or failed: *rc)

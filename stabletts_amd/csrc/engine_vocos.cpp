@@ -43,8 +43,9 @@ void vocos_build_params(st_engine* e, const st_vocos_config& c) {
 }
 
 // st_finalize of a vocoder handle: 16-bit GEMM weights.  Linear weights (out, in) are k = 1 convolutions; the k = 7
-// embed convolution packs as [cout][tap][cin] = the K order of launch_voc_im2col7's rows.  The head's 2050 output
-// rows are laid out as two planes of kVocHeadPlane rows (log-magnitude 0..1024, phase 0..1024, zero rows between).
+// embed convolution packs as [cout][tap][cin] = the K order of launch_voc_im2col7's rows, each row padded with zeros to
+// voc_im2col_pitch(M).  The head's n_fft + 2 output rows are laid out as two planes of voc_head_plane(n_fft) rows
+// (log-magnitude 0..n_fft/2, phase 0..n_fft/2, zero rows between): 1152 at n_fft 2048, 640 / 384 / 256 at 1024 / 512 / 256.
 int vocos_finalize(st_engine* e) {
     VocosState* v = e->voc;
     const st_vocos_config& c = v->cfg;
@@ -71,8 +72,25 @@ int vocos_finalize(st_engine* e) {
         return ST_OK;
     };
     int rc;
-    if ((rc = pack(v->embed, "backbone.embed.weight", "backbone.embed.bias", C, M, 7))) return rc;
-    v->embed.cin = 7 * M; v->embed.taps = 1;        // consumed as a k = 1 GEMM over the im2col rows
+    const int Kp = voc_im2col_pitch(M);
+    if (Kp == 7 * M) {
+        if ((rc = pack(v->embed, "backbone.embed.weight", "backbone.embed.bias", C, M, 7))) return rc;
+    } else {        // M % 64 != 0: [cout][7 M] packed into a staging buffer, then copied into rows of pitch Kp whose tail stays zero
+        Conv& cv = v->embed;
+        cv.cout = C; cv.split = false;
+        if ((rc = dev_alloc(e, &cv.w, (size_t)C * Kp * 2))) return rc;
+        if ((rc = dev_alloc(e, (void**)&cv.bias, (size_t)C * 4))) return rc;
+        void* stage = nullptr;
+        HIPCHK(e, hipMalloc(&stage, (size_t)C * 7 * M * 2));
+        hipError_t he = launch_pack_weight(e->dt, P(e, "backbone.embed.weight"), C, M, 7, 0, M, stage, 0, M, 0, M, 0, s);
+        if (he == hipSuccess) he = hipMemsetAsync(cv.w, 0, (size_t)C * Kp * 2, s);
+        if (he == hipSuccess) he = hipMemcpy2DAsync(cv.w, (size_t)Kp * 2, stage, (size_t)7 * M * 2, (size_t)7 * M * 2, C, hipMemcpyDeviceToDevice, s);
+        if (he == hipSuccess) he = hipStreamSynchronize(s);
+        hipFree(stage);
+        HIPCHK(e, he);
+        HIPCHK(e, hipMemcpyAsync(cv.bias, P(e, "backbone.embed.bias"), (size_t)C * 4, hipMemcpyDeviceToDevice, s));
+    }
+    v->embed.cin = Kp; v->embed.taps = 1;        // consumed as a k = 1 GEMM over the im2col rows
     v->pw1.assign(L, Conv()); v->pw2.assign(L, Conv());
     for (int i = 0; i < L; ++i) {
         if ((rc = pack_wsplit(v->pw1[i], vblk(i) + "pwconv1.weight", vblk(i) + "pwconv1.bias", F, C))) return rc;
@@ -80,7 +98,7 @@ int vocos_finalize(st_engine* e) {
     }
     {
         Conv& h = v->head;
-        const int bins = c.n_fft / 2 + 1, planes = 2 * kVocHeadPlane;
+        const int bins = c.n_fft / 2 + 1, plane = voc_head_plane(c.n_fft), planes = 2 * plane;
         // split-precision operands (round 5), as for the decoder's in_proj / final_proj: the head's output x feeds exp(x) -- an absolute
         // error of x is a RELATIVE error of the magnitude -- so the 16-bit rounding of its operands reached the waveform un-attenuated
         // (f16: hidden 4.8e-4 -> audio 1.1e-3).  K = [h_hi | h_lo | h_hi] against [W_hi | W_hi | W_lo]: 3x the MFMA work of one small GEMM.
@@ -92,14 +110,16 @@ int vocos_finalize(st_engine* e) {
         const float* W = P(e, "head.out.weight"); const float* Bv = P(e, "head.out.bias");
         for (int part = 0; part < 2; ++part) {       // head.py:104: mag, p = x.chunk(2, dim=1)
             for (int k3 = 0; k3 < 3; ++k3)
-                HIPCHK(e, launch_pack_weight(e->dt, W + (size_t)part * bins * C, bins, C, 1, 0, C, h.w, part * kVocHeadPlane, 3 * C, k3 * C, C, k3 == 2, s));
-            HIPCHK(e, hipMemcpyAsync(h.bias + part * kVocHeadPlane, Bv + (size_t)part * bins, (size_t)bins * 4, hipMemcpyDeviceToDevice, s));
+                HIPCHK(e, launch_pack_weight(e->dt, W + (size_t)part * bins * C, bins, C, 1, 0, C, h.w, part * plane, 3 * C, k3 * C, C, k3 == 2, s));
+            HIPCHK(e, hipMemcpyAsync(h.bias + part * plane, Bv + (size_t)part * bins, (size_t)bins * 4, hipMemcpyDeviceToDevice, s));
         }
     }
     HIPCHK(e, hipDeviceSynchronize());
     e->finalized = true;
     return ST_OK;
 }
+
+const st_vocos_config& vocos_config_of(const st_engine* e) { return e->voc->cfg; }
 
 void vocos_destroy(st_engine* e) {
     VocosState* v = e->voc;
@@ -120,8 +140,9 @@ int st_create_vocoder(const st_vocos_config* cfg, int device, st_engine** out) {
     if (cfg->operand_dtype != ST_OPERAND_BF16 && cfg->operand_dtype != ST_OPERAND_F16) return bad("operand_dtype", ST_ERR_INVALID);
     // limits of this native build
     if (!voc_dim_supported(cfg->dim)) return bad("native vocoder kernels are built for dim == 512, 768 or 1024", ST_ERR_UNSUPPORTED);
-    if (cfg->n_fft != kVocNfft || cfg->hop_length != kVocHop) return bad("native ISTFT is built for n_fft == 2048, hop_length == 512", ST_ERR_UNSUPPORTED);
-    if (cfg->input_channels % 64 != 0 || cfg->input_channels > 192) return bad("input_channels must be 64, 128 or 192", ST_ERR_UNSUPPORTED);
+    if (!voc_nfft_supported(cfg->n_fft) || cfg->hop_length != cfg->n_fft / 4)
+        return bad("native ISTFT is built for n_fft == 256, 512, 1024 or 2048 with hop_length == n_fft / 4", ST_ERR_UNSUPPORTED);
+    if (cfg->input_channels % 16 != 0 || cfg->input_channels > 192) return bad("input_channels must be a multiple of 16 up to 192", ST_ERR_UNSUPPORTED);
     if (cfg->intermediate_dim % 256 != 0) return bad("intermediate_dim must be a multiple of 256", ST_ERR_UNSUPPORTED);
     st_engine* e = nullptr;
     if (int rc = new_handle(KIND_VOCODER, device, &e)) return rc;
@@ -141,18 +162,19 @@ int st_create_vocoder(const st_vocos_config* cfg, int device, st_engine** out) {
 // One chunk of whole utterances: every GEMM runs over its R flattened rows, R = B * T, or the packed rows of a ragged chunk
 // (rg: mel and audio stay padded to T; only the im2col, the depthwise conv and the overlap-add know utterances and take the
 // ragged launcher).  The K loop of the conv GEMM forms an activation row's byte offset as a 32-bit value (t * cin * 2,
-// conv_gemm2_impl.h), so the callers size chunks to keep R * max(7 * M, C, F) * 2 below 2^31.
+// conv_gemm2_impl.h), so the callers size chunks to keep R * max(voc_im2col_pitch(M), C, F) * 2 below 2^31.
 static int vocos_forward_chunk(st_engine* e, const float* mel, float* audio, int B, int T, const RaggedChunk* rg, hipStream_t s) {
     VocosState* v = e->voc;
     const st_vocos_config& c = v->cfg;
     const int C = c.dim, F = c.intermediate_dim, M = c.input_channels, L = c.num_layers;
+    const int Kp = voc_im2col_pitch(M), plane = voc_head_plane(c.n_fft);
     const int64_t R = rg ? rg->rows : (int64_t)B * T;
 
     // workspace: im2col rows, fp32 residual stream, 16-bit operands, head output, windowed frames
     size_t off = 0;
     auto want = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_a16 = want((size_t)R * 7 * M * 2), o_x = want((size_t)R * C * 4), o_h16 = want((size_t)R * C * 2), o_h16lo = want((size_t)R * C * 2);
-    const size_t o_u16 = want((size_t)R * F * 2), o_head = want((size_t)R * 2 * kVocHeadPlane * 4), o_fr = want((size_t)R * kVocNfft * 4);
+    const size_t o_a16 = want((size_t)R * Kp * 2), o_x = want((size_t)R * C * 4), o_h16 = want((size_t)R * C * 2), o_h16lo = want((size_t)R * C * 2);
+    const size_t o_u16 = want((size_t)R * F * 2), o_head = want((size_t)R * 2 * plane * 4), o_fr = want((size_t)R * c.n_fft * 4);
     const size_t o_tiles = rg ? want((size_t)rg->n_tiles * sizeof(VocSeg)) : 0, o_groups = rg ? want((size_t)rg->n_groups * sizeof(VocSeg)) : 0;
     int rc = ensure_ws(e, off); if (rc) return rc;
     VocSeg* tiles = (VocSeg*)(e->ws + o_tiles); VocSeg* groups = (VocSeg*)(e->ws + o_groups);
@@ -174,7 +196,7 @@ static int vocos_forward_chunk(st_engine* e, const float* mel, float* audio, int
         } else {
             HIPCHK(e, launch_voc_im2col7(e->dt, mel, B, M, T, a16, s));
         }
-        ConvGemmArgs a = args(v->embed); a.a0 = a16; a.c0 = 7 * M; a.out32 = x;
+        ConvGemmArgs a = args(v->embed); a.a0 = a16; a.c0 = Kp; a.out32 = x;
         HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
         HIPCHK(e, launch_voc_ln(e->dt, x, P(e, "backbone.norm.weight"), P(e, "backbone.norm.bias"), R, C, x, nullptr, nullptr, s));
     }
@@ -206,19 +228,19 @@ static int vocos_forward_chunk(st_engine* e, const float* mel, float* audio, int
         ConvGemmArgs a = args(v->head); a.a0 = h16; a.c0 = C; a.a1 = h16lo; a.c1 = C; a.c2 = C; a.out32 = head;
         HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
     }
-    if (cap) { capture(e, "voc.hidden", x, R * C, false, s); capture(e, "voc.head_out", head, R * 2 * kVocHeadPlane, false, s); }
+    if (cap) { capture(e, "voc.hidden", x, R * C, false, s); capture(e, "voc.head_out", head, R * 2 * plane, false, s); }
     {   // ISTFT (head.py:104-116)
         ProfScope ps(e, s, PC_ODE, 0);
-        HIPCHK(e, launch_voc_spec_ifft(head, P(e, "head.istft.window"), R, frames, s));
-        if (rg) HIPCHK(e, launch_voc_overlap_add_ragged(frames, P(e, "head.istft.window"), rg->utt, B, T, audio, s));
-        else    HIPCHK(e, launch_voc_overlap_add(frames, P(e, "head.istft.window"), B, T, audio, s));
+        HIPCHK(e, launch_voc_spec_ifft(head, P(e, "head.istft.window"), R, c.n_fft, frames, s));
+        if (rg) HIPCHK(e, launch_voc_overlap_add_ragged(frames, P(e, "head.istft.window"), rg->utt, B, T, c.n_fft, audio, s));
+        else    HIPCHK(e, launch_voc_overlap_add(frames, P(e, "head.istft.window"), B, T, c.n_fft, audio, s));
     }
     return ST_OK;
 }
 
 // rows per chunk: 32-bit GEMM operand offsets (widest operand row: the im2col rows, C or F) and head output indices
 static int64_t vocos_max_rows(const st_vocos_config& c) {
-    const int64_t widest = std::max({7 * (int64_t)c.input_channels, (int64_t)c.dim, (int64_t)c.intermediate_dim, (int64_t)kVocHeadPlane});
+    const int64_t widest = std::max({(int64_t)voc_im2col_pitch(c.input_channels), (int64_t)c.dim, (int64_t)c.intermediate_dim, (int64_t)voc_head_plane(c.n_fft)});
     return (((int64_t)1 << 31) - 1) / (widest * 2);
 }
 

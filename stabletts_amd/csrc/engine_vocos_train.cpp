@@ -67,12 +67,24 @@ int vt_check_shape(st_engine* e, const VtCfg& c, int B, int T) {
     return ST_OK;
 }
 
+// The training path keeps the preset's ISTFT (kVocNfft / kVocHop, kVocHeadPlane) and im2col rows of exactly 7 M columns, so it
+// serves the handles st_create_vocoder admitted before the inference path took other n_fft and mel widths, and refuses the rest
+// before any allocation or launch.
+int vt_check_config(st_engine* e) {
+    const st_vocos_config& c = vocos_config_of(e);
+    if (c.n_fft != kVocNfft || c.hop_length != kVocHop || c.input_channels % 64 != 0)
+        return e->fail(ST_ERR_UNSUPPORTED, "native Vocos training is built for n_fft == 2048, hop_length == 512 and input_channels 64, 128 or 192 "
+                                           "(inference alone takes the other n_fft and mel widths)");
+    return ST_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int st_vocos_train_forward(st_engine* e, const float* mel, float* audio, int B, int T, void* stream) {
     int rc = check_handle(e, KIND_VOCODER); if (rc) return rc;
+    if ((rc = vt_check_config(e))) return rc;
     if ((rc = check_finalized(e))) return rc;
     if (!mel || !audio) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if ((rc = check_sizes(e, B, T))) return rc;
@@ -123,14 +135,15 @@ int st_vocos_train_forward(st_engine* e, const float* mel, float* audio, int B, 
     const int bins = c.NB / 2;
     HIPCHK(e, launch_vt_transpose(o, bins, (int)R, R, at(A.hrows), 2 * kVocHeadPlane, s));
     HIPCHK(e, launch_vt_transpose(o + (size_t)bins * R, bins, (int)R, R, at(A.hrows) + kVocHeadPlane, 2 * kVocHeadPlane, s));
-    HIPCHK(e, launch_voc_spec_ifft(at(A.hrows), P(e, "head.istft.window"), R, frames, s));
-    HIPCHK(e, launch_voc_overlap_add(frames, P(e, "head.istft.window"), B, T, audio, s));
+    HIPCHK(e, launch_voc_spec_ifft(at(A.hrows), P(e, "head.istft.window"), R, kVocNfft, frames, s));
+    HIPCHK(e, launch_voc_overlap_add(frames, P(e, "head.istft.window"), B, T, kVocNfft, audio, s));
     sd_train_commit(st, B, T, 0.0f, 0, false);
     return ST_OK;
 }
 
 int st_vocos_train_backward(st_engine* e, const float* d_audio, float* d_mel, float* grad_flat, int B, int T, void* stream) {
     int rc = check_handle(e, KIND_VOCODER); if (rc) return rc;
+    if ((rc = vt_check_config(e))) return rc;
     if (!d_audio || !grad_flat) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if ((rc = check_sizes(e, B, T))) return rc;
     SdTrain* st = e->sdt;

@@ -1,6 +1,7 @@
 // Vocos vocoder: the kernels around its GEMMs (vocoders/vocos/models/*.py; config.py:46-50 -> 128 -> 512, 8 ConvNeXt
 // blocks, ISTFT head n_fft 2048 / hop 512; the Vocos trainer's vocoders/vocos/config.py:21-26 -> 128 -> 768, 12 blocks).  Everything here is row-wise HBM-bound work on time-major tensors
 // [utterance][frame][channel]; the five GEMM shapes run on the implicit-GEMM kernels of conv_gemm2_impl.h.
+#include "audio_fft.h"
 #include "common.h"
 #include "vocos_launch.h"
 
@@ -10,7 +11,7 @@ namespace st {
 
 // ---------------------------------------------------------------- embed: im2col of the k = 7 convolution (backbone.py:28,51)
 // One block = 64 frames of one utterance: the (M x 70) mel tile is read with frames contiguous and written as
-// 16-bit rows [frame][tap][channel].  src: the utterance's mel (M, ld), T <= ld of its frames valid; rows: its frame 0.
+// 16-bit rows [frame][tap][channel] of pitch voc_im2col_pitch(M).  src: the utterance's mel (M, ld), T <= ld of its frames valid; rows: its frame 0.
 template <class P>
 __device__ __forceinline__ void voc_im2col7_tile(const float* __restrict__ src, int M, int ld, int T, int t0,
                                                  typename P::elem* __restrict__ rows, float* tile /* [M][72] */) {
@@ -20,11 +21,11 @@ __device__ __forceinline__ void voc_im2col7_tile(const float* __restrict__ src, 
         tile[c * 72 + k] = (t >= 0 && t < T) ? src[(size_t)c * ld + t] : 0.0f;
     }
     __syncthreads();
-    const int K = 7 * M;
-    for (int i = threadIdx.x; i < 64 * K; i += 256) {
-        const int f = i / K, r = i - f * K;
+    const int K = 7 * M, Kp = voc_im2col_pitch(M);      // columns K .. Kp - 1: the zero tail of the last 64-channel chunk
+    for (int i = threadIdx.x; i < 64 * Kp; i += 256) {
+        const int f = i / Kp, r = i - f * Kp;
         const int j = r / M, c = r - j * M;
-        if (t0 + f < T) rows[((size_t)t0 + f) * K + r] = to16<P>(tile[c * 72 + f + j]);
+        if (t0 + f < T) rows[((size_t)t0 + f) * Kp + r] = to16<P>(r < K ? tile[c * 72 + f + j] : 0.0f);
     }
 }
 
@@ -32,7 +33,7 @@ template <class P>
 __global__ __launch_bounds__(256) void voc_im2col7_kernel(const float* __restrict__ mel, int M, int T, typename P::elem* __restrict__ a16) {
     extern __shared__ float tile[];           // [M][72]
     const int b = blockIdx.y;
-    voc_im2col7_tile<P>(mel + (size_t)b * M * T, M, T, T, blockIdx.x * 64, a16 + (size_t)b * T * 7 * M, tile);
+    voc_im2col7_tile<P>(mel + (size_t)b * M * T, M, T, T, blockIdx.x * 64, a16 + (size_t)b * T * voc_im2col_pitch(M), tile);
 }
 
 // Ragged batch: block = one entry of the tile table (voc_segments_kernel); mel is padded (B, M, Tmax), the rows are packed.
@@ -41,7 +42,7 @@ __global__ __launch_bounds__(256) void voc_im2col7_ragged_kernel(const float* __
                                                                  typename P::elem* __restrict__ a16) {
     extern __shared__ float tile[];           // [M][72]
     const VocSeg sg = tiles[blockIdx.x];
-    voc_im2col7_tile<P>(mel + (size_t)sg.item * M * Tmax, M, Tmax, sg.T, sg.t0, a16 + (size_t)sg.row0 * 7 * M, tile);
+    voc_im2col7_tile<P>(mel + (size_t)sg.item * M * Tmax, M, Tmax, sg.T, sg.t0, a16 + (size_t)sg.row0 * voc_im2col_pitch(M), tile);
 }
 
 hipError_t launch_voc_im2col7(int dtype, const float* mel, int B, int M, int T, void* a16, hipStream_t s) {
@@ -355,60 +356,138 @@ __global__ __launch_bounds__(256) void voc_spec_ifft_kernel(const float* __restr
     }
 }
 
-hipError_t launch_voc_spec_ifft(const float* head, const float* window, int64_t rows, float* frames, hipStream_t s) {
-    hipLaunchKernelGGL(voc_spec_ifft_kernel, dim3((unsigned)rows), dim3(256), 0, s, head, window, frames);
+// n_fft 256, 512, 1024: the same steps with S = 2048 / N frames per block, so that every thread still does one radix-4 butterfly per
+// pass -- the H = N / 2 point Stockham transform of the feature front end (audio_fft.h: mel_fft<N>, with its radix-2 pass for H = 512
+// and 128; mel_twiddles<N> holds e^{-2 pi i m / N}).  mel_fft is the forward transform, so the block transforms conj Z and conjugates
+// the result, as mel_inverse_to_ws does: IDFT_H(Z) = conj(DFT_H(conj Z)).  The block of frames t0 .. t0 + S - 1 may reach past
+// `rows`: a dead frame reads no head row (its spectrum is zero) and writes no frame.
+template <int N>
+__global__ __launch_bounds__(256) void voc_spec_ifft_small_kernel(const float* __restrict__ head, const float* __restrict__ window,
+                                                                  long long rows, float* __restrict__ frames) {
+    constexpr int H = MelGeo<N>::H, S = MelGeo<N>::S, plane = voc_head_plane(N);
+    static_assert(S * H == 1024 && S * (H / 4) == 256, "one radix-4 butterfly per thread and pass");
+    __shared__ float2 b0[S * H], b1[S * (H + 1)], tw[H];
+    float2* spec = b1;      // the S spectra of H + 1 bins: read for the last time before mel_fft's first pass writes b1
+    const int tid = threadIdx.x;
+    const long long t0 = (long long)blockIdx.x * S;
+    mel_twiddles<N>(tw, tid);
+    for (int e = tid; e < S * (H + 1); e += 256) {
+        const int f = e / (H + 1), k = e - f * (H + 1);
+        float2 v = make_float2(0.0f, 0.0f);
+        if (t0 + f < rows) {
+            const float* row = head + (size_t)(t0 + f) * (2 * plane);
+            const float mag = fminf(expf(row[k]), 100.0f);           // head.py:105-106
+            float sn, cs;
+            sincosf(row[plane + k], &sn, &cs);                       // :108-109
+            v = make_float2(mag * cs, (k == 0 || k == H) ? 0.0f : mag * sn);
+        }
+        spec[e] = v;
+    }
+    __syncthreads();
+    for (int e = tid; e < S * H; e += 256) {
+        const int f = e / H, k = e - f * H;
+        const float2 a = spec[f * (H + 1) + k], c = spec[f * (H + 1) + H - k];
+        const float2 E = make_float2(0.5f * (a.x + c.x), 0.5f * (a.y - c.y));
+        float2 O = make_float2(0.5f * (a.x - c.x), 0.5f * (a.y + c.y));
+        O = cmul(O, make_float2(tw[k].x, -tw[k].y));                 // e^{+2 pi i k / N}
+        b0[e] = make_float2(E.x - O.y, -(E.y + O.x));                // conj(E + i O)
+    }
+    __syncthreads();
+    const float2* zz = mel_fft<N>(b0, b1, tw, tid);                  // conj z: x[2n] = Re, x[2n+1] = -Im
+    for (int e = tid; e < S * H; e += 256) {
+        const int f = e / H, n = e - f * H;
+        if (t0 + f >= rows) continue;
+        const float2 z = zz[e];
+        const float2 wv = *(const float2*)(window + 2 * n);
+        *(float2*)(frames + (size_t)(t0 + f) * N + 2 * n) = make_float2(z.x * (1.0f / H) * wv.x, -z.y * (1.0f / H) * wv.y);   // :56-57
+    }
+}
+
+// n_fft -> f(integral_constant<int, n_fft>) for the sizes st_create_vocoder admits
+template <class F>
+static hipError_t voc_for_nfft(int n_fft, F&& f) {
+    switch (n_fft) {
+        case 256:  f(std::integral_constant<int, 256>()); break;
+        case 512:  f(std::integral_constant<int, 512>()); break;
+        case 1024: f(std::integral_constant<int, 1024>()); break;
+        case 2048: f(std::integral_constant<int, 2048>()); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 
-// Overlap-add (fold, head.py:60-63), "same" trim (:48,63), window envelope (:66-69) and normalisation (:73).
-// Output sample s of utterance b sits at q = s + 768 of the untrimmed signal; frames floor((q - 2047 + 511) / 512) ..
-// floor(q / 512) cover it (at most 4), added in ascending frame order.
+hipError_t launch_voc_spec_ifft(const float* head, const float* window, int64_t rows, int n_fft, float* frames, hipStream_t s) {
+    return voc_for_nfft(n_fft, [&](auto nn) {
+        constexpr int N = decltype(nn)::value;
+        if constexpr (N == kVocNfft) {
+            hipLaunchKernelGGL(voc_spec_ifft_kernel, dim3((unsigned)rows), dim3(256), 0, s, head, window, frames);
+        } else {
+            constexpr int S = MelGeo<N>::S;
+            hipLaunchKernelGGL((voc_spec_ifft_small_kernel<N>), dim3((unsigned)((rows + S - 1) / S)), dim3(256), 0, s, head, window, (long long)rows, frames);
+        }
+    });
+}
+
+// Overlap-add (fold, head.py:60-63), "same" trim (:48,63), window envelope (:66-69) and normalisation (:73), hop = N / 4.
+// Output sample s of utterance b sits at q = s + (N - hop) / 2 of the untrimmed signal (768 at N = 2048); frames
+// floor((q - (N - 1) + hop - 1) / hop) .. floor(q / hop) cover it (at most 4), added in ascending frame order.
+template <int N>
 __device__ __forceinline__ float voc_ola_sample(const float* __restrict__ fr /* the utterance's frames */, const float* __restrict__ window,
                                                 int T, long long s) {
-    const long long q = s + (kVocNfft - kVocHop) / 2;
-    int f1 = (int)(q / kVocHop); if (f1 > T - 1) f1 = T - 1;
-    long long f0l = (q - (kVocNfft - 1) + kVocHop - 1) / kVocHop; if (q - (kVocNfft - 1) < 0) f0l = 0;
+    constexpr int hop = N / 4;
+    const long long q = s + (N - hop) / 2;
+    int f1 = (int)(q / hop); if (f1 > T - 1) f1 = T - 1;
+    long long f0l = (q - (N - 1) + hop - 1) / hop; if (q - (N - 1) < 0) f0l = 0;
     float y = 0.0f, env = 0.0f;
     for (int f = (int)f0l; f <= f1; ++f) {
-        const int off = (int)(q - (long long)f * kVocHop);
+        const int off = (int)(q - (long long)f * hop);
         const float wv = window[off];
-        y += fr[(size_t)f * kVocNfft + off];
+        y += fr[(size_t)f * N + off];
         env += wv * wv;
     }
     return y / env;
 }
 
+template <int N>
 __global__ __launch_bounds__(256) void voc_overlap_add_kernel(const float* __restrict__ frames, const float* __restrict__ window,
                                                               int T, float* __restrict__ audio) {
-    const long long len = (long long)T * kVocHop;
+    const long long len = (long long)T * (N / 4);
     const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
     if (s >= len) return;
     const int b = blockIdx.y;
-    audio[(size_t)b * len + s] = voc_ola_sample(frames + (size_t)b * T * kVocNfft, window, T, s);
+    audio[(size_t)b * len + s] = voc_ola_sample<N>(frames + (size_t)b * T * N, window, T, s);
 }
 
-// Ragged batch: packed frames -> padded audio (B, Tmax * 512); 2 * Tmax blocks per utterance on a 1-D grid, zeros from
-// sample T_b * 512 on.
+// Ragged batch: packed frames -> padded audio (B, Tmax * hop); `per` = ceil(Tmax * hop / 256) blocks per utterance on a 1-D grid,
+// zeros from sample T_b * hop on.  With hop 64 or 128 the last block of an utterance can reach past Tmax * hop: those threads
+// write nothing (the samples there are the next utterance's).
+template <int N>
 __global__ __launch_bounds__(256) void voc_overlap_add_ragged_kernel(const float* __restrict__ frames, const float* __restrict__ window,
-                                                                     const VocUtt* __restrict__ utt, int Tmax, float* __restrict__ audio) {
-    const int per = 2 * Tmax;                 // blocks per utterance (kVocHop / 256 per frame)
+                                                                     const VocUtt* __restrict__ utt, int Tmax, int per, float* __restrict__ audio) {
+    constexpr int hop = N / 4;
     const int b = blockIdx.x / per;
     const long long s = (long long)(blockIdx.x - b * per) * 256 + threadIdx.x;
+    if (s >= (long long)Tmax * hop) return;
     const VocUtt u = utt[b];
-    audio[(size_t)b * Tmax * kVocHop + s] = s < (long long)u.T * kVocHop ? voc_ola_sample(frames + (size_t)u.row0 * kVocNfft, window, u.T, s) : 0.0f;
+    audio[(size_t)b * Tmax * hop + s] = s < (long long)u.T * hop ? voc_ola_sample<N>(frames + (size_t)u.row0 * N, window, u.T, s) : 0.0f;
 }
 
-hipError_t launch_voc_overlap_add(const float* frames, const float* window, int B, int T, float* audio, hipStream_t s) {
-    const long long len = (long long)T * kVocHop;
-    hipLaunchKernelGGL(voc_overlap_add_kernel, dim3((unsigned)((len + 255) / 256), B), dim3(256), 0, s, frames, window, T, audio);
-    return hipGetLastError();
+hipError_t launch_voc_overlap_add(const float* frames, const float* window, int B, int T, int n_fft, float* audio, hipStream_t s) {
+    return voc_for_nfft(n_fft, [&](auto nn) {
+        constexpr int N = decltype(nn)::value;
+        const long long len = (long long)T * (N / 4);
+        hipLaunchKernelGGL((voc_overlap_add_kernel<N>), dim3((unsigned)((len + 255) / 256), B), dim3(256), 0, s, frames, window, T, audio);
+    });
 }
 
-hipError_t launch_voc_overlap_add_ragged(const float* frames, const float* window, const VocUtt* utt, int B, int Tmax, float* audio, hipStream_t s) {
-    static_assert(kVocHop == 512, "two 256-sample blocks per frame");
-    if ((long long)B * Tmax > kVocMaxPaddedFrames) return hipErrorInvalidValue;      // grid.x * 256 threads stays below 2^32
-    hipLaunchKernelGGL(voc_overlap_add_ragged_kernel, dim3((unsigned)(2ll * B * Tmax)), dim3(256), 0, s, frames, window, utt, Tmax, audio);
-    return hipGetLastError();
+hipError_t launch_voc_overlap_add_ragged(const float* frames, const float* window, const VocUtt* utt, int B, int Tmax, int n_fft, float* audio,
+                                         hipStream_t s) {
+    if ((long long)B * Tmax > kVocMaxPaddedFrames) return hipErrorInvalidValue;      // grid.x * 256 threads stays below 2^32 (per <= 2 * Tmax)
+    return voc_for_nfft(n_fft, [&](auto nn) {
+        constexpr int N = decltype(nn)::value;
+        const int per = (int)(((long long)Tmax * (N / 4) + 255) / 256);
+        hipLaunchKernelGGL((voc_overlap_add_ragged_kernel<N>), dim3((unsigned)((long long)B * per)), dim3(256), 0, s, frames, window, utt, Tmax, per, audio);
+    });
 }
 
 }  // namespace st

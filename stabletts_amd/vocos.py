@@ -68,7 +68,8 @@ class Vocos(NativeModule):
     """Same constructor as the reference: ``Vocos(VocosConfig(), MelConfig())`` -- any objects with the attributes
     input_channels / dim / intermediate_dim / num_layers and n_fft / hop_length (config.py:4-19,46-50).  The native kernels take
     dim 512 (the inference preset), 768 (the Vocos trainer's own generator, vocoders/vocos/config.py:21-26: 128 / 768 / 2048 / 12)
-    and 1024; any other dim is refused when the engine is created."""
+    and 1024; n_fft 256, 512, 1024 or 2048 with hop_length == n_fft / 4 (44.1 kHz: 2048 / 512, 22.05-24 kHz: 1024 / 256, 16 kHz:
+    512 / 128); input_channels a multiple of 16 up to 192.  Anything else is refused when the engine is created."""
     _what = "vocoder"
     _rebind = False             # st_finalize packs a vocoder's weights: every change re-loads
 

@@ -10,7 +10,9 @@ The training path is fp32 throughout (fp32-input MFMA GEMMs), so its waveform is
 run on f16 / bf16 operands: it is closer to the reference's than the inference one.  The engine reads the parameters in place
 (st_bind_param), so an optimizer step costs no copy; the 16-bit copies of the inference path are packed again only when a
 no_grad / eval call follows a parameter update.  Under ``torch.no_grad()`` or in ``eval()`` mode a call is the inference path of
-``stabletts_amd.vocos``, unchanged.  The engine keeps the activations of ONE training forward, and each forward can be
+``stabletts_amd.vocos``, unchanged.  Training is built for n_fft 2048 / hop_length 512 and input_channels 64, 128 or 192: at the
+other configurations the inference path takes (n_fft 256-1024, mel widths in steps of 16) the module still constructs, loads and
+vocodes under ``no_grad``, and a grad-enabled call raises the ``NativeError`` of ``ST_ERR_UNSUPPORTED``.  The engine keeps the activations of ONE training forward, and each forward can be
 differentiated once.
 """
 import torch

@@ -6,7 +6,10 @@ call, the ragged call and a loop of 32 single-utterance calls, and the ragged ca
 call; writes profiles/vocos_ragged_bench.txt (at the preset only).
 --dim D --intermediate-dim F --num-layers L (any of them; default the inference preset 512 / 1536 / 8): another generator, e.g. the
 Vocos trainer's own 768 / 2048 / 12 (vocoders/vocos/config.py:21-26).  --torch: beside the native call, the same forward written in
-torch ops (tests/vocos_vjp_restatement.torch_vocos) on the same GPU in fp32 and under fp16 autocast, the three legs in turn."""
+torch ops (tests/vocos_vjp_restatement.torch_vocos) on the same GPU in fp32 and under fp16 autocast, the three legs in turn.
+--n-fft N --hop-length H --input-channels M: another ISTFT size and mel width (n_fft 256 / 512 / 1024 / 2048 with hop n_fft / 4, M a
+multiple of 16 up to 192), e.g. a 22.05 kHz model's --n-fft 1024 --hop-length 256 --input-channels 80; for the dense and the
+--ragged leg.  --sample-rate R (default 44100; 22050 is usual for n_fft 1024, 16000 for 512) only scales audio_s_per_s."""
 import json
 import os
 import statistics
@@ -25,7 +28,8 @@ ragged = "--ragged" in sys.argv
 with_torch = "--torch" in sys.argv
 argv = [a for a in sys.argv if a not in ("--ragged", "--torch")]
 over = {}
-for flag, key in (("--dim", "dim"), ("--intermediate-dim", "intermediate_dim"), ("--num-layers", "num_layers")):
+for flag, key in (("--dim", "dim"), ("--intermediate-dim", "intermediate_dim"), ("--num-layers", "num_layers"), ("--n-fft", "n_fft"),
+                  ("--hop-length", "hop_length"), ("--input-channels", "input_channels"), ("--sample-rate", "sample_rate")):
     if flag in argv:
         i = argv.index(flag)
         over[key] = int(argv[i + 1])
@@ -33,6 +37,7 @@ for flag, key in (("--dim", "dim"), ("--intermediate-dim", "intermediate_dim"), 
 B = int(argv[1]) if len(argv) > 1 and not ragged else 32
 T = int(argv[2]) if len(argv) > 2 and not ragged else 1000
 dt = (argv[1] if len(argv) > 1 else "f16") if ragged else (argv[3] if len(argv) > 3 else "f16")
+sample_rate = over.pop("sample_rate", 44100)
 c = vo.vocos_config(**over)
 sd = vo.make_vocos_state_dict(77, c)
 m = Vocos(types.SimpleNamespace(input_channels=c.input_channels, dim=c.dim, intermediate_dim=c.intermediate_dim, num_layers=c.num_layers),
@@ -47,7 +52,7 @@ def ragged_leg():
     ROUNDS, CALLS, NB = 15, 5, 32
     lengths = np.random.default_rng(4).integers(600, 1001, NB).tolist()
     Tmax, rows = max(lengths), sum(lengths)
-    mel = torch.from_numpy(vo.make_mel(NB, Tmax, 3)).cuda()
+    mel = torch.from_numpy(vo.make_mel(NB, Tmax, 3, c.input_channels)).cuda()
     for b, n in enumerate(lengths):
         mel[b, :, n:] = 0.0
     solo = [mel[b:b + 1, :, :n].contiguous() for b, n in enumerate(lengths)]
@@ -67,7 +72,7 @@ def ragged_leg():
     med = {k: statistics.median(v) for k, v in ms.items()}
     spread = abs(med["dense_a"] - med["dense_b"]) / med["dense_a"]
     lines = [
-        {"workload": "vocos_bucket", "dtype": dt, "dim": c.dim, "intermediate_dim": c.intermediate_dim, "num_layers": c.num_layers, "B": NB, "Tmax": Tmax, "packed_rows": rows, "padded_rows": NB * Tmax,
+        {"workload": "vocos_bucket", "dtype": dt, "n_fft": c.n_fft, "hop_length": c.hop_length, "input_channels": c.input_channels, "dim": c.dim, "intermediate_dim": c.intermediate_dim, "num_layers": c.num_layers, "B": NB, "Tmax": Tmax, "packed_rows": rows, "padded_rows": NB * Tmax,
          "rows_ratio": round(rows / (NB * Tmax), 3), "rounds": ROUNDS, "calls_per_round": CALLS,
          "dense_padded_ms_median": round(med["dense_padded"], 3), "ragged_ms_median": round(med["ragged"], 3),
          "solo_loop_ms_median": round(med["solo_loop"], 3), "ragged_over_dense": round(med["ragged"] / med["dense_padded"], 3),
@@ -96,7 +101,7 @@ def ragged_leg():
 if ragged:
     ragged_leg()
     sys.exit(0)
-mel = torch.from_numpy(vo.make_mel(B, T, 3)).cuda()
+mel = torch.from_numpy(vo.make_mel(B, T, 3, c.input_channels)).cuda()
 for _ in range(3):
     m(mel)
 torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -105,7 +110,7 @@ for _ in range(10):
 torch.cuda.synchronize(); ms = (time.perf_counter() - t0) / 10 * 1e3
 eng = m.engine(); eng.profile_enable(True); m(mel); torch.cuda.synchronize()
 pr = eng.profile_read(); eng.profile_enable(False)
-flops = B * T * (2 * 7 * c.input_channels * c.dim + c.num_layers * 4 * c.dim * c.intermediate_dim + 2 * c.dim * 2050)
+flops = B * T * (2 * 7 * c.input_channels * c.dim + c.num_layers * 4 * c.dim * c.intermediate_dim + 2 * c.dim * (c.n_fft + 2))
 extra = {}
 if with_torch:      # the torch statement of the same forward on the same GPU, the legs in turn (medians of 7 rounds of 3 calls)
     from tests.vocos_vjp_restatement import torch_vocos
@@ -113,11 +118,11 @@ if with_torch:      # the torch statement of the same forward on the same GPU, t
 
     def t_fp32():
         with torch.no_grad():
-            return torch_vocos(tp, mel, c.num_layers)
+            return torch_vocos(tp, mel, c.num_layers, c.n_fft, c.hop_length)
 
     def t_fp16():
         with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
-            return torch_vocos(tp, mel, c.num_layers)
+            return torch_vocos(tp, mel, c.num_layers, c.n_fft, c.hop_length)
     legs = {"native": lambda: m(mel), "torch_fp32": t_fp32, "torch_fp16_autocast": t_fp16}
     for fn in legs.values():
         fn(); fn()
@@ -134,6 +139,6 @@ if with_torch:      # the torch statement of the same forward on the same GPU, t
     extra = {**extra, "legs_ms_median": {k: round(v, 3) for k, v in med.items()},
              "torch_fp32_over_native": round(med["torch_fp32"] / med["native"], 2),
              "torch_fp16_autocast_over_native": round(med["torch_fp16_autocast"] / med["native"], 2)}
-print(json.dumps({"B": B, "T": T, "dtype": dt, "dim": c.dim, "intermediate_dim": c.intermediate_dim, "num_layers": c.num_layers, "ms": round(ms, 3), **extra, "frames_per_s": round(B * T / ms * 1e3),
-                  "audio_s_per_s": round(B * T * 512 / 44100 / ms * 1e3, 1), "gemm_tflops": round(flops / ms / 1e9, 1),
+print(json.dumps({"B": B, "T": T, "dtype": dt, "n_fft": c.n_fft, "hop_length": c.hop_length, "input_channels": c.input_channels, "dim": c.dim, "intermediate_dim": c.intermediate_dim, "num_layers": c.num_layers, "ms": round(ms, 3), **extra, "frames_per_s": round(B * T / ms * 1e3),
+                  "audio_s_per_s": round(B * T * c.hop_length / sample_rate / ms * 1e3, 1), "gemm_tflops": round(flops / ms / 1e9, 1),
                   "classes_ms": {k: round(v["total_ms"], 3) for k, v in pr.items() if v["launches"]}}))
