@@ -1,6 +1,6 @@
 // Host side of libstabletts_hip.so: parameter store, weight packing, workspace arena and the estimator launch sequence behind
 // the C ABI of include/stabletts_hip.h (the ODE solve around it: engine_solve.cpp).  Reference path: models/estimator.py:103-138.
-#include "engine_internal.h"
+#include "engine_dit.h"
 #include "train_launch.h"
 #include "mas_launch.h"
 #include "align_train_launch.h"
@@ -37,11 +37,12 @@ void expect(st_engine* e, const std::string& name, std::vector<int64_t> shape) {
 }
 
 void build_param_table(st_engine* e) {
-    const int C = e->C, F = e->F, M = e->M, K = e->K, G = e->G;
+    DitState* dit = dit_of(e);
+    const int C = dit->C, F = dit->F, M = dit->M, K = dit->K, G = dit->G;
     if (e->kind == KIND_TEXT_ENCODER) {     // TextEncoder state_dict (models/text_encoder.py:22-26)
-        expect(e, "emb.weight", {e->n_vocab, C});
-        for (int i = 0; i < e->L; ++i) {
-            const std::string p = e->blk(i);
+        expect(e, "emb.weight", {dit->n_vocab, C});
+        for (int i = 0; i < dit->L; ++i) {
+            const std::string p = dit->blk(i);
             for (const char* nm : {"q", "k", "v", "o"}) {
                 expect(e, p + "attn.conv_" + nm + ".weight", {C, C, 1});
                 expect(e, p + "attn.conv_" + nm + ".bias", {C});
@@ -57,7 +58,7 @@ void build_param_table(st_engine* e) {
     expect(e, "time_mlp.layer.0.weight", {F, C}); expect(e, "time_mlp.layer.0.bias", {F});
     expect(e, "time_mlp.layer.2.weight", {C, F}); expect(e, "time_mlp.layer.2.bias", {C});
     expect(e, "in_proj.weight", {C, C + M, 1}); expect(e, "in_proj.bias", {C});
-    for (int i = 0; i < e->L; ++i) {
+    for (int i = 0; i < dit->L; ++i) {
         const std::string p = "blocks." + std::to_string(i) + ".";
         expect(e, p + "time_fusion.film.weight", {2 * C, C, 1}); expect(e, p + "time_fusion.film.bias", {2 * C});
         for (const char* nm : {"q", "k", "v", "o"}) {
@@ -77,7 +78,7 @@ void build_param_table(st_engine* e) {
     expect(e, "cond_proj.0.weight", {F, M, K}); expect(e, "cond_proj.0.bias", {F});
     expect(e, "cond_proj.2.weight", {F, F, K}); expect(e, "cond_proj.2.bias", {F});
     expect(e, "cond_proj.4.weight", {C, F, K}); expect(e, "cond_proj.4.bias", {C});
-    for (int i = 0; i < e->L / 2; ++i) {
+    for (int i = 0; i < dit->L / 2; ++i) {
         expect(e, "lsc_layers." + std::to_string(i) + ".weight", {C, 2 * C, K});
         expect(e, "lsc_layers." + std::to_string(i) + ".bias", {C});
     }
@@ -91,59 +92,65 @@ const float* P(st_engine* e, const std::string& name) { return e->params.at(name
 // few long-running blocks); otherwise row-complete 256x128 tiles where the epilogue needs whole rows (fused
 // LayerNorm, QKV planes), the 3-buffer pipeline for deep k=3 convs, 128x128 tiles for the rest.
 // 256 x 256 tiles (BIG / PHASED / RC1) are used when they waste little of the last frame tile and fill the chip
-static bool big_tiles(const st_engine* e, const ConvGemmArgs& a) {
+static int launches_in_flight(const DitState* dit) { return dit ? dit->conc : 1; }      // launch sequences that share the chip: the parts of a DiT solve
+static bool big_tiles(const st_engine* e, int conc, const ConvGemmArgs& a) {
     const int T = a.T;
     const bool fills = ((T + 255) / 256) * 256 * 10 <= ((T + 127) / 128) * 128 * 11;
-    const bool big_fills_chip = (int64_t)e->conc * a.n_items * ((T + 255) / 256) * (a.cout / 256) >= e->big_min_blocks;
+    const bool big_fills_chip = (int64_t)conc * a.n_items * ((T + 255) / 256) * (a.cout / 256) >= e->tile.big_min_blocks;
     return a.cout % 256 == 0 && fills && big_fills_chip;
 }
-bool gemm_is_phased(const st_engine* e, int taps, const ConvGemmArgs& a) { return taps == 3 && e->phased && big_tiles(e, a); }
+bool gemm_is_phased(const st_engine* e, int taps, const ConvGemmArgs& a) {
+    return taps == 3 && e->tile.phased && big_tiles(e, launches_in_flight(dit_or_null(e)), a);
+}
 
 hipError_t gemm(st_engine* e, int taps, int epi, const ConvGemmArgs& a, hipStream_t s) {
+    const DitState* dit = dit_or_null(e);      // the weight-stationary kernels below are the DiT kinds' own
+    const int conc = launches_in_flight(dit);
+    const bool big = big_tiles(e, conc, a);
     const bool bf = e->dt == DT_BF16;
     const int T = a.T;
-    if (epi == EPI_SILU && !gemm_is_phased(e, taps, a)) return hipErrorInvalidValue;      // callers ask gemm_is_phased first
+    if (epi == EPI_SILU && !(taps == 3 && e->tile.phased && big)) return hipErrorInvalidValue;      // callers ask gemm_is_phased first
     // Small grids (a few frame tiles in total: single-utterance synthesis): the K loop of one block is a serial chain
     // of DMA -> barrier -> MFMA stages, so a handful of blocks walking 24..48 stages each leaves the chip idle for
     // tens of microseconds.  Split the contraction over `ks` blocks per output tile (raw fp32 partial planes in
-    // e->kpart) and apply the epilogue -- including a fused LayerNorm -- in a row-wise finish kernel.
-    if (e->kpart && e->conc == 1 && a.cout == 256 && (epi == EPI_F32 || epi == EPI_RESGATE) && !a.w_item_stride) {
+    // e->tile.kpart) and apply the epilogue -- including a fused LayerNorm -- in a row-wise finish kernel.
+    if (e->tile.kpart && conc == 1 && a.cout == 256 && (epi == EPI_F32 || epi == EPI_RESGATE) && !a.w_item_stride) {
         const int nch = (a.c0 + a.c1 + a.c2) / 64;
         const int64_t blocks = (int64_t)a.n_items * ((T + 127) / 128) * 2;
         const int64_t plane = (int64_t)a.n_items * T * 256 * 4;
-        int ks = (int)std::min<int64_t>(std::min(nch, e->splitk_max), e->splitk_target / blocks);
-        ks = (int)std::min<int64_t>(ks, (int64_t)e->kpart_bytes / plane);
-        if (ks >= 2 && nch * taps >= e->splitk_min_stages) {
+        int ks = (int)std::min<int64_t>(std::min(nch, e->tile.splitk_max), e->tile.splitk_target / blocks);
+        ks = (int)std::min<int64_t>(ks, (int64_t)e->tile.kpart_bytes / plane);
+        if (ks >= 2 && nch * taps >= e->tile.splitk_min_stages) {
             ConvGemmArgs pa = a;
             pa.t_lim = nullptr;
             pa.bias = nullptr; pa.flags = 0; pa.mask = nullptr; pa.add32 = nullptr; pa.out16 = nullptr; pa.out16_lo = nullptr;
-            pa.ln_h16 = nullptr; pa.gate = nullptr; pa.res32 = nullptr; pa.branch32 = nullptr; pa.out32 = e->kpart; pa.ksplit = ks;
-            const int pcfg = e->small_tiles ? G2_T64 : G2_T128;
+            pa.ln_h16 = nullptr; pa.gate = nullptr; pa.res32 = nullptr; pa.branch32 = nullptr; pa.out32 = e->tile.kpart; pa.ksplit = ks;
+            const int pcfg = e->tile.small_tiles ? G2_T64 : G2_T128;
             hipError_t he = bf ? launch_conv_gemm2_bf16(pcfg, taps, EPI_F32, pa, s) : launch_conv_gemm2_f16(pcfg, taps, EPI_F32, pa, s);
             if (he != hipSuccess) return he;
-            return bf ? launch_splitk_finish_bf16(epi, a, e->kpart, ks, s) : launch_splitk_finish_f16(epi, a, e->kpart, ks, s);
+            return bf ? launch_splitk_finish_bf16(epi, a, e->tile.kpart, ks, s) : launch_splitk_finish_f16(epi, a, e->tile.kpart, ks, s);
         }
     }
     // the fused q/k/v projection of big grids: weights in registers, activations streamed (qkv_ws.hip; bit-identical)
-    if (epi == EPI_QKV && e->qkv_ws && !a.q_lo && !a.vt_lo && e->sink && a.w_frag && a.cout == 768 && a.c0 == 256 && !a.c1 && !a.c2 && a.n_heads == 4 &&
-        (int64_t)a.n_items * ((T + 63) / 64) >= e->qkv_ws_min_tiles) {      // (per LAUNCH: a block needs a handful of tiles to amortise its weight load)
-        ConvGemmArgs b = a; b.sink = e->sink;
+    if (dit && epi == EPI_QKV && dit->qkv_ws && !a.q_lo && !a.vt_lo && dit->sink && a.w_frag && a.cout == 768 && a.c0 == 256 && !a.c1 && !a.c2 && a.n_heads == 4 &&
+        (int64_t)a.n_items * ((T + 63) / 64) >= dit->qkv_ws_min_tiles) {      // (per LAUNCH: a block needs a handful of tiles to amortise its weight load)
+        ConvGemmArgs b = a; b.sink = dit->sink;
         return launch_qkv_ws(e->dt, b, s);
     }
     // the out projection (+ LayerNorm_2) of big grids in the same style (oproj_ws.hip; bit-identical)
-    if (epi == EPI_RESGATE && taps == 1 && e->oproj_ws && e->sink && a.w_frag && a.ln_h16 && !a.ln_film && a.cout == 256 && a.c0 == 256 &&
+    if (dit && epi == EPI_RESGATE && taps == 1 && dit->oproj_ws && dit->sink && a.w_frag && a.ln_h16 && !a.ln_film && a.cout == 256 && a.c0 == 256 &&
         !a.c1 && !a.c2 && !a.out16 && !a.res32 && !a.branch32 && !a.out32_readonly && a.out32 &&
-        (int64_t)a.n_items * ((T + 31) / 32) >= e->oproj_ws_min_tiles) {
-        ConvGemmArgs b = a; b.sink = e->sink;
+        (int64_t)a.n_items * ((T + 31) / 32) >= dit->oproj_ws_min_tiles) {
+        ConvGemmArgs b = a; b.sink = dit->sink;
         return launch_oproj_ws(e->dt, b, s);
     }
     int cfg;
-    if (big_tiles(e, a)) cfg = (e->phased && taps == 3) ? G2_PHASED : (epi == EPI_QKV && e->qkv_rc1) ? G2_RC1 : G2_BIG;
+    if (big) cfg = (e->tile.phased && taps == 3) ? G2_PHASED : (dit && epi == EPI_QKV && dit->qkv_rc1) ? G2_RC1 : G2_BIG;
     else if (a.ln_h16 || epi == EPI_QKV) cfg = G2_RC;
     else if (taps == 3 && a.c0 + a.c1 >= 512 && a.c2 == 0) cfg = G2_K3PIPE;
     else cfg = G2_T128;
     // latency-bound small grids: 64-frame tiles double the block count and halve every block's serial work
-    const bool tiny = e->small_tiles && e->conc == 1 && (int64_t)a.n_items * ((T + 127) / 128) * (a.cout / 128) <= e->small_tiles;
+    const bool tiny = e->tile.small_tiles && conc == 1 && (int64_t)a.n_items * ((T + 127) / 128) * (a.cout / 128) <= e->tile.small_tiles;
     if (tiny && cfg == G2_T128 && (epi == EPI_ACT16 ? taps == 3 : epi == EPI_F32)) cfg = G2_T64;
     if (tiny && cfg == G2_RC && epi == EPI_QKV) cfg = G2_RC64;
     return bf ? launch_conv_gemm2_bf16(cfg, taps, epi, a, s) : launch_conv_gemm2_f16(cfg, taps, epi, a, s);
@@ -190,7 +197,8 @@ void capture(st_engine* e, const std::string& name, const void* dev, int64_t n, 
 
 // ---- workspace plan (engine_internal.h: Plan) ------------------------------------------------
 size_t layout_plan(st_engine* e, int B, int T, bool cfg, int n_t, size_t off, Plan* p) {
-    const int C = e->C, F = e->F, Mp = e->Mp, L = e->L;
+    DitState* dit = dit_of(e);
+    const int C = dit->C, F = dit->F, Mp = dit->Mp, L = dit->L;
     p->B = B; p->T = T; p->cfg = cfg; p->n_t = n_t;
     p->Tp = (T + 63) / 64 * 64;
     p->N = cfg ? 2 * B : B;
@@ -234,7 +242,7 @@ size_t layout_plan(st_engine* e, int B, int T, bool cfg, int n_t, size_t off, Pl
     want((void**)&p->th, (size_t)n_t * F * 4);
     want((void**)&p->tau, (size_t)n_t * C * 4);
     want((void**)&p->film, (size_t)L * n_t * 2 * C * 4);
-    want((void**)&p->cvec, N * (size_t)e->G * 4);
+    want((void**)&p->cvec, N * (size_t)dit->G * 4);
     want((void**)&p->ada_tmp, N * (size_t)C * 4);
     want((void**)&p->ada, (size_t)L * N * 6 * C * 4);
     want((void**)&p->n_full, (size_t)B * 4);
@@ -247,7 +255,7 @@ size_t layout_plan(st_engine* e, int B, int T, bool cfg, int n_t, size_t off, Pl
 
 int ensure_ws(st_engine* e, size_t bytes) {
     if (bytes <= e->ws_cap) return ST_OK;
-    e->drop_graphs();      // instantiated graphs hold arena pointers
+    e->state->arena_moved();
     if (e->ws) { HIPCHK(e, hipDeviceSynchronize()); HIPCHK(e, hipFree(e->ws)); e->ws = nullptr; e->ws_cap = 0; }
     HIPCHK(e, hipMalloc((void**)&e->ws, bytes));
     e->ws_cap = bytes;
@@ -280,7 +288,8 @@ int make_plan(st_engine* e, int B, int T, bool cfg, int n_t, Plan* p) {
 }
 
 int ensure_rope(st_engine* e, int T, hipStream_t s) {
-    if (T <= e->rope_T) return ST_OK;
+    DitState* dit = dit_of(e);
+    if (T <= dit->rope_T) return ST_OK;
     // cos/sin cache of RotaryPositionalEmbeddings._build_cache (diffusion_transformer.py:145-171),
     // d = head_dim/2 = 32 rotary features -> 16 angles theta_j = 10000^(-2j/32), fp32 arithmetic.
     const int newT = (T + 255) / 256 * 256;
@@ -293,16 +302,16 @@ int ensure_rope(st_engine* e, int T, hipStream_t s) {
             hs[(size_t)t * 16 + j] = sinf(ang);
         }
     }
-    if (e->rope_cos) {
-        e->drop_graphs();      // instantiated graphs bake the old table pointers into the QKV kernel arguments
-        HIPCHK(e, hipDeviceSynchronize()); hipFree(e->rope_cos); hipFree(e->rope_sin);
-        e->rope_cos = e->rope_sin = nullptr; e->rope_T = 0;
+    if (dit->rope_cos) {
+        dit->drop_graphs();      // instantiated graphs bake the old table pointers into the QKV kernel arguments
+        HIPCHK(e, hipDeviceSynchronize()); hipFree(dit->rope_cos); hipFree(dit->rope_sin);
+        dit->rope_cos = dit->rope_sin = nullptr; dit->rope_T = 0;
     }
-    HIPCHK(e, hipMalloc((void**)&e->rope_cos, hc.size() * 4));
-    HIPCHK(e, hipMalloc((void**)&e->rope_sin, hs.size() * 4));
-    HIPCHK(e, hipMemcpy(e->rope_cos, hc.data(), hc.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(e, hipMemcpy(e->rope_sin, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
-    e->rope_T = newT;
+    HIPCHK(e, hipMalloc((void**)&dit->rope_cos, hc.size() * 4));
+    HIPCHK(e, hipMalloc((void**)&dit->rope_sin, hs.size() * 4));
+    HIPCHK(e, hipMemcpy(dit->rope_cos, hc.data(), hc.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(dit->rope_sin, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
+    dit->rope_T = newT;
     (void)s;
     return ST_OK;
 }
@@ -318,7 +327,7 @@ ConvGemmArgs base_args(const st_engine* e, const Plan& p, const Conv& cv, int n_
     // ragged batches: tiles past an utterance's last needed frame are skipped (every frame is computed under debug
     // capture, whose taps are compared over the whole padded tensor).  The shared uncond prenet item (index B of B + 1)
     // is needed as far as the longest utterance: entry B of t_lim.
-    if (e->ragged_skip && !e->capture && e->kind == KIND_DECODER) { a.t_lim = p.t_lim; a.t_lim_mod = (n_items == p.B + 1) ? p.B + 1 : p.B; }
+    if (e->tile.ragged_skip && !e->capture && e->kind == KIND_DECODER) { a.t_lim = p.t_lim; a.t_lim_mod = (n_items == p.B + 1) ? p.B + 1 : p.B; }
     return a;
 }
 
@@ -330,29 +339,30 @@ inline double conv_flops(const Plan& p, const Conv& cv, int n_items) {
 
 // cond prenet (estimator.py:83-89,118) + the loop-invariant cond half of in_proj (:120-121)
 int run_prenet(st_engine* e, const Plan& p, hipStream_t s) {
+    DitState* dit = dit_of(e);
     {
-        ConvGemmArgs a = base_args(e, p, e->pre[0], p.Pn);
-        a.a0 = p.mu16; a.c0 = e->Mp; a.flags = GF_SILU; a.out16 = p.pre1;
-        ProfScope ps(e, s, PC_PRENET, conv_flops(p, e->pre[0], p.Pn));
+        ConvGemmArgs a = base_args(e, p, dit->pre[0], p.Pn);
+        a.a0 = p.mu16; a.c0 = dit->Mp; a.flags = GF_SILU; a.out16 = p.pre1;
+        ProfScope ps(e, s, PC_PRENET, conv_flops(p, dit->pre[0], p.Pn));
         HIPCHK(e, gemm(e, 3, EPI_ACT16, a, s));
     }
     {
-        ConvGemmArgs a = base_args(e, p, e->pre[1], p.Pn);
-        a.a0 = p.pre1; a.c0 = e->F; a.flags = GF_SILU; a.out16 = p.pre2;
-        ProfScope ps(e, s, PC_PRENET, conv_flops(p, e->pre[1], p.Pn));
+        ConvGemmArgs a = base_args(e, p, dit->pre[1], p.Pn);
+        a.a0 = p.pre1; a.c0 = dit->F; a.flags = GF_SILU; a.out16 = p.pre2;
+        ProfScope ps(e, s, PC_PRENET, conv_flops(p, dit->pre[1], p.Pn));
         HIPCHK(e, gemm(e, 3, EPI_ACT16, a, s));
     }
     {
-        ConvGemmArgs a = base_args(e, p, e->pre[2], p.Pn);
-        a.a0 = p.pre2; a.c0 = e->F; a.out16 = p.cond16; a.out16_lo = p.cond16lo;
-        ProfScope ps(e, s, PC_PRENET, conv_flops(p, e->pre[2], p.Pn));
+        ConvGemmArgs a = base_args(e, p, dit->pre[2], p.Pn);
+        a.a0 = p.pre2; a.c0 = dit->F; a.out16 = p.cond16; a.out16_lo = p.cond16lo;
+        ProfScope ps(e, s, PC_PRENET, conv_flops(p, dit->pre[2], p.Pn));
         HIPCHK(e, gemm(e, 3, EPI_F32, a, s));
     }
-    capture(e, "cond", p.cond16, (int64_t)p.Pn * p.T * e->C, true, s);
+    capture(e, "cond", p.cond16, (int64_t)p.Pn * p.T * dit->C, true, s);
     {   // K = [cond_hi | cond_lo | cond_hi] against [W_hi | W_hi | W_lo]: once per solve, so the extra MFMA work is free
-        ConvGemmArgs a = base_args(e, p, e->inc, p.Pn);
-        a.a0 = p.cond16; a.c0 = e->C; a.a1 = p.cond16lo; a.c1 = e->C; a.c2 = e->C; a.out32 = p.cpart;
-        ProfScope ps(e, s, PC_INPROJ, conv_flops(p, e->inc, p.Pn));
+        ConvGemmArgs a = base_args(e, p, dit->inc, p.Pn);
+        a.a0 = p.cond16; a.c0 = dit->C; a.a1 = p.cond16lo; a.c1 = dit->C; a.c2 = dit->C; a.out32 = p.cpart;
+        ProfScope ps(e, s, PC_INPROJ, conv_flops(p, dit->inc, p.Pn));
         HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
     }
     return ST_OK;
@@ -360,13 +370,14 @@ int run_prenet(st_engine* e, const Plan& p, hipStream_t s) {
 
 // adaLN-Zero parameters from the speaker vectors (diffusion_transformer.py:92-96,110): loop invariant
 int run_adaln(st_engine* e, const Plan& p, hipStream_t s) {
-    const int C = e->C;
+    DitState* dit = dit_of(e);
+    const int C = dit->C;
     ProfScope ps(e, s, PC_PREP, 0);
-    if (e->G == C) HIPCHK(e, launch_silu_rows(p.cvec, (int64_t)p.N * C, p.ada_tmp, s));      // SiLU(c): the same input for every block
-    for (int i = 0; i < e->L; ++i) {
-        const std::string pre = e->blk(i) + "adaLN_modulation.";
-        if (e->G != C) {
-            HIPCHK(e, launch_linear(p.cvec, p.N, e->G, P(e, pre + "0.weight"), P(e, pre + "0.bias"), C, p.ada_tmp, 0, 0, s));
+    if (dit->G == C) HIPCHK(e, launch_silu_rows(p.cvec, (int64_t)p.N * C, p.ada_tmp, s));      // SiLU(c): the same input for every block
+    for (int i = 0; i < dit->L; ++i) {
+        const std::string pre = dit->blk(i) + "adaLN_modulation.";
+        if (dit->G != C) {
+            HIPCHK(e, launch_linear(p.cvec, p.N, dit->G, P(e, pre + "0.weight"), P(e, pre + "0.bias"), C, p.ada_tmp, 0, 0, s));
             HIPCHK(e, launch_linear(p.ada_tmp, p.N, C, P(e, pre + "2.weight"), P(e, pre + "2.bias"), 6 * C,
                                     p.ada + (size_t)i * p.N * 6 * C, 1, 0, s));
         } else {
@@ -379,12 +390,13 @@ int run_adaln(st_engine* e, const Plan& p, hipStream_t s) {
 
 // time embedding -> MLP -> FiLM (gamma, beta) for every evaluation time (estimator.py:117,31-33)
 int run_time_tables(st_engine* e, const Plan& p, hipStream_t s) {
-    const int C = e->C, F = e->F;
+    DitState* dit = dit_of(e);
+    const int C = dit->C, F = dit->F;
     ProfScope ps(e, s, PC_PREP, 0);
     HIPCHK(e, launch_time_embed(p.tvals, p.n_t, C, p.emb, s));
     HIPCHK(e, launch_linear(p.emb, p.n_t, C, P(e, "time_mlp.layer.0.weight"), P(e, "time_mlp.layer.0.bias"), F, p.th, 0, 1, s));
     HIPCHK(e, launch_linear(p.th, p.n_t, F, P(e, "time_mlp.layer.2.weight"), P(e, "time_mlp.layer.2.bias"), C, p.tau, 0, 0, s));
-    for (int i = 0; i < e->L; ++i) {
+    for (int i = 0; i < dit->L; ++i) {
         const std::string pre = "blocks." + std::to_string(i) + ".time_fusion.film.";
         HIPCHK(e, launch_linear(p.tau, p.n_t, C, P(e, pre + "weight"), P(e, pre + "bias"), 2 * C,
                                 p.film + (size_t)i * p.n_t * 2 * C, 0, 0, s));
@@ -400,7 +412,8 @@ int run_time_tables(st_engine* e, const Plan& p, hipStream_t s) {
 // Every FiLM + LayerNorm + modulate runs inside the epilogue of the GEMM that produces its input (row-complete
 // tiles): in_proj -> LN1 of block 0, FFN conv_2 -> LN1 of the next block, long-skip conv -> LN1, out-proj -> LN2.
 int run_estimator(st_engine* e, const Plan& p, const float* mask, int ev, hipStream_t s) {
-    const int C = e->C, F = e->F, L = e->L, N = p.N, T = p.T;
+    DitState* dit = dit_of(e);
+    const int C = dit->C, F = dit->F, L = dit->L, N = p.N, T = p.T;
     const int64_t rowsC = (int64_t)N * T * C;
     const bool cap = e->capture;
     // What the text encoder's blocks leave out of the decoder's, said once:
@@ -409,8 +422,8 @@ int run_estimator(st_engine* e, const Plan& p, const float* mask, int ev, hipStr
     const bool skips = dec;      // U-Net long skips: skip16 copies out of the first half, long-skip convs into the second
     const bool dec_fast_paths = dec;      // decoder-only paths not yet passed for the text encoder: the weight-stationary out-projection,
                                           // the fused FFN, split q / k operands, the lse statistic, ragged tile skipping, x3's dead fp32 copy
-    const bool split_qk = dec_fast_paths && e->attn_split;
-    const bool ragged = dec_fast_paths && e->ragged_skip && !cap;
+    const bool split_qk = dec_fast_paths && dit->attn_split;
+    const bool ragged = dec_fast_paths && e->tile.ragged_skip && !cap;
     const int ln1_by_ffn = skips ? L / 2 : L;      // blocks below this take their LN1 from the previous block's conv_2 (the others from their long-skip conv)
     auto ada_of = [&](int i) { return p.ada + (size_t)i * N * 6 * C; };
     // [FiLM_i +] LN1_i + modulate (start of block i) fused into the producing GEMM
@@ -426,13 +439,13 @@ int run_estimator(st_engine* e, const Plan& p, const float* mask, int ev, hipStr
     };
     if (film) {   // in_proj: X = Wx.x + (Wc.cond + b); also the first long-skip (estimator.py:120-121,129).  The fp32 ODE state
         // enters as the operand pair (x_hi, x_lo): K = [x_hi | x_lo | x_hi] against [W_hi | W_hi | W_lo]
-        ConvGemmArgs a = base_args(e, p, e->inx, N);
-        a.a0 = p.x16; a.c0 = e->Mp; a.a0_mod = p.B; a.a1 = p.x16lo; a.c1 = e->Mp; a.a1_mod = p.B; a.c2 = e->Mp;
+        ConvGemmArgs a = base_args(e, p, dit->inx, N);
+        a.a0 = p.x16; a.c0 = dit->Mp; a.a0_mod = p.B; a.a1 = p.x16lo; a.c1 = dit->Mp; a.a1_mod = p.B; a.c2 = dit->Mp;
         a.bias = nullptr;
         a.add32 = p.cpart; a.add_clamp = p.B;
         a.out32 = p.X; a.out16 = p.skip16[0];
         fuse_ln1(a, 0);
-        ProfScope ps(e, s, PC_INPROJ, conv_flops(p, e->inx, N));
+        ProfScope ps(e, s, PC_INPROJ, conv_flops(p, dit->inx, N));
         HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
     } else {      // no GEMM in front of block 0: its LN1 + modulate as a kernel of its own
         FilmLnArgs a; memset(&a, 0, sizeof(a));
@@ -448,24 +461,24 @@ int run_estimator(st_engine* e, const Plan& p, const float* mask, int ev, hipStr
         const float* ada_i = ada_of(i);
         if (skips && i >= L / 2) {   // U-Net long skip merge (estimator.py:131-132)
             const int j = i - L / 2;
-            ConvGemmArgs a = base_args(e, p, e->lsc[j], N);
+            ConvGemmArgs a = base_args(e, p, dit->lsc[j], N);
             a.a0 = p.cur16; a.c0 = C; a.a1 = p.skip16[L - 1 - i]; a.c1 = C;
             a.out32 = p.X;
             fuse_ln1(a, i);
-            ProfScope ps(e, s, PC_LSC, conv_flops(p, e->lsc[j], N));
-            if (!(e->skip_mask >> PC_LSC & 1)) HIPCHK(e, gemm(e, 3, EPI_F32, a, s));
+            ProfScope ps(e, s, PC_LSC, conv_flops(p, dit->lsc[j], N));
+            if (!(dit->skip_mask >> PC_LSC & 1)) HIPCHK(e, gemm(e, 3, EPI_F32, a, s));
         }
         if (cap) { capture(e, bn + "x1", p.X, rowsC, false, s); capture(e, bn + "h1", p.h16, rowsC, true, s); }
         {   // q, k, v projections + RoPE (diffusion_transformer.py:59-61,74-75)
-            ConvGemmArgs a = base_args(e, p, e->qkv[i], N);
+            ConvGemmArgs a = base_args(e, p, dit->qkv[i], N);
             a.a0 = p.h16; a.c0 = C;
-            a.q = p.q16; a.k = p.k16; a.vt = p.vt16; a.rope_cos = e->rope_cos; a.rope_sin = e->rope_sin;
+            a.q = p.q16; a.k = p.k16; a.vt = p.vt16; a.rope_cos = dit->rope_cos; a.rope_sin = dit->rope_sin;
             if (split_qk) { a.q_lo = p.q16lo; a.k_lo = p.k16lo; }      // (the generic tile writes the residual planes; the weight-stationary kernel has no room for them)
-            a.Tp = p.Tp; a.n_heads = e->H;
-            if ((int)e->qkv_frag.size() == L) a.w_frag = e->qkv_frag[i];
-            a.qscale = 1.4426950408889634f / sqrtf((float)(C / e->H));
-            ProfScope ps(e, s, PC_QKV, conv_flops(p, e->qkv[i], N));
-            if (!(e->skip_mask >> PC_QKV & 1)) HIPCHK(e, gemm(e, 1, EPI_QKV, a, s));
+            a.Tp = p.Tp; a.n_heads = dit->H;
+            if ((int)dit->qkv_frag.size() == L) a.w_frag = dit->qkv_frag[i];
+            a.qscale = 1.4426950408889634f / sqrtf((float)(C / dit->H));
+            ProfScope ps(e, s, PC_QKV, conv_flops(p, dit->qkv[i], N));
+            if (!(dit->skip_mask >> PC_QKV & 1)) HIPCHK(e, gemm(e, 1, EPI_QKV, a, s));
         }
         if (cap) {
             capture(e, bn + "q", p.q16, rowsC, true, s); capture(e, bn + "k", p.k16, rowsC, true, s);
@@ -474,51 +487,51 @@ int run_estimator(st_engine* e, const Plan& p, const float* mask, int ev, hipStr
         {
             AttnArgs a; memset(&a, 0, sizeof(a));
             a.q = p.q16; a.k = p.k16; a.vt = p.vt16; a.out = p.ao16; a.kbias = p.kbias; a.mask_mod = p.B; a.zeros = e->zeros;
-            a.kv_end = p.kv_end; a.n_full = p.n_full; a.T = T; a.Tp = p.Tp; a.H = e->H; a.n_items = N;
-            a.small_max_blocks = e->conc == 1 ? e->attn_small_blocks : 0;
+            a.kv_end = p.kv_end; a.n_full = p.n_full; a.T = T; a.Tp = p.Tp; a.H = dit->H; a.n_items = N;
+            a.small_max_blocks = dit->conc == 1 ? dit->attn_small_blocks : 0;
             if (split_qk) { a.q_lo = p.q16lo; a.k_lo = p.k16lo; }
-            if (dec_fast_paths) a.lse_max = e->lse_cells;
+            if (dec_fast_paths) a.lse_max = dit->lse_cells;
             if (ragged) a.t_lim = p.t_lim;
-            ProfScope ps(e, s, PC_ATTN, 4.0 * (double)N * e->H * (double)T * T * (C / e->H));
-            if (!(e->skip_mask >> PC_ATTN & 1)) HIPCHK(e, launch_attention(e->dt, a, s));
+            ProfScope ps(e, s, PC_ATTN, 4.0 * (double)N * dit->H * (double)T * T * (C / dit->H));
+            if (!(dit->skip_mask >> PC_ATTN & 1)) HIPCHK(e, launch_attention(e->dt, a, s));
         }
         if (cap) capture(e, bn + "attn", p.ao16, rowsC, true, s);
         // Big grids: the whole FFN as ONE kernel, u never leaves the CU (ffn_fused.h; bit-identical to the two launches below).
         // Debug capture keeps the two-kernel path (it taps u).
-        const bool fused = dec_fast_paths && e->fused_ffn && !cap && (int)e->ffn_stream.size() == L && e->ffn_stream[i] &&
-                           (int64_t)e->conc * N * ((T + kFfnFusedFrames - 1) / kFfnFusedFrames) >= e->big_min_blocks;
+        const bool fused = dec_fast_paths && dit->fused_ffn && !cap && (int)dit->ffn_stream.size() == L && dit->ffn_stream[i] &&
+                           (int64_t)dit->conc * N * ((T + kFfnFusedFrames - 1) / kFfnFusedFrames) >= e->tile.big_min_blocks;
         void* h2buf = fused ? p.h2_16 : p.h16;
         {   // out projection, gate, mask, residual (diffusion_transformer.py:65,111) + LN2, modulate, mask (:112,26)
-            ConvGemmArgs a = base_args(e, p, e->oproj[i], N);
+            ConvGemmArgs a = base_args(e, p, dit->oproj[i], N);
             a.a0 = p.ao16; a.c0 = C; a.mask = mask; a.gate = ada_i + 2 * C; a.gate_stride = 6 * C; a.out32 = p.X;
             a.ln_h16 = h2buf; a.ln_film = nullptr; a.ln_film_mod = 1;
             a.ln_ada = ada_i; a.ln_ada_stride = 6 * C; a.ln_shift_off = 3 * C; a.ln_scale_off = 4 * C; a.ln_mask_out = 1;
-            if (dec_fast_paths && (int)e->oproj_frag.size() == L && !cap) a.w_frag = e->oproj_frag[i];
-            ProfScope ps(e, s, PC_OPROJ, conv_flops(p, e->oproj[i], N));
-            if (!(e->skip_mask >> PC_OPROJ & 1)) HIPCHK(e, gemm(e, 1, EPI_RESGATE, a, s));
+            if (dec_fast_paths && (int)dit->oproj_frag.size() == L && !cap) a.w_frag = dit->oproj_frag[i];
+            ProfScope ps(e, s, PC_OPROJ, conv_flops(p, dit->oproj[i], N));
+            if (!(dit->skip_mask >> PC_OPROJ & 1)) HIPCHK(e, gemm(e, 1, EPI_RESGATE, a, s));
         }
         if (cap) { capture(e, bn + "x2", p.X, rowsC, false, s); capture(e, bn + "h2", p.h16, rowsC, true, s); }
         if (!fused) {   // FFN conv_1 + SiLU + mask (diffusion_transformer.py:26-28)
-            ConvGemmArgs a = base_args(e, p, e->ffn1[i], N);
+            ConvGemmArgs a = base_args(e, p, dit->ffn1[i], N);
             a.a0 = p.h16; a.c0 = C; a.mask = mask; a.flags = GF_SILU | GF_MASK; a.out16 = p.u16;
-            ProfScope ps(e, s, PC_FFN1, conv_flops(p, e->ffn1[i], N));
+            ProfScope ps(e, s, PC_FFN1, conv_flops(p, dit->ffn1[i], N));
             HIPCHK(e, gemm(e, 3, EPI_ACT16, a, s));
         }
         if (cap) capture(e, bn + "u", p.u16, (int64_t)N * T * F, true, s);
         void* copy16 = (skips && i + 1 < L / 2) ? p.skip16[i + 1] : p.cur16;
         {   // FFN conv_2, mask, gate, residual (diffusion_transformer.py:29-30,112) [+ FiLM/LN1 of block i+1]
-            ConvGemmArgs a = base_args(e, p, e->ffn2[i], N);
+            ConvGemmArgs a = base_args(e, p, dit->ffn2[i], N);
             a.a0 = p.u16; a.c0 = F; a.mask = mask; a.gate = ada_i + 5 * C; a.gate_stride = 6 * C; a.out32 = p.X;
-            if (fused) { a.a0 = h2buf; a.c0 = C; a.w = e->ffn_stream[i]; a.bias1 = e->ffn1[i].bias; a.cmid = F; a.flags = GF_SILU | GF_MASK; }
+            if (fused) { a.a0 = h2buf; a.c0 = C; a.w = dit->ffn_stream[i]; a.bias1 = dit->ffn1[i].bias; a.cmid = F; a.flags = GF_SILU | GF_MASK; }
             a.out16 = copy16;
             if (i + 1 == L) a.out16_lo = p.cur16lo;        // operand pair of final_proj / proj
             if (i + 1 < ln1_by_ffn) fuse_ln1(a, i + 1);    // the decoder's blocks >= L/2 start with the long-skip conv instead
             // ... which rebuilds the residual stream from the 16-bit operands (and final_proj reads only those): from
             // block L/2 - 1 on the fp32 copy of x3 is dead, so it is not written (40 % of this epilogue's HBM bytes)
             else if (dec_fast_paths && !cap) a.out32_readonly = 1;
-            ProfScope ps(e, s, PC_FFN2, conv_flops(p, e->ffn2[i], N) + (fused ? conv_flops(p, e->ffn1[i], N) : 0.0));
-            if (e->skip_mask >> PC_FFN2 & 1) {}
-            else if (fused && e->fused_ffn == 3) HIPCHK(e, launch_ffn_wino_f16(a, s));
+            ProfScope ps(e, s, PC_FFN2, conv_flops(p, dit->ffn2[i], N) + (fused ? conv_flops(p, dit->ffn1[i], N) : 0.0));
+            if (dit->skip_mask >> PC_FFN2 & 1) {}
+            else if (fused && dit->fused_ffn == 3) HIPCHK(e, launch_ffn_wino_f16(a, s));
             else if (fused) HIPCHK(e, e->dt == DT_BF16 ? launch_ffn_fused_bf16(a, s) : launch_ffn_fused_f16(a, s));
             else HIPCHK(e, gemm(e, 3, EPI_RESGATE, a, s));
         }
@@ -528,12 +541,12 @@ int run_estimator(st_engine* e, const Plan& p, const float* mask, int ev, hipStr
         }
     }
     {   // final_proj (estimator.py:136-138) / mu_x = proj(x) * x_mask (text_encoder.py:42); block output is already zero on padded frames
-        ConvGemmArgs a = base_args(e, p, e->fin, N);
+        ConvGemmArgs a = base_args(e, p, dit->fin, N);
         a.a0 = p.cur16; a.c0 = C; a.a1 = p.cur16lo; a.c1 = C; a.c2 = C; a.mask = mask; a.flags = GF_MASK; a.out32 = p.v32;
-        ProfScope ps(e, s, PC_FINAL, conv_flops(p, e->fin, N));
+        ProfScope ps(e, s, PC_FINAL, conv_flops(p, dit->fin, N));
         HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
     }
-    if (cap) capture(e, "v", p.v32, (int64_t)N * T * e->Mp, false, s);
+    if (cap) capture(e, "v", p.v32, (int64_t)N * T * dit->Mp, false, s);
     return ST_OK;
 }
 
@@ -556,22 +569,30 @@ int check_dropout(st_engine* e, float p_dropout) {
     return p_dropout >= 0.0f && p_dropout < 1.0f ? ST_OK : e->fail(ST_ERR_INVALID, "p_dropout must be in [0, 1)");
 }
 
-int check_ready(st_engine* e, int B, int T) {
+int check_ready(st_engine* e, Kind kind, int B, int T) {
     if (!e) return ST_ERR_INVALID;
     int rc = check_finalized(e); if (rc) return rc;
     if ((rc = check_sizes(e, B, T))) return rc;
-    if ((int64_t)2 * B * T * e->F >= (int64_t)1 << 31) return e->fail(ST_ERR_INVALID, "B*T too large for 32-bit row indexing");
-    return ST_OK;
+    const DitState* dit = dit_or_null(e);
+    if (dit && (int64_t)2 * B * T * dit->F >= (int64_t)1 << 31) return e->fail(ST_ERR_INVALID, "B*T too large for 32-bit row indexing");
+    return check_handle(e, kind);
 }
 
-int new_handle(Kind kind, int device, st_engine** out) {
+int new_handle(Kind kind, int device, std::unique_ptr<KindState> state, st_engine** out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { g_create_error = "no such HIP device"; return ST_ERR_HIP; }
     if (hipSetDevice(device) != hipSuccess) { g_create_error = "hipSetDevice failed"; return ST_ERR_HIP; }
     st_engine* e = new st_engine();
-    e->device = device; e->kind = kind;
+    e->device = device; e->kind = kind; e->state = std::move(state);
     *out = e;
     return ST_OK;
+}
+
+int KindState::repack(st_engine* e, hipStream_t) { return e->fail(ST_ERR_UNSUPPORTED, repack_refusal); }
+
+void free_owned(st_engine* e) {
+    for (void* p : e->owned) hipFree(p);
+    e->owned.clear(); e->weight_bytes = 0;
 }
 
 // st_load_param / st_bind_param: the table row of `name`, if the caller's shape is the expected one
@@ -615,49 +636,49 @@ static int create_engine(const st_config* cfg, Kind kind, int n_vocab, int devic
     if (cfg->gin_channels < 4 || cfg->gin_channels % 4 != 0) return bad("gin_channels must be a positive multiple of 4");
     if (cfg->operand_dtype != ST_OPERAND_BF16 && cfg->operand_dtype != ST_OPERAND_F16) return bad("operand_dtype");
     st_engine* e = nullptr;
-    if (int rc = new_handle(kind, device, &e)) return rc;
-    e->cfg = *cfg;
+    if (int rc = new_handle(kind, device, std::make_unique<DitState>(), &e)) return rc;
+    DitState* dit = dit_of(e);
+    dit->cfg = *cfg; dit->dec = kind == KIND_DECODER;
     e->dt = cfg->operand_dtype == ST_OPERAND_BF16 ? DT_BF16 : DT_F16;
-    e->M = cfg->noise_channels; e->Mp = (e->M + 127) / 128 * 128;
-    e->C = cfg->hidden_channels; e->F = cfg->filter_channels; e->H = cfg->n_heads; e->L = cfg->n_layers;
-    e->K = cfg->kernel_size; e->G = cfg->gin_channels;
-    e->n_vocab = n_vocab;
-    if (const char* mb = getenv("ST_BIG_MIN_BLOCKS")) e->big_min_blocks = atoi(mb);
-    if (const char* v = getenv("ST_PHASED")) e->phased = atoi(v);
-    if (const char* v = getenv("ST_FUSED_FFN")) e->fused_ffn = atoi(v);
+    dit->M = cfg->noise_channels; dit->Mp = (dit->M + 127) / 128 * 128;
+    dit->C = cfg->hidden_channels; dit->F = cfg->filter_channels; dit->H = cfg->n_heads; dit->L = cfg->n_layers;
+    dit->K = cfg->kernel_size; dit->G = cfg->gin_channels;
+    dit->n_vocab = n_vocab;
+    if (const char* mb = getenv("ST_BIG_MIN_BLOCKS")) e->tile.big_min_blocks = atoi(mb);
+    if (const char* v = getenv("ST_PHASED")) e->tile.phased = atoi(v);
+    if (const char* v = getenv("ST_FUSED_FFN")) dit->fused_ffn = atoi(v);
     // Default = the direct fused kernel, bit-identical to the two-kernel path.  Round 5 put the Winograd form on trial with O(1) adaLN
     // gates at B = 32 x T = 1000 (tools/parity_trained.py): one evaluation 8.8e-4 against the direct kernel's 7.3e-4 -- too close to the
     // 1e-3 bar for a 1.45 % gain, so it is opt-in (ST_FUSED_FFN=3; f16 only: it forms its operands with packed f16 adds).
-    if (e->fused_ffn < 0 || e->fused_ffn > 3 || e->fused_ffn == 2) e->fused_ffn = 1;
-    if (e->fused_ffn == 3 && e->dt != DT_F16) e->fused_ffn = 1;
-    if (const char* v = getenv("ST_RAGGED_SKIP")) e->ragged_skip = atoi(v);
+    if (dit->fused_ffn < 0 || dit->fused_ffn > 3 || dit->fused_ffn == 2) dit->fused_ffn = 1;
+    if (dit->fused_ffn == 3 && e->dt != DT_F16) dit->fused_ffn = 1;
+    if (const char* v = getenv("ST_RAGGED_SKIP")) e->tile.ragged_skip = atoi(v);
 #ifdef ST_DEVTOOLS      // developer builds only (ST_BUILD_DEFS=-DST_DEVTOOLS): a shipping library must not return garbage because of an environment variable
-    if (const char* v = getenv("ST_SKIP_CLASSES")) e->skip_mask = (unsigned)strtoul(v, nullptr, 0);
+    if (const char* v = getenv("ST_SKIP_CLASSES")) dit->skip_mask = (unsigned)strtoul(v, nullptr, 0);
 #endif
-    if (const char* v = getenv("ST_QKV_WS")) e->qkv_ws = atoi(v);
-    if (const char* v = getenv("ST_QKV_WS_MIN_TILES")) e->qkv_ws_min_tiles = atoi(v);
-    if (const char* v = getenv("ST_OPROJ_WS")) e->oproj_ws = atoi(v);
-    if (const char* v = getenv("ST_OPROJ_WS_MIN_TILES")) e->oproj_ws_min_tiles = atoi(v);
-    if (const char* v = getenv("ST_QKV_RC1")) e->qkv_rc1 = atoi(v);     // 0: compute every padded frame tile (A/B runs)
+    if (const char* v = getenv("ST_QKV_WS")) dit->qkv_ws = atoi(v);
+    if (const char* v = getenv("ST_QKV_WS_MIN_TILES")) dit->qkv_ws_min_tiles = atoi(v);
+    if (const char* v = getenv("ST_OPROJ_WS")) dit->oproj_ws = atoi(v);
+    if (const char* v = getenv("ST_OPROJ_WS_MIN_TILES")) dit->oproj_ws_min_tiles = atoi(v);
+    if (const char* v = getenv("ST_QKV_RC1")) dit->qkv_rc1 = atoi(v);     // 0: compute every padded frame tile (A/B runs)
     if (const char* v = getenv("ST_SMALL_GRID")) {      // 0: none of the small-grid variants (split-K convs, 64-frame tiles,
         if (atoi(v) == 0) {                               // key-split attention): results independent of the batch composition
-            e->splitk_target = 0; e->small_tiles = 0; e->attn_small_blocks = 0;
+            e->tile.splitk_target = 0; e->tile.small_tiles = 0; dit->attn_small_blocks = 0;
         }
     }
     build_param_table(e);
-    if (hipMalloc((void**)&e->kpart, kSplitKBytes) == hipSuccess) e->kpart_bytes = kSplitKBytes; else e->kpart = nullptr;
-    if (hipMalloc(&e->sink, 65536) != hipSuccess) e->sink = nullptr;      // (without it the q/k/v projection stays on the generic tile)
-    if (hipMalloc((void**)&e->lse_cells, kLseCells * 64) != hipSuccess ||
-        hipMemsetD32((hipDeviceptr_t)e->lse_cells, (int)0x80000000, kLseCells * 16) != hipSuccess) { (void)hipGetLastError(); e->lse_cells = nullptr; }
+    if (hipMalloc((void**)&e->tile.kpart, kSplitKBytes) == hipSuccess) e->tile.kpart_bytes = kSplitKBytes; else e->tile.kpart = nullptr;
+    if (hipMalloc(&dit->sink, 65536) != hipSuccess) dit->sink = nullptr;      // (without it the q/k/v projection stays on the generic tile)
+    if (hipMalloc((void**)&dit->lse_cells, kLseCells * 64) != hipSuccess ||
+        hipMemsetD32((hipDeviceptr_t)dit->lse_cells, (int)0x80000000, kLseCells * 16) != hipSuccess) { (void)hipGetLastError(); dit->lse_cells = nullptr; }
     if (hipMalloc(&e->zeros, 256) != hipSuccess || hipMemset(e->zeros, 0, 256) != hipSuccess) {
         g_create_error = "hipMalloc failed";
-        if (e->kpart) hipFree(e->kpart);
         delete e;
         return ST_ERR_HIP;
     }
-    if (hipHostMalloc((void**)&e->status_host, sizeof(int), hipHostMallocMapped) == hipSuccess &&
-        hipHostGetDevicePointer((void**)&e->status_dev, e->status_host, 0) == hipSuccess) *e->status_host = 0;
-    else { (void)hipGetLastError(); e->status_host = nullptr; e->status_dev = nullptr; }      // (guard unavailable: st_output_status says so)
+    if (hipHostMalloc((void**)&dit->status_host, sizeof(int), hipHostMallocMapped) == hipSuccess &&
+        hipHostGetDevicePointer((void**)&dit->status_dev, dit->status_host, 0) == hipSuccess) *dit->status_host = 0;
+    else { (void)hipGetLastError(); dit->status_host = nullptr; dit->status_dev = nullptr; }      // (guard unavailable: st_output_status says so)
     *out = e;
     return ST_OK;
 }
@@ -672,34 +693,6 @@ void st_destroy(st_engine* e) {
     if (!e) return;
     hipSetDevice(e->device);
     hipDeviceSynchronize();
-    e->drop_graphs();
-    train_destroy(e);
-    vocos_destroy(e);
-    style_destroy(e);
-    duration_destroy(e);
-    mel_destroy(e);
-    period_disc_destroy(e);
-    resolution_disc_destroy(e);
-    ffgan_destroy(e);
-    sd_train_destroy(e);
-    if (e->gstream) hipStreamDestroy(e->gstream);
-    e->part_streams.destroy();
-    for (auto& kv : e->params) if (kv.second.dev && !kv.second.borrowed) hipFree(kv.second.dev);
-    for (void* p : e->owned) hipFree(p);
-    for (auto& kv : e->caps) if (kv.second.dev) hipFree(kv.second.dev);
-    prof_collect(e);
-    for (hipEvent_t ev : e->ev_pool) hipEventDestroy(ev);
-    if (e->ws) hipFree(e->ws);
-    if (e->adams_buf) hipFree(e->adams_buf);
-    if (e->pk_fwd.dev) hipFree(e->pk_fwd.dev);
-    if (e->pk_T.dev) hipFree(e->pk_T.dev);
-    if (e->rope_cos) hipFree(e->rope_cos);
-    if (e->rope_sin) hipFree(e->rope_sin);
-    if (e->zeros) hipFree(e->zeros);
-    if (e->sink) hipFree(e->sink);
-    if (e->lse_cells) hipFree(e->lse_cells);
-    if (e->kpart) hipFree(e->kpart);
-    if (e->status_host) hipHostFree(e->status_host);
     delete e;
 }
 
@@ -722,9 +715,7 @@ int st_load_param(st_engine* e, const char* name, const float* data, const int64
     Param& p = *pp;
     HIPCHK(e, hipSetDevice(e->device));
     if (p.borrowed) { p.dev = nullptr; p.borrowed = false; }
-    if (!p.dev) {       // new pointer: the recorded re-pack jobs are stale, and so are instantiated graphs (they bake the fp32
-        HIPCHK(e, hipMalloc((void**)&p.dev, (size_t)p.numel() * 4)); pk_drop(e); e->drop_graphs();      // pointers of the adaLN / FiLM / time-MLP linears)
-    }
+    if (!p.dev) { HIPCHK(e, hipMalloc((void**)&p.dev, (size_t)p.numel() * 4)); e->state->params_moved(); }
     HIPCHK(e, hipMemcpy(p.dev, data, (size_t)p.numel() * 4, hipMemcpyDefault));
     p.loaded = true;
     e->finalized = false;
@@ -745,32 +736,13 @@ int st_bind_param(st_engine* e, const char* name, const float* data, const int64
     p.borrowed = true;
     p.loaded = true;
     e->finalized = false;
-    pk_drop(e);             // the recorded re-pack jobs hold the old pointer ...
-    e->drop_graphs();       // ... and instantiated solve graphs read the fp32 linears (adaLN, FiLM, time MLP) through it
+    e->state->params_moved();
     return ST_OK;
 }
 
 int st_repack(st_engine* e, void* stream) {
     if (!e) return ST_ERR_INVALID;
-    if (e->kind == KIND_VOCODER || e->kind == KIND_FFGAN) return e->fail(ST_ERR_UNSUPPORTED, "st_repack: vocoder handles re-pack through st_finalize");
-    if (e->kind == KIND_MEL_EXTRACTOR) return e->fail(ST_ERR_UNSUPPORTED, "st_repack: mel-extractor handles re-read their filter bank through st_finalize");
-    if (reads_params_in_place(e->kind)) return e->fail(ST_ERR_UNSUPPORTED, "st_repack: style-encoder / duration-predictor handles read their parameters in place");
-    if (e->kind == KIND_PERIOD_DISC || e->kind == KIND_RESOLUTION_DISC) {      // the weight norm again, on the caller's stream
-        if (!e->finalized) return e->fail(ST_ERR_STATE, "st_repack after st_bind_param / st_load_param of a new pointer: call st_finalize");
-        HIPCHK(e, hipSetDevice(e->device));
-        return e->kind == KIND_PERIOD_DISC ? period_disc_weights(e, (hipStream_t)stream) : resolution_disc_weights(e, (hipStream_t)stream);
-    }
-    if (!e->packed_once) return e->fail(ST_ERR_STATE, "st_repack needs one earlier st_finalize (it allocates the packed buffers)");
-    // A re-bind / re-load since the last st_finalize may have moved fp32 tensors: st_repack is for in-place updates only.
-    if (!e->finalized && !e->pk_fwd.ready)
-        return e->fail(ST_ERR_STATE, "st_repack after st_bind_param / st_load_param of a new pointer: call st_finalize");
-    for (auto& kv : e->params)
-        if (!kv.second.loaded) return e->fail(ST_ERR_STATE, "parameter not loaded: " + kv.first);
-    HIPCHK(e, hipSetDevice(e->device));
-    int rc = pack_all(e, (hipStream_t)stream); if (rc) return rc;
-    train_invalidate(e);
-    e->finalized = true;
-    return ST_OK;
+    return e->state->repack(e, (hipStream_t)stream);
 }
 
 int st_finalize(st_engine* e) {
@@ -779,51 +751,74 @@ int st_finalize(st_engine* e) {
     for (auto& kv : e->params)
         if (!kv.second.loaded) return e->fail(ST_ERR_STATE, "parameter not loaded: " + kv.first);
     HIPCHK(e, hipDeviceSynchronize());
-    if (e->kind == KIND_MEL_EXTRACTOR) return mel_finalize(e);      // the filter bank's band table
-    if (e->kind == KIND_PERIOD_DISC || e->kind == KIND_RESOLUTION_DISC) {      // the weight norm of the new tensors
-        if (int rc = e->kind == KIND_PERIOD_DISC ? period_disc_weights(e, nullptr) : resolution_disc_weights(e, nullptr)) return rc;
-        HIPCHK(e, hipDeviceSynchronize());
-        e->finalized = true;
-        return ST_OK;
-    }
-    if (reads_params_in_place(e->kind)) {
-        if (e->sdt) e->sdt->have = false;      // a re-bind / re-load: the held training activations are of other weights
-        e->finalized = true;
-        return ST_OK;
-    }
-    if (e->kind == KIND_VOCODER) {
-        if (e->sdt) e->sdt->have = false;      // st_vocos_train_forward's activations are of the weights before this re-bind / re-load
-        e->drop_graphs();
-        for (void* p : e->owned) hipFree(p);
-        e->owned.clear(); e->weight_bytes = 0;
-        return vocos_finalize(e);
-    }
-    if (e->kind == KIND_FFGAN) {
-        for (void* p : e->owned) hipFree(p);
-        e->owned.clear(); e->weight_bytes = 0;
-        return ffgan_finalize(e);
-    }
-    e->drop_graphs();          // instantiated graphs hold fp32 parameter pointers that a re-bind may have changed
-    pk_drop(e);                // ... and so do the recorded re-pack jobs
-    int rc = pack_all(e, nullptr); if (rc) return rc;
-    HIPCHK(e, hipDeviceSynchronize());
-    train_invalidate(e);
+    if (int rc = e->state->finalize(e)) return rc;
     e->finalized = true;
     return ST_OK;
 }
 
 }  // extern "C"
 
+st_engine::~st_engine() {
+    state.reset();
+    for (auto& kv : params) if (kv.second.dev && !kv.second.borrowed) hipFree(kv.second.dev);
+    for (void* p : owned) hipFree(p);
+    for (auto& kv : caps) if (kv.second.dev) hipFree(kv.second.dev);
+    prof_collect(this);
+    for (hipEvent_t ev : ev_pool) hipEventDestroy(ev);
+    if (ws) hipFree(ws);
+    if (zeros) hipFree(zeros);
+    if (tile.kpart) hipFree(tile.kpart);
+}
+
 namespace sthost {
-static void pk_push(st_engine::PackList& L, const PackJob& j0, size_t elems) {
+DitState::~DitState() {
+    drop_graphs();
+    train_destroy(this);
+    if (gstream) hipStreamDestroy(gstream);
+    part_streams.destroy();
+    if (adams_buf) hipFree(adams_buf);
+    if (pk_fwd.dev) hipFree(pk_fwd.dev);
+    if (pk_T.dev) hipFree(pk_T.dev);
+    if (rope_cos) hipFree(rope_cos);
+    if (rope_sin) hipFree(rope_sin);
+    if (sink) hipFree(sink);
+    if (lse_cells) hipFree(lse_cells);
+    if (status_host) hipHostFree(status_host);
+}
+
+int DitState::finalize(st_engine* e) {
+    params_moved();        // a re-bind may have changed the fp32 parameter pointers
+    int rc = pack_all(e, nullptr); if (rc) return rc;
+    HIPCHK(e, hipDeviceSynchronize());
+    train_invalidate(this);
+    return ST_OK;
+}
+
+int DitState::repack(st_engine* e, hipStream_t s) {
+    if (!packed_once) return e->fail(ST_ERR_STATE, "st_repack needs one earlier st_finalize (it allocates the packed buffers)");
+    // A re-bind / re-load since the last st_finalize may have moved fp32 tensors: st_repack is for in-place updates only.
+    if (!e->finalized && !pk_fwd.ready)
+        return e->fail(ST_ERR_STATE, "st_repack after st_bind_param / st_load_param of a new pointer: call st_finalize");
+    for (auto& kv : e->params)
+        if (!kv.second.loaded) return e->fail(ST_ERR_STATE, "parameter not loaded: " + kv.first);
+    HIPCHK(e, hipSetDevice(e->device));
+    int rc = pack_all(e, s); if (rc) return rc;
+    train_invalidate(this);
+    e->finalized = true;
+    return ST_OK;
+}
+
+int64_t DitState::device_bytes() const { return train_bytes(this); }
+
+static void pk_push(DitState::PackList& L, const PackJob& j0, size_t elems) {
     if (!L.recording) return;
     PackJob j = j0;
     j.blk0 = L.nblocks;
     L.jobs.push_back(j);
     L.nblocks += (unsigned)((elems + 255) / 256);
 }
-void pk_begin(st_engine::PackList& L) { L.jobs.clear(); L.nblocks = 0; L.ready = false; L.recording = true; }
-int pk_end(st_engine* e, st_engine::PackList& L, hipStream_t s) {
+void pk_begin(DitState::PackList& L) { L.jobs.clear(); L.nblocks = 0; L.ready = false; L.recording = true; }
+int pk_end(st_engine* e, DitState::PackList& L, hipStream_t s) {
     L.recording = false;
     if (L.jobs.empty()) return ST_OK;
     if (L.dev) { HIPCHK(e, hipStreamSynchronize(s)); hipFree(L.dev); L.dev = nullptr; }
@@ -833,26 +828,25 @@ int pk_end(st_engine* e, st_engine::PackList& L, hipStream_t s) {
     L.ready = true;
     return ST_OK;
 }
-bool pk_replay(st_engine* e, st_engine::PackList& L, hipStream_t s, int* rc) {
+bool pk_replay(st_engine* e, DitState::PackList& L, hipStream_t s, int* rc) {
     if (!L.ready) return false;
     *rc = ST_OK;
     if (launch_pack_jobs(e->dt, L.dev, (int)L.jobs.size(), L.nblocks, s) != hipSuccess) *rc = e->fail(ST_ERR_HIP, "launch_pack_jobs");
     return true;
 }
-void pk_drop(st_engine* e) { e->pk_fwd.ready = false; e->pk_T.ready = false; }
-int pk_weight(st_engine* e, st_engine::PackList& L, const float* src, int cout, int cin_total, int K, int ci_off, int ci_cnt, void* dst,
+int pk_weight(st_engine* e, DitState::PackList& L, const float* src, int cout, int cin_total, int K, int ci_off, int ci_cnt, void* dst,
               int row_off, int cin_p, int col_off, int slice_w, int lo, hipStream_t s) {
     HIPCHK(e, launch_pack_weight(e->dt, src, cout, cin_total, K, ci_off, ci_cnt, dst, row_off, cin_p, col_off, slice_w, lo, s));
     pk_push(L, PackJob{src, dst, 0, cout, cin_total, K, ci_off, ci_cnt, row_off, cin_p, col_off, slice_w, lo, 0u}, (size_t)cout * K * slice_w);
     return ST_OK;
 }
-int pk_weight_t(st_engine* e, st_engine::PackList& L, const float* src, int cout, int cin_total, int taps, int ci_off, int ci_cnt, void* dst,
+int pk_weight_t(st_engine* e, DitState::PackList& L, const float* src, int cout, int cin_total, int taps, int ci_off, int ci_cnt, void* dst,
                 int cin_p, int ld, int col_off, hipStream_t s) {
     HIPCHK(e, launch_pack_weight_t(e->dt, src, cout, cin_total, taps, ci_off, ci_cnt, dst, cin_p, ld, col_off, s));
     pk_push(L, PackJob{src, dst, 1, cout, cin_total, taps, ci_off, ci_cnt, 0, ld, col_off, 0, 0, 0u}, (size_t)ci_cnt * taps * cout);
     return ST_OK;
 }
-int pk_copy(st_engine* e, st_engine::PackList& L, float* dst, const float* src, int n, hipStream_t s) {
+int pk_copy(st_engine* e, DitState::PackList& L, float* dst, const float* src, int n, hipStream_t s) {
     HIPCHK(e, hipMemcpyAsync(dst, src, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     pk_push(L, PackJob{src, dst, 2, n, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0u}, (size_t)n);
     return ST_OK;
@@ -862,12 +856,13 @@ int pk_copy(st_engine* e, st_engine::PackList& L, float* dst, const float* src, 
 // allocated by the first call and re-used by every later one (shapes are fixed by the configuration), so instantiated
 // HIP graphs and in-flight launch sequences keep valid pointers and a re-pack is pure stream work.
 int pack_all(st_engine* e, hipStream_t s) {
-    const int C = e->C, F = e->F, M = e->M, Mp = e->Mp, K = e->K, L = e->L;
+    DitState* dit = dit_of(e);
+    const int C = dit->C, F = dit->F, M = dit->M, Mp = dit->Mp, K = dit->K, L = dit->L;
     {   // every later re-pack of the same tensors is one launch (the list was recorded by the first one)
         int prc;
-        if (e->packed_once && pk_replay(e, e->pk_fwd, s, &prc)) return prc;
+        if (dit->packed_once && pk_replay(e, dit->pk_fwd, s, &prc)) return prc;
     }
-    st_engine::PackList& PL = e->pk_fwd;
+    DitState::PackList& PL = dit->pk_fwd;
     pk_begin(PL);
     // generic packer: (cout, cin_total, taps) source slice -> Conv with padded dims.  split: the packed K dimension
     // is [W_hi | W_hi | W_lo] (W_lo = W - float(W_hi)), the weight side of a split-precision operand
@@ -886,71 +881,71 @@ int pack_all(st_engine* e, hipStream_t s) {
     };
     int rc;
     if (e->kind == KIND_TEXT_ENCODER) {
-        if ((rc = pack(e->fin, "proj.weight", P(e, "proj.bias"), M, Mp, C, 1, 0, C, C, true))) return rc;      // split precision: its error reaches mu_x un-gated
+        if ((rc = pack(dit->fin, "proj.weight", P(e, "proj.bias"), M, Mp, C, 1, 0, C, C, true))) return rc;      // split precision: its error reaches mu_x un-gated
     } else {
-    if (e->pre.size() != 3) e->pre.assign(3, Conv());
-    if ((rc = pack(e->pre[0], "cond_proj.0.weight", P(e, "cond_proj.0.bias"), F, F, M, K, 0, M, Mp, false))) return rc;
-    if ((rc = pack(e->pre[1], "cond_proj.2.weight", P(e, "cond_proj.2.bias"), F, F, F, K, 0, F, F, false))) return rc;
-    if ((rc = pack(e->pre[2], "cond_proj.4.weight", P(e, "cond_proj.4.bias"), C, C, F, K, 0, F, F, false))) return rc;
+    if (dit->pre.size() != 3) dit->pre.assign(3, Conv());
+    if ((rc = pack(dit->pre[0], "cond_proj.0.weight", P(e, "cond_proj.0.bias"), F, F, M, K, 0, M, Mp, false))) return rc;
+    if ((rc = pack(dit->pre[1], "cond_proj.2.weight", P(e, "cond_proj.2.bias"), F, F, F, K, 0, F, F, false))) return rc;
+    if ((rc = pack(dit->pre[2], "cond_proj.4.weight", P(e, "cond_proj.4.bias"), C, C, F, K, 0, F, F, false))) return rc;
     // in_proj input channel order [x(M) ; cond(C)] (estimator.py:120); both halves and final_proj take
     // split-precision operands: their rounding error reaches the estimator output without a gate in between
-    if ((rc = pack(e->inx, "in_proj.weight", nullptr, C, C, C + M, 1, 0, M, Mp, true))) return rc;
-    if ((rc = pack(e->inc, "in_proj.weight", P(e, "in_proj.bias"), C, C, C + M, 1, M, C, C, true))) return rc;
-    if ((rc = pack(e->fin, "final_proj.weight", P(e, "final_proj.bias"), M, Mp, C, 1, 0, C, C, true))) return rc;
-    if ((int)e->lsc.size() != L / 2) e->lsc.assign(L / 2, Conv());
+    if ((rc = pack(dit->inx, "in_proj.weight", nullptr, C, C, C + M, 1, 0, M, Mp, true))) return rc;
+    if ((rc = pack(dit->inc, "in_proj.weight", P(e, "in_proj.bias"), C, C, C + M, 1, M, C, C, true))) return rc;
+    if ((rc = pack(dit->fin, "final_proj.weight", P(e, "final_proj.bias"), M, Mp, C, 1, 0, C, C, true))) return rc;
+    if ((int)dit->lsc.size() != L / 2) dit->lsc.assign(L / 2, Conv());
     for (int i = 0; i < L / 2; ++i) {
         const std::string n = "lsc_layers." + std::to_string(i);
-        if ((rc = pack(e->lsc[i], n + ".weight", P(e, n + ".bias"), C, C, 2 * C, K, 0, 2 * C, 2 * C, false))) return rc;
+        if ((rc = pack(dit->lsc[i], n + ".weight", P(e, n + ".bias"), C, C, 2 * C, K, 0, 2 * C, 2 * C, false))) return rc;
     }
     }
-    if ((int)e->qkv.size() != L) { e->qkv.assign(L, Conv()); e->oproj.assign(L, Conv()); e->ffn1.assign(L, Conv()); e->ffn2.assign(L, Conv()); }
+    if ((int)dit->qkv.size() != L) { dit->qkv.assign(L, Conv()); dit->oproj.assign(L, Conv()); dit->ffn1.assign(L, Conv()); dit->ffn2.assign(L, Conv()); }
     for (int i = 0; i < L; ++i) {
-        const std::string b = e->blk(i);
-        Conv& q = e->qkv[i];
+        const std::string b = dit->blk(i);
+        Conv& q = dit->qkv[i];
         q.cout = 3 * C; q.cin = C; q.taps = 1;
         if (!q.w && (rc = dev_alloc(e, &q.w, (size_t)3 * C * C * 2))) return rc;
         if (!q.bias && (rc = dev_alloc(e, (void**)&q.bias, (size_t)3 * C * 4))) return rc;
         int r = 0;
-        const bool frag = C == 256 && e->H == 4;      // the weight-stationary kernel's copy (qkv_ws.hip)
+        const bool frag = C == 256 && dit->H == 4;      // the weight-stationary kernel's copy (qkv_ws.hip)
         if (frag) {
-            if ((int)e->qkv_frag.size() != L) e->qkv_frag.assign(L, nullptr);
-            if (!e->qkv_frag[i] && (rc = dev_alloc(e, &e->qkv_frag[i], (size_t)3 * C * C * 2))) return rc;
+            if ((int)dit->qkv_frag.size() != L) dit->qkv_frag.assign(L, nullptr);
+            if (!dit->qkv_frag[i] && (rc = dev_alloc(e, &dit->qkv_frag[i], (size_t)3 * C * C * 2))) return rc;
         }
         for (const char* nm : {"q", "k", "v"}) {
             const std::string n = b + "attn.conv_" + nm;
             if (frag) {
-                HIPCHK(e, launch_pack_qkv_frag(e->dt, P(e, n + ".weight"), r, e->qkv_frag[i], s));
-                pk_push(PL, PackJob{P(e, n + ".weight"), e->qkv_frag[i], 4, 0, 0, 0, 0, 0, r * 256, 0, 0, 0, 0, 0u}, (size_t)C * C);
+                HIPCHK(e, launch_pack_qkv_frag(e->dt, P(e, n + ".weight"), r, dit->qkv_frag[i], s));
+                pk_push(PL, PackJob{P(e, n + ".weight"), dit->qkv_frag[i], 4, 0, 0, 0, 0, 0, r * 256, 0, 0, 0, 0, 0u}, (size_t)C * C);
             }
             if ((rc = pk_weight(e, PL, P(e, n + ".weight"), C, C, 1, 0, C, q.w, r * C, C, 0, C, 0, s))) return rc;
             if ((rc = pk_copy(e, PL, q.bias + (size_t)r * C, P(e, n + ".bias"), C, s))) return rc;
             ++r;
         }
-        if ((rc = pack(e->oproj[i], b + "attn.conv_o.weight", P(e, b + "attn.conv_o.bias"), C, C, C, 1, 0, C, C, false))) return rc;
+        if ((rc = pack(dit->oproj[i], b + "attn.conv_o.weight", P(e, b + "attn.conv_o.bias"), C, C, C, 1, 0, C, C, false))) return rc;
         if (frag) {      // the weight-stationary out-projection kernel's copy (oproj_ws.hip): plane 0 of the same fragment order
-            if ((int)e->oproj_frag.size() != L) e->oproj_frag.assign(L, nullptr);
-            if (!e->oproj_frag[i] && (rc = dev_alloc(e, &e->oproj_frag[i], (size_t)C * C * 2))) return rc;
-            HIPCHK(e, launch_pack_qkv_frag(e->dt, P(e, b + "attn.conv_o.weight"), 0, e->oproj_frag[i], s));
-            pk_push(PL, PackJob{P(e, b + "attn.conv_o.weight"), e->oproj_frag[i], 4, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0u}, (size_t)C * C);
+            if ((int)dit->oproj_frag.size() != L) dit->oproj_frag.assign(L, nullptr);
+            if (!dit->oproj_frag[i] && (rc = dev_alloc(e, &dit->oproj_frag[i], (size_t)C * C * 2))) return rc;
+            HIPCHK(e, launch_pack_qkv_frag(e->dt, P(e, b + "attn.conv_o.weight"), 0, dit->oproj_frag[i], s));
+            pk_push(PL, PackJob{P(e, b + "attn.conv_o.weight"), dit->oproj_frag[i], 4, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0u}, (size_t)C * C);
         }
-        if ((rc = pack(e->ffn1[i], b + "mlp.conv_1.weight", P(e, b + "mlp.conv_1.bias"), F, F, C, K, 0, C, C, false))) return rc;
-        if ((rc = pack(e->ffn2[i], b + "mlp.conv_2.weight", P(e, b + "mlp.conv_2.bias"), C, C, F, K, 0, F, F, false))) return rc;
+        if ((rc = pack(dit->ffn1[i], b + "mlp.conv_1.weight", P(e, b + "mlp.conv_1.bias"), F, F, C, K, 0, C, C, false))) return rc;
+        if ((rc = pack(dit->ffn2[i], b + "mlp.conv_2.weight", P(e, b + "mlp.conv_2.bias"), C, C, F, K, 0, F, F, false))) return rc;
         if (e->kind == KIND_DECODER && C == 256 && K == 3 && F % 256 == 0 && F <= 2048) {      // the fused FFN kernel's weight stream (ffn_fused.h)
-            if ((int)e->ffn_stream.size() != L) e->ffn_stream.assign(L, nullptr);
-            if (!e->ffn_stream[i] && (rc = dev_alloc(e, &e->ffn_stream[i], (size_t)2 * F * C * K * 2))) return rc;
+            if ((int)dit->ffn_stream.size() != L) dit->ffn_stream.assign(L, nullptr);
+            if (!dit->ffn_stream[i] && (rc = dev_alloc(e, &dit->ffn_stream[i], (size_t)2 * F * C * K * 2))) return rc;
             for (int st = 0; st < 2; ++st) {
                 const float* src = P(e, b + (st ? "mlp.conv_2.weight" : "mlp.conv_1.weight"));
-                if (e->fused_ffn == 3) {      // ffn_wino.h: three transformed planes per tap triple
-                    HIPCHK(e, launch_pack_ffn_wino(src, st, F, e->ffn_stream[i], s));
-                    pk_push(PL, PackJob{src, e->ffn_stream[i], 5, F, 0, 0, 0, 0, 0, 0, 0, 0, st, 0u}, (size_t)F * C * K);
+                if (dit->fused_ffn == 3) {      // ffn_wino.h: three transformed planes per tap triple
+                    HIPCHK(e, launch_pack_ffn_wino(src, st, F, dit->ffn_stream[i], s));
+                    pk_push(PL, PackJob{src, dit->ffn_stream[i], 5, F, 0, 0, 0, 0, 0, 0, 0, 0, st, 0u}, (size_t)F * C * K);
                     continue;
                 }
-                HIPCHK(e, launch_pack_ffn_stream(e->dt, src, st, F, e->ffn_stream[i], s));
-                pk_push(PL, PackJob{src, e->ffn_stream[i], 3, F, 0, 0, 0, 0, 0, 0, 0, 0, st, 0u}, (size_t)F * C * K);
+                HIPCHK(e, launch_pack_ffn_stream(e->dt, src, st, F, dit->ffn_stream[i], s));
+                pk_push(PL, PackJob{src, dit->ffn_stream[i], 3, F, 0, 0, 0, 0, 0, 0, 0, 0, st, 0u}, (size_t)F * C * K);
             }
         }
     }
-    e->packed_once = true;
+    dit->packed_once = true;
     return pk_end(e, PL, s);
 }
 }  // namespace sthost
@@ -959,25 +954,25 @@ extern "C" {
 
 int st_estimator_forward(st_engine* e, const float* t, int t_len, const float* x, const float* mu,
                          const float* mask, const float* c, float* out, int B, int T, void* stream) {
-    int rc = check_ready(e, B, T); if (rc) return rc;
-    if ((rc = check_handle(e, KIND_DECODER))) return rc;
+    int rc = check_ready(e, KIND_DECODER, B, T); if (rc) return rc;
+    DitState* dit = dit_of(e);
     if (!t || !x || !mu || !mask || !c || !out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if (t_len != 1 && t_len != B) return e->fail(ST_ERR_INVALID, "t must have 1 or B elements");
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
     Plan p;
     if ((rc = make_plan(e, B, T, false, t_len, &p))) return rc;
-    e->arena_poisoned();      // an earlier call produced NaN / Inf: its stale frames must not be trusted (re-zero below)
+    dit->arena_poisoned(e);      // an earlier call produced NaN / Inf: its stale frames must not be trusted (re-zero below)
     if ((rc = arena_fresh(e, layout_sig(1, B, T, 0, t_len, 1), layout_plan(e, B, T, false, t_len, 0, &p), s))) return rc;
     bind_plan(e, &p);
     if ((rc = ensure_rope(e, T, s))) return rc;
     {
         ProfScope ps(e, s, PC_PREP, 0);
         HIPCHK(e, launch_mask_prep(mask, B, T, p.Tp, p.n_full, p.kv_end, p.kbias, p.t_lim, s));
-        HIPCHK(e, hipMemsetAsync(p.v32, 0, (size_t)p.N * T * e->Mp * 4, s));      // frames of skipped tiles: v = 0 (estimator.py:138)
-        HIPCHK(e, launch_to_time_major(e->dt, mu, B, e->M, T, e->Mp, nullptr, p.mu16, nullptr, s));
-        HIPCHK(e, launch_to_time_major(e->dt, x, B, e->M, T, e->Mp, nullptr, p.x16, p.x16lo, s));
-        HIPCHK(e, hipMemcpyAsync(p.cvec, c, (size_t)B * e->G * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(e, hipMemsetAsync(p.v32, 0, (size_t)p.N * T * dit->Mp * 4, s));      // frames of skipped tiles: v = 0 (estimator.py:138)
+        HIPCHK(e, launch_to_time_major(e->dt, mu, B, dit->M, T, dit->Mp, nullptr, p.mu16, nullptr, s));
+        HIPCHK(e, launch_to_time_major(e->dt, x, B, dit->M, T, dit->Mp, nullptr, p.x16, p.x16lo, s));
+        HIPCHK(e, hipMemcpyAsync(p.cvec, c, (size_t)B * dit->G * 4, hipMemcpyDeviceToDevice, s));
         HIPCHK(e, hipMemcpyAsync(p.tvals, t, (size_t)t_len * 4, hipMemcpyDeviceToDevice, s));
     }
     if ((rc = run_prenet(e, p, s))) return rc;
@@ -986,15 +981,15 @@ int st_estimator_forward(st_engine* e, const float* t, int t_len, const float* x
     if ((rc = run_estimator(e, p, mask, t_len == 1 ? 0 : -1, s))) return rc;
     {
         ProfScope ps(e, s, PC_PREP, 0);
-        HIPCHK(e, launch_from_time_major(p.v32, B, e->M, T, e->Mp, out, s, e->status_dev));
+        HIPCHK(e, launch_from_time_major(p.v32, B, dit->M, T, dit->Mp, out, s, dit->status_dev));
     }
     return ST_OK;
 }
 
 int st_text_encoder_forward(st_engine* e, const int64_t* tokens, const int64_t* lengths, const float* c,
                             float* x_out, float* mu_out, float* mask_out, int B, int T, void* stream) {
-    int rc = check_ready(e, B, T); if (rc) return rc;
-    if ((rc = check_handle(e, KIND_TEXT_ENCODER))) return rc;
+    int rc = check_ready(e, KIND_TEXT_ENCODER, B, T); if (rc) return rc;
+    DitState* dit = dit_of(e);
     if (!tokens || !lengths || !c || !x_out || !mu_out || !mask_out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
@@ -1005,17 +1000,17 @@ int st_text_encoder_forward(st_engine* e, const int64_t* tokens, const int64_t* 
     {
         ProfScope ps(e, s, PC_PREP, 0);
         // embedding * sqrt(C) * mask -> residual stream; the (B,1,T) mask is written straight into the caller's tensor
-        HIPCHK(e, launch_embed_tokens((const long long*)tokens, (const long long*)lengths, P(e, "emb.weight"), e->n_vocab,
-                                      e->C, sqrtf((float)e->C), B, T, p.X, mask_out, s));
+        HIPCHK(e, launch_embed_tokens((const long long*)tokens, (const long long*)lengths, P(e, "emb.weight"), dit->n_vocab,
+                                      dit->C, sqrtf((float)dit->C), B, T, p.X, mask_out, s));
         HIPCHK(e, launch_mask_prep(mask_out, B, T, p.Tp, p.n_full, p.kv_end, p.kbias, nullptr, s));
-        HIPCHK(e, launch_cvec_prep(c, nullptr, B, e->G, p.cvec, s));
+        HIPCHK(e, launch_cvec_prep(c, nullptr, B, dit->G, p.cvec, s));
     }
     if ((rc = run_adaln(e, p, s))) return rc;
     if ((rc = run_estimator(e, p, mask_out, 0, s))) return rc;
     {
         ProfScope ps(e, s, PC_PREP, 0);
-        HIPCHK(e, launch_from_time_major(p.X, B, e->C, T, e->C, x_out, s));
-        HIPCHK(e, launch_from_time_major(p.v32, B, e->M, T, e->Mp, mu_out, s));
+        HIPCHK(e, launch_from_time_major(p.X, B, dit->C, T, dit->C, x_out, s));
+        HIPCHK(e, launch_from_time_major(p.v32, B, dit->M, T, dit->Mp, mu_out, s));
     }
     return ST_OK;
 }
@@ -1135,11 +1130,12 @@ int st_duration_loss_backward(const float* logw, const int32_t* durations, const
 int st_output_status(st_engine* e, void* stream, int* nonfinite) {
     if (!e) return ST_ERR_INVALID;
     if (!nonfinite) return e->fail(ST_ERR_INVALID, "null argument");
-    if (!e->status_host) return e->fail(ST_ERR_UNSUPPORTED, "host-mapped status word unavailable on this device");
+    DitState* dit = dit_or_null(e);
+    if (!dit || !dit->status_host) return e->fail(ST_ERR_UNSUPPORTED, "host-mapped status word unavailable on this device");
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
-    *nonfinite = *e->status_host != 0;
-    e->arena_poisoned();      // clears the word; the next call re-zeroes the arena
+    *nonfinite = *dit->status_host != 0;
+    dit->arena_poisoned(e);      // clears the word; the next call re-zeroes the arena
     return ST_OK;
 }
 
@@ -1174,9 +1170,10 @@ int st_cfm_loss_scratch_floats(void) { return 2 * kCfmLossBlocks + 2; }
 
 int st_last_solve_stats(const st_engine* e, int64_t* nfe, int64_t* steps, int64_t* rejects) {
     if (!e) return ST_ERR_INVALID;
-    if (nfe) *nfe = e->last_nfe;
-    if (steps) *steps = e->last_steps;
-    if (rejects) *rejects = e->last_rejects;
+    const DitState* dit = dit_or_null(e);      // (a handle that never solves: zeros)
+    if (nfe) *nfe = dit ? dit->last_nfe : 0;
+    if (steps) *steps = dit ? dit->last_steps : 0;
+    if (rejects) *rejects = dit ? dit->last_rejects : 0;
     return ST_OK;
 }
 
@@ -1191,7 +1188,8 @@ int st_set_option(st_engine* e, const char* name, int value) {
     if (n == "attention_precision") {
         if (value != 0 && value != 1) return e->fail(ST_ERR_INVALID, "attention_precision: 0 (16-bit q / k operands) or 1 (split hi + lo operands)");
         if (e->kind != KIND_DECODER) return e->fail(ST_ERR_UNSUPPORTED, "attention_precision: CFM decoder handles only");
-        if (value != e->attn_split) { e->drop_graphs(); e->attn_split = value; }
+        DitState* dit = dit_of(e);
+        if (value != dit->attn_split) { dit->drop_graphs(); dit->attn_split = value; }
         return ST_OK;
     }
     if (n == "fused_ffn") return e->fail(ST_ERR_INVALID, "fused_ffn is read-only (ST_FUSED_FFN at st_create)");
@@ -1200,9 +1198,10 @@ int st_set_option(st_engine* e, const char* name, int value) {
 
 int st_get_option(const st_engine* e, const char* name, int* value) {
     if (!e || !name || !value) return ST_ERR_INVALID;
+    const DitState* dit = dit_or_null(e);      // (the other kinds answer with the values of a handle that st_create never configured)
     const std::string n(name);
-    if (n == "attention_precision") { *value = e->attn_split; return ST_OK; }
-    if (n == "fused_ffn") { *value = e->fused_ffn; return ST_OK; }
+    if (n == "attention_precision") { *value = dit ? dit->attn_split : 0; return ST_OK; }
+    if (n == "fused_ffn") { *value = dit ? dit->fused_ffn : -1; return ST_OK; }
     return ST_ERR_INVALID;
 }
 
@@ -1211,14 +1210,15 @@ int st_get_option(const st_engine* e, const char* name, int* value) {
 // it.  Synchronises `stream`, reads 16 words, resets the cells.
 int st_attention_stats(st_engine* e, void* stream, float* max_lse) {
     if (!e || !max_lse) return ST_ERR_INVALID;
-    if (!e->lse_cells) return e->fail(ST_ERR_STATE, "attention statistics unavailable (allocation failed at st_create)");
+    DitState* dit = dit_or_null(e);
+    if (!dit || !dit->lse_cells) return e->fail(ST_ERR_STATE, "attention statistics unavailable (allocation failed at st_create)");
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
     int cells[kLseCells * 16];
-    HIPCHK(e, hipMemcpy(cells, e->lse_cells, sizeof(cells), hipMemcpyDeviceToHost));
+    HIPCHK(e, hipMemcpy(cells, dit->lse_cells, sizeof(cells), hipMemcpyDeviceToHost));
     int best = (int)0x80000000;
     for (int c = 0; c < kLseCells; ++c) best = std::max(best, cells[c * 16]);
-    HIPCHK(e, hipMemsetD32((hipDeviceptr_t)e->lse_cells, (int)0x80000000, kLseCells * 16));
+    HIPCHK(e, hipMemsetD32((hipDeviceptr_t)dit->lse_cells, (int)0x80000000, kLseCells * 16));
     if (best == (int)0x80000000) { *max_lse = -INFINITY; return ST_OK; }
     const int bits = best >= 0 ? best : best ^ 0x7fffffff;
     float v; memcpy(&v, &bits, 4);
@@ -1297,8 +1297,7 @@ int st_profile_read(st_engine* e, int cls, int64_t* launches, double* total_ms, 
 
 int64_t st_device_bytes(const st_engine* e) {
     if (!e) return ST_ERR_INVALID;
-    int64_t n = e->weight_bytes + (int64_t)e->ws_cap + train_bytes(e);
-    if (e->sdt) n += (int64_t)(e->sdt->act_cap + e->sdt->scr_cap);
+    int64_t n = e->weight_bytes + (int64_t)e->ws_cap + e->state->device_bytes();
     for (auto& kv : e->params) if (kv.second.dev && !kv.second.borrowed) n += kv.second.numel() * 4;
     return n;
 }

@@ -15,7 +15,10 @@ using namespace sthost;
 
 namespace sthost {
 
-struct MelState {
+struct MelState : KindState {
+    MelState() : KindState("st_repack: mel-extractor handles re-read their filter bank through st_finalize") {}
+    ~MelState() override;
+    int finalize(st_engine* e) override;
     st_mel_config cfg{};
     int* band = nullptr;          // [n_mels][3]: lo, hi, offset into wband
     float* wband = nullptr;
@@ -31,27 +34,24 @@ struct MelState {
     int cap = 0, next = 0;
 };
 
-void mel_destroy(st_engine* e) {
-    MelState* m = e->mel;
-    if (!m) return;
-    for (int i = 0; i < MelState::kSlots; ++i) {
-        if (m->host[i]) hipHostFree(m->host[i]);
-        if (m->dev[i]) hipFree(m->dev[i]);
-        if (m->ev[i]) hipEventDestroy(m->ev[i]);
+MelState::~MelState() {
+    for (int i = 0; i < kSlots; ++i) {
+        if (host[i]) hipHostFree(host[i]);
+        if (dev[i]) hipFree(dev[i]);
+        if (ev[i]) hipEventDestroy(ev[i]);
     }
-    if (m->band) hipFree(m->band);
-    if (m->wband) hipFree(m->wband);
-    if (m->bandT) hipFree(m->bandT);
-    if (m->wbandT) hipFree(m->wbandT);
-    delete m; e->mel = nullptr;
+    if (band) hipFree(band);
+    if (wband) hipFree(wband);
+    if (bandT) hipFree(bandT);
+    if (wbandT) hipFree(wbandT);
 }
 
 // st_finalize of a mel handle: every filter's nonzero range [lo, hi) of bins, and its weights packed in bin order.  A filter
 // without a nonzero weight gets an empty range (its sum is 0, log(1e-5) after the clamp), as in the dense product.  The
 // transposed table gives every bin its range of mels with nonzero weights and those weights in mel order; a bin that no filter
 // reaches gets an empty range (dmag = 0), and an all-zero filter appears in no bin's range.
-int mel_finalize(st_engine* e) {
-    MelState* m = e->mel;
+int MelState::finalize(st_engine* e) {
+    MelState* m = this;
     const st_mel_config& c = m->cfg;
     if (c.n_mels > 0) {
         const int bins = c.n_fft / 2 + 1, M = c.n_mels;
@@ -92,7 +92,6 @@ int mel_finalize(st_engine* e) {
         HIPCHK(e, hipMemcpy(m->bandT, bandT.data(), bandT.size() * 4, hipMemcpyHostToDevice));
         HIPCHK(e, hipMemcpy(m->wbandT, wT.data(), wT.size() * 4, hipMemcpyHostToDevice));
     }
-    e->finalized = true;
     return ST_OK;
 }
 
@@ -109,9 +108,10 @@ static int mel_check(st_engine* e, const float* wave, float* out) {
 }
 
 static MelArgs mel_args(st_engine* e, const float* wave, float* out, bool log_mel) {
-    const st_mel_config& c = e->mel->cfg;
+    const MelState* m = state_of<MelState>(e);
+    const st_mel_config& c = m->cfg;
     MelArgs a{};
-    a.wave = wave; a.window = P(e, "spectrogram.window"); a.wband = e->mel->wband; a.band = e->mel->band; a.out = out;
+    a.wave = wave; a.window = P(e, "spectrogram.window"); a.wband = m->wband; a.band = m->band; a.out = out;
     a.n_fft = c.n_fft; a.hop = c.hop_length; a.pad = c.pad;
     a.rows = log_mel ? c.n_mels : c.n_fft / 2 + 1; a.log_mel = log_mel ? 1 : 0;
     return a;
@@ -135,10 +135,10 @@ int st_create_mel_extractor(const st_mel_config* cfg, int device, st_engine** ou
     if (cfg->win_length != cfg->n_fft) return bad("native kernels are built for win_length == n_fft", ST_ERR_UNSUPPORTED);
     if (cfg->n_fft < kMelMinNfft || cfg->n_fft > kMelMaxNfft || (cfg->n_fft & (cfg->n_fft - 1)))
         return bad("native kernels are built for n_fft a power of two in [32, 2048]", ST_ERR_UNSUPPORTED);
+    auto state = std::make_unique<MelState>();
+    state->cfg = *cfg;
     st_engine* e = nullptr;
-    if (int rc = new_handle(KIND_MEL_EXTRACTOR, device, &e)) return rc;
-    e->mel = new MelState();
-    e->mel->cfg = *cfg;
+    if (int rc = new_handle(KIND_MEL_EXTRACTOR, device, std::move(state), &e)) return rc;
     expect(e, "spectrogram.window", {cfg->win_length});                                        // utils/audio.py:17
     if (cfg->n_mels > 0) expect(e, "mel_scale.fb", {cfg->n_fft / 2 + 1, cfg->n_mels});         // :45 (MelScale's buffer)
     *out = e;
@@ -146,13 +146,13 @@ int st_create_mel_extractor(const st_mel_config* cfg, int device, st_engine** ou
 }
 
 int64_t st_mel_frames(const st_engine* e, int64_t L) {
-    if (!e || e->kind != KIND_MEL_EXTRACTOR) return ST_ERR_INVALID;
-    return frames_of(e->mel->cfg, L);
+    const MelState* m = state_if<MelState>(e, KIND_MEL_EXTRACTOR);
+    return m ? frames_of(m->cfg, L) : ST_ERR_INVALID;
 }
 
 int st_mel_forward(st_engine* e, const float* wave, int B, int64_t L, float* out, void* stream) {
     int rc = mel_check(e, wave, out); if (rc) return rc;
-    const st_mel_config& c = e->mel->cfg;
+    const st_mel_config& c = state_of<MelState>(e)->cfg;
     if (c.n_mels < 1) return e->fail(ST_ERR_STATE, "a linear-spectrogram extractor (n_mels = 0) has no mel output: st_mel_forward_ragged with ST_MEL_LINEAR");
     if (B < 1) return e->fail(ST_ERR_INVALID, "B must be >= 1");
     const int64_t T = frames_of(c, L);
@@ -173,7 +173,7 @@ int st_mel_forward_ragged(st_engine* e, const float* wave, const int64_t* sample
     if (!sample_offsets || !frame_offsets) return e->fail(ST_ERR_INVALID, "null offsets");
     if (B < 1) return e->fail(ST_ERR_INVALID, "B must be >= 1");
     if (output != ST_MEL_LOG && output != ST_MEL_LINEAR) return e->fail(ST_ERR_INVALID, "output must be ST_MEL_LOG or ST_MEL_LINEAR");
-    MelState* m = e->mel;
+    MelState* m = state_of<MelState>(e);
     const st_mel_config& c = m->cfg;
     if (output == ST_MEL_LOG && c.n_mels < 1) return e->fail(ST_ERR_STATE, "a linear-spectrogram extractor (n_mels = 0) has no mel output");
     const int FR = mel_tile_frames(c.n_fft);
@@ -228,8 +228,9 @@ int st_mel_forward_ragged(st_engine* e, const float* wave, const int64_t* sample
 }
 
 int64_t st_mel_backward_workspace_bytes(const st_engine* e, int B, int64_t L) {
-    if (!e || e->kind != KIND_MEL_EXTRACTOR || B < 1) return ST_ERR_INVALID;
-    const st_mel_config& c = e->mel->cfg;
+    const MelState* m = state_if<MelState>(e, KIND_MEL_EXTRACTOR);
+    if (!m || B < 1) return ST_ERR_INVALID;
+    const st_mel_config& c = m->cfg;
     const int64_t T = frames_of(c, L);
     if (T < 0) return ST_ERR_INVALID;
     return (int64_t)B * T * c.n_fft * (int64_t)sizeof(float);
@@ -240,7 +241,7 @@ int st_mel_backward(st_engine* e, const float* wave, const float* grad_out, int 
     int rc = mel_check(e, wave, grad_wave); if (rc) return rc;
     if (!grad_out || !workspace) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if (output != ST_MEL_LOG && output != ST_MEL_LINEAR) return e->fail(ST_ERR_INVALID, "output must be ST_MEL_LOG or ST_MEL_LINEAR");
-    MelState* m = e->mel;
+    MelState* m = state_of<MelState>(e);
     const st_mel_config& c = m->cfg;
     if (output == ST_MEL_LOG && c.n_mels < 1) return e->fail(ST_ERR_STATE, "a linear-spectrogram extractor (n_mels = 0) has no mel output");
     if (output == ST_MEL_LOG && c.n_mels > 2 * c.n_fft)

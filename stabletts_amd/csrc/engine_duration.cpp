@@ -12,8 +12,10 @@ using namespace sthost;
 
 namespace sthost {
 
-struct DurState {
+// Reads the loaded parameters in place: nothing to pack
+struct DurState : HeldState {
     st_duration_predictor_config cfg{};
+    DurState() : HeldState("st_repack: style-encoder / duration-predictor handles read their parameters in place") {}
 };
 
 static void duration_build_params(st_engine* e, const st_duration_predictor_config& c) {
@@ -25,8 +27,6 @@ static void duration_build_params(st_engine* e, const st_duration_predictor_conf
     expect(e, "proj.weight", {1, F, 1}); expect(e, "proj.bias", {1});
     expect(e, "cond.weight", {Ci, G, 1}); expect(e, "cond.bias", {Ci});                  // :22
 }
-
-void duration_destroy(st_engine* e) { delete e->dur; e->dur = nullptr; }
 
 }  // namespace sthost
 
@@ -40,10 +40,10 @@ int st_create_duration_predictor(const st_duration_predictor_config* cfg, int de
     // limits of this native build
     if (cfg->filter_channels % 128 != 0) return bad("filter_channels must be a multiple of 128", ST_ERR_UNSUPPORTED);
     if (cfg->kernel_size != 1 && cfg->kernel_size != 3 && cfg->kernel_size != 5) return bad("native convolutions are built for kernel_size 1, 3 or 5", ST_ERR_UNSUPPORTED);
+    auto state = std::make_unique<DurState>();
+    state->cfg = *cfg;
     st_engine* e = nullptr;
-    if (int rc = new_handle(KIND_DURATION_PREDICTOR, device, &e)) return rc;
-    e->dur = new DurState();
-    e->dur->cfg = *cfg;
+    if (int rc = new_handle(KIND_DURATION_PREDICTOR, device, std::move(state), &e)) return rc;
     duration_build_params(e, *cfg);
     *out = e;
     return ST_OK;
@@ -55,7 +55,7 @@ int st_duration_predictor_forward(st_engine* e, const float* x, const float* x_m
     if ((rc = check_finalized(e))) return rc;
     if (!x || !x_mask || !g || !logw_out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if ((rc = check_sizes(e, B, Tx, "Tx"))) return rc;
-    const st_duration_predictor_config& c = e->dur->cfg;
+    const st_duration_predictor_config& c = state_of<DurState>(e)->cfg;
     const int Ci = c.in_channels, F = c.filter_channels, K = c.kernel_size, G = c.gin_channels;
     const int64_t R = (int64_t)B * Tx;
     if (R * F >= ((int64_t)1 << 31) || R * Ci >= ((int64_t)1 << 31)) return e->fail(ST_ERR_INVALID, "B*Tx too large");
@@ -125,13 +125,13 @@ int st_duration_predictor_train_forward(st_engine* e, const float* x, const floa
     if (!x || !x_mask || !g || !logw_out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if ((rc = check_sizes(e, B, Tx, "Tx"))) return rc;
     if ((rc = check_dropout(e, p_dropout))) return rc;
-    const st_duration_predictor_config& c = e->dur->cfg;
+    const st_duration_predictor_config& c = state_of<DurState>(e)->cfg;
     const int Ci = c.in_channels, F = c.filter_channels, K = c.kernel_size, Gc = c.gin_channels;
     const int64_t R = (int64_t)B * Tx;
     if (R * F >= ((int64_t)1 << 31) || R * Ci >= ((int64_t)1 << 31)) return e->fail(ST_ERR_INVALID, "B*Tx too large");
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    SdTrain* st = sd_train_begin(e);
+    SdTrain* st = state_of<DurState>(e)->begin();
     const DurActs A = dur_acts(c, B, Tx);
     if ((rc = sd_train_grow(e, &st->act, &st->act_cap, A.end * 4))) return rc;
     float* act = (float*)st->act;
@@ -171,9 +171,10 @@ int st_duration_predictor_train_backward(st_engine* e, int64_t serial, int B, in
                                          void* stream) {
     int rc = check_handle(e, KIND_DURATION_PREDICTOR); if (rc) return rc;
     if (!grad_logw || !grad_flat) return e->fail(ST_ERR_INVALID, "null tensor pointer");
-    if ((rc = sd_train_check(e, "st_duration_predictor_train", "Tx", serial, B, Tx))) return rc;
-    SdTrain* st = e->sdt;
-    const st_duration_predictor_config& c = e->dur->cfg;
+    DurState* dur = state_of<DurState>(e);
+    SdTrain* st = &dur->held;
+    if ((rc = sd_train_check(e, *st, "st_duration_predictor_train", "Tx", serial, B, Tx))) return rc;
+    const st_duration_predictor_config& c = dur->cfg;
     const int Ci = c.in_channels, F = c.filter_channels, K = c.kernel_size, Gc = c.gin_channels;
     const int64_t R = (int64_t)B * Tx;
     HIPCHK(e, hipSetDevice(e->device));

@@ -30,7 +30,10 @@ struct FfConv {             // one convolution of the head: fragment-ordered 16-
     int cin = 0, cout = 0, taps = 0, dil = 1;
 };
 
-struct FfganState {
+struct FfganState : KindState {
+    FfganState() : KindState("st_repack: vocoder handles re-pack through st_finalize") {}
+    ~FfganState() override { slots.destroy(); }
+    int finalize(st_engine* e) override;
     st_ffgan_config cfg{};
     int hop = 1;
     bool split = false;                               // hi + lo operand pairs (e->dt names their 16-bit format)
@@ -133,8 +136,9 @@ static void ffgan_build_params(st_engine* e, const st_ffgan_config& c) {
 }
 
 // st_finalize of an ffgan handle: 16-bit GEMM weights of the encoder, w = g v / ||v|| of the head's convs in fragment order
-int ffgan_finalize(st_engine* e) {
-    FfganState* v = e->ffg;
+int FfganState::finalize(st_engine* e) {
+    free_owned(e);
+    FfganState* v = this;
     const st_ffgan_config& c = v->cfg;
     hipStream_t s = nullptr;
     const bool split = v->split;
@@ -209,14 +213,7 @@ int ffgan_finalize(st_engine* e) {
         HIPCHK(e, launch_ffg_pack_post(P(e, "head.conv_post." + kWn1), scale, cl, k, v->post_w, s));
     }
     HIPCHK(e, hipDeviceSynchronize());
-    e->finalized = true;
     return ST_OK;
-}
-
-void ffgan_destroy(st_engine* e) {
-    if (!e->ffg) return;
-    e->ffg->slots.destroy();
-    delete e->ffg; e->ffg = nullptr;
 }
 
 // widest level of one utterance, in channel-samples per mel frame: max over the levels of (product of the rates so far) * width
@@ -241,7 +238,7 @@ constexpr int kFfganMaxT = 1 << 20;
 // ragged chunk (rg: mel and audio stay padded to T; the im2col, the depthwise conv, the head's convolutions and the post kernel know
 // utterances and take their ragged form -- every level tensor of the head then holds R * up packed rows).
 static int ffgan_forward_chunk(st_engine* e, const float* mel, float* audio, int B, int T, const RaggedChunk* rg, hipStream_t s) {
-    FfganState* v = e->ffg;
+    FfganState* v = state_of<FfganState>(e);
     const st_ffgan_config& c = v->cfg;
     const int M = c.input_channels, Dmax = ffgan_max_dim(c), D = c.dims[c.n_stages - 1], C0 = c.upsample_initial_channel;
     const int64_t R = rg ? rg->rows : (int64_t)B * T, lvl = ffgan_level_elems(c) * R;
@@ -375,17 +372,17 @@ extern "C" {
 int st_create_ffgan(const st_ffgan_config* cfg, int device, st_engine** out) {
     if (!cfg || !out) { g_create_error = "null argument"; return ST_ERR_INVALID; }
     if (const char* why = ffgan_unsupported(*cfg)) { g_create_error = why; return ST_ERR_INVALID; }
+    auto state = std::make_unique<FfganState>();
+    state->cfg = *cfg;
+    state->split = cfg->operand_dtype == ST_OPERAND_BF16_SPLIT || cfg->operand_dtype == ST_OPERAND_F16_SPLIT;
+    for (int i = 0; i < cfg->n_upsamples; ++i) state->hop *= cfg->upsample_rates[i];
     st_engine* e = nullptr;
-    if (int rc = new_handle(KIND_FFGAN, device, &e)) return rc;
+    if (int rc = new_handle(KIND_FFGAN, device, std::move(state), &e)) return rc;
     e->dt = (cfg->operand_dtype == ST_OPERAND_BF16 || cfg->operand_dtype == ST_OPERAND_BF16_SPLIT) ? DT_BF16 : DT_F16;
-    e->ffg = new FfganState();
-    e->ffg->cfg = *cfg;
-    e->ffg->split = cfg->operand_dtype == ST_OPERAND_BF16_SPLIT || cfg->operand_dtype == ST_OPERAND_F16_SPLIT;
-    for (int i = 0; i < cfg->n_upsamples; ++i) e->ffg->hop *= cfg->upsample_rates[i];
-    e->splitk_target = 0; e->attn_small_blocks = 0;      // decoder-only small-grid paths
+    e->tile.splitk_target = 0;      // no split-K convs: the encoder's GEMMs run over the flattened rows of the whole batch
     ffgan_build_params(e, *cfg);
     if (hipMalloc(&e->zeros, 256) != hipSuccess || hipMemset(e->zeros, 0, 256) != hipSuccess) {
-        ffgan_destroy(e); delete e;
+        delete e;
         g_create_error = "hipMalloc failed";
         return ST_ERR_HIP;
     }
@@ -398,15 +395,16 @@ int st_ffgan_forward(st_engine* e, const float* mel, float* audio, int B, int T,
     if ((rc = check_finalized(e))) return rc;
     if (!mel || !audio) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if ((rc = check_sizes(e, B, T))) return rc;
-    const st_ffgan_config& c = e->ffg->cfg;
+    const FfganState* v = state_of<FfganState>(e);
+    const st_ffgan_config& c = v->cfg;
     const int64_t max_rows = ffgan_max_rows(c);
     if (T > max_rows || T > kFfganMaxT) return e->fail(ST_ERR_INVALID, "T too large: one utterance exceeds the vocoder's row indexing");
-    const int64_t head_item = ffgan_level_elems(c) * T * ffgan_head_sample_bytes(e->ffg);
+    const int64_t head_item = ffgan_level_elems(c) * T * ffgan_head_sample_bytes(v);
     const int chunk = (int)std::min<int64_t>({(int64_t)B, std::max<int64_t>(1, kFfganHeadBytes / head_item), max_rows / T, (int64_t)65535});
     if (chunk < B && e->capture) return e->fail(ST_ERR_INVALID, "debug capture holds whole-batch tensors: this batch runs in chunks");
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    const size_t mel_item = (size_t)c.input_channels * T, audio_item = (size_t)T * e->ffg->hop;
+    const size_t mel_item = (size_t)c.input_channels * T, audio_item = (size_t)T * v->hop;
     for (int b0 = 0; b0 < B; b0 += chunk) {
         rc = ffgan_forward_chunk(e, mel + b0 * mel_item, audio + b0 * audio_item, std::min(chunk, B - b0), T, nullptr, s);
         if (rc) return rc;
@@ -420,7 +418,7 @@ int st_ffgan_forward_ragged(st_engine* e, const float* mel, const int64_t* lengt
     if (!mel || !audio) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if (!lengths) return e->fail(ST_ERR_INVALID, "null lengths");
     if ((rc = check_sizes(e, B, T))) return rc;
-    FfganState* v = e->ffg;
+    FfganState* v = state_of<FfganState>(e);
     const st_ffgan_config& c = v->cfg;
     const int64_t max_rows = ffgan_max_rows(c);
     // validate everything and plan the chunks before touching the device: whole utterances, as many as keep the head's level tensors

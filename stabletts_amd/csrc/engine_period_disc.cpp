@@ -4,8 +4,7 @@
 // biases -- are read in place from the tensors st_load_param / st_bind_param hold, and the effective weights w = v g / ||v|| are
 // engine-owned buffers recomputed by st_finalize (new tensors) and st_repack (an in-place update), not per call.
 // Kept per training forward: the waveform and the post-activations of layers 0-4; the leaky ReLU's backward reads their signs.
-#include "engine_internal.h"
-#include "period_disc_launch.h"
+#include "engine_disc.h"
 #include "style_dp_launch.h"
 
 #include <algorithm>
@@ -20,22 +19,21 @@ constexpr int kPdLayers = 5;                                                  //
 constexpr int kPdCh[kPdLayers + 1] = {1, 32, 128, 512, 1024, 1024};           // channels before layer i / after layer i - 1
 constexpr int kPdStride[kPdLayers] = {3, 3, 3, 3, 1};
 
-struct PdState {
+struct PdState : DiscState {
     st_period_disc_config cfg{};
     float* w[kPdLayers + 1] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};     // effective weights; [5] = conv_post
+    ~PdState() override { for (float* p : w) if (p) hipFree(p); }
 };
 
 static std::string pd_name(int i) { return i < kPdLayers ? "convs." + std::to_string(i) + "." : std::string("conv_post."); }
-static const char* kPdG = "parametrizations.weight.original0";
-static const char* kPdV = "parametrizations.weight.original1";
 static int64_t pd_wnumel(int i) { return i < kPdLayers ? (int64_t)kPdCh[i + 1] * kPdCh[i] * kPdTaps : (int64_t)kPdCh[kPdLayers] * kPdPostTaps; }
 
 static void pd_build_params(st_engine* e) {
     for (int i = 0; i <= kPdLayers; ++i) {
         const int64_t co = i < kPdLayers ? kPdCh[i + 1] : 1, ci = i < kPdLayers ? kPdCh[i] : kPdCh[kPdLayers];
         const int64_t k = i < kPdLayers ? kPdTaps : kPdPostTaps;
-        expect(e, pd_name(i) + kPdG, {co, 1, 1, 1});
-        expect(e, pd_name(i) + kPdV, {co, ci, k, 1});
+        expect(e, pd_name(i) + kWnG, {co, 1, 1, 1});
+        expect(e, pd_name(i) + kWnV, {co, ci, k, 1});
         expect(e, pd_name(i) + "bias", {co});
     }
 }
@@ -68,25 +66,9 @@ static PdActs pd_acts(int B, const PdGeom& g) {
     return A;
 }
 
-void period_disc_destroy(st_engine* e) {
-    if (!e->pd) return;
-    for (float* w : e->pd->w) if (w) hipFree(w);
-    delete e->pd; e->pd = nullptr;
-}
-
-// w = v g / ||v|| of the six convs, as kernels on `s`
-int period_disc_weights(st_engine* e, hipStream_t s) {
-    for (int i = 0; i <= kPdLayers; ++i) {
-        const int co = i < kPdLayers ? kPdCh[i + 1] : 1;
-        HIPCHK(e, launch_pd_weight_norm(P(e, pd_name(i) + kPdV), P(e, pd_name(i) + kPdG), e->pd->w[i], co, (int)(pd_wnumel(i) / co), s));
-    }
-    if (e->sdt) e->sdt->have = false;      // the held activations are of the weights before
-    return ST_OK;
-}
-
 static int pd_check(st_engine* e, int B, int T, PdGeom* g) {
     int rc = check_sizes(e, B, T); if (rc) return rc;
-    const int p = e->pd->cfg.period;
+    const int p = state_of<PdState>(e)->cfg.period;
     const int n_pad = T % p ? p - T % p : 0;
     if (T <= n_pad)
         return e->fail(ST_ERR_INVALID, "T = " + std::to_string(T) + " is too short for period " + std::to_string(p) + ": the reflect padding of " +
@@ -100,8 +82,9 @@ static int pd_check(st_engine* e, int B, int T, PdGeom* g) {
 // The forward.  keep = nullptr: a0 lives in the workspace arena and every other layer writes its feature map only.
 // keep != nullptr: x and the post-activations a0 .. a4 go to keep's activation buffer as well.
 static int pd_forward(st_engine* e, const float* x, float* const* fmaps, int B, const PdGeom& g, SdTrain* keep, hipStream_t s) {
+    const PdState* pd = state_of<PdState>(e);
     const int p = g.p;
-    const float slope = e->pd->cfg.lrelu_slope;
+    const float slope = pd->cfg.lrelu_slope;
     int rc;
     float* a[kPdLayers] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     const float* xin = x;
@@ -117,14 +100,14 @@ static int pd_forward(st_engine* e, const float* x, float* const* fmaps, int B, 
         a[0] = (float*)e->ws;
         for (int i = 1; i < kPdLayers; ++i) a[i] = fmaps[i - 1];
     }
-    HIPCHK(e, launch_pd_l0_fwd(xin, e->pd->w[0], P(e, pd_name(0) + "bias"), a[0], B, g.T, g.Tp, g.H[1], p, slope, s));
+    HIPCHK(e, launch_pd_l0_fwd(xin, pd->w[0], P(e, pd_name(0) + "bias"), a[0], B, g.T, g.Tp, g.H[1], p, slope, s));
     for (int i = 1; i < kPdLayers; ++i) {
         PdConvArgs c;
-        c.in = a[i - 1]; c.w = e->pd->w[i]; c.bias = P(e, pd_name(i) + "bias"); c.out = a[i]; c.out2 = keep ? fmaps[i - 1] : nullptr;
+        c.in = a[i - 1]; c.w = pd->w[i]; c.bias = P(e, pd_name(i) + "bias"); c.out = a[i]; c.out2 = keep ? fmaps[i - 1] : nullptr;
         c.B = B; c.Cin = kPdCh[i]; c.Cout = kPdCh[i + 1]; c.Hin = g.H[i]; c.Hout = g.H[i + 1]; c.p = p; c.stride = kPdStride[i]; c.slope = slope;
         HIPCHK(e, launch_pd_conv(c, s));
     }
-    HIPCHK(e, launch_pd_post_fwd(a[4], e->pd->w[kPdLayers], P(e, pd_name(kPdLayers) + "bias"), fmaps[4], nullptr, B, kPdCh[kPdLayers], g.H[kPdLayers], p, s));
+    HIPCHK(e, launch_pd_post_fwd(a[4], pd->w[kPdLayers], P(e, pd_name(kPdLayers) + "bias"), fmaps[4], nullptr, B, kPdCh[kPdLayers], g.H[kPdLayers], p, s));
     return ST_OK;
 }
 
@@ -146,26 +129,27 @@ int st_create_period_discriminator(const st_period_disc_config* cfg, int device,
     // the leaky ReLU's backward takes the pre-activation's sign from the kept post-activation: the slope must keep it
     if (!(cfg->lrelu_slope > 0.0f) || !(cfg->lrelu_slope < 1e30f)) { g_create_error = "lrelu_slope must be positive and finite"; return ST_ERR_INVALID; }
     st_engine* e = nullptr;
-    if (int rc = new_handle(KIND_PERIOD_DISC, device, &e)) return rc;
-    e->pd = new PdState();
-    e->pd->cfg = *cfg;
+    if (int rc = new_handle(KIND_PERIOD_DISC, device, std::make_unique<PdState>(), &e)) return rc;
+    PdState* pd = state_of<PdState>(e);
+    pd->cfg = *cfg;
     pd_build_params(e);
     for (int i = 0; i <= kPdLayers; ++i) {
-        if (hipMalloc((void**)&e->pd->w[i], (size_t)pd_wnumel(i) * 4) != hipSuccess) {
+        if (hipMalloc((void**)&pd->w[i], (size_t)pd_wnumel(i) * 4) != hipSuccess) {
             g_create_error = "hipMalloc failed";
-            period_disc_destroy(e);
             delete e;
             return ST_ERR_HIP;
         }
         e->weight_bytes += pd_wnumel(i) * 4;
+        pd->convs.push_back({pd_name(i), pd->w[i], i < kPdLayers ? kPdCh[i + 1] : 1, pd_wnumel(i)});
     }
     *out = e;
     return ST_OK;
 }
 
 int st_period_disc_fmap_shape(const st_engine* e, int T, int index, int64_t* channels, int64_t* rows) {
-    if (!e || e->kind != KIND_PERIOD_DISC || !channels || !rows || T < 1 || index < 0 || index >= kPdLayers) return ST_ERR_INVALID;
-    const int p = e->pd->cfg.period;
+    const PdState* pd = state_if<PdState>(e, KIND_PERIOD_DISC);
+    if (!pd || !channels || !rows || T < 1 || index < 0 || index >= kPdLayers) return ST_ERR_INVALID;
+    const int p = pd->cfg.period;
     if (T <= (T % p ? p - T % p : 0)) return ST_ERR_INVALID;
     const PdGeom g = pd_geom(p, T);
     *channels = index < kPdLayers - 1 ? kPdCh[index + 2] : 1;
@@ -184,7 +168,7 @@ int st_period_disc_train_forward(st_engine* e, const float* x, float* const* fma
     PdGeom g;
     int rc = pd_entry(e, x, fmaps, B, T, &g); if (rc) return rc;
     HIPCHK(e, hipSetDevice(e->device));
-    SdTrain* st = sd_train_begin(e);
+    SdTrain* st = state_of<PdState>(e)->begin();
     if ((rc = pd_forward(e, x, fmaps, B, g, st, (hipStream_t)stream))) return rc;
     sd_train_commit(st, B, T, 0.0f, 0, false);
     return ST_OK;
@@ -195,16 +179,14 @@ int st_period_disc_train_backward(st_engine* e, const float* const* d_fmaps, flo
     if (!d_fmaps) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     PdGeom g;
     if ((rc = pd_check(e, B, T, &g))) return rc;
-    SdTrain* st = e->sdt;
-    if (!st || !st->have) return e->fail(ST_ERR_STATE, "st_period_disc_train_backward needs a preceding st_period_disc_train_forward");
-    if (B != st->B || T != st->T)
-        return e->fail(ST_ERR_STATE, "st_period_disc_train_backward: the engine holds the activations of a forward with B=" + std::to_string(st->B) +
-                       ", T=" + std::to_string(st->T) + ", not B=" + std::to_string(B) + ", T=" + std::to_string(T));
+    PdState* pd = state_of<PdState>(e);
+    SdTrain* st = &pd->held;
+    if ((rc = sd_train_check(e, *st, "st_period_disc_train", "T", -1, B, T))) return rc;
     if (!d_x && !grad_flat) return ST_OK;
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
     const int p = g.p;
-    const float slope = e->pd->cfg.lrelu_slope;
+    const float slope = pd->cfg.lrelu_slope;
 
     const PdActs A = pd_acts(B, g);
     const float* act = (const float*)st->act;
@@ -229,7 +211,7 @@ int st_period_disc_train_backward(st_engine* e, const float* const* d_fmaps, flo
     auto G = [&](const std::string& n) { return grad_flat + goff.at(n); };
     auto wn_bwd = [&](int i) {      // d w (in dW) -> d g, d v
         const int co = i < kPdLayers ? kPdCh[i + 1] : 1;
-        return launch_pd_weight_norm_bwd(dW, P(e, pd_name(i) + kPdV), P(e, pd_name(i) + kPdG), G(pd_name(i) + kPdV), G(pd_name(i) + kPdG), co,
+        return launch_pd_weight_norm_bwd(dW, P(e, pd_name(i) + kWnV), P(e, pd_name(i) + kWnG), G(pd_name(i) + kWnV), G(pd_name(i) + kWnG), co,
                                          (int)(pd_wnumel(i) / co), s);
     };
     // conv_post: the logits' gradient d_fmaps[4] (B, 1, H, p)
@@ -242,7 +224,7 @@ int st_period_disc_train_backward(st_engine* e, const float* const* d_fmaps, flo
             HIPCHK(e, wn_bwd(kPdLayers));
         }       // (no logits gradient: the three slices keep the caller's zeros)
     }
-    HIPCHK(e, launch_pd_post_dgrad(dy, e->pd->w[kPdLayers], a[4], d_fmaps[3], D, B, C4, H4, p, slope, s));      // D = d pre-activation of layer 4
+    HIPCHK(e, launch_pd_post_dgrad(dy, pd->w[kPdLayers], a[4], d_fmaps[3], D, B, C4, H4, p, slope, s));      // D = d pre-activation of layer 4
     for (int i = kPdLayers - 1; i >= 1; --i) {
         const int Cin = kPdCh[i], Cout = kPdCh[i + 1];
         if (grad_flat) {
@@ -254,7 +236,7 @@ int st_period_disc_train_backward(st_engine* e, const float* const* d_fmaps, flo
             HIPCHK(e, wn_bwd(i));
         }
         PdConvArgs c;       // d pre-activation of layer i - 1: the feature map below layer 1 is not returned, so nothing is added there
-        c.in = D; c.w = e->pd->w[i]; c.out = Dn; c.act = a[i - 1]; c.addg = i >= 2 ? d_fmaps[i - 2] : nullptr;
+        c.in = D; c.w = pd->w[i]; c.out = Dn; c.act = a[i - 1]; c.addg = i >= 2 ? d_fmaps[i - 2] : nullptr;
         c.B = B; c.Cin = Cout; c.Cout = Cin; c.Hin = g.H[i + 1]; c.Hout = g.H[i]; c.p = p; c.stride = kPdStride[i]; c.slope = slope;
         HIPCHK(e, launch_pd_conv_dgrad(c, s));
         std::swap(D, Dn);
@@ -263,7 +245,7 @@ int st_period_disc_train_backward(st_engine* e, const float* const* d_fmaps, flo
         HIPCHK(e, launch_pd_l0_wgrad(D, x, dW, G(pd_name(0) + "bias"), l0p, B, g.T, g.Tp, g.H[1], p, s));
         HIPCHK(e, wn_bwd(0));
     }
-    if (d_x) HIPCHK(e, launch_pd_l0_dgrad(D, e->pd->w[0], d_x, B, g.T, g.Tp, g.H[1], p, s));
+    if (d_x) HIPCHK(e, launch_pd_l0_dgrad(D, pd->w[0], d_x, B, g.T, g.Tp, g.H[1], p, s));
     return ST_OK;
 }
 

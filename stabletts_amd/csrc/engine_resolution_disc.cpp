@@ -5,9 +5,8 @@
 // and the effective weights w = v g / ||v|| are engine-owned, recomputed by st_finalize (new tensors) and st_repack (an in-place
 // update), not per call.  Kept per training forward: the spectrum and the post-activations of every band's layers 0-4; the leaky
 // ReLU's backward reads their signs.
-#include "engine_internal.h"
+#include "engine_disc.h"
 #include "audio_launch.h"
-#include "period_disc_launch.h"
 #include "resolution_disc_launch.h"
 #include "style_dp_launch.h"
 
@@ -25,7 +24,8 @@ constexpr int kRdConvs = kRdBands * kRdLayers + 1;            // index c * 5 + i
 constexpr int kRdPost = kRdConvs - 1;
 constexpr int kRdMaps = kRdBands * (kRdLayers - 1) + 1;       // returned maps: band-major layers 1..4, then conv_post's output
 
-struct RdState {
+struct RdState : DiscState {
+    ~RdState() override { if (wbuf) hipFree(wbuf); if (window) hipFree(window); }
     st_resolution_disc_config cfg{};
     float* wbuf = nullptr;              // the effective weights of the 26 convs, back to back
     float* w[kRdConvs] = {};
@@ -40,13 +40,11 @@ static int64_t rd_wnumel(int k) { return (int64_t)rd_cout(k) * rd_cin(k) * kRdRo
 static std::string rd_name(int k) {
     return k == kRdPost ? std::string("conv_post.") : "band_convs." + std::to_string(k / kRdLayers) + "." + std::to_string(k % kRdLayers) + ".";
 }
-static const char* kRdG = "parametrizations.weight.original0";
-static const char* kRdV = "parametrizations.weight.original1";
 
 static void rd_build_params(st_engine* e) {
     for (int k = 0; k < kRdConvs; ++k) {
-        expect(e, rd_name(k) + kRdG, {rd_cout(k), 1, 1, 1});
-        expect(e, rd_name(k) + kRdV, {rd_cout(k), rd_cin(k), kRdRows, rd_taps_w(k)});
+        expect(e, rd_name(k) + kWnG, {rd_cout(k), 1, 1, 1});
+        expect(e, rd_name(k) + kWnV, {rd_cout(k), rd_cin(k), kRdRows, rd_taps_w(k)});
         expect(e, rd_name(k) + "bias", {rd_cout(k)});
     }
 }
@@ -81,29 +79,15 @@ static RdActs rd_acts(int B, const RdGeom& g, bool all_layers) {
     return A;
 }
 
-void resolution_disc_destroy(st_engine* e) {
-    if (!e->rd) return;
-    if (e->rd->wbuf) hipFree(e->rd->wbuf);
-    if (e->rd->window) hipFree(e->rd->window);
-    delete e->rd; e->rd = nullptr;
-}
-
-// w = v g / ||v|| of the 26 convs, as kernels on `s`
-int resolution_disc_weights(st_engine* e, hipStream_t s) {
-    for (int k = 0; k < kRdConvs; ++k)
-        HIPCHK(e, launch_pd_weight_norm(P(e, rd_name(k) + kRdV), P(e, rd_name(k) + kRdG), e->rd->w[k], rd_cout(k), (int)(rd_wnumel(k) / rd_cout(k)), s));
-    if (e->sdt) e->sdt->have = false;      // the held activations are of the weights before
-    return ST_OK;
-}
-
 static int rd_check(st_engine* e, int B, int T, RdGeom* g) {
     int rc = check_sizes(e, B, T); if (rc) return rc;
-    const int W = e->rd->cfg.window_length;
+    const RdState* rd = state_of<RdState>(e);
+    const int W = rd->cfg.window_length;
     if (T <= W / 2)
         return e->fail(ST_ERR_INVALID, "T = " + std::to_string(T) + " is too short for window_length " + std::to_string(W) + ": the reflect padding of " +
                        std::to_string(W / 2) + " samples needs T > " + std::to_string(W / 2));
     if (B > 65535) return e->fail(ST_ERR_INVALID, "B too large for the resolution discriminator (at most 65535 items)");
-    *g = rd_geom(e->rd->cfg, T);
+    *g = rd_geom(rd->cfg, T);
     if ((int64_t)B * g->frames * W >= ((int64_t)1 << 31) || (int64_t)g->frames * g->bins >= ((int64_t)1 << 30))
         return e->fail(ST_ERR_INVALID, "B * T too large for the resolution discriminator (32-bit frame indexing)");
     return ST_OK;
@@ -112,7 +96,8 @@ static int rd_check(st_engine* e, int B, int T, RdGeom* g) {
 // The forward.  keep = nullptr: the spectrum and layer 0's activations live in the workspace arena and every other layer writes
 // its feature map only.  keep != nullptr: the spectrum and all post-activations go to keep's activation buffer as well.
 static int rd_forward(st_engine* e, const float* x, float* const* fmaps, int B, const RdGeom& g, SdTrain* keep, hipStream_t s) {
-    const float slope = e->rd->cfg.lrelu_slope;
+    const RdState* rd = state_of<RdState>(e);
+    const float slope = rd->cfg.lrelu_slope;
     const RdActs A = rd_acts(B, g, keep != nullptr);
     int rc;
     float* base;
@@ -129,7 +114,7 @@ static int rd_forward(st_engine* e, const float* x, float* const* fmaps, int B, 
         a[c][0] = base + A.a[c][0];
         for (int i = 1; i < kRdLayers; ++i) a[c][i] = keep ? base + A.a[c][i] : fmaps[c * (kRdLayers - 1) + i - 1];
     }
-    HIPCHK(e, launch_rd_stft(x, e->rd->window, spec, g.W, B, g.T, g.frames, s));
+    HIPCHK(e, launch_rd_stft(x, rd->window, spec, g.W, B, g.T, g.frames, s));
     for (int i = 0; i < kRdLayers; ++i) {
         RdConvArgs ca;
         ca.B = B; ca.Cin = i == 0 ? 2 : kRdCh; ca.Cout = kRdCh; ca.frames = g.frames; ca.taps_w = i == kRdLayers - 1 ? 3 : 9;
@@ -141,7 +126,7 @@ static int rd_forward(st_engine* e, const float* x, float* const* fmaps, int B, 
             bd.in_rs = i == 0 ? g.bins : g.Wd[c][i - 1];
             bd.Win = i == 0 ? g.Wd[c][0] : g.Wd[c][i - 1];
             bd.Wout = g.Wd[c][i];
-            bd.w = e->rd->w[k]; bd.bias = P(e, rd_name(k) + "bias");
+            bd.w = rd->w[k]; bd.bias = P(e, rd_name(k) + "bias");
             bd.out = a[c][i];
             bd.out2 = keep && i >= 1 ? fmaps[c * (kRdLayers - 1) + i - 1] : nullptr;
         }
@@ -155,7 +140,7 @@ static int rd_forward(st_engine* e, const float* x, float* const* fmaps, int B, 
     RdPostArgs pa{};
     for (int c = 0; c < kRdBands; ++c) pa.in[c] = a[c][kRdLayers - 1];
     std::copy(g.off, g.off + kRdBands + 1, pa.off);
-    pa.w = e->rd->w[kRdPost]; pa.bias = P(e, rd_name(kRdPost) + "bias"); pa.out = fmaps[kRdMaps - 1];
+    pa.w = rd->w[kRdPost]; pa.bias = P(e, rd_name(kRdPost) + "bias"); pa.out = fmaps[kRdMaps - 1];
     pa.B = B; pa.frames = g.frames; pa.slope = slope;
     HIPCHK(e, launch_rd_post_fwd(pa, s));
     return ST_OK;
@@ -187,9 +172,9 @@ int st_create_resolution_discriminator(const st_resolution_disc_config* cfg, int
         if (cfg->band_hi[c] <= cfg->band_lo[c]) { g_create_error = "every band must hold at least one bin"; return ST_ERR_UNSUPPORTED; }
     }
     st_engine* e = nullptr;
-    if (int rc = new_handle(KIND_RESOLUTION_DISC, device, &e)) return rc;
-    e->rd = new RdState();
-    e->rd->cfg = *cfg;
+    if (int rc = new_handle(KIND_RESOLUTION_DISC, device, std::make_unique<RdState>(), &e)) return rc;
+    RdState* rd = state_of<RdState>(e);
+    rd->cfg = *cfg;
     rd_build_params(e);
     int64_t total = 0;
     for (int k = 0; k < kRdConvs; ++k) total += (rd_wnumel(k) + 63) / 64 * 64;
@@ -198,24 +183,27 @@ int st_create_resolution_discriminator(const st_resolution_disc_config* cfg, int
     // the window of torchaudio's Spectrogram, whose distance from the exact one (~9e-8) would otherwise count as this engine's error
     const float step = (float)(2.0 * M_PI / W);
     for (int n = 0; n < W; ++n) win[n] = 0.5f - 0.5f * (float)std::cos((double)((float)n * step));
-    if (hipMalloc((void**)&e->rd->wbuf, (size_t)total * 4) != hipSuccess || hipMalloc((void**)&e->rd->window, (size_t)W * 4) != hipSuccess ||
-        hipMemcpy(e->rd->window, win.data(), (size_t)W * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    if (hipMalloc((void**)&rd->wbuf, (size_t)total * 4) != hipSuccess || hipMalloc((void**)&rd->window, (size_t)W * 4) != hipSuccess ||
+        hipMemcpy(rd->window, win.data(), (size_t)W * 4, hipMemcpyHostToDevice) != hipSuccess) {
         g_create_error = "hipMalloc failed";
-        resolution_disc_destroy(e);
         delete e;
         return ST_ERR_HIP;
     }
     int64_t off = 0;
-    for (int k = 0; k < kRdConvs; ++k) { e->rd->w[k] = e->rd->wbuf + off; off += (rd_wnumel(k) + 63) / 64 * 64; }
+    for (int k = 0; k < kRdConvs; ++k) {
+        rd->w[k] = rd->wbuf + off; off += (rd_wnumel(k) + 63) / 64 * 64;
+        rd->convs.push_back({rd_name(k), rd->w[k], rd_cout(k), rd_wnumel(k)});
+    }
     e->weight_bytes += total * 4 + (int64_t)W * 4;
     *out = e;
     return ST_OK;
 }
 
 int st_resolution_disc_fmap_shape(const st_engine* e, int T, int index, int64_t* channels, int64_t* frames, int64_t* width) {
-    if (!e || e->kind != KIND_RESOLUTION_DISC || !channels || !frames || !width || T < 1 || index < 0 || index >= kRdMaps) return ST_ERR_INVALID;
-    if (T <= e->rd->cfg.window_length / 2) return ST_ERR_INVALID;
-    const RdGeom g = rd_geom(e->rd->cfg, T);
+    const RdState* rd = state_if<RdState>(e, KIND_RESOLUTION_DISC);
+    if (!rd || !channels || !frames || !width || T < 1 || index < 0 || index >= kRdMaps) return ST_ERR_INVALID;
+    if (T <= rd->cfg.window_length / 2) return ST_ERR_INVALID;
+    const RdGeom g = rd_geom(rd->cfg, T);
     *frames = g.frames;
     if (index == kRdMaps - 1) { *channels = 1; *width = g.off[kRdBands]; }
     else { *channels = kRdCh; *width = g.Wd[index / (kRdLayers - 1)][index % (kRdLayers - 1) + 1]; }
@@ -223,9 +211,10 @@ int st_resolution_disc_fmap_shape(const st_engine* e, int T, int index, int64_t*
 }
 
 int st_resolution_disc_wgrad_planes(const st_engine* e, int B, int T, int band, int layer) {
-    if (!e || e->kind != KIND_RESOLUTION_DISC || B < 1 || T <= e->rd->cfg.window_length / 2 || band < 0 || band >= kRdBands || layer < 0 || layer >= kRdLayers)
+    const RdState* rd = state_if<RdState>(e, KIND_RESOLUTION_DISC);
+    if (!rd || B < 1 || T <= rd->cfg.window_length / 2 || band < 0 || band >= kRdBands || layer < 0 || layer >= kRdLayers)
         return ST_ERR_INVALID;
-    const RdGeom g = rd_geom(e->rd->cfg, T);
+    const RdGeom g = rd_geom(rd->cfg, T);
     return rd_wgrad_planes(B, layer == 0 ? 2 : kRdCh, g.frames, g.Wd[band][layer], layer == kRdLayers - 1 ? 3 : 9);
 }
 
@@ -240,7 +229,7 @@ int st_resolution_disc_train_forward(st_engine* e, const float* x, float* const*
     RdGeom g;
     int rc = rd_entry(e, x, fmaps, B, T, &g); if (rc) return rc;
     HIPCHK(e, hipSetDevice(e->device));
-    SdTrain* st = sd_train_begin(e);
+    SdTrain* st = state_of<RdState>(e)->begin();
     if ((rc = rd_forward(e, x, fmaps, B, g, st, (hipStream_t)stream))) return rc;
     sd_train_commit(st, B, T, 0.0f, 0, false);
     return ST_OK;
@@ -251,15 +240,13 @@ int st_resolution_disc_train_backward(st_engine* e, const float* const* d_fmaps,
     if (!d_fmaps) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     RdGeom g;
     if ((rc = rd_check(e, B, T, &g))) return rc;
-    SdTrain* st = e->sdt;
-    if (!st || !st->have) return e->fail(ST_ERR_STATE, "st_resolution_disc_train_backward needs a preceding st_resolution_disc_train_forward");
-    if (B != st->B || T != st->T)
-        return e->fail(ST_ERR_STATE, "st_resolution_disc_train_backward: the engine holds the activations of a forward with B=" + std::to_string(st->B) +
-                       ", T=" + std::to_string(st->T) + ", not B=" + std::to_string(B) + ", T=" + std::to_string(T));
+    RdState* rd = state_of<RdState>(e);
+    SdTrain* st = &rd->held;
+    if ((rc = sd_train_check(e, *st, "st_resolution_disc_train", "T", -1, B, T))) return rc;
     if (!d_x && !grad_flat) return ST_OK;
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    const float slope = e->rd->cfg.lrelu_slope;
+    const float slope = rd->cfg.lrelu_slope;
     const int Fr = g.frames, L4 = kRdLayers - 1;
 
     const RdActs A = rd_acts(B, g, true);
@@ -292,14 +279,14 @@ int st_resolution_disc_train_backward(st_engine* e, const float* const* d_fmaps,
     train_grad_layout(e, &goff);
     auto G = [&](const std::string& n) { return grad_flat + goff.at(n); };
     auto wn_bwd = [&](int k) {      // d w (in dW) -> d g, d v
-        return launch_pd_weight_norm_bwd(dW, P(e, rd_name(k) + kRdV), P(e, rd_name(k) + kRdG), G(rd_name(k) + kRdV), G(rd_name(k) + kRdG), rd_cout(k),
+        return launch_pd_weight_norm_bwd(dW, P(e, rd_name(k) + kWnV), P(e, rd_name(k) + kWnG), G(rd_name(k) + kWnV), G(rd_name(k) + kWnG), rd_cout(k),
                                          (int)(rd_wnumel(k) / rd_cout(k)), s);
     };
     // conv_post: the logits' gradient d_fmaps[20] (B, 1, frames, Wc)
     RdPostArgs pa{};
     for (int c = 0; c < kRdBands; ++c) { pa.in[c] = a[c][L4]; pa.addg[c] = d_fmaps[c * L4 + L4 - 1]; pa.dpre[c] = D[c]; }
     std::copy(g.off, g.off + kRdBands + 1, pa.off);
-    pa.w = e->rd->w[kRdPost]; pa.dy = d_fmaps[kRdMaps - 1]; pa.dw = dW; pa.part = red; pa.B = B; pa.frames = Fr; pa.slope = slope;
+    pa.w = rd->w[kRdPost]; pa.dy = d_fmaps[kRdMaps - 1]; pa.dw = dW; pa.part = red; pa.B = B; pa.frames = Fr; pa.slope = slope;
     if (grad_flat && pa.dy) {
         HIPCHK(e, launch_rd_post_wgrad(pa, s));
         HIPCHK(e, launch_sd_sum_frames(pa.dy, G(rd_name(kRdPost) + "bias"), B, 1, Fr * g.off[kRdBands], 0, s));
@@ -329,7 +316,7 @@ int st_resolution_disc_train_backward(st_engine* e, const float* const* d_fmaps,
         for (int c = 0; c < kRdBands; ++c) {
             RdBand& bd = ca.band[c];
             bd.in = D[c]; bd.in_rs = g.Wd[c][i]; bd.Win = g.Wd[c][i]; bd.Wout = g.Wd[c][i - 1];
-            bd.w = e->rd->w[c * kRdLayers + i]; bd.out = Dn[c]; bd.act = a[c][i - 1];
+            bd.w = rd->w[c * kRdLayers + i]; bd.out = Dn[c]; bd.act = a[c][i - 1];
             bd.addg = i >= 2 ? d_fmaps[c * L4 + i - 2] : nullptr;
         }
         HIPCHK(e, launch_rd_conv_dgrad(ca, s));
@@ -337,10 +324,10 @@ int st_resolution_disc_train_backward(st_engine* e, const float* const* d_fmaps,
     }
     if (d_x) {
         RdL0DgradArgs la{};
-        for (int c = 0; c < kRdBands; ++c) { la.d0[c] = D[c]; la.w[c] = e->rd->w[c * kRdLayers]; la.lo[c] = g.lo[c]; la.hi[c] = g.lo[c] + g.Wd[c][0]; }
+        for (int c = 0; c < kRdBands; ++c) { la.d0[c] = D[c]; la.w[c] = rd->w[c * kRdLayers]; la.lo[c] = g.lo[c]; la.hi[c] = g.lo[c] + g.Wd[c][0]; }
         la.dspec = scr + o_dspec; la.B = B; la.frames = Fr; la.bins = g.bins;
         HIPCHK(e, launch_rd_l0_dgrad(la, s));
-        HIPCHK(e, launch_rd_stft_backward(la.dspec, e->rd->window, scr + o_rows, d_x, g.W, B, g.T, Fr, s));
+        HIPCHK(e, launch_rd_stft_backward(la.dspec, rd->window, scr + o_rows, d_x, g.W, B, g.T, Fr, s));
     }
     return ST_OK;
 }

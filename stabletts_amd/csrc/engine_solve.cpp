@@ -1,7 +1,7 @@
 // The ODE solve behind st_cfm_solve (include/stabletts_hip.h): torchdiffeq's fixed-grid solvers over one or more solve parts on
 // as many streams, eager or replayed from a HIP graph, and the adaptive Runge-Kutta pairs and implicit Adams with their host-side
 // controllers.  Reference path: models/flow_matching.py:25-67 (CFMDecoder.forward, cfg_wrapper), torchdiffeq's solvers.
-#include "engine_internal.h"
+#include "engine_dit.h"
 
 #include <algorithm>
 #include <cmath>
@@ -78,24 +78,26 @@ static const RkTableau kAdaptiveHeun = {
 
 // f(t, state in p.x16) -> kout for the host-controlled solvers (the time tables are rebuilt per evaluation)
 int eval_rhs(st_engine* e, const Plan& p, const float* mask, int use_cfg, float cfg_strength, float t, float* kout, hipStream_t s) {
+    DitState* dit = dit_of(e);
     HIPCHK(e, launch_set_scalar(p.tvals, t, s));
     int r = run_time_tables(e, p, s); if (r) return r;
     r = run_estimator(e, p, mask, 0, s); if (r) return r;
     ProfScope ps(e, s, PC_ODE, 0);
-    HIPCHK(e, launch_cfg_combine(e->dt, p.v32, p.B, (int64_t)p.T * e->Mp, use_cfg, cfg_strength, kout, nullptr, nullptr, nullptr, 0.f, s));
-    e->last_nfe += 1;
+    HIPCHK(e, launch_cfg_combine(e->dt, p.v32, p.B, (int64_t)p.T * dit->Mp, use_cfg, cfg_strength, kout, nullptr, nullptr, nullptr, 0.f, s));
+    dit->last_nfe += 1;
     return ST_OK;
 }
 
 int solve_adaptive(st_engine* e, const Plan& p, const float* mask, int use_cfg, float cfg_strength,
                    const RkTableau& tb, hipStream_t s) {
+    DitState* dit = dit_of(e);
     const int S = tb.n;
     bool fsal = tb.csol[S] == 0.0;
     for (int j = 0; j < S; ++j) fsal = fsal && tb.csol[j] == tb.beta[S - 1][j];
     const double rtol = 1e-5, atol = 1e-5, t_end = 1.0;
     const int B = p.B;
-    const int64_t nstate = (int64_t)B * p.T * e->Mp;
-    const double count = (double)B * e->M * p.T;            // padded channels carry zeros and do not count
+    const int64_t nstate = (int64_t)B * p.T * dit->Mp;
+    const double count = (double)B * dit->M * p.T;            // padded channels carry zeros and do not count
     int rc;
     auto eval = [&](double t, float* kout) { return eval_rhs(e, p, mask, use_cfg, cfg_strength, (float)t, kout, s); };
     float host2[2];
@@ -162,7 +164,7 @@ int solve_adaptive(st_engine* e, const Plan& p, const float* mask, int use_cfg, 
             const double dfactor = ratio < 1.0 ? 1.0 : 0.2;
             dt_next = dt * std::min(10.0, std::max(0.9 / pow(ratio, 1.0 / (double)tb.order), dfactor));
         }
-        e->last_steps += 1;
+        dit->last_steps += 1;
         if (accept) {
             if (t1 >= t_end) {      // dense output at t_end inside [t, t1] -> p.ynew; slot 6 of the kernel is f1 = k[S]
                 const float* ks[7]; float cm[7];
@@ -178,7 +180,7 @@ int solve_adaptive(st_engine* e, const Plan& p, const float* mask, int use_cfg, 
             std::swap(k[0], k[S]);                   // f0 <- k[-1]
             t = t1;
         } else {
-            e->last_rejects += 1;
+            dit->last_rejects += 1;
         }
         dt = dt_next;
         if (!(dt > 0.0) || dt < 1e-12) return e->fail(ST_ERR_INVALID, std::string(tb.name) + ": step size underflow");
@@ -216,21 +218,22 @@ static void adams_weights(int order, bool implicit, double* w) {
 // an 8-byte read-back per iteration), at most 4 times; no convergence -> the oldest history entry is dropped.
 int solve_implicit_adams(st_engine* e, const Plan& p, const float* mask, int use_cfg, float cfg_strength, int n_steps,
                          hipStream_t s) {
+    DitState* dit = dit_of(e);
     constexpr int kMaxHist = 11, kMaxIters = 4, kExtra = 11;
     const double rtol = 1e-5, atol = 1e-5;
-    const int64_t nstate = (int64_t)p.B * p.T * e->Mp;
+    const int64_t nstate = (int64_t)p.B * p.T * dit->Mp;
     const size_t sbytes = (size_t)nstate * 4;
     int rc;
     // 19 state-sized fp32 buffers: 11 history + zero + dy x 2 + delta + f / Runge-Kutta stages x 3 + 1 spare; the plan has 8
-    if (e->adams_bytes < sbytes * kExtra) {
-        if (e->adams_buf) { HIPCHK(e, hipStreamSynchronize(s)); hipFree(e->adams_buf); e->adams_buf = nullptr; e->adams_bytes = 0; }
-        HIPCHK(e, hipMalloc(&e->adams_buf, sbytes * kExtra));
-        e->adams_bytes = sbytes * kExtra;
+    if (dit->adams_bytes < sbytes * kExtra) {
+        if (dit->adams_buf) { HIPCHK(e, hipStreamSynchronize(s)); hipFree(dit->adams_buf); dit->adams_buf = nullptr; dit->adams_bytes = 0; }
+        HIPCHK(e, hipMalloc(&dit->adams_buf, sbytes * kExtra));
+        dit->adams_bytes = sbytes * kExtra;
     }
     std::vector<float*> pool;
     for (int j = 0; j < 7; ++j) pool.push_back(p.kbuf[j]);
     pool.push_back(p.ynew);
-    for (int j = 0; j < kExtra; ++j) pool.push_back((float*)((char*)e->adams_buf + (size_t)j * sbytes));
+    for (int j = 0; j < kExtra; ++j) pool.push_back((float*)((char*)dit->adams_buf + (size_t)j * sbytes));
     float* zero = pool.back(); pool.pop_back();
     float* dyA = pool.back(); pool.pop_back();
     float* dyB = pool.back(); pool.pop_back();
@@ -297,7 +300,7 @@ int solve_implicit_adams(st_engine* e, const Plan& p, const float* mask, int use
             converged = host2[0] == 0.0f;
             std::swap(dy, dyn);
         }
-        if (!converged) { pool.push_back(hist.back()); hist.pop_back(); e->last_rejects += 1; }     // (torchdiffeq warns and drops the oldest sample)
+        if (!converged) { pool.push_back(hist.back()); hist.pop_back(); dit->last_rejects += 1; }     // (torchdiffeq warns and drops the oldest sample)
         if ((rc = combine(y, {dy}, {1.0f}, y, true))) return rc;            // y1 = y0 + dy, and its operands for the next f0
     }
     return ST_OK;
@@ -323,6 +326,7 @@ struct Solve {
 // bitwise independent of the split (an utterance never shares a tile with another).  Adaptive solvers keep ONE
 // part: their step controller takes the error norm over the whole batch.  ST_SPLIT=0|1|2 overrides (read per call).
 int solve_part_count(const st_engine* e, int B, int T, int use_cfg, bool adaptive) {
+    const DitState* dit = dit_of(e);
     int nparts = 1;
     const char* sv = getenv("ST_SPLIT");
     const int want = sv ? atoi(sv) : kDefaultSplit;
@@ -333,7 +337,7 @@ int solve_part_count(const st_engine* e, int B, int T, int use_cfg, bool adaptiv
     // ... with the generic q/k/v tile.  With the weight-stationary q/k/v kernel (qkv_ws.hip, default) TWO parts are faster: its
     // persistent blocks want >= 5 tiles each, i.e. half-batch launches (paired A/B, round 4: 2 parts + qkv_ws 24.60 ms against
     // 4 parts + generic tile 24.91, ragged 21.61 against 22.09; profiles/r04b_ab_parts_qkv_ws.txt)
-    if (!adaptive && !e->capture && want != 0 && want != 1 && want != 2 && frames >= 48000 && B >= 32 && !(e->qkv_ws && e->sink)) nparts = 4;
+    if (!adaptive && !e->capture && want != 0 && want != 1 && want != 2 && frames >= 48000 && B >= 32 && !(dit->qkv_ws && dit->sink)) nparts = 4;
     if (want > 2 && B >= want) nparts = std::min(want, kMaxParts);
     if (want == 1 || want == 0) nparts = 1;
     return nparts;
@@ -342,21 +346,22 @@ int solve_part_count(const st_engine* e, int B, int T, int use_cfg, bool adaptiv
 // Boundary conversions into the parts (caller's layouts -> engine operands), on the caller's stream.
 int boundary_in(st_engine* e, Solve& sv, const float* mu, const float* mask, const float* z, const float* c, const float* fake_speaker,
                 const float* fake_content, const std::vector<float>& tv, hipStream_t s) {
+    DitState* dit = dit_of(e);
     const int T = sv.T;
     for (auto& pt : sv.parts) {
         const Plan& p = pt.p;
         ProfScope ps(e, s, PC_PREP, 0);
         HIPCHK(e, launch_set_values(p.tvals, tv.data(), (int)tv.size(), s));   // by kernel argument: no copy, no sync
         HIPCHK(e, launch_mask_prep(mask + (int64_t)pt.b0 * T, pt.nb, T, p.Tp, p.n_full, p.kv_end, p.kbias, p.t_lim, s));
-        HIPCHK(e, hipMemsetAsync(p.v32, 0, (size_t)p.N * T * e->Mp * 4, s));      // frames of skipped tiles: v = 0 (estimator.py:138)
+        HIPCHK(e, hipMemsetAsync(p.v32, 0, (size_t)p.N * T * dit->Mp * 4, s));      // frames of skipped tiles: v = 0 (estimator.py:138)
         HIPCHK(e, launch_cvec_prep(mask + (int64_t)pt.b0 * T, nullptr, pt.nb, T, p.maskbuf, s));      // plain copy of the (B,1,T) mask
         pt.mask = p.maskbuf;
-        HIPCHK(e, launch_to_time_major(e->dt, mu + pt.b0 * sv.bct, pt.nb, e->M, T, e->Mp, nullptr, p.mu16, nullptr, s));
-        HIPCHK(e, launch_to_time_major(e->dt, z + pt.b0 * sv.bct, pt.nb, e->M, T, e->Mp, p.xstate, p.x16, p.x16lo, s));
-        HIPCHK(e, launch_cvec_prep(c + (int64_t)pt.b0 * e->G, sv.use_cfg ? fake_speaker : nullptr, pt.nb, e->G, p.cvec, s));
+        HIPCHK(e, launch_to_time_major(e->dt, mu + pt.b0 * sv.bct, pt.nb, dit->M, T, dit->Mp, nullptr, p.mu16, nullptr, s));
+        HIPCHK(e, launch_to_time_major(e->dt, z + pt.b0 * sv.bct, pt.nb, dit->M, T, dit->Mp, p.xstate, p.x16, p.x16lo, s));
+        HIPCHK(e, launch_cvec_prep(c + (int64_t)pt.b0 * dit->G, sv.use_cfg ? fake_speaker : nullptr, pt.nb, dit->G, p.cvec, s));
         if (sv.use_cfg) {
             // uncond branch inputs (flow_matching.py:59-60): fake_content over ALL frames, fake_speaker per item
-            HIPCHK(e, launch_fill_rows16(e->dt, fake_content, e->M, e->Mp, T,
+            HIPCHK(e, launch_fill_rows16(e->dt, fake_content, dit->M, dit->Mp, T,
                                          (char*)p.mu16 + (size_t)pt.nb * sv.per_item * 2, s));
         }
     }
@@ -415,11 +420,12 @@ int step_fixed(st_engine* e, const Solve& sv, const Part& pt, int i) {
 // from and joined back into `cs` -- on every exit: the guard joins them when an error returns early (before the caller re-zeroes
 // the arena they write, and before a capture ends), and the host interleaves the parts step by step, so part k trails part 0.
 int solve_body(st_engine* e, Solve& sv, hipStream_t cs) {
-    StreamFork& f = e->part_streams;
+    DitState* dit = dit_of(e);
+    StreamFork& f = dit->part_streams;
     ForkGuard guard{f, cs};
     const int nparts = (int)sv.parts.size();
     int rc;
-    e->conc = nparts;
+    dit->conc = nparts;
     HIPCHK(e, f.fork(cs, nparts - 1));
     for (int k = 0; k < nparts; ++k) sv.parts[k].s = k == 0 ? cs : f.child[k - 1];
     for (auto& pt : sv.parts) {
@@ -452,27 +458,28 @@ int solve_body(st_engine* e, Solve& sv, hipStream_t cs) {
 // not happen inside a capture) and replayed afterwards.  Adaptive solvers have a host-side controller and always run eagerly; so
 // do profiled / debug-captured solves.  Sets *replayed when the graph ran the body on `s` (else the caller runs it eagerly).
 int solve_graph(st_engine* e, Solve& sv, hipStream_t s, bool* replayed) {
+    DitState* dit = dit_of(e);
     const char* genv = getenv("ST_HIP_GRAPH");
     if (!(genv && atoi(genv) == 1 && !sv.adaptive && !e->prof && !e->capture)) return ST_OK;
     const int nparts = (int)sv.parts.size();
-    st_engine::SolveGraph* g = nullptr;
-    for (auto& q : e->graphs)
+    DitState::SolveGraph* g = nullptr;
+    for (auto& q : dit->graphs)
         if (q.B == sv.B && q.T == sv.T && q.n_steps == sv.n_steps && q.solver == sv.solver && q.use_cfg == (sv.use_cfg != 0) &&
             q.cfg_strength == sv.cfg_strength && q.ws == e->ws && q.parts == nparts) g = &q;
     if (!g) {
-        if (e->graphs.size() >= 16) e->drop_graphs();
-        e->graphs.push_back({sv.B, sv.T, sv.n_steps, sv.solver, sv.use_cfg != 0, sv.cfg_strength, e->ws, nparts, 0, nullptr});
-        g = &e->graphs.back();
+        if (dit->graphs.size() >= 16) dit->drop_graphs();
+        dit->graphs.push_back({sv.B, sv.T, sv.n_steps, sv.solver, sv.use_cfg != 0, sv.cfg_strength, e->ws, nparts, 0, nullptr});
+        g = &dit->graphs.back();
     }
     if (g->seen >= 1 && !g->exec) {
         // captured on an engine-owned stream (the caller's may be the legacy default stream, which cannot
         // capture); nothing executes during capture, the instantiated graph is launched on the caller's stream
-        if (!e->gstream) HIPCHK(e, hipStreamCreateWithFlags(&e->gstream, hipStreamNonBlocking));
+        if (!dit->gstream) HIPCHK(e, hipStreamCreateWithFlags(&dit->gstream, hipStreamNonBlocking));
         hipGraph_t graph = nullptr;
-        HIPCHK(e, hipStreamBeginCapture(e->gstream, hipStreamCaptureModeRelaxed));
-        const int brc = solve_body(e, sv, e->gstream);      // (its part streams are joined back into the capture stream on every exit)
-        const hipError_t ec = hipStreamEndCapture(e->gstream, &graph);
-        e->conc = 1;
+        HIPCHK(e, hipStreamBeginCapture(dit->gstream, hipStreamCaptureModeRelaxed));
+        const int brc = solve_body(e, sv, dit->gstream);      // (its part streams are joined back into the capture stream on every exit)
+        const hipError_t ec = hipStreamEndCapture(dit->gstream, &graph);
+        dit->conc = 1;
         if (brc) { if (graph) hipGraphDestroy(graph); return brc; }
         if (ec != hipSuccess || !graph) return e->fail(ST_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ec));
         const hipError_t ei = hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0);
@@ -493,8 +500,8 @@ extern "C" int st_cfm_solve(st_engine* e, const float* mu, const float* mask, co
                             int n_steps, int solver, int use_cfg, float cfg_strength,
                             const float* fake_speaker, const float* fake_content,
                             float* out, int B, int T, void* stream) {
-    int rc = check_ready(e, B, T); if (rc) return rc;
-    if ((rc = check_handle(e, KIND_DECODER))) return rc;
+    int rc = check_ready(e, KIND_DECODER, B, T); if (rc) return rc;
+    DitState* dit = dit_of(e);
     if (!mu || !mask || !z || !c || !out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if (n_steps < 1 || n_steps > 4096) return e->fail(ST_ERR_INVALID, "n_steps out of range");
     if (solver < ST_SOLVER_EULER || solver > ST_SOLVER_IMPLICIT_ADAMS)
@@ -508,7 +515,7 @@ extern "C" int st_cfm_solve(st_engine* e, const float* mu, const float* mask, co
     const int stages = solver == ST_SOLVER_EULER ? 1 : (solver == ST_SOLVER_MIDPOINT ? 2 : 4);
     const int n_t = adaptive ? 1 : n_steps * stages;
     const int nparts = solve_part_count(e, B, T, use_cfg, adaptive);
-    Solve sv{B, T, n_steps, solver, use_cfg, cfg_strength, adams, adaptive, (int64_t)T * e->Mp, (int64_t)e->M * T,
+    Solve sv{B, T, n_steps, solver, use_cfg, cfg_strength, adams, adaptive, (int64_t)T * dit->Mp, (int64_t)dit->M * T,
              std::vector<Part>((size_t)nparts), std::vector<float>((size_t)n_steps)};
     {
         size_t off = 0;
@@ -518,12 +525,12 @@ extern "C" int st_cfm_solve(st_engine* e, const float* mu, const float* mask, co
             off = layout_plan(e, sv.parts[k].nb, T, use_cfg != 0, n_t, off, &sv.parts[k].p);
         }
         if ((rc = ensure_ws(e, off))) return rc;
-        e->arena_poisoned();
+        dit->arena_poisoned(e);
         if ((rc = arena_fresh(e, layout_sig(2, B, T, use_cfg != 0, n_t, nparts), off, s))) return rc;
         for (auto& pt : sv.parts) bind_plan(e, &pt.p);
     }
     if ((rc = ensure_rope(e, T, s))) return rc;
-    if (nparts > 1) HIPCHK(e, e->part_streams.ensure(nparts - 1, 1, 0));
+    if (nparts > 1) HIPCHK(e, dit->part_streams.ensure(nparts - 1, 1, 0));
 
     // evaluation times, fp32 arithmetic as torchdiffeq does on the fp32 t_span (flow_matching.py:46)
     const std::vector<float> grid = linspace01(n_steps);
@@ -536,18 +543,18 @@ extern "C" int st_cfm_solve(st_engine* e, const float* mu, const float* mask, co
         else { tv[4 * i] = t0; tv[4 * i + 1] = t0 + dt / 3.0f; tv[4 * i + 2] = t0 + dt * 2.0f / 3.0f; tv[4 * i + 3] = t1; }
     }
     if ((rc = boundary_in(e, sv, mu, mask, z, c, fake_speaker, fake_content, tv, s))) return rc;
-    e->last_nfe = adaptive ? 0 : (int64_t)n_t; e->last_steps = adaptive && !adams ? 0 : n_steps; e->last_rejects = 0;
+    dit->last_nfe = adaptive ? 0 : (int64_t)n_t; dit->last_steps = adaptive && !adams ? 0 : n_steps; dit->last_rejects = 0;
 
     bool replayed = false;
     if ((rc = solve_graph(e, sv, s, &replayed))) return rc;
     if (!replayed) {
         rc = solve_body(e, sv, s);      // (returns with its part streams joined into s)
-        e->conc = 1;
+        dit->conc = 1;
         if (rc) { e->ws_sig = 0; return rc; }      // (a half-enqueued body: re-zero the arena next time)
     }
     for (auto& pt : sv.parts) {      // boundary conversion of the result
         ProfScope ps(e, s, PC_PREP, 0);
-        HIPCHK(e, launch_from_time_major(adaptive && !adams ? pt.p.ynew : pt.p.xstate, pt.nb, e->M, T, e->Mp, out + pt.b0 * sv.bct, s, e->status_dev));
+        HIPCHK(e, launch_from_time_major(adaptive && !adams ? pt.p.ynew : pt.p.xstate, pt.nb, dit->M, T, dit->Mp, out + pt.b0 * sv.bct, s, dit->status_dev));
     }
     return ST_OK;
 }

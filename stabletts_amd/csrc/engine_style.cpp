@@ -12,8 +12,10 @@ using namespace sthost;
 
 namespace sthost {
 
-struct StyleState {
+// Reads the loaded parameters in place: nothing to pack
+struct StyleState : HeldState {
     st_style_encoder_config cfg{};
+    StyleState() : HeldState("st_repack: style-encoder / duration-predictor handles read their parameters in place") {}
 };
 
 static void style_build_params(st_engine* e, const st_style_encoder_config& c) {
@@ -29,8 +31,6 @@ static void style_build_params(st_engine* e, const st_style_encoder_config& c) {
     expect(e, "fc.weight", {O, Hd}); expect(e, "fc.bias", {O});                              // :65
 }
 
-void style_destroy(st_engine* e) { delete e->sty; e->sty = nullptr; }
-
 int sd_train_grow(st_engine* e, char** buf, size_t* cap, size_t bytes) {
     if (bytes <= *cap) return ST_OK;
     if (*buf) { HIPCHK(e, hipDeviceSynchronize()); HIPCHK(e, hipFree(*buf)); *buf = nullptr; *cap = 0; }
@@ -39,32 +39,26 @@ int sd_train_grow(st_engine* e, char** buf, size_t* cap, size_t bytes) {
     return ST_OK;
 }
 
-void sd_train_destroy(st_engine* e) {
-    if (!e->sdt) return;
-    if (e->sdt->act) hipFree(e->sdt->act);
-    if (e->sdt->scr) hipFree(e->sdt->scr);
-    delete e->sdt; e->sdt = nullptr;
+HeldState::~HeldState() {
+    if (held.act) hipFree(held.act);
+    if (held.scr) hipFree(held.scr);
 }
 
-SdTrain* sd_train_begin(st_engine* e) {
-    if (!e->sdt) e->sdt = new SdTrain();
-    e->sdt->have = false;
-    return e->sdt;
-}
+int HeldState::finalize(st_engine*) { held.have = false; return ST_OK; }
 
 void sd_train_commit(SdTrain* st, int B, int T, float p_dropout, unsigned long long seed, bool masked) {
     st->serial += 1; st->have = true; st->B = B; st->T = T; st->p = p_dropout; st->seed = seed; st->masked = masked;
 }
 
-int sd_train_check(st_engine* e, const char* entry, const char* t_name, int64_t serial, int B, int T) {
-    const SdTrain* st = e->sdt;
+int sd_train_check(st_engine* e, const SdTrain& st, const char* entry, const char* t_name, int64_t serial, int B, int T) {
     const std::string fn(entry);
-    if (!st || !st->have) return e->fail(ST_ERR_STATE, fn + "_backward needs a preceding " + fn + "_forward");
-    if (serial != st->serial || B != st->B || T != st->T) {
+    if (!st.have) return e->fail(ST_ERR_STATE, fn + "_backward needs a preceding " + fn + "_forward");
+    if ((serial >= 0 && serial != st.serial) || B != st.B || T != st.T) {
         const std::string t = std::string(", ") + t_name + "=";
-        return e->fail(ST_ERR_STATE, fn + "_backward: the engine holds the activations of forward #" + std::to_string(st->serial) +
-                       " (B=" + std::to_string(st->B) + t + std::to_string(st->T) + "), not of #" + std::to_string(serial) +
-                       " (B=" + std::to_string(B) + t + std::to_string(T) + ")");
+        const std::string held = "B=" + std::to_string(st.B) + t + std::to_string(st.T), asked = "B=" + std::to_string(B) + t + std::to_string(T);
+        if (serial < 0) return e->fail(ST_ERR_STATE, fn + "_backward: the engine holds the activations of a forward with " + held + ", not " + asked);
+        return e->fail(ST_ERR_STATE, fn + "_backward: the engine holds the activations of forward #" + std::to_string(st.serial) +
+                       " (" + held + "), not of #" + std::to_string(serial) + " (" + asked + ")");
     }
     return ST_OK;
 }
@@ -83,10 +77,10 @@ int st_create_style_encoder(const st_style_encoder_config* cfg, int device, st_e
     if (cfg->style_hidden / cfg->style_head != 64) return bad("native attention is built for head_dim == 64", ST_ERR_UNSUPPORTED);
     if (cfg->style_kernel_size != 1 && cfg->style_kernel_size != 3 && cfg->style_kernel_size != 5)
         return bad("native convolutions are built for style_kernel_size 1, 3 or 5", ST_ERR_UNSUPPORTED);
+    auto state = std::make_unique<StyleState>();
+    state->cfg = *cfg;
     st_engine* e = nullptr;
-    if (int rc = new_handle(KIND_STYLE_ENCODER, device, &e)) return rc;
-    e->sty = new StyleState();
-    e->sty->cfg = *cfg;
+    if (int rc = new_handle(KIND_STYLE_ENCODER, device, std::move(state), &e)) return rc;
     style_build_params(e, *cfg);
     *out = e;
     return ST_OK;
@@ -97,7 +91,7 @@ int st_style_encoder_forward(st_engine* e, const float* mel, const float* mask, 
     if ((rc = check_finalized(e))) return rc;
     if (!mel || !c_out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if ((rc = check_sizes(e, B, T))) return rc;
-    const st_style_encoder_config& c = e->sty->cfg;
+    const st_style_encoder_config& c = state_of<StyleState>(e)->cfg;
     const int I = c.n_mel_channels, Hd = c.style_hidden, O = c.style_vector_dim, K = c.style_kernel_size, NH = c.style_head;
     const int64_t R = (int64_t)B * T;
     if (R * 3 * Hd >= ((int64_t)1 << 31) || R * O >= ((int64_t)1 << 31)) return e->fail(ST_ERR_INVALID, "B*T too large");
@@ -169,13 +163,13 @@ int st_style_encoder_train_forward(st_engine* e, const float* mel, const float* 
     if (!mel || !c_out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if ((rc = check_sizes(e, B, T))) return rc;
     if ((rc = check_dropout(e, p_dropout))) return rc;
-    const st_style_encoder_config& c = e->sty->cfg;
+    const st_style_encoder_config& c = state_of<StyleState>(e)->cfg;
     const int I = c.n_mel_channels, Hd = c.style_hidden, O = c.style_vector_dim, K = c.style_kernel_size, NH = c.style_head;
     const int64_t R = (int64_t)B * T;
     if (R * 3 * Hd >= ((int64_t)1 << 31) || R * O >= ((int64_t)1 << 31) || R * I >= ((int64_t)1 << 31)) return e->fail(ST_ERR_INVALID, "B*T too large");
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    SdTrain* st = sd_train_begin(e);
+    SdTrain* st = state_of<StyleState>(e)->begin();
     const StyleActs A = style_acts(c, B, T);
     if ((rc = sd_train_grow(e, &st->act, &st->act_cap, A.end * 4))) return rc;
     float* act = (float*)st->act;
@@ -217,9 +211,10 @@ int st_style_encoder_train_forward(st_engine* e, const float* mel, const float* 
 int st_style_encoder_train_backward(st_engine* e, int64_t serial, int B, int T, const float* grad_c, float* grad_flat, void* stream) {
     int rc = check_handle(e, KIND_STYLE_ENCODER); if (rc) return rc;
     if (!grad_c || !grad_flat) return e->fail(ST_ERR_INVALID, "null tensor pointer");
-    if ((rc = sd_train_check(e, "st_style_encoder_train", "T", serial, B, T))) return rc;
-    SdTrain* st = e->sdt;
-    const st_style_encoder_config& c = e->sty->cfg;
+    StyleState* sty = state_of<StyleState>(e);
+    SdTrain* st = &sty->held;
+    if ((rc = sd_train_check(e, *st, "st_style_encoder_train", "T", serial, B, T))) return rc;
+    const st_style_encoder_config& c = sty->cfg;
     const int I = c.n_mel_channels, Hd = c.style_hidden, O = c.style_vector_dim, K = c.style_kernel_size, NH = c.style_head;
     const int64_t R = (int64_t)B * T;
     HIPCHK(e, hipSetDevice(e->device));

@@ -16,7 +16,7 @@
 //   * the per-item vectors (time MLP, FiLM and adaLN linears) are tiny fp32 kernels.
 // The training forward uses plain GEMM epilogues + element-wise kernels (nothing fused across ops) because every
 // intermediate is needed again; the fused inference path of engine.cpp is untouched.
-#include "engine_internal.h"
+#include "engine_dit.h"
 #include "train_launch.h"
 
 #include <algorithm>
@@ -135,13 +135,14 @@ inline ConvGemmArgs cargs(const st_engine* e, const Conv& cv, int n_items, int T
 // K = taps x (its output channels, padded to ld)
 int pack_T(st_engine* e, TrainState* ts, Conv& cv, const std::string& wname, int cout, int cin_total, int taps, int ci_off,
            int ci_cnt, int cin_p, int ld, hipStream_t s) {
+    DitState* dit = dit_of(e);
     cv.cout = cin_p; cv.cin = ld; cv.taps = taps; cv.split = false;
     const size_t bytes = (size_t)cin_p * taps * ld * 2;
     if (!cv.w) {        // the padding is zeroed once; a re-pack rewrites exactly the payload elements
         HIPCHK(e, hipMalloc(&cv.w, bytes)); ts->owned.push_back(cv.w);
         HIPCHK(e, hipMemsetAsync(cv.w, 0, bytes, s));
     }
-    int rc = pk_weight_t(e, e->pk_T, P(e, wname), cout, cin_total, taps, ci_off, ci_cnt, cv.w, cin_p, ld, 0, s);
+    int rc = pk_weight_t(e, dit->pk_T, P(e, wname), cout, cin_total, taps, ci_off, ci_cnt, cv.w, cin_p, ld, 0, s);
     if (rc) return rc;
     cv.bias = nullptr;
     return ST_OK;
@@ -159,20 +160,20 @@ int64_t train_grad_layout(const st_engine* e, std::map<std::string, int64_t>* of
     return off;
 }
 
-void train_invalidate(st_engine* e) {
-    if (e->train) { e->train->packed = false; e->train->have_fwd = false; }
+void train_invalidate(DitState* dit) {
+    if (dit->train) { dit->train->packed = false; dit->train->have_fwd = false; }
 }
 
 // (re)packs the transposed weights after a parameter update; lazy: inference-only users never pay for it
 int train_prepare(st_engine* e, hipStream_t s) {
-    if (e->kind != KIND_DECODER && e->kind != KIND_TEXT_ENCODER) return ST_OK;
-    if (!e->train) {
-        e->train = new TrainState();
-        if (const char* v = getenv("ST_FUSE_SILU")) e->train->fuse_silu = atoi(v) != 0;
-        if (const char* v = getenv("ST_FUSE_TRAIN_LN")) e->train->fuse_ln = atoi(v) != 0;
-        if (const char* v = getenv("ST_TRAIN_VLO")) { e->train->v_lo = atoi(v) != 0; e->train->h_lo = atoi(v) == 2; }
-        if (const char* v = getenv("ST_TRAIN_SIDE")) { e->train->use_side = atoi(v) != 0; e->train->side_prio = atoi(v) == 2; }
-        TrainState* t0 = e->train;
+    DitState* dit = dit_of(e);
+    if (!dit->train) {
+        dit->train = new TrainState();
+        if (const char* v = getenv("ST_FUSE_SILU")) dit->train->fuse_silu = atoi(v) != 0;
+        if (const char* v = getenv("ST_FUSE_TRAIN_LN")) dit->train->fuse_ln = atoi(v) != 0;
+        if (const char* v = getenv("ST_TRAIN_VLO")) { dit->train->v_lo = atoi(v) != 0; dit->train->h_lo = atoi(v) == 2; }
+        if (const char* v = getenv("ST_TRAIN_SIDE")) { dit->train->use_side = atoi(v) != 0; dit->train->side_prio = atoi(v) == 2; }
+        TrainState* t0 = dit->train;
         if (t0->use_side) {
             // ST_TRAIN_SIDE=2 (opt-in): the side streams at the device's LOWEST priority.  Alone in a process that is 0.7 % faster (18.64 ->
             // 18.51 ms per step, the main chain being the critical path) -- but inside bench.py, next to the inference engines' part streams,
@@ -183,17 +184,17 @@ int train_prepare(st_engine* e, hipStream_t s) {
             HIPCHK(e, t0->side2.ensure(1, 1, 0, prio ? &least : nullptr));
         }
     }
-    TrainState* ts = e->train;
+    TrainState* ts = dit->train;
     if (ts->packed) return ST_OK;
     ts->have_fwd = false;
-    const int C = e->C, F = e->F, M = e->M, Mp = e->Mp, K = e->K, L = e->L;
+    const int C = dit->C, F = dit->F, M = dit->M, Mp = dit->Mp, K = dit->K, L = dit->L;
     int rc;
-    if (ts->grad_flat && pk_replay(e, e->pk_T, s, &rc)) {      // the usual case after an optimizer step: one launch
+    if (ts->grad_flat && pk_replay(e, dit->pk_T, s, &rc)) {      // the usual case after an optimizer step: one launch
         if (rc) return rc;
         ts->packed = true;
         return ST_OK;
     }
-    pk_begin(e->pk_T);
+    pk_begin(dit->pk_T);
     if (e->kind == KIND_TEXT_ENCODER) {      // text encoder: proj is the only convolution outside the blocks
         if ((rc = pack_T(e, ts, ts->finT, "proj.weight", M, C, 1, 0, C, C, Mp, s))) return rc;
     } else {
@@ -208,20 +209,20 @@ int train_prepare(st_engine* e, hipStream_t s) {
     ts->ffn1T.resize(L); ts->ffn2T.resize(L); ts->oprojT.resize(L); ts->qkvT.resize(L);
     ts->lscTa.resize(n_lsc); ts->lscTb.resize(n_lsc);
     for (int i = 0; i < L; ++i) {
-        const std::string b = e->blk(i);
+        const std::string b = dit->blk(i);
         if ((rc = pack_T(e, ts, ts->ffn1T[i], b + "mlp.conv_1.weight", F, C, K, 0, C, C, F, s))) return rc;
         if ((rc = pack_T(e, ts, ts->ffn2T[i], b + "mlp.conv_2.weight", C, F, K, 0, F, F, C, s))) return rc;
         if ((rc = pack_T(e, ts, ts->oprojT[i], b + "attn.conv_o.weight", C, C, 1, 0, C, C, C, s))) return rc;
         if (ts->h_lo) {      // forward q/k/v weights over K = [h_hi | h_lo]
             if ((int)ts->qkv2.size() != L) ts->qkv2.assign(L, Conv());
             Conv& q2 = ts->qkv2[i];
-            q2.cout = 3 * C; q2.cin = 2 * C; q2.taps = 1; q2.bias = e->qkv[i].bias;
+            q2.cout = 3 * C; q2.cin = 2 * C; q2.taps = 1; q2.bias = dit->qkv[i].bias;
             if (!q2.w) { HIPCHK(e, hipMalloc(&q2.w, (size_t)3 * C * 2 * C * 2)); ts->owned.push_back(q2.w); HIPCHK(e, hipMemsetAsync(q2.w, 0, (size_t)3 * C * 2 * C * 2, s)); }
             int r2 = 0;
             for (const char* nm : {"q", "k", "v"}) {
                 const float* w = P(e, b + "attn.conv_" + nm + ".weight");
-                if ((rc = pk_weight(e, e->pk_T, w, C, C, 1, 0, C, q2.w, r2 * C, 2 * C, 0, r2 == 2 ? C : 2 * C, 0, s))) return rc;
-                if (r2 == 2 && (rc = pk_weight(e, e->pk_T, w, C, C, 1, 0, C, q2.w, r2 * C, 2 * C, C, C, 0, s))) return rc;
+                if ((rc = pk_weight(e, dit->pk_T, w, C, C, 1, 0, C, q2.w, r2 * C, 2 * C, 0, r2 == 2 ? C : 2 * C, 0, s))) return rc;
+                if (r2 == 2 && (rc = pk_weight(e, dit->pk_T, w, C, C, 1, 0, C, q2.w, r2 * C, 2 * C, C, C, 0, s))) return rc;
                 ++r2;
             }
         }
@@ -231,7 +232,7 @@ int train_prepare(st_engine* e, hipStream_t s) {
         if (!q.w) { HIPCHK(e, hipMalloc(&q.w, (size_t)C * 3 * C * 2)); ts->owned.push_back(q.w); }
         int r = 0;
         for (const char* nm : {"q", "k", "v"}) {
-            if ((rc = pk_weight_t(e, e->pk_T, P(e, b + "attn.conv_" + nm + ".weight"), C, C, 1, 0, C, q.w, C, 3 * C, r * C, s))) return rc;
+            if ((rc = pk_weight_t(e, dit->pk_T, P(e, b + "attn.conv_" + nm + ".weight"), C, C, 1, 0, C, q.w, C, 3 * C, r * C, s))) return rc;
             ++r;
         }
     }
@@ -247,37 +248,40 @@ int train_prepare(st_engine* e, hipStream_t s) {
         ts->grad_numel = total;
         ts->gbase = ts->grad_flat;
     }
-    if ((rc = pk_end(e, e->pk_T, s))) return rc;
+    if ((rc = pk_end(e, dit->pk_T, s))) return rc;
     ts->packed = true;
     return ST_OK;
 }
 
-int64_t train_bytes(const st_engine* e) {      // transposed weights + gradient buffers + activation / scratch arena
-    if (!e->train) return 0;
-    int64_t n = (int64_t)e->train->ws_cap;
-    n += e->train->grad_numel * 4;
+int64_t train_bytes(const DitState* dit) {      // transposed weights + gradient buffers + activation / scratch arena
+    if (!dit->train) return 0;
+    int64_t n = (int64_t)dit->train->ws_cap;
+    n += dit->train->grad_numel * 4;
     auto add = [&](const Conv& c) { if (c.w) n += (int64_t)c.cout * c.taps * c.cin * 2; };
-    add(e->train->finT); add(e->train->inxT); add(e->train->incT);
-    for (auto& c : e->train->preT) add(c);
-    for (auto* v : {&e->train->ffn1T, &e->train->ffn2T, &e->train->oprojT, &e->train->qkvT, &e->train->lscTa, &e->train->lscTb})
+    add(dit->train->finT); add(dit->train->inxT); add(dit->train->incT);
+    for (auto& c : dit->train->preT) add(c);
+    for (auto* v : {&dit->train->ffn1T, &dit->train->ffn2T, &dit->train->oprojT, &dit->train->qkvT, &dit->train->lscTa, &dit->train->lscTb})
         for (auto& c : *v) add(c);
     return n;
 }
 
-void train_destroy(st_engine* e) {
-    if (!e->train) return;
-    for (void* p : e->train->owned) hipFree(p);
-    e->train->side.destroy();
-    e->train->side2.destroy();
-    if (e->train->ws) hipFree(e->train->ws);
-    delete e->train;
-    e->train = nullptr;
+int64_t DitState::train_serial() const { return train && train->have_fwd ? train->serial : 0; }
+
+void train_destroy(DitState* dit) {
+    if (!dit->train) return;
+    for (void* p : dit->train->owned) hipFree(p);
+    dit->train->side.destroy();
+    dit->train->side2.destroy();
+    if (dit->train->ws) hipFree(dit->train->ws);
+    delete dit->train;
+    dit->train = nullptr;
 }
 
 namespace {
 
 int layout_train(st_engine* e, TrainState* ts, int B, int T) {
-    const int C = e->C, F = e->F, Mp = e->Mp, L = e->L, H = e->H, G = e->G;
+    DitState* dit = dit_of(e);
+    const int C = dit->C, F = dit->F, Mp = dit->Mp, L = dit->L, H = dit->H, G = dit->G;
     const int Tp = (T + 63) / 64 * 64;
     const size_t N = B, TT = T, R = N * TT;
     size_t off = 0;
@@ -300,7 +304,7 @@ int layout_train(st_engine* e, TrainState* ts, int B, int T) {
     want_dec((void**)&ts->cpart, R * C * 4); want((void**)&ts->h0, R * C * 4); want((void**)&ts->v32, R * Mp * 4);
     if (!dec) {
         want((void**)&ts->ids, R * 4);
-        want(&ts->emb_ws, emb_bwd_scratch_bytes((int64_t)R, e->n_vocab, C));
+        want(&ts->emb_ws, emb_bwd_scratch_bytes((int64_t)R, dit->n_vocab, C));
         want((void**)&ts->unit_sc, 16);
     }
     for (int i = 0; i < L; ++i) {
@@ -338,7 +342,7 @@ int layout_train(st_engine* e, TrainState* ts, int B, int T) {
     // Mp columns are larger
     size_t max_frames = 0, max_cout = 0, max_prod = 0;
     {
-        const size_t K = e->K;
+        const size_t K = dit->K;
         const size_t shapes[][2] = {{(size_t)C, (size_t)Mp},              // final_proj
                                     {K * F, (size_t)C}, {K * C, (size_t)F},  // ffn conv_2, conv_1
                                     {(size_t)C, (size_t)C}, {(size_t)C, (size_t)3 * C},  // out-proj, q / k / v
@@ -390,7 +394,8 @@ inline const float* xpre_of(const TrainState* ts, int i, int L) {
 }
 
 void capture_train(st_engine* e, TrainState* ts, hipStream_t s) {
-    const int C = e->C, F = e->F, L = e->L, H = e->H, N = ts->B, T = ts->T, Tp = ts->Tp;
+    DitState* dit = dit_of(e);
+    const int C = dit->C, F = dit->F, L = dit->L, H = dit->H, N = ts->B, T = ts->T, Tp = ts->Tp;
     const int64_t R = (int64_t)N * T;
     if (e->capture) {
         for (int i = 0; i < L; ++i) {
@@ -410,6 +415,7 @@ void capture_train(st_engine* e, TrainState* ts, hipStream_t s) {
 // (bit-identical), else the stand-alone kernel.  mask: (mask_B, T), or nullptr for a site without mask and dropout (the cond prenet:
 // dc = no dropout, and the epilogue's dropout fields stay zero).
 int conv_silu(st_engine* e, TrainState* ts, ConvGemmArgs a, void* pre16, void* act16, const float* mask, int mask_B, const DropCfg& dc, hipStream_t s) {
+    DitState* dit = dit_of(e);
     a.out16 = pre16;
     if (ts->fuse_silu && gemm_is_phased(e, 3, a)) {
         a.act16 = act16;
@@ -417,7 +423,7 @@ int conv_silu(st_engine* e, TrainState* ts, ConvGemmArgs a, void* pre16, void* a
         HIPCHK(e, gemm(e, 3, EPI_SILU, a, s));
     } else {
         HIPCHK(e, gemm(e, 3, EPI_F32, a, s));
-        HIPCHK(e, launch_silu_drop(e->dt, pre16, act16, mask, mask_B, ts->T, e->F, (int64_t)ts->B * ts->T, dc, s));
+        HIPCHK(e, launch_silu_drop(e->dt, pre16, act16, mask, mask_B, ts->T, dit->F, (int64_t)ts->B * ts->T, dc, s));
     }
     return ST_OK;
 }
@@ -425,7 +431,8 @@ int conv_silu(st_engine* e, TrainState* ts, ConvGemmArgs a, void* pre16, void* a
 // The L DiT blocks of a training forward (diffusion_transformer.py:98-117), activations kept: the decoder's with FiLM on the
 // block input and the long-skip merges (estimator.py:126-132), the text encoder's without either (text_encoder.py:40-41).
 int fwd_blocks(st_engine* e, TrainState* ts, const float* m, float p_dropout, unsigned long long seed, hipStream_t s) {
-    const int C = e->C, F = e->F, L = e->L, H = e->H, N = ts->B, B = ts->B, T = ts->T, Tp = ts->Tp;
+    DitState* dit = dit_of(e);
+    const int C = dit->C, F = dit->F, L = dit->L, H = dit->H, N = ts->B, B = ts->B, T = ts->T, Tp = ts->Tp;
     const int64_t R = (int64_t)N * T;
     for (int i = 0; i < L; ++i) {
         LayerAct& A = ts->L[i];
@@ -433,7 +440,7 @@ int fwd_blocks(st_engine* e, TrainState* ts, const float* m, float p_dropout, un
         if (e->kind == KIND_DECODER && i >= L / 2) {   // long-skip merge (estimator.py:131-132)
             const int j = i - L / 2;
             const int src = L - 1 - i;      // 2, 1, 0 -> x3[1], x3[0], h0
-            ConvGemmArgs a = cargs(e, e->lsc[j], N, T, B);
+            ConvGemmArgs a = cargs(e, dit->lsc[j], N, T, B);
             a.a0 = ts->L[i - 1].x3_16; a.c0 = C; a.a1 = src == 0 ? ts->h0_16 : ts->L[src - 1].x3_16; a.c1 = C; a.out32 = A.lscout;
             HIPCHK(e, gemm(e, 3, EPI_F32, a, s));
         }
@@ -447,11 +454,11 @@ int fwd_blocks(st_engine* e, TrainState* ts, const float* m, float p_dropout, un
             HIPCHK(e, launch_train_ln(e->dt, a, s));
         }
         {
-            ConvGemmArgs a = cargs(e, ts->h_lo ? ts->qkv2[i] : e->qkv[i], N, T, B);
-            a.a0 = A.h1; a.c0 = C; a.q = A.q; a.k = A.k; a.vt = A.vt; a.vt_lo = A.vt_lo; a.rope_cos = e->rope_cos; a.rope_sin = e->rope_sin;
+            ConvGemmArgs a = cargs(e, ts->h_lo ? ts->qkv2[i] : dit->qkv[i], N, T, B);
+            a.a0 = A.h1; a.c0 = C; a.q = A.q; a.k = A.k; a.vt = A.vt; a.vt_lo = A.vt_lo; a.rope_cos = dit->rope_cos; a.rope_sin = dit->rope_sin;
             if (ts->h_lo) { a.a1 = A.h1lo; a.c1 = C; a.flags |= GF_K2_V_ONLY; }      // K = [h_hi | h_lo] against [W 0] (q, k rows: bit-identical) / [W_v W_v] (v rows)
             a.Tp = Tp; a.n_heads = H; a.qscale = 1.4426950408889634f / sqrtf((float)(C / H));
-            if ((int)e->qkv_frag.size() == e->L) a.w_frag = e->qkv_frag[i];      // weight-stationary kernel on big batches (bit-identical; re-packed with the other forward weights)
+            if ((int)dit->qkv_frag.size() == dit->L) a.w_frag = dit->qkv_frag[i];      // weight-stationary kernel on big batches (bit-identical; re-packed with the other forward weights)
             HIPCHK(e, gemm(e, 1, EPI_QKV, a, s));
         }
         {
@@ -464,7 +471,7 @@ int fwd_blocks(st_engine* e, TrainState* ts, const float* m, float p_dropout, un
         }
         if (ts->fuse_ln) {   // o = (Wo attn + b) * mask ; x2 = x1 + g_msa * o ; LN2 + modulate, masked -> h2: one GEMM with the
             // inference epilogue (EPI_RESGATE + fused LayerNorm) that also stores the branch output o the gate's gradient needs
-            ConvGemmArgs a = cargs(e, e->oproj[i], N, T, B);
+            ConvGemmArgs a = cargs(e, dit->oproj[i], N, T, B);
             a.a0 = A.attn16; a.c0 = C; a.mask = m; a.gate = ada_i + 2 * C; a.gate_stride = 6 * C;
             a.res32 = A.x1; a.out32 = A.x2; a.branch32 = A.o32;
             a.ln_h16 = A.h2; a.ln_film = nullptr; a.ln_film_mod = 1;
@@ -472,7 +479,7 @@ int fwd_blocks(st_engine* e, TrainState* ts, const float* m, float p_dropout, un
             HIPCHK(e, gemm(e, 1, EPI_RESGATE, a, s));
         } else {
             {   // o = (Wo attn + b) * mask
-                ConvGemmArgs a = cargs(e, e->oproj[i], N, T, B);
+                ConvGemmArgs a = cargs(e, dit->oproj[i], N, T, B);
                 a.a0 = A.attn16; a.c0 = C; a.mask = m; a.flags = GF_MASK; a.out32 = A.o32;
                 HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
             }
@@ -486,9 +493,9 @@ int fwd_blocks(st_engine* e, TrainState* ts, const float* m, float p_dropout, un
             }
         }
         {   // FFN (diffusion_transformer.py:25-30)
-            ConvGemmArgs a = cargs(e, e->ffn1[i], N, T, B); a.a0 = A.h2; a.c0 = C;
+            ConvGemmArgs a = cargs(e, dit->ffn1[i], N, T, B); a.a0 = A.h2; a.c0 = C;
             if (int rc = conv_silu(e, ts, a, A.a16, A.u16, m, B, make_drop(p_dropout, seed, 2 * i), s)) return rc;
-            a = cargs(e, e->ffn2[i], N, T, B); a.a0 = A.u16; a.c0 = F; a.mask = m;
+            a = cargs(e, dit->ffn2[i], N, T, B); a.a0 = A.u16; a.c0 = F; a.mask = m;
             if (ts->fuse_ln) {      // f = (W2 u + b) * mask ; x3 = x2 + g_mlp * f (+ its 16-bit copies) in the GEMM's epilogue
                 a.gate = ada_i + 5 * C; a.gate_stride = 6 * C; a.res32 = A.x2; a.out32 = A.x3; a.branch32 = A.f32b;
                 a.out16 = A.x3_16; a.out16_lo = i + 1 == L ? ts->x3lo : nullptr;
@@ -512,8 +519,9 @@ int fwd_blocks(st_engine* e, TrainState* ts, const float* m, float p_dropout, un
 // ---- the frame both training forwards put around their own input staging and fwd_blocks
 // begin: dgrad weights, the arena for (B, T), the RoPE table; nothing is held until fwd_commit
 int fwd_begin(st_engine* e, int B, int T, float p_dropout, unsigned long long seed, hipStream_t s) {
+    DitState* dit = dit_of(e);
     int rc = train_prepare(e, s); if (rc) return rc;
-    TrainState* ts = e->train;
+    TrainState* ts = dit->train;
     ts->have_fwd = false;
     if ((rc = layout_train(e, ts, B, T))) return rc;
     if ((rc = ensure_rope(e, T, s))) return rc;
@@ -524,7 +532,8 @@ int fwd_begin(st_engine* e, int B, int T, float p_dropout, unsigned long long se
 // adaLN modulation of every block from c (diffusion_transformer.py:92-96: [Linear(gin, hidden) if gin != hidden else Identity,
 // SiLU, Linear(hidden, 6 hidden)]) and, for the decoder, FiLM (gamma, beta) from tau: per-item vectors, one launch per family and 8 blocks
 int fwd_modulation(st_engine* e, TrainState* ts, hipStream_t s) {
-    const int C = e->C, L = e->L, N = ts->B;
+    DitState* dit = dit_of(e);
+    const int C = dit->C, L = dit->L, N = ts->B;
     const bool dec = e->kind == KIND_DECODER;
     for (int i0 = 0; i0 < L; i0 += 8) {
         LinearJobs jf; memset(&jf, 0, sizeof(jf));
@@ -534,12 +543,12 @@ int fwd_modulation(st_engine* e, TrainState* ts, hipStream_t s) {
                 const std::string pf = "blocks." + std::to_string(i) + ".time_fusion.film.";
                 jf.in[jf.n] = ts->tau; jf.W[jf.n] = P(e, pf + "weight"); jf.bias[jf.n] = P(e, pf + "bias"); jf.out[jf.n] = ts->film + (size_t)i * N * 2 * C; jf.n += 1;
             }
-            const std::string pa = e->blk(i) + "adaLN_modulation.2.";
+            const std::string pa = dit->blk(i) + "adaLN_modulation.2.";
             const float* ain = ts->cvec;
-            if (e->G != C) {
-                const std::string p0 = e->blk(i) + "adaLN_modulation.0.";
+            if (dit->G != C) {
+                const std::string p0 = dit->blk(i) + "adaLN_modulation.0.";
                 float* pre = ts->ada_pre + (size_t)i * N * C;
-                HIPCHK(e, launch_linear(ts->cvec, N, e->G, P(e, p0 + "weight"), P(e, p0 + "bias"), C, pre, 0, 0, s));
+                HIPCHK(e, launch_linear(ts->cvec, N, dit->G, P(e, p0 + "weight"), P(e, p0 + "bias"), C, pre, 0, 0, s));
                 ain = pre;
             }
             ja.in[ja.n] = ain; ja.W[ja.n] = P(e, pa + "weight"); ja.bias[ja.n] = P(e, pa + "bias"); ja.out[ja.n] = ts->ada + (size_t)i * N * 6 * C; ja.n += 1;
@@ -553,19 +562,21 @@ int fwd_modulation(st_engine* e, TrainState* ts, hipStream_t s) {
 // the dropout hash tables of all L attention sites, once: forward and backward read them.  Salts: attention site 2i + 1, FFN site 2i
 // (DropSeeds holds 16: st_create* admits no more blocks)
 int fwd_drop_tables(st_engine* e, TrainState* ts, hipStream_t s) {
-    const int L = e->L;
+    DitState* dit = dit_of(e);
+    const int L = dit->L;
     if (!make_drop(ts->p_drop, ts->seed, 1).thresh16) return ST_OK;
     DropSeeds sd; memset(&sd, 0, sizeof(sd));
     for (int i = 0; i < L; ++i) sd.seed[i] = make_drop(ts->p_drop, ts->seed, 2 * i + 1).seed;
-    HIPCHK(e, launch_drop_tables_multi(sd, L, ts->B * e->H * ts->T + 64, ts->Tp / 2, ts->drop_rowh_all, ts->drop_colh_all, ts->drop_row_stride, ts->drop_col_stride, s));
+    HIPCHK(e, launch_drop_tables_multi(sd, L, ts->B * dit->H * ts->T + 64, ts->Tp / 2, ts->drop_rowh_all, ts->drop_colh_all, ts->drop_row_stride, ts->drop_col_stride, s));
     return ST_OK;
 }
 
 // v32 = (W x3 + b) * mask on the split-precision pair of the last block's output: final_proj (estimator.py:136-138) / proj (text_encoder.py:42)
 int fwd_out_proj(st_engine* e, TrainState* ts, hipStream_t s) {
-    const int C = e->C;
-    ConvGemmArgs a = cargs(e, e->fin, ts->B, ts->T, ts->B);
-    a.a0 = ts->L[e->L - 1].x3_16; a.c0 = C; a.a1 = ts->x3lo; a.c1 = C; a.c2 = C; a.mask = ts->maskbuf; a.flags = GF_MASK; a.out32 = ts->v32;
+    DitState* dit = dit_of(e);
+    const int C = dit->C;
+    ConvGemmArgs a = cargs(e, dit->fin, ts->B, ts->T, ts->B);
+    a.a0 = ts->L[dit->L - 1].x3_16; a.c0 = C; a.a1 = ts->x3lo; a.c1 = C; a.c2 = C; a.mask = ts->maskbuf; a.flags = GF_MASK; a.out32 = ts->v32;
     HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
     return ST_OK;
 }
@@ -588,22 +599,22 @@ extern "C" {
 
 int st_train_forward(st_engine* e, const float* t, const float* x, const float* mu, const float* mask, const float* c,
                      float* out, int B, int T, float p_dropout, uint64_t seed, void* stream) {
-    int rc = check_ready(e, B, T); if (rc) return rc;
-    if ((rc = check_handle(e, KIND_DECODER))) return rc;
+    int rc = check_ready(e, KIND_DECODER, B, T); if (rc) return rc;
+    DitState* dit = dit_of(e);
     if (!t || !x || !mu || !mask || !c || !out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if ((rc = check_dropout(e, p_dropout))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
     if ((rc = fwd_begin(e, B, T, p_dropout, seed, s))) return rc;
-    TrainState* ts = e->train;
+    TrainState* ts = dit->train;
     ProfScope prof(e, s, PC_TRAIN_FWD, 0);
-    const int C = e->C, F = e->F, Mp = e->Mp, N = B, Tp = ts->Tp;
+    const int C = dit->C, F = dit->F, Mp = dit->Mp, N = B, Tp = ts->Tp;
     HIPCHK(e, launch_mask_prep(mask, B, T, Tp, ts->n_full, ts->kv_end, ts->kbias, nullptr, s));
     HIPCHK(e, launch_cvec_prep(mask, nullptr, B, T, ts->maskbuf, s));
     const float* m = ts->maskbuf;
-    HIPCHK(e, launch_to_time_major(e->dt, mu, B, e->M, T, Mp, nullptr, ts->mu16, nullptr, s));
-    HIPCHK(e, launch_to_time_major(e->dt, x, B, e->M, T, Mp, nullptr, ts->x16, ts->x16lo, s));
-    HIPCHK(e, launch_cvec_prep(c, nullptr, B, e->G, ts->cvec, s));
+    HIPCHK(e, launch_to_time_major(e->dt, mu, B, dit->M, T, Mp, nullptr, ts->mu16, nullptr, s));
+    HIPCHK(e, launch_to_time_major(e->dt, x, B, dit->M, T, Mp, nullptr, ts->x16, ts->x16lo, s));
+    HIPCHK(e, launch_cvec_prep(c, nullptr, B, dit->G, ts->cvec, s));
     HIPCHK(e, hipMemcpyAsync(ts->tvals, t, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     // per-item vectors: time embedding -> MLP (pre-activation kept) -> FiLM; adaLN
     HIPCHK(e, launch_time_embed(ts->tvals, B, C, ts->emb, s));
@@ -613,61 +624,56 @@ int st_train_forward(st_engine* e, const float* t, const float* x, const float* 
     if ((rc = fwd_drop_tables(e, ts, s))) return rc;
     {   // cond prenet (estimator.py:83-89,118): conv -> SiLU twice, pre-activations kept for SiLU'
         const DropCfg nodrop = make_drop(0.f, 0, 0);
-        ConvGemmArgs a = cargs(e, e->pre[0], N, T, B); a.a0 = ts->mu16; a.c0 = Mp;
+        ConvGemmArgs a = cargs(e, dit->pre[0], N, T, B); a.a0 = ts->mu16; a.c0 = Mp;
         if ((rc = conv_silu(e, ts, a, ts->a1, ts->p1, nullptr, 1, nodrop, s))) return rc;
-        a = cargs(e, e->pre[1], N, T, B); a.a0 = ts->p1; a.c0 = F;
+        a = cargs(e, dit->pre[1], N, T, B); a.a0 = ts->p1; a.c0 = F;
         if ((rc = conv_silu(e, ts, a, ts->a2, ts->p2, nullptr, 1, nodrop, s))) return rc;
-        a = cargs(e, e->pre[2], N, T, B); a.a0 = ts->p2; a.c0 = F; a.out16 = ts->cond16; a.out16_lo = ts->cond16lo;
+        a = cargs(e, dit->pre[2], N, T, B); a.a0 = ts->p2; a.c0 = F; a.out16 = ts->cond16; a.out16_lo = ts->cond16lo;
         HIPCHK(e, gemm(e, 3, EPI_F32, a, s));
-        a = cargs(e, e->inc, N, T, B); a.a0 = ts->cond16; a.c0 = C; a.a1 = ts->cond16lo; a.c1 = C; a.c2 = C; a.out32 = ts->cpart;
+        a = cargs(e, dit->inc, N, T, B); a.a0 = ts->cond16; a.c0 = C; a.a1 = ts->cond16lo; a.c1 = C; a.c2 = C; a.out32 = ts->cpart;
         HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
     }
     {   // in_proj (estimator.py:120-121): output kept in fp32 (FiLM input / long skip) and 16 bit (long-skip operand)
-        ConvGemmArgs a = cargs(e, e->inx, N, T, B);
+        ConvGemmArgs a = cargs(e, dit->inx, N, T, B);
         a.a0 = ts->x16; a.c0 = Mp; a.a1 = ts->x16lo; a.c1 = Mp; a.c2 = Mp; a.bias = nullptr;
         a.add32 = ts->cpart; a.add_clamp = N; a.out32 = ts->h0; a.out16 = ts->h0_16;
         HIPCHK(e, gemm(e, 1, EPI_F32, a, s));
     }
     if ((rc = fwd_blocks(e, ts, m, p_dropout, seed, s))) return rc;
     if ((rc = fwd_out_proj(e, ts, s))) return rc;
-    HIPCHK(e, launch_from_time_major(ts->v32, B, e->M, T, Mp, out, s));
+    HIPCHK(e, launch_from_time_major(ts->v32, B, dit->M, T, Mp, out, s));
     fwd_commit(e, ts, s);
     return ST_OK;
 }
 
-int64_t st_train_serial(const st_engine* e) {
-    if (!e) return 0;
-    // style encoder, duration predictor, vocoder (st_vocos_train_forward), period discriminator: the SdTrain protocol
-    if (e->kind != KIND_DECODER && e->kind != KIND_TEXT_ENCODER) return e->sdt && e->sdt->have ? e->sdt->serial : 0;
-    return e->train && e->train->have_fwd ? e->train->serial : 0;
-}
+int64_t st_train_serial(const st_engine* e) { return e ? e->state->train_serial() : 0; }
 
 // TextEncoder.forward (models/text_encoder.py:34-44) keeping the activations for st_text_encoder_train_backward: the embedding,
 // the L blocks of fwd_blocks without FiLM or long skips, proj on the split-precision operand pair (as the inference path).
 int st_text_encoder_train_forward(st_engine* e, const int64_t* tokens, const int64_t* lengths, const float* c, float* x_out,
                                   float* mu_out, float* mask_out, int B, int T, float p_dropout, uint64_t seed, void* stream) {
-    int rc = check_ready(e, B, T); if (rc) return rc;
-    if ((rc = check_handle(e, KIND_TEXT_ENCODER))) return rc;
+    int rc = check_ready(e, KIND_TEXT_ENCODER, B, T); if (rc) return rc;
+    DitState* dit = dit_of(e);
     if (!tokens || !lengths || !c || !x_out || !mu_out || !mask_out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if ((rc = check_dropout(e, p_dropout))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
     if ((rc = fwd_begin(e, B, T, p_dropout, seed, s))) return rc;
-    TrainState* ts = e->train;
+    TrainState* ts = dit->train;
     ProfScope prof(e, s, PC_TRAIN_FWD, 0);
-    const int C = e->C, L = e->L;
+    const int C = dit->C, L = dit->L;
     // x = emb[token] * sqrt(C) * mask (time-major fp32: block 0's input), the (B,1,T) mask, the ids the embedding backward sums by
-    HIPCHK(e, launch_embed_tokens((const long long*)tokens, (const long long*)lengths, P(e, "emb.weight"), e->n_vocab, C,
+    HIPCHK(e, launch_embed_tokens((const long long*)tokens, (const long long*)lengths, P(e, "emb.weight"), dit->n_vocab, C,
                                   sqrtf((float)C), B, T, ts->h0, ts->maskbuf, s));
-    HIPCHK(e, launch_emb_ids((const long long*)tokens, (const long long*)lengths, e->n_vocab, B, T, ts->ids, s));
+    HIPCHK(e, launch_emb_ids((const long long*)tokens, (const long long*)lengths, dit->n_vocab, B, T, ts->ids, s));
     HIPCHK(e, launch_mask_prep(ts->maskbuf, B, T, ts->Tp, ts->n_full, ts->kv_end, ts->kbias, nullptr, s));
-    HIPCHK(e, launch_cvec_prep(c, nullptr, B, e->G, ts->cvec, s));
+    HIPCHK(e, launch_cvec_prep(c, nullptr, B, dit->G, ts->cvec, s));
     if ((rc = fwd_modulation(e, ts, s))) return rc;
     if ((rc = fwd_drop_tables(e, ts, s))) return rc;
     if ((rc = fwd_blocks(e, ts, ts->maskbuf, p_dropout, seed, s))) return rc;
     if ((rc = fwd_out_proj(e, ts, s))) return rc;
     HIPCHK(e, launch_from_time_major(ts->L[L - 1].x3, B, C, T, C, x_out, s));
-    HIPCHK(e, launch_from_time_major(ts->v32, B, e->M, T, e->Mp, mu_out, s));
+    HIPCHK(e, launch_from_time_major(ts->v32, B, dit->M, T, dit->Mp, mu_out, s));
     HIPCHK(e, hipMemcpyAsync(mask_out, ts->maskbuf, (size_t)B * T * 4, hipMemcpyDeviceToDevice, s));
     fwd_commit(e, ts, s);
     return ST_OK;
@@ -770,7 +776,8 @@ namespace {
 
 struct BwdDims { int C, F, M, Mp, L, H, K, N, B, T, Tp; int64_t R; int chunks; };
 BwdDims bwd_dims(const st_engine* e, const TrainState* ts) {
-    BwdDims d{e->C, e->F, e->M, e->Mp, e->L, e->H, e->K, ts->B, ts->B, ts->T, ts->Tp, (int64_t)ts->B * ts->T, red_chunks(ts->T)};
+    const DitState* dit = dit_of(e);
+    BwdDims d{dit->C, dit->F, dit->M, dit->Mp, dit->L, dit->H, dit->K, ts->B, ts->B, ts->T, ts->Tp, (int64_t)ts->B * ts->T, red_chunks(ts->T)};
     return d;
 }
 
@@ -803,7 +810,8 @@ int bwd_begin(st_engine* e, TrainState* ts, hipStream_t s) {
 // dpre16 = dgrad(a) x SiLU'(pre16) [x the dropout of dc, * mask]: straight from the dgrad's epilogue where the phased tile runs, else
 // through fp32 tmpF and the stand-alone kernel.  mask as conv_silu's.
 int dgrad_silu(st_engine* e, TrainState* ts, ConvGemmArgs a, const void* pre16, void* dpre16, const float* mask, int mask_B, const DropCfg& dc, hipStream_t s) {
-    const int K = e->K;
+    DitState* dit = dit_of(e);
+    const int K = dit->K;
     if (ts->fuse_silu && K == 3 && gemm_is_phased(e, 3, a) && !a.bias) {
         a.out16 = dpre16; a.dact16 = pre16;
         if (mask) { a.mask = mask; a.drop_seed = dc.seed; a.drop_thresh16 = dc.thresh16; a.drop_scale = dc.scale; }
@@ -811,7 +819,7 @@ int dgrad_silu(st_engine* e, TrainState* ts, ConvGemmArgs a, const void* pre16, 
     } else {
         a.out32 = ts->tmpF;
         HIPCHK(e, gemm(e, K, EPI_F32, a, s));
-        HIPCHK(e, launch_silu_bwd(e->dt, ts->tmpF, pre16, mask, mask_B, ts->T, e->F, (int64_t)ts->B * ts->T, dc, dpre16, s));
+        HIPCHK(e, launch_silu_bwd(e->dt, ts->tmpF, pre16, mask, mask_B, ts->T, dit->F, (int64_t)ts->B * ts->T, dc, dpre16, s));
     }
     return ST_OK;
 }
@@ -850,13 +858,15 @@ int bwd_head(st_engine* e, TrainState* ts, const float* grad_out, hipStream_t s)
 // The gradient-independent operand copies of block i's attention backward: V back to natural rows, centred, as a hi + lo pair;
 // the means of q and k; centred T-layout copies of q and k (attention_bwd.hip's header says why).
 int attn_prep(st_engine* e, TrainState* ts, int i, hipStream_t s) {
-    const int H = e->H, N = ts->B, T = ts->T, Tp = ts->Tp;
+    DitState* dit = dit_of(e);
+    const int H = dit->H, N = ts->B, T = ts->T, Tp = ts->Tp;
     LayerAct& A = ts->L[i];
     HIPCHK(e, launch_attn_prep(e->dt, A.q, A.k, A.vt, A.vt_lo, N, H, T, Tp, ts->qmean, ts->kmean, ts->vmean, ts->qT, ts->kT, ts->vnat, ts->vnat_lo, s));
     return ST_OK;
 }
 
 int bwd_block(st_engine* e, TrainState* ts, int i, hipStream_t s) {
+    DitState* dit = dit_of(e);
     const BwdDims d = bwd_dims(e, ts);
     const int C = d.C, F = d.F, L = d.L, H = d.H, K = d.K, N = d.N, B = d.B, T = d.T, Tp = d.Tp, chunks = d.chunks;
     const int64_t R = d.R;
@@ -870,7 +880,7 @@ int bwd_block(st_engine* e, TrainState* ts, int i, hipStream_t s) {
         HIPCHK(e, ts->side2.record_join());
     }
     LayerAct& A = ts->L[i];
-    const std::string b = e->blk(i);
+    const std::string b = dit->blk(i);
     const float* ada_i = ts->ada + (size_t)i * N * 6 * C;
     float* dada_i = ts->dada + (size_t)i * N * 6 * C;
     // The gradient's magnitude changes by orders of magnitude from block to block (FiLM's gamma multiplies the whole residual
@@ -939,7 +949,7 @@ int bwd_block(st_engine* e, TrainState* ts, int i, hipStream_t s) {
         float* qs = ts->qs + 16 * i;
         HIPCHK(e, launch_qkv_grad_scales(ts->dq, ts->dk, ts->dv, R * C, ts->gsc, qbits, qs, s, true));
         HIPCHK(e, ts->side.wait_site(TrainState::DY_QKVW, s));
-        HIPCHK(e, launch_qkv_grad_pack(e->dt, ts->dq, ts->dk, ts->dv, e->rope_cos, e->rope_sin, N, H, T, qs, ts->dy[TrainState::DY_QKVD], ts->dy[TrainState::DY_QKVW], s));
+        HIPCHK(e, launch_qkv_grad_pack(e->dt, ts->dq, ts->dk, ts->dv, dit->rope_cos, dit->rope_sin, N, H, T, qs, ts->dy[TrainState::DY_QKVD], ts->dy[TrainState::DY_QKVW], s));
     }
     if (cap) { capture(e, "g.dq_" + std::to_string(i), ts->dq, R * C, false, s); capture(e, "g.dk_" + std::to_string(i), ts->dk, R * C, false, s);
                capture(e, "g.dv_" + std::to_string(i), ts->dv, R * C, false, s); capture(e, "g.dattn_" + std::to_string(i), ts->dy[TrainState::DY_DATTN], R * C, true, s); }
@@ -990,15 +1000,16 @@ int bwd_block(st_engine* e, TrainState* ts, int i, hipStream_t s) {
 // Every weight / bias gradient here has ONE producer (written, not accumulated: no zero fills); d c and d tau add up over
 // the blocks: the first block of a backward (L - 1) writes them, the others accumulate.
 int bwd_block_linears(st_engine* e, TrainState* ts, int i, hipStream_t s) {
-    const int C = e->C, L = e->L, N = ts->B;
+    DitState* dit = dit_of(e);
+    const int C = dit->C, L = dit->L, N = ts->B;
     const int acc = i == L - 1 ? 0 : 1;
-    const std::string pa = e->blk(i) + "adaLN_modulation.2.", p0 = e->blk(i) + "adaLN_modulation.0.";
+    const std::string pa = dit->blk(i) + "adaLN_modulation.2.", p0 = dit->blk(i) + "adaLN_modulation.0.";
     const float* dout = ts->dada + (size_t)i * N * 6 * C;
     const float* pre = ts->ada_pre + (size_t)i * N * C;
     HIPCHK(e, launch_linear_bwd_w(pre, dout, N, C, 6 * C, 1, G(ts, pa + "weight"), G(ts, pa + "bias"), 0, s));
     HIPCHK(e, launch_linear_bwd_in(pre, dout, P(e, pa + "weight"), N, C, 6 * C, 1, ts->dada_pre, 0, s));
-    HIPCHK(e, launch_linear_bwd_w(ts->cvec, ts->dada_pre, N, e->G, C, 0, G(ts, p0 + "weight"), G(ts, p0 + "bias"), 0, s));
-    HIPCHK(e, launch_linear_bwd_in(ts->cvec, ts->dada_pre, P(e, p0 + "weight"), N, e->G, C, 0, ts->dcvec, acc, s));
+    HIPCHK(e, launch_linear_bwd_w(ts->cvec, ts->dada_pre, N, dit->G, C, 0, G(ts, p0 + "weight"), G(ts, p0 + "bias"), 0, s));
+    HIPCHK(e, launch_linear_bwd_in(ts->cvec, ts->dada_pre, P(e, p0 + "weight"), N, dit->G, C, 0, ts->dcvec, acc, s));
     if (e->kind != KIND_DECODER) return ST_OK;      // (the text encoder's blocks have no FiLM)
     const std::string pf = "blocks." + std::to_string(i) + ".time_fusion.film.";
     const float* dfo = ts->dfilm + (size_t)i * N * 2 * C;
@@ -1011,12 +1022,13 @@ int bwd_block_linears(st_engine* e, TrainState* ts, int i, hipStream_t s) {
 // are complete when its backward part ends.  `acc`: add to d c / d tau (the first part of a backward writes them).  gin == hidden only:
 // with adaLN_modulation.0 in front, bwd_block_linears runs per block.
 int bwd_linears(st_engine* e, TrainState* ts, int lo, int hi, int acc, hipStream_t s) {
-    const int C = e->C, N = ts->B;
+    DitState* dit = dit_of(e);
+    const int C = dit->C, N = ts->B;
     for (int i0 = lo; i0 < hi; i0 += 8) {
         LinBwdJobs ja; memset(&ja, 0, sizeof(ja));
         LinBwdJobs jf; memset(&jf, 0, sizeof(jf));
         for (int i = i0; i < std::min(hi, i0 + 8); ++i) {
-            const std::string pa = e->blk(i) + "adaLN_modulation.2.";
+            const std::string pa = dit->blk(i) + "adaLN_modulation.2.";
             ja.in[ja.n] = ts->cvec; ja.dout[ja.n] = ts->dada + (size_t)i * N * 6 * C; ja.W[ja.n] = P(e, pa + "weight");
             ja.dW[ja.n] = G(ts, pa + "weight"); ja.db[ja.n] = G(ts, pa + "bias"); ja.n += 1;
             if (e->kind != KIND_DECODER) continue;      // (the text encoder's blocks have no FiLM)
@@ -1036,7 +1048,8 @@ int bwd_linears(st_engine* e, TrainState* ts, int lo, int hi, int acc, hipStream
 
 // The blocks hi - 1 .. lo of a backward, last first, then their per-item linears; `acc` as bwd_linears'
 int bwd_blocks(st_engine* e, TrainState* ts, int lo, int hi, int acc, hipStream_t s) {
-    const bool per_block = e->G != e->C;
+    DitState* dit = dit_of(e);
+    const bool per_block = dit->G != dit->C;
     int rc;
     for (int i = hi - 1; i >= lo; --i) {
         if ((rc = bwd_block(e, ts, i, s))) return rc;
@@ -1046,6 +1059,7 @@ int bwd_blocks(st_engine* e, TrainState* ts, int lo, int hi, int acc, hipStream_
 }
 
 int bwd_tail(st_engine* e, TrainState* ts, float* grad_x, float* grad_mu, float* grad_c, hipStream_t s) {
+    DitState* dit = dit_of(e);
     const BwdDims d = bwd_dims(e, ts);
     const int C = d.C, F = d.F, M = d.M, Mp = d.Mp, K = d.K, N = d.N, B = d.B, T = d.T;
     const int64_t R = d.R;
@@ -1055,7 +1069,7 @@ int bwd_tail(st_engine* e, TrainState* ts, float* grad_x, float* grad_mu, float*
     HIPCHK(e, launch_linear_bwd_w(ts->th_pre, ts->dtau, N, F, C, 1, G(ts, "time_mlp.layer.2.weight"), G(ts, "time_mlp.layer.2.bias"), 0, s));
     HIPCHK(e, launch_linear_bwd_in(ts->th_pre, ts->dtau, P(e, "time_mlp.layer.2.weight"), N, F, C, 1, ts->dth, 0, s));
     HIPCHK(e, launch_linear_bwd_w(ts->emb, ts->dth, N, C, F, 0, G(ts, "time_mlp.layer.0.weight"), G(ts, "time_mlp.layer.0.bias"), 0, s));
-    if (grad_c) HIPCHK(e, hipMemcpyAsync(grad_c, ts->dcvec, (size_t)N * e->G * 4, hipMemcpyDeviceToDevice, s));
+    if (grad_c) HIPCHK(e, hipMemcpyAsync(grad_c, ts->dcvec, (size_t)N * dit->G * 4, hipMemcpyDeviceToDevice, s));
     // ---- in_proj: h0 = Wx x + Wc cond + b
     void* const t0 = ts->dy[TrainState::DY_T0]; void* const t1 = ts->dy[TrainState::DY_T1]; void* const t2 = ts->dy[TrainState::DY_T2]; void* const t3 = ts->dy[TrainState::DY_T3];
     HIPCHK(e, launch_cast16(e->dt, ts->dX, nullptr, 1, T, C, R, nullptr, t0, s));
@@ -1096,12 +1110,13 @@ int bwd_tail(st_engine* e, TrainState* ts, float* grad_x, float* grad_mu, float*
 }
 
 int bwd_check(st_engine* e, Kind kind, int64_t serial, int B_, int T_, const char* who) {
-    if (e->kind != kind || !e->train || !e->train->have_fwd)
+    const TrainState* tr = e->kind == kind ? dit_of(e)->train : nullptr;      // (kind: KIND_DECODER or KIND_TEXT_ENCODER)
+    if (!tr || !tr->have_fwd)
         return e->fail(ST_ERR_STATE, std::string(who) + (kind == KIND_DECODER ? " needs a preceding st_train_forward" : " needs a preceding st_text_encoder_train_forward") +
                        " (none held: never run, or invalidated by a parameter update)");
-    if (serial != e->train->serial || B_ != e->train->B || T_ != e->train->T)
-        return e->fail(ST_ERR_STATE, std::string(who) + ": the engine holds the activations of forward #" + std::to_string(e->train->serial) +
-                       " (B=" + std::to_string(e->train->B) + ", T=" + std::to_string(e->train->T) + "), not of #" + std::to_string(serial) +
+    if (serial != tr->serial || B_ != tr->B || T_ != tr->T)
+        return e->fail(ST_ERR_STATE, std::string(who) + ": the engine holds the activations of forward #" + std::to_string(tr->serial) +
+                       " (B=" + std::to_string(tr->B) + ", T=" + std::to_string(tr->T) + "), not of #" + std::to_string(serial) +
                        " (B=" + std::to_string(B_) + ", T=" + std::to_string(T_) + "): one backward per forward, before the next grad-enabled forward");
     return ST_OK;
 }
@@ -1131,24 +1146,26 @@ int bwd_head_text(st_engine* e, TrainState* ts, const float* grad_x, const float
 }
 
 int bwd_text(st_engine* e, TrainState* ts, const float* grad_x, const float* grad_mu, float* grad_c, hipStream_t s) {
+    DitState* dit = dit_of(e);
     ProfScope prof(e, s, PC_TRAIN_BWD, 0);
     ForkGuard guard{ts->side, s};
-    const int L = e->L, C = e->C;
+    const int L = dit->L, C = dit->C;
     int rc;
     if ((rc = bwd_head_text(e, ts, grad_x, grad_mu, s))) return rc;
     if ((rc = bwd_blocks(e, ts, 0, L, 0, s))) return rc;
     // x = emb[token] * sqrt(C): dX is d (block 0's input), masked by its entry, in units of the current scale pair
-    HIPCHK(e, launch_emb_bwd(ts->dX, C, ts->ids, (int64_t)ts->B * ts->T, e->n_vocab, sqrtf((float)C), ts->gsc, ts->emb_ws,
+    HIPCHK(e, launch_emb_bwd(ts->dX, C, ts->ids, (int64_t)ts->B * ts->T, dit->n_vocab, sqrtf((float)C), ts->gsc, ts->emb_ws,
                              G(ts, "emb.weight"), s));
-    if (grad_c) HIPCHK(e, hipMemcpyAsync(grad_c, ts->dcvec, (size_t)ts->B * e->G * 4, hipMemcpyDeviceToDevice, s));
+    if (grad_c) HIPCHK(e, hipMemcpyAsync(grad_c, ts->dcvec, (size_t)ts->B * dit->G * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(e, ts->side.join(s));
     return ST_OK;
 }
 
 int bwd_part(st_engine* e, TrainState* ts, int part, const float* grad_out, float* grad_x, float* grad_mu, float* grad_c, hipStream_t s) {
+    DitState* dit = dit_of(e);
     ProfScope prof(e, s, PC_TRAIN_BWD, 0);
     ForkGuard guard{ts->side, s};      // (an early error return joins the side stream too)
-    const int L = e->L;
+    const int L = dit->L;
     int rc;
     if (part == 0) {
         if ((rc = bwd_head(e, ts, grad_out, s))) return rc;
@@ -1171,9 +1188,10 @@ int st_train_backward(st_engine* e, int64_t serial, int B_, int T_, const float*
                       float* grad_c, void* stream) {
     if (!e) return ST_ERR_INVALID;
     int rc = bwd_check(e, KIND_DECODER, serial, B_, T_, "st_train_backward"); if (rc) return rc;
+    DitState* dit = dit_of(e);
     if (!grad_out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     HIPCHK(e, hipSetDevice(e->device));
-    TrainState* ts = e->train;
+    TrainState* ts = dit->train;
     ts->gbase = ts->grad_flat; ts->next_part = 0; ts->own_grads_valid = false;
     for (int part = 0; part < 3; ++part)
         if ((rc = bwd_part(e, ts, part, grad_out, grad_x, grad_mu, grad_c, (hipStream_t)stream))) return rc;
@@ -1185,7 +1203,8 @@ int st_train_backward_part(st_engine* e, int64_t serial, int B_, int T_, int par
                            int64_t grad_numel, float* grad_x, float* grad_mu, float* grad_c, void* stream) {
     if (!e) return ST_ERR_INVALID;
     int rc = bwd_check(e, KIND_DECODER, serial, B_, T_, "st_train_backward_part"); if (rc) return rc;
-    TrainState* ts = e->train;
+    DitState* dit = dit_of(e);
+    TrainState* ts = dit->train;
     if (part < 0 || part > 2) return e->fail(ST_ERR_INVALID, "st_train_backward_part: part must be 0, 1 or 2");
     if (part == 0) {
         if (!grad_out) return e->fail(ST_ERR_INVALID, "null tensor pointer");
@@ -1208,9 +1227,10 @@ int st_text_encoder_train_backward(st_engine* e, int64_t serial, int B_, int T_,
                                    float* grad_flat, float* grad_c, void* stream) {
     if (!e) return ST_ERR_INVALID;
     int rc = bwd_check(e, KIND_TEXT_ENCODER, serial, B_, T_, "st_text_encoder_train_backward"); if (rc) return rc;
+    DitState* dit = dit_of(e);
     if (!grad_x && !grad_mu) return e->fail(ST_ERR_INVALID, "st_text_encoder_train_backward: grad_x and grad_mu are both null");
     HIPCHK(e, hipSetDevice(e->device));
-    TrainState* ts = e->train;
+    TrainState* ts = dit->train;
     ts->gbase = grad_flat ? grad_flat : ts->grad_flat; ts->own_grads_valid = false;
     rc = bwd_text(e, ts, grad_x, grad_mu, grad_c, (hipStream_t)stream);
     ts->own_grads_valid = !rc && ts->gbase == ts->grad_flat;
@@ -1219,11 +1239,13 @@ int st_text_encoder_train_backward(st_engine* e, int64_t serial, int B_, int T_,
 }
 
 int st_train_param_part(const st_engine* e, const char* name) {
-    if (!e || !name || (e->kind != KIND_DECODER && e->kind != KIND_TEXT_ENCODER)) return ST_ERR_INVALID;
+    if (!e || !name) return ST_ERR_INVALID;
+    const DitState* dit = dit_or_null(e);
+    if (!dit) return ST_ERR_INVALID;
     const std::string n(name);
     if (!e->params.count(n)) return ST_ERR_INVALID;
     if (e->kind == KIND_TEXT_ENCODER) return 0;      // the text encoder's backward is one part
-    if (n.rfind("blocks.", 0) == 0) return atoi(n.c_str() + 7) >= e->L / 2 ? 0 : 1;
+    if (n.rfind("blocks.", 0) == 0) return atoi(n.c_str() + 7) >= dit->L / 2 ? 0 : 1;
     if (n.rfind("final_proj.", 0) == 0 || n.rfind("lsc_layers.", 0) == 0) return 0;
     return 2;
 }
@@ -1240,24 +1262,26 @@ int64_t st_train_grad_numel(const st_engine* e) { return e ? train_grad_layout(e
 
 int st_param_grads_flat(st_engine* e, float* dst, int64_t numel, void* stream) {
     if (!e || !dst) return ST_ERR_INVALID;
-    if (!e->train || !e->train->grad_flat) return e->fail(ST_ERR_STATE, "no training state");
-    if (numel != e->train->grad_numel) return e->fail(ST_ERR_INVALID, "st_param_grads_flat: numel must be the sum of all parameter sizes");
-    if (!e->train->own_grads_valid) return e->fail(ST_ERR_STATE, "st_param_grads_flat: the last backward did not complete into the engine's own gradient buffer (it wrote into the caller's, or was abandoned)");
+    const DitState* dit = dit_or_null(e);
+    if (!dit || !dit->train || !dit->train->grad_flat) return e->fail(ST_ERR_STATE, "no training state");
+    if (numel != dit->train->grad_numel) return e->fail(ST_ERR_INVALID, "st_param_grads_flat: numel must be the sum of all parameter sizes");
+    if (!dit->train->own_grads_valid) return e->fail(ST_ERR_STATE, "st_param_grads_flat: the last backward did not complete into the engine's own gradient buffer (it wrote into the caller's, or was abandoned)");
     HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, hipMemcpyAsync(dst, e->train->grad_flat, (size_t)numel * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIPCHK(e, hipMemcpyAsync(dst, dit->train->grad_flat, (size_t)numel * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return ST_OK;
 }
 
 int st_param_grad(st_engine* e, const char* name, float* dst, int64_t numel, void* stream) {
     if (!e || !name || !dst) return ST_ERR_INVALID;
-    if (!e->train) return e->fail(ST_ERR_STATE, "no training state");
-    auto it = e->train->goff.find(name);
+    const DitState* dit = dit_or_null(e);
+    if (!dit || !dit->train) return e->fail(ST_ERR_STATE, "no training state");
+    auto it = dit->train->goff.find(name);
     auto pit = e->params.find(name);
-    if (it == e->train->goff.end() || pit == e->params.end()) return e->fail(ST_ERR_INVALID, std::string("unknown parameter: ") + name);
+    if (it == dit->train->goff.end() || pit == e->params.end()) return e->fail(ST_ERR_INVALID, std::string("unknown parameter: ") + name);
     if (pit->second.numel() != numel) return e->fail(ST_ERR_INVALID, std::string("size mismatch for gradient of ") + name);
-    if (!e->train->own_grads_valid) return e->fail(ST_ERR_STATE, "st_param_grad: the last backward did not complete into the engine's own gradient buffer (it wrote into the caller's, or was abandoned)");
+    if (!dit->train->own_grads_valid) return e->fail(ST_ERR_STATE, "st_param_grad: the last backward did not complete into the engine's own gradient buffer (it wrote into the caller's, or was abandoned)");
     HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, hipMemcpyAsync(dst, e->train->grad_flat + it->second, (size_t)numel * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIPCHK(e, hipMemcpyAsync(dst, dit->train->grad_flat + it->second, (size_t)numel * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return ST_OK;
 }
 

@@ -16,7 +16,10 @@ using namespace sthost;
 
 namespace sthost {
 
-struct VocosState {
+struct VocosState : HeldState {      // (held: st_vocos_train_forward's activations, engine_vocos_train.cpp)
+    VocosState() : HeldState("st_repack: vocoder handles re-pack through st_finalize") {}
+    ~VocosState() override { slots.destroy(); }
+    int finalize(st_engine* e) override;
     st_vocos_config cfg{};
     Conv embed, head;
     std::vector<Conv> pw1, pw2;
@@ -46,8 +49,10 @@ void vocos_build_params(st_engine* e, const st_vocos_config& c) {
 // embed convolution packs as [cout][tap][cin] = the K order of launch_voc_im2col7's rows, each row padded with zeros to
 // voc_im2col_pitch(M).  The head's n_fft + 2 output rows are laid out as two planes of voc_head_plane(n_fft) rows
 // (log-magnitude 0..n_fft/2, phase 0..n_fft/2, zero rows between): 1152 at n_fft 2048, 640 / 384 / 256 at 1024 / 512 / 256.
-int vocos_finalize(st_engine* e) {
-    VocosState* v = e->voc;
+int VocosState::finalize(st_engine* e) {
+    HeldState::finalize(e);
+    free_owned(e);
+    VocosState* v = this;
     const st_vocos_config& c = v->cfg;
     const int C = c.dim, F = c.intermediate_dim, M = c.input_channels, L = c.num_layers;
     hipStream_t s = nullptr;
@@ -115,18 +120,10 @@ int vocos_finalize(st_engine* e) {
         }
     }
     HIPCHK(e, hipDeviceSynchronize());
-    e->finalized = true;
     return ST_OK;
 }
 
-const st_vocos_config& vocos_config_of(const st_engine* e) { return e->voc->cfg; }
-
-void vocos_destroy(st_engine* e) {
-    VocosState* v = e->voc;
-    if (!v) return;
-    v->slots.destroy();
-    delete v; e->voc = nullptr;
-}
+const st_vocos_config& vocos_config_of(const st_engine* e) { return state_of<VocosState>(e)->cfg; }
 
 }  // namespace sthost
 
@@ -144,15 +141,15 @@ int st_create_vocoder(const st_vocos_config* cfg, int device, st_engine** out) {
         return bad("native ISTFT is built for n_fft == 256, 512, 1024 or 2048 with hop_length == n_fft / 4", ST_ERR_UNSUPPORTED);
     if (cfg->input_channels % 16 != 0 || cfg->input_channels > 192) return bad("input_channels must be a multiple of 16 up to 192", ST_ERR_UNSUPPORTED);
     if (cfg->intermediate_dim % 256 != 0) return bad("intermediate_dim must be a multiple of 256", ST_ERR_UNSUPPORTED);
+    auto state = std::make_unique<VocosState>();
+    state->cfg = *cfg;
     st_engine* e = nullptr;
-    if (int rc = new_handle(KIND_VOCODER, device, &e)) return rc;
+    if (int rc = new_handle(KIND_VOCODER, device, std::move(state), &e)) return rc;
     e->dt = cfg->operand_dtype == ST_OPERAND_BF16 ? DT_BF16 : DT_F16;
-    e->voc = new VocosState();
-    e->voc->cfg = *cfg;
-    e->splitk_target = 0; e->attn_small_blocks = 0;      // decoder-only small-grid paths
+    e->tile.splitk_target = 0;      // no split-K convs: the vocoder's GEMMs run over the flattened rows of the whole batch
     vocos_build_params(e, *cfg);
     if (hipMalloc(&e->zeros, 256) != hipSuccess || hipMemset(e->zeros, 0, 256) != hipSuccess) {
-        vocos_destroy(e); delete e;
+        delete e;
         return bad("hipMalloc failed", ST_ERR_HIP);
     }
     *out = e;
@@ -164,7 +161,7 @@ int st_create_vocoder(const st_vocos_config* cfg, int device, st_engine** out) {
 // ragged launcher).  The K loop of the conv GEMM forms an activation row's byte offset as a 32-bit value (t * cin * 2,
 // conv_gemm2_impl.h), so the callers size chunks to keep R * max(voc_im2col_pitch(M), C, F) * 2 below 2^31.
 static int vocos_forward_chunk(st_engine* e, const float* mel, float* audio, int B, int T, const RaggedChunk* rg, hipStream_t s) {
-    VocosState* v = e->voc;
+    VocosState* v = state_of<VocosState>(e);
     const st_vocos_config& c = v->cfg;
     const int C = c.dim, F = c.intermediate_dim, M = c.input_channels, L = c.num_layers;
     const int Kp = voc_im2col_pitch(M), plane = voc_head_plane(c.n_fft);
@@ -249,7 +246,7 @@ int st_vocos_forward(st_engine* e, const float* mel, float* audio, int B, int T,
     if ((rc = check_finalized(e))) return rc;
     if (!mel || !audio) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if ((rc = check_sizes(e, B, T))) return rc;
-    const st_vocos_config& c = e->voc->cfg;
+    const st_vocos_config& c = state_of<VocosState>(e)->cfg;
     const int64_t max_rows = vocos_max_rows(c);
     if (T > max_rows) return e->fail(ST_ERR_INVALID, "T too large: one utterance exceeds the vocoder's 32-bit row indexing");
     HIPCHK(e, hipSetDevice(e->device));
@@ -272,7 +269,7 @@ int st_vocos_forward_ragged(st_engine* e, const float* mel, const int64_t* lengt
     if (!mel || !audio) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if (!lengths) return e->fail(ST_ERR_INVALID, "null lengths");
     if ((rc = check_sizes(e, B, T))) return rc;
-    VocosState* v = e->voc;
+    VocosState* v = state_of<VocosState>(e);
     const st_vocos_config& c = v->cfg;
     const int64_t max_rows = vocos_max_rows(c);
     // validate everything and plan the chunks before touching the device: whole utterances, as many as keep the packed rows

@@ -94,7 +94,7 @@ int st_vocos_train_forward(st_engine* e, const float* mel, float* audio, int B, 
     const int64_t R = (int64_t)B * T;
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    SdTrain* st = sd_train_begin(e);
+    SdTrain* st = state_of<HeldState>(e)->begin();
     const VtActs A = vt_acts(c, R);
     if ((rc = sd_train_grow(e, &st->act, &st->act_cap, A.end * 4))) return rc;
     float* act = (float*)st->act;
@@ -146,11 +146,8 @@ int st_vocos_train_backward(st_engine* e, const float* d_audio, float* d_mel, fl
     if ((rc = vt_check_config(e))) return rc;
     if (!d_audio || !grad_flat) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     if ((rc = check_sizes(e, B, T))) return rc;
-    SdTrain* st = e->sdt;
-    if (!st || !st->have) return e->fail(ST_ERR_STATE, "st_vocos_train_backward needs a preceding st_vocos_train_forward");
-    if (B != st->B || T != st->T)
-        return e->fail(ST_ERR_STATE, "st_vocos_train_backward: the engine holds the activations of a forward with B=" + std::to_string(st->B) +
-                       ", T=" + std::to_string(st->T) + ", not B=" + std::to_string(B) + ", T=" + std::to_string(T));
+    SdTrain* st = &state_of<HeldState>(e)->held;
+    if ((rc = sd_train_check(e, *st, "st_vocos_train", "T", -1, B, T))) return rc;
     const VtCfg c = vt_cfg(e);
     const int C = c.C, F = c.F, M = c.M, L = c.L, NB = c.NB;
     const int64_t R = (int64_t)B * T;

@@ -1,4 +1,4 @@
-// Fork / join of engine-owned child streams (engine_internal.h: st_engine::part_streams, engine_train.cpp: TrainState::side*).
+// Fork / join of engine-owned child streams (engine_dit.h: DitState::part_streams, engine_train.cpp: TrainState::side*).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Are two builds of the library bitwise identical on the four fp32 handle kinds?  usage: python tools/fp32_bitwise_ab.py libA.so libB.so
+"""Are two builds of the library bitwise identical on the fp32 handle kinds and the two vocoders?  usage: python tools/fp32_bitwise_ab.py libA.so libB.so
 (developer tool: one fresh process per library, one after the other, each under its own time limit; stops at the first that fails.)
 
 Compared with torch.equal, at the shapes of the GPU tests (tile edges, every tap count, Cin / Cout off the 16 / 64 multiples,
@@ -9,6 +9,16 @@ split-K weight gradients):
   Vocos training                       waveform, parameter gradients and d mel at (B, T) = (2, 1), (2, 3), (2, 61), (1, 20) and
                                        (2, 9) with input_channels 128, on the small_linear configuration and weights
   period discriminator                 feature maps, d x and parameter gradients at every shape of tests/test_gpu_mpd.py: SHAPES
+  resolution discriminator, mel extractor, Vocos inference, FireflyGAN inference
+                                       one case each through the C ABI, at the configurations and shapes of
+                                       tests/test_gpu_handle_lifecycle.py; the resolution discriminator also through one training
+                                       forward and backward (feature maps, d x, every parameter gradient).  The configurations,
+                                       weights and forwards are imported from that test module (as the period discriminator's
+                                       shapes are from its own), so an edit there changes what is compared here.  These are the
+                                       smallest shapes each kind accepts: B = 1, T = 8 frames (97 samples for the discriminator, 64
+                                       for the mel extractor), and the mel extractor and the two vocoders compare ONE output
+                                       tensor each -- a check that moved host code still launches the same work, not a sweep
+                                       of tile paths (tests/test_gpu_vocoder.py, test_gpu_mel.py and test_gpu_ffgan.py are that)
 """
 import os
 import subprocess
@@ -112,10 +122,31 @@ def _mpd():
     return got
 
 
+def _other_kinds():
+    from tests import test_gpu_handle_lifecycle as L
+    got = {}
+    for name in ("resolution_disc", "mel_extractor", "vocoder", "ffgan"):
+        kind = L.KINDS[name]
+        eng = kind.create()
+        eng.load_state_dict(L._tensors(kind.weights(eng)))
+        got.update({f"{name}/out{i}": t.cpu() for i, t in enumerate(kind.forward(eng))})
+        if name == "resolution_disc":
+            shapes = kind.shapes(eng, L.B)
+            x, fmaps = L._rand((L.B, 1, kind.T), 10), [torch.empty(s, device="cuda") for s in shapes]
+            eng.resolution_disc_forward(x, fmaps, True, None)
+            d_x, flat = torch.empty_like(x), torch.zeros(eng.grad_layout()[None], device="cuda")
+            eng.resolution_disc_train_backward(L.B, kind.T, [L._rand(s, 20 + i) for i, s in enumerate(shapes)], d_x, flat, None)
+            got.update({f"{name}/train/out{i}": t.cpu() for i, t in enumerate(fmaps)})
+            got.update({f"{name}/train/d_x": d_x.cpu(), f"{name}/train/grad_flat": flat.cpu()})
+        torch.cuda.synchronize()
+        eng.close()
+    return got
+
+
 if len(sys.argv) == 3 and sys.argv[1] == "--run":
     sys.path.insert(0, ROOT)
     out = {}
-    for part in (_style_dp, _vocos, _mpd):
+    for part in (_style_dp, _vocos, _mpd, _other_kinds):
         out.update(part())
     torch.cuda.synchronize()
     torch.save(out, sys.argv[2])
@@ -136,7 +167,7 @@ for i, lib in enumerate(sys.argv[1:3]):
 a, b = outs
 assert sorted(a) == sorted(b), "the two runs saved different tensor names"
 diff = [n for n in a if not torch.equal(a[n].view(torch.int32), b[n].view(torch.int32))]      # bit patterns: NaN == NaN
-for group in ("style", "dp", "vocos", "mpd"):
+for group in ("style", "dp", "vocos", "mpd", "resolution_disc", "mel_extractor", "vocoder", "ffgan"):
     names = [n for n in a if n.startswith(group + "/")]
     print(f"{group}: {len(names)} tensors compared, {sum(n in diff for n in names)} differ")
 print(f"[{sys.argv[1]}] vs [{sys.argv[2]}]: {len(a)} tensors, differing: {len(diff)} {diff[:8]}")
