@@ -383,30 +383,30 @@ class Engine:
                                                      x_out.data_ptr(), mu_out.data_ptr(), mask_out.data_ptr(), B, T,
                                                      ctypes.c_void_p(stream)))
 
-    def vocos_forward(self, mel, audio, stream):
+    def _vocoder_forward(self, fn, mel, lengths, audio, stream):
+        """mel (B, input_channels, T) -> audio (B, T * hop); lengths (a sequence of B ints, host side): the ragged entry point `fn`."""
         B, _, T = mel.shape
-        self._check(self.lib.st_vocos_forward(self.handle, mel.data_ptr(), audio.data_ptr(), B, T, ctypes.c_void_p(stream)))
+        if lengths is None:
+            return self._check(fn(self.handle, mel.data_ptr(), audio.data_ptr(), B, T, ctypes.c_void_p(stream)))
+        if len(lengths) != B:
+            raise NativeError(ST_ERR_INVALID, f"lengths has {len(lengths)} entries, the batch has B = {B} utterances")
+        arr = (ctypes.c_int64 * B)(*lengths)
+        self._check(fn(self.handle, mel.data_ptr(), arr, audio.data_ptr(), B, T, ctypes.c_void_p(stream)))
+
+    def vocos_forward(self, mel, audio, stream):
+        self._vocoder_forward(self.lib.st_vocos_forward, mel, None, audio, stream)
 
     def ffgan_forward(self, mel, audio, stream):
         """mel (B, input_channels, T) -> audio (B, T * hop) (FireflyGAN vocoder handles)."""
-        B, _, T = mel.shape
-        self._check(self.lib.st_ffgan_forward(self.handle, mel.data_ptr(), audio.data_ptr(), B, T, ctypes.c_void_p(stream)))
+        self._vocoder_forward(self.lib.st_ffgan_forward, mel, None, audio, stream)
 
     def ffgan_forward_ragged(self, mel, lengths, audio, stream):
         """st_ffgan_forward with utterance b at its own length lengths[b] (a sequence of B ints, host side)."""
-        B, _, T = mel.shape
-        if len(lengths) != B:
-            raise NativeError(ST_ERR_INVALID, f"lengths has {len(lengths)} entries, the batch has B = {B} utterances")
-        arr = (ctypes.c_int64 * B)(*lengths)
-        self._check(self.lib.st_ffgan_forward_ragged(self.handle, mel.data_ptr(), arr, audio.data_ptr(), B, T, ctypes.c_void_p(stream)))
+        self._vocoder_forward(self.lib.st_ffgan_forward_ragged, mel, lengths, audio, stream)
 
     def vocos_forward_ragged(self, mel, lengths, audio, stream):
         """st_vocos_forward with utterance b at its own length lengths[b] (a sequence of B ints, host side)."""
-        B, _, T = mel.shape
-        if len(lengths) != B:
-            raise NativeError(ST_ERR_INVALID, f"lengths has {len(lengths)} entries, the batch has B = {B} utterances")
-        arr = (ctypes.c_int64 * B)(*lengths)
-        self._check(self.lib.st_vocos_forward_ragged(self.handle, mel.data_ptr(), arr, audio.data_ptr(), B, T, ctypes.c_void_p(stream)))
+        self._vocoder_forward(self.lib.st_vocos_forward_ragged, mel, lengths, audio, stream)
 
     def vocos_train_forward(self, mel, audio, stream):
         """st_vocos_forward in fp32 that keeps the activations for vocos_train_backward (vocoder handles)."""
@@ -420,42 +420,48 @@ class Engine:
         self._check(self.lib.st_vocos_train_backward(self.handle, d_audio.data_ptr(), d_mel.data_ptr() if d_mel is not None else None,
                                                      grad_flat.data_ptr(), B, T, ctypes.c_void_p(stream)))
 
-    def period_disc_fmap_shapes(self, B, T, period):
-        """The five feature-map shapes (B, C, H, period) of a (B, 1, T) input (period-discriminator handles)."""
+    def _disc_fmap_shapes(self, fn, n, B, T, n_dims, too_short):
+        """(B, *dims) of each of the n feature maps; `too_short`: the message when T is below the kind's minimum."""
         out = []
-        for i in range(5):
-            c, h = ctypes.c_int64(), ctypes.c_int64()
-            if self.lib.st_period_disc_fmap_shape(self.handle, int(T), i, ctypes.byref(c), ctypes.byref(h)) != ST_OK:
-                n_pad = (period - T % period) % period
-                raise NativeError(ST_ERR_INVALID, f"T = {T} is too short for period {period}: the reflect padding of {n_pad} samples "
-                                                  f"needs T > {n_pad}")
-            out.append((B, c.value, h.value, period))
+        for i in range(n):
+            dims = [ctypes.c_int64() for _ in range(n_dims)]
+            if fn(self.handle, int(T), i, *[ctypes.byref(d) for d in dims]) != ST_OK:
+                raise NativeError(ST_ERR_INVALID, too_short)
+            out.append((B, *[d.value for d in dims]))
         return out
 
-    def period_disc_forward(self, x, fmaps, train, stream):
-        """x (B, 1, T) -> the five feature maps; train: keep the activations for period_disc_train_backward."""
+    def _disc_forward(self, kind, n, x, fmaps, train, stream):
         B, _, T = x.shape
-        ptrs = (ctypes.c_void_p * 5)(*[f.data_ptr() for f in fmaps])
-        fn = self.lib.st_period_disc_train_forward if train else self.lib.st_period_disc_forward
+        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fmaps])
+        fn = getattr(self.lib, f"st_{kind}_train_forward" if train else f"st_{kind}_forward")
         self._check(fn(self.handle, x.data_ptr(), ptrs, B, T, ctypes.c_void_p(stream)))
 
-    def period_disc_train_backward(self, B, T, d_fmaps, d_x, grad_flat, stream):
-        """d_fmaps: five tensors or None each; d x (None: not wanted) and every parameter gradient into grad_flat (None: none wanted)."""
+    def _disc_train_backward(self, kind, n, B, T, d_fmaps, d_x, grad_flat, stream):
         if grad_flat is not None and grad_flat.numel() != self.grad_layout()[None]:
             raise ValueError("grad_flat must hold grad_layout()[None] floats")
         ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
-        ptrs = (ctypes.c_void_p * 5)(*[ptr(f) for f in d_fmaps])
-        self._check(self.lib.st_period_disc_train_backward(self.handle, ptrs, ptr(d_x), ptr(grad_flat), B, T, ctypes.c_void_p(stream)))
+        ptrs = (ctypes.c_void_p * n)(*[ptr(f) for f in d_fmaps])
+        self._check(getattr(self.lib, f"st_{kind}_train_backward")(self.handle, ptrs, ptr(d_x), ptr(grad_flat), B, T, ctypes.c_void_p(stream)))
+
+    def period_disc_fmap_shapes(self, B, T, period):
+        """The five feature-map shapes (B, C, H, period) of a (B, 1, T) input (period-discriminator handles)."""
+        n_pad = (period - T % period) % period
+        shapes = self._disc_fmap_shapes(self.lib.st_period_disc_fmap_shape, 5, B, T, 2,
+                                        f"T = {T} is too short for period {period}: the reflect padding of {n_pad} samples needs T > {n_pad}")
+        return [s + (period,) for s in shapes]
+
+    def period_disc_forward(self, x, fmaps, train, stream):
+        """x (B, 1, T) -> the five feature maps; train: keep the activations for period_disc_train_backward."""
+        self._disc_forward("period_disc", 5, x, fmaps, train, stream)
+
+    def period_disc_train_backward(self, B, T, d_fmaps, d_x, grad_flat, stream):
+        """d_fmaps: five tensors or None each; d x (None: not wanted) and every parameter gradient into grad_flat (None: none wanted)."""
+        self._disc_train_backward("period_disc", 5, B, T, d_fmaps, d_x, grad_flat, stream)
 
     def resolution_disc_fmap_shapes(self, B, T):
         """The 21 feature-map shapes (B, C, frames, width) of a (B, 1, T) input (resolution-discriminator handles)."""
-        out = []
-        for i in range(21):
-            c, f, w = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-            if self.lib.st_resolution_disc_fmap_shape(self.handle, int(T), i, ctypes.byref(c), ctypes.byref(f), ctypes.byref(w)) != ST_OK:
-                raise NativeError(ST_ERR_INVALID, f"T = {T} is too short for this window length: the reflect padding needs T > window_length / 2")
-            out.append((B, c.value, f.value, w.value))
-        return out
+        return self._disc_fmap_shapes(self.lib.st_resolution_disc_fmap_shape, 21, B, T, 3,
+                                      f"T = {T} is too short for this window length: the reflect padding needs T > window_length / 2")
 
     def resolution_disc_wgrad_planes(self, B, T, band, layer):
         """Split-K planes of the weight-gradient launch of band_convs.{band}.{layer} at (B, T) (tests / tools)."""
@@ -466,18 +472,11 @@ class Engine:
 
     def resolution_disc_forward(self, x, fmaps, train, stream):
         """x (B, 1, T) -> the 21 feature maps; train: keep the activations for resolution_disc_train_backward."""
-        B, _, T = x.shape
-        ptrs = (ctypes.c_void_p * 21)(*[f.data_ptr() for f in fmaps])
-        fn = self.lib.st_resolution_disc_train_forward if train else self.lib.st_resolution_disc_forward
-        self._check(fn(self.handle, x.data_ptr(), ptrs, B, T, ctypes.c_void_p(stream)))
+        self._disc_forward("resolution_disc", 21, x, fmaps, train, stream)
 
     def resolution_disc_train_backward(self, B, T, d_fmaps, d_x, grad_flat, stream):
         """d_fmaps: 21 tensors or None each; d x (None: not wanted) and every parameter gradient into grad_flat (None: none wanted)."""
-        if grad_flat is not None and grad_flat.numel() != self.grad_layout()[None]:
-            raise ValueError("grad_flat must hold grad_layout()[None] floats")
-        ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
-        ptrs = (ctypes.c_void_p * 21)(*[ptr(f) for f in d_fmaps])
-        self._check(self.lib.st_resolution_disc_train_backward(self.handle, ptrs, ptr(d_x), ptr(grad_flat), B, T, ctypes.c_void_p(stream)))
+        self._disc_train_backward("resolution_disc", 21, B, T, d_fmaps, d_x, grad_flat, stream)
 
     def finalize(self):
         """st_finalize on the parameters already loaded / bound: a vocoder handle packs its 16-bit inference copies again."""

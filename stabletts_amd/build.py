@@ -19,7 +19,7 @@ LIB = os.environ.get("ST_BUILD_OUT") or os.path.join(HERE, "libstabletts_hip.so"
 OBJ = os.path.join(HERE, "csrc", "build") if not os.environ.get("ST_BUILD_OUT") else LIB + ".obj"
 SOURCES = ["engine.cpp", "engine_solve.cpp", "engine_train.cpp", "engine_vocos.cpp", "engine_vocos_train.cpp", "engine_style.cpp", "engine_duration.cpp", "engine_audio.cpp", "engine_period_disc.cpp", "period_disc_kernels.hip", "engine_resolution_disc.cpp", "resolution_disc_kernels.hip", "engine_gan_loss.cpp", "gan_loss_kernels.hip", "engine_optim.cpp", "optim_kernels.hip", "engine_resample.cpp", "resample_kernels.hip", "engine_ffgan.cpp", "ffgan_kernels.hip", "vocos_kernels.hip", "vocos_train_kernels.hip", "audio_kernels.hip", "style_dp_kernels.hip", "style_dp_bwd.hip", "conv_gemm2_bf16.hip", "conv_gemm2_f16.hip", "ffn_fused_bf16.hip", "ffn_fused_f16.hip", "ffn_wino_f16.hip", "qkv_ws.hip", "oproj_ws.hip",
            "attention.hip", "attention_bwd.hip", "train_kernels.hip", "emb_bwd.hip", "wgrad_tn.hip", "misc_kernels.hip", "align_kernels.hip", "align_train_kernels.hip", "adaptive_ode.hip", "mas_kernels.hip"]
-HEADERS = ["common.h", "launch.h", "train_launch.h", "vocos_launch.h", "vocos_train_launch.h", "audio_launch.h", "audio_fft.h", "style_dp_launch.h", "style_dp_drop.h", "fp32_tile.h", "period_disc_launch.h", "resolution_disc_launch.h", "mas_launch.h", "align_train_launch.h", "gan_loss_launch.h", "optim_launch.h", "resample_launch.h", "ffgan_launch.h", "block_reduce.h", "engine_internal.h", "engine_dit.h", "engine_disc.h", "utt_slots.h", "stream_fork.h", "conv_gemm2_impl.h", "conv_gemm_phased.h", "conv_gemm2_inst.h", "ffn_fused.h", "ffn_wino.h", os.path.join("..", "..", "include", "stabletts_hip.h")]
+HEADERS = ["common.h", "launch.h", "train_launch.h", "vocos_launch.h", "vocos_train_launch.h", "audio_launch.h", "audio_fft.h", "style_dp_launch.h", "style_dp_drop.h", "fp32_tile.h", "period_disc_launch.h", "resolution_disc_launch.h", "mas_launch.h", "align_train_launch.h", "gan_loss_launch.h", "optim_launch.h", "resample_launch.h", "ffgan_launch.h", "block_reduce.h", "engine_internal.h", "engine_dit.h", "engine_disc.h", "engine_vocoder.h", "chunk_plan.h", "utt_slots.h", "stream_fork.h", "conv_gemm2_impl.h", "conv_gemm_phased.h", "conv_gemm2_inst.h", "ffn_fused.h", "ffn_wino.h", os.path.join("..", "..", "include", "stabletts_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result",
          "-Rpass-analysis=kernel-resource-usage"]
 # per-source flags: the attention kernels keep their fp32 row-sum adds scalar (common.h: add_f32_scalar)

@@ -681,17 +681,6 @@ __device__ __forceinline__ void attn_mean_nat_body(const typename P::elem* nat, 
     }
 }
 template <class P>
-__global__ __launch_bounds__(256) void attn_mean_nat_kernel(const typename P::elem* nat, int T, float* mean) {
-    attn_mean_nat_body<P>(nat, T, mean, blockIdx.x);
-}
-
-hipError_t launch_attn_mean_nat(int dtype, const void* nat, int n_heads_total, int T, float* mean, hipStream_t s) {
-    if (dtype == DT_BF16) hipLaunchKernelGGL((attn_mean_nat_kernel<OpBF16>), dim3(n_heads_total), dim3(256), 0, s, (const __bf16*)nat, T, mean);
-    else                  hipLaunchKernelGGL((attn_mean_nat_kernel<OpF16>), dim3(n_heads_total), dim3(256), 0, s, (const _Float16*)nat, T, mean);
-    return hipGetLastError();
-}
-
-template <class P>
 __device__ __forceinline__ void attn_to_T_body(const typename P::elem* nat, int64_t item_stride, int64_t head_stride,
                                                int row_stride, int H, int T, int Tp, const float* mean,
                                                typename P::elem* outT, int bx, int nh) {
@@ -751,11 +740,6 @@ __device__ __forceinline__ void attn_vmean_body(const typename P::elem* inT, con
         if (lane == 0) vmean[(size_t)nh * 64 + d] = v / (float)T;
     }
 }
-template <class P>
-__global__ __launch_bounds__(256) void attn_vmean_kernel(const typename P::elem* inT, int T, int Tp, float* vmean) {
-    attn_vmean_body<P>(inT, nullptr, T, Tp, vmean, blockIdx.x);
-}
-
 // T layout -> natural rows, centred: nat[t][d] = V^T[d][perm(t)] - c[d]
 template <class P, bool LO = false>
 __device__ __forceinline__ void attn_from_T_body(const typename P::elem* inT, const typename P::elem* inT_lo, int T, int Tp, const float* vmean,
@@ -782,12 +766,6 @@ __device__ __forceinline__ void attn_from_T_body(const typename P::elem* inT, co
         }
     }
 }
-template <class P>
-__global__ __launch_bounds__(256) void attn_from_T_kernel(const typename P::elem* inT, int T, int Tp, const float* vmean,
-                                                          typename P::elem* nat, typename P::elem* nat_lo) {
-    attn_from_T_body<P>(inT, nullptr, T, Tp, vmean, nat, nat_lo, blockIdx.x, blockIdx.y);
-}
-
 // The gradient-independent operand copies of one attention backward in TWO launches (were six): the three means (grid.y = q, k, v),
 // then the centred copies (grid.z = V back to natural rows as a hi + lo pair, Q^T, K^T).  Same bodies, same results.
 template <class P, bool VLO>
@@ -824,19 +802,6 @@ hipError_t launch_attn_prep(int dtype, const void* q, const void* k, const void*
     } else {
         if (vT_lo) attn_prep_launch<OpF16, true>(q, k, vT, vT_lo, n_items, H, T, Tp, qmean, kmean, vmean, qT, kT, vnat, vnat_lo, s);
         else       attn_prep_launch<OpF16, false>(q, k, vT, vT_lo, n_items, H, T, Tp, qmean, kmean, vmean, qT, kT, vnat, vnat_lo, s);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_attn_from_T(int dtype, const void* inT, int n_items, int H, int T, int Tp, float* vmean, void* nat, void* nat_lo,
-                              hipStream_t s) {
-    dim3 grid(Tp / 64, n_items * H);
-    if (dtype == DT_BF16) {
-        if (vmean) hipLaunchKernelGGL((attn_vmean_kernel<OpBF16>), dim3(n_items * H), dim3(256), 0, s, (const __bf16*)inT, T, Tp, vmean);
-        hipLaunchKernelGGL((attn_from_T_kernel<OpBF16>), grid, dim3(256), 0, s, (const __bf16*)inT, T, Tp, vmean, (__bf16*)nat, (__bf16*)nat_lo);
-    } else {
-        if (vmean) hipLaunchKernelGGL((attn_vmean_kernel<OpF16>), dim3(n_items * H), dim3(256), 0, s, (const _Float16*)inT, T, Tp, vmean);
-        hipLaunchKernelGGL((attn_from_T_kernel<OpF16>), grid, dim3(256), 0, s, (const _Float16*)inT, T, Tp, vmean, (_Float16*)nat, (_Float16*)nat_lo);
     }
     return hipGetLastError();
 }

@@ -10,13 +10,11 @@
 // [W_hi | W_hi | W_lo], or K = [a_hi | a_lo | a_hi | a_lo] against [W_hi | W_hi | W_lo | W_lo] (pwconv1 as an fp32-output GEMM, then the
 // GELU row kernel that writes the pair); the head runs the SPLIT instantiations of its convolution family on fp32 tensors: c1
 // stores its fp32 pre-activation and c2 applies the SiLU while it stages it.
-#include "engine_internal.h"
+#include "engine_vocoder.h"
 #include "ffgan_launch.h"
-#include "utt_slots.h"
 #include "vocos_launch.h"
 
 #include <algorithm>
-#include <cstring>
 #include <string>
 
 using namespace st;
@@ -264,12 +262,7 @@ static int ffgan_forward_chunk(st_engine* e, const float* mel, float* audio, int
     const int parts = v->parts();
     auto pair_src = [&](ConvGemmArgs& a, const void* pair, int K) { a.a0 = pair; a.c0 = 2 * K; a.c2 = (parts - 2) * K; };
 
-    auto args = [&](const Conv& cv) {
-        ConvGemmArgs a; memset(&a, 0, sizeof(a));
-        a.w = cv.w; a.bias = cv.bias; a.cout = cv.cout; a.T = (int)R; a.n_items = 1;     // flattened rows
-        a.a0_mod = 1; a.a1_mod = 1; a.mask_mod = 1; a.zeros = e->zeros;
-        return a;
-    };
+    auto args = [&](const Conv& cv) { return flat_gemm_args(e, cv, R); };
     // ---- ConvNeXtEncoder.forward (backbone.py:206-214)
     for (int i = 0; i < c.n_stages; ++i) {
         const int C = c.dims[i];
@@ -365,6 +358,17 @@ static int ffgan_forward_chunk(st_engine* e, const float* mel, float* audio, int
     return ST_OK;
 }
 
+// Chunks keep the packed rows within max_rows, the head's level tensors of those rows within kFfganHeadBytes (one utterance
+// always runs) and the grid within 65535 items; dense and ragged batches alike
+static VocoderGeom ffgan_geom(st_engine* e) {
+    FfganState* v = state_of<FfganState>(e);
+    const int64_t head_rows = std::max<int64_t>(1, kFfganHeadBytes / (ffgan_level_elems(v->cfg) * ffgan_head_sample_bytes(v)));
+    const ChunkLimits lim = {ffgan_max_rows(v->cfg), 65535, 0, head_rows};
+    return {lim, lim, v->cfg.input_channels, v->hop, &v->slots};
+}
+static int ffgan_dw_frames(int64_t) { return 1; }      // one depthwise group per packed row
+static const VocoderKind kFfganKind = {KIND_FFGAN, "the vocoder's row indexing", kFfganMaxT, ffgan_geom, ffgan_dw_frames, ffgan_forward_chunk};
+
 }  // namespace sthost
 
 extern "C" {
@@ -391,70 +395,11 @@ int st_create_ffgan(const st_ffgan_config* cfg, int device, st_engine** out) {
 }
 
 int st_ffgan_forward(st_engine* e, const float* mel, float* audio, int B, int T, void* stream) {
-    int rc = check_handle(e, KIND_FFGAN); if (rc) return rc;
-    if ((rc = check_finalized(e))) return rc;
-    if (!mel || !audio) return e->fail(ST_ERR_INVALID, "null tensor pointer");
-    if ((rc = check_sizes(e, B, T))) return rc;
-    const FfganState* v = state_of<FfganState>(e);
-    const st_ffgan_config& c = v->cfg;
-    const int64_t max_rows = ffgan_max_rows(c);
-    if (T > max_rows || T > kFfganMaxT) return e->fail(ST_ERR_INVALID, "T too large: one utterance exceeds the vocoder's row indexing");
-    const int64_t head_item = ffgan_level_elems(c) * T * ffgan_head_sample_bytes(v);
-    const int chunk = (int)std::min<int64_t>({(int64_t)B, std::max<int64_t>(1, kFfganHeadBytes / head_item), max_rows / T, (int64_t)65535});
-    if (chunk < B && e->capture) return e->fail(ST_ERR_INVALID, "debug capture holds whole-batch tensors: this batch runs in chunks");
-    HIPCHK(e, hipSetDevice(e->device));
-    hipStream_t s = (hipStream_t)stream;
-    const size_t mel_item = (size_t)c.input_channels * T, audio_item = (size_t)T * v->hop;
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-        rc = ffgan_forward_chunk(e, mel + b0 * mel_item, audio + b0 * audio_item, std::min(chunk, B - b0), T, nullptr, s);
-        if (rc) return rc;
-    }
-    return ST_OK;
+    return vocoder_forward(kFfganKind, e, mel, audio, B, T, stream);
 }
 
 int st_ffgan_forward_ragged(st_engine* e, const float* mel, const int64_t* lengths, float* audio, int B, int T, void* stream) {
-    int rc = check_handle(e, KIND_FFGAN); if (rc) return rc;
-    if ((rc = check_finalized(e))) return rc;
-    if (!mel || !audio) return e->fail(ST_ERR_INVALID, "null tensor pointer");
-    if (!lengths) return e->fail(ST_ERR_INVALID, "null lengths");
-    if ((rc = check_sizes(e, B, T))) return rc;
-    FfganState* v = state_of<FfganState>(e);
-    const st_ffgan_config& c = v->cfg;
-    const int64_t max_rows = ffgan_max_rows(c);
-    // validate everything and plan the chunks before touching the device: whole utterances, as many as keep the head's level tensors
-    // of the packed rows within kFfganHeadBytes (one utterance always runs), the packed rows within max_rows and the grid within 65535 items
-    if (T > kFfganMaxT) return e->fail(ST_ERR_INVALID, "T too large: one utterance exceeds the vocoder's row indexing");
-    for (int b = 0; b < B; ++b)
-        if (lengths[b] < 1 || lengths[b] > T)
-            return e->fail(ST_ERR_INVALID, "lengths[" + std::to_string(b) + "] = " + std::to_string(lengths[b]) + " must be in [1, T = " + std::to_string(T) + "]");
-    for (int b = 0; b < B; ++b)
-        if (lengths[b] > max_rows)
-            return e->fail(ST_ERR_INVALID, "lengths[" + std::to_string(b) + "] too large: one utterance exceeds the vocoder's row indexing");
-    const int64_t head_rows = std::max<int64_t>(1, kFfganHeadBytes / (ffgan_level_elems(c) * ffgan_head_sample_bytes(v)));
-    std::vector<int> starts;          // first utterance of every chunk, then B
-    int64_t rows = 0;
-    for (int b = 0; b < B; ++b) {
-        if (b == 0 || rows + lengths[b] > head_rows || rows + lengths[b] > max_rows || b - starts.back() >= 65535) { starts.push_back(b); rows = 0; }
-        rows += lengths[b];
-    }
-    starts.push_back(B);
-    const int n_chunks = (int)starts.size() - 1;
-    if (n_chunks > 1 && e->capture) return e->fail(ST_ERR_INVALID, "debug capture holds whole-batch tensors: this batch runs in chunks");
-    HIPCHK(e, hipSetDevice(e->device));
-    hipStream_t s = (hipStream_t)stream;
-    int slot = 0;
-    if ((rc = v->slots.acquire(e, B, &slot))) return rc;
-    std::vector<RaggedChunk> chunks(n_chunks);
-    for (int k = 0; k < n_chunks; ++k)      // one depthwise group per packed row
-        chunks[k] = v->slots.fill(slot, lengths, starts[k], starts[k + 1], [](int64_t) { return 1; });
-    if ((rc = v->slots.upload(e, slot, B, s))) return rc;
-    const size_t mel_item = (size_t)c.input_channels * T, audio_item = (size_t)T * v->hop;
-    for (int k = 0; k < n_chunks && rc == ST_OK; ++k)
-        rc = ffgan_forward_chunk(e, mel + starts[k] * mel_item, audio + starts[k] * audio_item, starts[k + 1] - starts[k], T, &chunks[k], s);
-    hipError_t he = v->slots.record(slot, s);       // also after a failed chunk: the copy and the launches before it read the slot
-    if (rc) return rc;
-    HIPCHK(e, he);
-    return ST_OK;
+    return vocoder_forward_ragged(kFfganKind, e, mel, lengths, audio, B, T, stream);
 }
 
 }  // extern "C"

@@ -111,13 +111,7 @@ static int pd_forward(st_engine* e, const float* x, float* const* fmaps, int B, 
     return ST_OK;
 }
 
-static int pd_entry(st_engine* e, const float* x, float* const* fmaps, int B, int T, PdGeom* g) {
-    int rc = check_handle(e, KIND_PERIOD_DISC); if (rc) return rc;
-    if ((rc = check_finalized(e))) return rc;
-    if (!x || !fmaps) return e->fail(ST_ERR_INVALID, "null tensor pointer");
-    for (int i = 0; i < kPdLayers; ++i) if (!fmaps[i]) return e->fail(ST_ERR_INVALID, "null tensor pointer");
-    return pd_check(e, B, T, g);
-}
+static const DiscKind<PdGeom> kPdKind = {KIND_PERIOD_DISC, kPdLayers, "st_period_disc_train", pd_check, pd_forward};
 
 }  // namespace sthost
 
@@ -158,33 +152,21 @@ int st_period_disc_fmap_shape(const st_engine* e, int T, int index, int64_t* cha
 }
 
 int st_period_disc_forward(st_engine* e, const float* x, float* const* fmaps, int B, int T, void* stream) {
-    PdGeom g;
-    int rc = pd_entry(e, x, fmaps, B, T, &g); if (rc) return rc;
-    HIPCHK(e, hipSetDevice(e->device));
-    return pd_forward(e, x, fmaps, B, g, nullptr, (hipStream_t)stream);
+    return disc_forward(kPdKind, e, x, fmaps, B, T, false, stream);
 }
 
 int st_period_disc_train_forward(st_engine* e, const float* x, float* const* fmaps, int B, int T, void* stream) {
-    PdGeom g;
-    int rc = pd_entry(e, x, fmaps, B, T, &g); if (rc) return rc;
-    HIPCHK(e, hipSetDevice(e->device));
-    SdTrain* st = state_of<PdState>(e)->begin();
-    if ((rc = pd_forward(e, x, fmaps, B, g, st, (hipStream_t)stream))) return rc;
-    sd_train_commit(st, B, T, 0.0f, 0, false);
-    return ST_OK;
+    return disc_forward(kPdKind, e, x, fmaps, B, T, true, stream);
 }
 
 int st_period_disc_train_backward(st_engine* e, const float* const* d_fmaps, float* d_x, float* grad_flat, int B, int T, void* stream) {
-    int rc = check_handle(e, KIND_PERIOD_DISC); if (rc) return rc;
-    if (!d_fmaps) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     PdGeom g;
-    if ((rc = pd_check(e, B, T, &g))) return rc;
-    PdState* pd = state_of<PdState>(e);
-    SdTrain* st = &pd->held;
-    if ((rc = sd_train_check(e, *st, "st_period_disc_train", "T", -1, B, T))) return rc;
-    if (!d_x && !grad_flat) return ST_OK;
-    HIPCHK(e, hipSetDevice(e->device));
-    hipStream_t s = (hipStream_t)stream;
+    DiscBackward bw;
+    int rc = disc_backward_begin(kPdKind, e, d_fmaps, d_x, grad_flat, B, T, stream, &g, &bw);
+    if (rc || !bw.st) return rc;
+    const PdState* pd = state_of<PdState>(e);
+    SdTrain* st = bw.st;
+    hipStream_t s = bw.s;
     const int p = g.p;
     const float slope = pd->cfg.lrelu_slope;
 
@@ -194,26 +176,17 @@ int st_period_disc_train_backward(st_engine* e, const float* const* d_fmaps, flo
     const float* a[kPdLayers];
     for (int i = 0; i < kPdLayers; ++i) a[i] = act + A.a[i];
     // scratch: two gradient planes, one weight-shaped plane, the split-K planes, layer 0's partial sums
-    size_t ws = 0, wmax = 0;
-    if (grad_flat) {
+    size_t ws = 0;
+    if (grad_flat)
         for (int i = 1; i < kPdLayers; ++i) ws = std::max(ws, pd_wgrad_scratch_floats(B, kPdCh[i], kPdCh[i + 1], g.H[i + 1], p));
-        for (int i = 0; i <= kPdLayers; ++i) wmax = std::max(wmax, (size_t)pd_wnumel(i));
-    }
     FloatArena ar;
-    const size_t o_d0 = ar.want(A.widest), o_d1 = ar.want(A.widest), o_dw = ar.want(wmax), o_ws = ar.want(ws),
+    const size_t o_d0 = ar.want(A.widest), o_d1 = ar.want(A.widest), o_dw = ar.want(bw.wmax), o_ws = ar.want(ws),
                  o_l0 = ar.want(grad_flat ? pd_l0_scratch_floats(B, g.H[1], p) : 0);
     if ((rc = sd_train_grow(e, &st->scr, &st->scr_cap, ar.off * 4))) return rc;
     float* scr = (float*)st->scr;
-    float* D = scr + o_d0; float* Dn = scr + o_d1; float* dW = scr + o_dw; float* wsp = scr + o_ws; float* l0p = scr + o_l0;
-
-    std::map<std::string, int64_t> goff;
-    train_grad_layout(e, &goff);
-    auto G = [&](const std::string& n) { return grad_flat + goff.at(n); };
-    auto wn_bwd = [&](int i) {      // d w (in dW) -> d g, d v
-        const int co = i < kPdLayers ? kPdCh[i + 1] : 1;
-        return launch_pd_weight_norm_bwd(dW, P(e, pd_name(i) + kWnV), P(e, pd_name(i) + kWnG), G(pd_name(i) + kWnV), G(pd_name(i) + kWnG), co,
-                                         (int)(pd_wnumel(i) / co), s);
-    };
+    float* D = scr + o_d0; float* Dn = scr + o_d1; float* dW = bw.dW = scr + o_dw; float* wsp = scr + o_ws; float* l0p = scr + o_l0;
+    auto G = [&](const std::string& n) { return bw.G(n); };
+    auto wn_bwd = [&](int i) { return bw.wn_bwd(e, i); };
     // conv_post: the logits' gradient d_fmaps[4] (B, 1, H, p)
     const int C4 = kPdCh[kPdLayers], H4 = g.H[kPdLayers];
     const float* dy = d_fmaps[4];

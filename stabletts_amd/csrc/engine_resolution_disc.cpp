@@ -146,13 +146,7 @@ static int rd_forward(st_engine* e, const float* x, float* const* fmaps, int B, 
     return ST_OK;
 }
 
-static int rd_entry(st_engine* e, const float* x, float* const* fmaps, int B, int T, RdGeom* g) {
-    int rc = check_handle(e, KIND_RESOLUTION_DISC); if (rc) return rc;
-    if ((rc = check_finalized(e))) return rc;
-    if (!x || !fmaps) return e->fail(ST_ERR_INVALID, "null tensor pointer");
-    for (int i = 0; i < kRdMaps; ++i) if (!fmaps[i]) return e->fail(ST_ERR_INVALID, "null tensor pointer");
-    return rd_check(e, B, T, g);
-}
+static const DiscKind<RdGeom> kRdKind = {KIND_RESOLUTION_DISC, kRdMaps, "st_resolution_disc_train", rd_check, rd_forward};
 
 }  // namespace sthost
 
@@ -219,33 +213,21 @@ int st_resolution_disc_wgrad_planes(const st_engine* e, int B, int T, int band, 
 }
 
 int st_resolution_disc_forward(st_engine* e, const float* x, float* const* fmaps, int B, int T, void* stream) {
-    RdGeom g;
-    int rc = rd_entry(e, x, fmaps, B, T, &g); if (rc) return rc;
-    HIPCHK(e, hipSetDevice(e->device));
-    return rd_forward(e, x, fmaps, B, g, nullptr, (hipStream_t)stream);
+    return disc_forward(kRdKind, e, x, fmaps, B, T, false, stream);
 }
 
 int st_resolution_disc_train_forward(st_engine* e, const float* x, float* const* fmaps, int B, int T, void* stream) {
-    RdGeom g;
-    int rc = rd_entry(e, x, fmaps, B, T, &g); if (rc) return rc;
-    HIPCHK(e, hipSetDevice(e->device));
-    SdTrain* st = state_of<RdState>(e)->begin();
-    if ((rc = rd_forward(e, x, fmaps, B, g, st, (hipStream_t)stream))) return rc;
-    sd_train_commit(st, B, T, 0.0f, 0, false);
-    return ST_OK;
+    return disc_forward(kRdKind, e, x, fmaps, B, T, true, stream);
 }
 
 int st_resolution_disc_train_backward(st_engine* e, const float* const* d_fmaps, float* d_x, float* grad_flat, int B, int T, void* stream) {
-    int rc = check_handle(e, KIND_RESOLUTION_DISC); if (rc) return rc;
-    if (!d_fmaps) return e->fail(ST_ERR_INVALID, "null tensor pointer");
     RdGeom g;
-    if ((rc = rd_check(e, B, T, &g))) return rc;
-    RdState* rd = state_of<RdState>(e);
-    SdTrain* st = &rd->held;
-    if ((rc = sd_train_check(e, *st, "st_resolution_disc_train", "T", -1, B, T))) return rc;
-    if (!d_x && !grad_flat) return ST_OK;
-    HIPCHK(e, hipSetDevice(e->device));
-    hipStream_t s = (hipStream_t)stream;
+    DiscBackward bw;
+    int rc = disc_backward_begin(kRdKind, e, d_fmaps, d_x, grad_flat, B, T, stream, &g, &bw);
+    if (rc || !bw.st) return rc;
+    const RdState* rd = state_of<RdState>(e);
+    SdTrain* st = bw.st;
+    hipStream_t s = bw.s;
     const float slope = rd->cfg.lrelu_slope;
     const int Fr = g.frames, L4 = kRdLayers - 1;
 
@@ -256,32 +238,24 @@ int st_resolution_disc_train_backward(st_engine* e, const float* const* d_fmaps,
     for (int c = 0; c < kRdBands; ++c) for (int i = 0; i < kRdLayers; ++i) a[c][i] = act + A.a[c][i];
     // scratch: two gradient planes per band, the range sums of the bias / conv_post reductions (no band is wider than the spectrum),
     // one weight-shaped plane, the split-K planes, the spectrum's gradient and the frame rows
-    size_t ws = 0, wmax = 0;
-    if (grad_flat) {
+    size_t ws = 0;
+    if (grad_flat)
         for (int c = 0; c < kRdBands; ++c)
             for (int i = 0; i < kRdLayers; ++i) ws = std::max(ws, rd_wgrad_scratch_floats(B, i == 0 ? 2 : kRdCh, Fr, g.Wd[c][i], i == L4 ? 3 : 9));
-        for (int k = 0; k < kRdConvs; ++k) wmax = std::max(wmax, (size_t)rd_wnumel(k));
-    }
     FloatArena ar;
     size_t o_d[kRdBands][2];
     for (int c = 0; c < kRdBands; ++c) for (int j = 0; j < 2; ++j) o_d[c][j] = ar.want((size_t)B * kRdCh * Fr * g.Wd[c][0]);
     const size_t o_red = ar.want(grad_flat ? std::max(rd_bias_scratch_floats(B, Fr, g.bins),
                                                        rd_post_wgrad_scratch_floats(B, Fr, g.off[kRdBands])) : 0);
-    const size_t o_dw = ar.want(wmax), o_ws = ar.want(ws), o_dspec = ar.want(d_x ? (size_t)B * 2 * Fr * g.bins : 0),
+    const size_t o_dw = ar.want(bw.wmax), o_ws = ar.want(ws), o_dspec = ar.want(d_x ? (size_t)B * 2 * Fr * g.bins : 0),
                  o_rows = ar.want(d_x ? (size_t)B * Fr * g.W : 0);
     if ((rc = sd_train_grow(e, &st->scr, &st->scr_cap, ar.off * 4))) return rc;
     float* scr = (float*)st->scr;
     float* D[kRdBands]; float* Dn[kRdBands];
     for (int c = 0; c < kRdBands; ++c) { D[c] = scr + o_d[c][0]; Dn[c] = scr + o_d[c][1]; }
-    float* dW = scr + o_dw; float* wsp = scr + o_ws; float* red = scr + o_red;      // red: the range sums of the O(N) reductions
-
-    std::map<std::string, int64_t> goff;
-    train_grad_layout(e, &goff);
-    auto G = [&](const std::string& n) { return grad_flat + goff.at(n); };
-    auto wn_bwd = [&](int k) {      // d w (in dW) -> d g, d v
-        return launch_pd_weight_norm_bwd(dW, P(e, rd_name(k) + kWnV), P(e, rd_name(k) + kWnG), G(rd_name(k) + kWnV), G(rd_name(k) + kWnG), rd_cout(k),
-                                         (int)(rd_wnumel(k) / rd_cout(k)), s);
-    };
+    float* dW = bw.dW = scr + o_dw; float* wsp = scr + o_ws; float* red = scr + o_red;      // red: the range sums of the O(N) reductions
+    auto G = [&](const std::string& n) { return bw.G(n); };
+    auto wn_bwd = [&](int k) { return bw.wn_bwd(e, k); };
     // conv_post: the logits' gradient d_fmaps[20] (B, 1, frames, Wc)
     RdPostArgs pa{};
     for (int c = 0; c < kRdBands; ++c) { pa.in[c] = a[c][L4]; pa.addg[c] = d_fmaps[c * L4 + L4 - 1]; pa.dpre[c] = D[c]; }

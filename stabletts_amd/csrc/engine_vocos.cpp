@@ -4,11 +4,11 @@
 // layer scale + residual, head) run on the implicit-GEMM kernels of the decoder over the FLATTENED rows of the batch
 // (taps = 1: rows are independent); everything between them is in vocos_kernels.hip.
 #include "engine_internal.h"
-#include "utt_slots.h"
+#include "engine_vocoder.h"
 #include "vocos_launch.h"
 
 #include <algorithm>
-#include <cstring>
+#include <limits>
 #include <string>
 
 using namespace st;
@@ -24,6 +24,7 @@ struct VocosState : HeldState {      // (held: st_vocos_train_forward's activati
     Conv embed, head;
     std::vector<Conv> pw1, pw2;
     UttSlots slots;      // ragged calls: the utterance tables (utt_slots.h)
+    int grid_y = 0;      // the device's hipDeviceAttributeMaxGridDimY: the dense im2col and overlap-add kernels put the utterance on grid.y
 };
 
 static std::string vblk(int i) { return "backbone.convnext." + std::to_string(i) + "."; }
@@ -152,6 +153,10 @@ int st_create_vocoder(const st_vocos_config* cfg, int device, st_engine** out) {
         delete e;
         return bad("hipMalloc failed", ST_ERR_HIP);
     }
+    if (hipDeviceGetAttribute(&state_of<VocosState>(e)->grid_y, hipDeviceAttributeMaxGridDimY, e->device) != hipSuccess) {
+        delete e;
+        return bad("hipDeviceGetAttribute failed", ST_ERR_HIP);
+    }
     *out = e;
     return ST_OK;
 }
@@ -178,12 +183,7 @@ static int vocos_forward_chunk(st_engine* e, const float* mel, float* audio, int
     void* a16 = e->ws + o_a16; float* x = (float*)(e->ws + o_x); void* h16 = e->ws + o_h16; void* h16lo = e->ws + o_h16lo; void* u16 = e->ws + o_u16;
     float* head = (float*)(e->ws + o_head); float* frames = (float*)(e->ws + o_fr);
 
-    auto args = [&](const Conv& cv) {
-        ConvGemmArgs a; memset(&a, 0, sizeof(a));
-        a.w = cv.w; a.bias = cv.bias; a.cout = cv.cout; a.T = (int)R; a.n_items = 1;     // flattened rows
-        a.a0_mod = 1; a.a1_mod = 1; a.mask_mod = 1; a.zeros = e->zeros;
-        return a;
-    };
+    auto args = [&](const Conv& cv) { return flat_gemm_args(e, cv, R); };
     const bool cap = e->capture;
     {   // embed (backbone.py:51) + LayerNorm (:52)
         ProfScope ps(e, s, PC_PRENET, 2.0 * R * C * 7.0 * M);
@@ -241,69 +241,20 @@ static int64_t vocos_max_rows(const st_vocos_config& c) {
     return (((int64_t)1 << 31) - 1) / (widest * 2);
 }
 
+// dense: the utterance on grid.y; ragged: the padded frames of one overlap-add launch
+static VocoderGeom vocos_geom(st_engine* e) {
+    VocosState* v = state_of<VocosState>(e);
+    const int64_t max_rows = vocos_max_rows(v->cfg), no_cap = std::numeric_limits<int64_t>::max();
+    return {{max_rows, v->grid_y, 0, 0}, {max_rows, no_cap, kVocMaxPaddedFrames, 0}, v->cfg.input_channels, v->cfg.hop_length, &v->slots};
+}
+static const VocoderKind kVocosKind = {KIND_VOCODER, "the vocoder's 32-bit row indexing", 0, vocos_geom, voc_dw_frames, vocos_forward_chunk};
+
 int st_vocos_forward(st_engine* e, const float* mel, float* audio, int B, int T, void* stream) {
-    int rc = check_handle(e, KIND_VOCODER); if (rc) return rc;
-    if ((rc = check_finalized(e))) return rc;
-    if (!mel || !audio) return e->fail(ST_ERR_INVALID, "null tensor pointer");
-    if ((rc = check_sizes(e, B, T))) return rc;
-    const st_vocos_config& c = state_of<VocosState>(e)->cfg;
-    const int64_t max_rows = vocos_max_rows(c);
-    if (T > max_rows) return e->fail(ST_ERR_INVALID, "T too large: one utterance exceeds the vocoder's 32-bit row indexing");
-    HIPCHK(e, hipSetDevice(e->device));
-    int grid_y = 0;       // the im2col and overlap-add kernels put the utterance on grid.y
-    HIPCHK(e, hipDeviceGetAttribute(&grid_y, hipDeviceAttributeMaxGridDimY, e->device));
-    const int chunk = (int)std::min<int64_t>({(int64_t)B, max_rows / T, (int64_t)grid_y});
-    if (chunk < B && e->capture) return e->fail(ST_ERR_INVALID, "debug capture holds whole-batch tensors: this batch runs in chunks");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t mel_item = (size_t)c.input_channels * T, audio_item = (size_t)T * c.hop_length;
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-        rc = vocos_forward_chunk(e, mel + b0 * mel_item, audio + b0 * audio_item, std::min(chunk, B - b0), T, nullptr, s);
-        if (rc) return rc;
-    }
-    return ST_OK;
+    return vocoder_forward(kVocosKind, e, mel, audio, B, T, stream);
 }
 
 int st_vocos_forward_ragged(st_engine* e, const float* mel, const int64_t* lengths, float* audio, int B, int T, void* stream) {
-    int rc = check_handle(e, KIND_VOCODER); if (rc) return rc;
-    if ((rc = check_finalized(e))) return rc;
-    if (!mel || !audio) return e->fail(ST_ERR_INVALID, "null tensor pointer");
-    if (!lengths) return e->fail(ST_ERR_INVALID, "null lengths");
-    if ((rc = check_sizes(e, B, T))) return rc;
-    VocosState* v = state_of<VocosState>(e);
-    const st_vocos_config& c = v->cfg;
-    const int64_t max_rows = vocos_max_rows(c);
-    // validate everything and plan the chunks before touching the device: whole utterances, as many as keep the packed rows
-    // within max_rows (and the padded frames within one overlap-add launch)
-    for (int b = 0; b < B; ++b)
-        if (lengths[b] < 1 || lengths[b] > T)
-            return e->fail(ST_ERR_INVALID, "lengths[" + std::to_string(b) + "] = " + std::to_string(lengths[b]) + " must be in [1, T = " + std::to_string(T) + "]");
-    for (int b = 0; b < B; ++b)
-        if (lengths[b] > max_rows)
-            return e->fail(ST_ERR_INVALID, "lengths[" + std::to_string(b) + "] too large: one utterance exceeds the vocoder's 32-bit row indexing");
-    if (T > kVocMaxPaddedFrames) return e->fail(ST_ERR_INVALID, "T too large: the padded audio of one utterance exceeds one launch");
-    std::vector<int> starts;          // first utterance of every chunk, then B
-    int64_t rows = 0;
-    for (int b = 0; b < B; ++b) {
-        if (b == 0 || rows + lengths[b] > max_rows || (int64_t)(b - starts.back() + 1) * T > kVocMaxPaddedFrames) { starts.push_back(b); rows = 0; }
-        rows += lengths[b];
-    }
-    starts.push_back(B);
-    const int n_chunks = (int)starts.size() - 1;
-    if (n_chunks > 1 && e->capture) return e->fail(ST_ERR_INVALID, "debug capture holds whole-batch tensors: this batch runs in chunks");
-    HIPCHK(e, hipSetDevice(e->device));
-    hipStream_t s = (hipStream_t)stream;
-    int slot = 0;
-    if ((rc = v->slots.acquire(e, B, &slot))) return rc;
-    std::vector<RaggedChunk> chunks(n_chunks);
-    for (int k = 0; k < n_chunks; ++k) chunks[k] = v->slots.fill(slot, lengths, starts[k], starts[k + 1], voc_dw_frames);
-    if ((rc = v->slots.upload(e, slot, B, s))) return rc;
-    const size_t mel_item = (size_t)c.input_channels * T, audio_item = (size_t)T * c.hop_length;
-    for (int k = 0; k < n_chunks && rc == ST_OK; ++k)
-        rc = vocos_forward_chunk(e, mel + starts[k] * mel_item, audio + starts[k] * audio_item, starts[k + 1] - starts[k], T, &chunks[k], s);
-    hipError_t he = v->slots.record(slot, s);       // also after a failed chunk: the copy and the launches before it read the slot
-    if (rc) return rc;
-    HIPCHK(e, he);
-    return ST_OK;
+    return vocoder_forward_ragged(kVocosKind, e, mel, lengths, audio, B, T, stream);
 }
 
 }  // extern "C"

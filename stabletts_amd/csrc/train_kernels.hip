@@ -21,12 +21,7 @@ DropCfg make_drop(float p, unsigned long long seed, int salt) {
     return d;
 }
 
-__global__ __launch_bounds__(256) void drop_tables_kernel(unsigned long long seed, int n_rows, int n_colpairs, unsigned* rowh, unsigned* colh) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_rows) rowh[i] = drop_rowh(seed, (unsigned)i);
-    if (i < n_colpairs) colh[i] = drop_colh(seed, (unsigned)i);
-}
-// ... for every attention site of one forward in ONE launch (grid.y = site); the backward re-reads the tables
+// the dropout hash tables of every attention site of one forward in ONE launch (grid.y = site); the backward re-reads the tables
 __global__ __launch_bounds__(256) void drop_tables_multi_kernel(DropSeeds sd, int n_rows, int n_colpairs, unsigned* rowh, unsigned* colh,
                                                                 size_t row_stride, size_t col_stride) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -39,11 +34,6 @@ hipError_t launch_drop_tables_multi(const DropSeeds& sd, int n_sites, int n_rows
     if (n_sites < 1 || n_sites > 16) return hipErrorInvalidValue;
     const int n = n_rows > n_colpairs ? n_rows : n_colpairs;
     hipLaunchKernelGGL(drop_tables_multi_kernel, dim3((n + 255) / 256, n_sites), dim3(256), 0, s, sd, n_rows, n_colpairs, rowh, colh, row_stride, col_stride);
-    return hipGetLastError();
-}
-hipError_t launch_drop_tables(const DropCfg& d, int n_rows, int n_colpairs, unsigned* rowh, unsigned* colh, hipStream_t s) {
-    const int n = n_rows > n_colpairs ? n_rows : n_colpairs;
-    hipLaunchKernelGGL(drop_tables_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d.seed, n_rows, n_colpairs, rowh, colh);
     return hipGetLastError();
 }
 
@@ -241,26 +231,6 @@ hipError_t launch_reduce_sites(const RedSites& S, int n_items, int chunks, hipSt
     int total = 0;
     for (int q = 0; q < S.n; ++q) { if (S.s[q].K < 1 || S.s[q].K > 2) return hipErrorInvalidValue; total += S.s[q].K; }
     hipLaunchKernelGGL(reduce_sites_kernel, dim3(total, n_items), dim3(256), 0, s, S, chunks);
-    return hipGetLastError();
-}
-
-struct RedOff { int off[4]; };
-__global__ __launch_bounds__(256) void reduce_parts_kernel(const float* part, int chunks, int K, float* out, int out_stride,
-                                                            RedOff off, int accumulate, const float* unscale) {
-    const int k = blockIdx.x, n = blockIdx.y, ch = threadIdx.x;
-    float v = 0.f;
-    for (int c = 0; c < chunks; ++c) v += part[(((size_t)n * chunks + c) * K + k) * 256 + ch];
-    if (unscale) v *= unscale[1];
-    float* dst = out + (size_t)n * out_stride + off.off[k] + ch;
-    *dst = accumulate ? *dst + v : v;
-}
-
-hipError_t launch_reduce_parts(const float* part, int n_items, int chunks, int K, float* out, int out_stride,
-                               const int* out_off, int accumulate, const float* unscale, hipStream_t s) {
-    if (K < 1 || K > 4) return hipErrorInvalidValue;
-    RedOff off;
-    for (int k = 0; k < 4; ++k) off.off[k] = k < K ? out_off[k] : 0;     // out_off is a HOST array
-    hipLaunchKernelGGL(reduce_parts_kernel, dim3(K, n_items), dim3(256), 0, s, part, chunks, K, out, out_stride, off, accumulate, unscale);
     return hipGetLastError();
 }
 
@@ -490,27 +460,6 @@ hipError_t launch_qkv_grad_scales(const float* dq, const float* dk, const float*
     hipLaunchKernelGGL(qkv_scales_kernel, dim3(1), dim3(1), 0, s, bits3, gsc, qs);
     return hipGetLastError();
 }
-__global__ void grad_rescale_kernel(const unsigned* bits, float* sc) {
-    const float m = __uint_as_float(*bits);
-    float f = 1.0f;
-    if (m > 0.f && (m < 2.0f || m >= 512.0f)) {
-        int ex = 5 - (int)floorf(log2f(m));
-        const int cur = (int)floorf(log2f(sc[0]));
-        if (cur + ex > 100) ex = 100 - cur;              // keep the total scale a finite fp32 power of two
-        if (cur + ex < -100) ex = -100 - cur;
-        f = exp2f((float)ex);
-    }
-    sc[2] = f;
-    sc[0] *= f; sc[1] = 1.0f / sc[0];
-}
-hipError_t launch_grad_rescale(const float* g, int64_t n, unsigned* bits, float* sc, hipStream_t s) {
-    hipError_t e = hipMemsetAsync(bits, 0, 4, s);
-    if (e != hipSuccess) return e;
-    int grid = (int)((n / 4 + 255) / 256); if (grid > 512) grid = 512; if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(absmax_kernel, dim3(grid), dim3(256), 0, s, g, n, bits);
-    hipLaunchKernelGGL(grad_rescale_kernel, dim3(1), dim3(1), 0, s, bits, sc);
-    return hipGetLastError();
-}
 // max |x| into a cell GROUP (publish_block_max): the fall-back of a re-centring point whose producer is a GEMM epilogue
 __global__ __launch_bounds__(256) void absmax_cells_kernel(const float* x, int64_t n, unsigned* cells) {
     float m = 0.f;
@@ -560,21 +509,6 @@ hipError_t launch_recentre(float* a, int64_t n, unsigned* cells, bool have_max, 
     hipLaunchKernelGGL(rescale_apply_kernel, dim3(grid), dim3(256), 0, s, a, n / 4, cells, sc, sc_next);
     return hipGetLastError();
 }
-__global__ __launch_bounds__(256) void scale_by_kernel(float* a, int64_t n4, const float* sc) {
-    const float f = sc[2];
-    if (f == 1.0f) return;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        float4 v = *(float4*)(a + 4 * i);
-        v.x *= f; v.y *= f; v.z *= f; v.w *= f;
-        *(float4*)(a + 4 * i) = v;
-    }
-}
-hipError_t launch_scale_by(float* a, int64_t n, const float* sc, hipStream_t s) {
-    if (n & 3) return hipErrorInvalidValue;
-    int grid = (int)((n / 4 + 255) / 256); if (grid > 2048) grid = 2048; if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(scale_by_kernel, dim3(grid), dim3(256), 0, s, a, n / 4, sc);
-    return hipGetLastError();
-}
 __global__ __launch_bounds__(256) void scale_inplace_kernel(float* a, int64_t n, const float* sc) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) a[i] *= sc[1];
@@ -584,14 +518,6 @@ hipError_t launch_unscale_inplace(float* a, int64_t n, const float* sc, hipStrea
     return hipGetLastError();
 }
 
-__global__ __launch_bounds__(256) void add_inplace_kernel(float* a, const float* b, int64_t n) {
-    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (i >= n) return;
-    float4 x = *(const float4*)(a + i);
-    const float4 y = *(const float4*)(b + i);
-    x.x += y.x; x.y += y.y; x.z += y.z; x.w += y.w;
-    *(float4*)(a + i) = x;
-}
 __global__ __launch_bounds__(256) void add_rescaled_kernel(float* a, const float* b, int64_t n, const float* sc, const float* sc_b, unsigned* amax) {
     float mx = 0.f;
     for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * blockDim.x * 4) {
@@ -608,15 +534,6 @@ hipError_t launch_add_rescaled(float* a, const float* b, int64_t n, const float*
     if (n & 3) return hipErrorInvalidValue;
     int grid = (int)((n / 4 + 255) / 256); if (grid > 2048) grid = 2048; if (grid < 1) grid = 1;
     hipLaunchKernelGGL(add_rescaled_kernel, dim3(grid), dim3(256), 0, s, a, b, n, sc, sc_b, amax);
-    return hipGetLastError();
-}
-__global__ void copy_scalars_kernel(float* dst, const float* src, int n) { if ((int)threadIdx.x < n) dst[threadIdx.x] = src[threadIdx.x]; }
-hipError_t launch_copy_scalars(float* dst, const float* src, int n, hipStream_t s) {
-    hipLaunchKernelGGL(copy_scalars_kernel, dim3(1), dim3(64), 0, s, dst, src, n);
-    return hipGetLastError();
-}
-hipError_t launch_add_inplace(float* a, const float* b, int64_t n, hipStream_t s) {
-    hipLaunchKernelGGL(add_inplace_kernel, dim3((int)((n / 4 + 255) / 256)), dim3(256), 0, s, a, b, n);
     return hipGetLastError();
 }
 

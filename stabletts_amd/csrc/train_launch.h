@@ -35,29 +35,23 @@ hipError_t launch_silu_drop(int dtype, const void* a16, void* u16, const float* 
 // ---------------------------------------------------------------- backward elementwise + per-item channel reductions
 // Every kernel below walks blocks of kRedRows frames of one item; per-(item, channel) sums are accumulated in
 // registers (a lane owns the same 4 channels for every frame), combined per block and written to
-// part[item][chunk][k][256]; launch_reduce_parts adds the chunks in order (deterministic, no atomics).
+// part[item][chunk][k][256]; launch_reduce_sites adds the chunks in order (deterministic, no atomics).
 constexpr int kRedRows = 32;
 inline int red_chunks(int T) { return (T + kRedRows - 1) / kRedRows; }
-// out[n][k][256] (+)= sum_chunk part[n][chunk][k][256]
-hipError_t launch_reduce_parts(const float* part, int n_items, int chunks, int K, float* out, int out_stride,
-                               const int* out_off, int accumulate, const float* unscale, hipStream_t s);
 
 // Gradient scaling (see train_kernels.hip): sc[0] = power-of-two scale that puts max |g| at ~2^8, sc[1] = 1 / sc[0].
 // Kernels that take `scale` multiply by sc[0]; kernels that take `unscale` multiply by sc[1] (nullptr: 1).
 hipError_t launch_grad_scale(const float* g, int64_t n, unsigned* bits, float* sc, hipStream_t s);
 hipError_t launch_unscale_inplace(float* a, int64_t n, const float* sc, hipStream_t s);
-// Block-boundary re-centring of the pass-wide scale: if max |g| (g = the running fp32 gradient, in scaled units) has left
-// [2^4, 2^12), sc[2] = the power of two that brings it back to ~2^8 (else 1), and sc[0] *= sc[2], sc[1] = 1 / sc[0].
-// launch_scale_by then multiplies a tensor that lives in scaled units by sc[2] (returns at once when it is 1).
-hipError_t launch_grad_rescale(const float* g, int64_t n, unsigned* bits, float* sc, hipStream_t s);
-hipError_t launch_scale_by(float* a, int64_t n, const float* sc, hipStream_t s);
-// The same re-centring as ONE launch (+ one when no producer published the maximum): `cells` is a group of kMaxCells maxima 64
-// bytes apart (zeroed by the caller; producers: ln_bwd / add_rescaled `amax`, or the absmax pass run here when !have_max);
-// a *= f and sc_next = {sc[0] f, 1 / (sc[0] f), f}.  sc is only read: kernels enqueued later are handed sc_next.
+// Block-boundary re-centring of the pass-wide scale: if max |a| (a = the running fp32 gradient, in scaled units) has left
+// [2^4, 2^12), f = the power of two that brings it back to ~2^8 (else 1).  ONE launch (+ one when no producer published the
+// maximum): `cells` is a group of kMaxCells maxima 64 bytes apart (zeroed by the caller; producers: ln_bwd / add_rescaled `amax`,
+// or the absmax pass run here when !have_max); a *= f and sc_next = {sc[0] f, 1 / (sc[0] f), f}.  sc is only read: kernels
+// enqueued later are handed sc_next.
 constexpr int kMaxCells = 16;
 constexpr int kMaxCellWords = kMaxCells * 16;
 hipError_t launch_recentre(float* a, int64_t n, unsigned* cells, bool have_max, const float* sc, float* sc_next, hipStream_t s);
-// every per-(item, channel) sum of one backward block in one launch (replaces one launch_reduce_parts per row kernel)
+// every per-(item, channel) sum of one backward block in one launch: out[n][off[k] ..][256] = sum_chunk part[n][chunk][k][256]
 struct RedSite { const float* part; int K; float* out; int out_stride; int off[2]; const float* unscale; };
 struct RedSites { RedSite s[6]; int n; };
 hipError_t launch_reduce_sites(const RedSites& S, int n_items, int chunks, hipStream_t s);
@@ -91,14 +85,12 @@ hipError_t launch_emb_bwd(const float* dX, int C, const int* ids, int64_t R, int
 // dA16 = dU * mask * dropout * SiLU'(a16)   over [rows][F]
 hipError_t launch_silu_bwd(int dtype, const float* dU, const void* a16, const float* mask, int mask_mod, int T, int F,
                            int64_t rows, DropCfg drop, void* dA16, hipStream_t s);
-// y16 = to16(x * mask?)  /  y = a + b  /  fp32 row-slices
+// y16 = to16(x * mask?)
 hipError_t launch_cast16(int dtype, const float* x, const float* mask, int mask_mod, int T, int C, int64_t rows,
                          const float* scale, void* y16, hipStream_t s);
-hipError_t launch_add_inplace(float* a, const float* b, int64_t n, hipStream_t s);
 // a += b * sc[0] / sc_b[0]: b was written when the pass-wide scale was sc_b[0], a lives at the current scale sc[0] (both powers of two)
 // amax != null: also publishes max |a| after the add into the cell group (launch_recentre's input)
 hipError_t launch_add_rescaled(float* a, const float* b, int64_t n, const float* sc, const float* sc_b, unsigned* amax, hipStream_t s);
-hipError_t launch_copy_scalars(float* dst, const float* src, int n, hipStream_t s);
 
 // ---------------------------------------------------------------- weight gradient as a forward GEMM
 // dW[co][j][ci] = sum_{n,t} dY[n][t][co] * X[n][t + j - taps/2][ci].  With K-contiguous transposed copies
@@ -115,7 +107,7 @@ hipError_t launch_wgrad_dyt(int dtype, const void* dy, int cout, int64_t R, int 
 // in memory ([frame][channel]) and reads the k-strided MFMA fragments with ds_read_b64_tr_b16.  Splits K over ranges of 32-frame chunks (cps chunks
 // per block; a chunk lies inside one item): partial[S = ceil(n_items * ceil(T / 32) / cps)][taps*Cin][cout].  Needs cout % 256 == 0, c0 % 64 == c1 % 64 == 0.
 // part_b != null: the blocks of the first N tile also write part_b[S][cout] = column sums of dY over their K range (bias-gradient
-// partials as a by-product of the A fragments they already hold; replaces the colsum_rows pass over dY).
+// partials as a by-product of the A fragments they already hold: no separate pass over dY).
 hipError_t launch_wgrad_tn(int dtype, const void* dy, int cout, const void* x0, int c0, const void* x1, int c1, int taps,
                            int n_items, int T, int cps, const void* zeros, float* partial, float* part_b, hipStream_t s);
 // ONE launch for every output of a weight-gradient GEMM: up to three (co_start, co_cnt) row blocks of the fused q/k/v projection, each
@@ -123,8 +115,6 @@ hipError_t launch_wgrad_tn(int dtype, const void* dy, int cout, const void* x0, 
 struct WgradRed { float* dW; float* db; const float* unscale; int cin_total, ci_off, ci_cnt, co_start, co_cnt; };
 hipError_t launch_wgrad_reduce_multi(const float* partial, const float* part_b, int S, int cin, int cout, int taps, const WgradRed* outs,
                                      int n_outs, hipStream_t s);
-// part_b[rowblock][cout] = column sums of every 64-row block of dY [R][cout] (bias-gradient partials for launch_bias_reduce)
-hipError_t launch_colsum_rows(int dtype, const void* dy, int cout, int64_t R, float* part_b, hipStream_t s);
 // dW (reference layout (co_cnt, Cin_total, taps), fp32) [co - co_start][ci_off + ci][j] = sum_s partial[s][j*Cin + ci][co]
 // for co in [co_start, co_start + co_cnt) (a row block of a fused projection), ci < ci_cnt
 hipError_t launch_wgrad_reduce(const float* partial, int S, int cin, int cout, int taps, float* dW, int cin_total,
@@ -157,17 +147,13 @@ hipError_t launch_linear_bwd_in(const float* in, const float* dout, const float*
 // (mean != nullptr: mean[item*H + h][64] is subtracted from the valid positions -- centred copy)
 hipError_t launch_attn_to_T(int dtype, const void* nat, int64_t item_stride, int64_t head_stride, int row_stride,
                             int n_items, int H, int T, int Tp, const float* mean, void* outT, hipStream_t s);
-// mean[nh][64] over the T positions of a natural-layout tensor
-hipError_t launch_attn_mean_nat(int dtype, const void* nat, int n_heads_total, int T, float* mean, hipStream_t s);
-// natural copy of a T-layout tensor, CENTRED when vmean != nullptr: vmean[item][H][64] = mean over the positions is
-// computed first and subtracted (attention_bwd.hip, "Precision")
-// nat_lo (optional): 16-bit rounding residual of the centred values (hi + lo operand pair)
-// the three means + the three centred copies of one attention backward in two launches (same bodies as the single launches below)
+// The three means + the three centred copies of one attention backward in two launches: qT / kT as launch_attn_to_T with the
+// means of q / k over the positions subtracted, vnat = the natural copy of the T-layout v, CENTRED: vmean[item][H][64] = its mean
+// over the positions is computed first and subtracted (attention_bwd.hip, "Precision")
+// vnat_lo (optional): 16-bit rounding residual of the centred values (hi + lo operand pair)
 // vT_lo (optional): the forward's rounding residuals of v (hi + lo v operands): the mean and the centred pair are then formed from vT + vT_lo
 hipError_t launch_attn_prep(int dtype, const void* q, const void* k, const void* vT, const void* vT_lo, int n_items, int H, int T, int Tp, float* qmean,
                             float* kmean, float* vmean, void* qT, void* kT, void* vnat, void* vnat_lo, hipStream_t s);
-hipError_t launch_attn_from_T(int dtype, const void* inT, int n_items, int H, int T, int Tp, float* vmean, void* nat, void* nat_lo,
-                              hipStream_t s);
 struct AttnBwdArgs {
     const void* q; const void* k; const void* v;       // natural [item][H][T][64] (q pre-scaled by log2e/8, RoPE applied; v CENTRED)
     const void* vlo;                                   // rounding residual of the centred v (second operand of dP = dO v^T)

@@ -252,41 +252,4 @@ hipError_t launch_wgrad_tn(int dtype, const void* dy, int cout, const void* x0, 
     return dtype == DT_BF16 ? launch_wgrad_tn_t<OpBF16>(w, partial, S, s) : launch_wgrad_tn_t<OpF16>(w, partial, S, s);
 }
 
-// part_b[rowblock][co] = sum over the block's 64 rows of dY[r][co] (the bias-gradient partials launch_bias_reduce adds up):
-// block = 64 rows x 64 channels, thread = 8 channels (16 bytes) of one of 32 row pairs
-template <class P>
-__global__ __launch_bounds__(256) void colsum_rows_kernel(const typename P::elem* dy, int cout, int64_t R, float* part_b) {
-    __shared__ float red[32][64 + 1];
-    const int64_t r0 = (int64_t)blockIdx.x * 64;
-    const int ch0 = blockIdx.y * 64;
-    const int tx = threadIdx.x & 7, ty = threadIdx.x >> 3;
-    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int64_t r = r0 + ty + 32 * u;
-        if (r < R) {
-            const typename P::vec8 x = as_vec8<P>(*(const uint4*)(dy + (size_t)r * cout + ch0 + tx * 8));
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] += (float)x[e];
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) red[ty][tx * 8 + e] = v[e];
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        float t = 0.f;
-#pragma unroll
-        for (int q = 0; q < 32; ++q) t += red[q][threadIdx.x];
-        part_b[(size_t)blockIdx.x * cout + ch0 + threadIdx.x] = t;
-    }
-}
-
-hipError_t launch_colsum_rows(int dtype, const void* dy, int cout, int64_t R, float* part_b, hipStream_t s) {
-    if (cout & 63) return hipErrorInvalidValue;
-    dim3 grid((unsigned)((R + 63) / 64), (unsigned)(cout / 64));
-    if (dtype == DT_BF16) hipLaunchKernelGGL((colsum_rows_kernel<OpBF16>), grid, dim3(256), 0, s, (const __bf16*)dy, cout, R, part_b);
-    else                  hipLaunchKernelGGL((colsum_rows_kernel<OpF16>), grid, dim3(256), 0, s, (const _Float16*)dy, cout, R, part_b);
-    return hipGetLastError();
-}
-
 }  // namespace st

@@ -32,8 +32,9 @@ from ._native_module import NativeModule, check_activations_live, param_grad_vie
 __all__ = ["DiscriminatorP", "MultiPeriodDiscriminator", "DiscriminatorR", "MultiResolutionDiscriminator"]
 
 
-class _DiscriminatorPFn(torch.autograd.Function):
-    """DiscriminatorP.forward under autograd.  Inputs (module, parameter names, x, *parameters) -> the five feature maps."""
+class _DiscriminatorFn(torch.autograd.Function):
+    """A native discriminator's forward under autograd.  Inputs (module, parameter names, x, *parameters) -> its feature maps
+    (DiscriminatorP: five, DiscriminatorR: 21)."""
 
     @staticmethod
     def forward(ctx, mod, names, x, *params):
@@ -52,7 +53,7 @@ class _DiscriminatorPFn(torch.autograd.Function):
         if all(g is None for g in grads):
             return (None,) * len(need)
         if ctx.spent:
-            raise RuntimeError("stabletts_amd: this DiscriminatorP forward has been differentiated already -- the native backward runs once "
+            raise RuntimeError(f"stabletts_amd: this {ctx.mod._noun} forward has been differentiated already -- the native backward runs once "
                                "per forward (its scratch overwrites what a second pass would need); run the forward again")
         mod, eng, dev = ctx.mod, ctx.eng, ctx.dev
         check_activations_live(mod, eng, ctx.serial, ctx.vers)
@@ -63,16 +64,79 @@ class _DiscriminatorPFn(torch.autograd.Function):
         with torch.cuda.device(dev):
             flat = torch.zeros(lay[None], device=dev, dtype=torch.float32) if any(need[3:]) else None    # (gaps and unreached slices stay 0)
             d_x = torch.empty(B, 1, T, device=dev, dtype=torch.float32) if need[2] else None
-            eng.period_disc_train_backward(B, T, gs, d_x, flat, torch.cuda.current_stream(dev).cuda_stream)
+            getattr(eng, mod._native + "_train_backward")(B, T, gs, d_x, flat, torch.cuda.current_stream(dev).cuda_stream)
         if d_x is not None:
             d_x = d_x.to(ctx.x_dtype)
         pg = param_grad_views(flat, lay, ctx.names, ctx.params, need[3:]) if flat is not None else [None] * len(ctx.params)
         return (None, None, d_x) + tuple(pg)
 
 
-class DiscriminatorP(NativeModule):
-    _what = "period discriminator"
+class _Discriminator(NativeModule):
+    """What DiscriminatorP and DiscriminatorR share.  A class defines ``_noun`` (its name in messages), ``_native`` (the prefix of
+    its ``_lib.Engine`` methods), ``_config()`` (what its handle was created from), ``_fmap_shapes(eng, B, T)`` and, where the
+    input has a minimum length, ``_check_input(x)``."""
     native_training = True
+
+    def engine(self):
+        eng = self._engine
+        if eng is not None and getattr(eng, "disc_config", None) != self._config():
+            eng.close()                      # the configuration was re-assigned after construction: another handle
+            self._engine = None
+        eng = super().engine()
+        eng.disc_config = self._config()
+        return eng
+
+    def _check_input(self, x):
+        pass
+
+    def _run(self, eng, xf, train):
+        B, _, T = xf.shape
+        dev = xf.device
+        with torch.cuda.device(dev):
+            fmaps = [torch.empty(s, device=dev, dtype=torch.float32) for s in self._fmap_shapes(eng, B, T)]
+            getattr(eng, self._native + "_forward")(xf, fmaps, train, torch.cuda.current_stream(dev).cuda_stream)
+        return fmaps
+
+    def _feature_maps(self, x: Tensor) -> List[Tensor]:
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            self.engine()      # raises: no CPU fallback
+        if x.device != dev:
+            raise ValueError(f"the input is on {x.device}, the {self._what}'s parameters are on {dev}")
+        if x.dim() != 3 or x.shape[1] != 1:
+            raise ValueError("x must be (B, 1, T)")
+        self._check_input(x)
+        if self.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            named = list(self.named_parameters())
+            return list(_DiscriminatorFn.apply(self, [n for n, _ in named], x, *[p for _, p in named]))
+        with torch.no_grad():
+            return self._run(self.engine(), x.detach().to(torch.float32).contiguous(), False)
+
+
+class _MultiDiscriminator(nn.Module):
+    """``forward`` of MultiPeriodDiscriminator and MultiResolutionDiscriminator over ``self.discriminators``."""
+
+    def forward(self, y: Tensor, y_hat: Tensor) -> Tuple[List[Tensor], List[Tensor], List[List[Tensor]], List[List[Tensor]]]:
+        """As the reference: (y_d_rs, y_d_gs, fmap_rs, fmap_gs).  Every discriminator runs ONCE on cat([y, y_hat]) -- the weights are
+        read once and each engine holds one forward -- and the halves come back as views, bitwise what each signal gives alone."""
+        if y.shape[1:] != y_hat.shape[1:]:
+            raise ValueError(f"y {tuple(y.shape)} and y_hat {tuple(y_hat.shape)} must agree in every dimension but the batch")
+        n = y.shape[0]
+        x = torch.cat([y, y_hat.to(y.dtype)], dim=0)
+        y_d_rs, y_d_gs, fmap_rs, fmap_gs = [], [], [], []
+        for d in self.discriminators:
+            logits, fmap = d(x)
+            y_d_rs.append(logits[:n])
+            y_d_gs.append(logits[n:])
+            fmap_rs.append([f[:n] for f in fmap])
+            fmap_gs.append([f[n:] for f in fmap])
+        return y_d_rs, y_d_gs, fmap_rs, fmap_gs
+
+
+class DiscriminatorP(_Discriminator):
+    _what = "period discriminator"
+    _noun = "DiscriminatorP"
+    _native = "period_disc"
 
     def __init__(self, period: int, in_channels: int = 1, kernel_size: int = 5, stride: int = 3, lrelu_slope: float = 0.1):
         super().__init__()
@@ -98,99 +162,22 @@ class DiscriminatorP(NativeModule):
         return _lib.Engine(0, 0, 0, 0, 0, 0, 0, self.operand_dtype, dev,
                            period_discriminator=dict(period=self.period, lrelu_slope=self.lrelu_slope))
 
-    def engine(self):
-        eng = self._engine
-        if eng is not None and getattr(eng, "pd_config", None) != (self.period, float(self.lrelu_slope)):
-            eng.close()                      # period / slope re-assigned after construction: another handle
-            self._engine = None
-        eng = super().engine()
-        eng.pd_config = (self.period, float(self.lrelu_slope))
-        return eng
+    def _config(self):
+        return (self.period, float(self.lrelu_slope))
 
-    def _run(self, eng, xf, train):
-        B, _, T = xf.shape
-        dev = xf.device
-        with torch.cuda.device(dev):
-            fmaps = [torch.empty(s, device=dev, dtype=torch.float32) for s in eng.period_disc_fmap_shapes(B, T, self.period)]
-            eng.period_disc_forward(xf, fmaps, train, torch.cuda.current_stream(dev).cuda_stream)
-        return fmaps
+    def _fmap_shapes(self, eng, B, T):
+        return eng.period_disc_fmap_shapes(B, T, self.period)
 
     def forward(self, x: Tensor) -> Tuple[Tensor, List[Tensor]]:
         """x (B, 1, T) -> (logits (B, H * period), [the four feature maps after convs.1..4, conv_post's output])."""
-        dev = next(self.parameters()).device
-        if dev.type != "cuda":
-            self.engine()      # raises: no CPU fallback
-        if x.device != dev:
-            raise ValueError(f"the input is on {x.device}, the {self._what}'s parameters are on {dev}")
-        if x.dim() != 3 or x.shape[1] != 1:
-            raise ValueError("x must be (B, 1, T)")
-        if self.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            named = list(self.named_parameters())
-            fmap = list(_DiscriminatorPFn.apply(self, [n for n, _ in named], x, *[p for _, p in named]))
-        else:
-            with torch.no_grad():
-                fmap = self._run(self.engine(), x.detach().to(torch.float32).contiguous(), False)
+        fmap = self._feature_maps(x)
         return torch.flatten(fmap[-1], 1, -1), fmap
 
 
-class MultiPeriodDiscriminator(nn.Module):
+class MultiPeriodDiscriminator(_MultiDiscriminator):
     def __init__(self, periods: Tuple[int, ...] = (2, 3, 5, 7, 11)):
         super().__init__()
         self.discriminators = nn.ModuleList([DiscriminatorP(period=p) for p in periods])
-
-    def forward(self, y: Tensor, y_hat: Tensor):
-        """As the reference: (y_d_rs, y_d_gs, fmap_rs, fmap_gs).  Every period runs ONCE on cat([y, y_hat]) -- the weights are read
-        once and each engine holds one forward -- and the halves come back as views, bitwise what each signal gives alone."""
-        if y.shape[1:] != y_hat.shape[1:]:
-            raise ValueError(f"y {tuple(y.shape)} and y_hat {tuple(y_hat.shape)} must agree in every dimension but the batch")
-        n = y.shape[0]
-        x = torch.cat([y, y_hat.to(y.dtype)], dim=0)
-        y_d_rs, y_d_gs, fmap_rs, fmap_gs = [], [], [], []
-        for d in self.discriminators:
-            logits, fmap = d(x)
-            y_d_rs.append(logits[:n])
-            y_d_gs.append(logits[n:])
-            fmap_rs.append([f[:n] for f in fmap])
-            fmap_gs.append([f[n:] for f in fmap])
-        return y_d_rs, y_d_gs, fmap_rs, fmap_gs
-
-
-class _DiscriminatorRFn(torch.autograd.Function):
-    """DiscriminatorR.forward under autograd.  Inputs (module, parameter names, x, *parameters) -> the 21 feature maps."""
-
-    @staticmethod
-    def forward(ctx, mod, names, x, *params):
-        eng = mod.engine()
-        dev = x.device
-        xf = x.detach().to(torch.float32).contiguous()
-        fmaps = mod._run(eng, xf, True)
-        ctx.mod, ctx.eng, ctx.serial, ctx.vers = mod, eng, eng.train_serial(), mod._param_key()[1]
-        ctx.names, ctx.params, ctx.shape, ctx.dev, ctx.x_dtype, ctx.spent = names, params, (xf.shape[0], xf.shape[2]), dev, x.dtype, False
-        ctx.set_materialize_grads(False)
-        return tuple(fmaps)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        need = ctx.needs_input_grad
-        if all(g is None for g in grads):
-            return (None,) * len(need)
-        if ctx.spent:
-            raise RuntimeError("stabletts_amd: this DiscriminatorR forward has been differentiated already -- the native backward runs once "
-                               "per forward (its scratch overwrites what a second pass would need); run the forward again")
-        mod, eng, dev = ctx.mod, ctx.eng, ctx.dev
-        check_activations_live(mod, eng, ctx.serial, ctx.vers)
-        ctx.spent = True
-        B, T = ctx.shape
-        gs = [None if g is None else g.detach().to(device=dev, dtype=torch.float32).contiguous() for g in grads]
-        lay = eng.grad_layout()
-        with torch.cuda.device(dev):
-            flat = torch.zeros(lay[None], device=dev, dtype=torch.float32) if any(need[3:]) else None    # (gaps and unreached slices stay 0)
-            d_x = torch.empty(B, 1, T, device=dev, dtype=torch.float32) if need[2] else None
-            eng.resolution_disc_train_backward(B, T, gs, d_x, flat, torch.cuda.current_stream(dev).cuda_stream)
-        if d_x is not None:
-            d_x = d_x.to(ctx.x_dtype)
-        pg = param_grad_views(flat, lay, ctx.names, ctx.params, need[3:]) if flat is not None else [None] * len(ctx.params)
-        return (None, None, d_x) + tuple(pg)
 
 
 class _SpectrogramWindow(nn.Module):
@@ -203,9 +190,10 @@ class _SpectrogramWindow(nn.Module):
         self.register_buffer("window", torch.hann_window(window_length))
 
 
-class DiscriminatorR(NativeModule):
+class DiscriminatorR(_Discriminator):
     _what = "resolution discriminator"
-    native_training = True
+    _noun = "DiscriminatorR"
+    _native = "resolution_disc"
     lrelu_slope = 0.1           # the reference hard-codes it (discriminator.py:163); an instance may override it before its first call
 
     def __init__(self, window_length: int, channels: int = 32, hop_factor: float = 0.25,
@@ -244,62 +232,22 @@ class DiscriminatorR(NativeModule):
             cfg[f"band_lo{c}"], cfg[f"band_hi{c}"] = lo, hi
         return _lib.Engine(0, 0, 0, 0, 0, 0, 0, self.operand_dtype, dev, resolution_discriminator=cfg)
 
-    def engine(self):
-        eng = self._engine
-        if eng is not None and getattr(eng, "rd_config", None) != self._config():
-            eng.close()                      # window / bands / slope re-assigned after construction: another handle
-            self._engine = None
-        eng = super().engine()
-        eng.rd_config = self._config()
-        return eng
+    def _fmap_shapes(self, eng, B, T):
+        return eng.resolution_disc_fmap_shapes(B, T)
 
-    def _run(self, eng, xf, train):
-        B, _, T = xf.shape
-        dev = xf.device
-        with torch.cuda.device(dev):
-            fmaps = [torch.empty(s, device=dev, dtype=torch.float32) for s in eng.resolution_disc_fmap_shapes(B, T)]
-            eng.resolution_disc_forward(xf, fmaps, train, torch.cuda.current_stream(dev).cuda_stream)
-        return fmaps
+    def _check_input(self, x):
+        if x.shape[2] <= self.window_length // 2:
+            raise ValueError(f"T = {x.shape[2]} is too short for window_length {self.window_length}: the reflect padding of "
+                             f"{self.window_length // 2} samples needs T > {self.window_length // 2}")
 
     def forward(self, x: Tensor) -> Tuple[Tensor, List[Tensor]]:
         """x (B, 1, T) -> (logits (B, 1, frames, F'), [layers 1..4 of band 0, .. of band 4, conv_post's output]): 21 maps, the last
         being the first return value itself."""
-        dev = next(self.parameters()).device
-        if dev.type != "cuda":
-            self.engine()      # raises: no CPU fallback
-        if x.device != dev:
-            raise ValueError(f"the input is on {x.device}, the {self._what}'s parameters are on {dev}")
-        if x.dim() != 3 or x.shape[1] != 1:
-            raise ValueError("x must be (B, 1, T)")
-        if x.shape[2] <= self.window_length // 2:
-            raise ValueError(f"T = {x.shape[2]} is too short for window_length {self.window_length}: the reflect padding of "
-                             f"{self.window_length // 2} samples needs T > {self.window_length // 2}")
-        if self.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            named = list(self.named_parameters())
-            fmap = list(_DiscriminatorRFn.apply(self, [n for n, _ in named], x, *[p for _, p in named]))
-        else:
-            with torch.no_grad():
-                fmap = self._run(self.engine(), x.detach().to(torch.float32).contiguous(), False)
+        fmap = self._feature_maps(x)
         return fmap[-1], fmap
 
 
-class MultiResolutionDiscriminator(nn.Module):
+class MultiResolutionDiscriminator(_MultiDiscriminator):
     def __init__(self, fft_sizes: Tuple[int, ...] = (2048, 1024, 512)):
         super().__init__()
         self.discriminators = nn.ModuleList([DiscriminatorR(window_length=w) for w in fft_sizes])
-
-    def forward(self, y: Tensor, y_hat: Tensor) -> Tuple[List[Tensor], List[Tensor], List[List[Tensor]], List[List[Tensor]]]:
-        """As the reference: (y_d_rs, y_d_gs, fmap_rs, fmap_gs).  Every resolution runs ONCE on cat([y, y_hat]) -- the weights are
-        read once and each engine holds one forward -- and the halves come back as views, bitwise what each signal gives alone."""
-        if y.shape[1:] != y_hat.shape[1:]:
-            raise ValueError(f"y {tuple(y.shape)} and y_hat {tuple(y_hat.shape)} must agree in every dimension but the batch")
-        n = y.shape[0]
-        x = torch.cat([y, y_hat.to(y.dtype)], dim=0)
-        y_d_rs, y_d_gs, fmap_rs, fmap_gs = [], [], [], []
-        for d in self.discriminators:
-            logits, fmap = d(x)
-            y_d_rs.append(logits[:n])
-            y_d_gs.append(logits[n:])
-            fmap_rs.append([f[:n] for f in fmap])
-            fmap_gs.append([f[n:] for f in fmap])
-        return y_d_rs, y_d_gs, fmap_rs, fmap_gs

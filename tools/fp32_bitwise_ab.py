@@ -18,7 +18,9 @@ split-K weight gradients):
                                        smallest shapes each kind accepts: B = 1, T = 8 frames (97 samples for the discriminator, 64
                                        for the mel extractor), and the mel extractor and the two vocoders compare ONE output
                                        tensor each -- a check that moved host code still launches the same work, not a sweep
-                                       of tile paths (tests/test_gpu_vocoder.py, test_gpu_mel.py and test_gpu_ffgan.py are that)
+                                       of tile paths (tests/test_gpu_vocoder.py, test_gpu_mel.py and test_gpu_ffgan.py are that).
+                                       Each vocoder also runs its ragged entry point once on the same handle: one chunk, B = 3,
+                                       T = 40, lengths (40, 17, 1)
 """
 import os
 import subprocess
@@ -28,6 +30,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_SECONDS = 600
+RAGGED_B, RAGGED_T, RAGGED_LENGTHS = 3, 40, (40, 17, 1)
 VOCOS_SHAPES = [(2, 1, {}), (2, 3, {}), (2, 61, {}), (1, 20, {}), (2, 9, dict(input_channels=128))]
 
 
@@ -138,6 +141,13 @@ def _other_kinds():
             eng.resolution_disc_train_backward(L.B, kind.T, [L._rand(s, 20 + i) for i, s in enumerate(shapes)], d_x, flat, None)
             got.update({f"{name}/train/out{i}": t.cpu() for i, t in enumerate(fmaps)})
             got.update({f"{name}/train/d_x": d_x.cpu(), f"{name}/train/grad_flat": flat.cpu()})
+        if name in ("vocoder", "ffgan"):      # the ragged entry point, one chunk: utterances at full, odd and unit length
+            M, hop = (L.VOCOS["input_channels"], L.VOCOS["hop_length"]) if name == "vocoder" else \
+                (L.FFGAN["backbone"]["input_channels"], L.FFGAN["head"]["hop_length"])
+            audio = torch.zeros(RAGGED_B, RAGGED_T * hop, device="cuda")
+            ragged = eng.vocos_forward_ragged if name == "vocoder" else eng.ffgan_forward_ragged
+            ragged(L._rand((RAGGED_B, M, RAGGED_T), 30), RAGGED_LENGTHS, audio, None)
+            got[f"{name}/ragged/out0"] = audio.cpu()
         torch.cuda.synchronize()
         eng.close()
     return got
