@@ -309,7 +309,7 @@ def adams_coefficients(order):
     return [float(x) for x in bashforth], [float(x) for x in moulton]
 
 
-def odeint_implicit_adams(f, y0, t_span, rtol=1e-5, atol=1e-5, max_order=12, max_iters=4, stats=None):
+def odeint_implicit_adams(f, y0, t_span, rtol=1e-5, atol=1e-5, max_order=12, max_iters=4, stats=None, log=None):
     """torchdiffeq's 'implicit_adams' (fixed_adams.py: AdamsBashforthMoulton on the fixed grid t_span, as offered by the
     reference's webui.py:110 and called at models/flow_matching.py:54 with rtol = atol = 1e-5), restated from memory of the
     published source -- torchdiffeq is absent offline: PARITY UNPINNED.  Per grid step:
@@ -318,11 +318,13 @@ def odeint_implicit_adams(f, y0, t_span, rtol=1e-5, atol=1e-5, max_order=12, max
       history's length followed by functional iteration of the Adams-Moulton corrector with one more sample,
       dy <- dt * m0 * f(t1, y0 + dy) + delta, at most max_iters times, stopping when
       max |dy_old - dy| / (atol + rtol * max(|dy_old|, |dy|)) < 1; if the iteration does not converge the OLDEST history
-      entry is dropped (and torchdiffeq warns).  y1 = y0 + dy."""
+      entry is dropped (and torchdiffeq warns).  y1 = y0 + dy.
+    stats receives nfe and rejects (steps whose corrector did not converge); log, a list, receives every corrector iteration's
+    max |dy_old - dy| / tol -- the number the convergence decision compares with 1.  Neither alters the arithmetic."""
     import collections
     prev_f = collections.deque(maxlen=max_order - 1)
     y = y0
-    nfe = 0
+    nfe = rejects = 0
     for i in range(len(t_span) - 1):
         t0, t1 = t_span[i], t_span[i + 1]
         dt = t1 - t0
@@ -349,14 +351,18 @@ def odeint_implicit_adams(f, y0, t_span, rtol=1e-5, atol=1e-5, max_order=12, max
                 nfe += 1
                 dy = (dt * moul[0]) * fn + delta
                 tol = atol + rtol * torch.max(dy_old.abs(), dy.abs())
-                converged = bool(((dy_old - dy).abs() / tol).max() < 1)
+                worst = ((dy_old - dy).abs() / tol).max()
+                converged = bool(worst < 1)
+                if log is not None:
+                    log.append(float(worst))
                 if converged:
                     break
             if not converged:
                 prev_f.pop()
+                rejects += 1
         y = y + dy
     if stats is not None:
-        stats.update(nfe=nfe)
+        stats.update(nfe=nfe, steps=len(t_span) - 1, rejects=rejects)
     return y
 
 
@@ -401,13 +407,15 @@ ADAPTIVE_TABLEAUS = {
 }
 
 
-def odeint_adaptive(f, y0, method="dopri5", t_end=1.0, rtol=1e-5, atol=1e-5, stats=None):
+def odeint_adaptive(f, y0, method="dopri5", t_end=1.0, rtol=1e-5, atol=1e-5, stats=None, log=None):
     """torchdiffeq's RKAdaptiveStepsizeODESolver as called at models/flow_matching.py:54 (rtol=atol=1e-5),
     integrating from 0 to t_end and returning the state at t_end.  Intermediate output times only add
     interpolation, never change the steps, so they are not modelled.  Steps are NOT clipped to t_end: the last
     step may overshoot and the result is the 4th-order dense-output interpolant at t_end (_interp_fit with
     f0 = k[0], f1 = k[-1]).  As in torchdiffeq, the derivative carried into the next step is k[-1] whether or not
-    the tableau is FSAL.  Time is carried in float64 on the host; f receives it as an fp32 0-dim tensor."""
+    the tableau is FSAL.  Time is carried in float64 on the host; f receives it as an fp32 0-dim tensor.
+    stats receives nfe, steps, rejects, the initial step's h0 and the dense output's argument interp_x; log, a list, receives every
+    step's error ratio -- the number the accept decision compares with 1.  Neither alters the arithmetic."""
     alphas, betas, c_sol, c_err, c_mid, order = ADAPTIVE_TABLEAUS[method]
     fsal = c_sol[-1] == 0.0 and list(c_sol[:-1]) == list(betas[-1])
     tt = lambda t: torch.tensor(t, dtype=torch.float32)
@@ -438,6 +446,8 @@ def odeint_adaptive(f, y0, method="dopri5", t_end=1.0, rtol=1e-5, atol=1e-5, sta
         err = sum((c * dt) * kj for c, kj in zip(c_err, k) if c != 0.0)
         tol = atol + rtol * torch.max(y.abs(), y1.abs())
         ratio = _rms(err / tol)
+        if log is not None:
+            log.append(ratio)
         accept = ratio <= 1.0
         # _optimal_step_size(safety 0.9, ifactor 10, dfactor 0.2, order)
         if ratio == 0.0:
@@ -458,7 +468,7 @@ def odeint_adaptive(f, y0, method="dopri5", t_end=1.0, rtol=1e-5, atol=1e-5, sta
                 x = (t_end - t) / (t1 - t)
                 out = (((a * x + b) * x + c) * x + d) * x + y
                 if stats is not None:
-                    stats.update(nfe=nfe, steps=steps, rejects=rejects)
+                    stats.update(nfe=nfe, steps=steps, rejects=rejects, h0=h0, interp_x=x)
                 return out
             y, fcur, t = y1, k[-1], t1
         else:

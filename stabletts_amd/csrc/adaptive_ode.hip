@@ -106,21 +106,26 @@ __global__ __launch_bounds__(256) void dopri5_interp_kernel(const InterpArgs a) 
     if (i >= a.n) return;
     const float4 y0 = *(const float4*)(a.y0 + i), y1 = *(const float4*)(a.y1 + i);
     const float4 f0 = *(const float4*)(a.k[0] + i), f1 = *(const float4*)(a.k[6] + i);
-    float ym[4] = {y0.x, y0.y, y0.z, y0.w};
+    // _interp_fit's coefficients in the increments d1 = y1 - y0 and dm = y_mid - y0 (= the mid-point combination itself):
+    //   a = 2 dt (f1 - f0) - 8 (y1 + y0) + 16 y_mid = 2 dt (f1 - f0) - 8 d1 + 16 dm,   b = ... + 14 d1 - 32 dm,   c = ... - 5 d1 + 16 dm
+    // -- the same polynomial, without the cancellation of terms as large as 32 |y| that costs the literal fp32 form several
+    // roundings of the state (a constant field: 6 against 1)
+    float dm[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < 7; ++j) {
         const float4 kv = *(const float4*)(a.k[j] + i);
         const float c = a.cmid_dt[j];
-        ym[0] += c * kv.x; ym[1] += c * kv.y; ym[2] += c * kv.z; ym[3] += c * kv.w;
+        dm[0] += c * kv.x; dm[1] += c * kv.y; dm[2] += c * kv.z; dm[3] += c * kv.w;
     }
     const float Y0[4] = {y0.x, y0.y, y0.z, y0.w}, Y1[4] = {y1.x, y1.y, y1.z, y1.w};
     const float F0[4] = {f0.x, f0.y, f0.z, f0.w}, F1[4] = {f1.x, f1.y, f1.z, f1.w};
     float o[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const float ca = 2.f * a.dt * (F1[e] - F0[e]) - 8.f * (Y1[e] + Y0[e]) + 16.f * ym[e];
-        const float cb = a.dt * (5.f * F0[e] - 3.f * F1[e]) + 18.f * Y0[e] + 14.f * Y1[e] - 32.f * ym[e];
-        const float cc = a.dt * (F1[e] - 4.f * F0[e]) - 11.f * Y0[e] - 5.f * Y1[e] + 16.f * ym[e];
+        const float d1 = Y1[e] - Y0[e];
+        const float ca = 2.f * a.dt * (F1[e] - F0[e]) - 8.f * d1 + 16.f * dm[e];
+        const float cb = a.dt * (5.f * F0[e] - 3.f * F1[e]) + 14.f * d1 - 32.f * dm[e];
+        const float cc = a.dt * (F1[e] - 4.f * F0[e]) - 5.f * d1 + 16.f * dm[e];
         const float cd = a.dt * F0[e];
         o[e] = (((ca * a.x + cb) * a.x + cc) * a.x + cd) * a.x + Y0[e];
     }
