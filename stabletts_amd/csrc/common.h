@@ -272,7 +272,7 @@ __device__ __forceinline__ unsigned drop_ffn_hash(const D& d, unsigned long long
     return drop_mix32(((unsigned)d.seed ^ ((unsigned)(i >> 1) * 0x9E3779B1u)) + (unsigned)(d.seed >> 32));
 }
 
-// Fused-FFN weight stream (launch.h: launch_pack_ffn_stream; ffn_fused.h consumes it): element idx of one stage's
+// Fused-FFN weight stream (a PACK_FFN_STREAM job writes it, ffn_fused.h consumes it): element idx of one stage's
 // F*256*3 values -> source offset in the fp32 conv weight and destination offset in the stream (16-bit elements).  hidden = 256
 // hard-wired.  stage = 0: conv_1, 1: conv_2.
 //   idx = ((c*24 + sl)*16 + f)*512 + lane*8 + e;  sl = (ci, tap, kp) = ci*6 + tap*2 + kp
@@ -311,6 +311,83 @@ __host__ __device__ __forceinline__ float ffn_wino_plane(const float* g3, int pl
 // consecutive 1-KiB pieces, lane-linear.
 __host__ __device__ __forceinline__ size_t qkv_frag_index(int plane, int co, int ci) {
     return ((((size_t)(plane * 8 + (co >> 5)) * 16 + (ci >> 4)) * 64 + ((ci >> 3) & 1) * 32 + (co & 31)) << 3) + (ci & 7);
+}
+
+// ---------------------------------------------------------------- weight-packing jobs
+// Every packed weight layout is ONE job description: its element count (pack_job_elems) and its index map (pack_job_map) are written
+// here once, for the host (recorder, tests/host/pack_index_check.cpp) and for the two kernels of misc_kernels.hip that apply them (a
+// list of jobs in one launch, one job by value).  src = fp32 parameter, dst = 16-bit packed buffer (fp32 for PACK_COPY).
+//   PACK_WEIGHT      (cout, cin_total, K) -> [row_off + co][K][cin_p], columns [col_off, col_off + slice_w): source channels
+//                    [ci_off, ci_off + ci_cnt), then zeros; lo != 0 packs the rounding residual W - float(to16(W))
+//   PACK_WEIGHT_T    dgrad weights: [ci][t][col_off + co] (row length cin_p) = W[co][ci_off + ci][K - 1 - t], ci < ci_cnt
+//   PACK_COPY        fp32 copy of `cout` elements (biases)
+//   PACK_FFN_STREAM  ffn_stream_index (lo = stage, cout = F)        PACK_FFN_WINO  ffn_wino_index (lo = stage, cout = F; f16 only)
+//   PACK_QKV_FRAG    qkv_frag_index of a (256, 256, 1) weight (row_off = 256 * plane)
+// blk0 = first 256-thread block of the job in a list's merged grid (jobs sorted by blk0; set by the recorder).
+enum PackKind { PACK_WEIGHT = 0, PACK_WEIGHT_T = 1, PACK_COPY = 2, PACK_FFN_STREAM = 3, PACK_QKV_FRAG = 4, PACK_FFN_WINO = 5 };
+struct PackJob { const float* src; void* dst; int kind, cout, cin_total, K, ci_off, ci_cnt, row_off, cin_p, col_off, slice_w, lo; unsigned blk0; };
+
+inline PackJob pack_job_weight(const float* src, int cout, int cin_total, int K, int ci_off, int ci_cnt, void* dst, int row_off,
+                               int cin_p, int col_off, int slice_w, int lo) {
+    return PackJob{src, dst, PACK_WEIGHT, cout, cin_total, K, ci_off, ci_cnt, row_off, cin_p, col_off, slice_w, lo, 0u};
+}
+inline PackJob pack_job_weight_t(const float* src, int cout, int cin_total, int taps, int ci_off, int ci_cnt, void* dst, int ld, int col_off) {
+    return PackJob{src, dst, PACK_WEIGHT_T, cout, cin_total, taps, ci_off, ci_cnt, 0, ld, col_off, 0, 0, 0u};
+}
+inline PackJob pack_job_copy(float* dst, const float* src, int n) { return PackJob{src, dst, PACK_COPY, n, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0u}; }
+inline PackJob pack_job_ffn_stream(const float* src, int stage, int F, void* dst) { return PackJob{src, dst, PACK_FFN_STREAM, F, 0, 0, 0, 0, 0, 0, 0, 0, stage, 0u}; }
+inline PackJob pack_job_ffn_wino(const float* src, int stage, int F, void* dst) { return PackJob{src, dst, PACK_FFN_WINO, F, 0, 0, 0, 0, 0, 0, 0, 0, stage, 0u}; }
+inline PackJob pack_job_qkv_frag(const float* src, int plane, void* dst) { return PackJob{src, dst, PACK_QKV_FRAG, 0, 0, 0, 0, 0, plane * 256, 0, 0, 0, 0, 0u}; }
+
+__host__ __device__ __forceinline__ size_t pack_job_elems(const PackJob& j) {
+    switch (j.kind) {
+    case PACK_WEIGHT:     return (size_t)j.cout * j.K * j.slice_w;
+    case PACK_WEIGHT_T:   return (size_t)j.ci_cnt * j.K * j.cout;
+    case PACK_FFN_STREAM:
+    case PACK_FFN_WINO:   return (size_t)j.cout * 256 * 3;
+    case PACK_QKV_FRAG:   return 256 * 256;
+    default:              return (size_t)j.cout;
+    }
+}
+// 256-thread blocks of a job: the only place a job's grid is computed
+__host__ __device__ __forceinline__ unsigned pack_job_blocks(const PackJob& j) { return (unsigned)((pack_job_elems(j) + 255) / 256); }
+
+// element idx < pack_job_elems(j) -> offsets in j.src / j.dst.  src == kPackZero: no source, the element is zero padding (PACK_WEIGHT);
+// variant: the plane of ffn_wino_plane (PACK_FFN_WINO: src is then tap 0 of the triple), else 0
+constexpr size_t kPackZero = ~(size_t)0;
+struct PackElem { size_t src, dst; int variant; };
+__host__ __device__ __forceinline__ PackElem pack_job_map(const PackJob& j, size_t idx) {
+    PackElem m{idx, idx, 0};
+    switch (j.kind) {
+    case PACK_WEIGHT: {
+        const int ci = (int)(idx % j.slice_w);
+        const int t = (int)((idx / j.slice_w) % j.K);
+        const int co = (int)(idx / ((size_t)j.slice_w * j.K));
+        m.src = ci < j.ci_cnt ? ((size_t)co * j.cin_total + j.ci_off + ci) * j.K + t : kPackZero;
+        m.dst = ((size_t)(j.row_off + co) * j.K + t) * j.cin_p + j.col_off + ci;
+    } break;
+    case PACK_WEIGHT_T: {
+        const int co = (int)(idx % j.cout);
+        const int t = (int)((idx / j.cout) % j.K);
+        const int ci = (int)(idx / ((size_t)j.cout * j.K));
+        m.src = ((size_t)co * j.cin_total + j.ci_off + ci) * j.K + (j.K - 1 - t);
+        m.dst = ((size_t)ci * j.K + t) * j.cin_p + j.col_off + co;
+    } break;
+    case PACK_FFN_STREAM: ffn_stream_index(idx, j.lo, j.cout, &m.src, &m.dst); break;
+    case PACK_FFN_WINO:   ffn_wino_index(idx, j.lo, j.cout, &m.src, &m.dst, &m.variant); break;
+    case PACK_QKV_FRAG:   m.dst = qkv_frag_index(j.row_off >> 8, (int)(idx >> 8), (int)(idx & 255)); break;
+    default: break;      // PACK_COPY: the identity
+    }
+    return m;
+}
+// the job of a list whose block range [blk0, blk0 + pack_job_blocks) holds block `blk` of the merged grid (binary search)
+__host__ __device__ __forceinline__ int pack_job_find(const PackJob* jobs, int njobs, unsigned blk) {
+    int lo = 0, hi = njobs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (jobs[mid].blk0 <= blk) lo = mid; else hi = mid - 1;
+    }
+    return lo;
 }
 
 }  // namespace st

@@ -810,55 +810,41 @@ int DitState::repack(st_engine* e, hipStream_t s) {
 
 int64_t DitState::device_bytes() const { return train_bytes(this); }
 
-static void pk_push(DitState::PackList& L, const PackJob& j0, size_t elems) {
-    if (!L.recording) return;
-    PackJob j = j0;
+// A PackList (engine_dit.h): begin -> pk_push per job -> end (upload + the one launch); replay = the one launch again.
+void pk_begin(DitState::PackList& L) { L.jobs.clear(); L.nblocks = 0; L.ready = false; }
+void pk_push(DitState::PackList& L, PackJob j) {
     j.blk0 = L.nblocks;
+    L.nblocks += pack_job_blocks(j);
     L.jobs.push_back(j);
-    L.nblocks += (unsigned)((elems + 255) / 256);
 }
-void pk_begin(DitState::PackList& L) { L.jobs.clear(); L.nblocks = 0; L.ready = false; L.recording = true; }
+static int pk_run(st_engine* e, DitState::PackList& L, hipStream_t s) {
+    HIPCHK(e, launch_pack_jobs(e->dt, L.dev, (int)L.jobs.size(), L.nblocks, s));
+    return ST_OK;
+}
 int pk_end(st_engine* e, DitState::PackList& L, hipStream_t s) {
-    L.recording = false;
     if (L.jobs.empty()) return ST_OK;
     if (L.dev) { HIPCHK(e, hipStreamSynchronize(s)); hipFree(L.dev); L.dev = nullptr; }
     HIPCHK(e, hipMalloc((void**)&L.dev, L.jobs.size() * sizeof(PackJob)));
     HIPCHK(e, hipMemcpyAsync(L.dev, L.jobs.data(), L.jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice, s));
+    int rc = pk_run(e, L, s); if (rc) return rc;
     HIPCHK(e, hipStreamSynchronize(s));        // (pageable source; once per parameter binding)
     L.ready = true;
     return ST_OK;
 }
 bool pk_replay(st_engine* e, DitState::PackList& L, hipStream_t s, int* rc) {
     if (!L.ready) return false;
-    *rc = ST_OK;
-    if (launch_pack_jobs(e->dt, L.dev, (int)L.jobs.size(), L.nblocks, s) != hipSuccess) *rc = e->fail(ST_ERR_HIP, "launch_pack_jobs");
+    *rc = pk_run(e, L, s);
     return true;
-}
-int pk_weight(st_engine* e, DitState::PackList& L, const float* src, int cout, int cin_total, int K, int ci_off, int ci_cnt, void* dst,
-              int row_off, int cin_p, int col_off, int slice_w, int lo, hipStream_t s) {
-    HIPCHK(e, launch_pack_weight(e->dt, src, cout, cin_total, K, ci_off, ci_cnt, dst, row_off, cin_p, col_off, slice_w, lo, s));
-    pk_push(L, PackJob{src, dst, 0, cout, cin_total, K, ci_off, ci_cnt, row_off, cin_p, col_off, slice_w, lo, 0u}, (size_t)cout * K * slice_w);
-    return ST_OK;
-}
-int pk_weight_t(st_engine* e, DitState::PackList& L, const float* src, int cout, int cin_total, int taps, int ci_off, int ci_cnt, void* dst,
-                int cin_p, int ld, int col_off, hipStream_t s) {
-    HIPCHK(e, launch_pack_weight_t(e->dt, src, cout, cin_total, taps, ci_off, ci_cnt, dst, cin_p, ld, col_off, s));
-    pk_push(L, PackJob{src, dst, 1, cout, cin_total, taps, ci_off, ci_cnt, 0, ld, col_off, 0, 0, 0u}, (size_t)ci_cnt * taps * cout);
-    return ST_OK;
-}
-int pk_copy(st_engine* e, DitState::PackList& L, float* dst, const float* src, int n, hipStream_t s) {
-    HIPCHK(e, hipMemcpyAsync(dst, src, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-    pk_push(L, PackJob{src, dst, 2, n, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0u}, (size_t)n);
-    return ST_OK;
 }
 
 // Packs every convolution's weights into the 16-bit MFMA operand layouts on stream `s`.  The packed buffers are
 // allocated by the first call and re-used by every later one (shapes are fixed by the configuration), so instantiated
-// HIP graphs and in-flight launch sequences keep valid pointers and a re-pack is pure stream work.
+// HIP graphs and in-flight launch sequences keep valid pointers and a re-pack is pure stream work: one launch of the
+// job list the first call recorded, for as long as the parameter tensors stay where they are.
 int pack_all(st_engine* e, hipStream_t s) {
     DitState* dit = dit_of(e);
     const int C = dit->C, F = dit->F, M = dit->M, Mp = dit->Mp, K = dit->K, L = dit->L;
-    {   // every later re-pack of the same tensors is one launch (the list was recorded by the first one)
+    {
         int prc;
         if (dit->packed_once && pk_replay(e, dit->pk_fwd, s, &prc)) return prc;
     }
@@ -874,9 +860,9 @@ int pack_all(st_engine* e, hipStream_t s) {
         // (the zero padding is written once, at allocation: a re-pack rewrites exactly the payload elements)
         if (!cv.w) { if ((rc = dev_alloc(e, &cv.w, wbytes))) return rc; HIPCHK(e, hipMemsetAsync(cv.w, 0, wbytes, s)); }
         for (int part = 0; part < (split ? 3 : 1); ++part)
-            if ((rc = pk_weight(e, PL, P(e, wname), cout, cin_total, taps, ci_off, ci_cnt, cv.w, 0, cv.cin, part * cin_p, cin_p, part == 2, s))) return rc;
+            pk_push(PL, pack_job_weight(P(e, wname), cout, cin_total, taps, ci_off, ci_cnt, cv.w, 0, cv.cin, part * cin_p, cin_p, part == 2));
         if (!cv.bias) { if ((rc = dev_alloc(e, (void**)&cv.bias, (size_t)cout_p * 4))) return rc; HIPCHK(e, hipMemsetAsync(cv.bias, 0, (size_t)cout_p * 4, s)); }
-        if (bias_src && (rc = pk_copy(e, PL, cv.bias, bias_src, cout, s))) return rc;
+        if (bias_src) pk_push(PL, pack_job_copy(cv.bias, bias_src, cout));
         return ST_OK;
     };
     int rc;
@@ -913,20 +899,16 @@ int pack_all(st_engine* e, hipStream_t s) {
         }
         for (const char* nm : {"q", "k", "v"}) {
             const std::string n = b + "attn.conv_" + nm;
-            if (frag) {
-                HIPCHK(e, launch_pack_qkv_frag(e->dt, P(e, n + ".weight"), r, dit->qkv_frag[i], s));
-                pk_push(PL, PackJob{P(e, n + ".weight"), dit->qkv_frag[i], 4, 0, 0, 0, 0, 0, r * 256, 0, 0, 0, 0, 0u}, (size_t)C * C);
-            }
-            if ((rc = pk_weight(e, PL, P(e, n + ".weight"), C, C, 1, 0, C, q.w, r * C, C, 0, C, 0, s))) return rc;
-            if ((rc = pk_copy(e, PL, q.bias + (size_t)r * C, P(e, n + ".bias"), C, s))) return rc;
+            if (frag) pk_push(PL, pack_job_qkv_frag(P(e, n + ".weight"), r, dit->qkv_frag[i]));
+            pk_push(PL, pack_job_weight(P(e, n + ".weight"), C, C, 1, 0, C, q.w, r * C, C, 0, C, 0));
+            pk_push(PL, pack_job_copy(q.bias + (size_t)r * C, P(e, n + ".bias"), C));
             ++r;
         }
         if ((rc = pack(dit->oproj[i], b + "attn.conv_o.weight", P(e, b + "attn.conv_o.bias"), C, C, C, 1, 0, C, C, false))) return rc;
         if (frag) {      // the weight-stationary out-projection kernel's copy (oproj_ws.hip): plane 0 of the same fragment order
             if ((int)dit->oproj_frag.size() != L) dit->oproj_frag.assign(L, nullptr);
             if (!dit->oproj_frag[i] && (rc = dev_alloc(e, &dit->oproj_frag[i], (size_t)C * C * 2))) return rc;
-            HIPCHK(e, launch_pack_qkv_frag(e->dt, P(e, b + "attn.conv_o.weight"), 0, dit->oproj_frag[i], s));
-            pk_push(PL, PackJob{P(e, b + "attn.conv_o.weight"), dit->oproj_frag[i], 4, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0u}, (size_t)C * C);
+            pk_push(PL, pack_job_qkv_frag(P(e, b + "attn.conv_o.weight"), 0, dit->oproj_frag[i]));
         }
         if ((rc = pack(dit->ffn1[i], b + "mlp.conv_1.weight", P(e, b + "mlp.conv_1.bias"), F, F, C, K, 0, C, C, false))) return rc;
         if ((rc = pack(dit->ffn2[i], b + "mlp.conv_2.weight", P(e, b + "mlp.conv_2.bias"), C, C, F, K, 0, F, F, false))) return rc;
@@ -935,13 +917,8 @@ int pack_all(st_engine* e, hipStream_t s) {
             if (!dit->ffn_stream[i] && (rc = dev_alloc(e, &dit->ffn_stream[i], (size_t)2 * F * C * K * 2))) return rc;
             for (int st = 0; st < 2; ++st) {
                 const float* src = P(e, b + (st ? "mlp.conv_2.weight" : "mlp.conv_1.weight"));
-                if (dit->fused_ffn == 3) {      // ffn_wino.h: three transformed planes per tap triple
-                    HIPCHK(e, launch_pack_ffn_wino(src, st, F, dit->ffn_stream[i], s));
-                    pk_push(PL, PackJob{src, dit->ffn_stream[i], 5, F, 0, 0, 0, 0, 0, 0, 0, 0, st, 0u}, (size_t)F * C * K);
-                    continue;
-                }
-                HIPCHK(e, launch_pack_ffn_stream(e->dt, src, st, F, dit->ffn_stream[i], s));
-                pk_push(PL, PackJob{src, dit->ffn_stream[i], 3, F, 0, 0, 0, 0, 0, 0, 0, 0, st, 0u}, (size_t)F * C * K);
+                // (ST_FUSED_FFN=3, ffn_wino.h: three transformed planes per tap triple)
+                pk_push(PL, dit->fused_ffn == 3 ? pack_job_ffn_wino(src, st, F, dit->ffn_stream[i]) : pack_job_ffn_stream(src, st, F, dit->ffn_stream[i]));
             }
         }
     }

@@ -3,6 +3,7 @@
 // st_cfm_solve) and engine_train.cpp (training: forward that keeps activations + backward).  Not part of the C ABI.
 #pragma once
 #include "engine_internal.h"
+#include "common.h"
 #include "stream_fork.h"
 
 constexpr int kMaxParts = 1 + sthost::StreamFork::kMaxChildren;      // solve parts: part 0 on the caller's stream, the others on part_streams
@@ -19,9 +20,12 @@ struct DitState : KindState {
     int n_vocab = 0;
     // parameter-name prefix of DiT block i: estimator.py:13,79 "blocks.i.block." / text_encoder.py:25 "encoder.i."
     std::string blk(int i) const { return dec ? "blocks." + std::to_string(i) + ".block." : "encoder." + std::to_string(i) + "."; }
-    // Re-pack job lists (launch.h: PackJob): the first pack runs its individual launches and records them; later re-packs of
-    // the same parameter tensors are ONE launch per list.  Dropped whenever a parameter pointer may have changed.
-    struct PackList { std::vector<st::PackJob> jobs; st::PackJob* dev = nullptr; unsigned nblocks = 0; bool ready = false; bool recording = false; };
+    // Packing job lists (common.h: PackJob): pack_all / train_prepare record one job per packed tensor slice and run the list as ONE
+    // launch, the first pack included; later re-packs of the same parameter tensors launch the uploaded list again.  Dropped whenever
+    // a parameter pointer may have changed.  The blocks of a list run concurrently, so no two of its jobs may write the same
+    // destination element: every job of the two lists has a buffer, row block or column slice of its own (split parts and the
+    // [h_hi | h_lo] q/k/v halves are disjoint column ranges, q / k / v disjoint rows or planes, the two FFN stages disjoint slabs).
+    struct PackList { std::vector<st::PackJob> jobs; st::PackJob* dev = nullptr; unsigned nblocks = 0; bool ready = false; };
     PackList pk_fwd, pk_T;
     bool packed_once = false;          // pack_all has allocated the packed-weight buffers (st_repack re-uses them)
 
@@ -102,16 +106,12 @@ int arena_fresh(st_engine* e, uint64_t sig, size_t used_bytes, hipStream_t s);
 int ensure_rope(st_engine* e, int T, hipStream_t s);
 // The common entry checks of the DiT kinds' forwards: null handle, finalized, sizes, then the handle's kind and 32-bit row indexing
 int check_ready(st_engine* e, Kind kind, int B, int T);
-int pack_all(st_engine* e, hipStream_t s);
-// recorder / replayer of a PackList: begin -> the pk_* calls (individual launch + record) -> end (upload); replay = one launch
+int pack_all(st_engine* e, hipStream_t s);            // (re)packs every 16-bit weight; allocates on the first call only
+// recorder / replayer of a PackList: begin -> pk_push per job (append only) -> end (upload + one launch); replay = that launch again
 bool pk_replay(st_engine* e, DitState::PackList& L, hipStream_t s, int* rc);      // true: the list was replayed (or failed: *rc)
 void pk_begin(DitState::PackList& L);
+void pk_push(DitState::PackList& L, st::PackJob j);
 int pk_end(st_engine* e, DitState::PackList& L, hipStream_t s);
-int pk_weight(st_engine* e, DitState::PackList& L, const float* src, int cout, int cin_total, int K, int ci_off, int ci_cnt, void* dst,
-              int row_off, int cin_p, int col_off, int slice_w, int lo, hipStream_t s);
-int pk_weight_t(st_engine* e, DitState::PackList& L, const float* src, int cout, int cin_total, int taps, int ci_off, int ci_cnt, void* dst,
-                int cin_p, int ld, int col_off, hipStream_t s);
-int pk_copy(st_engine* e, DitState::PackList& L, float* dst, const float* src, int n, hipStream_t s);            // (re)packs every 16-bit weight; allocates on the first call only
 
 // ---- engine.cpp: the workspace plan of one estimator pass (or solve part) and the launch sequences that use it
 struct Plan {

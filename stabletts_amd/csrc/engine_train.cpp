@@ -142,8 +142,7 @@ int pack_T(st_engine* e, TrainState* ts, Conv& cv, const std::string& wname, int
         HIPCHK(e, hipMalloc(&cv.w, bytes)); ts->owned.push_back(cv.w);
         HIPCHK(e, hipMemsetAsync(cv.w, 0, bytes, s));
     }
-    int rc = pk_weight_t(e, dit->pk_T, P(e, wname), cout, cin_total, taps, ci_off, ci_cnt, cv.w, cin_p, ld, 0, s);
-    if (rc) return rc;
+    pk_push(dit->pk_T, pack_job_weight_t(P(e, wname), cout, cin_total, taps, ci_off, ci_cnt, cv.w, ld, 0));
     cv.bias = nullptr;
     return ST_OK;
 }
@@ -221,8 +220,8 @@ int train_prepare(st_engine* e, hipStream_t s) {
             int r2 = 0;
             for (const char* nm : {"q", "k", "v"}) {
                 const float* w = P(e, b + "attn.conv_" + nm + ".weight");
-                if ((rc = pk_weight(e, dit->pk_T, w, C, C, 1, 0, C, q2.w, r2 * C, 2 * C, 0, r2 == 2 ? C : 2 * C, 0, s))) return rc;
-                if (r2 == 2 && (rc = pk_weight(e, dit->pk_T, w, C, C, 1, 0, C, q2.w, r2 * C, 2 * C, C, C, 0, s))) return rc;
+                pk_push(dit->pk_T, pack_job_weight(w, C, C, 1, 0, C, q2.w, r2 * C, 2 * C, 0, r2 == 2 ? C : 2 * C, 0));
+                if (r2 == 2) pk_push(dit->pk_T, pack_job_weight(w, C, C, 1, 0, C, q2.w, r2 * C, 2 * C, C, C, 0));
                 ++r2;
             }
         }
@@ -232,7 +231,7 @@ int train_prepare(st_engine* e, hipStream_t s) {
         if (!q.w) { HIPCHK(e, hipMalloc(&q.w, (size_t)C * 3 * C * 2)); ts->owned.push_back(q.w); }
         int r = 0;
         for (const char* nm : {"q", "k", "v"}) {
-            if ((rc = pk_weight_t(e, dit->pk_T, P(e, b + "attn.conv_" + nm + ".weight"), C, C, 1, 0, C, q.w, C, 3 * C, r * C, s))) return rc;
+            pk_push(dit->pk_T, pack_job_weight_t(P(e, b + "attn.conv_" + nm + ".weight"), C, C, 1, 0, C, q.w, 3 * C, r * C));
             ++r;
         }
     }
@@ -1006,14 +1005,14 @@ int bwd_block_linears(st_engine* e, TrainState* ts, int i, hipStream_t s) {
     const std::string pa = dit->blk(i) + "adaLN_modulation.2.", p0 = dit->blk(i) + "adaLN_modulation.0.";
     const float* dout = ts->dada + (size_t)i * N * 6 * C;
     const float* pre = ts->ada_pre + (size_t)i * N * C;
-    HIPCHK(e, launch_linear_bwd_w(pre, dout, N, C, 6 * C, 1, G(ts, pa + "weight"), G(ts, pa + "bias"), 0, s));
+    HIPCHK(e, launch_linear_bwd_w(pre, dout, N, C, 6 * C, 1, G(ts, pa + "weight"), G(ts, pa + "bias"), s));
     HIPCHK(e, launch_linear_bwd_in(pre, dout, P(e, pa + "weight"), N, C, 6 * C, 1, ts->dada_pre, 0, s));
-    HIPCHK(e, launch_linear_bwd_w(ts->cvec, ts->dada_pre, N, dit->G, C, 0, G(ts, p0 + "weight"), G(ts, p0 + "bias"), 0, s));
+    HIPCHK(e, launch_linear_bwd_w(ts->cvec, ts->dada_pre, N, dit->G, C, 0, G(ts, p0 + "weight"), G(ts, p0 + "bias"), s));
     HIPCHK(e, launch_linear_bwd_in(ts->cvec, ts->dada_pre, P(e, p0 + "weight"), N, dit->G, C, 0, ts->dcvec, acc, s));
     if (e->kind != KIND_DECODER) return ST_OK;      // (the text encoder's blocks have no FiLM)
     const std::string pf = "blocks." + std::to_string(i) + ".time_fusion.film.";
     const float* dfo = ts->dfilm + (size_t)i * N * 2 * C;
-    HIPCHK(e, launch_linear_bwd_w(ts->tau, dfo, N, C, 2 * C, 0, G(ts, pf + "weight"), G(ts, pf + "bias"), 0, s));
+    HIPCHK(e, launch_linear_bwd_w(ts->tau, dfo, N, C, 2 * C, 0, G(ts, pf + "weight"), G(ts, pf + "bias"), s));
     HIPCHK(e, launch_linear_bwd_in(ts->tau, dfo, P(e, pf + "weight"), N, C, 2 * C, 0, ts->dtau, acc, s));
     return ST_OK;
 }
@@ -1066,9 +1065,9 @@ int bwd_tail(st_engine* e, TrainState* ts, float* grad_x, float* grad_mu, float*
     int rc;
     // ---- the time MLP's gradients and d c first: d tau and d c are complete since part 1, nothing below feeds them, and at the END of this
     // part these small launches queued behind the prenet's weight-gradient GEMMs on the side stream (120-210 us each in the kernel trace)
-    HIPCHK(e, launch_linear_bwd_w(ts->th_pre, ts->dtau, N, F, C, 1, G(ts, "time_mlp.layer.2.weight"), G(ts, "time_mlp.layer.2.bias"), 0, s));
+    HIPCHK(e, launch_linear_bwd_w(ts->th_pre, ts->dtau, N, F, C, 1, G(ts, "time_mlp.layer.2.weight"), G(ts, "time_mlp.layer.2.bias"), s));
     HIPCHK(e, launch_linear_bwd_in(ts->th_pre, ts->dtau, P(e, "time_mlp.layer.2.weight"), N, F, C, 1, ts->dth, 0, s));
-    HIPCHK(e, launch_linear_bwd_w(ts->emb, ts->dth, N, C, F, 0, G(ts, "time_mlp.layer.0.weight"), G(ts, "time_mlp.layer.0.bias"), 0, s));
+    HIPCHK(e, launch_linear_bwd_w(ts->emb, ts->dth, N, C, F, 0, G(ts, "time_mlp.layer.0.weight"), G(ts, "time_mlp.layer.0.bias"), s));
     if (grad_c) HIPCHK(e, hipMemcpyAsync(grad_c, ts->dcvec, (size_t)N * dit->G * 4, hipMemcpyDeviceToDevice, s));
     // ---- in_proj: h0 = Wx x + Wc cond + b
     void* const t0 = ts->dy[TrainState::DY_T0]; void* const t1 = ts->dy[TrainState::DY_T1]; void* const t2 = ts->dy[TrainState::DY_T2]; void* const t3 = ts->dy[TrainState::DY_T3];

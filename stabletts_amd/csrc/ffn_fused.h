@@ -19,7 +19,7 @@
 //     the SiLU step overwrites area s with u's sub-chunk s; while S2 walks the sub-chunks, the areas it has finished with are
 //     refilled with h for the next chunk (area 3 during the next S1).  Same row pitch / XOR swizzle as the conv kernels, so ONE
 //     set of 12 fragment addresses (tap x k-step) serves both stages; the area is an immediate offset.
-//   weight RING of 5 slabs of 16 KiB.  The weights come as ONE linear stream in consumption order (launch_pack_ffn_stream): a
+//   weight RING of 5 slabs of 16 KiB.  The weights come as ONE linear stream in consumption order (common.h: PACK_FFN_STREAM): a
 //     slab = one phase = K 32 x 256 rows = 16 MFMA A-fragments stored lane-linear, so a fragment read is base + lane*16 + immediate
 //     (conflict-free, one address register) and the DMA source is contiguous.
 //   conv_1 bias (F floats) and a 1-KiB sink for padding pieces.

@@ -44,7 +44,7 @@ struct ConvGemmArgs {
     const float* rope_cos; const float* rope_sin;   // [T][16]
     int Tp; float qscale; int n_heads;
     const void* zeros;                // >= 16 bytes of zeros in global memory (halo source of the LDS-DMA path)
-    const void* w_frag;               // qkv_ws.hip: the q/k/v weight in fragment order (launch_pack_qkv_frag)
+    const void* w_frag;               // qkv_ws.hip: the q/k/v weight in fragment order (PACK_QKV_FRAG)
     void* sink;                       // >= 64 KiB of scratch that rows outside the tensor are stored to (qkv_ws.hip: every wave issues a FIXED number of stores)
     // fused prologue of the NEXT op (row-complete tiles, cout == 256): FiLM -> *mask -> LayerNorm -> modulate.
     // When ln_h16 != nullptr, out32 receives the post-FiLM residual stream and ln_h16 the 16-bit operand.
@@ -63,7 +63,7 @@ struct ConvGemmArgs {
     void* act16; const void* dact16;
     unsigned long long drop_seed; unsigned drop_thresh16; float drop_scale;
     int ksplit;                       // > 1: split-K launch (EPI_F32 only): out32 = partial planes [ksplit][items][T][cout], raw sums
-    // fused FFN (ffn_fused.h): w = the fused weight stream (launch_pack_ffn_stream), bias1 = conv_1's bias [cmid], cmid = the
+    // fused FFN (ffn_fused.h): w = the fused weight stream (PACK_FFN_STREAM), bias1 = conv_1's bias [cmid], cmid = the
     // intermediate width (filter_channels); every other field describes conv_2's EPI_RESGATE epilogue, a0 = the FFN input
     const float* bias1; int cmid;
     unsigned long long* dbg;          // diagnostics (ST_STAGE_TIMING builds of tools/gemm2_bench only), else nullptr
@@ -90,20 +90,18 @@ hipError_t launch_ffn_fused_f16(const ConvGemmArgs& a, hipStream_t s);
 // Weight stream of the fused FFN kernel, in the order the kernel consumes it: for each 256-channel chunk c of the intermediate
 // width, 24 conv_1 slabs (cin chunk, tap, k-step pair) then 24 conv_2 slabs (u sub-chunk, tap, k-step pair); a slab = 16 MFMA
 // A-fragments of 1 KiB stored lane-linear (fragment (ksl, a8): rows a8*32.., k-step 2*kp+ksl).  stage 0: src = conv_1 weight
-// (F, 256, 3); stage 1: src = conv_2 weight (256, F, 3).  (common.h: ffn_stream_index)
-hipError_t launch_pack_ffn_stream(int dtype, const float* src, int stage, int F, void* dst, hipStream_t s);
-hipError_t launch_pack_ffn_wino(const float* src, int stage, int F, void* dst, hipStream_t s);      // ffn_wino.h's stream (f16)
+// (F, 256, 3); stage 1: src = conv_2 weight (256, F, 3).  (common.h: ffn_stream_index, packed by a PACK_FFN_STREAM job; the
+// Winograd kernel reads ffn_wino_index's order, a PACK_FFN_WINO job, f16 only)
 hipError_t launch_ffn_wino_f16(const ConvGemmArgs& a, hipStream_t s);                                   // Winograd F(2,3) fused FFN, f16 operands only
 // Fused q / k / v projection + RoPE of big grids as a weight-stationary persistent kernel (qkv_ws.hip): same arguments and results
 // (bit for bit) as launch_conv_gemm2_*(G2_RC*, 1, EPI_QKV, ...); needs hidden = 256, 4 heads, a.sink.
 hipError_t launch_qkv_ws(int dtype, const ConvGemmArgs& a, hipStream_t s);
 // The attention out-projection + gate + residual + LayerNorm_2 + modulate of big grids as a weight-stationary persistent kernel
 // (oproj_ws.hip): same arguments and results (bit for bit) as launch_conv_gemm2_*(G2_BIG, 1, EPI_RESGATE, ...) with ln_h16 set, no
-// FiLM, the residual updated in place; needs hidden = 256, a.w_frag (plane 0 of a launch_pack_qkv_frag copy), a.sink.
+// FiLM, the residual updated in place; needs hidden = 256, a.w_frag (plane 0 of a PACK_QKV_FRAG copy), a.sink.
 hipError_t launch_oproj_ws(int dtype, const ConvGemmArgs& a, hipStream_t s);
-// plane (0 q, 1 k, 2 v) of the fragment-ordered weight copy that kernel reads: src = fp32 conv weight (256, 256, 1) of the plane,
-// dst = the whole 3 x 256 x 256 16-bit buffer (common.h: qkv_frag_index).  PackJob kind 4 (row_off = 256 * plane) is the same map.
-hipError_t launch_pack_qkv_frag(int dtype, const float* src, int plane, void* dst, hipStream_t s);
+// (the fragment-ordered weight copies those two kernels read: common.h, qkv_frag_index, packed by PACK_QKV_FRAG jobs -- plane 0 q, 1 k,
+// 2 v of one 3 x 256 x 256 16-bit buffer, each from the fp32 conv weight (256, 256, 1) of the plane)
 constexpr int kGemmFramesPerTile = 128;
 constexpr int kGemmChannelsPerTile = 128;
 
@@ -183,20 +181,18 @@ hipError_t launch_cfg_combine(int dtype, const float* v, int B, int64_t per_item
 hipError_t launch_lincomb(int dtype, const float* x, const float* const* k, const float* coef, int nk,
                           int64_t n, float* y32, void* y16, void* y16lo, hipStream_t s);
 
-// weight packing: src fp32 (cout, cin_total, K) -> dst16 [cout_p][K][cin_p], columns [col_off, col_off + slice_w):
-// source channels [ci_off, ci_off + ci_cnt) then zeros.  dst row offset `row_off` (QKV concat).  lo != 0 packs the
-// rounding residual W - float(to16(W)) instead of W (split-precision weights).
+// Weight packing (common.h: PackJob -- every layout's element count and index map).  launch_pack_weight: one PACK_WEIGHT job in a
+// launch of its own: src fp32 (cout, cin_total, K) -> dst16 [cout_p][K][cin_p], columns [col_off, col_off + slice_w): source
+// channels [ci_off, ci_off + ci_cnt) then zeros.  dst row offset `row_off` (QKV concat).  lo != 0 packs the rounding residual
+// W - float(to16(W)) instead of W (split-precision weights).
 hipError_t launch_pack_weight(int dtype, const float* src, int cout, int cin_total, int K, int ci_off,
                               int ci_cnt, void* dst, int row_off, int cin_p, int col_off, int slice_w, int lo,
                               hipStream_t s);
 hipError_t launch_cvt16_to_f32(int dtype, const void* src, float* dst, int64_t n, hipStream_t s);
-// One launch for a whole list of packing jobs (the ~100 launch_pack_weight / launch_pack_weight_t calls and ~60 bias copies of a
-// re-pack after an optimizer step are each a few microseconds of launch latency: 0.75 ms per training step as separate launches).
-// kind 0: launch_pack_weight's mapping, kind 1: launch_pack_weight_t's (train_launch.h), kind 2: fp32 copy of `cout` elements,
-// kind 3: launch_pack_ffn_stream's (lo = stage, cout = F), kind 4: launch_pack_qkv_frag's (row_off = 256 * plane),
-// kind 5: launch_pack_ffn_wino's (lo = stage, cout = F).
-// blk0 = first 256-thread block of the job in the merged grid (jobs sorted by blk0).
-struct PackJob { const float* src; void* dst; int kind, cout, cin_total, K, ci_off, ci_cnt, row_off, cin_p, col_off, slice_w, lo; unsigned blk0; };
+// One launch for a whole list of packing jobs in device memory (the ~100 weight jobs and ~60 bias copies of a DiT kind are each a few
+// microseconds of launch latency: 0.75 ms per training step as separate launches).  jobs sorted by blk0, nblocks = the sum of
+// pack_job_blocks; no two jobs of a list may write the same destination element (the blocks run concurrently).
+struct PackJob;
 hipError_t launch_pack_jobs(int dtype, const PackJob* jobs_dev, int njobs, unsigned nblocks, hipStream_t s);
 
 // ---------------------------------------------------------------- compute_loss's own arithmetic (flow_matching.py:86-100)

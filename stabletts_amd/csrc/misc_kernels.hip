@@ -455,31 +455,49 @@ hipError_t launch_lincomb(int dtype, const float* x, const float* const* k, cons
 }
 
 // ------------------------------------------------------------------------------------------
-// weight packing: (cout, cin_total, K) fp32 -> [row_off + co][K][cin_p] 16-bit, columns [col_off, col_off + slice_w)
+// weight packing (common.h: PackJob): element idx of job j, in whichever layout the job names
 template <class P>
-__global__ void pack_weight_kernel(const float* src, int cout, int cin_total, int K, int ci_off, int ci_cnt,
-                                   typename P::elem* dst, int row_off, int cin_p, int col_off, int slice_w, int lo) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t total = (size_t)cout * K * slice_w;
-    if (idx >= total) return;
-    const int ci = (int)(idx % slice_w);
-    const int j = (int)((idx / slice_w) % K);
-    const int co = (int)(idx / ((size_t)slice_w * K));
-    float v = 0.f;
-    if (ci < ci_cnt) v = src[((size_t)co * cin_total + ci_off + ci) * K + j];
-    if (lo) v -= (float)to16<P>(v);
-    dst[((size_t)(row_off + co) * K + j) * cin_p + col_off + ci] = to16<P>(v);
+__device__ __forceinline__ void pack_job_apply(const PackJob& j, size_t idx) {
+    if (idx >= pack_job_elems(j)) return;
+    const PackElem m = pack_job_map(j, idx);
+    typename P::elem* dst = (typename P::elem*)j.dst;
+    if (j.kind == PACK_WEIGHT) {
+        float v = 0.f;
+        if (m.src != kPackZero) v = j.src[m.src];
+        if (j.lo) v -= (float)to16<P>(v);
+        dst[m.dst] = to16<P>(v);
+    } else if (j.kind == PACK_FFN_WINO) {
+        dst[m.dst] = to16<P>(ffn_wino_plane(j.src + m.src, m.variant));
+    } else if (j.kind == PACK_COPY) {
+        ((float*)j.dst)[m.dst] = j.src[m.src];
+    } else {                        // PACK_WEIGHT_T, PACK_FFN_STREAM, PACK_QKV_FRAG: a permutation
+        dst[m.dst] = to16<P>(j.src[m.src]);
+    }
+}
+// a whole list in one launch: jobs in device memory, the job of a block found by a block-uniform binary search
+template <class P>
+__global__ __launch_bounds__(256) void pack_jobs_kernel(const PackJob* jobs, int njobs) {
+    const PackJob j = jobs[pack_job_find(jobs, njobs, blockIdx.x)];
+    pack_job_apply<P>(j, (size_t)(blockIdx.x - j.blk0) * 256 + threadIdx.x);
+}
+template <class P>
+__global__ __launch_bounds__(256) void pack_job_kernel(const PackJob j) {
+    pack_job_apply<P>(j, (size_t)blockIdx.x * 256 + threadIdx.x);
 }
 
+hipError_t launch_pack_jobs(int dtype, const PackJob* jobs_dev, int njobs, unsigned nblocks, hipStream_t s) {
+    if (njobs < 1 || nblocks < 1) return hipSuccess;
+    if (dtype == DT_BF16) hipLaunchKernelGGL((pack_jobs_kernel<OpBF16>), dim3(nblocks), dim3(256), 0, s, jobs_dev, njobs);
+    else                  hipLaunchKernelGGL((pack_jobs_kernel<OpF16>), dim3(nblocks), dim3(256), 0, s, jobs_dev, njobs);
+    return hipGetLastError();
+}
+// one weight job in a launch of its own (the vocoders pack afresh at every finalize and keep no list)
 hipError_t launch_pack_weight(int dtype, const float* src, int cout, int cin_total, int K, int ci_off,
                               int ci_cnt, void* dst, int row_off, int cin_p, int col_off, int slice_w, int lo,
                               hipStream_t s) {
-    const size_t total = (size_t)cout * K * slice_w;
-    const int grid = (int)((total + 255) / 256);
-    if (dtype == DT_BF16)
-        hipLaunchKernelGGL((pack_weight_kernel<OpBF16>), dim3(grid), dim3(256), 0, s, src, cout, cin_total, K, ci_off, ci_cnt, (__bf16*)dst, row_off, cin_p, col_off, slice_w, lo);
-    else
-        hipLaunchKernelGGL((pack_weight_kernel<OpF16>), dim3(grid), dim3(256), 0, s, src, cout, cin_total, K, ci_off, ci_cnt, (_Float16*)dst, row_off, cin_p, col_off, slice_w, lo);
+    const PackJob j = pack_job_weight(src, cout, cin_total, K, ci_off, ci_cnt, dst, row_off, cin_p, col_off, slice_w, lo);
+    if (dtype == DT_BF16) hipLaunchKernelGGL((pack_job_kernel<OpBF16>), dim3(pack_job_blocks(j)), dim3(256), 0, s, j);
+    else                  hipLaunchKernelGGL((pack_job_kernel<OpF16>), dim3(pack_job_blocks(j)), dim3(256), 0, s, j);
     return hipGetLastError();
 }
 
@@ -566,51 +584,6 @@ hipError_t launch_cfm_loss_bwd(const float* pred, const float* u, const float* s
     const int64_t n = (int64_t)B * M * T;
     int grid = (int)((n / 4 + 255) / 256); if (grid > 2048) grid = 2048; if (grid < 1) grid = 1;
     hipLaunchKernelGGL(cfm_loss_bwd_kernel, dim3(grid), dim3(256), 0, s, pred, u, scratch, grad_loss, n, gpred);
-    return hipGetLastError();
-}
-
-// fused-FFN weight stream (common.h: ffn_stream_index)
-template <class P>
-__global__ void pack_ffn_stream_kernel(const float* src, int stage, int F, typename P::elem* dst) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)F * 256 * 3) return;
-    size_t so, dof;
-    ffn_stream_index(idx, stage, F, &so, &dof);
-    dst[dof] = to16<P>(src[so]);
-}
-
-hipError_t launch_pack_ffn_stream(int dtype, const float* src, int stage, int F, void* dst, hipStream_t s) {
-    const size_t total = (size_t)F * 256 * 3;
-    const int grid = (int)((total + 255) / 256);
-    if (dtype == DT_BF16) hipLaunchKernelGGL((pack_ffn_stream_kernel<OpBF16>), dim3(grid), dim3(256), 0, s, src, stage, F, (__bf16*)dst);
-    else                  hipLaunchKernelGGL((pack_ffn_stream_kernel<OpF16>), dim3(grid), dim3(256), 0, s, src, stage, F, (_Float16*)dst);
-    return hipGetLastError();
-}
-
-// weight stream of the Winograd fused FFN (common.h: ffn_wino_index; f16 only)
-__global__ void pack_ffn_wino_kernel(const float* src, int stage, int F, _Float16* dst) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)F * 256 * 3) return;
-    size_t so, dof; int pl;
-    ffn_wino_index(idx, stage, F, &so, &dof, &pl);
-    dst[dof] = (_Float16)ffn_wino_plane(src + so, pl);
-}
-hipError_t launch_pack_ffn_wino(const float* src, int stage, int F, void* dst, hipStream_t s) {
-    const size_t total = (size_t)F * 256 * 3;
-    hipLaunchKernelGGL(pack_ffn_wino_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, stage, F, (_Float16*)dst);
-    return hipGetLastError();
-}
-
-// fragment-ordered q/k/v weight (common.h: qkv_frag_index)
-template <class P>
-__global__ void pack_qkv_frag_kernel(const float* src, int plane, typename P::elem* dst) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= 256 * 256) return;
-    dst[qkv_frag_index(plane, idx >> 8, idx & 255)] = to16<P>(src[idx]);
-}
-hipError_t launch_pack_qkv_frag(int dtype, const float* src, int plane, void* dst, hipStream_t s) {
-    if (dtype == DT_BF16) hipLaunchKernelGGL((pack_qkv_frag_kernel<OpBF16>), dim3(256), dim3(256), 0, s, src, plane, (__bf16*)dst);
-    else                  hipLaunchKernelGGL((pack_qkv_frag_kernel<OpF16>), dim3(256), dim3(256), 0, s, src, plane, (_Float16*)dst);
     return hipGetLastError();
 }
 

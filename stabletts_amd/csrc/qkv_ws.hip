@@ -9,7 +9,7 @@
 // Here the WEIGHTS live in registers and the activations stream:
 //   * a block = 8 waves owns ONE plane (q, k or v: 256 output channels); wave w owns channels 32 w .. 32 w + 32 and keeps their
 //     16 fragments (K = 256 = 16 k-steps x 4 registers = 64 VGPRs) for the whole launch, loaded as 16 coalesced 1-KiB pieces from
-//     a fragment-ordered copy of the weight (launch_pack_qkv_frag).  No weight byte crosses LDS.
+//     a fragment-ordered copy of the weight (common.h: PACK_QKV_FRAG).  No weight byte crosses LDS.
 //   * the block walks a list of 64-frame activation tiles (one frame-tile position tf, items lane, lane + L, lane + 2L ...): a
 //     tile = 64 frames x 256 channels x 2 B = 32 KiB arrives by LDS-DMA into one of two slots (4 chunk images of 64 rows x 128 B
 //     with the source-side XOR swizzle of the conv kernels: conflict-free ds_read_b128 B-fragments), one tile ahead of the
@@ -115,7 +115,7 @@ void qkv_ws_kernel(const ConvGemmArgs g, int L) {
     issue_tile(ncur, 0);
 
     // ---- the wave's weights: 16 fragments (lane (channel l31, hi) holds K slots ks*16 + hi*8 .. +8) from the fragment-ordered copy
-    // of the packed q/k/v weight (launch_pack_qkv_frag: [plane][wave][k-step][lane][8]) -- 16 coalesced 1-KiB loads per wave; read
+    // of the packed q/k/v weight (PACK_QKV_FRAG: [plane][wave][k-step][lane][8]) -- 16 coalesced 1-KiB loads per wave; read
     // straight from the row-major weight the same fragments are 32 scattered 32-byte pieces per instruction (prologue 3.5 -> 1 us)
     vec8 wf[16];
     {

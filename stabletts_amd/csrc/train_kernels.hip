@@ -756,131 +756,12 @@ hipError_t launch_bias_reduce(const float* part_b, int rowblocks, int cout, floa
     return hipGetLastError();
 }
 
-// dgrad weights: Wd[ci][j][col_off + co] = W[co][ci_off + ci][taps - 1 - j]; rows ci >= ci_cnt and columns co >= cout stay zero
-template <class P>
-__global__ void pack_weight_t_kernel(const float* src, int cout, int cin_total, int taps, int ci_off, int ci_cnt,
-                                     typename P::elem* dst, int ld, int col_off) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t total = (size_t)ci_cnt * taps * cout;
-    if (idx >= total) return;
-    const int co = (int)(idx % cout);
-    const int j = (int)((idx / cout) % taps);
-    const int ci = (int)(idx / ((size_t)cout * taps));
-    const float v = src[((size_t)co * cin_total + ci_off + ci) * taps + (taps - 1 - j)];
-    dst[((size_t)ci * taps + j) * ld + col_off + co] = to16<P>(v);
-}
-
-hipError_t launch_pack_weight_t(int dtype, const float* src, int cout, int cin_total, int taps, int ci_off, int ci_cnt,
-                                void* dst, int cin_p, int ld, int col_off, hipStream_t s) {
-    (void)cin_p;
-    const size_t total = (size_t)ci_cnt * taps * cout;
-    const int grid = (int)((total + 255) / 256);
-    if (dtype == DT_BF16) hipLaunchKernelGGL((pack_weight_t_kernel<OpBF16>), dim3(grid), dim3(256), 0, s, src, cout, cin_total, taps, ci_off, ci_cnt, (__bf16*)dst, ld, col_off);
-    else                  hipLaunchKernelGGL((pack_weight_t_kernel<OpF16>), dim3(grid), dim3(256), 0, s, src, cout, cin_total, taps, ci_off, ci_cnt, (_Float16*)dst, ld, col_off);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------ merged re-pack (launch.h: PackJob)
-template <class P>
-__global__ __launch_bounds__(256) void pack_jobs_kernel(const PackJob* jobs, int njobs) {
-    int lo = 0, hi = njobs - 1;                 // block-uniform binary search: the job whose block range holds blockIdx.x
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (jobs[mid].blk0 <= blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const PackJob j = jobs[lo];
-    const size_t idx = (size_t)(blockIdx.x - j.blk0) * 256 + threadIdx.x;
-    if (j.kind == 0) {              // pack_weight_kernel (misc_kernels.hip)
-        const size_t total = (size_t)j.cout * j.K * j.slice_w;
-        if (idx >= total) return;
-        const int ci = (int)(idx % j.slice_w);
-        const int t = (int)((idx / j.slice_w) % j.K);
-        const int co = (int)(idx / ((size_t)j.slice_w * j.K));
-        float v = 0.f;
-        if (ci < j.ci_cnt) v = j.src[((size_t)co * j.cin_total + j.ci_off + ci) * j.K + t];
-        if (j.lo) v -= (float)to16<P>(v);
-        ((typename P::elem*)j.dst)[((size_t)(j.row_off + co) * j.K + t) * j.cin_p + j.col_off + ci] = to16<P>(v);
-    } else if (j.kind == 1) {       // pack_weight_t_kernel (above); cin_p carries its `ld`
-        const size_t total = (size_t)j.ci_cnt * j.K * j.cout;
-        if (idx >= total) return;
-        const int co = (int)(idx % j.cout);
-        const int t = (int)((idx / j.cout) % j.K);
-        const int ci = (int)(idx / ((size_t)j.cout * j.K));
-        const float v = j.src[((size_t)co * j.cin_total + j.ci_off + ci) * j.K + (j.K - 1 - t)];
-        ((typename P::elem*)j.dst)[((size_t)ci * j.K + t) * j.cin_p + j.col_off + co] = to16<P>(v);
-    } else if (j.kind == 3) {       // pack_ffn_stream_kernel (misc_kernels.hip): lo = stage, cout = F
-        if (idx >= (size_t)j.cout * 256 * 3) return;
-        size_t so, dof;
-        ffn_stream_index(idx, j.lo, j.cout, &so, &dof);
-        ((typename P::elem*)j.dst)[dof] = to16<P>(j.src[so]);
-    } else if (j.kind == 5) {       // pack_ffn_wino_kernel (misc_kernels.hip): lo = stage, cout = F; f16 engines only
-        if (idx >= (size_t)j.cout * 256 * 3) return;
-        size_t so, dof; int pl;
-        ffn_wino_index(idx, j.lo, j.cout, &so, &dof, &pl);
-        ((typename P::elem*)j.dst)[dof] = to16<P>(ffn_wino_plane(j.src + so, pl));
-    } else if (j.kind == 4) {       // pack_qkv_frag_kernel (misc_kernels.hip): row_off = 256 * plane
-        if (idx >= 256 * 256) return;
-        ((typename P::elem*)j.dst)[qkv_frag_index(j.row_off >> 8, (int)(idx >> 8), (int)(idx & 255))] = to16<P>(j.src[idx]);
-    } else {                        // fp32 copy (biases)
-        if (idx < (size_t)j.cout) ((float*)j.dst)[idx] = j.src[idx];
-    }
-}
-
-hipError_t launch_pack_jobs(int dtype, const PackJob* jobs_dev, int njobs, unsigned nblocks, hipStream_t s) {
-    if (njobs < 1 || nblocks < 1) return hipSuccess;
-    if (dtype == DT_BF16) hipLaunchKernelGGL((pack_jobs_kernel<OpBF16>), dim3(nblocks), dim3(256), 0, s, jobs_dev, njobs);
-    else                  hipLaunchKernelGGL((pack_jobs_kernel<OpF16>), dim3(nblocks), dim3(256), 0, s, jobs_dev, njobs);
-    return hipGetLastError();
-}
-
 // ------------------------------------------------------------------------------------------ small fp32 linears: backward
 // (adaLN / FiLM / time-MLP linears on per-item vectors: n = batch items, a few hundred inputs and outputs.  Register-blocked so
 //  that every loaded value feeds 8 multiply-adds -- one output per thread cost 2 loads and, with SiLU on the input, one expf per
 //  multiply-add: 35 us per launch, 27 launches per step.)
-// dW[o][k] += sum_n dout[n][o] * act(in[n][k]) ; db[o] += sum_n dout[n][o].  block = 64 inputs x 8 consecutive outputs, its 4
+// dW[o][k] = sum_n dout[n][o] * act(in[n][k]) ; db[o] = sum_n dout[n][o].  block = 64 inputs x 8 consecutive outputs, its 4
 // waves take every fourth item (the loop is a chain of L2-latency loads: four short chains + a fixed-order LDS combine)
-__global__ __launch_bounds__(256) void linear_bwd_w_kernel(const float* in, const float* dout, int n, int k, int o, int silu_in,
-                                                           float* dW, float* db, int accumulate) {
-    __shared__ float red[4][16][64];
-    const int tx = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int ki = blockIdx.x * 64 + tx, o0 = blockIdx.y * 8;
-    float acc[8], accb[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { acc[j] = 0.f; accb[j] = 0.f; }
-    const bool full = o0 + 8 <= o && (o & 3) == 0;
-    if (ki < k) {
-#pragma unroll 4
-        for (int ni = g; ni < n; ni += 4) {
-            float x = in[(size_t)ni * k + ki];
-            if (silu_in) x = silu_f(x);
-            float d[8];
-            if (full) {
-                const float4 d0 = *(const float4*)(dout + (size_t)ni * o + o0), d1 = *(const float4*)(dout + (size_t)ni * o + o0 + 4);
-                d[0] = d0.x; d[1] = d0.y; d[2] = d0.z; d[3] = d0.w; d[4] = d1.x; d[5] = d1.y; d[6] = d1.z; d[7] = d1.w;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) d[j] = o0 + j < o ? dout[(size_t)ni * o + o0 + j] : 0.f;
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { acc[j] += d[j] * x; accb[j] += d[j]; }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { red[g][j][tx] = acc[j]; red[g][8 + j][tx] = accb[j]; }
-    __syncthreads();
-    if (ki >= k) return;
-    for (int j = g; j < 8; j += 4) {          // wave g finishes outputs o0 + g, o0 + g + 4
-        if (o0 + j >= o) continue;
-        const float t = ((red[0][j][tx] + red[1][j][tx]) + red[2][j][tx]) + red[3][j][tx];
-        float* w = dW + (size_t)(o0 + j) * k + ki;
-        *w = accumulate ? *w + t : t;
-        if (ki == 0 && db) {
-            const float tb = ((red[0][8 + j][0] + red[1][8 + j][0]) + red[2][8 + j][0]) + red[3][8 + j][0];
-            db[o0 + j] = accumulate ? db[o0 + j] + tb : tb;
-        }
-    }
-}
-
 // Several layers of one shape in ONE launch (grid.z = layer): dW_j / db_j written (not accumulated).
 __global__ __launch_bounds__(256) void linear_bwd_w_multi_kernel(LinBwdJobs J, int n, int k, int o, int silu_in) {
     __shared__ float red[4][16][64];
@@ -925,7 +806,8 @@ hipError_t launch_linear_bwd_w_multi(const LinBwdJobs& J, int n, int k, int o, i
     return hipGetLastError();
 }
 // din[n][k] (+)= act'(in[n][k]) * sum_j sum_o dout_j[n][o] * W_j[o][k] over the J.n layers (they share the input `in`): one launch,
-// layers summed in order inside each thread group (deterministic)
+// layers summed in order inside each thread group.  block = one item x 64 inputs x 16 output groups; fixed combination order:
+// deterministic.  (8 items per block to share the W loads was measured slower: the loop is latency-, not traffic-bound.)
 __global__ __launch_bounds__(1024) void linear_bwd_in_multi_kernel(LinBwdJobs J, const float* in, int n, int k, int o, int silu_in, float* din, int accumulate) {
     __shared__ float red[16][64];
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
@@ -955,40 +837,17 @@ hipError_t launch_linear_bwd_in_multi(const LinBwdJobs& J, const float* in, int 
     return hipGetLastError();
 }
 
-hipError_t launch_linear_bwd_w(const float* in, const float* dout, int n, int k, int o, int silu_in, float* dW, float* db,
-                               int accumulate, hipStream_t s) {
-    hipLaunchKernelGGL(linear_bwd_w_kernel, dim3((unsigned)((k + 63) / 64), (unsigned)((o + 7) / 8)), dim3(256), 0, s, in, dout, n, k, o, silu_in, dW, db, accumulate);
-    return hipGetLastError();
+// One layer = the multi form with one job.
+hipError_t launch_linear_bwd_w(const float* in, const float* dout, int n, int k, int o, int silu_in, float* dW, float* db, hipStream_t s) {
+    LinBwdJobs J; memset(&J, 0, sizeof(J));
+    J.in[0] = in; J.dout[0] = dout; J.dW[0] = dW; J.db[0] = db; J.n = 1;
+    return launch_linear_bwd_w_multi(J, n, k, o, silu_in, s);
 }
-
-// din[n][k] (+)= act'(in[n][k]) * sum_o dout[n][o] * W[o][k].  block = one item x 64 inputs x 16 output groups; fixed combination
-// order: deterministic.  (8 items per block to share the W loads was measured slower: the loop is latency-, not traffic-bound.)
-__global__ __launch_bounds__(1024) void linear_bwd_in_kernel(const float* in, const float* dout, const float* W, int n, int k, int o,
-                                                             int silu_in, float* din, int accumulate) {
-    __shared__ float red[16][64];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int ni = blockIdx.y, ki = blockIdx.x * 64 + tx;
-    float acc = 0.f;
-    if (ki < k) {
-#pragma unroll 8
-        for (int oi = ty; oi < o; oi += 16) acc += dout[(size_t)ni * o + oi] * W[(size_t)oi * k + ki];
-    }
-    red[ty][tx] = acc;
-    __syncthreads();
-    if (ty == 0 && ki < k) {
-        float t = 0.f;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) t += red[g][tx];
-        const size_t idx = (size_t)ni * k + ki;
-        if (silu_in) t *= silu_grad(in[idx]);
-        din[idx] = accumulate ? din[idx] + t : t;
-    }
-}
-
 hipError_t launch_linear_bwd_in(const float* in, const float* dout, const float* W, int n, int k, int o, int silu_in,
                                 float* din, int accumulate, hipStream_t s) {
-    hipLaunchKernelGGL(linear_bwd_in_kernel, dim3((k + 63) / 64, n), dim3(1024), 0, s, in, dout, W, n, k, o, silu_in, din, accumulate);
-    return hipGetLastError();
+    LinBwdJobs J; memset(&J, 0, sizeof(J));
+    J.dout[0] = dout; J.W[0] = W; J.n = 1;
+    return launch_linear_bwd_in_multi(J, in, n, k, o, silu_in, din, accumulate, s);
 }
 
 }  // namespace st

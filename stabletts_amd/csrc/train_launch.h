@@ -123,19 +123,15 @@ hipError_t launch_wgrad_reduce(const float* partial, int S, int cin, int cout, i
 hipError_t launch_bias_reduce(const float* part_b, int rowblocks, int cout, float* db, int co_start, int co_cnt,
                               const float* unscale, hipStream_t s);
 
-// dgrad weights: dst16 [Cin_p][taps][ld] columns [col_off, col_off + cout): Wd[ci][j][co] = W[co][ci_off + ci][taps - 1 - j]
-hipError_t launch_pack_weight_t(int dtype, const float* src, int cout, int cin_total, int taps, int ci_off, int ci_cnt,
-                                void* dst, int cin_p, int ld, int col_off, hipStream_t s);
-
 // ---------------------------------------------------------------- small fp32 linears (adaLN, FiLM, time MLP): backward
-// out = W act(in) + b:  dW[o][k] (+)= sum_n dout[n][o] act(in[n][k]);  db[o] (+)= sum_n dout[n][o]
+// out = W act(in) + b:  dW[o][k] = sum_n dout[n][o] act(in[n][k]);  db[o] = sum_n dout[n][o]
 // several layers of one shape per launch (the per-item linears of the blocks of one backward part)
 struct LinBwdJobs { const float* in[8]; const float* dout[8]; const float* W[8]; float* dW[8]; float* db[8]; int n; };
 hipError_t launch_linear_bwd_w_multi(const LinBwdJobs& J, int n, int k, int o, int silu_in, hipStream_t s);
+// din[n][k] (+)= (sum_j sum_o dout_j[n][o] W_j[o][k]) * act'(in[n][k]): the layers share the input `in`
 hipError_t launch_linear_bwd_in_multi(const LinBwdJobs& J, const float* in, int n, int k, int o, int silu_in, float* din, int accumulate, hipStream_t s);
-hipError_t launch_linear_bwd_w(const float* in, const float* dout, int n, int k, int o, int silu_in, float* dW, float* db,
-                               int accumulate, hipStream_t s);
-// din[n][k] (+)= (sum_o dout[n][o] W[o][k]) * act'(in[n][k])
+// one layer: the same launches with a single job
+hipError_t launch_linear_bwd_w(const float* in, const float* dout, int n, int k, int o, int silu_in, float* dW, float* db, hipStream_t s);
 hipError_t launch_linear_bwd_in(const float* in, const float* dout, const float* W, int n, int k, int o, int silu_in,
                                 float* din, int accumulate, hipStream_t s);
 

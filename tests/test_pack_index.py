@@ -1,5 +1,6 @@
 """CPU check of the weight-layout index maps the kernels and the packers share (csrc/common.h: ffn_stream_index, ffn_wino_index,
-qkv_frag_index): compiled for the HOST with hipcc, no GPU."""
+qkv_frag_index) and of the packing jobs built on them (pack_job_elems, pack_job_map, pack_job_find: the weight and the transposed
+layouts, the block ranges of a job list): compiled for the HOST with hipcc, no GPU."""
 import os
 import shutil
 import subprocess
